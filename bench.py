@@ -10,8 +10,14 @@ B*L*n_gpus / (T * seconds_per_step), i.e. finished audio samples per second of
 the full T=200 loop, with x, weights and schedule resident in HBM.
 
     python bench.py --gpus 1 --steps 200 --warmup 5
+    python bench.py --gpus 1 --steps 200 --warmup 5 --full     # + rooflines, other precisions / configs, CPU baselines
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
+
+A plain run sets up, warms up, times the steps and prints the line; everything else it can measure (the full-loop
+timing, per-kernel rooflines, the exact-f32 leg, the other BASELINE configs, CPU baselines, the 1-rank RCCL overhead
+of --mode train) runs only under --full.  --dump-outputs DIR writes what the timed path computed in its last step
+(sampling: the state x, B x 1 x L; training: the loss and the parameters) as DIR/<name>.npy.
 
 Multi-GPU: sampling shards by independent clips -- every rank runs its own batch
 with its own Philox stream and there is NO data-path collective ("weak" scaling;
@@ -95,6 +101,12 @@ def main():
     ap.add_argument("--mode", default="sample", choices=["sample", "train"],
                     help="sample: the headline reverse-diffusion step; train: one DP training step "
                          "(forward_train + backward + RCCL gradient all-reduce + Adam)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the timed steps (full loop, rooflines, exact-f32 leg, extra configs, "
+                         "CPU baselines, DP overhead); a plain run times the headline steps only. The --no-* switches "
+                         "below trim a --full run")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path computed in its last step to DIR/<name>.npy (float32, <= 64 MB)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-train-baseline", action="store_true",
                     help="also time one training step of the CPU oracle at B=1 beside the training leg / --mode train (~100 s)")
@@ -103,6 +115,10 @@ def main():
     ap.add_argument("--no-full-loop", action="store_true",
                     help="skip the complete T-step dws_sampler_run beside the timed steps (profiler passes: counters serialise kernels)")
     args = ap.parse_args()
+    if not args.full:
+        if args.cpu_train_baseline:
+            ap.error("--cpu-train-baseline needs --full")
+        args.no_cpu_baseline = args.no_roofline = args.no_extra = args.no_full_loop = True
 
     cfg = dict(CONFIGS[args.config])
     if args.batch:
@@ -131,8 +147,8 @@ def main():
     if args.mode == "train":
         if args.precision not in ("f32", "bf16x6") or cfg["model"]["_name_"] == "wavenet":
             args.precision = "f32"       # WaveNet training and the narrower splits have no split backward
-        return train_bench(args, cfg, world, rank, dev, ddist, red_dev)
-    result = sample_bench(args, cfg, world, rank, dev, ddist, red_dev)
+        return train_bench(args, cfg, world, rank, dev, ddist, red_dev, dump_dir=args.dump_outputs)
+    result = sample_bench(args, cfg, world, rank, dev, ddist, red_dev, dump_dir=args.dump_outputs)
     default_run = (args.config == "wnet_h256_d36_T200" and not args.batch and args.precision == "bf16x6")
     if rank == 0 and world == 1 and not args.no_extra and default_run:
         # the other BASELINE configs, short legs in the same process (NOT `value`): C3, C4 sampling, C5's per-GPU training step.
@@ -143,7 +159,7 @@ def main():
         # against the better of the single process and the quota-sized whole-host leg (context only: a GPU/CPU ratio says
         # nothing about kernel quality, the roofline fraction does)
         result["gpu_over_cpu"] = result["value"] / result["cpu_baseline"]["best"]["value"]
-    if rank == 0 and default_run:
+    if rank == 0 and default_run and args.full:
         result["summary"] = summary(result)          # LAST key: every config's number survives a tail of the line
     if rank == 0:
         print(json.dumps(result))

@@ -10,8 +10,9 @@ from .configs import (DTYPE_NAMES, PEAK_BF16_MFMA_TFLOPS, PEAK_F32_MFMA_TFLOPS, 
 from .work import (layer_algorithmic_work, profiled_step_ms, sashimi_tail_work, wavenet_traffic, wino_executed_work)
 
 
-def sample_bench(args, cfg, world, rank, dev, ddist, red_dev, extras=True, full=True):
-    """One sampling measurement (the headline, or an extra leg): returns the result line as a dict (rank 0 prints it)."""
+def sample_bench(args, cfg, world, rank, dev, ddist, red_dev, extras=True, full=True, dump_dir=None):
+    """One sampling measurement (the headline, or an extra leg): returns the result line as a dict (rank 0 prints it).
+    dump_dir: write the sampler state x the timed steps left (what a caller of dws_sampler_steps receives) there."""
     import ctypes
     import numpy as np
     from diffwave_sashimi_amd import _lib
@@ -35,15 +36,16 @@ def sample_bench(args, cfg, world, rank, dev, ddist, red_dev, extras=True, full=
         net._set_condition(mel)
         # the conditioner runs once per batch of utterances, not per reverse step: timed on its own (outside `value`,
         # whose unit is the per-step rate) so that the end-to-end rate of a whole T-step run can be stated beside it
+        # (`--full` only: a plain run times the steps and nothing else)
         cond_all = []
-        for _ in range(6):
+        for _ in range(6 if getattr(args, "full", True) else 0):
             m2 = mel + 0.0                  # a new tensor each time: the module caches on the mel it was given
             torch.cuda.synchronize()
             tc = time.perf_counter()
             net._set_condition(m2)
             torch.cuda.synchronize()
             cond_all.append((time.perf_counter() - tc) * 1e3)
-        cond_ms = sorted(cond_all[1:])[len(cond_all[1:]) // 2]      # median of five after one more untimed call
+        cond_ms = sorted(cond_all[1:])[len(cond_all[1:]) // 2] if cond_all else None   # median of five after one more untimed call
     x = torch.randn(B, 1, L, device=dev, generator=torch.Generator(device=dev).manual_seed(1234 + rank))
     stream = _lib.current_stream()
     seed = ddist.rank_seed(1234, rank)
@@ -64,6 +66,9 @@ def sample_bench(args, cfg, world, rank, dev, ddist, red_dev, extras=True, full=
     run(args.steps)
     barrier()
     mine = time.perf_counter() - t0
+    if dump_dir:       # before anything below touches x again
+        from .dump import dump_outputs
+        dump_outputs(dump_dir, {"x": x}, rank, world)
     elapsed = ddist.max_over_ranks(mine, red_dev)
     per_rank_ms = [t / args.steps * 1e3 for t in ddist.gather_over_ranks(mine, red_dev)]
     ms_per_step = elapsed / args.steps * 1e3
@@ -102,7 +107,7 @@ def sample_bench(args, cfg, world, rank, dev, ddist, red_dev, extras=True, full=
             "ms": loop_ms, "T": T, "ms_per_step": loop_ms / T, "ratio_to_timed_ms_per_step": loop_ms / T / ms_per_step,
             "samples_per_s_this_rank": B * L / (loop_ms * 1e-3), "finite": bool(torch.isfinite(x).all())}
 
-    if "Tmel" in cfg:
+    if "Tmel" in cfg and cond_ms is not None:
         result["conditioner_ms_per_batch"] = cond_ms
         result["conditioner_ms_all_calls"] = cond_all
         result["end_to_end_samples_per_s_incl_conditioner"] = ddist.aggregate_throughput(

@@ -10,11 +10,12 @@ from .cpu_baseline import cpu_train_baseline
 from .work import forward_gemm_flops, layer_algorithmic_work, wino_dgrad_executed_work, wino_executed_work, wino_wgrad_executed_work
 
 
-def train_bench(args, cfg, world, rank, dev, ddist, red_dev=None, emit=True):
+def train_bench(args, cfg, world, rank, dev, ddist, red_dev=None, emit=True, dump_dir=None):
     red_dev = red_dev or dev
     """One data-parallel training step (`train.py:118-143`): q-sample + forward_train + MSE + backward through the
     HIP engine, bucketed asynchronous RCCL all-reduce of the gradients, Adam.  Synthetic audio
-    U(-0.3, 0.3) (SURVEY.md 8d).  Not the headline metric; reported as training audio samples/s."""
+    U(-0.3, 0.3) (SURVEY.md 8d).  Not the headline metric; reported as training audio samples/s.
+    dump_dir: write the last timed step's loss and the parameters it left there."""
     import torch.nn as nn
     from diffwave_sashimi_amd.distributed_util import apply_gradient_allreduce
     from diffwave_sashimi_amd.sampling import calc_diffusion_hyperparams
@@ -49,6 +50,12 @@ def train_bench(args, cfg, world, rank, dev, ddist, red_dev=None, emit=True):
         loss = step()
     ddist.barrier()
     mine = time.perf_counter() - t0
+    if dump_dir:       # before the extra steps below move the weights again
+        from .dump import dump_outputs
+        with torch.no_grad():
+            params = torch.cat([p.detach().reshape(-1) for p in net.parameters()])
+        dump_outputs(dump_dir, {"loss": loss, "params": params}, rank, world)
+        del params
     elapsed = ddist.max_over_ranks(mine, red_dev)
     per_rank_ms = [t / args.steps * 1e3 for t in ddist.gather_over_ranks(mine, red_dev)]
     per_rank_loss = ddist.gather_over_ranks(float(loss.detach()), red_dev)      # each rank's own shard (seed 99 + rank)
@@ -63,7 +70,8 @@ def train_bench(args, cfg, world, rank, dev, ddist, red_dev=None, emit=True):
                        "exposed_ms_per_rank": ddist.gather_over_ranks(float(red.exposed_ms() or 0.0), red_dev),
                        "buckets": len(red.buckets), "bucket_mbytes": [b.flat.numel() * 4 / 2 ** 20 for b in red.buckets],
                        "bucket_ready": red.bucket_ready_points(), "gradient_slots": red.last_stats}
-    if world == 1 and not ddist.dist.is_initialized() and os.environ.get("DWS_BENCH_NO_DP_OVERHEAD") is None:
+    if world == 1 and not ddist.dist.is_initialized() and os.environ.get("DWS_BENCH_NO_DP_OVERHEAD") is None and \
+            getattr(args, "full", True):
         # What data parallelism adds to ONE rank's step besides the wire time: the same steps inside a 1-rank RCCL group
         # (apply_gradient_allreduce: gradients written into the flat buckets, hooks, bucketed asynchronous all-reduces,
         # division) minus the plain steps above.  Measurable on a one-GPU box; the N-rank exchange itself is the driver's

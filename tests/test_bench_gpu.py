@@ -7,6 +7,7 @@ import socket
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 from tests.conftest import ROOT
@@ -33,7 +34,7 @@ def _last_json(out):
 
 def test_single_gpu_line_has_roofline_and_cpu_baseline(gpu):
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--config", "wnet_h128_d30_T200", "--steps", "4",
-                        "--warmup", "1"], capture_output=True, text=True, timeout=900, cwd=ROOT)
+                        "--warmup", "1", "--full"], capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
     d = _last_json(r.stdout)
     assert REQUIRED <= set(d) and d["n_gpus"] == 1 and d["steps"] == 4 and d["warmup"] == 1
@@ -67,6 +68,22 @@ def test_single_gpu_line_has_roofline_and_cpu_baseline(gpu):
     assert "gpu_over_cpu_whole_host" not in d
 
 
+def test_plain_line_times_the_steps_only_and_dumps_the_state(gpu, tmp_path):
+    """Without --full the line carries the headline keys and nothing that needs runs of its own; --dump-outputs writes
+    the sampler state the timed steps left (B x 1 x L, float32)."""
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--config", "wnet_h128_d30_T200", "--batch", "2",
+                        "--steps", "3", "--warmup", "1", "--dump-outputs", str(tmp_path)],
+                       capture_output=True, text=True, timeout=900, cwd=ROOT)
+    assert r.returncode == 0, r.stderr[-3000:]
+    d = _last_json(r.stdout)
+    assert REQUIRED <= set(d) and d["steps"] == 3 and d["warmup"] == 1 and d["state_finite"]
+    assert abs(d["value"] - 2 * 16000 / (200 * d["ms_per_step"] * 1e-3)) < 1e-6 * d["value"]
+    for key in ("roofline", "full_loop", "cpu_baseline", "extra_f32_exact", "extra_configs", "summary"):
+        assert key not in d, key
+    x = np.load(tmp_path / "x.npy")
+    assert x.shape == (2, 1, 16000) and x.dtype == np.float32 and np.isfinite(x).all()
+
+
 def test_two_ranks_aggregate(gpu):
     env = dict(os.environ, DWS_BENCH_SHARE_GPU="1", OMP_NUM_THREADS="2")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
@@ -85,7 +102,8 @@ def test_default_headline_line_carries_the_other_baseline_configs(gpu):
     """The default command (what the driver runs) evidences BASELINE configs 3, 4 and 5 too: `extra_configs` holds a
     short sampling leg for unet_d64 and the conditional unet_d32, and one GPU's training step of unet_d128, each with
     its own ms/step and roofline; the WaveNet roofline prices the Winograd kernel on the flops it executes."""
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "4", "--warmup", "1", "--no-cpu-baseline"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "4", "--warmup", "1", "--no-cpu-baseline",
+                        "--full"],
                        capture_output=True, text=True, timeout=1500, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
     d = _last_json(r.stdout)

@@ -11,7 +11,7 @@ for v in "$@"; do
   export DWS_HIPCC_FLAGS_$STEM="$DEF $flags"
   touch $R/diffwave-sashimi_amd/csrc/$STEM.hip; python $R/diffwave-sashimi_amd/build.py > /dev/null
   W=/tmp/prof_$name; rm -rf $W; mkdir -p $W
-  rocprofv3 --kernel-trace --stats -d $W/stats -o stats -- python $R/bench.py --config $CFG --steps 10 --warmup 2 --no-cpu-baseline > $W/stats.log 2>&1
+  rocprofv3 --kernel-trace --stats -d $W/stats -o stats -- python $R/bench.py --full --config $CFG --steps 10 --warmup 2 --no-cpu-baseline > $W/stats.log 2>&1
   echo "== $name ($flags): $(grep '^{' $W/stats.log | tail -1 | python -c 'import json,sys; d=json.loads(sys.stdin.read()); print(d["ms_per_step"])')"
   python $R/tools/rocpd_summary.py stats $W/stats/stats_results.db | head -8 | cut -c1-150
   rm -rf $W

@@ -14,9 +14,9 @@ for what in "$@"; do
     c5train) ARGS="--config unet_d128_n6_T200 --mode train --steps 4 --warmup 2";;
     wntrain) ARGS="--config wnet_h256_d36_T200 --mode train --steps 6 --warmup 2";;
   esac
-  python $R/bench.py $ARGS > /tmp/b_$what.log 2>&1; grep '^{' /tmp/b_$what.log | tail -1 > $OUT/${TAG}_bench_$what.json
+  python $R/bench.py --full $ARGS > /tmp/b_$what.log 2>&1; grep '^{' /tmp/b_$what.log | tail -1 > $OUT/${TAG}_bench_$what.json
   W=/tmp/prof_$what; rm -rf $W; mkdir -p $W
-  rocprofv3 --kernel-trace --stats -d $W/stats -o stats -- python $R/bench.py $ARGS --no-cpu-baseline --no-full-loop > $W/stats.log 2>&1
+  rocprofv3 --kernel-trace --stats -d $W/stats -o stats -- python $R/bench.py --full $ARGS --no-cpu-baseline --no-full-loop > $W/stats.log 2>&1
   python $R/tools/rocpd_summary.py stats $W/stats/stats_results.db | head -45 > $OUT/${TAG}_${what}_kernel_stats.txt
   rm -rf $W
 done

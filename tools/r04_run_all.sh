@@ -7,11 +7,11 @@ if [ "$1" = "tests" ]; then
   python -m pytest tests -m gpu -q --timeout 900 --durations=8 2>&1 | tail -30 > $OUT/r04_gputest.log; tail -3 $OUT/r04_gputest.log
 fi
 # the line the driver records: default command (headline + full loop + extra_configs + cpu_baseline)
-T0=$(date +%s); python bench.py > /tmp/b_default.log 2> /tmp/b_default.err; T1=$(date +%s)
+T0=$(date +%s); python bench.py --full > /tmp/b_default.log 2> /tmp/b_default.err; T1=$(date +%s)
 grep '^{' /tmp/b_default.log | tail -1 > $OUT/r04_bench_default.json
-echo "python bench.py: $((T1 - T0)) s wall clock" > $OUT/r04_bench_default_wallclock.txt
+echo "python bench.py --full: $((T1 - T0)) s wall clock" > $OUT/r04_bench_default_wallclock.txt
 # clock under the Winograd kernel ALONE (no bf16x3 leg, no roofline leg: 400 replays of the f32 step)
-tools/sclk_log.sh $OUT/r04_sclk_c2_f32_only.txt -- python bench.py --config wnet_h256_d36_T200 --steps 400 --warmup 3 --no-cpu-baseline --no-extra --no-roofline > /tmp/c2clk.log 2>&1
+tools/sclk_log.sh $OUT/r04_sclk_c2_f32_only.txt -- python bench.py --full --config wnet_h256_d36_T200 --steps 400 --warmup 3 --no-cpu-baseline --no-extra --no-roofline > /tmp/c2clk.log 2>&1
 head -3 $OUT/r04_sclk_c2_f32_only.txt
 tools/r02_measure.sh r04 c2 c3 c4 d128 c5train wntrain
 tools/profile_kernel.sh r04_wavenet_f32 wn_layer_wino

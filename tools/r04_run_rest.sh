@@ -2,9 +2,9 @@
 # GPU box: the part of tools/r04_run_all.sh after the per-config bench lines (default line, counters, traces).
 R=${GRAFT_REPO_ROOT:-/root/repo}; OUT=$R/gpurun_out; mkdir -p $OUT
 cd $R
-T0=$(date +%s); python bench.py > /tmp/b_default.log 2> /tmp/b_default.err; T1=$(date +%s)
+T0=$(date +%s); python bench.py --full > /tmp/b_default.log 2> /tmp/b_default.err; T1=$(date +%s)
 grep '^{' /tmp/b_default.log | tail -1 > $OUT/r04_bench_default.json
-echo "python bench.py: $((T1 - T0)) s wall clock" > $OUT/r04_bench_default_wallclock.txt
+echo "python bench.py --full: $((T1 - T0)) s wall clock" > $OUT/r04_bench_default_wallclock.txt
 tail -3 /tmp/b_default.err
 tools/r04_traffic.sh r04 > /dev/null
 tools/profile_kernel.sh r04_sashimi_d64_fftconv fftconv --config unet_d64_n6_T200

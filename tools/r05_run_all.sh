@@ -6,20 +6,20 @@ R=${GRAFT_REPO_ROOT:-/root/repo}; O=$R/gpurun_out; mkdir -p $O; cd $R
 PART=${1:-1}
 if [ "$PART" = 1 ]; then
   SECONDS=0
-  python bench.py > $O/r05_bench_default.json 2> $O/r05_bench_default.err
-  echo "$SECONDS s wall (python bench.py, all legs)" > $O/r05_bench_default_wallclock.txt
-  python bench.py --precision bf16x6 --no-extra > $O/r05_bench_c2_bf16x6.json 2>> $O/r05_bench_default.err
-  python bench.py --precision f16x3 --no-extra --no-cpu-baseline > $O/r05_bench_c2_f16x3.json 2>> $O/r05_bench_default.err
+  python bench.py --full > $O/r05_bench_default.json 2> $O/r05_bench_default.err
+  echo "$SECONDS s wall (python bench.py --full, all legs)" > $O/r05_bench_default_wallclock.txt
+  python bench.py --full --precision bf16x6 --no-extra > $O/r05_bench_c2_bf16x6.json 2>> $O/r05_bench_default.err
+  python bench.py --full --precision f16x3 --no-extra --no-cpu-baseline > $O/r05_bench_c2_f16x3.json 2>> $O/r05_bench_default.err
   for C in unet_d64_n6_T200 unet_d32_n6_T50_cond; do
-    python bench.py --config $C --no-extra --no-cpu-baseline > $O/r05_bench_${C}.json 2>> $O/r05_bench_default.err
-    python bench.py --config $C --no-extra --no-cpu-baseline --precision bf16x6 > $O/r05_bench_${C}_bf16x6.json 2>> $O/r05_bench_default.err
-    python bench.py --config $C --no-extra --no-cpu-baseline --precision f16x3 > $O/r05_bench_${C}_f16x3.json 2>> $O/r05_bench_default.err
+    python bench.py --full --config $C --no-extra --no-cpu-baseline > $O/r05_bench_${C}.json 2>> $O/r05_bench_default.err
+    python bench.py --full --config $C --no-extra --no-cpu-baseline --precision bf16x6 > $O/r05_bench_${C}_bf16x6.json 2>> $O/r05_bench_default.err
+    python bench.py --full --config $C --no-extra --no-cpu-baseline --precision f16x3 > $O/r05_bench_${C}_f16x3.json 2>> $O/r05_bench_default.err
   done
-  python bench.py --config unet_d128_n6_T200 --mode train --steps 6 --warmup 2 > $O/r05_bench_c5train.json 2>> $O/r05_bench_default.err
-  DWS_BENCH_NO_DP_OVERHEAD=1 python bench.py --config unet_d128_n6_T200 --mode train --precision bf16x6 --steps 6 --warmup 2 > $O/r05_bench_c5train_bf16x6.json 2>> $O/r05_bench_default.err
-  python bench.py --config wnet_h128_d30_T200 --no-extra --no-cpu-baseline > $O/r05_bench_wavenet_h128.json 2>> $O/r05_bench_default.err
-  python bench.py --config wnet_h128_d30_T200 --no-extra --no-cpu-baseline --precision bf16x6 > $O/r05_bench_wavenet_h128_bf16x6.json 2>> $O/r05_bench_default.err
-  python bench.py --config wnet_h128_d30_T200 --no-extra --no-cpu-baseline --precision f16x3 > $O/r05_bench_wavenet_h128_f16x3.json 2>> $O/r05_bench_default.err
+  python bench.py --full --config unet_d128_n6_T200 --mode train --steps 6 --warmup 2 > $O/r05_bench_c5train.json 2>> $O/r05_bench_default.err
+  DWS_BENCH_NO_DP_OVERHEAD=1 python bench.py --full --config unet_d128_n6_T200 --mode train --precision bf16x6 --steps 6 --warmup 2 > $O/r05_bench_c5train_bf16x6.json 2>> $O/r05_bench_default.err
+  python bench.py --full --config wnet_h128_d30_T200 --no-extra --no-cpu-baseline > $O/r05_bench_wavenet_h128.json 2>> $O/r05_bench_default.err
+  python bench.py --full --config wnet_h128_d30_T200 --no-extra --no-cpu-baseline --precision bf16x6 > $O/r05_bench_wavenet_h128_bf16x6.json 2>> $O/r05_bench_default.err
+  python bench.py --full --config wnet_h128_d30_T200 --no-extra --no-cpu-baseline --precision f16x3 > $O/r05_bench_wavenet_h128_f16x3.json 2>> $O/r05_bench_default.err
   for f in $O/r05_bench_*.json; do echo "== $f"; python - "$f" <<'PY'
 import json, sys
 try:

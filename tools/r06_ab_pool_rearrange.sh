@@ -17,7 +17,7 @@ cat $O/r06_ab_pool_rearrange.txt
   for V in old new; do
     W=/tmp/prof_pool_$V; rm -rf $W; mkdir -p $W
     if [ $V = old ]; then export DWS_POOL_REARRANGE_OLD=1; else unset DWS_POOL_REARRANGE_OLD; fi
-    DWS_BENCH_NO_DP_OVERHEAD=1 rocprofv3 --kernel-trace --stats -d $W/stats -o stats -- python $R/bench.py --config unet_d128_n6_T200 --mode train --precision f32 --steps 3 --warmup 1 --no-cpu-baseline > $W/stats.log 2>&1
+    DWS_BENCH_NO_DP_OVERHEAD=1 rocprofv3 --kernel-trace --stats -d $W/stats -o stats -- python $R/bench.py --full --config unet_d128_n6_T200 --mode train --precision f32 --steps 3 --warmup 1 --no-cpu-baseline > $W/stats.log 2>&1
     echo "## under rocprofv3, $V" >> $O/r06_ab_pool_rearrange.txt
     python $R/tools/rocpd_summary.py stats $W/stats/stats_results.db | grep -i "pool_rearrange" | cut -c1-150 >> $O/r06_ab_pool_rearrange.txt
     rm -rf $W

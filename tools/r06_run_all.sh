@@ -7,16 +7,16 @@ R=${GRAFT_REPO_ROOT:-/root/repo}; O=$R/gpurun_out; mkdir -p $O; cd $R
 PART=${1:-1}
 if [ "$PART" = 1 ]; then
   SECONDS=0
-  python bench.py > $O/r06_bench_default.json 2> $O/r06_bench_default.err
-  echo "$SECONDS s wall (python bench.py, all legs)" > $O/r06_bench_default_wallclock.txt
-  python bench.py --precision f32 --no-extra --no-cpu-baseline > $O/r06_bench_c2_f32.json 2>> $O/r06_bench_default.err
+  python bench.py --full > $O/r06_bench_default.json 2> $O/r06_bench_default.err
+  echo "$SECONDS s wall (python bench.py --full, all legs)" > $O/r06_bench_default_wallclock.txt
+  python bench.py --full --precision f32 --no-extra --no-cpu-baseline > $O/r06_bench_c2_f32.json 2>> $O/r06_bench_default.err
   for C in unet_d64_n6_T200 unet_d32_n6_T50_cond wnet_h128_d30_T200; do
     for P in bf16x6 f32; do
-      python bench.py --config $C --no-extra --no-cpu-baseline --precision $P > $O/r06_bench_${C}_$P.json 2>> $O/r06_bench_default.err
+      python bench.py --full --config $C --no-extra --no-cpu-baseline --precision $P > $O/r06_bench_${C}_$P.json 2>> $O/r06_bench_default.err
     done
   done
-  python bench.py --config unet_d128_n6_T200 --mode train --precision f32 --steps 6 --warmup 2 > $O/r06_bench_c5train_f32.json 2>> $O/r06_bench_default.err
-  DWS_BENCH_NO_DP_OVERHEAD=1 python bench.py --config unet_d128_n6_T200 --mode train --precision bf16x6 --steps 6 --warmup 2 > $O/r06_bench_c5train_bf16x6.json 2>> $O/r06_bench_default.err
+  python bench.py --full --config unet_d128_n6_T200 --mode train --precision f32 --steps 6 --warmup 2 > $O/r06_bench_c5train_f32.json 2>> $O/r06_bench_default.err
+  DWS_BENCH_NO_DP_OVERHEAD=1 python bench.py --full --config unet_d128_n6_T200 --mode train --precision bf16x6 --steps 6 --warmup 2 > $O/r06_bench_c5train_bf16x6.json 2>> $O/r06_bench_default.err
   for f in $O/r06_bench_*.json; do echo "== $f"; python - "$f" <<'PY'
 import json, sys
 try:
@@ -45,7 +45,7 @@ elif [ "$PART" = 2 ]; then
   cd /tmp && export TMPDIR=/tmp
   for P in f32 bf16x6; do
     W=/tmp/prof_c5_$P; rm -rf $W; mkdir -p $W
-    DWS_BENCH_NO_DP_OVERHEAD=1 rocprofv3 --kernel-trace --stats -d $W/stats -o stats -- python $R/bench.py --config unet_d128_n6_T200 --mode train --precision $P --steps 4 --warmup 2 --no-cpu-baseline > $W/stats.log 2>&1
+    DWS_BENCH_NO_DP_OVERHEAD=1 rocprofv3 --kernel-trace --stats -d $W/stats -o stats -- python $R/bench.py --full --config unet_d128_n6_T200 --mode train --precision $P --steps 4 --warmup 2 --no-cpu-baseline > $W/stats.log 2>&1
     python $R/tools/rocpd_summary.py stats $W/stats/stats_results.db | head -45 > $O/r06_c5train_${P}_kernel_stats.txt
     rm -rf $W
   done
