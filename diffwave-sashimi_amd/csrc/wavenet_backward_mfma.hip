@@ -53,8 +53,8 @@ __device__ __forceinline__ float gelu_grad_b(float x) { return dws_gelu_grad(x);
 //      (the two GLU halves of the same channels): out = o = acc + bias [B,2H,L] and
 //      out2 = x1 = res + o_a sigmoid(o_b) (+ aux)  [B,H,L]
 //
-// SPLIT (precision = "bf16x6" in training; T = 1, 16-byte staging only): the same GEMM on the bf16 matrix cores with every
-// operand as an exact 3-term bf16 split and six partial products (bf16_split.h).  The staged fp32 chunk is split ONCE by
+// SPLIT (precision = "bf16x6" in training; T = 1, 16-byte staging only; every epilogue, WaveNet's gate adjoint included): the
+// same GEMM on the bf16 matrix cores with every operand as an exact 3-term bf16 split and six partial products (bf16_split.h).  The staged fp32 chunk is split ONCE by
 // the workgroup (one 16-byte B item of eight k values per thread and chunk, three terms) into a second LDS buffer while
 // the previous chunk's MFMAs run; the A fragments stay the fp32 ones of pack_a_frag (the weights change every step) and
 // are split by the wave that owns the rows.  Slot e = 4 g + j of a 16-wide k-block is k = 16 kb + 8 g + 2 j + lhi -- the
@@ -63,7 +63,7 @@ template <int MT, int T, int EPI, int SPLIT = 0>
 __global__ __launch_bounds__(256, 2) __attribute__((amdgpu_waves_per_eu(2, 2))) void tapconv_mfma_kernel(TapConvArgs a) {
     constexpr int P = 64, NT = 2, KC = 32;
     constexpr int ROWS = T * KC, RPW = ROWS / 4;
-    static_assert(!SPLIT || (T == 1 && EPI != 1), "split instances: pointwise GEMMs");
+    static_assert(!SPLIT || T == 1, "split instances: pointwise GEMMs");
     constexpr int BOP_FLOATS = SPLIT ? (KC / 16) * 2 * 3 * P * 4 : 0;     // one split chunk: [k-block][k half][term][column] 16-byte items
     // T = 3: measured faster with 2 workgroups per CU than with 3 (456 -> 384 us on the C = 256 adjoint), so the
     // allocation is padded past a third of the 160 KB LDS
@@ -477,15 +477,15 @@ bool tapconv_ln_supported(int epi, int M, int L) {
     return false;
 }
 
-// split instances: T = 1, not the gate adjoint, and the 16-byte staging form (the kernel's x4 condition)
+// split instances: T = 1 and the 16-byte staging form (the kernel's x4 condition)
 static bool tapconv_split_ok(const TapConvArgs& a) {
-    return a.split == 1 && a.T == 1 && a.epi != 1 && a.L % 4 == 0 && ((((size_t)a.src0) | ((size_t)a.src1)) % 16 == 0);
+    return a.split == 1 && a.T == 1 && a.L % 4 == 0 && ((((size_t)a.src0) | ((size_t)a.src1)) % 16 == 0);
 }
 
 template <int T, int EPI>
 static int launch_tc(const TapConvArgs& a, hipStream_t s) {
     const int nt = a.B * ceil_div(a.L, 64);
-    if constexpr (T == 1 && EPI != 1) {
+    if constexpr (T == 1) {
         if (tapconv_split_ok(a)) {
             if constexpr (EPI == 6) {
                 hipLaunchKernelGGL((tapconv_mfma_kernel<2, T, EPI, 1>), dim3(nt, a.M / 256), dim3(256), 0, s, a);
@@ -1051,15 +1051,17 @@ int wgrad_mfma_nsplit(int B, int O, int C, int L, int T) {
 }
 
 int launch_wgrad_mfma(const WgradArgs& a_in, int T, float scale, float* dW, hipStream_t s) {
-    ProfileScope ps(a_in.split == 1 ? "wgrad_bx6" : "wgrad_mfma", s);
+    static const bool no_dma = getenv("DWS_WGRAD_NO_DMA") != nullptr;
+    static const bool no_dma4 = getenv("DWS_WGRAD_NO_DMA4") != nullptr;
+    const bool dma4 = T == 1 && !a_in.xact && !a_in.addc && !no_dma && !no_dma4 && a_in.L % 4 == 0 &&
+                      (a_in.xL ? a_in.xL : a_in.L) % 4 == 0 && ((size_t)a_in.dY | (size_t)a_in.X) % 16 == 0;
+    // the name says which arithmetic ran: the split instance exists in the 16-byte single-tap kernel only
+    ProfileScope ps(a_in.split == 1 && dma4 ? "wgrad_bx6" : "wgrad_mfma", s);
     DWS_CHECK((size_t)a_in.B * std::max(a_in.O, a_in.C) * std::max(a_in.L, a_in.xL) * 4 < ((size_t)1 << 31), DWS_ERR_UNSUPPORTED,
               "wgrad_mfma: operand larger than 2 GiB (B=%d rows=%d L=%d)", a_in.B, std::max(a_in.O, a_in.C), a_in.L);
     WgradArgs a = a_in;
     const dim3 grid(ceil_div(a.O, 128), ceil_div(a.C, 128), T * a.nsplit);
-    static const bool no_dma = getenv("DWS_WGRAD_NO_DMA") != nullptr;
-    static const bool no_dma4 = getenv("DWS_WGRAD_NO_DMA4") != nullptr;
-    if (T == 1 && !a.xact && !a.addc && !no_dma && !no_dma4 && a.L % 4 == 0 && (a.xL ? a.xL : a.L) % 4 == 0 &&
-        ((size_t)a.dY | (size_t)a.X) % 16 == 0) {
+    if (dma4) {
         constexpr int lds = 2 * 2 * 128 * 64 * 4;
         static bool attr4_dev[DWS_MAX_DEVICES] = {};
     bool& attr4 = attr4_dev[current_device_slot()];

@@ -13,6 +13,7 @@
 #include <algorithm>
 #include <cstdlib>
 
+#include "bf16_split.h"
 #include "wavenet_backward.h"
 
 namespace dws {
@@ -172,13 +173,158 @@ __global__ __launch_bounds__(512, 1) void tapwino_mfma_kernel(TapConvArgs a, int
     }
 }
 
+// SPLIT form (precision = "bf16x6"): the same pairing on the bf16 matrix cores with every operand as an exact 3-term bf16 split
+// and six partial products (bf16_split.h).  MT = 1 (the split A terms beside four accumulator sets), chunks of KC = 16 input
+// channels: raw rows double-buffered as above, and the transformed columns t0..t3 formed in fp32 from the raw rows (the
+// roundings of the f32 kernel) and THEN split -- the split of a difference is not the difference of the splits -- once per
+// chunk by the workgroup into a second, double-buffered LDS area of 16-byte B items [j][k half][term][column]; one item per
+// thread and chunk, built under the previous chunk's MFMAs.  The A fragments are the fp32 ones of pack_a_frag (the weights
+// change every step), split in registers by the wave that owns the rows.  Slot e of a lane's 16-wide k-block is
+// k = 8 (e >> 2) + 2 (e & 3) + lhi: the order the fp32 fragments of two k-groups already hold per lane.
+__global__ __launch_bounds__(512, 1) void tapwino_bx6_kernel(TapConvArgs a, int log2d) {
+    constexpr int P = 64, KC = 16, ROWS = 4 * KC;
+    constexpr int BOP_BYTES = 4 * 2 * 3 * P * 16;
+    __shared__ __attribute__((aligned(16))) float lds[2 * ROWS * P + 2 * BOP_BYTES / 4];
+    char* const bop = reinterpret_cast<char*>(lds + 2 * ROWS * P);
+
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int wm = wave & 3, wn = wave >> 2;
+    const int l31 = lane & 31, lhi = lane >> 5;
+    const int L = a.L, d = 1 << log2d;
+    const int nq = ((L + 2 * d - 1) >> (log2d + 1)) << log2d;
+    const int ntq = (nq + P - 1) / P;
+    const int tile = xcd_remap(blockIdx.x, gridDim.x);
+    const int b = tile / ntq, q0 = (tile % ntq) * P;
+    auto pos_of = [&](int q) { return ((q >> log2d) << (log2d + 1)) + (q & (d - 1)); };
+    if (pos_of(q0) >= L) return;                                    // (uniform: before any barrier)
+    const int K = a.K0, ncb = K / KC;
+
+    const int pv = pos_of(q0 + lane) * 4;
+    const bool x4 = (L % 4 == 0) && log2d >= 2 && ((size_t)a.src0 % 16 == 0);
+    const int p4 = pos_of(q0 + 4 * (lane & 15));
+    auto stage_dma = [&](int cb, int buf) {
+        float* xs = lds + buf * (ROWS * P);
+        const float* base = a.src0 + ((size_t)b * K + (size_t)cb * KC) * L;
+        if (x4) {
+            __amdgpu_buffer_rsrc_t r = __builtin_amdgcn_make_buffer_rsrc((void*)base, 0, KC * L * 4, 0x00020000);
+#pragma unroll
+            for (int i = 0; i < ROWS / 32; ++i) {
+                const int ii = wave + 8 * i, j = ii / (KC / 4), r4 = ii % (KC / 4);
+                const int pos = p4 + (j - 1) * d;
+                const int voff = ((unsigned)pos < (unsigned)L) ? ((4 * r4 + (lane >> 4)) * L + pos) * 4 : 0x7ffffff0;
+                __builtin_amdgcn_raw_ptr_buffer_load_lds(r, xs + (j * KC + 4 * r4) * P, 16, voff, 0, 0, 0);
+            }
+            return;
+        }
+#pragma unroll
+        for (int i = 0; i < ROWS / 8; ++i) {
+            const int row = wave + 8 * i;
+            const int j = row / KC, cc = row % KC;
+            __amdgpu_buffer_rsrc_t r = __builtin_amdgcn_make_buffer_rsrc((void*)(base + (size_t)cc * L), 0, L * 4, 0x00020000);
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(r, xs + row * P, 4, pv + (j - 1) * d * 4, 0, 0, 0);
+        }
+    };
+    // this thread's B item of a chunk: product j = wave >> 1, k half wave & 1 (wave-uniform), column lane
+    auto transform = [&](int cb) {
+        const int j = wave >> 1, h = wave & 1;
+        const float* xs = lds + (cb & 1) * (ROWS * P) + lane;
+        bx_bf16x8 it[3];
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+            const int k = 8 * (e >> 2) + 2 * (e & 3) + h;
+            const float x1 = xs[(1 * KC + k) * P], x2 = xs[(2 * KC + k) * P];
+            float t;
+            if (j == 0) t = xs[(0 * KC + k) * P] - x2;
+            else if (j == 1) t = x1 + x2;
+            else if (j == 2) t = x2 - x1;
+            else t = x1 - xs[(3 * KC + k) * P];
+            SplitBf16x3::split1(t, it, e);
+        }
+        char* dst = bop + (cb & 1) * BOP_BYTES + (((j * 2 + h) * 3) * P + lane) * 16;
+#pragma unroll
+        for (int t = 0; t < 3; ++t) *reinterpret_cast<bx_bf16x8*>(dst + t * (P * 16)) = it[t];
+    };
+
+    f32x16 acc[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[j][r] = 0.f;
+    __amdgpu_buffer_rsrc_t rA = __builtin_amdgcn_make_buffer_rsrc((void*)a.A, 0, a.M * a.nkg_total * 8 * 4, 0x00020000);
+    const int lane16 = lane * 16;
+    const int mt = blockIdx.y * 4 + wm;
+    // k-groups of chunk cb, product j in the packed [M][4 K] order (32-channel blocks: k' = (cb32 * 4 + j) * 32 + cc)
+    auto load_a = [&](f32x4 (&dst)[4][2], int cb) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+#pragma unroll
+            for (int g = 0; g < 2; ++g) {
+                const int kg = (cb >> 1) * 16 + j * 4 + (cb & 1) * 2 + g;
+                dst[j][g] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rA, lane16, (mt * a.nkg_total + kg) * 1024, 0));
+            }
+    };
+
+    f32x4 a_cur[4][2], a_nxt[4][2];
+    stage_dma(0, 0);
+    if (ncb > 1) stage_dma(1, 1);
+    load_a(a_cur, 0);
+    __builtin_amdgcn_s_waitcnt(0x0F70);   // vmcnt(0): hipcc does not make a barrier wait for LDS-DMA
+    __syncthreads();
+    transform(0);
+    __syncthreads();
+    for (int cb = 0; cb < ncb; ++cb) {
+        if (cb + 2 < ncb) stage_dma(cb + 2, cb & 1);       // raw buffer of chunk cb: transformed an iteration ago
+        if (cb + 1 < ncb) load_a(a_nxt, cb + 1);
+        __builtin_amdgcn_sched_barrier(0);
+        if (cb + 1 < ncb) transform(cb + 1);               // raw chunk cb + 1 landed at the last barrier
+        const char* bb = bop + (cb & 1) * BOP_BYTES + (lhi * 3 * P + wn * 32 + l31) * 16;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            bx_bf16x8 bq[3], af[3];
+#pragma unroll
+            for (int t = 0; t < 3; ++t) bq[t] = *reinterpret_cast<const bx_bf16x8*>(bb + ((j * 6 + t) * P) * 16);
+#pragma unroll
+            for (int e = 0; e < 8; ++e) SplitBf16x3::split1(a_cur[j][e >> 2][e & 3], af, e);
+#pragma unroll
+            for (int t = 0; t < 6; ++t) acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[BX6_IA[t]], bq[BX6_IB[t]], acc[j], 0, 0, 0);
+        }
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+#pragma unroll
+            for (int g = 0; g < 2; ++g) a_cur[j][g] = a_nxt[j][g];
+        __builtin_amdgcn_s_waitcnt(0x0F70);   // chunk cb + 2 and the next A fragments (this wave's), then everyone's
+        __syncthreads();                      // split chunk cb + 1 visible; split buffer cb & 1 free again
+    }
+
+    // y[p] = m0 + m1 + m2, y[p+d] = m1 - m2 - m3  (+ addin * addscale)
+    const int p = pos_of(q0 + wn * 32 + l31);
+    const bool ok0 = p < L, ok1 = p + d < L;
+    const size_t boff = (size_t)b * a.M * L;
+    float* __restrict__ ob = a.out + boff;
+    const float* __restrict__ ab = a.addin ? a.addin + boff : nullptr;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+        const int row = mt * 32 + (r & 3) + 8 * (r >> 2) + 4 * lhi;
+        const int i0 = row * L + p;
+        const float m0 = acc[0][r], m1 = acc[1][r], m2 = acc[2][r], m3 = acc[3][r];
+        float y0 = m0 + m1 + m2, y1 = m1 - m2 - m3;
+        if (ab) {
+            if (ok0) y0 = fmaf(ab[i0], a.addscale, y0);
+            if (ok1) y1 = fmaf(ab[i0 + d], a.addscale, y1);
+        }
+        if (ok0) ob[i0] = y0;
+        if (ok1) ob[i0 + d] = y1;
+    }
+}
+
 bool tapwino_mfma_supported(int M, int K, int dil) {
     static const bool off = getenv("DWS_TAPCONV_DIRECT") != nullptr;
     return !off && M % 128 == 0 && K % 32 == 0 && K > 0 && dil > 0 && (dil & (dil - 1)) == 0;
 }
 
 int launch_tapwino_mfma(const TapConvArgs& a, hipStream_t s) {
-    ProfileScope ps("tapconv_mfma", s);
+    ProfileScope ps(a.split == 1 ? "tapwino_bx6" : "tapconv_mfma", s);
     DWS_CHECK(tapwino_mfma_supported(a.M, a.K0, a.dil) && a.K1 == 0 && a.T == 3 && a.epi == 0 && a.sign == -1, DWS_ERR_UNSUPPORTED,
               "tapwino_mfma: M=%d K=%d+%d T=%d dil=%d epi=%d sign=%d", a.M, a.K0, a.K1, a.T, a.dil, a.epi, a.sign);
     DWS_CHECK((long long)a.M * a.L < (1ll << 31) / 4, DWS_ERR_UNSUPPORTED, "tapwino_mfma: M * L too large for 32-bit offsets");
@@ -186,7 +332,9 @@ int launch_tapwino_mfma(const TapConvArgs& a, hipStream_t s) {
     while ((1 << log2d) < a.dil) ++log2d;
     const int nq = (int)((((long long)a.L + 2 * a.dil - 1) >> (log2d + 1)) << log2d);
     const int nt = a.B * ceil_div(nq, 64);
-    if (a.M % 256 == 0)
+    if (a.split == 1)   // precision = bf16x6: any L, both staging forms
+        hipLaunchKernelGGL(tapwino_bx6_kernel, dim3(nt, a.M / 128), dim3(512), 0, s, a, log2d);
+    else if (a.M % 256 == 0)
         hipLaunchKernelGGL((tapwino_mfma_kernel<2>), dim3(nt, a.M / 256), dim3(512), 0, s, a, log2d);
     else
         hipLaunchKernelGGL((tapwino_mfma_kernel<1>), dim3(nt, a.M / 128), dim3(512), 0, s, a, log2d);
@@ -204,7 +352,14 @@ int launch_tapwino_mfma(const TapConvArgs& a, hipStream_t s) {
 // registers go to LDS; Xh = X + addc[b, c] inside [0, L), 0 outside, so the per-(b, c) constant enters with the factor
 // in(pa) +- in(pb)).  The bias gradient rides on product 1, whose dY operand sums every position exactly once.
 // ---------------------------------------------------------------------------
-__global__ __launch_bounds__(256, 2) void wgrad_wino_kernel(WgradArgs a, int log2d) {
+// SPLIT (precision = "bf16x6"): both operands of a chunk are formed in fp32 when the registers go to LDS (u_j from dY, t_j from
+// Xh, as above), and the MFMA loop carries them as exact 3-term bf16 splits with six products per 16 pair columns on
+// v_mfma_f32_32x32x16_bf16: a lane supplies eight consecutive columns of its row and splits them in registers.  The split-K
+// partials and their fixed-order reduce are the f32 kernel's (deterministic).
+// The split instance runs one workgroup per CU: with the next chunk's prefetch registers live, the split fragments do not fit
+// the 256 registers of two (112 bytes of scratch per lane at (256, 2)).
+template <int SPLIT>
+__global__ __launch_bounds__(256, SPLIT ? 1 : 2) void wgrad_wino_kernel(WgradArgs a, int log2d) {
     constexpr int PC = 64, LD = PC + 2, RPW = 32;
     __shared__ float sdy[128 * LD];
     __shared__ float sx[128 * LD];
@@ -290,6 +445,32 @@ __global__ __launch_bounds__(256, 2) void wgrad_wino_kernel(WgradArgs a, int log
 #pragma unroll 8
             for (int p = 0; p < PC; ++p) bsum += sdy[tid * LD + p];
         }
+        if constexpr (SPLIT) {
+            // (the prefetch registers of the next chunk are live here: one dY row tile split at a time keeps the loop out of scratch)
+#pragma unroll 1
+            for (int kb = 0; kb < PC / 16; ++kb) {
+                const int p8 = kb * 16 + 8 * lhi;      // columns p8 .. p8 + 7 of the lane's rows
+                bx_bf16x8 fb[2][3];
+#pragma unroll
+                for (int j = 0; j < 2; ++j) {
+                    const float* rb = sx + (wc * 64 + j * 32 + l31) * LD + p8;
+#pragma unroll
+                    for (int e = 0; e < 8; ++e) SplitBf16x3::split1(rb[e], fb[j], e);
+                }
+#pragma unroll
+                for (int i = 0; i < 2; ++i) {
+                    bx_bf16x8 fa[3];
+                    const float* ra = sdy + (wo * 64 + i * 32 + l31) * LD + p8;
+#pragma unroll
+                    for (int e = 0; e < 8; ++e) SplitBf16x3::split1(ra[e], fa, e);
+#pragma unroll
+                    for (int t = 0; t < 6; ++t)
+#pragma unroll
+                        for (int j = 0; j < 2; ++j)
+                            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[BX6_IA[t]], fb[j][BX6_IB[t]], acc[i][j], 0, 0, 0);
+                }
+            }
+        } else {
 #pragma unroll 8
         for (int ks = 0; ks < PC / 2; ++ks) {
             const int pp = ks * 2 + lhi;
@@ -303,6 +484,7 @@ __global__ __launch_bounds__(256, 2) void wgrad_wino_kernel(WgradArgs a, int log
 #pragma unroll
                 for (int j = 0; j < 2; ++j)
                     acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[i], bv[j], acc[i][j], 0, 0, 0);
+        }
         }
     }
     // partial[split][o][c][j]
@@ -372,10 +554,11 @@ int wgrad_wino_nsplit(int B, int O, int C, int L, int dil) {
 
 // a.partial: [nsplit][O][C][4] floats, a.nsplit from wgrad_wino_nsplit
 int launch_wgrad_wino(const WgradArgs& a, float scale, float* dW, hipStream_t s) {
-    ProfileScope ps("wgrad_mfma", s);
+    ProfileScope ps(a.split == 1 ? "wgrad_wino_bx6" : "wgrad_mfma", s);
     DWS_CHECK(wgrad_wino_supported(a), DWS_ERR_UNSUPPORTED, "wgrad_wino: dil=%d xact=%d xL=%d", a.dil, a.xact, a.xL);
     const dim3 grid(ceil_div(a.O, 128), ceil_div(a.C, 128), 4 * a.nsplit);
-    hipLaunchKernelGGL(wgrad_wino_kernel, grid, dim3(256), 0, s, a, log2_of(a.dil));
+    if (a.split == 1) hipLaunchKernelGGL(wgrad_wino_kernel<1>, grid, dim3(256), 0, s, a, log2_of(a.dil));
+    else hipLaunchKernelGGL(wgrad_wino_kernel<0>, grid, dim3(256), 0, s, a, log2_of(a.dil));
     const size_t noc = (size_t)a.O * a.C;
     const int blocks1 = (int)ceil_div(noc, 256), blocks2 = a.bias_part ? ceil_div(a.O, 256) : 0;
     hipLaunchKernelGGL(wgrad_wino_reduce_kernel, dim3(blocks1 + blocks2), dim3(256), 0, s, (const float*)a.partial, dW, noc,

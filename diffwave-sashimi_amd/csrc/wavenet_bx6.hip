@@ -14,7 +14,8 @@
 //     commit: 6 bytes per weight) stream from L2 one (k-block, product) step ahead; 12 MFMAs per step;
 //     step embedding + conv bias enter as one extra k-block per product (A = the fp32 correction row of the f32
 //     Winograd path split in registers, B = the Winograd transform of the in-range indicator: exact in bf16);
-//   * gate in registers, split, -> LDS gate tile [k-octet][term][64 columns];
+//   * gate in registers, split, -> LDS gate tile [k-octet][term][64 columns]; the EXTRA instance adds the mel term and, in
+//     training (precision = "bf16x6"), saves the pre-activations H [B, 2C, L] for the gate adjoint as wavenet_wino.hip does;
 //   * GEMM2 [res; skip] = [Wr; Ws] g with the biases as an extra k-block;
 //   * epilogue: each wave transposes its row tiles through a private 8 KB LDS slot and moves them as row-major
 //     16-byte accesses: x' = (x + res) sqrt(.5) with x re-read (L2-hot: this tile staged it), skip += as load-add-store
@@ -587,6 +588,11 @@ __global__ __launch_bounds__(C * 2, (C >= 128 ? 2 : 1)) void wn_layer_bx6_kernel
                     ht += melb[(size_t)ch * L + pos];
                     hs += melb[(size_t)(C + ch) * L + pos];
                 }
+                if (EXTRA && a.hsave && pos < L) {   // training: keep the pre-activations for the gate adjoint (dword stores)
+                    float* __restrict__ hb = a.hsave + (size_t)b * 2 * C * L;
+                    hb[(size_t)ch * L + pos] = ht;
+                    hb[(size_t)(C + ch) * L + pos] = hs;
+                }
                 const float g = bx6_gate(ht, hs) * P::SG;
                 if (n == 0) g0[e] = g; else g1[e] = g;
             }
@@ -743,13 +749,13 @@ static int launch_bx6_t(const WnLayerArgs& a, int log2d, hipStream_t s) {
     const int ntl = (nblk * dil + 31) / 32;
     const int ntiles = a.B * ntl;
     static const bool trace = std::getenv("DWS_BX6_TRACE") != nullptr;
-    if (trace && !a.melc) {
+    if (trace && !a.melc && !a.hsave) {
         wino_trace_launch(ntiles, T::WAVES, a, s, [&](const WnLayerArgs& at) {
             hipLaunchKernelGGL((wn_layer_bx6_kernel<P, C, S, false>), dim3(ntiles), dim3(T::NTH), 0, s, at, log2d);
         }, P::NT == 3 ? "bx6" : "f16x3");
         return DWS_OK;
     }
-    if (a.melc) hipLaunchKernelGGL((wn_layer_bx6_kernel<P, C, S, true>), dim3(ntiles), dim3(T::NTH), 0, s, a, log2d);
+    if (a.melc || a.hsave) hipLaunchKernelGGL((wn_layer_bx6_kernel<P, C, S, true>), dim3(ntiles), dim3(T::NTH), 0, s, a, log2d);
     else hipLaunchKernelGGL((wn_layer_bx6_kernel<P, C, S, false>), dim3(ntiles), dim3(T::NTH), 0, s, a, log2d);
     return DWS_OK;
 }
@@ -774,8 +780,8 @@ int launch_wn_layer_bx6(int C, int S, const WnLayerArgs& a, int split, hipStream
     DWS_CHECK((int64_t)a.L + 4 * (int64_t)a.dilation < ((int64_t)1 << 28), DWS_ERR_UNSUPPORTED, "wn_layer_bx6: L too large");
     DWS_CHECK((int64_t)(C > S ? C : S) * a.L * 4 < ((int64_t)1 << 31), DWS_ERR_UNSUPPORTED,
               "wn_layer_bx6: %d channels x L=%d exceed a 2 GiB tensor per clip", C > S ? C : S, a.L);
-    DWS_CHECK(a.hsave == nullptr, DWS_ERR_UNSUPPORTED, "wn_layer_bx6: the training forward runs with precision=f32");
     if (split == WN_SPLIT_F16X3) {
+        DWS_CHECK(a.hsave == nullptr, DWS_ERR_UNSUPPORTED, "wn_layer_f16x3: the training forward runs with precision=f32 or bf16x6");
         DWS_CHECK(a.wscale != nullptr, DWS_ERR_INVALID, "wn_layer_f16x3: no weight scales");
         return launch_bx6_p<SplitF16x2>(C, S, a, log2d, s);
     }

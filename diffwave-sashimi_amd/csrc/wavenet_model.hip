@@ -281,6 +281,10 @@ struct WaveNetModel : dws_model {
         WgradArgs w{};
         w.dY = dY; w.X = X; w.addc = addc; w.addc_bstride = addc_bs;
         w.B = (int)B; w.O = O; w.C = Cc; w.L = (int)L; w.dil = dil;
+        // precision = bf16x6: the weight gradients on the bf16 matrix cores -- single-tap ones in wgrad_dma4_kernel<1> where the
+        // launch takes the 16-byte kernel, the dilated conv's in wgrad_wino_kernel<1>; the one-channel convolutions (init_conv,
+        // final_conv.2) and the direct three-tap form stay exact f32
+        w.split = (bf16x6 && O > 1 && Cc > 1) ? 1 : 0;
         const bool wino_w = T == 3 && wino_opt && wgrad_wino_supported(w);   // conv_algo covers this adjoint too
         w.nsplit = wino_w ? wgrad_wino_nsplit((int)B, O, Cc, (int)L, dil) : wgrad_mfma_nsplit((int)B, O, Cc, (int)L, T);
         DWS_TRY(wpart.ensure((size_t)w.nsplit * O * Cc * (wino_w ? 4 : T) * 4));
@@ -360,7 +364,8 @@ struct WaveNetModel : dws_model {
 
     int forward_train(const float* audio, const float* steps, float* out, hipStream_t s) override {
         DWS_CHECK(B > 0, DWS_ERR_STATE, "forward before prepare");
-        DWS_CHECK(!bf16x3 && !bf16x6 && !f16x3, DWS_ERR_UNSUPPORTED, "training runs with precision=f32 (no split-precision backward is built)");
+        DWS_CHECK(!bf16x3 && !f16x3 && (!bf16x6 || mfma_bwd), DWS_ERR_UNSUPPORTED,
+                  "training runs with precision=f32, or bf16x6 where the MFMA adjoints run (no bf16x3 / f16x3 backward is built)");
         DWS_CHECK(melBm == 0 || (melBm == B && mfma_bwd), DWS_ERR_UNSUPPORTED,
                   "mel-conditional training needs one mel per clip (got %lld for B=%lld) and the MFMA adjoints (channels %% 32 == 0)",
                   (long long)melBm, (long long)B);
@@ -512,7 +517,7 @@ struct WaveNetModel : dws_model {
             if (bwd_pack_version != commit_version) DWS_TRY(pack_bwd(s));
             TapConvArgs f{};
             f.src0 = dyb.f(); f.K0 = S; f.A = ATf.f(); f.nkg_total = S / 8; f.M = S; f.T = 1; f.dil = 1; f.sign = 1;
-            f.out = dskip.f(); f.B = nB; f.L = nL;
+            f.out = dskip.f(); f.B = nB; f.L = nL; f.split = bf16x6 ? 1 : 0;
             DWS_TRY(launch_tapconv_mfma(f, s));
         } else {
             DWS_TRY(launch_conv_t(dyb.f(), Wf.f(), dskip.f(), nB, S, S, nL, 1, 1, scale, 0, s));
@@ -532,7 +537,7 @@ struct WaveNetModel : dws_model {
                 TapConvArgs q{};
                 q.src0 = dskip.f(); q.K0 = S; q.src1 = dx_out; q.K1 = dx_out ? C : 0;
                 q.A = ATg[n].f(); q.nkg_total = (S + C) / 8; q.M = C; q.T = 1; q.dil = 1; q.sign = 1; q.epi = 1;
-                q.H = tH[n].f(); q.dH = dHb.f(); q.g = gate.f(); q.B = nB; q.L = nL;
+                q.H = tH[n].f(); q.dH = dHb.f(); q.g = gate.f(); q.B = nB; q.L = nL; q.split = bf16x6 ? 1 : 0;
                 DWS_TRY(launch_tapconv_mfma(q, s));
             } else {
                 if (dx_out) {
@@ -579,7 +584,7 @@ struct WaveNetModel : dws_model {
                 q.src0 = dHb.f(); q.K0 = 2 * C; q.A = ATd[n].f(); q.nkg_total = 6 * C / 8; q.M = C; q.T = 3; q.dil = dil;
                 q.sign = -1; q.out = dh; q.B = nB; q.L = nL;
                 if (wino_opt && tapwino_mfma_supported(C, 2 * C, dil) && ATw[n].p) {   // conv_algo covers the adjoint too
-                    q.A = ATw[n].f(); q.nkg_total = C;
+                    q.A = ATw[n].f(); q.nkg_total = C; q.split = bf16x6 ? 1 : 0;
                     DWS_TRY(launch_tapwino_mfma(q, s));
                 } else {
                     DWS_CHECK(ATd[n].p, DWS_ERR_STATE, "backward: layer %d's direct adjoint weights were not packed", n);

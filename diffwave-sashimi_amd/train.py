@@ -177,7 +177,7 @@ def train(rank, num_gpus, diffusion_cfg, model_cfg, dataset_cfg, generate_cfg, c
         raise RuntimeError("the dataset holds fewer clips than one batch")
     print("Data loaded")
     net = construct_model(dict(model_cfg)).cuda().train()
-    if precision not in (None, "f32"):      # `+engine.precision=bf16x6`: SaShiMi's GEMMs and weight gradients on the bf16 matrix cores
+    if precision not in (None, "f32"):      # `+engine.precision=bf16x6`: the split GEMMs of either backbone's step on the bf16 matrix cores
         net.set_option("precision", precision)
     print(f"{type(net).__name__} parameters: {sum(p.numel() for p in net.parameters()) / 1e6:.6f}M")   # `utils.py:76-88`
     if num_gpus > 1:

@@ -133,7 +133,9 @@ int dws_model_update_params(dws_model* m, int32_t count, const char* const* name
  *               = "bf16x6" WaveNet residual layers on the bf16 matrix cores at fp32-EQUIVALENT accuracy: every GEMM
  *                          operand as an exact 3-term bf16 split (24 significand bits), the six partial products above
  *                          2^-26 accumulated in fp32, Winograd F(2,3) form (the f32 path's algorithm and roundings).
- *                          WaveNet: inference only.  SaShiMi: the S4 block tails
+ *                          WaveNet: the residual layers in sampling and in forward_train; in training also the gate
+ *                          adjoint, dskip = Wf^T dy and the res / skip / final_conv.0 weight gradients (where L % 4 == 0),
+ *                          the dilated conv's data and weight gradients in Winograd form (any L).  SaShiMi: the S4 block tails
  *                          (all H) in sampling; in training the pointwise GEMMs and weight gradients of the step.
  *                          What "fp32-equivalent" was MEASURED to mean (tests/test_bf16x6_gpu.py, test_full_size_gpu.py,
  *                          test_split_trajectory_gpu.py): operands are carried exactly, products are exact, the fp32
@@ -145,7 +147,8 @@ int dws_model_update_params(dws_model* m, int32_t count, const char* const* name
  *                          path's error (WaveNet and SaShiMi, B = 1 .. 32, L = 16000), T = 200 trajectories within 3e-7
  *                          of the f32 path's.  Results do not depend on the batch position of a clip (bitwise).
  *                          Where no split instance exists (SaShiMi stages whose length is not a multiple of 4, channel
- *                          counts the MFMA tiling does not cover, the pooling GEMMs, 3-tap training GEMMs) the f32
+ *                          counts the MFMA tiling does not cover, the pooling GEMMs, 3-tap training GEMMs, WaveNet
+ *                          adjoints at L % 4 != 0, the one-channel convolutions, the step-embedding MLP) the f32
  *                          kernels run: the tap "split_launches" reports how many GEMM launches of the last forward ran
  *                          split and how many fell back.
  *               = "f16x3"  the same kernels with a 2-term fp16 split of power-of-two scaled operands (22 significand
@@ -178,8 +181,8 @@ int dws_model_set_condition(dws_model* m, const float* mel, int64_t Bm, int64_t 
  * (`generate.py:50`; the int64 steps of `train.py:218` are converted by the host side). */
 int dws_model_forward(dws_model* m, const float* audio, const float* steps, float* out, void* stream);
 
-/* Training path (`train.py:198-222`): both backbones, unconditional and mel-conditional, fp32 precision
- * (precision=bf16x3 returns DWS_ERR_UNSUPPORTED; SaShiMi channel counts that are not multiples of 32 train on a
+/* Training path (`train.py:198-222`): both backbones, unconditional and mel-conditional, precision f32 or bf16x6
+ * (precision=bf16x3 / f16x3 return DWS_ERR_UNSUPPORTED, as does WaveNet bf16x6 where the MFMA adjoints do not run; SaShiMi channel counts that are not multiples of 32 train on a
  * plain-FMA GEMM instead of the MFMA adjoints).
  * forward_train == forward but keeps the activations backward needs inside the model -- of ONE forward:
  * every forward_train must be followed by its backward before the next forward_train.  backward takes dLoss/d(eps)[B, out_channels, L] and produces the gradient of every RAW
