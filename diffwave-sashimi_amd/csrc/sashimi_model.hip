@@ -150,6 +150,7 @@ struct Stage {
                                  // until the run length changes (the decision depends on L and the `L` buffers only, not on B)
     DevBuf U, Uf, Y, g, x1, n2, ffu, y;
     DevBuf d2, dh, dx1, du;  // training path gradients: [B][max(2,FF) H][L], [B][H][L] x 3
+    DevBuf Gf;               // training on rocFFT: the spectrum of the block's input u, recomputed in the backward ([B][H][L+1])
 };
 
 struct FftTables {
@@ -508,19 +509,27 @@ struct SashimiModel : dws_model {
         return DWS_OK;
     }
 
-    // Can this commit generate the kernels group by group?  Training mode, every block on the fused convolution at its kernel's own
-    // length (what train_supported() asks for anyway).  DWS_S4_KERNELS_PER_BLOCK=1: the per-block chain (same-box A/B).
+    // Can this commit generate the kernels group by group?  Training mode, every block at its kernel's own length (what
+    // train_supported() asks for anyway), none on the segmented path, at least one on the fused convolution.  The blocks of
+    // stages on rocFFT (odd lengths, more than 16384 samples) keep the per-block chain (build_kernel, rocfft_conv_backward);
+    // the fused ones stack.  DWS_S4_KERNELS_PER_BLOCK=1: the per-block chain for every block (same-box A/B).
+    static bool stacks(const SLayer* l) {
+        int lg = 0;
+        return fftconv_supported(l->L, &lg);
+    }
     bool stacked_kernels_possible(hipStream_t s) {
         static const bool off = getenv("DWS_S4_KERNELS_PER_BLOCK") != nullptr;
         if (off || !keep_cauchy || getenv("DWS_SASHIMI_ROCFFT")) return false;
+        bool any = false;
         for (auto* l : all) {
             if (l->kind != L_BLOCK) continue;
-            int lg = 0;
             int64_t Lk = 0;
-            if (kernel_len(l, s, &Lk) != DWS_OK || Lk != l->L || !fftconv_supported(l->L, &lg) || stages[l->stage]->seg) return false;
+            if (kernel_len(l, s, &Lk) != DWS_OK || Lk != l->L || stages[l->stage]->seg) return false;
+            if (!stacks(l)) continue;
             if (!P("__z." + std::to_string(l->L)) || !P("__omega." + std::to_string(l->L))) return false;
+            any = true;
         }
-        return true;
+        return any;
     }
 
     // parameters -> K_f of every block, one chain per group of same-shaped blocks (s4.py:704-807, 1391-1403; build_kernel's chain)
@@ -529,6 +538,7 @@ struct SashimiModel : dws_model {
         for (auto* g : kgroups) g->layers.clear();      // (the run length may have changed since the last commit)
         for (auto* l : all) {
             if (l->kind != L_BLOCK) continue;
+            if (!stacks(l)) { l->grp = -1; continue; }    // rocFFT stage: generated by build_kernel (commit)
             KGroup* g = nullptr;
             for (auto* c : kgroups)
                 if (c->H == l->H && c->L == l->L) g = c;
@@ -704,7 +714,7 @@ struct SashimiModel : dws_model {
                         l->Ao_c6.release(); l->A1_c6.release(); l->A2_c6.release();
                     }
                 }
-                if (!kernels_stacked) { l->grp = -1; DWS_TRY(build_kernel(l, s)); }
+                if (!kernels_stacked || !stacks(l)) { l->grp = -1; DWS_TRY(build_kernel(l, s)); }
             }
         }
         if (kernels_stacked) DWS_TRY(build_kernels_stacked(s));
@@ -1252,8 +1262,8 @@ struct SashimiModel : dws_model {
         DWS_CHECK(!cond || melBm > 0, DWS_ERR_STATE, "conditional model: install the mel (set_condition) before forward_train");
         for (auto* l : all) {
             if (l->kind == L_BLOCK) {
-                DWS_CHECK(l->log2m > 0, DWS_ERR_UNSUPPORTED,
-                          "sashimi training needs the fused FFT convolution (L even, <= 16384 per stage); stage L=%d", l->L);
+                // (a stage runs the fused LDS convolution or rocFFT; the segmented path needs kernels shorter than the stage)
+                DWS_CHECK(!l->seg, DWS_ERR_UNSUPPORTED, "sashimi training does not run the segmented convolution (stage L=%d)", l->L);
                 DWS_CHECK(l->Lk == l->L, DWS_ERR_UNSUPPORTED,
                           "sashimi training runs at the kernels' own length (stage runs at %d, kernel length %d)", l->L, l->Lk);
             }
@@ -1275,6 +1285,11 @@ struct SashimiModel : dws_model {
         for (auto* l : all) {
             if (l->kind == L_BLOCK) {
                 const size_t n = (size_t)B * l->H * l->L * 4;
+                if (l->log2m == 0) {    // rocFFT stage: padded rows, spectra, plans (prepare() made them for this B already)
+                    Stage* st = stages[l->stage];
+                    DWS_TRY(ensure_rocfft_stage(st));
+                    DWS_TRY(st->Gf.ensure((size_t)B * st->H * (st->L + 1) * 8));
+                }
                 DWS_TRY(l->t_u.ensure(n)); DWS_TRY(l->t_a.ensure(n)); DWS_TRY(l->t_o.ensure(2 * n));
                 DWS_TRY(l->t_g.ensure(n)); DWS_TRY(l->t_ge.ensure((size_t)FF * n));
                 DWS_TRY(l->t_x1.ensure(n)); DWS_TRY(l->t_n2.ensure(n)); DWS_TRY(l->t_f1.ensure((size_t)FF * n));
@@ -1330,13 +1345,17 @@ struct SashimiModel : dws_model {
                     DWS_TRY(launch_ln(x, P(p + ".norm1.m"), P(p + ".norm1.s"), part_t.f() + l->pt_off, pt_total, l->t_u.f(), nB, H,
                                       Ls, (size_t)Ls, s));
                 ln1_done = false;
-                FftTables* t = tables[l->log2m];
-                FftConvArgs fa{};
-                fa.u = l->t_u.f(); fa.g = l->t_g.f(); fa.pre = l->t_a.f(); fa.D = P(p + ".layer.D");
-                fa.tw = (const c2*)t->tw.p; fa.twp = (const c2*)t->twp.p;
-                fa.kfa = (const c2*)l->kfa_v; fa.kfb = (const c2*)l->kfb_v; fa.kfs = (const c2*)l->kfs_v;
-                fa.B = nB; fa.H = H; fa.L = Ls;
-                DWS_TRY(launch_fftconv(l->log2m, fa, s));
+                if (l->log2m > 0) {
+                    FftTables* t = tables[l->log2m];
+                    FftConvArgs fa{};
+                    fa.u = l->t_u.f(); fa.g = l->t_g.f(); fa.pre = l->t_a.f(); fa.D = P(p + ".layer.D");
+                    fa.tw = (const c2*)t->tw.p; fa.twp = (const c2*)t->twp.p;
+                    fa.kfa = (const c2*)l->kfa_v; fa.kfb = (const c2*)l->kfb_v; fa.kfs = (const c2*)l->kfs_v;
+                    fa.B = nB; fa.H = H; fa.L = Ls;
+                    DWS_TRY(launch_fftconv(l->log2m, fa, s));
+                } else {
+                    DWS_TRY(rocfft_conv_forward(l, st, s));
+                }
                 // LN2(x1) out of the epilogue that produces x1 when the tile holds every channel (H = 128): the separate
                 // LayerNorm pass (read x1, write n2) becomes one extra store
                 bool ln2_done = false;
@@ -1424,7 +1443,7 @@ struct SashimiModel : dws_model {
     }
 
     int kernel_backward(SLayer* l, const float* da, hipStream_t s) {
-        const int H = l->H, Ls = l->L, Lh = Ls / 2 + 1, N = NS, nB = (int)B;
+        const int H = l->H, Ls = l->L, Lh = Ls / 2 + 1, nB = (int)B;
         const int M = 1 << l->log2m, Nf = 2 * M;
         if (kernels_stacked && l->grp >= 0) {
             // this block's spectrum gradient into its rows of the group's stack; the rest of the chain runs once per group
@@ -1443,7 +1462,6 @@ struct SashimiModel : dws_model {
             if (--g->pending == 0) DWS_TRY(group_backward(g, s));
             return DWS_OK;
         }
-        const std::string k = l->prefix + ".layer.kernel.kernel";
         FftTables* t = tables[l->log2m];
         const int nbs = std::max(1, std::min(nB, ceil_div(512, H)));
         const int bchunk = ceil_div(nB, nbs);
@@ -1463,6 +1481,14 @@ struct SashimiModel : dws_model {
         DWS_TRY(launch_s4_twosided_pow2_bwd(dKt.f(), dkt.f(), G(l->prefix + ".layer.D"), H, Ls, Nf,
                                             1.f / ((float)Nf * (float)Ls), 1.f / (float)Nf, s));
         DWS_TRY(fft.exec(0, Ls, 2 * H, dkt.p, dkf.p, s));
+        return kernel_params_backward(l, Ls, s);
+    }
+
+    // The chain behind the tap gradient of one block: dkf = R2C(dk) [2][H][Lk/2+1] -> Woodbury -> Cauchy -> s4_prep adjoints ->
+    // the gradients of C, B, P, inv_w_real, w_imag, log_dt
+    int kernel_params_backward(SLayer* l, int Lk, hipStream_t s) {
+        const int H = l->H, Lh = Lk / 2 + 1, N = NS;
+        const std::string k = l->prefix + ".layer.kernel.kernel";
         // v, w dt, dt, r of this block: kept by build_kernel when this commit already ran in training mode, else regenerated
         const bool cached = l->cache_version == commit_version && l->t_cr.p;
         DevBuf& bv = cached ? l->t_cv : cv;
@@ -1474,7 +1500,7 @@ struct SashimiModel : dws_model {
         DWS_TRY(cgw.ensure((size_t)6 * H * N * 8));
         const int nparts = ceil_div(Lh, 256);
         DWS_TRY(cpdt.ensure((size_t)H * nparts * 4));
-        const float* z = P("__z." + std::to_string(Ls));
+        const float* z = P("__z." + std::to_string(Lk));
         if (!cached) {
             DWS_TRY(bv.ensure((size_t)6 * H * N * 8));
             DWS_TRY(bw.ensure((size_t)H * N * 8));
@@ -1484,13 +1510,61 @@ struct SashimiModel : dws_model {
                                    P(k + ".log_dt"), bv.f(), bw.f(), bd.f(), H, N, s));
             DWS_TRY(launch_cauchy_sym_fwd_bcast(bv.f(), z, bw.f(), br.f(), 6 * H, N, Lh, H, s));
         }
-        DWS_TRY(launch_s4_woodbury_bwd(br.f(), P("__omega." + std::to_string(Ls)), bd.f(), dkf.f(), cgr.f(), cpdt.f(), H,
-                                       Lh, (Ls % 2) == 0, s));
+        DWS_TRY(launch_s4_woodbury_bwd(br.f(), P("__omega." + std::to_string(Lk)), bd.f(), dkf.f(), cgr.f(), cpdt.f(), H,
+                                       Lh, (Lk % 2) == 0, s));
         DWS_TRY(launch_cauchy_sym_bwd_bcast(bv.f(), z, bw.f(), cgr.f(), cgv.f(), cgw.f(), 6 * H, N, Lh, H, s));
         DWS_TRY(launch_s4_prep_bwd(P(k + ".C"), P(k + ".B"), P(k + ".P"), P(k + ".inv_w_real"), P(k + ".w_imag"),
                                    P(k + ".log_dt"), cgv.f(), cgw.f(), cpdt.f(), nparts, G(k + ".C"), G(k + ".B"), G(k + ".P"),
                                    G(k + ".inv_w_real"), G(k + ".w_imag"), G(k + ".log_dt"), H, N, s));
         return DWS_OK;
+    }
+
+    // S4 convolution of a block whose stage runs on rocFFT (odd length, or more than 16384 samples), training forward: the
+    // sampling path's R2C -> spectrum multiply -> C2R (run_block) on the padded rows of u = t_u, whose epilogue also keeps the
+    // pre-activation a in t_a.  t_u stays unpadded so that the previous block's epilogue can still write it (ln1_done); the
+    // padded rows are a copy.
+    int rocfft_conv_forward(SLayer* l, Stage* st, hipStream_t s) {
+        ProfileScope ps("long_stage_fwd", s);
+        const int H = l->H, Ls = l->L, nB = (int)B, rows = nB * H;
+        DWS_TRY(launch_pad_rows(l->t_u.f(), st->U.f(), rows, Ls, s));
+        {
+            ProfileScope ps("rocfft_r2c", s);
+            DWS_TRY(fft.exec(0, 2 * Ls, rows, st->U.p, st->Uf.p, s));
+        }
+        DWS_TRY(launch_spec_mul(st->Uf.f(), l->Kf.f(), nB, H, Ls + 1, s));
+        {
+            ProfileScope ps("rocfft_c2r", s);
+            DWS_TRY(fft.exec(1, 2 * Ls, rows, st->Uf.p, st->Y.p, s));
+        }
+        return launch_s4_post_train(st->Y.f(), l->t_u.f(), P(l->prefix + ".layer.D"), l->t_a.f(), l->t_g.f(), nB, H, Ls, s);
+    }
+
+    // Its adjoint, given da [B][H][L]: du = C2R(conj(K_f) dA) / 2L + D da into `du`, d fc_t(e) = sum_l du into dpt, dD, and the
+    // kernel parameters' gradients through dK_f = sum_b conj(U_b) dA_b -> C2R -> the two-sided assembly backwards -> the chain of
+    // kernel_params_backward.  U_f is recomputed here (one R2C of the padded t_u) instead of being kept from the forward: keeping
+    // it would cost B H (L+1) 8 bytes per block for the whole step (90 MB per top-stage block of ljspeech_harder, twelve of them)
+    // to save one transform of the same size, and it would need an out-of-place spectrum multiply in the forward.
+    int rocfft_conv_backward(SLayer* l, Stage* st, const float* da, float* du, hipStream_t s) {
+        ProfileScope ps("long_stage_bwd", s);
+        const int H = l->H, Ls = l->L, Lf = Ls + 1, nB = (int)B, rows = nB * H;
+        const int Lk = l->Lk, Lt = std::min(Ls, Lk), Lh = Lk / 2 + 1;
+        DWS_TRY(dKf.ensure((size_t)H * Lf * 8));
+        DWS_TRY(dKt.ensure((size_t)H * 2 * Ls * 4));
+        DWS_TRY(dkt.ensure((size_t)2 * H * Lk * 4));
+        DWS_TRY(dkf.ensure((size_t)2 * H * Lh * 8));
+        DWS_TRY(launch_pad_rows(l->t_u.f(), st->U.f(), rows, Ls, s));
+        DWS_TRY(fft.exec(0, 2 * Ls, rows, st->U.p, st->Gf.p, s));       // U
+        DWS_TRY(launch_pad_rows(da, st->U.f(), rows, Ls, s));
+        DWS_TRY(fft.exec(0, 2 * Ls, rows, st->U.p, st->Uf.p, s));       // dA
+        DWS_TRY(launch_conv_adjoint_spec(st->Gf.f(), st->Uf.f(), l->Kf.f(), dKf.f(), nB, H, Lf, s));
+        DWS_TRY(fft.exec(1, 2 * Ls, rows, st->Uf.p, st->Y.p, s));
+        DWS_TRY(launch_conv_adjoint_epi(st->Y.f(), da, P(l->prefix + ".layer.D"), du, dpt.f() + l->pt_off, (int)pt_total, nB, H, Ls, s));
+        // dK = C2R(dK_f) / 2L; K = [k0 | 0 | reversed k1] / Lk (s4_twosided_kernel); dD[h] = sum u da = dK[h][0]
+        DWS_TRY(fft.exec(1, 2 * Ls, H, dKf.p, dKt.p, s));
+        DWS_TRY(launch_s4_twosided_bwd(dKt.f(), dkt.f(), G(l->prefix + ".layer.D"), H, Ls, Lk, Lt,
+                                       1.f / ((float)(2 * Ls) * (float)Lk), 1.f / (float)(2 * Ls), s));
+        DWS_TRY(fft.exec(0, Lk, 2 * H, dkt.p, dkf.p, s));
+        return kernel_params_backward(l, Lk, s);
     }
 
     // (dm, ds) of a LayerNorm from its adjoint's per-block partials [2][nblk].  Every adjoint of a backward writes its own slot of
@@ -1610,19 +1684,23 @@ struct SashimiModel : dws_model {
                 DWS_TRY(wgrad(st->d2.f(), l->t_g.f(), 2 * H, H, Ls, 0, G(p + ".layer.output_linear.0.weight"),
                               G(p + ".layer.output_linear.0.bias"), s));
                 // a = conv(u, K) + D u: du = conv^T(da) + D da; kernel parameters from corr(u, da)
-                FftTables* t = tables[l->log2m];
-                FftConvArgs fa{};
-                fa.u = st->dh.f(); fa.g = st->du.f(); fa.D = P(p + ".layer.D"); fa.conj_k = 1; fa.no_act = 1;
-                fa.tw = (const c2*)t->tw.p; fa.twp = (const c2*)t->twp.p;
-                fa.kfa = (const c2*)l->kfa_v; fa.kfb = (const c2*)l->kfb_v; fa.kfs = (const c2*)l->kfs_v;
-                fa.B = nB; fa.H = H; fa.L = Ls;
-                // d fc_t(e)[b, h] = sum_l du[b, h, l] leaves with the row (a workgroup owns it) where the plan allows
-                const bool rs_fused = fftconv_rowsum_supported(l->log2m) && getenv("DWS_NO_ROWSUM_FUSION") == nullptr;
-                if (rs_fused) { fa.rowsum = dpt.f() + l->pt_off; fa.rowsum_bstride = (int)pt_total; }
-                DWS_TRY(launch_fftconv(l->log2m, fa, s));
-                DWS_TRY(kernel_backward(l, st->dh.f(), s));
+                if (l->log2m == 0) {    // rocFFT stage (rocfft_conv_backward also writes d fc_t(e) and every S4 kernel gradient)
+                    DWS_TRY(rocfft_conv_backward(l, st, st->dh.f(), st->du.f(), s));
+                } else {
+                    FftTables* t = tables[l->log2m];
+                    FftConvArgs fa{};
+                    fa.u = st->dh.f(); fa.g = st->du.f(); fa.D = P(p + ".layer.D"); fa.conj_k = 1; fa.no_act = 1;
+                    fa.tw = (const c2*)t->tw.p; fa.twp = (const c2*)t->twp.p;
+                    fa.kfa = (const c2*)l->kfa_v; fa.kfb = (const c2*)l->kfb_v; fa.kfs = (const c2*)l->kfs_v;
+                    fa.B = nB; fa.H = H; fa.L = Ls;
+                    // d fc_t(e)[b, h] = sum_l du[b, h, l] leaves with the row (a workgroup owns it) where the plan allows
+                    const bool rs_fused = fftconv_rowsum_supported(l->log2m) && getenv("DWS_NO_ROWSUM_FUSION") == nullptr;
+                    if (rs_fused) { fa.rowsum = dpt.f() + l->pt_off; fa.rowsum_bstride = (int)pt_total; }
+                    DWS_TRY(launch_fftconv(l->log2m, fa, s));
+                    DWS_TRY(kernel_backward(l, st->dh.f(), s));
+                    if (!rs_fused) DWS_TRY(launch_rowsum_bc(st->du.f(), dpt.f() + l->pt_off, pt_total, nB, H, Ls, s));
+                }
                 // u = LN1(x) + fc_t(e): dx = dx1 + LN'(du)
-                if (!rs_fused) DWS_TRY(launch_rowsum_bc(st->du.f(), dpt.f() + l->pt_off, pt_total, nB, H, Ls, s));
                 DWS_TRY(launch_ln_bwd(x, st->du.f(), P(p + ".norm1.m"), P(p + ".norm1.s"), st->dx1.f(), din, written[e.in_node],
                                       ln_slot(), nB, H, Ls, s));
                 DWS_TRY(ln_scalars(p + ".norm1", nblk, s));

@@ -33,4 +33,14 @@ int launch_s4_woodbury_bwd(const float* r, const float* omega, const float* dt, 
 int launch_s4_prep_bwd(const float* C, const float* Bp, const float* P, const float* iwr, const float* wim,
                        const float* log_dt, const float* gv, const float* gw6, const float* part_dt, int nparts, float* gC,
                        float* gB, float* gP, float* giwr, float* gwim, float* glogdt, int H, int N, hipStream_t s);
+
+// sashimi_train_long.hip: training of the blocks whose stage runs on rocFFT (odd lengths, more than 16384 samples)
+int launch_pad_rows(const float* in, float* out, int rows, int L, hipStream_t s);
+int launch_s4_post_train(const float* yc, const float* u, const float* D, float* pre, float* g, int B, int H, int L,
+                         hipStream_t s);
+int launch_conv_adjoint_spec(const float* uf, float* daf, const float* kf, float* dkf, int B, int H, int Lf, hipStream_t s);
+int launch_conv_adjoint_epi(const float* yc, const float* da, const float* D, float* du, float* rowsum, int rs_bstride, int B,
+                            int H, int L, hipStream_t s);
+int launch_s4_twosided_bwd(const float* dK, float* dk, float* dD, int H, int L, int Lk, int Lt, float sc, float scD,
+                           hipStream_t s);
 }  // namespace dws
