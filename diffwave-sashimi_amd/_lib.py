@@ -11,6 +11,7 @@ LIB_PATH = os.environ.get("DWS_LIB") or os.path.join(HERE, "libdws.so")
 DWS_OK, DWS_ERR_INVALID, DWS_ERR_UNSUPPORTED, DWS_ERR_HIP, DWS_ERR_STATE = 0, -1, -2, -3, -4
 DWS_KIND_WAVENET, DWS_KIND_SASHIMI = 1, 2
 DWS_MAX_POOL = 8
+DWS_SAMPLER_DDPM, DWS_SAMPLER_DDIM = 0, 1
 
 c_f32p = ctypes.c_void_p  # device pointers travel as integers
 
@@ -79,6 +80,9 @@ _SIGS = {
                                          ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float),
                                          ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_uint64,
                                          ctypes.c_int32, ctypes.c_void_p]),
+    "dws_sampler_run_schedule": (ctypes.c_int, [ctypes.c_void_p, c_f32p, ctypes.c_int32, ctypes.c_int32,
+                                                ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float), c_f32p,
+                                                ctypes.c_uint64, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p]),
     "dws_mel_spectrogram": (ctypes.c_int, [c_f32p, ctypes.c_int64, ctypes.c_int64, c_f32p, c_f32p, ctypes.c_int32,
                                            ctypes.c_int32, ctypes.c_int32, ctypes.c_float, c_f32p, ctypes.c_void_p]),
     "dws_gemm_bf16x6": (ctypes.c_int, [c_f32p] * 3 + [ctypes.c_int64] * 3 + [ctypes.c_void_p]),

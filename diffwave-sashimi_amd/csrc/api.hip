@@ -8,6 +8,8 @@ int sampler_run(dws_model* m, float* x, const float* alpha, const float* alpha_b
                 const float* noise, uint64_t seed, int init_from_seed, int use_graph, hipStream_t s);
 int sampler_steps(dws_model* m, float* x, const float* alpha, const float* alpha_bar, const float* sigma, int T,
                   int t_start, int n_steps, uint64_t seed, int use_graph, hipStream_t s);
+int sampler_run_schedule(dws_model* m, float* x, int kind, int S, const float* net_steps, const float* coef,
+                         const float* noise, uint64_t seed, int init_from_seed, int use_graph, hipStream_t s);
 }  // namespace dws
 
 dws_model::~dws_model() {
@@ -27,6 +29,8 @@ dws_model::~dws_model() {
 void dws_model::drop_graph() {
     if (smp_graph) hipGraphExecDestroy(smp_graph);
     smp_graph = nullptr;
+    if (sch_graph) hipGraphExecDestroy(sch_graph);
+    sch_graph = nullptr;
 }
 
 dws::ParamSpec* dws_model::add_param(const std::string& name, std::vector<int64_t> shape, int dtype) {
@@ -398,6 +402,13 @@ int dws_model_read_tap(dws_model* m, const char* tap, float* dst, int64_t capaci
         DWS_HIP(hipMemcpyAsync(dst, m->smp_eps.p, (size_t)n * 4, hipMemcpyDeviceToDevice, (hipStream_t)stream));
         return DWS_OK;
     }
+    if (std::strcmp(tap, "sampler_graphs") == 0) {  // number of sampler graphs this model has instantiated (one float)
+        DWS_CHECK(capacity >= 1, DWS_ERR_INVALID, "tap buffer too small");
+        const float v = (float)m->graphs_made;
+        DWS_HIP(hipMemcpyAsync(dst, &v, 4, hipMemcpyHostToDevice, (hipStream_t)stream));
+        DWS_HIP(hipStreamSynchronize((hipStream_t)stream));
+        return DWS_OK;
+    }
     return m->read_tap(tap, dst, capacity, (hipStream_t)stream);
 }
 
@@ -414,6 +425,14 @@ int dws_sampler_steps(dws_model* m, float* x, const float* alpha, const float* a
     DWS_CHECK(m && x, DWS_ERR_INVALID, "dws_sampler_steps: null argument");
     return dws::sampler_steps(m, x, alpha, alpha_bar, sigma, T, t_start, n_steps, seed, use_graph,
                               (hipStream_t)stream);
+}
+
+int dws_sampler_run_schedule(dws_model* m, float* x, int32_t kind, int32_t S, const float* net_steps,
+                             const float* coef, const float* noise, uint64_t seed, int32_t init_from_seed,
+                             int32_t use_graph, void* stream) {
+    DWS_CHECK(m && x, DWS_ERR_INVALID, "dws_sampler_run_schedule: null argument");
+    return dws::sampler_run_schedule(m, x, kind, S, net_steps, coef, noise, seed, init_from_seed, use_graph,
+                                     (hipStream_t)stream);
 }
 
 }  // extern "C"

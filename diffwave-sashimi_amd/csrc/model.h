@@ -101,6 +101,36 @@ struct PrepBatch {
     }
 };
 
+int launch_iota_f32(float* out, int n, hipStream_t s);   // wavenet_kernels.hip
+
+// Key of a sampler step table: the step values it holds (null steps = t = 0..T-1), compared bit for bit.
+struct StepKey {
+    std::vector<float> v;
+    bool valid = false;
+    bool same(int T, const float* steps) const {
+        if (!valid || (int)v.size() != T) return false;
+        if (steps) return std::memcmp(v.data(), steps, (size_t)T * 4) == 0;
+        for (int t = 0; t < T; ++t)
+            if (v[t] != (float)t) return false;
+        return true;
+    }
+    // write the step values into the device array `dev` [T] and remember them
+    int upload(int T, const float* steps, float* dev, hipStream_t s) {
+        valid = false;
+        if (steps) {
+            v.assign(steps, steps + T);
+            DWS_HIP(hipMemcpyAsync(dev, v.data(), (size_t)T * 4, hipMemcpyHostToDevice, s));
+            DWS_HIP(hipStreamSynchronize(s));   // `v` is rewritten by the next rebuild
+        } else {
+            v.resize((size_t)T);
+            for (int t = 0; t < T; ++t) v[t] = (float)t;
+            DWS_TRY(launch_iota_f32(dev, T, s));
+        }
+        valid = true;
+        return DWS_OK;
+    }
+};
+
 struct ParamSpec {
     std::string name;
     std::vector<int64_t> shape;
@@ -154,6 +184,26 @@ struct dws_model {
     const void* g_x = nullptr;
     const void* g_noise = nullptr;
     uint64_t g_seed = 0;
+    // few-step sampler (dws_sampler_run_schedule): tables, state, x and graph of its own -- the two entry points never
+    // replay each other's graph.  Its graph updates sch_x in place and reads the seed from sch_state, so neither the
+    // caller's x nor the seed is baked in.
+    dws::DevBuf sch_tables;               // DDPM [3][S] c1, c2, sigma; DDIM [5][S] k1 .. k5
+    std::vector<float> sch_host_tables;   // host copy of what is resident (upload skipped when identical)
+    dws::DevBuf sch_state;                // int32 step index, int32 finished update blocks, uint64 Philox seed
+    dws::DevBuf sch_x;                    // [B, C, L]
+    hipGraphExec_t sch_graph = nullptr;
+    struct SchKey {
+        int64_t B, L;
+        int S, kind, vec;
+        const void *tables, *noise, *eps, *x, *state;
+        uint64_t table_gen;
+        bool operator==(const SchKey& o) const {
+            return B == o.B && L == o.L && S == o.S && kind == o.kind && vec == o.vec && tables == o.tables &&
+                   noise == o.noise && eps == o.eps && x == o.x && state == o.state && table_gen == o.table_gen;
+        }
+    } sch_key{};
+    uint64_t step_table_gen = 0;          // bumped by every step-table rebuild (build_step_table)
+    int64_t graphs_made = 0;              // tap "sampler_graphs": graphs instantiated by either entry point
 
     // ---- staged gradient hand-over (data-parallel overlap, dws_model_set_grad_sinks): the host names a destination and a
     // GROUP (its all-reduce bucket) per parameter; backward() copies a group's gradients to their destinations (one launch)
@@ -193,8 +243,9 @@ struct dws_model {
     virtual int set_condition(const float* mel, int64_t Bm, int64_t Tmel, hipStream_t s) = 0;
     // steps may be null only while step_idx is set (sampler): the step-only terms then come from the step table
     virtual int forward(const float* audio, const float* steps, float* out, hipStream_t s) = 0;
-    // evaluate everything that depends on the diffusion step only for t = 0..T-1 (kept until the weights or T change)
-    virtual int build_step_table(int T, hipStream_t s) = 0;
+    // evaluate everything that depends on the diffusion step only, at T steps: the HOST values `steps` [T], or
+    // t = 0..T-1 when null (kept while the weights and the step values stay)
+    virtual int build_step_table(int T, const float* steps, hipStream_t s) = 0;
     virtual int read_tap(const char* tap, float* dst, int64_t capacity, hipStream_t s) = 0;
     // training path: forward that keeps what backward needs; backward fills ParamSpec::grad of every parameter
     virtual int forward_train(const float* audio, const float* steps, float* out, hipStream_t s);

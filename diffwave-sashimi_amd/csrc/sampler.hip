@@ -46,6 +46,13 @@ __device__ __forceinline__ void normal4(uint64_t seed, uint32_t t, uint64_t g, f
 // sampler state in device memory: [0] the step index t, [1] number of update blocks that have finished this step
 __global__ void smp_set_step_kernel(int* t_dev, int t) { t_dev[0] = t; t_dev[1] = 0; }
 
+// the few-step sampler's state also holds the Philox seed ([2..3]): its captured step bakes in no seed
+__global__ void smp_set_state_kernel(int* st, int t, uint64_t seed) {
+    st[0] = t;
+    st[1] = 0;
+    *reinterpret_cast<uint64_t*>(st + 2) = seed;
+}
+
 __global__ void smp_fill_normal_kernel(float* __restrict__ x, size_t n, uint64_t seed, uint32_t stream_id) {
     for (size_t g = (size_t)blockIdx.x * blockDim.x + threadIdx.x; g * 4 < n; g += (size_t)gridDim.x * blockDim.x) {
         float z[4];
@@ -63,11 +70,14 @@ __global__ void smp_fill_normal_kernel(float* __restrict__ x, size_t n, uint64_t
 // tests/test_sampler_gpu.py::test_step_table_sampler_equals_the_per_step_loop: 1 ulp on most elements once t > 0).
 // The last block to finish moves the step index on (t <- t - 1): every block has read t by then, and the next kernel
 // that reads it is stream-ordered behind this one -- no separate one-thread launch per step.
+// seed_dev non-null (few-step sampler): the Philox seed is read from device memory instead of `seed`.
 __global__ void smp_update_kernel(float* __restrict__ x, const float* __restrict__ eps,
                                   const float* __restrict__ tables, int* __restrict__ t_dev,
-                                  const float* __restrict__ noise, uint64_t seed, size_t n, int T) {
+                                  const float* __restrict__ noise, uint64_t seed, const uint64_t* seed_dev, size_t n,
+                                  int T) {
 #pragma clang fp contract(off)
     const int t = __builtin_amdgcn_readfirstlane(*(volatile int*)t_dev);
+    if (seed_dev) seed = *(const volatile uint64_t*)seed_dev;
     const float c1 = tables[t], c2 = tables[T + t], sg = tables[2 * T + t];
     const float* nz = noise ? noise + (size_t)t * n : nullptr;
     for (size_t g = (size_t)blockIdx.x * blockDim.x + threadIdx.x; g * 4 < n; g += (size_t)gridDim.x * blockDim.x) {
@@ -98,8 +108,77 @@ __global__ void smp_update_kernel(float* __restrict__ x, const float* __restrict
     }
 }
 
-static int upload_tables(dws_model* m, const float* alpha, const float* alpha_bar, const float* sigma, int T,
-                         hipStream_t s) {
+// DDIM step (Song et al., ICLR 2021, eq. 12) with k[5][S] = k1 .. k5 of sampling.ddim_coefficients, per element:
+//   u = (x - k1 eps) / k2;  x = k3 u + k4 eps;  if s > 0 and k5 > 0: x = x + k5 z
+// every product, difference, quotient and sum rounded once in this order (contraction off, plain operators, as in
+// smp_update_kernel).  z: noise[s] or Philox (seed, s) in normal4's layout; the seed comes from the state (st + 2).
+// VEC: every group of 4 is in range and x / eps / noise are 16-byte aligned -> float4 loads and stores.
+template <bool VEC>
+__global__ void smp_ddim_kernel(float* __restrict__ x, const float* __restrict__ eps, const float* __restrict__ k,
+                                int* __restrict__ st, const float* __restrict__ noise, size_t n, int S) {
+#pragma clang fp contract(off)
+    const int s = __builtin_amdgcn_readfirstlane(*(volatile int*)st);
+    const uint64_t seed = *(const volatile uint64_t*)(st + 2);
+    const float k1 = k[s], k2 = k[S + s], k3 = k[2 * S + s], k4 = k[3 * S + s], k5 = k[4 * S + s];
+    const bool add = s > 0 && k5 > 0.f;
+    const float* nz = noise ? noise + (size_t)s * n : nullptr;
+    for (size_t g = (size_t)blockIdx.x * blockDim.x + threadIdx.x; g * 4 < n; g += (size_t)gridDim.x * blockDim.x) {
+        float xv[4] = {0.f, 0.f, 0.f, 0.f}, ev[4] = {0.f, 0.f, 0.f, 0.f}, z[4] = {0.f, 0.f, 0.f, 0.f};
+        if (VEC) {
+            const float4 a = reinterpret_cast<const float4*>(x)[g], e = reinterpret_cast<const float4*>(eps)[g];
+            xv[0] = a.x; xv[1] = a.y; xv[2] = a.z; xv[3] = a.w;
+            ev[0] = e.x; ev[1] = e.y; ev[2] = e.z; ev[3] = e.w;
+            if (add && nz) {
+                const float4 q = reinterpret_cast<const float4*>(nz)[g];
+                z[0] = q.x; z[1] = q.y; z[2] = q.z; z[3] = q.w;
+            }
+        } else {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const size_t i = g * 4 + j;
+                if (i >= n) break;
+                xv[j] = x[i]; ev[j] = eps[i];
+                if (add && nz) z[j] = nz[i];
+            }
+        }
+        if (add && !nz) normal4(seed, (uint32_t)s, g, z);
+        float r[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const float p = k1 * ev[j];
+            const float d = xv[j] - p;
+            const float u = d / k2;
+            const float a = k3 * u;
+            const float b = k4 * ev[j];
+            float v = a + b;
+            if (add) {
+                const float q = k5 * z[j];
+                v = v + q;
+            }
+            r[j] = v;
+        }
+        if (VEC) {
+            reinterpret_cast<float4*>(x)[g] = make_float4(r[0], r[1], r[2], r[3]);
+        } else {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const size_t i = g * 4 + j;
+                if (i >= n) break;
+                x[i] = r[j];
+            }
+        }
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        if (atomicAdd(reinterpret_cast<unsigned*>(st + 1), 1u) == gridDim.x - 1) {
+            st[1] = 0;
+            st[0] = s - 1;
+        }
+    }
+}
+
+// c1 = (1 - alpha) / sqrt(1 - alpha_bar), c2 = sqrt(alpha), sigma: [3][T]
+static std::vector<float> ddpm_table(const float* alpha, const float* alpha_bar, const float* sigma, int T) {
     std::vector<float> h(3 * (size_t)T);
     for (int t = 0; t < T; ++t) {
         // fp32 scalar arithmetic in the reference's order (`generate.py:52`)
@@ -109,6 +188,12 @@ static int upload_tables(dws_model* m, const float* alpha, const float* alpha_ba
         h[T + t] = sqrtf(alpha[t]);
         h[2 * T + t] = sigma[t];
     }
+    return h;
+}
+
+static int upload_tables(dws_model* m, const float* alpha, const float* alpha_bar, const float* sigma, int T,
+                         hipStream_t s) {
+    std::vector<float> h = ddpm_table(alpha, alpha_bar, sigma, T);
     // the device copy is keyed on the table CONTENTS (same T with another beta schedule must not reuse it)
     if (m->smp_T == T && m->smp_host_tables == h) return DWS_OK;
     DWS_TRY(m->smp_tables.ensure(h.size() * 4));
@@ -130,7 +215,19 @@ static int one_step(dws_model* m, float* x, const float* noise, uint64_t seed, i
     DWS_TRY(st);
     const int blocks = (int)std::min<size_t>(ceil_div(n, 4 * 256), 4096);
     hipLaunchKernelGGL(smp_update_kernel, dim3(blocks), dim3(256), 0, s, x, m->smp_eps.f(), m->smp_tables.f(), t_dev,
-                       noise, seed, n, T);
+                       noise, seed, (const uint64_t*)nullptr, n, T);
+    return DWS_OK;
+}
+
+// The caller's stream may be the legacy null stream, which cannot be
+// captured: capture and replay on an engine-owned stream that is ordered
+// after / before the caller's stream with events.
+static int ensure_capture_stream(dws_model* m) {
+    if (!m->smp_stream) {
+        DWS_HIP(hipStreamCreateWithFlags(&m->smp_stream, hipStreamNonBlocking));
+        DWS_HIP(hipEventCreateWithFlags(&m->smp_ev_in, hipEventDisableTiming));
+        DWS_HIP(hipEventCreateWithFlags(&m->smp_ev_out, hipEventDisableTiming));
+    }
     return DWS_OK;
 }
 
@@ -144,7 +241,7 @@ static int run_steps(dws_model* m, float* x, int T, int t_start, int n_steps, co
     const size_t n = (size_t)m->B * m->d.out_channels * m->L;
     DWS_TRY(m->smp_eps.ensure(n * 4));
     m->smp_eps_B = m->B; m->smp_eps_L = m->L;
-    DWS_TRY(m->build_step_table(T, s));   // step-only part of the network for t = 0..T-1 (kept while weights and T stay)
+    DWS_TRY(m->build_step_table(T, nullptr, s));   // step-only part of the network for t = 0..T-1 (kept while weights and T stay)
     int* t_dev = static_cast<int*>(m->smp_state.p);
 
     if (!use_graph) {
@@ -153,14 +250,7 @@ static int run_steps(dws_model* m, float* x, int T, int t_start, int n_steps, co
         DWS_HIP(hipGetLastError());
         return DWS_OK;
     }
-    // The caller's stream may be the legacy null stream, which cannot be
-    // captured: capture and replay on an engine-owned stream that is ordered
-    // after / before the caller's stream with events.
-    if (!m->smp_stream) {
-        DWS_HIP(hipStreamCreateWithFlags(&m->smp_stream, hipStreamNonBlocking));
-        DWS_HIP(hipEventCreateWithFlags(&m->smp_ev_in, hipEventDisableTiming));
-        DWS_HIP(hipEventCreateWithFlags(&m->smp_ev_out, hipEventDisableTiming));
-    }
+    DWS_TRY(ensure_capture_stream(m));
     hipStream_t cs = m->smp_stream;
     DWS_HIP(hipEventRecord(m->smp_ev_in, s));
     DWS_HIP(hipStreamWaitEvent(cs, m->smp_ev_in, 0));
@@ -181,6 +271,7 @@ static int run_steps(dws_model* m, float* x, int T, int t_start, int n_steps, co
         e = hipGraphInstantiate(&m->smp_graph, graph, nullptr, nullptr, 0);
         hipGraphDestroy(graph);
         DWS_HIP(e);
+        ++m->graphs_made;
         m->g_B = m->B; m->g_L = m->L; m->g_T = T; m->g_x = x; m->g_noise = noise; m->g_seed = seed;
     }
     for (int i = 0; i < n_steps; ++i) DWS_HIP(hipGraphLaunch(m->smp_graph, cs));
@@ -207,6 +298,117 @@ int sampler_steps(dws_model* m, float* x, const float* alpha, const float* alpha
     // re-uploaded only when the coefficients differ from the resident ones (3T host flops per call)
     DWS_TRY(upload_tables(m, alpha, alpha_bar, sigma, T, s));
     return run_steps(m, x, T, t_start, n_steps, nullptr, seed, use_graph, s);
+}
+
+// ---- few-step samplers (dws_sampler_run_schedule) ----
+// One reverse step of the schedule: forward at row *st of the step table, then the DDPM or DDIM update.
+static int schedule_step(dws_model* m, float* x, int kind, int S, const float* noise, bool vec, hipStream_t s) {
+    const size_t n = (size_t)m->B * m->d.out_channels * m->L;
+    int* st = static_cast<int*>(m->sch_state.p);
+    m->step_idx = st;
+    const int rc = m->forward(x, nullptr, m->smp_eps.f(), s);
+    m->step_idx = nullptr;
+    DWS_TRY(rc);
+    const int blocks = (int)std::min<size_t>(ceil_div(n, 4 * 256), 4096);
+    if (kind == DWS_SAMPLER_DDPM)
+        hipLaunchKernelGGL(smp_update_kernel, dim3(blocks), dim3(256), 0, s, x, m->smp_eps.f(), m->sch_tables.f(), st,
+                           noise, (uint64_t)0, reinterpret_cast<const uint64_t*>(st + 2), n, S);
+    else if (vec)
+        hipLaunchKernelGGL(smp_ddim_kernel<true>, dim3(blocks), dim3(256), 0, s, x, m->smp_eps.f(), m->sch_tables.f(),
+                           st, noise, n, S);
+    else
+        hipLaunchKernelGGL(smp_ddim_kernel<false>, dim3(blocks), dim3(256), 0, s, x, m->smp_eps.f(), m->sch_tables.f(),
+                           st, noise, n, S);
+    return DWS_OK;
+}
+
+int sampler_run_schedule(dws_model* m, float* x, int kind, int S, const float* net_steps, const float* coef,
+                         const float* noise, uint64_t seed, int init_from_seed, int use_graph, hipStream_t s) {
+    DWS_CHECK(kind == DWS_SAMPLER_DDPM || kind == DWS_SAMPLER_DDIM, DWS_ERR_INVALID, "sampler: unknown kind %d", kind);
+    DWS_CHECK(S >= 1, DWS_ERR_INVALID, "sampler: S = %d steps (needs S >= 1)", S);
+    DWS_CHECK(net_steps && coef, DWS_ERR_INVALID, "sampler: null net_steps or coefficients");
+    for (int i = 0; i < S; ++i)
+        DWS_CHECK(std::isfinite(net_steps[i]), DWS_ERR_INVALID, "sampler: net_steps[%d] = %g is not finite", i,
+                  (double)net_steps[i]);
+    const int rows = kind == DWS_SAMPLER_DDIM ? 5 : 3;
+    for (int i = 0; i < rows * S; ++i)
+        DWS_CHECK(std::isfinite(coef[i]), DWS_ERR_INVALID, "sampler: coefficient row %d, step %d = %g is not finite",
+                  i / S, i % S, (double)coef[i]);
+    if (kind == DWS_SAMPLER_DDIM)
+        for (int i = 0; i < S; ++i)
+            DWS_CHECK(coef[S + i] > 0.f, DWS_ERR_INVALID, "sampler: DDIM k2[%d] = %g (needs k2 > 0)", i, (double)coef[S + i]);
+    DWS_CHECK(m->B > 0, DWS_ERR_STATE, "sampler before dws_model_prepare");
+    DWS_CHECK(m->d.in_channels == m->d.out_channels, DWS_ERR_INVALID,
+              "sampler needs in_channels == out_channels (x and eps share a shape, `generate.py:52`)");
+    if (m->dirty) DWS_TRY(m->commit(s));
+    const size_t n = (size_t)m->B * m->d.out_channels * m->L;
+
+    // update tables, keyed on their contents; DDIM's are used as given
+    std::vector<float> h = kind == DWS_SAMPLER_DDIM ? std::vector<float>(coef, coef + 5 * (size_t)S)
+                                                    : ddpm_table(coef, coef + S, coef + 2 * (size_t)S, S);
+    if (!m->sch_tables.p || h.size() != m->sch_host_tables.size() ||
+        std::memcmp(h.data(), m->sch_host_tables.data(), h.size() * 4) != 0) {
+        DWS_TRY(m->sch_tables.ensure(h.size() * 4));
+        DWS_HIP(hipMemcpyAsync(m->sch_tables.p, h.data(), h.size() * 4, hipMemcpyHostToDevice, s));
+        DWS_HIP(hipStreamSynchronize(s));
+        m->sch_host_tables.swap(h);
+    }
+    DWS_TRY(m->smp_eps.ensure(n * 4));
+    m->smp_eps_B = m->B; m->smp_eps_L = m->L;
+    DWS_TRY(m->build_step_table(S, net_steps, s));   // the network's step-only part at net_steps (kept while they stay)
+    DWS_TRY(m->sch_state.ensure(16));
+    int* st = static_cast<int*>(m->sch_state.p);
+    const int blocks = (int)std::min<size_t>(ceil_div(n, 4 * 256), 4096);
+    const auto aligned = [](const void* p) { return ((uintptr_t)p & 15) == 0; };
+
+    if (!use_graph) {
+        const bool vec = n % 4 == 0 && aligned(x) && aligned(noise);
+        hipLaunchKernelGGL(smp_set_state_kernel, dim3(1), dim3(1), 0, s, st, S - 1, seed);
+        if (init_from_seed)
+            hipLaunchKernelGGL(smp_fill_normal_kernel, dim3(blocks), dim3(256), 0, s, x, n, seed, (uint32_t)S);
+        for (int i = 0; i < S; ++i) DWS_TRY(schedule_step(m, x, kind, S, noise, vec, s));
+        DWS_HIP(hipGetLastError());
+        return DWS_OK;
+    }
+    // graph: x_T goes into the model-owned state buffer before the replays and x_0 comes out after them, the seed
+    // through the state word -- a new x or seed replays the same graph
+    DWS_TRY(ensure_capture_stream(m));
+    DWS_TRY(m->sch_x.ensure(n * 4));
+    float* xs = m->sch_x.f();
+    const bool vec = n % 4 == 0 && aligned(noise);   // (xs and eps come from hipMalloc)
+    hipStream_t cs = m->smp_stream;
+    DWS_HIP(hipEventRecord(m->smp_ev_in, s));
+    DWS_HIP(hipStreamWaitEvent(cs, m->smp_ev_in, 0));
+    hipLaunchKernelGGL(smp_set_state_kernel, dim3(1), dim3(1), 0, cs, st, S - 1, seed);
+    if (init_from_seed)
+        hipLaunchKernelGGL(smp_fill_normal_kernel, dim3(blocks), dim3(256), 0, cs, xs, n, seed, (uint32_t)S);
+    else
+        DWS_HIP(hipMemcpyAsync(xs, x, n * 4, hipMemcpyDeviceToDevice, cs));
+    const dws_model::SchKey key{m->B, m->L, S, kind, vec ? 1 : 0, m->sch_tables.p, noise, m->smp_eps.p, xs, st,
+                                m->step_table_gen};
+    if (!m->sch_graph || !(key == m->sch_key)) {
+        if (m->sch_graph) hipGraphExecDestroy(m->sch_graph);
+        m->sch_graph = nullptr;
+        hipGraph_t graph = nullptr;
+        DWS_HIP(hipStreamBeginCapture(cs, hipStreamCaptureModeThreadLocal));
+        int rc = schedule_step(m, xs, kind, S, noise, vec, cs);
+        hipError_t e = hipStreamEndCapture(cs, &graph);
+        if (rc != DWS_OK) {
+            if (graph) hipGraphDestroy(graph);
+            return rc;
+        }
+        DWS_HIP(e);
+        e = hipGraphInstantiate(&m->sch_graph, graph, nullptr, nullptr, 0);
+        hipGraphDestroy(graph);
+        DWS_HIP(e);
+        ++m->graphs_made;
+        m->sch_key = key;
+    }
+    for (int i = 0; i < S; ++i) DWS_HIP(hipGraphLaunch(m->sch_graph, cs));
+    DWS_HIP(hipMemcpyAsync(x, xs, n * 4, hipMemcpyDeviceToDevice, cs));
+    DWS_HIP(hipEventRecord(m->smp_ev_out, cs));
+    DWS_HIP(hipStreamWaitEvent(s, m->smp_ev_out, 0));
+    return DWS_OK;
 }
 
 }  // namespace dws

@@ -1012,21 +1012,24 @@ struct SashimiModel : dws_model {
     DevBuf tab_steps, tab_emb, tab_h1, tab_h2, tab_pt;
     int tab_T = 0;
     uint64_t tab_version = ~0ull;
+    StepKey tab_key;   // the step VALUES the table holds (same T with other steps must not reuse it)
     const float* pt_base() const { return step_idx ? tab_pt.f() : part_t.f(); }
     int pt_bstride() const { return step_idx ? 0 : pt_total; }
-    int build_step_table(int T, hipStream_t s) override {
+    int build_step_table(int T, const float* steps, hipStream_t s) override {
         if (dirty) DWS_TRY(commit(s));
-        if (tab_T == T && tab_version == commit_version) return DWS_OK;
+        if (tab_version == commit_version && tab_key.same(T, steps)) return DWS_OK;
         drop_graph();   // a captured step holds pointers into the old table
+        tab_version = ~0ull;   // invalid until the rebuild has finished
         DWS_TRY(tab_steps.ensure((size_t)T * 4));
         DWS_TRY(tab_emb.ensure((size_t)T * Ein * 4));
         DWS_TRY(tab_h1.ensure((size_t)T * Emid * 4));
         DWS_TRY(tab_h2.ensure((size_t)T * Eout * 4));
         DWS_TRY(tab_pt.ensure((size_t)T * pt_total * 4));
-        DWS_TRY(launch_iota_f32(tab_steps.f(), T, s));   // steps[t] = float(t), as `generate.py:50` feeds them
+        DWS_TRY(tab_key.upload(T, steps, tab_steps.f(), s));   // steps[t] = float(t) when null, as `generate.py:50` feeds them
         DWS_TRY(embed_rows(tab_steps.f(), T, tab_emb.f(), tab_h1.f(), tab_h2.f(), tab_pt.f(), s));
         tab_T = T;
         tab_version = commit_version;
+        ++step_table_gen;
         return DWS_OK;
     }
 

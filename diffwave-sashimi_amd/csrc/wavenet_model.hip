@@ -406,14 +406,16 @@ struct WaveNetModel : dws_model {
     }
 
     // Step table of a sampler run (sampler.hip): in sampling every clip is at the same step (`generate.py:50`), so the
-    // step-only part of the forward is evaluated ONCE for t = 0..T-1 -- tab_pt [T][NL*C], tab_abt [NL][T][abt_row] -- and
-    // the captured reverse step reads row *step_idx: no embedding kernels in a replay.
+    // step-only part of the forward is evaluated ONCE for t = 0..T-1 (or the T step values a few-step sampler hands in)
+    // -- tab_pt [T][NL*C], tab_abt [NL][T][abt_row] -- and the captured reverse step reads row *step_idx: no embedding
+    // kernels in a replay.
     DevBuf tab_steps, tab_emb, tab_h1, tab_h2, tab_pt, tab_abt;
     int tab_T = 0;
     uint64_t tab_version = ~0ull;
-    int build_step_table(int T, hipStream_t s) override {
+    StepKey tab_key;   // the step VALUES the table holds (same T with other steps must not reuse it)
+    int build_step_table(int T, const float* steps, hipStream_t s) override {
         if (dirty) DWS_TRY(commit(s));
-        if (tab_T == T && tab_version == commit_version) return DWS_OK;
+        if (tab_version == commit_version && tab_key.same(T, steps)) return DWS_OK;
         drop_graph();   // a captured step holds pointers into the old table
         {   // the table grows with T x layers x channels (0.06 GB at T = 200, C = 256; 0.3-0.6 GB at T = 1000): bounded, so that
             // a wrong T fails with a message instead of an allocation of whatever size it implies
@@ -431,10 +433,12 @@ struct WaveNetModel : dws_model {
             DWS_TRY(tab_abt.ensure(n));
             DWS_HIP(hipMemsetAsync(tab_abt.p, 0, n, s));   // unused k entries of the correction k-group stay zero
         }
-        DWS_TRY(launch_iota_f32(tab_steps.f(), T, s));   // steps[t] = float(t), as `generate.py:50` feeds them
+        tab_version = ~0ull;   // invalid until the rebuild has finished
+        DWS_TRY(tab_key.upload(T, steps, tab_steps.f(), s));   // steps[t] = float(t) when null, as `generate.py:50` feeds them
         DWS_TRY(embed_rows(tab_steps.f(), T, tab_emb.f(), tab_h1.f(), tab_h2.f(), tab_pt.f(), tab_abt.p, nullptr, nullptr, s));
         tab_T = T;
         tab_version = commit_version;
+        ++step_table_gen;
         return DWS_OK;
     }
 

@@ -186,19 +186,37 @@ def smooth_ckpt(path, min_ckpt, max_ckpt):
 @torch.no_grad()
 def generate(rank, diffusion_cfg, model_cfg, dataset_cfg, ckpt_iter="max", n_samples=1, name=None, batch_size=None,
              ckpt_smooth=None, mel_path=None, mel_name=None, dataloader=None, exp_root="exp", seed=None,
-             written=None, precision=None):
+             written=None, precision=None, sampler="ddpm", steps=None, eta=0.0):
     """``generate.py:58-200``.  ``ckpt_iter`` may additionally be ``"init"``: seeded random weights
     (no checkpoint), for smoke runs without trained weights.  ``precision`` (not in the reference; CLI:
-    ``+engine.precision=bf16x6|f16x3``): the engine's opt-in matrix arithmetic, see ``include/dws.h``."""
+    ``+engine.precision=bf16x6|f16x3``): the engine's opt-in matrix arithmetic, see ``include/dws.h``.
+
+    ``sampler`` (not in the reference; CLI ``generate.sampler=...``): ``ddpm`` (default) is the reference's loop,
+    including its use of ``diffusion.beta``; ``aligned`` runs the short ``diffusion.beta`` schedule with the network at
+    the aligned fractional training steps (``sampling.align_steps``); ``ddim`` runs DDIM over ``steps`` of the T
+    training steps with ``eta`` (default 0)."""
     from .models import construct_model
-    from .sampling import calc_diffusion_hyperparams, sampling
+    from .sampling import calc_diffusion_hyperparams, ddim_steps, sampling, sampling_aligned, sampling_ddim
     from scipy.io.wavfile import write as wavwrite
 
+    sampler = sampler or "ddpm"
+    if sampler not in ("ddpm", "aligned", "ddim"):
+        raise ValueError(f"generate.sampler={sampler!r}: expected ddpm, aligned or ddim")
+    if sampler == "aligned" and diffusion_cfg.get("beta") is None:
+        raise ValueError("generate.sampler=aligned needs diffusion.beta (the short inference schedule, e.g. "
+                         "diffusion.beta=[0.0001,0.001,0.01,0.05,0.2,0.5])")
+    if sampler == "ddim" and steps is None:
+        raise ValueError("generate.sampler=ddim needs generate.steps (the number of DDIM steps, or a list of them)")
     if rank is not None and torch.cuda.is_available():
         torch.cuda.set_device(rank % torch.cuda.device_count())
     rank = rank or 0
     local_path, output_directory = local_directory(name, model_cfg, diffusion_cfg, dataset_cfg, "waveforms", exp_root)
     dh = calc_diffusion_hyperparams(**diffusion_cfg, fast=True)
+    if sampler == "ddim":        # DDIM runs on the training schedule (the T-step linspace), never on diffusion.beta
+        dh_train = calc_diffusion_hyperparams(diffusion_cfg["T"], diffusion_cfg["beta_0"], diffusion_cfg["beta_T"])
+        n_evals = len(ddim_steps(dh_train["T"], steps))
+    else:
+        n_evals = dh["T"]
     model_kwargs = {k: v for k, v in model_cfg.items()}
     net = construct_model(model_kwargs).cuda().eval()
     if precision not in (None, "f32"):
@@ -249,11 +267,20 @@ def generate(rank, diffusion_cfg, model_cfg, dataset_cfg, ckpt_iter="max", n_sam
     out = []
     for i in range(n_samples // batch_size):
         s = None if seed is None else seed + 1000 * rank + i
-        out.append(sampling(net, (batch_size, 1, audio_length), dh, condition=mel, seed=s))
+        size = (batch_size, 1, audio_length)
+        if sampler == "aligned":
+            out.append(sampling_aligned(net, size, diffusion_cfg, condition=mel, seed=s))
+        elif sampler == "ddim":
+            out.append(sampling_ddim(net, size, dh_train, steps, eta=float(eta or 0.0), condition=mel, seed=s))
+        else:
+            out.append(sampling(net, size, dh, condition=mel, seed=s))
     generated_audio = torch.cat(out, dim=0)
     torch.cuda.synchronize()
     print(f"generated {n_samples} samples shape {tuple(generated_audio.shape)} at iteration {ckpt_iter} in "
           f"{time.perf_counter() - t0:.1f} seconds")
+    if sampler != "ddpm":
+        print(f"sampler {sampler}{f' (eta={float(eta or 0.0)})' if sampler == 'ddim' else ''}: {n_evals} network "
+              f"evaluations per batch")
     for i in range(n_samples):
         outfile = "{}k_{}.wav".format(ckpt_iter // 1000, n_samples * rank + i)   # `generate.py:189`
         wavwrite(os.path.join(output_directory, outfile), dataset_cfg["sampling_rate"],

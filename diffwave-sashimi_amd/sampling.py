@@ -32,8 +32,32 @@ def _host_table(t):
     return a, a.ctypes.data_as(ctypes.POINTER(ctypes.c_float))
 
 
+def _prepare_run(net, size, steps, condition, x_T, noise, seed):
+    """Shared set-up of the sampler entry points: the engine's parameters / shape / condition, the state tensor x
+    (x_T, or to be drawn on the device: init = 1), the injected noise [steps, B, C, L] and the seed."""
+    B, C, L = size
+    dev = torch.device("cuda")
+    if seed is None:
+        seed = int(torch.randint(0, 2 ** 63 - 1, (1,), dtype=torch.int64).item())
+    net._train_generation += 1     # the sampler's forwards overwrite the activations of a pending training forward
+    net._sync_params(L)
+    net._prepare(B, L)
+    net._set_condition(condition)
+    if x_T is None:
+        x = torch.empty(size, device=dev, dtype=torch.float32)
+        init = 1
+    else:
+        x = x_T.detach().to(device=dev, dtype=torch.float32).contiguous().clone()
+        init = 0
+    nz = None
+    if noise is not None:
+        nz = noise.detach().to(device=dev, dtype=torch.float32).contiguous()
+        assert tuple(nz.shape) == (steps, B, C, L)
+    return x, init, nz, seed
+
+
 def sampling(net, size, diffusion_hyperparams, condition=None, *, x_T=None, noise=None, seed=None,
-             use_graph=True):
+             use_graph=True, net_steps=None):
     """``x_0 = sampling(net, (B, C, L), dh, condition)`` as in ``generate.py:23-55``.
 
     Extra keyword-only arguments (not in the reference):
@@ -41,30 +65,19 @@ def sampling(net, size, diffusion_hyperparams, condition=None, *, x_T=None, nois
       noise  injected variance noise [T,B,C,L] (``noise[t]`` is added after step t>0) -- parity mode
       seed   Philox seed for the on-device RNG (default: a fresh draw from torch's CPU generator per call, so
              successive unseeded calls differ -- as the reference's do -- and ``torch.manual_seed`` still governs)
+      net_steps  float[T]: the network sees ``net_steps[t]`` at step t instead of t, with the DDPM update of ``dh``
+             unchanged (e.g. ``align_steps`` for DiffWave's fast schedule; ``dws_sampler_run_schedule``).  Not the
+             reference's loop.
     """
     dh = diffusion_hyperparams
     T, Alpha, Alpha_bar, Sigma = dh["T"], dh["Alpha"], dh["Alpha_bar"], dh["Sigma"]
     assert len(Alpha) == T and len(Alpha_bar) == T and len(Sigma) == T and len(size) == 3
-    B, C, L = size
+    if net_steps is not None:
+        coef = np.stack([_host_table(Alpha)[0], _host_table(Alpha_bar)[0], _host_table(Sigma)[0]])
+        return _run_schedule(net, size, _lib.DWS_SAMPLER_DDPM, net_steps, coef, condition, x_T, noise, seed, use_graph)
     lib = _lib.load()
-    dev = torch.device("cuda")
-    if seed is None:
-        seed = int(torch.randint(0, 2 ** 63 - 1, (1,), dtype=torch.int64).item())
     with torch.no_grad():
-        net._train_generation += 1     # the sampler's forwards overwrite the activations of a pending training forward
-        net._sync_params(L)
-        net._prepare(B, L)
-        net._set_condition(condition)
-        if x_T is None:
-            x = torch.empty(size, device=dev, dtype=torch.float32)
-            init = 1
-        else:
-            x = x_T.detach().to(device=dev, dtype=torch.float32).contiguous().clone()
-            init = 0
-        nz = None
-        if noise is not None:
-            nz = noise.detach().to(device=dev, dtype=torch.float32).contiguous()
-            assert tuple(nz.shape) == (T, B, C, L)
+        x, init, nz, seed = _prepare_run(net, size, T, condition, x_T, noise, seed)
         a, pa = _host_table(Alpha)
         ab, pab = _host_table(Alpha_bar)
         sg, psg = _host_table(Sigma)
@@ -72,3 +85,116 @@ def sampling(net, size, diffusion_hyperparams, condition=None, *, x_T=None, nois
                                        1 if use_graph else 0, _lib.current_stream()))
         torch.cuda.current_stream().synchronize()  # nz / tables must outlive the enqueued work
     return x
+
+
+def _run_schedule(net, size, kind, net_steps, coef, condition, x_T, noise, seed, use_graph):
+    """``dws_sampler_run_schedule``: S steps s = S-1..0, the network at ``net_steps[s]``, update tables ``coef``."""
+    assert len(size) == 3
+    steps = np.ascontiguousarray(np.asarray(net_steps, dtype=np.float32).reshape(-1))
+    S = steps.shape[0]
+    coef = np.ascontiguousarray(np.asarray(coef, dtype=np.float32))
+    if S < 1 or coef.shape != ((5 if kind == _lib.DWS_SAMPLER_DDIM else 3), S):
+        raise ValueError(f"sampler: {S} net steps with coefficient tables of shape {coef.shape}")
+    lib = _lib.load()
+    fp = ctypes.POINTER(ctypes.c_float)
+    with torch.no_grad():
+        x, init, nz, seed = _prepare_run(net, size, S, condition, x_T, noise, seed)
+        _lib.check(lib.dws_sampler_run_schedule(net._handle, x.data_ptr(), kind, S, steps.ctypes.data_as(fp),
+                                                coef.ctypes.data_as(fp), _lib.ptr(nz), seed, init,
+                                                1 if use_graph else 0, _lib.current_stream()))
+        torch.cuda.current_stream().synchronize()  # nz must outlive the enqueued work
+    return x
+
+
+# --------------------------------------------------------------------------- few-step schedules (not the reference's)
+def align_steps(T, beta_0, beta_T, infer_betas):
+    """DiffWave's step alignment (Kong et al., ICLR 2021, App. B): the fractional training step whose noise level
+    matches each step of a short inference schedule ``infer_betas``.  float64 throughout: training
+    ``abar_t = prod_{i<=t} (1 - beta_i)`` over ``linspace(beta_0, beta_T, T)``, inference
+    ``gamma_s = prod_{i<=s} (1 - beta'_i)``; for the first t in 0..T-2 with ``abar_{t+1} <= gamma_s <= abar_t``,
+    ``t_s = t + (sqrt(abar_t) - sqrt(gamma_s)) / (sqrt(abar_t) - sqrt(abar_{t+1}))``, rounded to float32 once.
+    A gamma_s outside ``[abar_{T-1}, abar_0]`` by a relative 1e-9 at most is clamped to that end; further out ->
+    ValueError.  ``infer_betas = linspace(beta_0, beta_T, T)`` gives exactly 0, 1, ..., T-1."""
+    T = int(T)
+    if T < 1:
+        raise ValueError(f"align_steps: T = {T}")
+    abar = np.cumprod(1.0 - np.linspace(beta_0, beta_T, T, dtype=np.float64))
+    gamma = np.cumprod(1.0 - np.asarray(infer_betas, dtype=np.float64).reshape(-1))
+    sab = np.sqrt(abar)
+    lo, hi = abar[-1], abar[0]
+    out = np.empty(gamma.shape[0], dtype=np.float64)
+    for s, g in enumerate(gamma):
+        if g > hi or g < lo:
+            end = hi if g > hi else lo
+            if not abs(g - end) <= 1e-9 * end:
+                raise ValueError(f"align_steps: gamma_{s} = {g!r} is outside the training range "
+                                 f"[abar_{T - 1}, abar_0] = [{lo!r}, {hi!r}]")
+            g = end
+        if T == 1:
+            out[s] = 0.0
+            continue
+        t = int(np.flatnonzero((abar[1:] <= g) & (g <= abar[:-1]))[0])
+        out[s] = t + (sab[t] - np.sqrt(g)) / (sab[t] - sab[t + 1])
+    return out.astype(np.float32)
+
+
+def ddim_steps(T, S):
+    """DDIM's sub-sequence of the T training steps: ``tau_i = rint(i (T-1) / (S-1))``, i = 0..S-1 (``[T-1]`` for
+    S = 1).  ``S`` may also be an explicit increasing list of steps in 0..T-1."""
+    T = int(T)
+    if isinstance(S, (list, tuple, np.ndarray)):
+        tau = [int(t) for t in S]
+        if len(tau) < 1 or any(float(a) != b for a, b in zip(tau, S)):
+            raise ValueError(f"ddim_steps: steps must be a non-empty list of integers, got {list(S)}")
+        if tau[0] < 0 or tau[-1] > T - 1 or any(b <= a for a, b in zip(tau, tau[1:])):
+            raise ValueError(f"ddim_steps: steps must increase strictly within 0..{T - 1}, got {tau}")
+        return tau
+    S = int(S)
+    if S < 1 or S > T:
+        raise ValueError(f"ddim_steps: S = {S} steps out of T = {T} (needs 1 <= S <= T)")
+    if S == 1:
+        return [T - 1]
+    tau = [int(np.rint(i * (T - 1) / (S - 1))) for i in range(S)]
+    assert all(b > a for a, b in zip(tau, tau[1:]))
+    return tau
+
+
+def ddim_coefficients(alpha_bar, tau, eta):
+    """Update tables of DDIM (Song et al., ICLR 2021) over the steps ``tau``: float32 [5][S] = k1..k5 with
+    ``a_s = abar[tau_s]``, ``p_s = abar[tau_{s-1}]`` (``p_0 = 1``), ``sigma_s = eta sqrt((1-p_s)/(1-a_s))
+    sqrt(1 - a_s/p_s)``; ``k1 = sqrt(1-a)``, ``k2 = sqrt(a)``, ``k3 = sqrt(p)``, ``k4 = sqrt(max(0, 1-p-sigma^2))``,
+    ``k5 = sigma``, in float64 from the float32 ``Alpha_bar`` of ``calc_diffusion_hyperparams``, rounded once.  The
+    engine's step is then ``u = (x - k1 eps) / k2; x = k3 u + k4 eps (+ k5 z for s > 0)``."""
+    if isinstance(alpha_bar, torch.Tensor):
+        alpha_bar = alpha_bar.detach().cpu().numpy()
+    ab = np.asarray(alpha_bar, dtype=np.float32).astype(np.float64)
+    tau = np.asarray(tau, dtype=np.int64).reshape(-1)
+    a = ab[tau]
+    p = np.concatenate([[1.0], ab[tau[:-1]]])
+    sigma = float(eta) * np.sqrt((1.0 - p) / (1.0 - a)) * np.sqrt(1.0 - a / p)
+    k = np.stack([np.sqrt(1.0 - a), np.sqrt(a), np.sqrt(p), np.sqrt(np.maximum(0.0, 1.0 - p - sigma * sigma)), sigma])
+    return k.astype(np.float32)
+
+
+def sampling_ddim(net, size, dh_train, steps, eta=0.0, condition=None, *, x_T=None, noise=None, seed=None,
+                  use_graph=True):
+    """DDIM over ``ddim_steps(T, steps)`` of the training schedule ``dh_train`` (``steps``: S or an explicit list),
+    deterministic for ``eta = 0``.  ``noise``: injected z, [S, B, C, L] (``noise[s]`` is used after step s > 0).
+    Not the reference's loop."""
+    tau = ddim_steps(dh_train["T"], steps)
+    coef = ddim_coefficients(dh_train["Alpha_bar"], tau, eta)
+    return _run_schedule(net, size, _lib.DWS_SAMPLER_DDIM, np.asarray(tau, dtype=np.float32), coef, condition, x_T,
+                         noise, seed, use_graph)
+
+
+def sampling_aligned(net, size, diffusion_cfg, condition=None, **kw):
+    """DiffWave's fast sampling with step alignment from a ``diffusion:`` config block with a short ``beta`` list:
+    the reference's update tables of that list (``calc_diffusion_hyperparams(..., fast=True)``), the network at the
+    aligned fractional steps (``align_steps``).  Keyword arguments as ``sampling``."""
+    beta = diffusion_cfg.get("beta")
+    if beta is None:
+        raise ValueError("aligned sampling needs diffusion.beta (the short inference schedule, e.g. "
+                         "[0.0001, 0.001, 0.01, 0.05, 0.2, 0.5])")
+    T, b0, bT = diffusion_cfg["T"], diffusion_cfg["beta_0"], diffusion_cfg["beta_T"]
+    dh = calc_diffusion_hyperparams(T, b0, bT, beta=beta, fast=True)
+    return sampling(net, size, dh, condition, net_steps=align_steps(T, b0, bT, beta), **kw)

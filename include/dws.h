@@ -252,6 +252,34 @@ int dws_sampler_steps(dws_model* m, float* x, const float* alpha, const float* a
                       const float* sigma, int32_t T, int32_t t_start, int32_t n_steps,
                       uint64_t seed, int32_t use_graph, void* stream);
 
+/* Few-step samplers (not the reference's loop): S reverse steps s = S-1 .. 0 with the
+ * network at net_steps[s] -- any finite float, e.g. the fractional training steps of
+ * DiffWave's step alignment or the sub-sequence tau of DDIM.  The step table is built
+ * at these values (kept while the values and the weights stay).
+ *
+ *   kind       DWS_SAMPLER_DDPM: coef = alpha[S], alpha_bar[S], sigma[S] (S-row tables of
+ *              calc_diffusion_hyperparams); the update and its c1/c2 arithmetic are those of
+ *              dws_sampler_run.
+ *              DWS_SAMPLER_DDIM: coef = k1[S] .. k5[S] (sampling.ddim_coefficients, taken as
+ *              given); per element, each operation rounded once, in this order:
+ *                u = (x - k1 eps) / k2;  x = k3 u + k4 eps;  if s > 0 and k5 > 0: x = x + k5 z
+ *   net_steps  HOST float[S];  coef  HOST float[3 or 5][S]
+ *   noise      optional DEVICE [S, B, C, L]: noise[s] is z of step s.  NULL -> Philox keyed
+ *              by (seed, s, element); a seed-driven x_T uses stream S.  With S = T, the
+ *              training tables and net_steps = 0..T-1, DDPM is bit-identical to dws_sampler_run.
+ *
+ * With use_graph the captured step works on a model-owned state buffer and reads the seed
+ * from device memory: x_T is copied (or drawn) in before the replays and x_0 copied out
+ * after them, so a new seed or a new x needs no new capture.  One graph per (B, L, S, kind,
+ * tables, step table, noise pointer); tap "sampler_graphs" counts the graphs a model has
+ * instantiated (both entry points).  Bad input (S < 1, non-finite steps or coefficients,
+ * DDIM k2 <= 0) -> DWS_ERR_INVALID. */
+#define DWS_SAMPLER_DDPM 0
+#define DWS_SAMPLER_DDIM 1
+int dws_sampler_run_schedule(dws_model* m, float* x, int32_t kind, int32_t S, const float* net_steps,
+                             const float* coef, const float* noise, uint64_t seed, int32_t init_from_seed,
+                             int32_t use_graph, void* stream);
+
 /* Mel-spectrogram front-end of the vocoding path: TacotronSTFT.mel_spectrogram
  * (`dataloaders/stft.py:196-244`) as called by Mel2Samp.get_mel (`dataloaders/mel2samp.py:76-82`) and
  * generate.py:147-153.  audio [B][T] in [-1, 1]; window [n_fft] (the Hann window, centre-padded to

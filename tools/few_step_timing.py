@@ -1,0 +1,167 @@
+"""Whole-call wall clock of the few-step samplers (dws_sampler_run_schedule) next to the full-T sampler and S x one
+step, on one GPU: host clock around each call, every call ending in a device synchronise, after warm-up.
+
+    python tools/few_step_timing.py [--repeats 5] [--out FILE]
+
+Legs: config 4 (unet_d32_n6_T50_cond, B = 32, mel [1, 80, 63]) aligned S = 6 under f32 and bf16x6; config 2
+(wnet_h256_d36_T200, B = 16) DDIM S = 50 under bf16x6 (the headline arithmetic).  Per leg: the first call (step-table
+build + capture + instantiate + S replays), repeat calls with a new seed and a new output tensor (replays only),
+the per-step time of the plain sampler's captured step (dws_sampler_steps) and the full-T dws_sampler_run call.
+Capture + instantiate alone: `capture_cost`."""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+
+
+def _clock(fn):
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    fn()
+    torch.cuda.synchronize()
+    return (time.perf_counter() - t0) * 1e3
+
+
+def _stats(v):
+    return dict(median_ms=round(statistics.median(v), 3), min_ms=round(min(v), 3), max_ms=round(max(v), 3), n=len(v))
+
+
+def _step_ms(net, size, dh, repeats, n_steps=10):
+    """Per-step time of the plain sampler's captured step (dws_sampler_steps, the graph replayed n_steps times)."""
+    from diffwave_sashimi_amd import _lib
+    from diffwave_sashimi_amd.sampling import _host_table, _prepare_run
+    lib = _lib.load()
+    T = dh["T"]
+    with torch.no_grad():
+        x, _, _, _ = _prepare_run(net, size, T, getattr(net, "_timing_mel", None), torch.randn(size), None, 1)
+    a, pa = _host_table(dh["Alpha"])
+    ab, pab = _host_table(dh["Alpha_bar"])
+    sg, psg = _host_table(dh["Sigma"])
+    run = lambda: _lib.check(lib.dws_sampler_steps(net._handle, x.data_ptr(), pa, pab, psg, T, T - 1, n_steps, 1, 1,
+                                                   _lib.current_stream()))
+    run()
+    return [_clock(run) / n_steps for _ in range(repeats)]
+
+
+def leg(name, cfg_name, precision, kind, S, repeats):
+    from benchlib.configs import CONFIGS, build_model
+    from diffwave_sashimi_amd.sampling import calc_diffusion_hyperparams, sampling, sampling_aligned, sampling_ddim
+    cfg = CONFIGS[cfg_name]
+    dev = torch.device("cuda")
+    net = build_model(cfg, dev)
+    if precision != "f32":
+        net.set_option("precision", precision)
+    B, L = cfg["B"], cfg["L"]
+    size = (B, 1, L)
+    mel = None
+    if "Tmel" in cfg:
+        g = torch.Generator().manual_seed(2)
+        mel = (torch.rand(1, 80, cfg["Tmel"], generator=g) * 13.5 - 11.5).to(dev)
+    net._timing_mel = mel
+    d = cfg["diffusion"]
+    dh_train = calc_diffusion_hyperparams(d["T"], d["beta_0"], d["beta_T"])
+    if kind == "aligned":
+        dcfg = dict(d, beta=[1e-4, 1e-3, 1e-2, 0.05, 0.2, 0.5])
+        call = lambda seed: sampling_aligned(net, size, dcfg, mel, seed=seed)
+    else:
+        call = lambda seed: sampling_ddim(net, size, dh_train, S, 0.0, mel, seed=seed)
+    # warm-up: code objects, the plain sampler's graph, allocator (another shape's first call)
+    sampling(net, size, calc_diffusion_hyperparams(4, d["beta_0"], d["beta_T"]), mel, seed=0)
+    first = _clock(lambda: call(100))
+    repeat = [_clock(lambda i=i: call(101 + i)) for i in range(repeats)]
+    graphs = int(net.read_tap("sampler_graphs", (1,)).item())
+    step = _step_ms(net, size, dh_train, repeats)
+    full =[_clock(lambda i=i: sampling(net, size, dh_train, mel, seed=500 + i)) for i in range(max(3, repeats // 2))]
+    st = statistics.median(step)
+    rec = dict(leg=name, config=cfg_name, precision=precision, sampler=kind, S=S, B=B, L=L,
+               first_call=round(first, 3), repeat_call=_stats(repeat), graphs_after_repeats=graphs,
+               step=_stats(step), S_x_step_ms=round(S * st, 3),
+               repeat_over_S_x_step=round(statistics.median(repeat) / (S * st), 4),
+               full_T=dict(T=d["T"], **_stats(full)))
+    del net
+    torch.cuda.empty_cache()
+    return rec
+
+
+def capture_cost(cfg_name, precision, kind, S, repeats):
+    """Capture + instantiate of the schedule graph alone: alternate two schedules of the same S whose step tables
+    differ, so that every call rebuilds the table AND recaptures; subtract the same alternation run eagerly
+    (table rebuild, no graph) and normalise per call: (graph alternation - eager alternation) - (graph repeat -
+    eager repeat) isolates capture + instantiate."""
+    from benchlib.configs import CONFIGS, build_model
+    from diffwave_sashimi_amd.sampling import calc_diffusion_hyperparams, sampling_ddim
+    cfg = CONFIGS[cfg_name]
+    dev = torch.device("cuda")
+    net = build_model(cfg, dev)
+    if precision != "f32":
+        net.set_option("precision", precision)
+    B, L = cfg["B"], cfg["L"]
+    size = (B, 1, L)
+    mel = None
+    if "Tmel" in cfg:
+        g = torch.Generator().manual_seed(2)
+        mel = (torch.rand(1, 80, cfg["Tmel"], generator=g) * 13.5 - 11.5).to(dev)
+    d = cfg["diffusion"]
+    dh = calc_diffusion_hyperparams(d["T"], d["beta_0"], d["beta_T"])
+    tau_a = list(range(S))
+    tau_b = list(range(1, S + 1))
+    run = lambda tau, g, seed: sampling_ddim(net, size, dh, tau, 0.0, mel, seed=seed, use_graph=g)
+    for g in (True, False):
+        run(tau_a, g, 1), run(tau_b, g, 1)
+    alt = {True: [], False: []}
+    rep = {True: [], False: []}
+    for i in range(repeats):
+        for g in (True, False):
+            run(tau_a, g, 0)
+            alt[g].append(_clock(lambda: run(tau_b, g, i)))      # other steps: table rebuild (+ capture)
+            run(tau_a, g, 0)
+            rep[g].append(_clock(lambda: run(tau_a, g, i)))      # same steps, new seed: replays only
+    med = {k: statistics.median(v) for k, v in alt.items()}
+    medr = {k: statistics.median(v) for k, v in rep.items()}
+    per = [(alt[True][i] - alt[False][i]) - (rep[True][i] - rep[False][i]) for i in range(repeats)]
+    rec = dict(config=cfg_name, precision=precision, S=S,
+               graph_alternating=_stats(alt[True]), eager_alternating=_stats(alt[False]),
+               graph_repeat=_stats(rep[True]), eager_repeat=_stats(rep[False]),
+               capture_plus_instantiate_ms=_stats(per),
+               capture_plus_instantiate_median_formula_ms=round((med[True] - med[False]) - (medr[True] - medr[False]), 3))
+    del net
+    torch.cuda.empty_cache()
+    return rec
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--repeats", type=int, default=5)
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--legs", default="c4_f32,c4_bx6,c2_ddim50,capture")
+    args = ap.parse_args()
+    assert torch.cuda.is_available(), "needs a GPU"
+    legs = {
+        "c4_f32": lambda: leg("config4 aligned S=6 f32", "unet_d32_n6_T50_cond", "f32", "aligned", 6, args.repeats),
+        "c4_bx6": lambda: leg("config4 aligned S=6 bf16x6", "unet_d32_n6_T50_cond", "bf16x6", "aligned", 6, args.repeats),
+        "c2_ddim50": lambda: leg("config2 DDIM S=50 bf16x6", "wnet_h256_d36_T200", "bf16x6", "ddim", 50, args.repeats),
+        "capture": lambda: [capture_cost("unet_d32_n6_T50_cond", "f32", "ddim", 6, args.repeats),
+                            capture_cost("wnet_h256_d36_T200", "bf16x6", "ddim", 50, args.repeats)],
+    }
+    out = []
+    for k in args.legs.split(","):
+        r = legs[k]()
+        for x in (r if isinstance(r, list) else [r]):
+            print(json.dumps(x), flush=True)
+            out.append(x)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            json.dump(out, f, indent=1)
+
+
+if __name__ == "__main__":
+    main()
