@@ -12,6 +12,7 @@ DWS_OK, DWS_ERR_INVALID, DWS_ERR_UNSUPPORTED, DWS_ERR_HIP, DWS_ERR_STATE = 0, -1
 DWS_KIND_WAVENET, DWS_KIND_SASHIMI = 1, 2
 DWS_MAX_POOL = 8
 DWS_SAMPLER_DDPM, DWS_SAMPLER_DDIM = 0, 1
+DWS_START_AS_GIVEN, DWS_START_QSAMPLE = 0, 1
 
 c_f32p = ctypes.c_void_p  # device pointers travel as integers
 
@@ -32,6 +33,15 @@ class ModelDesc(ctypes.Structure):
         ("d_model", ctypes.c_int32), ("n_layers", ctypes.c_int32), ("n_pool", ctypes.c_int32),
         ("pool", ctypes.c_int32 * DWS_MAX_POOL), ("expand", ctypes.c_int32), ("ff", ctypes.c_int32),
         ("unet", ctypes.c_int32), ("L", ctypes.c_int32),
+    ]
+
+
+class SamplerEdit(ctypes.Structure):
+    """Mirror of ``dws_sampler_edit`` (include/dws.h): what ``dws_sampler_run_edit`` takes beyond the schedule entry."""
+    _fields_ = [
+        ("edit_coef", ctypes.POINTER(ctypes.c_float)),      # host [4][S]
+        ("known", c_f32p), ("mask", ctypes.c_void_p), ("known_noise", c_f32p), ("start_noise", c_f32p),
+        ("start_step", ctypes.c_int32), ("start_mode", ctypes.c_int32),
     ]
 
 
@@ -83,6 +93,10 @@ _SIGS = {
     "dws_sampler_run_schedule": (ctypes.c_int, [ctypes.c_void_p, c_f32p, ctypes.c_int32, ctypes.c_int32,
                                                 ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float), c_f32p,
                                                 ctypes.c_uint64, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p]),
+    "dws_sampler_run_edit": (ctypes.c_int, [ctypes.c_void_p, c_f32p, ctypes.c_int32, ctypes.c_int32,
+                                            ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float), c_f32p,
+                                            ctypes.c_uint64, ctypes.c_int32, ctypes.c_int32,
+                                            ctypes.POINTER(SamplerEdit), ctypes.c_void_p]),
     "dws_mel_spectrogram": (ctypes.c_int, [c_f32p, ctypes.c_int64, ctypes.c_int64, c_f32p, c_f32p, ctypes.c_int32,
                                            ctypes.c_int32, ctypes.c_int32, ctypes.c_float, c_f32p, ctypes.c_void_p]),
     "dws_gemm_bf16x6": (ctypes.c_int, [c_f32p] * 3 + [ctypes.c_int64] * 3 + [ctypes.c_void_p]),

@@ -9,7 +9,8 @@ int sampler_run(dws_model* m, float* x, const float* alpha, const float* alpha_b
 int sampler_steps(dws_model* m, float* x, const float* alpha, const float* alpha_bar, const float* sigma, int T,
                   int t_start, int n_steps, uint64_t seed, int use_graph, hipStream_t s);
 int sampler_run_schedule(dws_model* m, float* x, int kind, int S, const float* net_steps, const float* coef,
-                         const float* noise, uint64_t seed, int init_from_seed, int use_graph, hipStream_t s);
+                         const float* noise, uint64_t seed, int init_from_seed, int use_graph,
+                         const dws_sampler_edit* e, hipStream_t s);
 }  // namespace dws
 
 dws_model::~dws_model() {
@@ -31,6 +32,8 @@ void dws_model::drop_graph() {
     smp_graph = nullptr;
     if (sch_graph) hipGraphExecDestroy(sch_graph);
     sch_graph = nullptr;
+    if (edit_graph) hipGraphExecDestroy(edit_graph);
+    edit_graph = nullptr;
 }
 
 dws::ParamSpec* dws_model::add_param(const std::string& name, std::vector<int64_t> shape, int dtype) {
@@ -431,7 +434,15 @@ int dws_sampler_run_schedule(dws_model* m, float* x, int32_t kind, int32_t S, co
                              const float* coef, const float* noise, uint64_t seed, int32_t init_from_seed,
                              int32_t use_graph, void* stream) {
     DWS_CHECK(m && x, DWS_ERR_INVALID, "dws_sampler_run_schedule: null argument");
-    return dws::sampler_run_schedule(m, x, kind, S, net_steps, coef, noise, seed, init_from_seed, use_graph,
+    return dws::sampler_run_schedule(m, x, kind, S, net_steps, coef, noise, seed, init_from_seed, use_graph, nullptr,
+                                     (hipStream_t)stream);
+}
+
+int dws_sampler_run_edit(dws_model* m, float* x, int32_t kind, int32_t S, const float* net_steps, const float* coef,
+                         const float* noise, uint64_t seed, int32_t init_from_seed, int32_t use_graph,
+                         const dws_sampler_edit* edit, void* stream) {
+    DWS_CHECK(m && x && edit, DWS_ERR_INVALID, "dws_sampler_run_edit: null argument");
+    return dws::sampler_run_schedule(m, x, kind, S, net_steps, coef, noise, seed, init_from_seed, use_graph, edit,
                                      (hipStream_t)stream);
 }
 

@@ -197,11 +197,22 @@ struct dws_model {
         int S, kind, vec;
         const void *tables, *noise, *eps, *x, *state;
         uint64_t table_gen;
+        const void *edit, *known, *mask, *known_noise;   // the edited step's (all null for the unedited one)
         bool operator==(const SchKey& o) const {
             return B == o.B && L == o.L && S == o.S && kind == o.kind && vec == o.vec && tables == o.tables &&
-                   noise == o.noise && eps == o.eps && x == o.x && state == o.state && table_gen == o.table_gen;
+                   noise == o.noise && eps == o.eps && x == o.x && state == o.state && table_gen == o.table_gen &&
+                   edit == o.edit && known == o.known && mask == o.mask && known_noise == o.known_noise;
         }
     } sch_key{};
+    // editing (dws_sampler_run_edit): the step that ends in the replacement of the known region is a graph of its own
+    // beside sch_graph (same state, x, eps and step table), so edited and unedited calls alternate without a capture.
+    // The known clip and the mask are copied into model-owned buffers before the replays, like x into sch_x.
+    dws::DevBuf sch_edit;                 // [2][S] q1, q2 of sampling.edit_coefficients
+    std::vector<float> sch_host_edit;     // host copy of what is resident
+    dws::DevBuf sch_known;                // float [B, C, L]
+    dws::DevBuf sch_mask;                 // uint8 [B, C, L] (rounded up to whole groups of four)
+    hipGraphExec_t edit_graph = nullptr;
+    SchKey edit_key{};
     uint64_t step_table_gen = 0;          // bumped by every step-table rebuild (build_step_table)
     int64_t graphs_made = 0;              // tap "sampler_graphs": graphs instantiated by either entry point
 

@@ -177,6 +177,139 @@ __global__ void smp_ddim_kernel(float* __restrict__ x, const float* __restrict__
     }
 }
 
+// Editing step of dws_sampler_run_edit (inpainting by replacement: Song et al., ICLR 2021, "imputation"; the base case
+// of RePaint): the DDPM (tab = c1, c2, sigma) or DDIM (tab = k1 .. k5) update of step s exactly as smp_update_kernel /
+// smp_ddim_kernel write it, then, where mask != 0, the element is overwritten with the known audio y noised to the level
+// the state is at after step s:
+//   v = (s > 0) ? (q1[s] * y) + (q2[s] * zk) : y          edit = q1[S], q2[S] (sampling.edit_coefficients)
+// two products and one sum, each rounded once (contraction off, plain operators).  zk: known_noise[s] or Philox stream
+// S + 1 + s in normal4's layout, drawn only for groups that hold a known element (no other element reads it).
+// VEC: every group of 4 is in range and all pointers are 16-byte aligned -> float4 for x / eps / y / the noises and the
+// four mask bytes of the group as one 32-bit load.
+template <int KIND, bool VEC>
+__global__ void smp_edit_kernel(float* __restrict__ x, const float* __restrict__ eps, const float* __restrict__ tab,
+                                const float* __restrict__ edit, int* __restrict__ st, const float* __restrict__ noise,
+                                const float* __restrict__ y, const uint8_t* __restrict__ mask,
+                                const float* __restrict__ known_noise, size_t n, int S) {
+#pragma clang fp contract(off)
+    const int s = __builtin_amdgcn_readfirstlane(*(volatile int*)st);
+    const uint64_t seed = *(const volatile uint64_t*)(st + 2);
+    const float k1 = tab[s], k2 = tab[S + s], k3 = tab[2 * S + s];
+    const float k4 = KIND == DWS_SAMPLER_DDIM ? tab[3 * S + s] : 0.f, k5 = KIND == DWS_SAMPLER_DDIM ? tab[4 * S + s] : 0.f;
+    const bool add = KIND == DWS_SAMPLER_DDIM ? (s > 0 && k5 > 0.f) : s > 0;
+    const float q1 = edit[s], q2 = edit[S + s];
+    const float* nz = noise ? noise + (size_t)s * n : nullptr;
+    const float* kz = known_noise ? known_noise + (size_t)s * n : nullptr;
+    for (size_t g = (size_t)blockIdx.x * blockDim.x + threadIdx.x; g * 4 < n; g += (size_t)gridDim.x * blockDim.x) {
+        float xv[4] = {0.f, 0.f, 0.f, 0.f}, ev[4] = {0.f, 0.f, 0.f, 0.f}, z[4] = {0.f, 0.f, 0.f, 0.f};
+        float yv[4] = {0.f, 0.f, 0.f, 0.f}, zk[4] = {0.f, 0.f, 0.f, 0.f};
+        uint32_t mk = 0;    // byte j: mask of element 4g + j
+        if (VEC) {
+            const float4 a = reinterpret_cast<const float4*>(x)[g], e = reinterpret_cast<const float4*>(eps)[g];
+            xv[0] = a.x; xv[1] = a.y; xv[2] = a.z; xv[3] = a.w;
+            ev[0] = e.x; ev[1] = e.y; ev[2] = e.z; ev[3] = e.w;
+            if (add && nz) {
+                const float4 q = reinterpret_cast<const float4*>(nz)[g];
+                z[0] = q.x; z[1] = q.y; z[2] = q.z; z[3] = q.w;
+            }
+            mk = reinterpret_cast<const uint32_t*>(mask)[g];
+            if (mk) {
+                const float4 k = reinterpret_cast<const float4*>(y)[g];
+                yv[0] = k.x; yv[1] = k.y; yv[2] = k.z; yv[3] = k.w;
+                if (s > 0 && kz) {
+                    const float4 q = reinterpret_cast<const float4*>(kz)[g];
+                    zk[0] = q.x; zk[1] = q.y; zk[2] = q.z; zk[3] = q.w;
+                }
+            }
+        } else {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const size_t i = g * 4 + j;
+                if (i >= n) break;
+                xv[j] = x[i]; ev[j] = eps[i];
+                if (add && nz) z[j] = nz[i];
+                if (mask[i]) {
+                    mk |= 1u << (8 * j);
+                    yv[j] = y[i];
+                    if (s > 0 && kz) zk[j] = kz[i];
+                }
+            }
+        }
+        if (add && !nz) normal4(seed, (uint32_t)s, g, z);
+        if (mk && s > 0 && !kz) normal4(seed, (uint32_t)(S + 1 + s), g, zk);
+        float r[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            float v;
+            if (KIND == DWS_SAMPLER_DDIM) {      // smp_ddim_kernel's order
+                const float p = k1 * ev[j];
+                const float d = xv[j] - p;
+                const float u = d / k2;
+                const float a = k3 * u;
+                const float b = k4 * ev[j];
+                v = a + b;
+                if (add) {
+                    const float q = k5 * z[j];
+                    v = v + q;
+                }
+            } else {                             // smp_update_kernel's order: k1 = c1, k2 = c2, k3 = sigma
+                const float p = k1 * ev[j];
+                v = (xv[j] - p) / k2;
+                if (add) {
+                    const float q = k3 * z[j];
+                    v = v + q;
+                }
+            }
+            if ((mk >> (8 * j)) & 0xffu) {
+                v = yv[j];
+                if (s > 0) {
+                    const float a = q1 * yv[j];
+                    const float b = q2 * zk[j];
+                    v = a + b;
+                }
+            }
+            r[j] = v;
+        }
+        if (VEC) {
+            reinterpret_cast<float4*>(x)[g] = make_float4(r[0], r[1], r[2], r[3]);
+        } else {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const size_t i = g * 4 + j;
+                if (i >= n) break;
+                x[i] = r[j];
+            }
+        }
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        if (atomicAdd(reinterpret_cast<unsigned*>(st + 1), 1u) == gridDim.x - 1) {
+            st[1] = 0;
+            st[0] = s - 1;
+        }
+    }
+}
+
+// Partial start in q-sample mode: x holds clean audio and becomes the state at step s0,
+//   x = (n1 * x) + (n2 * z0)      n1 = sqrt(level[s0]), n2 = sqrt(1 - level[s0])
+// two products and one sum, each rounded once.  z0: the injected tensor or Philox stream `stream_id` (2S + 1).
+__global__ void smp_qsample_kernel(float* __restrict__ x, const float* __restrict__ z0, float n1, float n2, size_t n,
+                                   uint64_t seed, uint32_t stream_id) {
+#pragma clang fp contract(off)
+    for (size_t g = (size_t)blockIdx.x * blockDim.x + threadIdx.x; g * 4 < n; g += (size_t)gridDim.x * blockDim.x) {
+        float z[4] = {0.f, 0.f, 0.f, 0.f};
+        if (!z0) normal4(seed, stream_id, g, z);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const size_t i = g * 4 + j;
+            if (i >= n) break;
+            const float a = n1 * x[i];
+            const float b = n2 * (z0 ? z0[i] : z[j]);
+            x[i] = a + b;
+        }
+    }
+}
+
 // c1 = (1 - alpha) / sqrt(1 - alpha_bar), c2 = sqrt(alpha), sigma: [3][T]
 static std::vector<float> ddpm_table(const float* alpha, const float* alpha_bar, const float* sigma, int T) {
     std::vector<float> h(3 * (size_t)T);
@@ -300,9 +433,20 @@ int sampler_steps(dws_model* m, float* x, const float* alpha, const float* alpha
     return run_steps(m, x, T, t_start, n_steps, nullptr, seed, use_graph, s);
 }
 
-// ---- few-step samplers (dws_sampler_run_schedule) ----
-// One reverse step of the schedule: forward at row *st of the step table, then the DDPM or DDIM update.
-static int schedule_step(dws_model* m, float* x, int kind, int S, const float* noise, bool vec, hipStream_t s) {
+// ---- few-step samplers (dws_sampler_run_schedule) and their editing modes (dws_sampler_run_edit) ----
+// device side of a known-region replacement: the resident q1 / q2 table, the model-owned copies of the known audio and
+// the mask, the caller's injected known-region noise (or null)
+struct EditStep {
+    const float* table;
+    const float* known;
+    const uint8_t* mask;
+    const float* known_noise;
+};
+
+// One reverse step of the schedule: forward at row *st of the step table, then the DDPM or DDIM update (with the
+// replacement of the known region when `ed` is given).
+static int schedule_step(dws_model* m, float* x, int kind, int S, const float* noise, bool vec, const EditStep* ed,
+                         hipStream_t s) {
     const size_t n = (size_t)m->B * m->d.out_channels * m->L;
     int* st = static_cast<int*>(m->sch_state.p);
     m->step_idx = st;
@@ -310,6 +454,18 @@ static int schedule_step(dws_model* m, float* x, int kind, int S, const float* n
     m->step_idx = nullptr;
     DWS_TRY(rc);
     const int blocks = (int)std::min<size_t>(ceil_div(n, 4 * 256), 4096);
+    if (ed) {
+#define DWS_EDIT_LAUNCH(KIND, VEC)                                                                                     \
+    hipLaunchKernelGGL((smp_edit_kernel<KIND, VEC>), dim3(blocks), dim3(256), 0, s, x, m->smp_eps.f(),                 \
+                       m->sch_tables.f(), ed->table, st, noise, ed->known, ed->mask, ed->known_noise, n, S)
+        if (kind == DWS_SAMPLER_DDPM) {
+            if (vec) DWS_EDIT_LAUNCH(DWS_SAMPLER_DDPM, true); else DWS_EDIT_LAUNCH(DWS_SAMPLER_DDPM, false);
+        } else {
+            if (vec) DWS_EDIT_LAUNCH(DWS_SAMPLER_DDIM, true); else DWS_EDIT_LAUNCH(DWS_SAMPLER_DDIM, false);
+        }
+#undef DWS_EDIT_LAUNCH
+        return DWS_OK;
+    }
     if (kind == DWS_SAMPLER_DDPM)
         hipLaunchKernelGGL(smp_update_kernel, dim3(blocks), dim3(256), 0, s, x, m->smp_eps.f(), m->sch_tables.f(), st,
                            noise, (uint64_t)0, reinterpret_cast<const uint64_t*>(st + 2), n, S);
@@ -322,8 +478,12 @@ static int schedule_step(dws_model* m, float* x, int kind, int S, const float* n
     return DWS_OK;
 }
 
+// e null: dws_sampler_run_schedule.  e given: dws_sampler_run_edit -- the run starts at e->start_step (the initial value
+// of the device step counter, and the number of replays), optionally from a q-sample of x, and with `known` / `mask`
+// every step ends in the replacement of the known region (the edited step, a graph of its own).
 int sampler_run_schedule(dws_model* m, float* x, int kind, int S, const float* net_steps, const float* coef,
-                         const float* noise, uint64_t seed, int init_from_seed, int use_graph, hipStream_t s) {
+                         const float* noise, uint64_t seed, int init_from_seed, int use_graph,
+                         const dws_sampler_edit* e, hipStream_t s) {
     DWS_CHECK(kind == DWS_SAMPLER_DDPM || kind == DWS_SAMPLER_DDIM, DWS_ERR_INVALID, "sampler: unknown kind %d", kind);
     DWS_CHECK(S >= 1, DWS_ERR_INVALID, "sampler: S = %d steps (needs S >= 1)", S);
     DWS_CHECK(net_steps && coef, DWS_ERR_INVALID, "sampler: null net_steps or coefficients");
@@ -337,6 +497,26 @@ int sampler_run_schedule(dws_model* m, float* x, int kind, int S, const float* n
     if (kind == DWS_SAMPLER_DDIM)
         for (int i = 0; i < S; ++i)
             DWS_CHECK(coef[S + i] > 0.f, DWS_ERR_INVALID, "sampler: DDIM k2[%d] = %g (needs k2 > 0)", i, (double)coef[S + i]);
+    const int start = e ? e->start_step : S - 1;
+    const bool masked = e && e->known && e->mask;
+    const bool qsample = e && e->start_mode == DWS_START_QSAMPLE;
+    if (e) {
+        DWS_CHECK(start >= 0 && start < S, DWS_ERR_INVALID, "sampler: start_step = %d (needs 0 .. %d)", start, S - 1);
+        DWS_CHECK((e->known != nullptr) == (e->mask != nullptr), DWS_ERR_INVALID,
+                  "sampler: known and mask come together (got %s only)", e->known ? "known" : "mask");
+        DWS_CHECK(!e->known_noise || masked, DWS_ERR_INVALID, "sampler: known_noise without known / mask");
+        DWS_CHECK(e->start_mode == DWS_START_AS_GIVEN || e->start_mode == DWS_START_QSAMPLE, DWS_ERR_INVALID,
+                  "sampler: unknown start mode %d", e->start_mode);
+        DWS_CHECK(!e->start_noise || qsample, DWS_ERR_INVALID, "sampler: start_noise without the q-sample start mode");
+        DWS_CHECK(e->edit_coef, DWS_ERR_INVALID, "sampler: null edit coefficients");
+        for (int i = 0; i < 4 * S; ++i)
+            DWS_CHECK(std::isfinite(e->edit_coef[i]), DWS_ERR_INVALID,
+                      "sampler: edit coefficient row %d, step %d = %g is not finite", i / S, i % S, (double)e->edit_coef[i]);
+        DWS_CHECK(!(qsample && init_from_seed), DWS_ERR_INVALID,
+                  "sampler: the q-sample start noises the given x; it cannot be combined with init_from_seed");
+        DWS_CHECK(!init_from_seed || start == S - 1, DWS_ERR_INVALID,
+                  "sampler: init_from_seed draws x_T, the state of step S-1 = %d (start_step = %d)", S - 1, start);
+    }
     DWS_CHECK(m->B > 0, DWS_ERR_STATE, "sampler before dws_model_prepare");
     DWS_CHECK(m->d.in_channels == m->d.out_channels, DWS_ERR_INVALID,
               "sampler needs in_channels == out_channels (x and eps share a shape, `generate.py:52`)");
@@ -353,6 +533,18 @@ int sampler_run_schedule(dws_model* m, float* x, int kind, int S, const float* n
         DWS_HIP(hipStreamSynchronize(s));
         m->sch_host_tables.swap(h);
     }
+    if (masked) {   // q1, q2 beside them, keyed the same way (n1, n2 stay on the host: arguments of the q-sample kernel)
+        const size_t nq = 2 * (size_t)S;
+        if (!m->sch_edit.p || nq != m->sch_host_edit.size() ||
+            std::memcmp(e->edit_coef, m->sch_host_edit.data(), nq * 4) != 0) {
+            DWS_TRY(m->sch_edit.ensure(nq * 4));
+            DWS_HIP(hipMemcpyAsync(m->sch_edit.p, e->edit_coef, nq * 4, hipMemcpyHostToDevice, s));
+            DWS_HIP(hipStreamSynchronize(s));
+            m->sch_host_edit.assign(e->edit_coef, e->edit_coef + nq);
+        }
+        DWS_TRY(m->sch_known.ensure(n * 4));
+        DWS_TRY(m->sch_mask.ensure((n + 3) / 4 * 4));
+    }
     DWS_TRY(m->smp_eps.ensure(n * 4));
     m->smp_eps_B = m->B; m->smp_eps_L = m->L;
     DWS_TRY(m->build_step_table(S, net_steps, s));   // the network's step-only part at net_steps (kept while they stay)
@@ -360,51 +552,72 @@ int sampler_run_schedule(dws_model* m, float* x, int kind, int S, const float* n
     int* st = static_cast<int*>(m->sch_state.p);
     const int blocks = (int)std::min<size_t>(ceil_div(n, 4 * 256), 4096);
     const auto aligned = [](const void* p) { return ((uintptr_t)p & 15) == 0; };
+    const float* known_noise = masked ? e->known_noise : nullptr;
+    const EditStep step{m->sch_edit.f(), m->sch_known.f(), static_cast<const uint8_t*>(m->sch_mask.p), known_noise};
+    const EditStep* ed = masked ? &step : nullptr;
+    // what precedes the steps, on the stream that runs them: the step counter at `start`, the known clip and the mask
+    // into their model-owned buffers, the q-sample of the start
+    const auto begin = [&](float* xr, hipStream_t q) -> int {
+        hipLaunchKernelGGL(smp_set_state_kernel, dim3(1), dim3(1), 0, q, st, start, seed);
+        if (masked) {
+            DWS_HIP(hipMemcpyAsync(m->sch_known.p, e->known, n * 4, hipMemcpyDeviceToDevice, q));
+            DWS_HIP(hipMemcpyAsync(m->sch_mask.p, e->mask, n, hipMemcpyDeviceToDevice, q));
+        }
+        if (qsample)
+            hipLaunchKernelGGL(smp_qsample_kernel, dim3(blocks), dim3(256), 0, q, xr, e->start_noise,
+                               e->edit_coef[2 * (size_t)S + start], e->edit_coef[3 * (size_t)S + start], n, seed,
+                               (uint32_t)(2 * S + 1));
+        return DWS_OK;
+    };
 
     if (!use_graph) {
-        const bool vec = n % 4 == 0 && aligned(x) && aligned(noise);
-        hipLaunchKernelGGL(smp_set_state_kernel, dim3(1), dim3(1), 0, s, st, S - 1, seed);
+        const bool vec = n % 4 == 0 && aligned(x) && aligned(noise) && aligned(known_noise);
         if (init_from_seed)
             hipLaunchKernelGGL(smp_fill_normal_kernel, dim3(blocks), dim3(256), 0, s, x, n, seed, (uint32_t)S);
-        for (int i = 0; i < S; ++i) DWS_TRY(schedule_step(m, x, kind, S, noise, vec, s));
+        DWS_TRY(begin(x, s));
+        for (int i = 0; i <= start; ++i) DWS_TRY(schedule_step(m, x, kind, S, noise, vec, ed, s));
         DWS_HIP(hipGetLastError());
         return DWS_OK;
     }
     // graph: x_T goes into the model-owned state buffer before the replays and x_0 comes out after them, the seed
-    // through the state word -- a new x or seed replays the same graph
+    // through the state word -- a new x or seed (or known clip, mask, start step) replays the same graph
     DWS_TRY(ensure_capture_stream(m));
     DWS_TRY(m->sch_x.ensure(n * 4));
     float* xs = m->sch_x.f();
-    const bool vec = n % 4 == 0 && aligned(noise);   // (xs and eps come from hipMalloc)
+    const bool vec = n % 4 == 0 && aligned(noise) && aligned(known_noise);   // (xs, eps, known, mask come from hipMalloc)
     hipStream_t cs = m->smp_stream;
     DWS_HIP(hipEventRecord(m->smp_ev_in, s));
     DWS_HIP(hipStreamWaitEvent(cs, m->smp_ev_in, 0));
-    hipLaunchKernelGGL(smp_set_state_kernel, dim3(1), dim3(1), 0, cs, st, S - 1, seed);
     if (init_from_seed)
         hipLaunchKernelGGL(smp_fill_normal_kernel, dim3(blocks), dim3(256), 0, cs, xs, n, seed, (uint32_t)S);
     else
         DWS_HIP(hipMemcpyAsync(xs, x, n * 4, hipMemcpyDeviceToDevice, cs));
+    DWS_TRY(begin(xs, cs));
     const dws_model::SchKey key{m->B, m->L, S, kind, vec ? 1 : 0, m->sch_tables.p, noise, m->smp_eps.p, xs, st,
-                                m->step_table_gen};
-    if (!m->sch_graph || !(key == m->sch_key)) {
-        if (m->sch_graph) hipGraphExecDestroy(m->sch_graph);
-        m->sch_graph = nullptr;
+                                m->step_table_gen, ed ? ed->table : nullptr, ed ? ed->known : nullptr,
+                                ed ? ed->mask : nullptr, known_noise};
+    // the edited step has a graph of its own: edited and unedited calls may alternate without a new capture
+    hipGraphExec_t& exec = masked ? m->edit_graph : m->sch_graph;
+    dws_model::SchKey& have = masked ? m->edit_key : m->sch_key;
+    if (!exec || !(key == have)) {
+        if (exec) hipGraphExecDestroy(exec);
+        exec = nullptr;
         hipGraph_t graph = nullptr;
         DWS_HIP(hipStreamBeginCapture(cs, hipStreamCaptureModeThreadLocal));
-        int rc = schedule_step(m, xs, kind, S, noise, vec, cs);
-        hipError_t e = hipStreamEndCapture(cs, &graph);
+        int rc = schedule_step(m, xs, kind, S, noise, vec, ed, cs);
+        hipError_t err = hipStreamEndCapture(cs, &graph);
         if (rc != DWS_OK) {
             if (graph) hipGraphDestroy(graph);
             return rc;
         }
-        DWS_HIP(e);
-        e = hipGraphInstantiate(&m->sch_graph, graph, nullptr, nullptr, 0);
+        DWS_HIP(err);
+        err = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
         hipGraphDestroy(graph);
-        DWS_HIP(e);
+        DWS_HIP(err);
         ++m->graphs_made;
-        m->sch_key = key;
+        have = key;
     }
-    for (int i = 0; i < S; ++i) DWS_HIP(hipGraphLaunch(m->sch_graph, cs));
+    for (int i = 0; i <= start; ++i) DWS_HIP(hipGraphLaunch(exec, cs));
     DWS_HIP(hipMemcpyAsync(x, xs, n * 4, hipMemcpyDeviceToDevice, cs));
     DWS_HIP(hipEventRecord(m->smp_ev_out, cs));
     DWS_HIP(hipStreamWaitEvent(s, m->smp_ev_out, 0));

@@ -183,10 +183,39 @@ def smooth_ckpt(path, min_ckpt, max_ckpt):
 
 
 # --------------------------------------------------------------------------- generate
+def _load_clip(dataset_cfg, stem, audio_length, conditional):
+    """``<dataset.data_path>/<stem>.wav`` as a [1, 1, audio_length] clip in [-1, 1], read as ``train.SpeechCommands``
+    reads one (int16 / 32768, int32 / 2^31, float as it is; first channel).  Unconditional: fitted to the segment the
+    way ``train.fix_length`` fits a clip; conditional: the length must be the mel's."""
+    from scipy.io import wavfile
+    from .train import fix_length
+    path = os.path.join(str(dataset_cfg["data_path"]), f"{stem}.wav")
+    sr, x = wavfile.read(path)
+    if sr != dataset_cfg["sampling_rate"]:
+        raise ValueError("{} SR doesn't match target {} SR".format(sr, dataset_cfg["sampling_rate"]))
+    if x.dtype == np.int16:
+        x = x.astype(np.float32) / 32768.0
+    elif x.dtype == np.int32:
+        x = x.astype(np.float32) / 2147483648.0
+    else:
+        x = x.astype(np.float32)
+    if x.ndim == 2:
+        x = x[:, 0]
+    t = torch.from_numpy(np.ascontiguousarray(x)).unsqueeze(0)
+    if conditional:
+        if t.shape[1] != audio_length:
+            raise ValueError(f"{path} has {t.shape[1]} samples; the mel condition needs mel frames x hop_length = "
+                             f"{audio_length}")
+    else:
+        t = fix_length(t, audio_length)
+    return t.unsqueeze(0)
+
+
 @torch.no_grad()
 def generate(rank, diffusion_cfg, model_cfg, dataset_cfg, ckpt_iter="max", n_samples=1, name=None, batch_size=None,
              ckpt_smooth=None, mel_path=None, mel_name=None, dataloader=None, exp_root="exp", seed=None,
-             written=None, precision=None, sampler="ddpm", steps=None, eta=0.0):
+             written=None, precision=None, sampler="ddpm", steps=None, eta=0.0, known_name=None, keep=None,
+             start_name=None, start_step=None, start_noise=True):
     """``generate.py:58-200``.  ``ckpt_iter`` may additionally be ``"init"``: seeded random weights
     (no checkpoint), for smoke runs without trained weights.  ``precision`` (not in the reference; CLI:
     ``+engine.precision=bf16x6|f16x3``): the engine's opt-in matrix arithmetic, see ``include/dws.h``.
@@ -194,11 +223,25 @@ def generate(rank, diffusion_cfg, model_cfg, dataset_cfg, ckpt_iter="max", n_sam
     ``sampler`` (not in the reference; CLI ``generate.sampler=...``): ``ddpm`` (default) is the reference's loop,
     including its use of ``diffusion.beta``; ``aligned`` runs the short ``diffusion.beta`` schedule with the network at
     the aligned fractional training steps (``sampling.align_steps``); ``ddim`` runs DDIM over ``steps`` of the T
-    training steps with ``eta`` (default 0)."""
+    training steps with ``eta`` (default 0).
+
+    Editing (not in the reference; with any ``sampler``): ``known_name`` (a wav stem under ``dataset.data_path``) with
+    ``keep`` (``[start, end)`` sample spans of it that are kept) inpaints the rest -- every clip of the batch gets the
+    same known audio and its own noise; ``start_name`` with ``start_step`` starts the loop at that step from the wav,
+    noised to the step's level first unless ``start_noise`` is false (then the wav is the state as given)."""
     from .models import construct_model
-    from .sampling import calc_diffusion_hyperparams, ddim_steps, sampling, sampling_aligned, sampling_ddim
+    from .sampling import (calc_diffusion_hyperparams, ddim_steps, sampling, sampling_aligned, sampling_ddim,
+                           spans_to_mask)
     from scipy.io.wavfile import write as wavwrite
 
+    if known_name is not None and not keep:
+        raise ValueError("generate.known_name needs generate.keep: at least one [start, end) span of kept samples")
+    if keep and known_name is None:
+        raise ValueError("generate.keep needs generate.known_name (the wav whose samples are kept)")
+    if start_name is not None and start_step is None:
+        raise ValueError("generate.start_name needs generate.start_step (the step the loop starts at)")
+    if start_step is not None and start_name is None:
+        raise ValueError("generate.start_step needs generate.start_name (the wav the loop starts from)")
     sampler = sampler or "ddpm"
     if sampler not in ("ddpm", "aligned", "ddim"):
         raise ValueError(f"generate.sampler={sampler!r}: expected ddpm, aligned or ddim")
@@ -262,6 +305,14 @@ def generate(rank, diffusion_cfg, model_cfg, dataset_cfg, ckpt_iter="max", n_sam
         audio_length = mel.shape[-1] * dataset_cfg["hop_length"]
     else:
         audio_length, mel = dataset_cfg["segment_length"], None
+    edit = {}
+    if known_name is not None:
+        edit["known"] = _load_clip(dataset_cfg, known_name, audio_length, mel is not None)
+        edit["mask"] = spans_to_mask((batch_size, 1, audio_length), keep)
+    if start_name is not None:
+        edit["x_start"] = _load_clip(dataset_cfg, start_name, audio_length, mel is not None)
+        edit["start_step"] = start_step
+        edit["start_noise"] = None if start_noise else False
 
     t0 = time.perf_counter()
     out = []
@@ -269,11 +320,11 @@ def generate(rank, diffusion_cfg, model_cfg, dataset_cfg, ckpt_iter="max", n_sam
         s = None if seed is None else seed + 1000 * rank + i
         size = (batch_size, 1, audio_length)
         if sampler == "aligned":
-            out.append(sampling_aligned(net, size, diffusion_cfg, condition=mel, seed=s))
+            out.append(sampling_aligned(net, size, diffusion_cfg, condition=mel, seed=s, **edit))
         elif sampler == "ddim":
-            out.append(sampling_ddim(net, size, dh_train, steps, eta=float(eta or 0.0), condition=mel, seed=s))
+            out.append(sampling_ddim(net, size, dh_train, steps, eta=float(eta or 0.0), condition=mel, seed=s, **edit))
         else:
-            out.append(sampling(net, size, dh, condition=mel, seed=s))
+            out.append(sampling(net, size, dh, condition=mel, seed=s, **edit))
     generated_audio = torch.cat(out, dim=0)
     torch.cuda.synchronize()
     print(f"generated {n_samples} samples shape {tuple(generated_audio.shape)} at iteration {ckpt_iter} in "

@@ -56,8 +56,89 @@ def _prepare_run(net, size, steps, condition, x_T, noise, seed):
     return x, init, nz, seed
 
 
+def edit_coefficients(levels):
+    """Tables of the editing modes over the S steps of a run: float32 [4][S] = q1, q2, n1, n2 with ``level[s]`` the
+    cumulative alpha_bar of step s (DDPM: the run's ``Alpha_bar``; DDIM: ``Alpha_bar_train[tau]``) and
+    ``p_s = level[s-1]`` (``p_0 = 1``) the level the state is at after step s: ``q1 = sqrt(p)``, ``q2 = sqrt(1-p)``,
+    ``n1 = sqrt(level)``, ``n2 = sqrt(1-level)``, in float64 from the float32 levels, rounded once (the convention of
+    ``ddim_coefficients``, whose k3 row q1 equals)."""
+    if isinstance(levels, torch.Tensor):
+        levels = levels.detach().cpu().numpy()
+    lv = np.asarray(levels, dtype=np.float32).astype(np.float64).reshape(-1)
+    if lv.shape[0] < 1:
+        raise ValueError("edit_coefficients: no levels")
+    p = np.concatenate([[1.0], lv[:-1]])
+    return np.stack([np.sqrt(p), np.sqrt(1.0 - p), np.sqrt(lv), np.sqrt(1.0 - lv)]).astype(np.float32)
+
+
+def spans_to_mask(size, spans):
+    """Bool mask ``[1, 1, L]`` (broadcastable to ``size = (B, C, L)``) that is True inside the ``[start, end)`` sample
+    spans; overlapping spans unite, no span gives an all-False mask.  A continuation keeps one span ``[0, n)``."""
+    L = int(size[-1])
+    m = torch.zeros(1, 1, L, dtype=torch.bool)
+    for sp in spans:
+        if len(sp) != 2 or any(int(v) != v for v in sp) or not 0 <= sp[0] <= sp[1] <= L:
+            raise ValueError(f"spans_to_mask: span {list(sp)} is not [start, end) with 0 <= start <= end <= {L}")
+        m[..., int(sp[0]):int(sp[1])] = True
+    return m
+
+
+def _check_edit(size, S, x_T, known=None, mask=None, known_noise=None, x_start=None, start_step=None,
+                start_noise=None):
+    """Argument checks of the editing modes, all on the host and before any GPU work (ValueError).  Returns
+    (known [B,C,L] float32 | None, mask [B,C,L] uint8 | None, known_noise | None, x_start [B,C,L] | None, start_step,
+    start_noise tensor | None, q-sample?)."""
+    size = tuple(int(v) for v in size)
+
+    def expand(name, t, dtype=None):
+        t = torch.as_tensor(t).detach()
+        try:
+            ok = torch.broadcast_shapes(tuple(t.shape), size) == size
+        except RuntimeError:
+            ok = False
+        if not ok:
+            raise ValueError(f"sampler: {name} of shape {tuple(t.shape)} does not broadcast to {size}")
+        return t.expand(size)
+
+    def exact(name, t, shape):
+        t = torch.as_tensor(t).detach()
+        if tuple(t.shape) != shape:
+            raise ValueError(f"sampler: {name} has shape {tuple(t.shape)}, expected {shape}")
+        return t
+
+    if (known is None) != (mask is None):
+        raise ValueError("sampler: known= and mask= come together")
+    if known_noise is not None and known is None:
+        raise ValueError("sampler: known_noise= without known= / mask=")
+    if known is not None:
+        known = expand("known", known)
+        mask = expand("mask", mask)
+        if mask.dtype != torch.bool and not bool(((mask == 0) | (mask == 1)).all()):
+            raise ValueError("sampler: mask must be bool or hold only 0 and 1 (soft masks are not built)")
+        mask = mask != 0
+        if known_noise is not None:
+            known_noise = exact("known_noise", known_noise, (S,) + size)
+    if x_start is None:
+        if start_step is not None or start_noise is not None:
+            raise ValueError("sampler: start_step= / start_noise= without x_start=")
+        return known, mask, known_noise, None, S - 1, None, False
+    if x_T is not None:
+        raise ValueError("sampler: x_start= and x_T= are two initial states; give one")
+    x_start = expand("x_start", x_start)
+    start_step = S - 1 if start_step is None else start_step
+    if isinstance(start_step, bool) or int(start_step) != start_step or not 0 <= start_step <= S - 1:
+        raise ValueError(f"sampler: start_step = {start_step!r} (needs an integer in 0..{S - 1})")
+    qsample = start_noise is not False
+    if start_noise is None or start_noise is False:
+        start_noise = None
+    else:
+        start_noise = exact("start_noise", start_noise, size)
+    return known, mask, known_noise, x_start, int(start_step), start_noise, qsample
+
+
 def sampling(net, size, diffusion_hyperparams, condition=None, *, x_T=None, noise=None, seed=None,
-             use_graph=True, net_steps=None):
+             use_graph=True, net_steps=None, known=None, mask=None, known_noise=None, x_start=None, start_step=None,
+             start_noise=None):
     """``x_0 = sampling(net, (B, C, L), dh, condition)`` as in ``generate.py:23-55``.
 
     Extra keyword-only arguments (not in the reference):
@@ -68,13 +149,30 @@ def sampling(net, size, diffusion_hyperparams, condition=None, *, x_T=None, nois
       net_steps  float[T]: the network sees ``net_steps[t]`` at step t instead of t, with the DDPM update of ``dh``
              unchanged (e.g. ``align_steps`` for DiffWave's fast schedule; ``dws_sampler_run_schedule``).  Not the
              reference's loop.
+    Editing (``dws_sampler_run_edit``; all off by default, and then this is exactly the path above):
+      known, mask  inpainting / continuation by replacement: ``known`` audio and ``mask`` (bool or 0/1, non-zero =
+             known), both broadcastable to [B,C,L].  After every step the known region of the state is overwritten
+             with ``known`` noised to the level the state is at; the result holds ``known`` exactly where mask is set.
+      known_noise  injected noise of that replacement, [T,B,C,L] (parity mode; default Philox)
+      x_start, start_step  partial start: run steps ``start_step .. 0`` only (default T-1) from ``x_start``
+      start_noise  None: ``x_start`` is clean audio, noised to step ``start_step`` with Philox noise first (q-sample);
+             a [B,C,L] tensor: the same with this noise; False: ``x_start`` is the state at ``start_step`` as given.
+      Without ``net_steps`` an edited run goes through the schedule entry with ``net_steps = 0..T-1`` (bit-identical
+      to ``dws_sampler_run``).
     """
     dh = diffusion_hyperparams
     T, Alpha, Alpha_bar, Sigma = dh["T"], dh["Alpha"], dh["Alpha_bar"], dh["Sigma"]
     assert len(Alpha) == T and len(Alpha_bar) == T and len(Sigma) == T and len(size) == 3
+    edit = dict(known=known, mask=mask, known_noise=known_noise, x_start=x_start, start_step=start_step,
+                start_noise=start_noise)
+    if all(v is None for v in edit.values()):
+        edit = None
+    elif net_steps is None:
+        net_steps = np.arange(T, dtype=np.float32)
     if net_steps is not None:
         coef = np.stack([_host_table(Alpha)[0], _host_table(Alpha_bar)[0], _host_table(Sigma)[0]])
-        return _run_schedule(net, size, _lib.DWS_SAMPLER_DDPM, net_steps, coef, condition, x_T, noise, seed, use_graph)
+        return _run_schedule(net, size, _lib.DWS_SAMPLER_DDPM, net_steps, coef, condition, x_T, noise, seed, use_graph,
+                             edit=edit, levels=coef[1])
     lib = _lib.load()
     with torch.no_grad():
         x, init, nz, seed = _prepare_run(net, size, T, condition, x_T, noise, seed)
@@ -87,22 +185,40 @@ def sampling(net, size, diffusion_hyperparams, condition=None, *, x_T=None, nois
     return x
 
 
-def _run_schedule(net, size, kind, net_steps, coef, condition, x_T, noise, seed, use_graph):
-    """``dws_sampler_run_schedule``: S steps s = S-1..0, the network at ``net_steps[s]``, update tables ``coef``."""
+def _run_schedule(net, size, kind, net_steps, coef, condition, x_T, noise, seed, use_graph, edit=None, levels=None):
+    """``dws_sampler_run_schedule``: S steps s = S-1..0, the network at ``net_steps[s]``, update tables ``coef``.
+    ``edit``: the editing arguments of ``sampling`` (-> ``dws_sampler_run_edit``), ``levels`` the run's alpha_bar."""
     assert len(size) == 3
     steps = np.ascontiguousarray(np.asarray(net_steps, dtype=np.float32).reshape(-1))
     S = steps.shape[0]
     coef = np.ascontiguousarray(np.asarray(coef, dtype=np.float32))
     if S < 1 or coef.shape != ((5 if kind == _lib.DWS_SAMPLER_DDIM else 3), S):
         raise ValueError(f"sampler: {S} net steps with coefficient tables of shape {coef.shape}")
+    if edit is not None:
+        known, mask, known_noise, x_start, start_step, start_noise, qsample = _check_edit(size, S, x_T, **edit)
+        if x_start is not None:
+            x_T = x_start
     lib = _lib.load()
     fp = ctypes.POINTER(ctypes.c_float)
     with torch.no_grad():
         x, init, nz, seed = _prepare_run(net, size, S, condition, x_T, noise, seed)
-        _lib.check(lib.dws_sampler_run_schedule(net._handle, x.data_ptr(), kind, S, steps.ctypes.data_as(fp),
+        if edit is None:
+            _lib.check(lib.dws_sampler_run_schedule(net._handle, x.data_ptr(), kind, S, steps.ctypes.data_as(fp),
+                                                    coef.ctypes.data_as(fp), _lib.ptr(nz), seed, init,
+                                                    1 if use_graph else 0, _lib.current_stream()))
+        else:
+            dev = x.device
+            q = np.ascontiguousarray(edit_coefficients(levels))
+            on_dev = lambda t, dt: None if t is None else t.to(device=dev, dtype=dt).contiguous()
+            known, known_noise, start_noise = (on_dev(t, torch.float32) for t in (known, known_noise, start_noise))
+            mask = on_dev(mask, torch.uint8)
+            ed = _lib.SamplerEdit(q.ctypes.data_as(fp), _lib.ptr(known), _lib.ptr(mask), _lib.ptr(known_noise),
+                                  _lib.ptr(start_noise), start_step,
+                                  _lib.DWS_START_QSAMPLE if qsample else _lib.DWS_START_AS_GIVEN)
+            _lib.check(lib.dws_sampler_run_edit(net._handle, x.data_ptr(), kind, S, steps.ctypes.data_as(fp),
                                                 coef.ctypes.data_as(fp), _lib.ptr(nz), seed, init,
-                                                1 if use_graph else 0, _lib.current_stream()))
-        torch.cuda.current_stream().synchronize()  # nz must outlive the enqueued work
+                                                1 if use_graph else 0, ctypes.byref(ed), _lib.current_stream()))
+        torch.cuda.current_stream().synchronize()  # nz (and the editing tensors) must outlive the enqueued work
     return x
 
 
@@ -177,14 +293,19 @@ def ddim_coefficients(alpha_bar, tau, eta):
 
 
 def sampling_ddim(net, size, dh_train, steps, eta=0.0, condition=None, *, x_T=None, noise=None, seed=None,
-                  use_graph=True):
+                  use_graph=True, known=None, mask=None, known_noise=None, x_start=None, start_step=None,
+                  start_noise=None):
     """DDIM over ``ddim_steps(T, steps)`` of the training schedule ``dh_train`` (``steps``: S or an explicit list),
     deterministic for ``eta = 0``.  ``noise``: injected z, [S, B, C, L] (``noise[s]`` is used after step s > 0).
-    Not the reference's loop."""
+    The editing arguments are those of ``sampling`` (levels: ``Alpha_bar[tau]``).  Not the reference's loop."""
     tau = ddim_steps(dh_train["T"], steps)
     coef = ddim_coefficients(dh_train["Alpha_bar"], tau, eta)
+    edit = dict(known=known, mask=mask, known_noise=known_noise, x_start=x_start, start_step=start_step,
+                start_noise=start_noise)
+    if all(v is None for v in edit.values()):
+        edit = None
     return _run_schedule(net, size, _lib.DWS_SAMPLER_DDIM, np.asarray(tau, dtype=np.float32), coef, condition, x_T,
-                         noise, seed, use_graph)
+                         noise, seed, use_graph, edit=edit, levels=_host_table(dh_train["Alpha_bar"])[0][tau])
 
 
 def sampling_aligned(net, size, diffusion_cfg, condition=None, **kw):

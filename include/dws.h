@@ -280,6 +280,60 @@ int dws_sampler_run_schedule(dws_model* m, float* x, int32_t kind, int32_t S, co
                              const float* coef, const float* noise, uint64_t seed, int32_t init_from_seed,
                              int32_t use_graph, void* stream);
 
+/* Editing runs on the few-step entry (not the reference's loop): inpainting / continuation by
+ * known-region replacement (Song et al., ICLR 2021, "imputation"; the base case of RePaint) and
+ * a partial start (DiffWave's zero-shot denoising and latent interpolation, SDEdit).  Everything
+ * dws_sampler_run_schedule takes means the same here; `edit` adds:
+ *
+ *   edit_coef    HOST float[4][S] = q1, q2, n1, n2 (sampling.edit_coefficients).  With level[s]
+ *                the cumulative alpha_bar of step s of this run and p_s = level[s-1] (p_0 = 1)
+ *                the level the state is at AFTER step s:  q1 = sqrt(p), q2 = sqrt(1 - p)
+ *                (q1[0] = 1, q2[0] = 0), n1 = sqrt(level), n2 = sqrt(1 - level).
+ *   known, mask  DEVICE float [B, C, L] and uint8 [B, C, L] (non-zero = known), both or neither.
+ *                After the ordinary update of step s has produced v for an element:
+ *                  if mask:  v = (s > 0) ? (q1[s] * known) + (q2[s] * zk) : known
+ *                two products and one sum, each rounded once; at s = 0 the known samples come out
+ *                bitwise equal to `known`.  Where mask is zero the element gets exactly the value
+ *                dws_sampler_run_schedule would have written.
+ *   known_noise  optional DEVICE [S, B, C, L]: known_noise[s] is zk of step s (s > 0).  NULL ->
+ *                Philox.
+ *   start_step   s0 in 0 .. S-1: steps s0 .. 0 run (s0 + 1 network evaluations).  S-1 = a whole run.
+ *   start_mode   DWS_START_AS_GIVEN: x is the state at step s0 (with s0 = S-1: x_T).
+ *                DWS_START_QSAMPLE: x holds clean audio and the run first forms
+ *                  x = (n1[s0] * x) + (n2[s0] * z0)       (same rounding rule)
+ *   start_noise  optional DEVICE [B, C, L]: z0.  NULL -> Philox.  Only with DWS_START_QSAMPLE.
+ *
+ * Philox streams of a run, normal4(seed, stream, group of four along the flattened [B, C, L]):
+ * the update noise of step s is stream s and a drawn x_T stream S, as in dws_sampler_run_schedule;
+ * the known-region noise after step s is stream S + 1 + s; the start noise is stream 2S + 1.  No
+ * stream is used twice in a run.
+ *
+ * With use_graph, `known` and `mask` are copied into model-owned buffers before the replays (like
+ * x), q1 / q2 sit on the device beside the update tables, keyed on their contents, and
+ * start_step only sets the initial value of the device step counter and the number of replays; the
+ * q-sample runs once before the replays.  So a new seed, x, known clip, mask or start step REPLAYS
+ * the graph captured for that (B, L, S, kind, tables, step table, noise / known_noise pointers,
+ * replacement on / off); another of those captures anew.  The step with the replacement is a graph
+ * of its own beside the unedited one (a call without known / mask replays dws_sampler_run_schedule's
+ * graph), so the two kinds of call alternate without a capture; tap "sampler_graphs" counts both.
+ * Bad input -> DWS_ERR_INVALID: start_step outside 0 .. S-1, known without mask or the reverse,
+ * known_noise without known, non-finite or missing edit coefficients, DWS_START_QSAMPLE or a
+ * start_step other than S-1 together with init_from_seed, start_noise without DWS_START_QSAMPLE. */
+#define DWS_START_AS_GIVEN 0
+#define DWS_START_QSAMPLE  1
+typedef struct dws_sampler_edit {
+    const float*   edit_coef;     /* HOST   float[4][S] */
+    const float*   known;         /* DEVICE float[B, C, L] or NULL */
+    const uint8_t* mask;          /* DEVICE uint8[B, C, L] or NULL */
+    const float*   known_noise;   /* DEVICE float[S, B, C, L] or NULL */
+    const float*   start_noise;   /* DEVICE float[B, C, L] or NULL */
+    int32_t        start_step;
+    int32_t        start_mode;
+} dws_sampler_edit;
+int dws_sampler_run_edit(dws_model* m, float* x, int32_t kind, int32_t S, const float* net_steps,
+                         const float* coef, const float* noise, uint64_t seed, int32_t init_from_seed,
+                         int32_t use_graph, const dws_sampler_edit* edit, void* stream);
+
 /* Mel-spectrogram front-end of the vocoding path: TacotronSTFT.mel_spectrogram
  * (`dataloaders/stft.py:196-244`) as called by Mel2Samp.get_mel (`dataloaders/mel2samp.py:76-82`) and
  * generate.py:147-153.  audio [B][T] in [-1, 1]; window [n_fft] (the Hann window, centre-padded to

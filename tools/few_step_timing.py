@@ -7,7 +7,8 @@ Legs: config 4 (unet_d32_n6_T50_cond, B = 32, mel [1, 80, 63]) aligned S = 6 und
 (wnet_h256_d36_T200, B = 16) DDIM S = 50 under bf16x6 (the headline arithmetic).  Per leg: the first call (step-table
 build + capture + instantiate + S replays), repeat calls with a new seed and a new output tensor (replays only),
 the per-step time of the plain sampler's captured step (dws_sampler_steps) and the full-T dws_sampler_run call.
-Capture + instantiate alone: `capture_cost`."""
+Capture + instantiate alone: `capture_cost`.  `--legs edit_c4,edit_c2` (not in the default list): the unedited schedule
+call against the same call with a half-clip continuation mask (dws_sampler_run_edit), alternating in one process."""
 import argparse
 import json
 import os
@@ -137,6 +138,53 @@ def capture_cost(cfg_name, precision, kind, S, repeats):
     return rec
 
 
+def edit_leg(name, cfg_name, precision, kind, S, repeats):
+    """The editing step's cost: in one process and alternating, the unedited schedule call (the yardstick: the same
+    code path as without the editing modes) and the same call with a half-clip continuation mask; every call a new
+    seed.  The margin for the difference of the medians is the unedited leg's own min-max spread.  Also first call -
+    repeat call of the edited graph (capture + instantiate; the step table exists by then)."""
+    from benchlib.configs import CONFIGS, build_model
+    from diffwave_sashimi_amd.sampling import calc_diffusion_hyperparams, sampling_aligned, sampling_ddim, spans_to_mask
+    cfg = CONFIGS[cfg_name]
+    dev = torch.device("cuda")
+    net = build_model(cfg, dev)
+    if precision != "f32":
+        net.set_option("precision", precision)
+    B, L = cfg["B"], cfg["L"]
+    size = (B, 1, L)
+    mel = None
+    if "Tmel" in cfg:
+        g = torch.Generator().manual_seed(2)
+        mel = (torch.rand(1, 80, cfg["Tmel"], generator=g) * 13.5 - 11.5).to(dev)
+    d = cfg["diffusion"]
+    dh_train = calc_diffusion_hyperparams(d["T"], d["beta_0"], d["beta_T"])
+    g = torch.Generator().manual_seed(3)
+    edit = dict(known=(torch.rand(size, generator=g) * 2 - 1).to(dev), mask=spans_to_mask(size, [[0, L // 2]]).to(dev))
+    if kind == "aligned":
+        dcfg = dict(d, beta=[1e-4, 1e-3, 1e-2, 0.05, 0.2, 0.5])
+        call = lambda seed, **kw: sampling_aligned(net, size, dcfg, mel, seed=seed, **kw)
+    else:
+        call = lambda seed, **kw: sampling_ddim(net, size, dh_train, S, 0.0, mel, seed=seed, **kw)
+    call(1), call(2)                                        # warm-up: code objects, step table, the unedited graph
+    first = _clock(lambda: call(100, **edit))
+    call(101, **edit)
+    plain, edited = [], []
+    for i in range(repeats):
+        plain.append(_clock(lambda: call(200 + i)))
+        edited.append(_clock(lambda: call(300 + i, **edit)))
+    graphs = int(net.read_tap("sampler_graphs", (1,)).item())
+    mp, me = statistics.median(plain), statistics.median(edited)
+    rec = dict(leg=name, config=cfg_name, precision=precision, sampler=kind, S=S, B=B, L=L, mask="first half kept",
+               unedited_call=_stats(plain), edited_call=_stats(edited),
+               edited_minus_unedited_median_ms=round(me - mp, 3),
+               unedited_spread_ms=round(max(plain) - min(plain), 3),
+               edited_first_call=round(first, 3), edited_first_minus_repeat_ms=round(first - me, 3),
+               graphs_after_repeats=graphs)
+    del net
+    torch.cuda.empty_cache()
+    return rec
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--repeats", type=int, default=5)
@@ -148,6 +196,10 @@ def main():
         "c4_f32": lambda: leg("config4 aligned S=6 f32", "unet_d32_n6_T50_cond", "f32", "aligned", 6, args.repeats),
         "c4_bx6": lambda: leg("config4 aligned S=6 bf16x6", "unet_d32_n6_T50_cond", "bf16x6", "aligned", 6, args.repeats),
         "c2_ddim50": lambda: leg("config2 DDIM S=50 bf16x6", "wnet_h256_d36_T200", "bf16x6", "ddim", 50, args.repeats),
+        "edit_c4": lambda: edit_leg("config4 aligned S=6 f32, continuation", "unet_d32_n6_T50_cond", "f32", "aligned", 6,
+                                    args.repeats),
+        "edit_c2": lambda: edit_leg("config2 DDIM S=50 bf16x6, continuation", "wnet_h256_d36_T200", "bf16x6", "ddim", 50,
+                                    args.repeats),
         "capture": lambda: [capture_cost("unet_d32_n6_T50_cond", "f32", "ddim", 6, args.repeats),
                             capture_cost("wnet_h256_d36_T200", "bf16x6", "ddim", 50, args.repeats)],
     }
