@@ -7,16 +7,14 @@
 // `s4.py:1388`) and, in set_condition(), the mel conditioner terms.
 // The per-step path is then LN+emb -> rocFFT r2c -> spectrum multiply -> c2r ->
 // D-skip+GELU -> 1x1+GLU+residual -> LN -> FF -> residual per block.
-#include <rocfft/rocfft.h>
-
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
-#include <mutex>
 
 #include "conditioner.h"
 #include "fftconv.h"
 #include "model.h"
+#include "s4_kernel_chain.h"
 #include "sashimi.h"
 #include "sashimi_mfma.h"
 #include "sashimi_train.h"
@@ -24,79 +22,6 @@
 #include "wavenet_backward.h"
 
 namespace dws {
-
-#define DWS_FFT(expr)                                                                                  \
-    do {                                                                                               \
-        rocfft_status _r = (expr);                                                                     \
-        if (_r != rocfft_status_success)                                                               \
-            return set_error(DWS_ERR_HIP, "%s failed: rocfft_status %d (%s:%d)", #expr, (int)_r, __FILE__, __LINE__); \
-    } while (0)
-
-// rocFFT, through its native API: batched 1-D real transforms, out of place, unscaled, rows packed back to back (the
-// defaults of a plan without a description: input distance n reals / n/2+1 complex, output the other way round).  Used
-// where the fused LDS FFT does not apply: the irfft(n = L) of the kernel generation (`s4.py:796-805`) and its adjoint,
-// and the R2C / C2R pair of stage lengths the fused kernels do not cover (odd lengths; more than 16384 taps).
-// A plan owns its work buffer and execution info, so rocfft_execute never allocates (it may run inside a stream capture).
-struct RocfftPlan {
-    rocfft_plan plan = nullptr;
-    rocfft_execution_info info = nullptr;
-    DevBuf work;
-};
-
-// rocfft_setup() / rocfft_cleanup() act on process-global state (plan repository, RTC cache, logging): set up once per
-// process; never torn down from a model's destructor -- another model in the process may still hold plans.
-static int rocfft_setup_once() {
-    static std::once_flag once;
-    static rocfft_status st = rocfft_status_success;
-    std::call_once(once, [] { st = rocfft_setup(); });
-    if (st != rocfft_status_success) return set_error(DWS_ERR_HIP, "rocfft_setup failed: rocfft_status %d", (int)st);
-    return DWS_OK;
-}
-
-struct FftPlans {
-    std::map<std::tuple<int, int, int>, RocfftPlan*> plans;  // (type, n, batch)
-    ~FftPlans() {
-        for (auto& kv : plans) {
-            if (kv.second->info) rocfft_execution_info_destroy(kv.second->info);
-            if (kv.second->plan) rocfft_plan_destroy(kv.second->plan);
-            delete kv.second;
-        }
-    }
-    // type 0: R2C rows of n reals (dist n) -> n/2+1 complex; type 1: C2R n/2+1 complex -> n reals (dist n)
-    int get(int type, int n, int batch, RocfftPlan** out) {
-        auto key = std::make_tuple(type, n, batch);
-        auto it = plans.find(key);
-        if (it == plans.end()) {
-            DWS_TRY(rocfft_setup_once());
-            RocfftPlan* p = new RocfftPlan();
-            it = plans.emplace(key, p).first;      // owned by the map from here on (freed with it, also after an error)
-            const size_t len[1] = {(size_t)n};
-            DWS_FFT(rocfft_plan_create(&p->plan, rocfft_placement_notinplace,
-                                       type == 0 ? rocfft_transform_type_real_forward : rocfft_transform_type_real_inverse,
-                                       rocfft_precision_single, 1, len, (size_t)batch, nullptr));
-            size_t wbytes = 0;
-            DWS_FFT(rocfft_plan_get_work_buffer_size(p->plan, &wbytes));
-            DWS_FFT(rocfft_execution_info_create(&p->info));
-            if (wbytes) {
-                DWS_TRY(p->work.ensure(wbytes));
-                DWS_FFT(rocfft_execution_info_set_work_buffer(p->info, p->work.p, wbytes));
-            }
-        }
-        DWS_CHECK(it->second->plan && it->second->info, DWS_ERR_HIP, "rocFFT plan (type %d, n %d, batch %d) was not created", type, n, batch);
-        *out = it->second;
-        return DWS_OK;
-    }
-    // one batched transform on stream s (the real inverse may use its input as scratch, as rocFFT documents)
-    int exec(int type, int n, int batch, void* in, void* out, hipStream_t s) {
-        RocfftPlan* p = nullptr;
-        DWS_TRY(get(type, n, batch, &p));
-        DWS_FFT(rocfft_execution_info_set_stream(p->info, (void*)s));
-        void* ib[1] = {in};
-        void* ob[1] = {out};
-        DWS_FFT(rocfft_execute(p->plan, ib, ob, p->info));
-        return DWS_OK;
-    }
-};
 
 enum { L_BLOCK = 0, L_DOWN = 1, L_UP = 2 };
 
@@ -115,16 +40,13 @@ struct SLayer {
     DevBuf wscale_c6;            // f16x3: the three matrices' power-of-two scales
     bool mfma = false, mfma2 = false;
     DevBuf Kf;            // rocFFT path: [H][L+1] complex spectrum of the two-sided kernel (n = 2L)
-    DevBuf kfa, kfb, kfs; // fused path: pair-ordered spectrum at the power-of-two size (fftconv.h)
-    const void *kfa_v = nullptr, *kfb_v = nullptr, *kfs_v = nullptr;   // what the convolution reads: the buffers above, or this block's
-                                                                       // slice of its group's stacked spectra (KGroup)
+    S4Chain own;          // the block's kernel generation as a chain of its own (not used while the block belongs to a group);
+                          // own.kfa / kfb / kfs also hold the first of the segmented path's three spectra
+    const void *kfa_v = nullptr, *kfb_v = nullptr, *kfs_v = nullptr;   // fused path: what the convolution reads -- this block's rows
+                                                                       // of its chain's pair-ordered spectra (take_spectra)
     int grp = -1, gidx = 0;   // training: stacked kernel generation -- group (blocks of one shape) and position in it
     int log2m = 0;        // > 0: fused LDS FFT convolution is used for this block
     bool seg = false;     // stage longer than the largest LDS transform: segmented fused path (fftconv_seg_kernel)
-    // training: the Cauchy products of the kernel generation (v, w dt, dt, r: `s4.py:740-775`) are kept per block so the
-    // backward does not regenerate them (one Cauchy forward per block and step less); valid for commit cache_version
-    DevBuf t_cv, t_cwdt, t_cdt, t_cr;
-    uint64_t cache_version = ~0ull;
     DevBuf kfa_c, kfb_c, kfs_c, kfa_a, kfb_a, kfs_a;   // seg: spectra of the causal / anti-causal kernel half, shifted
     DevBuf melW0, melW1, melWc, melc;
     DevBuf out;           // activation produced by this layer
@@ -153,10 +75,6 @@ struct Stage {
     DevBuf Gf;               // training on rocFFT: the spectrum of the block's input u, recomputed in the backward ([B][H][L+1])
 };
 
-struct FftTables {
-    DevBuf tw, twn, twp;
-};
-
 // Training: the S4 blocks of one shape (H, L) -- 12 + 12 + 6 in BASELINE config 5 -- generate their kernels, and run the adjoint of
 // that generation, STACKED along H: every launch of the chain (s4_prep, Cauchy, Woodbury, rocFFT, re-placement, spectrum, pair
 // order; and backwards) is indexed by a row h < H and is launched once over n * H rows.  Per block the chain is ~12 launches of
@@ -164,37 +82,32 @@ struct FftTables {
 struct KGroup {
     int H = 0, L = 0, log2m = 0;
     std::vector<SLayer*> layers;
+    S4Chain chain;                         // over Ht rows; chain.par points at the stacked parameters below
     DevBuf C, Bp, P, iwr, wim, logdt;      // stacked parameters: [2][Ht][N] complex, [Ht][N] complex x 2, [Ht][N] x 2, [Ht]
-    DevBuf v, wdt, dt, r, kf;              // s4_prep / Cauchy products (read again by the adjoint), spectrum [2][Ht][Lh]
-    DevBuf kfa, kfb, kfs;                  // pair-ordered spectra [Ht][M/2] x 2, [Ht][3]: a block reads its H rows
     DevBuf dKf, gC, gB, gP, giwr, gwim, glogdt, gD;   // adjoint: stacked spectrum gradient, stacked parameter gradients
     int pending = 0;                       // blocks of this backward whose correlation has not run yet
     CopyBatch stack, unstack;
     int Ht() const { return H * (int)layers.size(); }
 };
 
-struct SashimiModel : dws_model {
+struct SashimiModel : dws_model, S4Workspace {
     int Cin, Cout, D, NL, E, FF, NS = 32, Ein, Emid, Eout, MB;
     bool cond, unet;
     std::vector<int> pool;
     std::vector<SLayer*> d_layers, c_layers, u_layers, all;
     std::vector<Stage*> stages;
     int pt_total = 0;
-    FftPlans fft;
-    std::map<int, FftTables*> tables;  // by log2(M)
     DevBuf Wi, Wt_all, bt_all, Wf, Af, freq;
     CopyBatch stack_fc_t, unstack_fc_t;   // per-layer fc_t tensors <-> their stacked buffers, one launch each
     bool freq_ready = false;
     DevBuf x_init, emb, h1, h2, part_t, nfin, scratch_out;
-    // commit scratch
-    DevBuf cv, cwdt, cdt, cr, ckf, ck, cK, cKf;
     int64_t melBm = 0;
     // training path
     std::vector<Exec> plan;
     DevBuf dx_init, ty, ta1, ta2, tAfT, tmp_pack, wpart, dWfold, lnpart, pool_scr, chain_tmp, dpt, dh2, dh1, dWt_all, dbt_all;
-    DevBuf bpart, fpart, dKf, dKt, dkt, dkf, cgr, cgv, cgw, cpdt, dyb, dnf;
+    DevBuf bpart, fpart, dKf, dyb, dnf;
     uint64_t commit_version = 0, train_pack_version = ~0ull;
-    bool keep_cauchy = false;         // set by the first forward_train: build_kernel then fills the per-block caches
+    bool keep_cauchy = false;         // set by the first forward_train: commits then keep every chain's Cauchy products
     std::vector<KGroup*> kgroups;     // training commits: blocks grouped by shape (build_kernels_stacked)
     bool kernels_stacked = false;     // the last commit generated the kernels group by group
     bool trained_fwd = false;
@@ -229,26 +142,6 @@ struct SashimiModel : dws_model {
         for (auto* g : kgroups) delete g;
         for (auto* l : all) delete l;
         for (auto* s : stages) delete s;
-        for (auto& kv : tables) delete kv.second;
-    }
-
-    int get_tables(int log2m, FftTables** out, hipStream_t s) {
-        auto it = tables.find(log2m);
-        if (it == tables.end()) {
-            auto* t = new FftTables();
-            std::vector<float> tw, twn, twp;
-            build_fft_tables(log2m, tw, twn, twp);
-            DWS_TRY(t->tw.ensure(tw.size() * 4));
-            DWS_TRY(t->twn.ensure(twn.size() * 4));
-            DWS_TRY(t->twp.ensure(twp.size() * 4));
-            DWS_HIP(hipMemcpyAsync(t->tw.p, tw.data(), tw.size() * 4, hipMemcpyHostToDevice, s));
-            DWS_HIP(hipMemcpyAsync(t->twn.p, twn.data(), twn.size() * 4, hipMemcpyHostToDevice, s));
-            DWS_HIP(hipMemcpyAsync(t->twp.p, twp.data(), twp.size() * 4, hipMemcpyHostToDevice, s));
-            DWS_HIP(hipStreamSynchronize(s));
-            it = tables.emplace(log2m, t).first;
-        }
-        *out = it->second;
-        return DWS_OK;
     }
 
     void wn(const std::string& p, std::vector<int64_t> vshape) {
@@ -422,9 +315,19 @@ struct SashimiModel : dws_model {
         return DWS_OK;
     }
 
-    // S4 convolution kernel of one block: parameters -> K_f   (s4.py:704-807, 1391-1403)
-    int build_kernel(SLayer* l, hipStream_t s) {
-        const int H = l->H, L = l->L, N = NS;
+    // the six kernel tensors of a block, or (backward: G() records the access) their gradients
+    S4Tensors kernel_tensors(const SLayer* l, bool grad) {
+        const std::string k = l->prefix + ".layer.kernel.kernel";
+        auto t = [&](const char* name) { return grad ? G(k + name) : P(k + name); };
+        return {t(".C"), t(".B"), t(".P"), t(".inv_w_real"), t(".w_imag"), t(".log_dt")};
+    }
+
+    // Cauchy products of this commit's chains: kept for the backward in training mode (commit() bumps commit_version when it
+    // is done), in the shared scratch otherwise
+    uint64_t products_version() const { return keep_cauchy ? commit_version + 1 : S4_NOT_KEPT; }
+
+    // one block as a chain over its own tensors, at the length its kernel was set up for
+    int block_chain(SLayer* l, S4Chain& c, hipStream_t s) {
         const std::string k = l->prefix + ".layer.kernel.kernel";
         int64_t Lbuf = 0;
         DWS_TRY(kernel_len(l, s, &Lbuf));
@@ -433,59 +336,51 @@ struct SashimiModel : dws_model {
         DWS_CHECK(Lbuf > 0 && Lbuf < (1 << 28), DWS_ERR_STATE,
                   "%s.L = %lld: C must have been through _setup_C(l_max) (s4.py:524-551) before it is handed to the engine",
                   k.c_str(), (long long)Lbuf);
-        const int Lk = (int)Lbuf, Lh = Lk / 2 + 1, Lt = std::min(L, Lk);
-        l->Lk = Lk;
-        const std::string zname = "__z." + std::to_string(Lk), oname = "__omega." + std::to_string(Lk);
+        l->Lk = (int)Lbuf;
+        const std::string zname = "__z." + std::to_string(l->Lk), oname = "__omega." + std::to_string(l->Lk);
         DWS_CHECK(P(zname) && P(oname), DWS_ERR_STATE, "FFT nodes %s / %s were not handed to the engine", zname.c_str(),
                   oname.c_str());
-        // training keeps the Cauchy products per block (kernel_backward reads them); sampling shares one scratch
-        DevBuf& bv = keep_cauchy ? l->t_cv : cv;
-        DevBuf& bw = keep_cauchy ? l->t_cwdt : cwdt;
-        DevBuf& bd = keep_cauchy ? l->t_cdt : cdt;
-        DevBuf& br = keep_cauchy ? l->t_cr : cr;
-        DWS_TRY(bv.ensure((size_t)6 * H * N * 8));
-        DWS_TRY(bw.ensure((size_t)H * N * 8));
-        DWS_TRY(bd.ensure((size_t)H * 4));
-        DWS_TRY(br.ensure((size_t)6 * H * Lh * 8));
-        DWS_TRY(ckf.ensure((size_t)2 * H * Lh * 8));
-        DWS_TRY(ck.ensure((size_t)2 * H * Lk * 4));
-        DWS_TRY(launch_s4_prep(P(k + ".C"), P(k + ".B"), P(k + ".P"), P(k + ".inv_w_real"), P(k + ".w_imag"),
-                               P(k + ".log_dt"), bv.f(), bw.f(), bd.f(), H, N, s));
-        DWS_TRY(launch_cauchy_sym_fwd_bcast(bv.f(), P(zname), bw.f(), br.f(), 6 * H, N, Lh, H, s));
-        DWS_TRY(launch_s4_woodbury(br.f(), P(oname), bd.f(), ckf.f(), H, Lh, (Lk % 2) == 0, s));
-        l->cache_version = keep_cauchy ? commit_version + 1 : ~0ull;   // commit() bumps commit_version when it is done
-        DWS_TRY(fft.exec(1, Lk, 2 * H, ckf.p, ck.p, s));
+        c.rows = l->H; c.N = NS; c.Lk = l->Lk;
+        c.par = kernel_tensors(l, false); c.z = P(zname); c.omega = P(oname);
+        return DWS_OK;
+    }
+
+    // the blocks of a chain read their H rows of its pair-ordered spectra
+    static void take_spectra(const S4Chain& c, SLayer* const* blocks, size_t n, int lg) {
+        const size_t half = (size_t)1 << (lg - 1);
+        for (size_t i = 0; i < n; ++i) {
+            SLayer* l = blocks[i];
+            l->kfa_v = c.kfa.f() + i * l->H * half * 2;
+            l->kfb_v = c.kfb.f() + i * l->H * half * 2;
+            l->kfs_v = c.kfs.f() + i * l->H * 3 * 2;
+            l->Lk = c.Lk; l->log2m = lg; l->seg = false;
+        }
+    }
+
+    // S4 convolution kernel of one block: parameters -> K_f   (s4.py:704-807, 1391-1403)
+    int build_kernel(SLayer* l, hipStream_t s) {
+        const int H = l->H, L = l->L;
+        S4Chain& c = l->own;
+        DWS_TRY(block_chain(l, c, s));
+        const int Lk = c.Lk, Lt = std::min(L, Lk);
+        DWS_TRY(s4_taps_forward(*this, c, products_version(), s));
         int lg = 0;
         if (fftconv_supported(L, &lg) && !getenv("DWS_SASHIMI_ROCFFT")) {
-            // fused path: spectrum at the power-of-two size Nf = 2M with the anti-causal half re-placed,
-            // produced by the same LDS FFT the per-step kernel uses, stored in its pair order
-            const int M = 1 << lg, Nf = 2 * M;
-            FftTables* t;
-            DWS_TRY(get_tables(lg, &t, s));
-            DWS_TRY(cK.ensure((size_t)H * Nf * 4));
-            DWS_TRY(cKf.ensure((size_t)H * (M + 1) * 8));
-            DWS_TRY(l->kfa.ensure((size_t)H * (M / 2) * 8));
-            DWS_TRY(l->kfb.ensure((size_t)H * (M / 2) * 8));
-            DWS_TRY(l->kfs.ensure((size_t)H * 3 * 8));
-            DWS_TRY(launch_s4_twosided_pow2(ck.f(), cK.f(), H, Lt, Nf, Lk, s));
-            DWS_TRY(launch_rfft_rows(lg, cK.f(), cKf.f(), t->tw.f(), t->twn.f(), H, s));
-            DWS_TRY(launch_kf_permute(cKf.f(), l->kfa.f(), l->kfb.f(), l->kfs.f(), H, lg, s));
-            if (l->grp < 0) { l->kfa_v = l->kfa.p; l->kfb_v = l->kfb.p; l->kfs_v = l->kfs.p; }   // (a block of a stacked commit keeps reading its group's rows: the tap "k:" regenerates into the block's own buffers)
-            l->log2m = lg;
-            l->seg = false;
+            DWS_TRY(s4_fused_spectrum(*this, c, Lt, lg, s));
+            take_spectra(c, &l, 1, lg);
         } else if (stages[l->stage]->seg) {
             // vocoding lengths: three pair-ordered spectra at M = 16384 -- the two-sided kernel, and its causal and
             // anti-causal halves alone shifted by half the transform ((-1)^k), see FftConvSegArgs
             DWS_CHECK(fftconv_seg_supported(L, Lt), DWS_ERR_UNSUPPORTED,
                       "%s: stage of %d samples with %d kernel taps per direction: more taps than one 16384-sample segment",
-                      k.c_str(), L, Lt);
+                      (l->prefix + ".layer.kernel.kernel").c_str(), L, Lt);
             lg = FFTCONV_SEG_LOG2M;
             const int M = 1 << lg, Nf = 2 * M;
             FftTables* t;
             DWS_TRY(get_tables(lg, &t, s));
             DWS_TRY(cK.ensure((size_t)H * Nf * 4));
             DWS_TRY(cKf.ensure((size_t)H * (M + 1) * 8));
-            DevBuf* dst[3][3] = {{&l->kfa, &l->kfb, &l->kfs}, {&l->kfa_c, &l->kfb_c, &l->kfs_c}, {&l->kfa_a, &l->kfb_a, &l->kfs_a}};
+            DevBuf* dst[3][3] = {{&c.kfa, &c.kfb, &c.kfs}, {&l->kfa_c, &l->kfb_c, &l->kfs_c}, {&l->kfa_a, &l->kfb_a, &l->kfs_a}};
             for (int which = 0; which < 3; ++which) {
                 DWS_TRY(dst[which][0]->ensure((size_t)H * (M / 2) * 8));
                 DWS_TRY(dst[which][1]->ensure((size_t)H * (M / 2) * 8));
@@ -532,7 +427,20 @@ struct SashimiModel : dws_model {
         return any;
     }
 
-    // parameters -> K_f of every block, one chain per group of same-shaped blocks (s4.py:704-807, 1391-1403; build_kernel's chain)
+    // A block's kernel tensors (or their gradients) <-> its H rows, block i of n, of a group's stack: the C planes of a block
+    // go to their plane of the stack
+    static void stack_rows(CopyBatch& b, bool unstack, const S4Tensors& blk, const S4Tensors& st, size_t i, int H, int N, int n) {
+        const size_t hn = (size_t)H * N, HN = hn * n;
+        auto cp = [&](float* pb, float* ps, size_t cnt) { unstack ? b.add(ps, pb, cnt) : b.add(pb, ps, cnt); };
+        for (int c = 0; c < 2; ++c) cp(blk.C + c * hn * 2, st.C + (c * HN + i * hn) * 2, hn * 2);
+        cp(blk.B, st.B + i * hn * 2, hn * 2);
+        cp(blk.P, st.P + i * hn * 2, hn * 2);
+        cp(blk.inv_w_real, st.inv_w_real + i * hn, hn);
+        cp(blk.w_imag, st.w_imag + i * hn, hn);
+        cp(blk.log_dt, st.log_dt + i * H, (size_t)H);
+    }
+
+    // parameters -> K_f of every block, one chain per group of same-shaped blocks (s4.py:704-807, 1391-1403)
     int build_kernels_stacked(hipStream_t s) {
         const int N = NS;
         for (auto* g : kgroups) g->layers.clear();      // (the run length may have changed since the last commit)
@@ -549,50 +457,23 @@ struct SashimiModel : dws_model {
         }
         for (auto* g : kgroups) {
             if (g->layers.empty()) continue;
-            const int H = g->H, L = g->L, Ht = g->Ht(), Lk = L, Lh = Lk / 2 + 1;
+            const int H = g->H, L = g->L, Ht = g->Ht(), n = (int)g->layers.size();
             int lg = 0;
             DWS_CHECK(fftconv_supported(L, &lg), DWS_ERR_STATE, "stacked kernel generation on a stage without the fused convolution");
-            const int M = 1 << lg, Nf = 2 * M;
             g->log2m = lg;
-            FftTables* t;
-            DWS_TRY(get_tables(lg, &t, s));
             const size_t HN = (size_t)Ht * N;
             DWS_TRY(g->C.ensure(2 * HN * 8)); DWS_TRY(g->Bp.ensure(HN * 8)); DWS_TRY(g->P.ensure(HN * 8));
             DWS_TRY(g->iwr.ensure(HN * 4)); DWS_TRY(g->wim.ensure(HN * 4)); DWS_TRY(g->logdt.ensure((size_t)Ht * 4));
-            DWS_TRY(g->v.ensure(6 * HN * 8)); DWS_TRY(g->wdt.ensure(HN * 8)); DWS_TRY(g->dt.ensure((size_t)Ht * 4));
-            DWS_TRY(g->r.ensure((size_t)6 * Ht * Lh * 8)); DWS_TRY(g->kf.ensure((size_t)2 * Ht * Lh * 8));
-            DWS_TRY(g->kfa.ensure((size_t)Ht * (M / 2) * 8)); DWS_TRY(g->kfb.ensure((size_t)Ht * (M / 2) * 8));
-            DWS_TRY(g->kfs.ensure((size_t)Ht * 3 * 8));
-            DWS_TRY(ck.ensure((size_t)2 * Ht * Lk * 4)); DWS_TRY(cK.ensure((size_t)Ht * Nf * 4)); DWS_TRY(cKf.ensure((size_t)Ht * (M + 1) * 8));
-            // the blocks' parameters into the stacked layout (one launch; the C planes of a block go to their plane of the stack)
-            g->stack.begin();
-            const size_t hn = (size_t)H * N;
-            for (size_t i = 0; i < g->layers.size(); ++i) {
-                const std::string k = g->layers[i]->prefix + ".layer.kernel.kernel";
-                for (int c = 0; c < 2; ++c) g->stack.add(P(k + ".C") + c * hn * 2, g->C.f() + (c * HN + i * hn) * 2, hn * 2);
-                g->stack.add(P(k + ".B"), g->Bp.f() + i * hn * 2, hn * 2);
-                g->stack.add(P(k + ".P"), g->P.f() + i * hn * 2, hn * 2);
-                g->stack.add(P(k + ".inv_w_real"), g->iwr.f() + i * hn, hn);
-                g->stack.add(P(k + ".w_imag"), g->wim.f() + i * hn, hn);
-                g->stack.add(P(k + ".log_dt"), g->logdt.f() + i * H, (size_t)H);
-            }
+            S4Chain& c = g->chain;
+            c.rows = Ht; c.N = N; c.Lk = L;
+            c.par = {g->C.f(), g->Bp.f(), g->P.f(), g->iwr.f(), g->wim.f(), g->logdt.f()};
+            c.z = P("__z." + std::to_string(L)); c.omega = P("__omega." + std::to_string(L));
+            g->stack.begin();      // the blocks' parameters into the stacked layout (one launch)
+            for (int i = 0; i < n; ++i) stack_rows(g->stack, false, kernel_tensors(g->layers[i], false), c.par, i, H, N, n);
             DWS_TRY(g->stack.run(s));
-            const float* z = P("__z." + std::to_string(Lk));
-            DWS_TRY(launch_s4_prep(g->C.f(), g->Bp.f(), g->P.f(), g->iwr.f(), g->wim.f(), g->logdt.f(), g->v.f(), g->wdt.f(), g->dt.f(), Ht, N, s));
-            DWS_TRY(launch_cauchy_sym_fwd_bcast(g->v.f(), z, g->wdt.f(), g->r.f(), 6 * Ht, N, Lh, Ht, s));
-            DWS_TRY(launch_s4_woodbury(g->r.f(), P("__omega." + std::to_string(Lk)), g->dt.f(), g->kf.f(), Ht, Lh, (Lk % 2) == 0, s));
-            DWS_TRY(fft.exec(1, Lk, 2 * Ht, g->kf.p, ck.p, s));
-            DWS_TRY(launch_s4_twosided_pow2(ck.f(), cK.f(), Ht, L, Nf, Lk, s));
-            DWS_TRY(launch_rfft_rows(lg, cK.f(), cKf.f(), t->tw.f(), t->twn.f(), Ht, s));
-            DWS_TRY(launch_kf_permute(cKf.f(), g->kfa.f(), g->kfb.f(), g->kfs.f(), Ht, lg, s));
-            for (size_t i = 0; i < g->layers.size(); ++i) {
-                SLayer* l = g->layers[i];
-                l->kfa_v = g->kfa.f() + i * (size_t)H * (M / 2) * 2;
-                l->kfb_v = g->kfb.f() + i * (size_t)H * (M / 2) * 2;
-                l->kfs_v = g->kfs.f() + i * (size_t)H * 3 * 2;
-                l->Lk = Lk; l->log2m = lg; l->seg = false;
-                l->cache_version = commit_version + 1;      // (commit() bumps commit_version when it is done)
-            }
+            DWS_TRY(s4_taps_forward(*this, c, products_version(), s));
+            DWS_TRY(s4_fused_spectrum(*this, c, L, lg, s));
+            take_spectra(c, g->layers.data(), g->layers.size(), lg);
         }
         return DWS_OK;
     }
@@ -665,17 +546,19 @@ struct SashimiModel : dws_model {
             if (l->kind == L_BLOCK) {
                 const int H = l->H;
                 if (l->mfma) {
+                    // (Wo, W1, W2) of the block's tail, in the order the packed copies below are made
+                    struct { const float* w; int rows, cols; const float* bias; int bias_len; } tail[3] = {
+                        {P(l->prefix + ".layer.output_linear.0.weight"), 2 * H, H, P(l->prefix + ".layer.output_linear.0.bias"), 2 * H},
+                        {l->W1.f(), FF * H, H, P(l->prefix + ".ff.ff.0.conv.bias"), FF * H},
+                        {l->W2.f(), H, FF * H, P(l->prefix + ".ff.ff.2.conv.bias"), H}};
                     if (s4_tail_chain_supported(H, FF)) {   // chain-ordered columns for the register-chained tail kernel
                         DWS_TRY(chain_tmp.ensure((size_t)FF * H * H * 4));
-                        DWS_TRY(l->Ao_c.ensure((size_t)2 * H * H * 4));
-                        DWS_TRY(l->A1_c.ensure((size_t)FF * H * H * 4));
-                        DWS_TRY(l->A2_c.ensure((size_t)FF * H * H * 4));
-                        DWS_TRY(launch_chain_permute_cols(P(l->prefix + ".layer.output_linear.0.weight"), chain_tmp.f(), 2 * H, H, s));
-                        DWS_TRY(launch_pack_a_frag(chain_tmp.f(), l->Ao_c.f(), 2 * H, H, s));
-                        DWS_TRY(launch_chain_permute_cols(l->W1.f(), chain_tmp.f(), FF * H, H, s));
-                        DWS_TRY(launch_pack_a_frag(chain_tmp.f(), l->A1_c.f(), FF * H, H, s));
-                        DWS_TRY(launch_chain_permute_cols(l->W2.f(), chain_tmp.f(), H, FF * H, s));
-                        DWS_TRY(launch_pack_a_frag(chain_tmp.f(), l->A2_c.f(), H, FF * H, s));
+                        DevBuf* dst[3] = {&l->Ao_c, &l->A1_c, &l->A2_c};
+                        for (int i = 0; i < 3; ++i) {
+                            DWS_TRY(dst[i]->ensure((size_t)tail[i].rows * tail[i].cols * 4));
+                            DWS_TRY(launch_chain_permute_cols(tail[i].w, chain_tmp.f(), tail[i].rows, tail[i].cols, s));
+                            DWS_TRY(launch_pack_a_frag(chain_tmp.f(), dst[i]->f(), tail[i].rows, tail[i].cols, s));
+                        }
                     }
                     const int split = f16x3 ? WN_SPLIT_F16X3 : WN_SPLIT_BF16X6;
                     const size_t wb = 2 * (size_t)wn_split_terms(split);            // bytes per packed weight
@@ -683,33 +566,28 @@ struct SashimiModel : dws_model {
                     if (f16x3) {     // (H >= 256: the LDS-tile kernel's split instances scale the fp32 fragments in registers)
                         DWS_TRY(l->wscale_c6.ensure(3 * 4));
                         sc = l->wscale_c6.f();
-                        DWS_TRY(launch_weight_scale(P(l->prefix + ".layer.output_linear.0.weight"), (size_t)2 * H * H,
-                                                    P(l->prefix + ".layer.output_linear.0.bias"), 2 * H, nullptr, 0, sc, s));
-                        DWS_TRY(launch_weight_scale(l->W1.f(), (size_t)FF * H * H, P(l->prefix + ".ff.ff.0.conv.bias"), FF * H, nullptr, 0, sc + 1, s));
-                        DWS_TRY(launch_weight_scale(l->W2.f(), (size_t)FF * H * H, P(l->prefix + ".ff.ff.2.conv.bias"), H, nullptr, 0, sc + 2, s));
+                        for (int i = 0; i < 3; ++i)
+                            DWS_TRY(launch_weight_scale(tail[i].w, (size_t)tail[i].rows * tail[i].cols, tail[i].bias, tail[i].bias_len,
+                                                        nullptr, 0, sc + i, s));
                     }
                     if (split_tails() && s4_tail_chain6_supported(H, FF)) {
                         DWS_TRY(chain_tmp.ensure((size_t)FF * H * H * 4));
-                        DWS_TRY(l->Ao_c6.ensure((size_t)2 * H * H * wb));
-                        DWS_TRY(l->A1_c6.ensure((size_t)FF * H * H * wb));
-                        DWS_TRY(l->A2_c6.ensure((size_t)FF * H * H * wb));
-                        DWS_TRY(launch_chain16_permute_cols(P(l->prefix + ".layer.output_linear.0.weight"), chain_tmp.f(), 2 * H, H, s));
-                        DWS_TRY(launch_pack_a_bx6(chain_tmp.f(), l->Ao_c6.p, 2 * H, H, split, sc, s));
-                        DWS_TRY(launch_chain16_permute_cols(l->W1.f(), chain_tmp.f(), FF * H, H, s));
-                        DWS_TRY(launch_pack_a_bx6(chain_tmp.f(), l->A1_c6.p, FF * H, H, split, sc ? sc + 1 : nullptr, s));
-                        DWS_TRY(launch_chain16_permute_cols(l->W2.f(), chain_tmp.f(), H, FF * H, s));
-                        DWS_TRY(launch_pack_a_bx6(chain_tmp.f(), l->A2_c6.p, H, FF * H, split, sc ? sc + 2 : nullptr, s));
+                        DevBuf* dst[3] = {&l->Ao_c6, &l->A1_c6, &l->A2_c6};
+                        for (int i = 0; i < 3; ++i) {
+                            DWS_TRY(dst[i]->ensure((size_t)tail[i].rows * tail[i].cols * wb));
+                            DWS_TRY(launch_chain16_permute_cols(tail[i].w, chain_tmp.f(), tail[i].rows, tail[i].cols, s));
+                            DWS_TRY(launch_pack_a_bx6(chain_tmp.f(), dst[i]->p, tail[i].rows, tail[i].cols, split, sc ? sc + i : nullptr, s));
+                        }
                     } else if (split_tails() && s4_tail_wide6_supported(H, FF)) {   // one blob [Wo | W1 | W2], k-block-major fragments
                         DWS_TRY(chain_tmp.ensure((size_t)FF * H * H * 4));
                         DWS_TRY(l->Ao_c6.ensure((size_t)(2 + 2 * FF) * H * H * wb));
                         l->A1_c6.release(); l->A2_c6.release();
                         char* blob = static_cast<char*>(l->Ao_c6.p);
-                        DWS_TRY(launch_chain16_permute_cols(P(l->prefix + ".layer.output_linear.0.weight"), chain_tmp.f(), 2 * H, H, s));
-                        DWS_TRY(launch_pack_a_bx6_kmajor(chain_tmp.f(), blob, 2 * H, H, split, sc, s));
-                        DWS_TRY(launch_chain16_permute_cols(l->W1.f(), chain_tmp.f(), FF * H, H, s));
-                        DWS_TRY(launch_pack_a_bx6_kmajor(chain_tmp.f(), blob + (size_t)2 * H * H * wb, FF * H, H, split, sc ? sc + 1 : nullptr, s));
-                        DWS_TRY(launch_chain16_permute_cols(l->W2.f(), chain_tmp.f(), H, FF * H, s));
-                        DWS_TRY(launch_pack_a_bx6_kmajor(chain_tmp.f(), blob + (size_t)(2 + FF) * H * H * wb, H, FF * H, split, sc ? sc + 2 : nullptr, s));
+                        for (int i = 0; i < 3; ++i) {
+                            DWS_TRY(launch_chain16_permute_cols(tail[i].w, chain_tmp.f(), tail[i].rows, tail[i].cols, s));
+                            DWS_TRY(launch_pack_a_bx6_kmajor(chain_tmp.f(), blob, tail[i].rows, tail[i].cols, split, sc ? sc + i : nullptr, s));
+                            blob += (size_t)tail[i].rows * tail[i].cols * wb;
+                        }
                     } else {
                         l->Ao_c6.release(); l->A1_c6.release(); l->A2_c6.release();
                     }
@@ -889,7 +767,7 @@ struct SashimiModel : dws_model {
             FftConvSegArgs fa{};
             fa.u = st->y.f(); fa.g = st->g.f(); fa.D = P(p + ".layer.D");
             fa.tw = (const c2*)t->tw.p; fa.twp = (const c2*)t->twp.p;
-            fa.kfa[0] = (const c2*)l->kfa.p; fa.kfb[0] = (const c2*)l->kfb.p; fa.kfs[0] = (const c2*)l->kfs.p;
+            fa.kfa[0] = (const c2*)l->own.kfa.p; fa.kfb[0] = (const c2*)l->own.kfb.p; fa.kfs[0] = (const c2*)l->own.kfs.p;
             fa.kfa[1] = (const c2*)l->kfa_c.p; fa.kfb[1] = (const c2*)l->kfb_c.p; fa.kfs[1] = (const c2*)l->kfs_c.p;
             fa.kfa[2] = (const c2*)l->kfa_a.p; fa.kfb[2] = (const c2*)l->kfb_a.p; fa.kfs[2] = (const c2*)l->kfs_a.p;
             fa.B = nB; fa.H = H; fa.L = Ls;
@@ -1404,122 +1282,47 @@ struct SashimiModel : dws_model {
         return DWS_OK;
     }
 
-    // gradient of the S4 kernel parameters of one block from u and da (s4.py:704-807 backwards)
-    // The adjoint of a group's stacked kernel generation, once the spectrum gradients of all its blocks are in g->dKf
-    // (kernel_backward's chain with Ht = n H rows); the stacked parameter gradients leave for the blocks' tensors in one launch.
+    // The adjoint of a group's stacked kernel generation, once the spectrum gradients of all its blocks are in g->dKf; the
+    // stacked parameter gradients leave for the blocks' tensors in one launch.
     int group_backward(KGroup* g, hipStream_t s) {
-        const int H = g->H, Ht = g->Ht(), Ls = g->L, Lh = Ls / 2 + 1, N = NS;
-        const int M = 1 << g->log2m, Nf = 2 * M;
-        const size_t HN = (size_t)Ht * N, hn = (size_t)H * N;
-        DWS_TRY(dKt.ensure((size_t)Ht * Nf * 4));
-        DWS_TRY(dkt.ensure((size_t)2 * Ht * Ls * 4));
-        DWS_TRY(dkf.ensure((size_t)2 * Ht * Lh * 8));
-        DWS_TRY(cgr.ensure((size_t)6 * Ht * Lh * 8));
-        DWS_TRY(cgv.ensure(6 * HN * 8));
-        DWS_TRY(cgw.ensure(6 * HN * 8));
-        const int nparts = ceil_div(Lh, 256);
-        DWS_TRY(cpdt.ensure((size_t)Ht * nparts * 4));
+        const int H = g->H, Ht = g->Ht(), N = NS, n = (int)g->layers.size();
+        const size_t HN = (size_t)Ht * N;
         DWS_TRY(g->gC.ensure(2 * HN * 8)); DWS_TRY(g->gB.ensure(HN * 8)); DWS_TRY(g->gP.ensure(HN * 8));
         DWS_TRY(g->giwr.ensure(HN * 4)); DWS_TRY(g->gwim.ensure(HN * 4)); DWS_TRY(g->glogdt.ensure((size_t)Ht * 4));
         DWS_TRY(g->gD.ensure((size_t)Ht * 4));
-        DWS_TRY(fft.exec(1, Nf, Ht, g->dKf.p, dKt.p, s));
-        DWS_TRY(launch_s4_twosided_pow2_bwd(dKt.f(), dkt.f(), g->gD.f(), Ht, Ls, Nf, 1.f / ((float)Nf * (float)Ls), 1.f / (float)Nf, s));
-        DWS_TRY(fft.exec(0, Ls, 2 * Ht, dkt.p, dkf.p, s));
-        DWS_TRY(launch_s4_woodbury_bwd(g->r.f(), P("__omega." + std::to_string(Ls)), g->dt.f(), dkf.f(), cgr.f(), cpdt.f(), Ht, Lh,
-                                       (Ls % 2) == 0, s));
-        DWS_TRY(launch_cauchy_sym_bwd_bcast(g->v.f(), P("__z." + std::to_string(Ls)), g->wdt.f(), cgr.f(), cgv.f(), cgw.f(), 6 * Ht, N, Lh,
-                                            Ht, s));
-        DWS_TRY(launch_s4_prep_bwd(g->C.f(), g->Bp.f(), g->P.f(), g->iwr.f(), g->wim.f(), g->logdt.f(), cgv.f(), cgw.f(), cpdt.f(), nparts,
-                                   g->gC.f(), g->gB.f(), g->gP.f(), g->giwr.f(), g->gwim.f(), g->glogdt.f(), Ht, N, s));
+        const S4Tensors grad{g->gC.f(), g->gB.f(), g->gP.f(), g->giwr.f(), g->gwim.f(), g->glogdt.f()};
+        DWS_TRY(s4_spectrum_adjoint(*this, g->chain, g->log2m, g->dKf.f(), g->gD.f(), s));
+        DWS_TRY(s4_taps_adjoint(*this, g->chain, commit_version, grad, s));
         g->unstack.begin();
-        for (size_t i = 0; i < g->layers.size(); ++i) {
-            const std::string p = g->layers[i]->prefix, k = p + ".layer.kernel.kernel";
-            for (int c = 0; c < 2; ++c) g->unstack.add(g->gC.f() + (c * HN + i * hn) * 2, G(k + ".C") + c * hn * 2, hn * 2);
-            g->unstack.add(g->gB.f() + i * hn * 2, G(k + ".B"), hn * 2);
-            g->unstack.add(g->gP.f() + i * hn * 2, G(k + ".P"), hn * 2);
-            g->unstack.add(g->giwr.f() + i * hn, G(k + ".inv_w_real"), hn);
-            g->unstack.add(g->gwim.f() + i * hn, G(k + ".w_imag"), hn);
-            g->unstack.add(g->glogdt.f() + i * H, G(k + ".log_dt"), (size_t)H);
-            g->unstack.add(g->gD.f() + i * H, G(p + ".layer.D"), (size_t)H);
+        for (int i = 0; i < n; ++i) {
+            stack_rows(g->unstack, true, kernel_tensors(g->layers[i], true), grad, i, H, N, n);
+            g->unstack.add(g->gD.f() + (size_t)i * H, G(g->layers[i]->prefix + ".layer.D"), (size_t)H);
         }
         return g->unstack.run(s);
     }
 
+    // gradient of the S4 kernel parameters of one block from u and da (s4.py:704-807 backwards): the block's spectrum gradient
+    // dK_f = corr(u, da), then the adjoint of its chain -- at once for a block on its own, once per group when the last of the
+    // group's blocks has put its rows into the group's stack
     int kernel_backward(SLayer* l, const float* da, hipStream_t s) {
-        const int H = l->H, Ls = l->L, Lh = Ls / 2 + 1, nB = (int)B;
-        const int M = 1 << l->log2m, Nf = 2 * M;
-        if (kernels_stacked && l->grp >= 0) {
-            // this block's spectrum gradient into its rows of the group's stack; the rest of the chain runs once per group
-            KGroup* g = kgroups[l->grp];
-            FftTables* t = tables[l->log2m];
-            const int nbs = std::max(1, std::min(nB, ceil_div(512, H)));
-            const int bchunk = ceil_div(nB, nbs);
-            const int nchunks = ceil_div(nB, bchunk);
-            DWS_TRY(fpart.ensure((size_t)nchunks * H * (M + 1) * 8));
-            DWS_TRY(g->dKf.ensure((size_t)g->Ht() * (M + 1) * 8));
-            FftCorrArgs c{};
-            c.u = l->t_u.f(); c.da = da; c.part = (c2*)fpart.p; c.tw = (const c2*)t->tw.p; c.twp = (const c2*)t->twp.p;
-            c.B = nB; c.H = H; c.L = Ls; c.bchunk = bchunk;
-            DWS_TRY(launch_fftcorr(l->log2m, c, s));
-            DWS_TRY(launch_sum_leading(fpart.f(), g->dKf.f() + (size_t)l->gidx * H * (M + 1) * 2, (size_t)H * (M + 1) * 2, nchunks, 1.f, s));
-            if (--g->pending == 0) DWS_TRY(group_backward(g, s));
-            return DWS_OK;
-        }
+        KGroup* g = (kernels_stacked && l->grp >= 0) ? kgroups[l->grp] : nullptr;
+        const int H = l->H, nB = (int)B, M = 1 << l->log2m;
+        const size_t row_floats = (size_t)H * (M + 1) * 2;
         FftTables* t = tables[l->log2m];
         const int nbs = std::max(1, std::min(nB, ceil_div(512, H)));
         const int bchunk = ceil_div(nB, nbs);
         const int nchunks = ceil_div(nB, bchunk);
-        DWS_TRY(fpart.ensure((size_t)nchunks * H * (M + 1) * 8));
-        DWS_TRY(dKf.ensure((size_t)H * (M + 1) * 8));
-        DWS_TRY(dKt.ensure((size_t)H * Nf * 4));
-        DWS_TRY(dkt.ensure((size_t)2 * H * Ls * 4));
-        DWS_TRY(dkf.ensure((size_t)2 * H * Lh * 8));
+        DevBuf& dst = g ? g->dKf : dKf;      // the block's rows of its chain's spectrum gradient
+        DWS_TRY(fpart.ensure(nchunks * row_floats * 4));
+        DWS_TRY(dst.ensure((g ? g->layers.size() : 1) * row_floats * 4));
         FftCorrArgs c{};
         c.u = l->t_u.f(); c.da = da; c.part = (c2*)fpart.p; c.tw = (const c2*)t->tw.p; c.twp = (const c2*)t->twp.p;
-        c.B = nB; c.H = H; c.L = Ls; c.bchunk = bchunk;
+        c.B = nB; c.H = H; c.L = l->L; c.bchunk = bchunk;
         DWS_TRY(launch_fftcorr(l->log2m, c, s));
-        DWS_TRY(launch_sum_leading(fpart.f(), dKf.f(), (size_t)H * (M + 1) * 2, nchunks, 1.f, s));
-        DWS_TRY(fft.exec(1, Nf, H, dKf.p, dKt.p, s));
-        // dK_t = C2R / Nf; k enters K as k / L (s4_twosided_pow2); dD[h] = sum u da = dK_t[h][0]
-        DWS_TRY(launch_s4_twosided_pow2_bwd(dKt.f(), dkt.f(), G(l->prefix + ".layer.D"), H, Ls, Nf,
-                                            1.f / ((float)Nf * (float)Ls), 1.f / (float)Nf, s));
-        DWS_TRY(fft.exec(0, Ls, 2 * H, dkt.p, dkf.p, s));
-        return kernel_params_backward(l, Ls, s);
-    }
-
-    // The chain behind the tap gradient of one block: dkf = R2C(dk) [2][H][Lk/2+1] -> Woodbury -> Cauchy -> s4_prep adjoints ->
-    // the gradients of C, B, P, inv_w_real, w_imag, log_dt
-    int kernel_params_backward(SLayer* l, int Lk, hipStream_t s) {
-        const int H = l->H, Lh = Lk / 2 + 1, N = NS;
-        const std::string k = l->prefix + ".layer.kernel.kernel";
-        // v, w dt, dt, r of this block: kept by build_kernel when this commit already ran in training mode, else regenerated
-        const bool cached = l->cache_version == commit_version && l->t_cr.p;
-        DevBuf& bv = cached ? l->t_cv : cv;
-        DevBuf& bw = cached ? l->t_cwdt : cwdt;
-        DevBuf& bd = cached ? l->t_cdt : cdt;
-        DevBuf& br = cached ? l->t_cr : cr;
-        DWS_TRY(cgr.ensure((size_t)6 * H * Lh * 8));
-        DWS_TRY(cgv.ensure((size_t)6 * H * N * 8));
-        DWS_TRY(cgw.ensure((size_t)6 * H * N * 8));
-        const int nparts = ceil_div(Lh, 256);
-        DWS_TRY(cpdt.ensure((size_t)H * nparts * 4));
-        const float* z = P("__z." + std::to_string(Lk));
-        if (!cached) {
-            DWS_TRY(bv.ensure((size_t)6 * H * N * 8));
-            DWS_TRY(bw.ensure((size_t)H * N * 8));
-            DWS_TRY(bd.ensure((size_t)H * 4));
-            DWS_TRY(br.ensure((size_t)6 * H * Lh * 8));
-            DWS_TRY(launch_s4_prep(P(k + ".C"), P(k + ".B"), P(k + ".P"), P(k + ".inv_w_real"), P(k + ".w_imag"),
-                                   P(k + ".log_dt"), bv.f(), bw.f(), bd.f(), H, N, s));
-            DWS_TRY(launch_cauchy_sym_fwd_bcast(bv.f(), z, bw.f(), br.f(), 6 * H, N, Lh, H, s));
-        }
-        DWS_TRY(launch_s4_woodbury_bwd(br.f(), P("__omega." + std::to_string(Lk)), bd.f(), dkf.f(), cgr.f(), cpdt.f(), H,
-                                       Lh, (Lk % 2) == 0, s));
-        DWS_TRY(launch_cauchy_sym_bwd_bcast(bv.f(), z, bw.f(), cgr.f(), cgv.f(), cgw.f(), 6 * H, N, Lh, H, s));
-        DWS_TRY(launch_s4_prep_bwd(P(k + ".C"), P(k + ".B"), P(k + ".P"), P(k + ".inv_w_real"), P(k + ".w_imag"),
-                                   P(k + ".log_dt"), cgv.f(), cgw.f(), cpdt.f(), nparts, G(k + ".C"), G(k + ".B"), G(k + ".P"),
-                                   G(k + ".inv_w_real"), G(k + ".w_imag"), G(k + ".log_dt"), H, N, s));
-        return DWS_OK;
+        DWS_TRY(launch_sum_leading(fpart.f(), dst.f() + (g ? l->gidx : 0) * row_floats, row_floats, nchunks, 1.f, s));
+        if (g) return --g->pending == 0 ? group_backward(g, s) : DWS_OK;
+        DWS_TRY(s4_spectrum_adjoint(*this, l->own, l->log2m, dKf.f(), G(l->prefix + ".layer.D"), s));
+        return s4_taps_adjoint(*this, l->own, commit_version, kernel_tensors(l, true), s);
     }
 
     // S4 convolution of a block whose stage runs on rocFFT (odd length, or more than 16384 samples), training forward: the
@@ -1543,9 +1346,9 @@ struct SashimiModel : dws_model {
     }
 
     // Its adjoint, given da [B][H][L]: du = C2R(conj(K_f) dA) / 2L + D da into `du`, d fc_t(e) = sum_l du into dpt, dD, and the
-    // kernel parameters' gradients through dK_f = sum_b conj(U_b) dA_b -> C2R -> the two-sided assembly backwards -> the chain of
-    // kernel_params_backward.  U_f is recomputed here (one R2C of the padded t_u) instead of being kept from the forward: keeping
-    // it would cost B H (L+1) 8 bytes per block for the whole step (90 MB per top-stage block of ljspeech_harder, twelve of them)
+    // kernel parameters' gradients through dK_f = sum_b conj(U_b) dA_b -> C2R -> the two-sided assembly backwards -> the taps
+    // adjoint of the block's chain.  U_f is recomputed here (one R2C of the padded t_u) instead of being kept from the forward:
+    // keeping it would cost B H (L+1) 8 bytes per block for the whole step (90 MB per top-stage block of ljspeech_harder, twelve of them)
     // to save one transform of the same size, and it would need an out-of-place spectrum multiply in the forward.
     int rocfft_conv_backward(SLayer* l, Stage* st, const float* da, float* du, hipStream_t s) {
         ProfileScope ps("long_stage_bwd", s);
@@ -1567,7 +1370,7 @@ struct SashimiModel : dws_model {
         DWS_TRY(launch_s4_twosided_bwd(dKt.f(), dkt.f(), G(l->prefix + ".layer.D"), H, Ls, Lk, Lt,
                                        1.f / ((float)(2 * Ls) * (float)Lk), 1.f / (float)(2 * Ls), s));
         DWS_TRY(fft.exec(0, Lk, 2 * H, dkt.p, dkf.p, s));
-        return kernel_params_backward(l, Lk, s);
+        return s4_taps_adjoint(*this, l->own, commit_version, kernel_tensors(l, true), s);
     }
 
     // (dm, ds) of a LayerNorm from its adjoint's per-block partials [2][nblk].  Every adjoint of a backward writes its own slot of
@@ -1795,7 +1598,9 @@ struct SashimiModel : dws_model {
             if (dirty) DWS_TRY(commit(s));
             for (auto* l : all)
                 if (l->kind == L_BLOCK && l->prefix == t.substr(2)) {
-                    DWS_TRY(build_kernel(l, s));  // regenerates the (unnormalised) time-domain kernel into scratch
+                    S4Chain c;      // regenerates the (unnormalised) time-domain kernel into scratch; nothing of the commit moves
+                    DWS_TRY(block_chain(l, c, s));
+                    DWS_TRY(s4_taps_forward(*this, c, S4_NOT_KEPT, s));
                     const size_t n = (size_t)2 * l->H * l->Lk;
                     DWS_CHECK((size_t)capacity >= n, DWS_ERR_INVALID, "tap buffer too small");
                     DWS_HIP(hipMemcpyAsync(dst, ck.p, n * 4, hipMemcpyDeviceToDevice, s));

@@ -267,8 +267,8 @@ torch.save({"losses": losses, "cauchy_launches": n.value,
 
 
 def test_stacked_kernel_generation_is_the_per_block_chain(tmp_path, gpu):
-    """Training commits generate the S4 kernels of all blocks of one shape in ONE chain over n H rows (`s4.py:704-807`; `KGroup` in
-    sashimi_model.hip) and run the chain's adjoint once per group.  Same loss and gradients as one chain per block
+    """Training commits generate the S4 kernels of all blocks of one shape in ONE chain over n H rows (`s4.py:704-807`; `S4Chain` in
+    s4_kernel_chain.hip over a `KGroup` of sashimi_model.hip) and run the chain's adjoint once per group.  Same loss and gradients as one chain per block
     (`DWS_S4_KERNELS_PER_BLOCK=1`, read once per process: two fresh processes) up to the rounding of rocFFT's batched transforms,
     on d128 (H = 128 / 256 / 512, two blocks per level and direction: groups of 4 / 4 / 2), over three steps."""
     import os

@@ -1,5 +1,5 @@
 """Per-shape times of the symmetric Cauchy kernels at the shapes one config-5 training step launches them with
-(`sashimi_model.hip: build_kernel / backward`: rows = 6 H with w broadcast over H, N = 32 conjugate pairs, L/2+1 bins)
+(`s4_kernel_chain.hip: s4_taps_forward / s4_taps_adjoint`: rows = 6 H with w broadcast over H, N = 32 conjugate pairs, L/2+1 bins)
 -- through the public C-ABI (`dws_cauchy_sym_fwd/bwd`, w materialised per row), HIP events on the launch stream.
 usage: python tools/cauchy_times.py [reps]"""
 import os
