@@ -4,13 +4,18 @@
 #include "model.h"
 
 namespace dws {
+struct SamplerProgram;
 int sampler_run(dws_model* m, float* x, const float* alpha, const float* alpha_bar, const float* sigma, int T,
                 const float* noise, uint64_t seed, int init_from_seed, int use_graph, hipStream_t s);
 int sampler_steps(dws_model* m, float* x, const float* alpha, const float* alpha_bar, const float* sigma, int T,
                   int t_start, int n_steps, uint64_t seed, int use_graph, hipStream_t s);
 int sampler_run_schedule(dws_model* m, float* x, int kind, int S, const float* net_steps, const float* coef,
                          const float* noise, uint64_t seed, int init_from_seed, int use_graph,
-                         const dws_sampler_edit* e, hipStream_t s);
+                         const dws_sampler_edit* e, const SamplerProgram* pg, hipStream_t s);
+int sampler_run_program(dws_model* m, float* x, int kind, int S, const float* net_steps, const float* coef, int V,
+                        const int32_t* visit_step, const float* jump_coef, const float* noise, uint64_t seed,
+                        int init_from_seed, int use_graph, const dws_sampler_edit* e, hipStream_t s);
+int philox_normal(float* x, int64_t n, uint64_t seed, uint32_t stream_id, hipStream_t s);
 }  // namespace dws
 
 dws_model::~dws_model() {
@@ -34,6 +39,8 @@ void dws_model::drop_graph() {
     sch_graph = nullptr;
     if (edit_graph) hipGraphExecDestroy(edit_graph);
     edit_graph = nullptr;
+    if (prog_graph) hipGraphExecDestroy(prog_graph);
+    prog_graph = nullptr;
 }
 
 dws::ParamSpec* dws_model::add_param(const std::string& name, std::vector<int64_t> shape, int dtype) {
@@ -435,7 +442,7 @@ int dws_sampler_run_schedule(dws_model* m, float* x, int32_t kind, int32_t S, co
                              int32_t use_graph, void* stream) {
     DWS_CHECK(m && x, DWS_ERR_INVALID, "dws_sampler_run_schedule: null argument");
     return dws::sampler_run_schedule(m, x, kind, S, net_steps, coef, noise, seed, init_from_seed, use_graph, nullptr,
-                                     (hipStream_t)stream);
+                                     nullptr, (hipStream_t)stream);
 }
 
 int dws_sampler_run_edit(dws_model* m, float* x, int32_t kind, int32_t S, const float* net_steps, const float* coef,
@@ -443,7 +450,20 @@ int dws_sampler_run_edit(dws_model* m, float* x, int32_t kind, int32_t S, const 
                          const dws_sampler_edit* edit, void* stream) {
     DWS_CHECK(m && x && edit, DWS_ERR_INVALID, "dws_sampler_run_edit: null argument");
     return dws::sampler_run_schedule(m, x, kind, S, net_steps, coef, noise, seed, init_from_seed, use_graph, edit,
-                                     (hipStream_t)stream);
+                                     nullptr, (hipStream_t)stream);
+}
+
+int dws_sampler_run_program(dws_model* m, float* x, int32_t kind, int32_t S, const float* net_steps, const float* coef,
+                            int32_t V, const int32_t* visit_step, const float* jump_coef, const float* noise,
+                            uint64_t seed, int32_t init_from_seed, int32_t use_graph, const dws_sampler_edit* edit,
+                            void* stream) {
+    DWS_CHECK(m && x && edit, DWS_ERR_INVALID, "dws_sampler_run_program: null argument");
+    return dws::sampler_run_program(m, x, kind, S, net_steps, coef, V, visit_step, jump_coef, noise, seed,
+                                    init_from_seed, use_graph, edit, (hipStream_t)stream);
+}
+
+int dws_philox_normal(float* x, int64_t n, uint64_t seed, uint32_t stream_id, void* stream) {
+    return dws::philox_normal(x, n, seed, stream_id, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -189,7 +189,7 @@ struct dws_model {
     // caller's x nor the seed is baked in.
     dws::DevBuf sch_tables;               // DDPM [3][S] c1, c2, sigma; DDIM [5][S] k1 .. k5
     std::vector<float> sch_host_tables;   // host copy of what is resident (upload skipped when identical)
-    dws::DevBuf sch_state;                // int32 step index, int32 finished update blocks, uint64 Philox seed
+    dws::DevBuf sch_state;                // int32 step index, int32 finished update blocks, uint64 Philox seed, int32 visit
     dws::DevBuf sch_x;                    // [B, C, L]
     hipGraphExec_t sch_graph = nullptr;
     struct SchKey {
@@ -198,10 +198,13 @@ struct dws_model {
         const void *tables, *noise, *eps, *x, *state;
         uint64_t table_gen;
         const void *edit, *known, *mask, *known_noise;   // the edited step's (all null for the unedited one)
+        int V = 0;                                       // the resampling step's: visits and the program tables
+        const void* prog = nullptr;
         bool operator==(const SchKey& o) const {
             return B == o.B && L == o.L && S == o.S && kind == o.kind && vec == o.vec && tables == o.tables &&
                    noise == o.noise && eps == o.eps && x == o.x && state == o.state && table_gen == o.table_gen &&
-                   edit == o.edit && known == o.known && mask == o.mask && known_noise == o.known_noise;
+                   edit == o.edit && known == o.known && mask == o.mask && known_noise == o.known_noise && V == o.V &&
+                   prog == o.prog;
         }
     } sch_key{};
     // editing (dws_sampler_run_edit): the step that ends in the replacement of the known region is a graph of its own
@@ -213,6 +216,12 @@ struct dws_model {
     dws::DevBuf sch_mask;                 // uint8 [B, C, L] (rounded up to whole groups of four)
     hipGraphExec_t edit_graph = nullptr;
     SchKey edit_key{};
+    // resampling (dws_sampler_run_program): the reverse visit of a program is a third graph beside the two above; the
+    // program tables sit in a model-owned buffer keyed on their contents, so a new program of the same V replays it.
+    dws::DevBuf sch_prog;                 // int32 step_of[V], float ja[V], jb[V], indexed by the visit number
+    std::vector<uint32_t> sch_host_prog;  // host copy of what is resident
+    hipGraphExec_t prog_graph = nullptr;
+    SchKey prog_key{};
     uint64_t step_table_gen = 0;          // bumped by every step-table rebuild (build_step_table)
     int64_t graphs_made = 0;              // tap "sampler_graphs": graphs instantiated by either entry point
 

@@ -8,6 +8,7 @@
 // (parity mode) or from an on-device Philox4x32-10 counter RNG, so that one
 // reverse step is a fixed kernel sequence: captured once, replayed T times.
 #include <cmath>
+#include <functional>
 
 #include "model.h"
 
@@ -51,6 +52,26 @@ __global__ void smp_set_state_kernel(int* st, int t, uint64_t seed) {
     st[0] = t;
     st[1] = 0;
     *reinterpret_cast<uint64_t*>(st + 2) = seed;
+}
+
+// a program run (dws_sampler_run_program) also keeps the visit number v in the state ([4]): the noise rows and Philox
+// streams of a visit are indexed by v, the step table and the update tables by the step word [0] = step_of[v]
+__global__ void smp_set_program_state_kernel(int* st, int t, int v, uint64_t seed) {
+    st[0] = t;
+    st[1] = 0;
+    *reinterpret_cast<uint64_t*>(st + 2) = seed;
+    st[4] = v;
+}
+
+// End of a visit's kernel: the last block to arrive moves the program on, visit <- v - 1 and step <- step_of[v - 1]
+// (the row the next visit's network reads; -1 behind the last visit).  Every block has read the state by then and the
+// next kernel that reads it is stream-ordered behind this one, as with the step counter of the kernels above.
+__device__ __forceinline__ void smp_program_advance(int* __restrict__ st, const int* __restrict__ step_of, int v) {
+    if (atomicAdd(reinterpret_cast<unsigned*>(st + 1), 1u) == gridDim.x - 1) {
+        st[1] = 0;
+        st[4] = v - 1;
+        st[0] = v > 0 ? step_of[v - 1] : -1;
+    }
 }
 
 __global__ void smp_fill_normal_kernel(float* __restrict__ x, size_t n, uint64_t seed, uint32_t stream_id) {
@@ -290,6 +311,165 @@ __global__ void smp_edit_kernel(float* __restrict__ x, const float* __restrict__
     }
 }
 
+// Reverse visit of dws_sampler_run_program (RePaint's resampling): smp_edit_kernel's update and replacement at step
+// s = st[0], in the same operation order, but the visit number v = st[4] names the noise: noise[v] / known_noise[v], or
+// Philox streams v and V + 1 + v (a step that is visited again draws fresh noise).  The last block moves the program on
+// (smp_program_advance) instead of counting the step down.
+template <int KIND, bool VEC>
+__global__ void smp_resample_kernel(float* __restrict__ x, const float* __restrict__ eps, const float* __restrict__ tab,
+                                    const float* __restrict__ edit, int* __restrict__ st,
+                                    const int* __restrict__ step_of, const float* __restrict__ noise,
+                                    const float* __restrict__ y, const uint8_t* __restrict__ mask,
+                                    const float* __restrict__ known_noise, size_t n, int S, int V) {
+#pragma clang fp contract(off)
+    const int s = __builtin_amdgcn_readfirstlane(*(volatile int*)st);
+    const int v = __builtin_amdgcn_readfirstlane(*(volatile int*)(st + 4));
+    const uint64_t seed = *(const volatile uint64_t*)(st + 2);
+    const float k1 = tab[s], k2 = tab[S + s], k3 = tab[2 * S + s];
+    const float k4 = KIND == DWS_SAMPLER_DDIM ? tab[3 * S + s] : 0.f, k5 = KIND == DWS_SAMPLER_DDIM ? tab[4 * S + s] : 0.f;
+    const bool add = KIND == DWS_SAMPLER_DDIM ? (s > 0 && k5 > 0.f) : s > 0;
+    const float q1 = edit[s], q2 = edit[S + s];
+    const float* nz = noise ? noise + (size_t)v * n : nullptr;
+    const float* kz = known_noise ? known_noise + (size_t)v * n : nullptr;
+    for (size_t g = (size_t)blockIdx.x * blockDim.x + threadIdx.x; g * 4 < n; g += (size_t)gridDim.x * blockDim.x) {
+        float xv[4] = {0.f, 0.f, 0.f, 0.f}, ev[4] = {0.f, 0.f, 0.f, 0.f}, z[4] = {0.f, 0.f, 0.f, 0.f};
+        float yv[4] = {0.f, 0.f, 0.f, 0.f}, zk[4] = {0.f, 0.f, 0.f, 0.f};
+        uint32_t mk = 0;    // byte j: mask of element 4g + j
+        if (VEC) {
+            const float4 a = reinterpret_cast<const float4*>(x)[g], e = reinterpret_cast<const float4*>(eps)[g];
+            xv[0] = a.x; xv[1] = a.y; xv[2] = a.z; xv[3] = a.w;
+            ev[0] = e.x; ev[1] = e.y; ev[2] = e.z; ev[3] = e.w;
+            if (add && nz) {
+                const float4 q = reinterpret_cast<const float4*>(nz)[g];
+                z[0] = q.x; z[1] = q.y; z[2] = q.z; z[3] = q.w;
+            }
+            mk = reinterpret_cast<const uint32_t*>(mask)[g];
+            if (mk) {
+                const float4 k = reinterpret_cast<const float4*>(y)[g];
+                yv[0] = k.x; yv[1] = k.y; yv[2] = k.z; yv[3] = k.w;
+                if (s > 0 && kz) {
+                    const float4 q = reinterpret_cast<const float4*>(kz)[g];
+                    zk[0] = q.x; zk[1] = q.y; zk[2] = q.z; zk[3] = q.w;
+                }
+            }
+        } else {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const size_t i = g * 4 + j;
+                if (i >= n) break;
+                xv[j] = x[i]; ev[j] = eps[i];
+                if (add && nz) z[j] = nz[i];
+                if (mask[i]) {
+                    mk |= 1u << (8 * j);
+                    yv[j] = y[i];
+                    if (s > 0 && kz) zk[j] = kz[i];
+                }
+            }
+        }
+        if (add && !nz) normal4(seed, (uint32_t)v, g, z);
+        if (mk && s > 0 && !kz) normal4(seed, (uint32_t)(V + 1 + v), g, zk);
+        float r[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            float w;
+            if (KIND == DWS_SAMPLER_DDIM) {      // smp_ddim_kernel's order
+                const float p = k1 * ev[j];
+                const float d = xv[j] - p;
+                const float u = d / k2;
+                const float a = k3 * u;
+                const float b = k4 * ev[j];
+                w = a + b;
+                if (add) {
+                    const float q = k5 * z[j];
+                    w = w + q;
+                }
+            } else {                             // smp_update_kernel's order: k1 = c1, k2 = c2, k3 = sigma
+                const float p = k1 * ev[j];
+                w = (xv[j] - p) / k2;
+                if (add) {
+                    const float q = k3 * z[j];
+                    w = w + q;
+                }
+            }
+            if ((mk >> (8 * j)) & 0xffu) {
+                w = yv[j];
+                if (s > 0) {
+                    const float a = q1 * yv[j];
+                    const float b = q2 * zk[j];
+                    w = a + b;
+                }
+            }
+            r[j] = w;
+        }
+        if (VEC) {
+            reinterpret_cast<float4*>(x)[g] = make_float4(r[0], r[1], r[2], r[3]);
+        } else {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const size_t i = g * 4 + j;
+                if (i >= n) break;
+                x[i] = r[j];
+            }
+        }
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) smp_program_advance(st, step_of, v);
+}
+
+// Jump visit of dws_sampler_run_program: the whole state, known region included, goes from position k up to k + j in one
+// draw of the forward process' exact marginal q(x_{k+j} | x_k),
+//   x = (ja * x) + (jb * z)      ja = jump[v], jb = jump[V + v] (sampling.jump_coefficients)
+// two products and one sum, each rounded once.  z: noise[v] or Philox stream v in normal4's layout.  No network runs.
+// VEC: every group of 4 is in range and x / noise are 16-byte aligned -> float4 loads and stores.
+template <bool VEC>
+__global__ void smp_jump_kernel(float* __restrict__ x, const float* __restrict__ jump, int* __restrict__ st,
+                                const int* __restrict__ step_of, const float* __restrict__ noise, size_t n, int V) {
+#pragma clang fp contract(off)
+    const int v = __builtin_amdgcn_readfirstlane(*(volatile int*)(st + 4));
+    const uint64_t seed = *(const volatile uint64_t*)(st + 2);
+    const float ja = jump[v], jb = jump[V + v];
+    const float* nz = noise ? noise + (size_t)v * n : nullptr;
+    for (size_t g = (size_t)blockIdx.x * blockDim.x + threadIdx.x; g * 4 < n; g += (size_t)gridDim.x * blockDim.x) {
+        float xv[4] = {0.f, 0.f, 0.f, 0.f}, z[4] = {0.f, 0.f, 0.f, 0.f};
+        if (VEC) {
+            const float4 a = reinterpret_cast<const float4*>(x)[g];
+            xv[0] = a.x; xv[1] = a.y; xv[2] = a.z; xv[3] = a.w;
+            if (nz) {
+                const float4 q = reinterpret_cast<const float4*>(nz)[g];
+                z[0] = q.x; z[1] = q.y; z[2] = q.z; z[3] = q.w;
+            }
+        } else {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const size_t i = g * 4 + j;
+                if (i >= n) break;
+                xv[j] = x[i];
+                if (nz) z[j] = nz[i];
+            }
+        }
+        if (!nz) normal4(seed, (uint32_t)v, g, z);
+        float r[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const float a = ja * xv[j];
+            const float b = jb * z[j];
+            r[j] = a + b;
+        }
+        if (VEC) {
+            reinterpret_cast<float4*>(x)[g] = make_float4(r[0], r[1], r[2], r[3]);
+        } else {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const size_t i = g * 4 + j;
+                if (i >= n) break;
+                x[i] = r[j];
+            }
+        }
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) smp_program_advance(st, step_of, v);
+}
+
 // Partial start in q-sample mode: x holds clean audio and becomes the state at step s0,
 //   x = (n1 * x) + (n2 * z0)      n1 = sqrt(level[s0]), n2 = sqrt(1 - level[s0])
 // two products and one sum, each rounded once.  z0: the injected tensor or Philox stream `stream_id` (2S + 1).
@@ -436,6 +616,13 @@ int sampler_steps(dws_model* m, float* x, const float* alpha, const float* alpha
 // ---- few-step samplers (dws_sampler_run_schedule) and their editing modes (dws_sampler_run_edit) ----
 // device side of a known-region replacement: the resident q1 / q2 table, the model-owned copies of the known audio and
 // the mask, the caller's injected known-region noise (or null)
+// host side of a program: visit_step[V] in execution order, jump_coef[2][V] indexed by the visit number
+struct SamplerProgram {
+    int V;
+    const int32_t* visit_step;
+    const float* jump_coef;
+};
+
 struct EditStep {
     const float* table;
     const float* known;
@@ -443,10 +630,17 @@ struct EditStep {
     const float* known_noise;
 };
 
+// device side of a program (dws_sampler_run_program): the resident step_of[V] and jump[2][V] tables
+struct ProgStep {
+    const int* step_of;
+    const float* jump;
+    int V;
+};
+
 // One reverse step of the schedule: forward at row *st of the step table, then the DDPM or DDIM update (with the
-// replacement of the known region when `ed` is given).
+// replacement of the known region when `ed` is given; as a visit of a program when `pr` is given too).
 static int schedule_step(dws_model* m, float* x, int kind, int S, const float* noise, bool vec, const EditStep* ed,
-                         hipStream_t s) {
+                         const ProgStep* pr, hipStream_t s) {
     const size_t n = (size_t)m->B * m->d.out_channels * m->L;
     int* st = static_cast<int*>(m->sch_state.p);
     m->step_idx = st;
@@ -454,6 +648,19 @@ static int schedule_step(dws_model* m, float* x, int kind, int S, const float* n
     m->step_idx = nullptr;
     DWS_TRY(rc);
     const int blocks = (int)std::min<size_t>(ceil_div(n, 4 * 256), 4096);
+    if (ed && pr) {
+#define DWS_RESAMPLE_LAUNCH(KIND, VEC)                                                                                 \
+    hipLaunchKernelGGL((smp_resample_kernel<KIND, VEC>), dim3(blocks), dim3(256), 0, s, x, m->smp_eps.f(),             \
+                       m->sch_tables.f(), ed->table, st, pr->step_of, noise, ed->known, ed->mask, ed->known_noise, n,  \
+                       S, pr->V)
+        if (kind == DWS_SAMPLER_DDPM) {
+            if (vec) DWS_RESAMPLE_LAUNCH(DWS_SAMPLER_DDPM, true); else DWS_RESAMPLE_LAUNCH(DWS_SAMPLER_DDPM, false);
+        } else {
+            if (vec) DWS_RESAMPLE_LAUNCH(DWS_SAMPLER_DDIM, true); else DWS_RESAMPLE_LAUNCH(DWS_SAMPLER_DDIM, false);
+        }
+#undef DWS_RESAMPLE_LAUNCH
+        return DWS_OK;
+    }
     if (ed) {
 #define DWS_EDIT_LAUNCH(KIND, VEC)                                                                                     \
     hipLaunchKernelGGL((smp_edit_kernel<KIND, VEC>), dim3(blocks), dim3(256), 0, s, x, m->smp_eps.f(),                 \
@@ -481,9 +688,12 @@ static int schedule_step(dws_model* m, float* x, int kind, int S, const float* n
 // e null: dws_sampler_run_schedule.  e given: dws_sampler_run_edit -- the run starts at e->start_step (the initial value
 // of the device step counter, and the number of replays), optionally from a q-sample of x, and with `known` / `mask`
 // every step ends in the replacement of the known region (the edited step, a graph of its own).
+// pg given (with e, known and mask; checked by sampler_run_program): the host walks the program's V visits in order, a
+// reverse visit as a replay of the resampling step (a third graph), a jump visit as a launch of smp_jump_kernel; the
+// noise rows and Philox streams are numbered by the visit with V in the place of S.
 int sampler_run_schedule(dws_model* m, float* x, int kind, int S, const float* net_steps, const float* coef,
                          const float* noise, uint64_t seed, int init_from_seed, int use_graph,
-                         const dws_sampler_edit* e, hipStream_t s) {
+                         const dws_sampler_edit* e, const SamplerProgram* pg, hipStream_t s) {
     DWS_CHECK(kind == DWS_SAMPLER_DDPM || kind == DWS_SAMPLER_DDIM, DWS_ERR_INVALID, "sampler: unknown kind %d", kind);
     DWS_CHECK(S >= 1, DWS_ERR_INVALID, "sampler: S = %d steps (needs S >= 1)", S);
     DWS_CHECK(net_steps && coef, DWS_ERR_INVALID, "sampler: null net_steps or coefficients");
@@ -548,8 +758,27 @@ int sampler_run_schedule(dws_model* m, float* x, int kind, int S, const float* n
     DWS_TRY(m->smp_eps.ensure(n * 4));
     m->smp_eps_B = m->B; m->smp_eps_L = m->L;
     DWS_TRY(m->build_step_table(S, net_steps, s));   // the network's step-only part at net_steps (kept while they stay)
-    DWS_TRY(m->sch_state.ensure(16));
+    DWS_TRY(m->sch_state.ensure(32));
     int* st = static_cast<int*>(m->sch_state.p);
+    const int V = pg ? pg->V : 0;
+    const int R = pg ? V : S;     // streams R (a drawn x_T) and 2R + 1 (the q-sample) lie behind the per-visit ones
+    if (pg) {   // step_of[V] and ja[V], jb[V] in one model-owned buffer, keyed on their contents
+        std::vector<uint32_t> h(3 * (size_t)V);
+        for (int i = 0; i < V; ++i) {
+            const int v = V - 1 - i;      // visit_step is in execution order, the tables are indexed by v
+            h[v] = (uint32_t)std::max(pg->visit_step[i], 0);
+            std::memcpy(&h[V + v], &pg->jump_coef[v], 4);
+            std::memcpy(&h[2 * (size_t)V + v], &pg->jump_coef[V + v], 4);
+        }
+        if (!m->sch_prog.p || h != m->sch_host_prog) {
+            DWS_TRY(m->sch_prog.ensure(h.size() * 4));
+            DWS_HIP(hipMemcpyAsync(m->sch_prog.p, h.data(), h.size() * 4, hipMemcpyHostToDevice, s));
+            DWS_HIP(hipStreamSynchronize(s));
+            m->sch_host_prog.swap(h);
+        }
+    }
+    const ProgStep prog{static_cast<const int*>(m->sch_prog.p), m->sch_prog.f() + V, V};
+    const ProgStep* pr = pg ? &prog : nullptr;
     const int blocks = (int)std::min<size_t>(ceil_div(n, 4 * 256), 4096);
     const auto aligned = [](const void* p) { return ((uintptr_t)p & 15) == 0; };
     const float* known_noise = masked ? e->known_noise : nullptr;
@@ -558,7 +787,10 @@ int sampler_run_schedule(dws_model* m, float* x, int kind, int S, const float* n
     // what precedes the steps, on the stream that runs them: the step counter at `start`, the known clip and the mask
     // into their model-owned buffers, the q-sample of the start
     const auto begin = [&](float* xr, hipStream_t q) -> int {
-        hipLaunchKernelGGL(smp_set_state_kernel, dim3(1), dim3(1), 0, q, st, start, seed);
+        if (pg)
+            hipLaunchKernelGGL(smp_set_program_state_kernel, dim3(1), dim3(1), 0, q, st, start, V - 1, seed);
+        else
+            hipLaunchKernelGGL(smp_set_state_kernel, dim3(1), dim3(1), 0, q, st, start, seed);
         if (masked) {
             DWS_HIP(hipMemcpyAsync(m->sch_known.p, e->known, n * 4, hipMemcpyDeviceToDevice, q));
             DWS_HIP(hipMemcpyAsync(m->sch_mask.p, e->mask, n, hipMemcpyDeviceToDevice, q));
@@ -566,16 +798,35 @@ int sampler_run_schedule(dws_model* m, float* x, int kind, int S, const float* n
         if (qsample)
             hipLaunchKernelGGL(smp_qsample_kernel, dim3(blocks), dim3(256), 0, q, xr, e->start_noise,
                                e->edit_coef[2 * (size_t)S + start], e->edit_coef[3 * (size_t)S + start], n, seed,
-                               (uint32_t)(2 * S + 1));
+                               (uint32_t)(2 * R + 1));
+        return DWS_OK;
+    };
+    // the walk: `reverse` enqueues one reverse step on q; a jump visit is a launch of its own between them
+    const auto walk = [&](float* xr, bool vec, hipStream_t q, const std::function<int()>& reverse) -> int {
+        if (!pg) {
+            for (int i = 0; i <= start; ++i) DWS_TRY(reverse());
+            return DWS_OK;
+        }
+        for (int i = 0; i < V; ++i) {
+            if (pg->visit_step[i] >= 0) {
+                DWS_TRY(reverse());
+            } else if (vec) {
+                hipLaunchKernelGGL(smp_jump_kernel<true>, dim3(blocks), dim3(256), 0, q, xr, pr->jump, st, pr->step_of,
+                                   noise, n, V);
+            } else {
+                hipLaunchKernelGGL(smp_jump_kernel<false>, dim3(blocks), dim3(256), 0, q, xr, pr->jump, st, pr->step_of,
+                                   noise, n, V);
+            }
+        }
         return DWS_OK;
     };
 
     if (!use_graph) {
         const bool vec = n % 4 == 0 && aligned(x) && aligned(noise) && aligned(known_noise);
         if (init_from_seed)
-            hipLaunchKernelGGL(smp_fill_normal_kernel, dim3(blocks), dim3(256), 0, s, x, n, seed, (uint32_t)S);
+            hipLaunchKernelGGL(smp_fill_normal_kernel, dim3(blocks), dim3(256), 0, s, x, n, seed, (uint32_t)R);
         DWS_TRY(begin(x, s));
-        for (int i = 0; i <= start; ++i) DWS_TRY(schedule_step(m, x, kind, S, noise, vec, ed, s));
+        DWS_TRY(walk(x, vec, s, [&]() { return schedule_step(m, x, kind, S, noise, vec, ed, pr, s); }));
         DWS_HIP(hipGetLastError());
         return DWS_OK;
     }
@@ -589,22 +840,23 @@ int sampler_run_schedule(dws_model* m, float* x, int kind, int S, const float* n
     DWS_HIP(hipEventRecord(m->smp_ev_in, s));
     DWS_HIP(hipStreamWaitEvent(cs, m->smp_ev_in, 0));
     if (init_from_seed)
-        hipLaunchKernelGGL(smp_fill_normal_kernel, dim3(blocks), dim3(256), 0, cs, xs, n, seed, (uint32_t)S);
+        hipLaunchKernelGGL(smp_fill_normal_kernel, dim3(blocks), dim3(256), 0, cs, xs, n, seed, (uint32_t)R);
     else
         DWS_HIP(hipMemcpyAsync(xs, x, n * 4, hipMemcpyDeviceToDevice, cs));
     DWS_TRY(begin(xs, cs));
     const dws_model::SchKey key{m->B, m->L, S, kind, vec ? 1 : 0, m->sch_tables.p, noise, m->smp_eps.p, xs, st,
                                 m->step_table_gen, ed ? ed->table : nullptr, ed ? ed->known : nullptr,
-                                ed ? ed->mask : nullptr, known_noise};
-    // the edited step has a graph of its own: edited and unedited calls may alternate without a new capture
-    hipGraphExec_t& exec = masked ? m->edit_graph : m->sch_graph;
-    dws_model::SchKey& have = masked ? m->edit_key : m->sch_key;
+                                ed ? ed->mask : nullptr, known_noise, V, pr ? m->sch_prog.p : nullptr};
+    // the edited step and the resampling step have graphs of their own: the three kinds of call may alternate without a
+    // new capture
+    hipGraphExec_t& exec = pg ? m->prog_graph : masked ? m->edit_graph : m->sch_graph;
+    dws_model::SchKey& have = pg ? m->prog_key : masked ? m->edit_key : m->sch_key;
     if (!exec || !(key == have)) {
         if (exec) hipGraphExecDestroy(exec);
         exec = nullptr;
         hipGraph_t graph = nullptr;
         DWS_HIP(hipStreamBeginCapture(cs, hipStreamCaptureModeThreadLocal));
-        int rc = schedule_step(m, xs, kind, S, noise, vec, ed, cs);
+        int rc = schedule_step(m, xs, kind, S, noise, vec, ed, pr, cs);
         hipError_t err = hipStreamEndCapture(cs, &graph);
         if (rc != DWS_OK) {
             if (graph) hipGraphDestroy(graph);
@@ -617,10 +869,57 @@ int sampler_run_schedule(dws_model* m, float* x, int kind, int S, const float* n
         ++m->graphs_made;
         have = key;
     }
-    for (int i = 0; i <= start; ++i) DWS_HIP(hipGraphLaunch(exec, cs));
+    DWS_TRY(walk(xs, vec, cs, [&]() -> int {
+        DWS_HIP(hipGraphLaunch(exec, cs));
+        return DWS_OK;
+    }));
     DWS_HIP(hipMemcpyAsync(x, xs, n * 4, hipMemcpyDeviceToDevice, cs));
     DWS_HIP(hipEventRecord(m->smp_ev_out, cs));
     DWS_HIP(hipStreamWaitEvent(s, m->smp_ev_out, 0));
+    return DWS_OK;
+}
+
+// dws_sampler_run_program: the program must be a walk (see include/dws.h) before anything is enqueued
+int sampler_run_program(dws_model* m, float* x, int kind, int S, const float* net_steps, const float* coef, int V,
+                        const int32_t* visit_step, const float* jump_coef, const float* noise, uint64_t seed,
+                        int init_from_seed, int use_graph, const dws_sampler_edit* e, hipStream_t s) {
+    DWS_CHECK(S >= 1, DWS_ERR_INVALID, "sampler: S = %d steps (needs S >= 1)", S);
+    DWS_CHECK(e->known && e->mask, DWS_ERR_INVALID, "sampler: a program run needs known and mask");
+    DWS_CHECK(V >= 1 && visit_step && jump_coef, DWS_ERR_INVALID, "sampler: empty program or null tables (V = %d)", V);
+    const int start = e->start_step;
+    DWS_CHECK(start >= 0 && start < S, DWS_ERR_INVALID, "sampler: start_step = %d (needs 0 .. %d)", start, S - 1);
+    const int K = start + 1;
+    int pos = K;    // the position the state is at: reverse step s takes it from s + 1 to s
+    for (int i = 0; i < V; ++i) {
+        const int v = V - 1 - i, a = visit_step[i];
+        if (a >= 0) {
+            DWS_CHECK(a == pos - 1, DWS_ERR_INVALID,
+                      "sampler: program entry %d is reverse step %d, but the state is at position %d (step %d is next)", i,
+                      a, pos, pos - 1);
+            pos = a;
+        } else {
+            DWS_CHECK(a >= -S && pos - a <= K, DWS_ERR_INVALID,
+                      "sampler: program entry %d = %d jumps up from position %d beyond the start position %d", i, a, pos, K);
+            const float ja = jump_coef[v], jb = jump_coef[V + v];
+            DWS_CHECK(std::isfinite(ja) && std::isfinite(jb) && ja > 0.f, DWS_ERR_INVALID,
+                      "sampler: jump coefficients of program entry %d = %g, %g (need finite values, ja > 0)", i, (double)ja,
+                      (double)jb);
+            pos -= a;
+        }
+    }
+    DWS_CHECK(pos == 0 && visit_step[V - 1] == 0, DWS_ERR_INVALID,
+              "sampler: the program ends at position %d (its last visit must be reverse step 0)", pos);
+    const SamplerProgram pg{V, visit_step, jump_coef};
+    return sampler_run_schedule(m, x, kind, S, net_steps, coef, noise, seed, init_from_seed, use_graph, e, &pg, s);
+}
+
+// dws_philox_normal: n values of Philox stream `stream_id` in normal4's layout (group g = elements 4g .. 4g + 3)
+int philox_normal(float* x, int64_t n, uint64_t seed, uint32_t stream_id, hipStream_t s) {
+    DWS_CHECK(x && n >= 0, DWS_ERR_INVALID, "dws_philox_normal: null x or n = %lld", (long long)n);
+    if (n == 0) return DWS_OK;
+    const int blocks = (int)std::min<size_t>(ceil_div((size_t)n, 4 * 256), 4096);
+    hipLaunchKernelGGL(smp_fill_normal_kernel, dim3(blocks), dim3(256), 0, s, x, (size_t)n, seed, stream_id);
+    DWS_HIP(hipGetLastError());
     return DWS_OK;
 }
 

@@ -215,7 +215,7 @@ def _load_clip(dataset_cfg, stem, audio_length, conditional):
 def generate(rank, diffusion_cfg, model_cfg, dataset_cfg, ckpt_iter="max", n_samples=1, name=None, batch_size=None,
              ckpt_smooth=None, mel_path=None, mel_name=None, dataloader=None, exp_root="exp", seed=None,
              written=None, precision=None, sampler="ddpm", steps=None, eta=0.0, known_name=None, keep=None,
-             start_name=None, start_step=None, start_noise=True):
+             start_name=None, start_step=None, start_noise=True, resample_jump=None, resample_n=None):
     """``generate.py:58-200``.  ``ckpt_iter`` may additionally be ``"init"``: seeded random weights
     (no checkpoint), for smoke runs without trained weights.  ``precision`` (not in the reference; CLI:
     ``+engine.precision=bf16x6|f16x3``): the engine's opt-in matrix arithmetic, see ``include/dws.h``.
@@ -228,10 +228,13 @@ def generate(rank, diffusion_cfg, model_cfg, dataset_cfg, ckpt_iter="max", n_sam
     Editing (not in the reference; with any ``sampler``): ``known_name`` (a wav stem under ``dataset.data_path``) with
     ``keep`` (``[start, end)`` sample spans of it that are kept) inpaints the rest -- every clip of the batch gets the
     same known audio and its own noise; ``start_name`` with ``start_step`` starts the loop at that step from the wav,
-    noised to the step's level first unless ``start_noise`` is false (then the wav is the state as given)."""
+    noised to the step's level first unless ``start_noise`` is false (then the wav is the state as given).
+    ``resample_jump`` with ``resample_n`` (both or neither; they need ``known_name``) run the inpainting with RePaint's
+    resampling: at every ``resample_jump``-th position the chain goes back up that many steps and down again,
+    ``resample_n`` times in all (``sampling.repaint_program``)."""
     from .models import construct_model
-    from .sampling import (calc_diffusion_hyperparams, ddim_steps, sampling, sampling_aligned, sampling_ddim,
-                           spans_to_mask)
+    from .sampling import (calc_diffusion_hyperparams, ddim_steps, program_evaluations, repaint_program, sampling,
+                           sampling_aligned, sampling_ddim, spans_to_mask)
     from scipy.io.wavfile import write as wavwrite
 
     if known_name is not None and not keep:
@@ -242,6 +245,12 @@ def generate(rank, diffusion_cfg, model_cfg, dataset_cfg, ckpt_iter="max", n_sam
         raise ValueError("generate.start_name needs generate.start_step (the step the loop starts at)")
     if start_step is not None and start_name is None:
         raise ValueError("generate.start_step needs generate.start_name (the wav the loop starts from)")
+    if (resample_jump is None) != (resample_n is None):
+        raise ValueError("generate.resample_jump and generate.resample_n come together (got "
+                         f"{'resample_jump' if resample_n is None else 'resample_n'} only)")
+    if resample_jump is not None and known_name is None:
+        raise ValueError("generate.resample_jump / generate.resample_n need generate.known_name (resampling harmonises "
+                         "an inpainting run)")
     sampler = sampler or "ddpm"
     if sampler not in ("ddpm", "aligned", "ddim"):
         raise ValueError(f"generate.sampler={sampler!r}: expected ddpm, aligned or ddim")
@@ -260,6 +269,9 @@ def generate(rank, diffusion_cfg, model_cfg, dataset_cfg, ckpt_iter="max", n_sam
         n_evals = len(ddim_steps(dh_train["T"], steps))
     else:
         n_evals = dh["T"]
+    if resample_jump is not None:       # checked here, before a model is built
+        repaint_program(n_evals, resample_jump, resample_n, start_step)
+        n_evals = program_evaluations(n_evals, resample_jump, resample_n, start_step)
     model_kwargs = {k: v for k, v in model_cfg.items()}
     net = construct_model(model_kwargs).cuda().eval()
     if precision not in (None, "f32"):
@@ -313,6 +325,8 @@ def generate(rank, diffusion_cfg, model_cfg, dataset_cfg, ckpt_iter="max", n_sam
         edit["x_start"] = _load_clip(dataset_cfg, start_name, audio_length, mel is not None)
         edit["start_step"] = start_step
         edit["start_noise"] = None if start_noise else False
+    if resample_jump is not None:
+        edit["resample"] = (resample_jump, resample_n)
 
     t0 = time.perf_counter()
     out = []
@@ -329,7 +343,7 @@ def generate(rank, diffusion_cfg, model_cfg, dataset_cfg, ckpt_iter="max", n_sam
     torch.cuda.synchronize()
     print(f"generated {n_samples} samples shape {tuple(generated_audio.shape)} at iteration {ckpt_iter} in "
           f"{time.perf_counter() - t0:.1f} seconds")
-    if sampler != "ddpm":
+    if sampler != "ddpm" or resample_jump is not None:
         print(f"sampler {sampler}{f' (eta={float(eta or 0.0)})' if sampler == 'ddim' else ''}: {n_evals} network "
               f"evaluations per batch")
     for i in range(n_samples):

@@ -83,11 +83,132 @@ def spans_to_mask(size, spans):
     return m
 
 
+def _is_int(v):
+    if isinstance(v, bool):
+        return False
+    return isinstance(v, (int, np.integer)) or (isinstance(v, (float, np.floating)) and float(v).is_integer())
+
+
+def _start_position(S, start_step):
+    S = int(S)
+    if start_step is None:
+        return S
+    if not _is_int(start_step) or not 0 <= start_step <= S - 1:
+        raise ValueError(f"sampler: start_step = {start_step!r} (needs an integer in 0..{S - 1})")
+    return int(start_step) + 1
+
+
+def repaint_program(S, jump, resamples, start_step=None):
+    """RePaint's schedule (Lugmayr et al., CVPR 2022) as the ``visit_step`` array of ``dws_sampler_run_program``: int32
+    [V] in execution order, ``s >= 0`` a reverse visit at step s, ``-jump`` a jump visit up by ``jump`` positions.
+
+    The state starts at position ``K = S`` (``start_step + 1`` with a partial start); reverse step s takes it from
+    position s + 1 to s.  Jump points are the positions ``k = 0, jump, 2 jump, ...`` with ``k + jump <= K - 1``, each with
+    a counter ``resamples - 1`` that never refills.  After every reverse visit: if the position reached is a jump point
+    whose counter is above zero, the counter goes down by one and the state jumps up to ``k + jump``; the walk ends with
+    the reverse visit that reaches position 0 with no jump left there.  ``K + (resamples-1) * jump * #jump points``
+    network evaluations (``program_evaluations``).  ``S = 6, jump = 2, resamples = 2`` gives
+    ``[5, 4, 3, 2, -2, 3, 2, 1, 0, -2, 1, 0]``; ``resamples = 1`` gives ``K-1 .. 0``."""
+    if not _is_int(S) or S < 1:
+        raise ValueError(f"repaint_program: S = {S!r} (needs an integer >= 1)")
+    K = _start_position(S, start_step)
+    if not _is_int(jump) or jump < 1:
+        raise ValueError(f"sampler: resample jump = {jump!r} (needs an integer >= 1)")
+    if not _is_int(resamples) or resamples < 1:
+        raise ValueError(f"sampler: resamples = {resamples!r} (needs an integer >= 1)")
+    j, r = int(jump), int(resamples)
+    if r > 1 and j > K - 1:
+        raise ValueError(f"sampler: resample jump = {j} leaves no jump point below the start position {K} "
+                         f"(needs jump <= {K - 1})")
+    left = {k: r - 1 for k in range(0, K - j, j)}
+    prog, pos = [], K
+    while True:
+        pos -= 1
+        prog.append(pos)
+        if left.get(pos, 0) > 0:
+            left[pos] -= 1
+            prog.append(-j)
+            pos += j
+        elif pos == 0:
+            break
+    return np.asarray(prog, dtype=np.int32)
+
+
+def program_evaluations(S, jump, resamples, start_step=None):
+    """Network evaluations of ``repaint_program(S, jump, resamples, start_step)``: K + (r-1) j (number of jump points)."""
+    K = _start_position(S, start_step)
+    return K + (int(resamples) - 1) * int(jump) * len(range(0, K - int(jump), int(jump)))
+
+
+def _walk(S, visit_step, start_step=None):
+    """(visit number v, position before, position after) of every entry of a program; ValueError when it is no walk."""
+    K = _start_position(S, start_step)
+    vs = np.asarray(visit_step).reshape(-1)
+    V, pos, out = len(vs), K, []
+    for i, a in enumerate(int(a) for a in vs):
+        new = a if a >= 0 else pos - a
+        if (a >= 0 and a != pos - 1) or new > K:
+            raise ValueError(f"sampler: program entry {i} = {a} is no move from position {pos} (start position {K})")
+        out.append((V - 1 - i, pos, new))
+        pos = new
+    if V < 1 or pos != 0 or vs[-1] != 0:
+        raise ValueError("sampler: a program ends in reverse step 0")
+    return out
+
+
+def jump_coefficients(levels, visit_step, start_step=None):
+    """Jump tables of a program over a run with ``levels`` (as ``edit_coefficients``): float32 [2][V] = ja, jb indexed by
+    the visit number ``v = V-1-i`` of entry i.  With ``P[0] = 1``, ``P[k] = level[k-1]`` the level of position k, a jump
+    from k to k+j has ``ja = sqrt(P[k+j] / P[k])``, ``jb = sqrt(1 - P[k+j] / P[k])`` -- the forward process' marginal
+    ``q(x_{k+j} | x_k)`` -- in float64 from the float32 levels, rounded once.  Reverse visits hold zeros."""
+    if isinstance(levels, torch.Tensor):
+        levels = levels.detach().cpu().numpy()
+    lv = np.asarray(levels, dtype=np.float32).astype(np.float64).reshape(-1)
+    P = np.concatenate([[1.0], lv])
+    walk = _walk(lv.shape[0], visit_step, start_step)
+    out = np.zeros((2, len(walk)), dtype=np.float32)
+    for v, k, kj in walk:
+        if kj > k:
+            out[0, v] = np.sqrt(P[kj] / P[k])
+            out[1, v] = np.sqrt(1.0 - P[kj] / P[k])
+    return out
+
+
+def program_streams(visit_step):
+    """Philox stream ids of a program run: ``visit`` [V] (stream v: the update noise of reverse visit v, z of jump visit
+    v), ``known`` [V] (stream V + 1 + v after reverse visit v; -1 for a jump visit, which draws none), ``x_T`` = V (a
+    drawn initial state) and ``start`` = 2V + 1 (the q-sample).  With the program ``K-1 .. 0`` of a whole run these are
+    ``dws_sampler_run_edit``'s: s, S + 1 + s, S and 2S + 1."""
+    vs = np.asarray(visit_step).reshape(-1)
+    V = len(vs)
+    v = np.arange(V)
+    return dict(visit=v, known=np.where(vs[::-1] >= 0, V + 1 + v, -1), x_T=V, start=2 * V + 1)
+
+
+def _check_resample(size, S, resample, noise, known=None, mask=None, x_start=None, start_step=None, **_):
+    """Argument checks of ``resample=(jump, resamples)`` before any GPU work (ValueError).  Returns the program."""
+    if known is None or mask is None:
+        raise ValueError("sampler: resample= needs known= and mask= (resampling harmonises an inpainting run)")
+    try:
+        jump, resamples = resample
+    except (TypeError, ValueError):
+        raise ValueError(f"sampler: resample = {resample!r} (needs (jump, resamples))")
+    if x_start is None:
+        start_step = None
+    elif start_step is None:
+        start_step = S - 1
+    prog = repaint_program(S, jump, resamples, start_step)
+    if noise is not None and tuple(torch.as_tensor(noise).shape) != (len(prog),) + tuple(int(v) for v in size):
+        raise ValueError(f"sampler: noise has shape {tuple(noise.shape)}, a program of {len(prog)} visits needs "
+                         f"{(len(prog),) + tuple(size)}")
+    return prog
+
+
 def _check_edit(size, S, x_T, known=None, mask=None, known_noise=None, x_start=None, start_step=None,
-                start_noise=None):
+                start_noise=None, rows=None):
     """Argument checks of the editing modes, all on the host and before any GPU work (ValueError).  Returns
     (known [B,C,L] float32 | None, mask [B,C,L] uint8 | None, known_noise | None, x_start [B,C,L] | None, start_step,
-    start_noise tensor | None, q-sample?)."""
+    start_noise tensor | None, q-sample?).  ``rows``: leading dimension of known_noise (default S; V in a program run)."""
     size = tuple(int(v) for v in size)
 
     def expand(name, t, dtype=None):
@@ -117,7 +238,7 @@ def _check_edit(size, S, x_T, known=None, mask=None, known_noise=None, x_start=N
             raise ValueError("sampler: mask must be bool or hold only 0 and 1 (soft masks are not built)")
         mask = mask != 0
         if known_noise is not None:
-            known_noise = exact("known_noise", known_noise, (S,) + size)
+            known_noise = exact("known_noise", known_noise, (S if rows is None else rows,) + size)
     if x_start is None:
         if start_step is not None or start_noise is not None:
             raise ValueError("sampler: start_step= / start_noise= without x_start=")
@@ -138,7 +259,7 @@ def _check_edit(size, S, x_T, known=None, mask=None, known_noise=None, x_start=N
 
 def sampling(net, size, diffusion_hyperparams, condition=None, *, x_T=None, noise=None, seed=None,
              use_graph=True, net_steps=None, known=None, mask=None, known_noise=None, x_start=None, start_step=None,
-             start_noise=None):
+             start_noise=None, resample=None):
     """``x_0 = sampling(net, (B, C, L), dh, condition)`` as in ``generate.py:23-55``.
 
     Extra keyword-only arguments (not in the reference):
@@ -159,20 +280,25 @@ def sampling(net, size, diffusion_hyperparams, condition=None, *, x_T=None, nois
              a [B,C,L] tensor: the same with this noise; False: ``x_start`` is the state at ``start_step`` as given.
       Without ``net_steps`` an edited run goes through the schedule entry with ``net_steps = 0..T-1`` (bit-identical
       to ``dws_sampler_run``).
+    Resampling (``dws_sampler_run_program``; needs ``known`` / ``mask``):
+      resample  ``(jump, resamples)``: RePaint's schedule (``repaint_program``) -- at every ``jump``-th position the
+             chain goes back up ``jump`` steps and down again, ``resamples`` times in all, so that the generated part
+             is harmonised with the kept part.  ``noise`` and ``known_noise`` are then [V,B,C,L], indexed by the visit.
+             ``resamples = 1`` is the edited run above, bit for bit.
     """
     dh = diffusion_hyperparams
     T, Alpha, Alpha_bar, Sigma = dh["T"], dh["Alpha"], dh["Alpha_bar"], dh["Sigma"]
     assert len(Alpha) == T and len(Alpha_bar) == T and len(Sigma) == T and len(size) == 3
     edit = dict(known=known, mask=mask, known_noise=known_noise, x_start=x_start, start_step=start_step,
                 start_noise=start_noise)
-    if all(v is None for v in edit.values()):
+    if resample is None and all(v is None for v in edit.values()):
         edit = None
     elif net_steps is None:
         net_steps = np.arange(T, dtype=np.float32)
     if net_steps is not None:
         coef = np.stack([_host_table(Alpha)[0], _host_table(Alpha_bar)[0], _host_table(Sigma)[0]])
         return _run_schedule(net, size, _lib.DWS_SAMPLER_DDPM, net_steps, coef, condition, x_T, noise, seed, use_graph,
-                             edit=edit, levels=coef[1])
+                             edit=edit, levels=coef[1], resample=resample)
     lib = _lib.load()
     with torch.no_grad():
         x, init, nz, seed = _prepare_run(net, size, T, condition, x_T, noise, seed)
@@ -185,23 +311,29 @@ def sampling(net, size, diffusion_hyperparams, condition=None, *, x_T=None, nois
     return x
 
 
-def _run_schedule(net, size, kind, net_steps, coef, condition, x_T, noise, seed, use_graph, edit=None, levels=None):
+def _run_schedule(net, size, kind, net_steps, coef, condition, x_T, noise, seed, use_graph, edit=None, levels=None,
+                  resample=None):
     """``dws_sampler_run_schedule``: S steps s = S-1..0, the network at ``net_steps[s]``, update tables ``coef``.
-    ``edit``: the editing arguments of ``sampling`` (-> ``dws_sampler_run_edit``), ``levels`` the run's alpha_bar."""
+    ``edit``: the editing arguments of ``sampling`` (-> ``dws_sampler_run_edit``), ``levels`` the run's alpha_bar.
+    ``resample``: (jump, resamples) on top of ``edit`` (-> ``dws_sampler_run_program``)."""
     assert len(size) == 3
     steps = np.ascontiguousarray(np.asarray(net_steps, dtype=np.float32).reshape(-1))
     S = steps.shape[0]
     coef = np.ascontiguousarray(np.asarray(coef, dtype=np.float32))
     if S < 1 or coef.shape != ((5 if kind == _lib.DWS_SAMPLER_DDIM else 3), S):
         raise ValueError(f"sampler: {S} net steps with coefficient tables of shape {coef.shape}")
+    prog = None
+    if resample is not None:
+        prog = _check_resample(size, S, resample, noise, **(edit or {}))
     if edit is not None:
-        known, mask, known_noise, x_start, start_step, start_noise, qsample = _check_edit(size, S, x_T, **edit)
+        known, mask, known_noise, x_start, start_step, start_noise, qsample = _check_edit(
+            size, S, x_T, rows=None if prog is None else len(prog), **edit)
         if x_start is not None:
             x_T = x_start
     lib = _lib.load()
     fp = ctypes.POINTER(ctypes.c_float)
     with torch.no_grad():
-        x, init, nz, seed = _prepare_run(net, size, S, condition, x_T, noise, seed)
+        x, init, nz, seed = _prepare_run(net, size, S if prog is None else len(prog), condition, x_T, noise, seed)
         if edit is None:
             _lib.check(lib.dws_sampler_run_schedule(net._handle, x.data_ptr(), kind, S, steps.ctypes.data_as(fp),
                                                     coef.ctypes.data_as(fp), _lib.ptr(nz), seed, init,
@@ -215,9 +347,17 @@ def _run_schedule(net, size, kind, net_steps, coef, condition, x_T, noise, seed,
             ed = _lib.SamplerEdit(q.ctypes.data_as(fp), _lib.ptr(known), _lib.ptr(mask), _lib.ptr(known_noise),
                                   _lib.ptr(start_noise), start_step,
                                   _lib.DWS_START_QSAMPLE if qsample else _lib.DWS_START_AS_GIVEN)
-            _lib.check(lib.dws_sampler_run_edit(net._handle, x.data_ptr(), kind, S, steps.ctypes.data_as(fp),
-                                                coef.ctypes.data_as(fp), _lib.ptr(nz), seed, init,
-                                                1 if use_graph else 0, ctypes.byref(ed), _lib.current_stream()))
+            if prog is None:
+                _lib.check(lib.dws_sampler_run_edit(net._handle, x.data_ptr(), kind, S, steps.ctypes.data_as(fp),
+                                                    coef.ctypes.data_as(fp), _lib.ptr(nz), seed, init,
+                                                    1 if use_graph else 0, ctypes.byref(ed), _lib.current_stream()))
+            else:
+                prog = np.ascontiguousarray(prog, dtype=np.int32)
+                jc = np.ascontiguousarray(jump_coefficients(levels, prog, start_step))
+                _lib.check(lib.dws_sampler_run_program(
+                    net._handle, x.data_ptr(), kind, S, steps.ctypes.data_as(fp), coef.ctypes.data_as(fp), len(prog),
+                    prog.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), jc.ctypes.data_as(fp), _lib.ptr(nz), seed, init,
+                    1 if use_graph else 0, ctypes.byref(ed), _lib.current_stream()))
         torch.cuda.current_stream().synchronize()  # nz (and the editing tensors) must outlive the enqueued work
     return x
 
@@ -294,18 +434,20 @@ def ddim_coefficients(alpha_bar, tau, eta):
 
 def sampling_ddim(net, size, dh_train, steps, eta=0.0, condition=None, *, x_T=None, noise=None, seed=None,
                   use_graph=True, known=None, mask=None, known_noise=None, x_start=None, start_step=None,
-                  start_noise=None):
+                  start_noise=None, resample=None):
     """DDIM over ``ddim_steps(T, steps)`` of the training schedule ``dh_train`` (``steps``: S or an explicit list),
     deterministic for ``eta = 0``.  ``noise``: injected z, [S, B, C, L] (``noise[s]`` is used after step s > 0).
-    The editing arguments are those of ``sampling`` (levels: ``Alpha_bar[tau]``).  Not the reference's loop."""
+    The editing arguments and ``resample`` are those of ``sampling`` (levels: ``Alpha_bar[tau]``).  Not the reference's
+    loop."""
     tau = ddim_steps(dh_train["T"], steps)
     coef = ddim_coefficients(dh_train["Alpha_bar"], tau, eta)
     edit = dict(known=known, mask=mask, known_noise=known_noise, x_start=x_start, start_step=start_step,
                 start_noise=start_noise)
-    if all(v is None for v in edit.values()):
+    if resample is None and all(v is None for v in edit.values()):
         edit = None
     return _run_schedule(net, size, _lib.DWS_SAMPLER_DDIM, np.asarray(tau, dtype=np.float32), coef, condition, x_T,
-                         noise, seed, use_graph, edit=edit, levels=_host_table(dh_train["Alpha_bar"])[0][tau])
+                         noise, seed, use_graph, edit=edit, levels=_host_table(dh_train["Alpha_bar"])[0][tau],
+                         resample=resample)
 
 
 def sampling_aligned(net, size, diffusion_cfg, condition=None, **kw):

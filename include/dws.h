@@ -325,7 +325,7 @@ typedef struct dws_sampler_edit {
     const float*   edit_coef;     /* HOST   float[4][S] */
     const float*   known;         /* DEVICE float[B, C, L] or NULL */
     const uint8_t* mask;          /* DEVICE uint8[B, C, L] or NULL */
-    const float*   known_noise;   /* DEVICE float[S, B, C, L] or NULL */
+    const float*   known_noise;   /* DEVICE float[S, B, C, L] ([V, B, C, L] in a program run) or NULL */
     const float*   start_noise;   /* DEVICE float[B, C, L] or NULL */
     int32_t        start_step;
     int32_t        start_mode;
@@ -333,6 +333,52 @@ typedef struct dws_sampler_edit {
 int dws_sampler_run_edit(dws_model* m, float* x, int32_t kind, int32_t S, const float* net_steps,
                          const float* coef, const float* noise, uint64_t seed, int32_t init_from_seed,
                          int32_t use_graph, const dws_sampler_edit* edit, void* stream);
+
+/* RePaint's resampling (Lugmayr et al., CVPR 2022) on the editing entry: a PROGRAM of V visits in place of the countdown
+ * s0 .. 0, so that the chain can walk back up a few steps and down again and the generated part is harmonised with the
+ * kept part.  Everything dws_sampler_run_edit takes means the same here; `edit` must carry known and mask.
+ *
+ * Positions: the state is at position k in 0 .. S with level P[k], P[0] = 1, P[k] = level[k-1] (the p of edit_coef
+ * extended by P[S]); reverse step s takes it from position s+1 to s.  The run starts at K = start_step + 1.
+ *
+ *   visit_step   HOST int32[V] in execution order; entry i is visit number v = V-1-i (visits count down like steps).
+ *                  s >= 0  reverse visit at step s: dws_sampler_run_edit's step s unchanged in arithmetic and operation
+ *                          order -- the network at step-table row s, the update with tables row s, then where mask
+ *                          v = (s > 0) ? (q1[s] * known) + (q2[s] * zk) : known
+ *                  -j < 0  jump visit from the position k reached up to k + j: no network; the whole state, known
+ *                          region included, becomes   x = (ja * x) + (jb * z)
+ *                          two products and one sum, each rounded once -- one draw of the forward process' exact
+ *                          marginal q(x_{k+j} | x_k), equal in distribution to j single forward steps.
+ *   jump_coef    HOST float[2][V] = ja, jb indexed by v (sampling.jump_coefficients): ja = sqrt(P[k+j] / P[k]),
+ *                jb = sqrt(1 - P[k+j] / P[k]) in float64 from the float32 levels, rounded once; zero on reverse visits.
+ *   noise        optional DEVICE [V, B, C, L]: row v is the update noise of reverse visit v or z of jump visit v.
+ *   edit->known_noise  optional DEVICE [V, B, C, L]: row v is zk of reverse visit v.
+ *
+ * Philox streams, normal4(seed, stream, group): visit v (update noise of a reverse visit, z of a jump visit) is stream
+ * v; the known-region noise after reverse visit v is stream V + 1 + v; a drawn x_T is stream V; the start noise is stream
+ * 2V + 1.  No stream is used twice, and a step that is visited again draws fresh noise.  The program s0 .. 0 has v = s
+ * and reproduces dws_sampler_run_edit bit for bit; over a whole run (V = S) every stream id coincides too, with a partial
+ * start V = s0 + 1 < S numbers the known-region and start streams differently (bit-equal with injected noise).
+ *
+ * The device state holds the visit number beside the step word; the last block of every visit's kernel writes
+ * visit = v - 1 and step = step_of[v - 1] from a device table, so nothing crosses between host and device inside a run
+ * and the network reads row *step of the step table as before.  The host enqueues the visits in order: a reverse visit
+ * is a replay of the resampling step (forward + update + replacement), a graph of its own beside the unedited and the
+ * edited one; a jump visit is one kernel launch between the replays.  step_of and ja / jb sit in a model-owned buffer
+ * keyed on their contents: a new seed, x, known clip, mask, start step or program of the same V REPLAYS the graph, and
+ * calls of the three kinds alternate on one model without a capture (tap "sampler_graphs" counts all three).
+ * use_graph = 0 does the same walk with direct launches.
+ * Bad input -> DWS_ERR_INVALID, before anything is enqueued: what dws_sampler_run_edit rejects; known / mask missing;
+ * V < 1; a program that is no walk (the first reverse visit is not start_step, a reverse visit is not one below the
+ * position reached, a jump lands above K, the last visit is not reverse step 0); ja or jb not finite or ja <= 0. */
+int dws_sampler_run_program(dws_model* m, float* x, int32_t kind, int32_t S, const float* net_steps,
+                            const float* coef, int32_t V, const int32_t* visit_step, const float* jump_coef,
+                            const float* noise, uint64_t seed, int32_t init_from_seed, int32_t use_graph,
+                            const dws_sampler_edit* edit, void* stream);
+
+/* x[0 .. n) (DEVICE) = Philox stream `stream_id` of `seed` exactly as the samplers draw it: normal4(seed, stream_id, g)
+ * gives elements 4g .. 4g+3.  For checking the stream assignment of a seeded run from outside. */
+int dws_philox_normal(float* x, int64_t n, uint64_t seed, uint32_t stream_id, void* stream);
 
 /* Mel-spectrogram front-end of the vocoding path: TacotronSTFT.mel_spectrogram
  * (`dataloaders/stft.py:196-244`) as called by Mel2Samp.get_mel (`dataloaders/mel2samp.py:76-82`) and

@@ -8,7 +8,9 @@ Legs: config 4 (unet_d32_n6_T50_cond, B = 32, mel [1, 80, 63]) aligned S = 6 und
 build + capture + instantiate + S replays), repeat calls with a new seed and a new output tensor (replays only),
 the per-step time of the plain sampler's captured step (dws_sampler_steps) and the full-T dws_sampler_run call.
 Capture + instantiate alone: `capture_cost`.  `--legs edit_c4,edit_c2` (not in the default list): the unedited schedule
-call against the same call with a half-clip continuation mask (dws_sampler_run_edit), alternating in one process."""
+call against the same call with a half-clip continuation mask (dws_sampler_run_edit), alternating in one process.
+`--legs resample_c4` (not in the default list either): that edited call against the same call with resample=(2, 2)
+(dws_sampler_run_program: 10 network evaluations and 2 jumps for S = 6), alternating in one process."""
 import argparse
 import json
 import os
@@ -185,6 +187,54 @@ def edit_leg(name, cfg_name, precision, kind, S, repeats):
     return rec
 
 
+def resample_leg(name, cfg_name, precision, S, repeats, jump=2, resamples=2):
+    """The resampling call's cost per network evaluation beside the edited call's per step: in one process and
+    alternating, the aligned call with a half-clip continuation mask (the yardstick) and the same call with
+    resample=(jump, resamples); every call a new seed.  The margin for the difference per evaluation is the edited
+    leg's own min-max spread per step.  Also first call - repeat call of the resampling graph (capture + instantiate;
+    the step table and the other two graphs exist by then)."""
+    from benchlib.configs import CONFIGS, build_model
+    from diffwave_sashimi_amd.sampling import program_evaluations, repaint_program, sampling_aligned, spans_to_mask
+    cfg = CONFIGS[cfg_name]
+    dev = torch.device("cuda")
+    net = build_model(cfg, dev)
+    if precision != "f32":
+        net.set_option("precision", precision)
+    B, L = cfg["B"], cfg["L"]
+    size = (B, 1, L)
+    mel = None
+    if "Tmel" in cfg:
+        g = torch.Generator().manual_seed(2)
+        mel = (torch.rand(1, 80, cfg["Tmel"], generator=g) * 13.5 - 11.5).to(dev)
+    g = torch.Generator().manual_seed(3)
+    edit = dict(known=(torch.rand(size, generator=g) * 2 - 1).to(dev), mask=spans_to_mask(size, [[0, L // 2]]).to(dev))
+    dcfg = dict(cfg["diffusion"], beta=[1e-4, 1e-3, 1e-2, 0.05, 0.2, 0.5][:S])
+    call = lambda seed, **kw: sampling_aligned(net, size, dcfg, mel, seed=seed, **edit, **kw)
+    evals = program_evaluations(S, jump, resamples)
+    V = len(repaint_program(S, jump, resamples))
+    sampling_aligned(net, size, dcfg, mel, seed=1)          # warm-up: code objects, step table, the unedited graph
+    call(2), call(3)                                        # ... and the edited graph
+    first = _clock(lambda: call(100, resample=(jump, resamples)))
+    call(101, resample=(jump, resamples))
+    edited, resampled = [], []
+    for i in range(repeats):
+        edited.append(_clock(lambda: call(200 + i)))
+        resampled.append(_clock(lambda: call(300 + i, resample=(jump, resamples))))
+    graphs = int(net.read_tap("sampler_graphs", (1,)).item())
+    me, mr = statistics.median(edited), statistics.median(resampled)
+    rec = dict(leg=name, config=cfg_name, precision=precision, sampler="aligned", S=S, B=B, L=L, mask="first half kept",
+               resample=[jump, resamples], visits=V, evaluations=evals, jumps=V - evals,
+               edited_call=_stats(edited), resampled_call=_stats(resampled),
+               edited_per_step_ms=round(me / S, 3), resampled_per_evaluation_ms=round(mr / evals, 3),
+               per_evaluation_minus_per_step_ms=round(mr / evals - me / S, 3),
+               edited_per_step_spread_ms=round((max(edited) - min(edited)) / S, 3),
+               resampled_first_call=round(first, 3), resampled_first_minus_repeat_ms=round(first - mr, 3),
+               graphs_after_repeats=graphs)
+    del net
+    torch.cuda.empty_cache()
+    return rec
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--repeats", type=int, default=5)
@@ -200,6 +250,8 @@ def main():
                                     args.repeats),
         "edit_c2": lambda: edit_leg("config2 DDIM S=50 bf16x6, continuation", "wnet_h256_d36_T200", "bf16x6", "ddim", 50,
                                     args.repeats),
+        "resample_c4": lambda: resample_leg("config4 aligned S=6 f32, continuation, resample=(2,2)",
+                                            "unet_d32_n6_T50_cond", "f32", 6, args.repeats),
         "capture": lambda: [capture_cost("unet_d32_n6_T50_cond", "f32", "ddim", 6, args.repeats),
                             capture_cost("wnet_h256_d36_T200", "bf16x6", "ddim", 50, args.repeats)],
     }
