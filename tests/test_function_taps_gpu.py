@@ -9,6 +9,8 @@
                                                                  tensors go through the HIP LayerNorm)
   a9  FF (`models/sashimi.py:60-75`)                             taps "out:<block>" of a block whose S4 branch is
                                                                  switched off vs oracle.sashimi.ff(LN2(x))
+  a14 S4.forward (`models/s4.py:1376-1437`)                      tests/test_s4_convolution_gpu.py: the same tap with the tail
+                                                                 made transparent vs a float64 convolution, every FFT plan
 """
 import numpy as np
 import pytest
