@@ -11,7 +11,7 @@ LIB_PATH = os.environ.get("DWS_LIB") or os.path.join(HERE, "libdws.so")
 DWS_OK, DWS_ERR_INVALID, DWS_ERR_UNSUPPORTED, DWS_ERR_HIP, DWS_ERR_STATE = 0, -1, -2, -3, -4
 DWS_KIND_WAVENET, DWS_KIND_SASHIMI = 1, 2
 DWS_MAX_POOL = 8
-DWS_SAMPLER_DDPM, DWS_SAMPLER_DDIM = 0, 1
+DWS_SAMPLER_DDPM, DWS_SAMPLER_DDIM, DWS_SAMPLER_DPMPP2M = 0, 1, 2
 DWS_START_AS_GIVEN, DWS_START_QSAMPLE = 0, 1
 
 c_f32p = ctypes.c_void_p  # device pointers travel as integers

@@ -187,10 +187,12 @@ struct dws_model {
     // few-step sampler (dws_sampler_run_schedule): tables, state, x and graph of its own -- the two entry points never
     // replay each other's graph.  Its graph updates sch_x in place and reads the seed from sch_state, so neither the
     // caller's x nor the seed is baked in.
-    dws::DevBuf sch_tables;               // DDPM [3][S] c1, c2, sigma; DDIM [5][S] k1 .. k5
+    dws::DevBuf sch_tables;               // DDPM [3][S] c1, c2, sigma; DDIM [5][S] k1 .. k5; DPM-Solver++(2M) [5][S] m1 .. m5
     std::vector<float> sch_host_tables;   // host copy of what is resident (upload skipped when identical)
-    dws::DevBuf sch_state;                // int32 step index, int32 finished update blocks, uint64 Philox seed, int32 visit
+    dws::DevBuf sch_state;                // int32 step index, int32 finished update blocks, uint64 Philox seed, int32 visit,
+                                          // int32 history-valid word (DPM-Solver++(2M): sch_hist holds the last step's x0)
     dws::DevBuf sch_x;                    // [B, C, L]
+    dws::DevBuf sch_hist;                 // [B, C, L] the previous step's data prediction (DWS_SAMPLER_DPMPP2M; first use)
     hipGraphExec_t sch_graph = nullptr;
     struct SchKey {
         int64_t B, L;
@@ -200,11 +202,12 @@ struct dws_model {
         const void *edit, *known, *mask, *known_noise;   // the edited step's (all null for the unedited one)
         int V = 0;                                       // the resampling step's: visits and the program tables
         const void* prog = nullptr;
+        const void* hist = nullptr;                      // the multistep kind's history buffer (null for the others)
         bool operator==(const SchKey& o) const {
             return B == o.B && L == o.L && S == o.S && kind == o.kind && vec == o.vec && tables == o.tables &&
                    noise == o.noise && eps == o.eps && x == o.x && state == o.state && table_gen == o.table_gen &&
                    edit == o.edit && known == o.known && mask == o.mask && known_noise == o.known_noise && V == o.V &&
-                   prog == o.prog;
+                   prog == o.prog && hist == o.hist;
         }
     } sch_key{};
     // editing (dws_sampler_run_edit): the step that ends in the replacement of the known region is a graph of its own

@@ -47,11 +47,14 @@ __device__ __forceinline__ void normal4(uint64_t seed, uint32_t t, uint64_t g, f
 // sampler state in device memory: [0] the step index t, [1] number of update blocks that have finished this step
 __global__ void smp_set_step_kernel(int* t_dev, int t) { t_dev[0] = t; t_dev[1] = 0; }
 
-// the few-step sampler's state also holds the Philox seed ([2..3]): its captured step bakes in no seed
+// the few-step sampler's state also holds the Philox seed ([2..3]): its captured step bakes in no seed.  [5] is the
+// history-valid word of the multistep kind (DWS_SAMPLER_DPMPP2M): 0 at the start of every run, 1 once a step of that kind
+// has left its data prediction in the history buffer, 0 again behind a jump visit
 __global__ void smp_set_state_kernel(int* st, int t, uint64_t seed) {
     st[0] = t;
     st[1] = 0;
     *reinterpret_cast<uint64_t*>(st + 2) = seed;
+    st[5] = 0;
 }
 
 // a program run (dws_sampler_run_program) also keeps the visit number v in the state ([4]): the noise rows and Philox
@@ -61,16 +64,20 @@ __global__ void smp_set_program_state_kernel(int* st, int t, int v, uint64_t see
     st[1] = 0;
     *reinterpret_cast<uint64_t*>(st + 2) = seed;
     st[4] = v;
+    st[5] = 0;
 }
 
 // End of a visit's kernel: the last block to arrive moves the program on, visit <- v - 1 and step <- step_of[v - 1]
 // (the row the next visit's network reads; -1 behind the last visit).  Every block has read the state by then and the
 // next kernel that reads it is stream-ordered behind this one, as with the step counter of the kernels above.
-__device__ __forceinline__ void smp_program_advance(int* __restrict__ st, const int* __restrict__ step_of, int v) {
+// hist_valid >= 0: the new value of the history-valid word (1 behind a multistep reverse visit, 0 behind a jump visit).
+__device__ __forceinline__ void smp_program_advance(int* __restrict__ st, const int* __restrict__ step_of, int v,
+                                                    int hist_valid) {
     if (atomicAdd(reinterpret_cast<unsigned*>(st + 1), 1u) == gridDim.x - 1) {
         st[1] = 0;
         st[4] = v - 1;
         st[0] = v > 0 ? step_of[v - 1] : -1;
+        if (hist_valid >= 0) st[5] = hist_valid;
     }
 }
 
@@ -198,6 +205,87 @@ __global__ void smp_ddim_kernel(float* __restrict__ x, const float* __restrict__
     }
 }
 
+// DPM-Solver++(2M) step (Lu et al., 2022; the multistep solver in the data prediction) with m[5][S] = m1 .. m5 of
+// sampling.dpmpp_coefficients, per element:
+//   p = m1 eps;  d = x - p;  x0 = d / m2;  D = x0;  if second: g = x0 - hist; e = m5 g; D = x0 + e
+//   a = m3 x;  b = m4 D;  v = a + b;  hist = x0
+// every product, difference, quotient and sum rounded once in this order (contraction off, plain operators).  Returns v
+// and leaves x0 in `h`.  With second = false this is DDIM's step at eta = 0 written in the data prediction.
+__device__ __forceinline__ float smp_dpmpp_elem(float x, float eps, float& h, float m1, float m2, float m3, float m4,
+                                                float m5, bool second) {
+#pragma clang fp contract(off)
+    const float p = m1 * eps;
+    const float d = x - p;
+    const float x0 = d / m2;
+    float D = x0;
+    if (second) {
+        const float g = x0 - h;
+        const float e = m5 * g;
+        D = x0 + e;
+    }
+    const float a = m3 * x;
+    const float b = m4 * D;
+    h = x0;
+    return a + b;
+}
+
+// Plain step of DWS_SAMPLER_DPMPP2M.  hist [B, C, L] carries the previous step's x0 across the replays; it is read only
+// when second = (history-valid word st[5] != 0) && m5[s] != 0 and written by every step.  No noise: the solver is
+// deterministic.  The last block counts the step down and sets the valid word.
+// VEC: every group of 4 is in range and x / eps / hist are 16-byte aligned -> float4 loads and stores.
+template <bool VEC>
+__global__ void smp_dpmpp_kernel(float* __restrict__ x, const float* __restrict__ eps, float* __restrict__ hist,
+                                 const float* __restrict__ m, int* __restrict__ st, size_t n, int S) {
+#pragma clang fp contract(off)
+    const int s = __builtin_amdgcn_readfirstlane(*(volatile int*)st);
+    const int valid = __builtin_amdgcn_readfirstlane(*(volatile int*)(st + 5));
+    const float m1 = m[s], m2 = m[S + s], m3 = m[2 * S + s], m4 = m[3 * S + s], m5 = m[4 * S + s];
+    const bool second = valid != 0 && m5 != 0.f;
+    for (size_t g = (size_t)blockIdx.x * blockDim.x + threadIdx.x; g * 4 < n; g += (size_t)gridDim.x * blockDim.x) {
+        float xv[4] = {0.f, 0.f, 0.f, 0.f}, ev[4] = {0.f, 0.f, 0.f, 0.f}, hv[4] = {0.f, 0.f, 0.f, 0.f};
+        if (VEC) {
+            const float4 a = reinterpret_cast<const float4*>(x)[g], e = reinterpret_cast<const float4*>(eps)[g];
+            xv[0] = a.x; xv[1] = a.y; xv[2] = a.z; xv[3] = a.w;
+            ev[0] = e.x; ev[1] = e.y; ev[2] = e.z; ev[3] = e.w;
+            if (second) {
+                const float4 q = reinterpret_cast<const float4*>(hist)[g];
+                hv[0] = q.x; hv[1] = q.y; hv[2] = q.z; hv[3] = q.w;
+            }
+        } else {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const size_t i = g * 4 + j;
+                if (i >= n) break;
+                xv[j] = x[i]; ev[j] = eps[i];
+                if (second) hv[j] = hist[i];
+            }
+        }
+        float r[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) r[j] = smp_dpmpp_elem(xv[j], ev[j], hv[j], m1, m2, m3, m4, m5, second);
+        if (VEC) {
+            reinterpret_cast<float4*>(x)[g] = make_float4(r[0], r[1], r[2], r[3]);
+            reinterpret_cast<float4*>(hist)[g] = make_float4(hv[0], hv[1], hv[2], hv[3]);
+        } else {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const size_t i = g * 4 + j;
+                if (i >= n) break;
+                x[i] = r[j];
+                hist[i] = hv[j];
+            }
+        }
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        if (atomicAdd(reinterpret_cast<unsigned*>(st + 1), 1u) == gridDim.x - 1) {
+            st[1] = 0;
+            st[0] = s - 1;
+            st[5] = 1;
+        }
+    }
+}
+
 // Editing step of dws_sampler_run_edit (inpainting by replacement: Song et al., ICLR 2021, "imputation"; the base case
 // of RePaint): the DDPM (tab = c1, c2, sigma) or DDIM (tab = k1 .. k5) update of step s exactly as smp_update_kernel /
 // smp_ddim_kernel write it, then, where mask != 0, the element is overwritten with the known audio y noised to the level
@@ -205,25 +293,29 @@ __global__ void smp_ddim_kernel(float* __restrict__ x, const float* __restrict__
 //   v = (s > 0) ? (q1[s] * y) + (q2[s] * zk) : y          edit = q1[S], q2[S] (sampling.edit_coefficients)
 // two products and one sum, each rounded once (contraction off, plain operators).  zk: known_noise[s] or Philox stream
 // S + 1 + s in normal4's layout, drawn only for groups that hold a known element (no other element reads it).
-// VEC: every group of 4 is in range and all pointers are 16-byte aligned -> float4 for x / eps / y / the noises and the
-// four mask bytes of the group as one 32-bit load.
+// KIND = DWS_SAMPLER_DPMPP2M (tab = m1 .. m5): smp_dpmpp_kernel's step -- no update noise; hist gets the network's
+// prediction x0, before the replacement; the last block also sets the history-valid word.  hist is null for the others.
+// VEC: every group of 4 is in range and all pointers are 16-byte aligned -> float4 for x / eps / y / the noises / hist and
+// the four mask bytes of the group as one 32-bit load.
 template <int KIND, bool VEC>
 __global__ void smp_edit_kernel(float* __restrict__ x, const float* __restrict__ eps, const float* __restrict__ tab,
                                 const float* __restrict__ edit, int* __restrict__ st, const float* __restrict__ noise,
                                 const float* __restrict__ y, const uint8_t* __restrict__ mask,
-                                const float* __restrict__ known_noise, size_t n, int S) {
+                                const float* __restrict__ known_noise, float* __restrict__ hist, size_t n, int S) {
 #pragma clang fp contract(off)
     const int s = __builtin_amdgcn_readfirstlane(*(volatile int*)st);
     const uint64_t seed = *(const volatile uint64_t*)(st + 2);
+    const int valid = KIND == DWS_SAMPLER_DPMPP2M ? __builtin_amdgcn_readfirstlane(*(volatile int*)(st + 5)) : 0;
     const float k1 = tab[s], k2 = tab[S + s], k3 = tab[2 * S + s];
-    const float k4 = KIND == DWS_SAMPLER_DDIM ? tab[3 * S + s] : 0.f, k5 = KIND == DWS_SAMPLER_DDIM ? tab[4 * S + s] : 0.f;
-    const bool add = KIND == DWS_SAMPLER_DDIM ? (s > 0 && k5 > 0.f) : s > 0;
+    const float k4 = KIND != DWS_SAMPLER_DDPM ? tab[3 * S + s] : 0.f, k5 = KIND != DWS_SAMPLER_DDPM ? tab[4 * S + s] : 0.f;
+    const bool add = KIND == DWS_SAMPLER_DPMPP2M ? false : KIND == DWS_SAMPLER_DDIM ? (s > 0 && k5 > 0.f) : s > 0;
+    const bool second = KIND == DWS_SAMPLER_DPMPP2M && valid != 0 && k5 != 0.f;
     const float q1 = edit[s], q2 = edit[S + s];
     const float* nz = noise ? noise + (size_t)s * n : nullptr;
     const float* kz = known_noise ? known_noise + (size_t)s * n : nullptr;
     for (size_t g = (size_t)blockIdx.x * blockDim.x + threadIdx.x; g * 4 < n; g += (size_t)gridDim.x * blockDim.x) {
         float xv[4] = {0.f, 0.f, 0.f, 0.f}, ev[4] = {0.f, 0.f, 0.f, 0.f}, z[4] = {0.f, 0.f, 0.f, 0.f};
-        float yv[4] = {0.f, 0.f, 0.f, 0.f}, zk[4] = {0.f, 0.f, 0.f, 0.f};
+        float yv[4] = {0.f, 0.f, 0.f, 0.f}, zk[4] = {0.f, 0.f, 0.f, 0.f}, hv[4] = {0.f, 0.f, 0.f, 0.f};
         uint32_t mk = 0;    // byte j: mask of element 4g + j
         if (VEC) {
             const float4 a = reinterpret_cast<const float4*>(x)[g], e = reinterpret_cast<const float4*>(eps)[g];
@@ -232,6 +324,10 @@ __global__ void smp_edit_kernel(float* __restrict__ x, const float* __restrict__
             if (add && nz) {
                 const float4 q = reinterpret_cast<const float4*>(nz)[g];
                 z[0] = q.x; z[1] = q.y; z[2] = q.z; z[3] = q.w;
+            }
+            if (second) {
+                const float4 q = reinterpret_cast<const float4*>(hist)[g];
+                hv[0] = q.x; hv[1] = q.y; hv[2] = q.z; hv[3] = q.w;
             }
             mk = reinterpret_cast<const uint32_t*>(mask)[g];
             if (mk) {
@@ -249,6 +345,7 @@ __global__ void smp_edit_kernel(float* __restrict__ x, const float* __restrict__
                 if (i >= n) break;
                 xv[j] = x[i]; ev[j] = eps[i];
                 if (add && nz) z[j] = nz[i];
+                if (second) hv[j] = hist[i];
                 if (mask[i]) {
                     mk |= 1u << (8 * j);
                     yv[j] = y[i];
@@ -262,7 +359,9 @@ __global__ void smp_edit_kernel(float* __restrict__ x, const float* __restrict__
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             float v;
-            if (KIND == DWS_SAMPLER_DDIM) {      // smp_ddim_kernel's order
+            if (KIND == DWS_SAMPLER_DPMPP2M) {          // smp_dpmpp_kernel's order; hv[j] <- x0
+                v = smp_dpmpp_elem(xv[j], ev[j], hv[j], k1, k2, k3, k4, k5, second);
+            } else if (KIND == DWS_SAMPLER_DDIM) {      // smp_ddim_kernel's order
                 const float p = k1 * ev[j];
                 const float d = xv[j] - p;
                 const float u = d / k2;
@@ -293,12 +392,15 @@ __global__ void smp_edit_kernel(float* __restrict__ x, const float* __restrict__
         }
         if (VEC) {
             reinterpret_cast<float4*>(x)[g] = make_float4(r[0], r[1], r[2], r[3]);
+            if (KIND == DWS_SAMPLER_DPMPP2M)
+                reinterpret_cast<float4*>(hist)[g] = make_float4(hv[0], hv[1], hv[2], hv[3]);
         } else {
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 const size_t i = g * 4 + j;
                 if (i >= n) break;
                 x[i] = r[j];
+                if (KIND == DWS_SAMPLER_DPMPP2M) hist[i] = hv[j];
             }
         }
     }
@@ -307,6 +409,7 @@ __global__ void smp_edit_kernel(float* __restrict__ x, const float* __restrict__
         if (atomicAdd(reinterpret_cast<unsigned*>(st + 1), 1u) == gridDim.x - 1) {
             st[1] = 0;
             st[0] = s - 1;
+            if (KIND == DWS_SAMPLER_DPMPP2M) st[5] = 1;
         }
     }
 }
@@ -314,26 +417,29 @@ __global__ void smp_edit_kernel(float* __restrict__ x, const float* __restrict__
 // Reverse visit of dws_sampler_run_program (RePaint's resampling): smp_edit_kernel's update and replacement at step
 // s = st[0], in the same operation order, but the visit number v = st[4] names the noise: noise[v] / known_noise[v], or
 // Philox streams v and V + 1 + v (a step that is visited again draws fresh noise).  The last block moves the program on
-// (smp_program_advance) instead of counting the step down.
+// (smp_program_advance) instead of counting the step down, and sets the history-valid word for DWS_SAMPLER_DPMPP2M.
 template <int KIND, bool VEC>
 __global__ void smp_resample_kernel(float* __restrict__ x, const float* __restrict__ eps, const float* __restrict__ tab,
                                     const float* __restrict__ edit, int* __restrict__ st,
                                     const int* __restrict__ step_of, const float* __restrict__ noise,
                                     const float* __restrict__ y, const uint8_t* __restrict__ mask,
-                                    const float* __restrict__ known_noise, size_t n, int S, int V) {
+                                    const float* __restrict__ known_noise, float* __restrict__ hist, size_t n, int S,
+                                    int V) {
 #pragma clang fp contract(off)
     const int s = __builtin_amdgcn_readfirstlane(*(volatile int*)st);
     const int v = __builtin_amdgcn_readfirstlane(*(volatile int*)(st + 4));
     const uint64_t seed = *(const volatile uint64_t*)(st + 2);
+    const int valid = KIND == DWS_SAMPLER_DPMPP2M ? __builtin_amdgcn_readfirstlane(*(volatile int*)(st + 5)) : 0;
     const float k1 = tab[s], k2 = tab[S + s], k3 = tab[2 * S + s];
-    const float k4 = KIND == DWS_SAMPLER_DDIM ? tab[3 * S + s] : 0.f, k5 = KIND == DWS_SAMPLER_DDIM ? tab[4 * S + s] : 0.f;
-    const bool add = KIND == DWS_SAMPLER_DDIM ? (s > 0 && k5 > 0.f) : s > 0;
+    const float k4 = KIND != DWS_SAMPLER_DDPM ? tab[3 * S + s] : 0.f, k5 = KIND != DWS_SAMPLER_DDPM ? tab[4 * S + s] : 0.f;
+    const bool add = KIND == DWS_SAMPLER_DPMPP2M ? false : KIND == DWS_SAMPLER_DDIM ? (s > 0 && k5 > 0.f) : s > 0;
+    const bool second = KIND == DWS_SAMPLER_DPMPP2M && valid != 0 && k5 != 0.f;
     const float q1 = edit[s], q2 = edit[S + s];
     const float* nz = noise ? noise + (size_t)v * n : nullptr;
     const float* kz = known_noise ? known_noise + (size_t)v * n : nullptr;
     for (size_t g = (size_t)blockIdx.x * blockDim.x + threadIdx.x; g * 4 < n; g += (size_t)gridDim.x * blockDim.x) {
         float xv[4] = {0.f, 0.f, 0.f, 0.f}, ev[4] = {0.f, 0.f, 0.f, 0.f}, z[4] = {0.f, 0.f, 0.f, 0.f};
-        float yv[4] = {0.f, 0.f, 0.f, 0.f}, zk[4] = {0.f, 0.f, 0.f, 0.f};
+        float yv[4] = {0.f, 0.f, 0.f, 0.f}, zk[4] = {0.f, 0.f, 0.f, 0.f}, hv[4] = {0.f, 0.f, 0.f, 0.f};
         uint32_t mk = 0;    // byte j: mask of element 4g + j
         if (VEC) {
             const float4 a = reinterpret_cast<const float4*>(x)[g], e = reinterpret_cast<const float4*>(eps)[g];
@@ -342,6 +448,10 @@ __global__ void smp_resample_kernel(float* __restrict__ x, const float* __restri
             if (add && nz) {
                 const float4 q = reinterpret_cast<const float4*>(nz)[g];
                 z[0] = q.x; z[1] = q.y; z[2] = q.z; z[3] = q.w;
+            }
+            if (second) {
+                const float4 q = reinterpret_cast<const float4*>(hist)[g];
+                hv[0] = q.x; hv[1] = q.y; hv[2] = q.z; hv[3] = q.w;
             }
             mk = reinterpret_cast<const uint32_t*>(mask)[g];
             if (mk) {
@@ -359,6 +469,7 @@ __global__ void smp_resample_kernel(float* __restrict__ x, const float* __restri
                 if (i >= n) break;
                 xv[j] = x[i]; ev[j] = eps[i];
                 if (add && nz) z[j] = nz[i];
+                if (second) hv[j] = hist[i];
                 if (mask[i]) {
                     mk |= 1u << (8 * j);
                     yv[j] = y[i];
@@ -372,7 +483,9 @@ __global__ void smp_resample_kernel(float* __restrict__ x, const float* __restri
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             float w;
-            if (KIND == DWS_SAMPLER_DDIM) {      // smp_ddim_kernel's order
+            if (KIND == DWS_SAMPLER_DPMPP2M) {          // smp_dpmpp_kernel's order; hv[j] <- x0
+                w = smp_dpmpp_elem(xv[j], ev[j], hv[j], k1, k2, k3, k4, k5, second);
+            } else if (KIND == DWS_SAMPLER_DDIM) {      // smp_ddim_kernel's order
                 const float p = k1 * ev[j];
                 const float d = xv[j] - p;
                 const float u = d / k2;
@@ -403,23 +516,28 @@ __global__ void smp_resample_kernel(float* __restrict__ x, const float* __restri
         }
         if (VEC) {
             reinterpret_cast<float4*>(x)[g] = make_float4(r[0], r[1], r[2], r[3]);
+            if (KIND == DWS_SAMPLER_DPMPP2M)
+                reinterpret_cast<float4*>(hist)[g] = make_float4(hv[0], hv[1], hv[2], hv[3]);
         } else {
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 const size_t i = g * 4 + j;
                 if (i >= n) break;
                 x[i] = r[j];
+                if (KIND == DWS_SAMPLER_DPMPP2M) hist[i] = hv[j];
             }
         }
     }
     __syncthreads();
-    if (threadIdx.x == 0) smp_program_advance(st, step_of, v);
+    if (threadIdx.x == 0) smp_program_advance(st, step_of, v, KIND == DWS_SAMPLER_DPMPP2M ? 1 : -1);
 }
 
 // Jump visit of dws_sampler_run_program: the whole state, known region included, goes from position k up to k + j in one
 // draw of the forward process' exact marginal q(x_{k+j} | x_k),
 //   x = (ja * x) + (jb * z)      ja = jump[v], jb = jump[V + v] (sampling.jump_coefficients)
 // two products and one sum, each rounded once.  z: noise[v] or Philox stream v in normal4's layout.  No network runs.
+// The jump re-noises the state, so the last block also clears the history-valid word: the multistep kind's next step is
+// first order.
 // VEC: every group of 4 is in range and x / noise are 16-byte aligned -> float4 loads and stores.
 template <bool VEC>
 __global__ void smp_jump_kernel(float* __restrict__ x, const float* __restrict__ jump, int* __restrict__ st,
@@ -467,7 +585,7 @@ __global__ void smp_jump_kernel(float* __restrict__ x, const float* __restrict__
         }
     }
     __syncthreads();
-    if (threadIdx.x == 0) smp_program_advance(st, step_of, v);
+    if (threadIdx.x == 0) smp_program_advance(st, step_of, v, 0);
 }
 
 // Partial start in q-sample mode: x holds clean audio and becomes the state at step s0,
@@ -637,8 +755,8 @@ struct ProgStep {
     int V;
 };
 
-// One reverse step of the schedule: forward at row *st of the step table, then the DDPM or DDIM update (with the
-// replacement of the known region when `ed` is given; as a visit of a program when `pr` is given too).
+// One reverse step of the schedule: forward at row *st of the step table, then the DDPM, DDIM or DPM-Solver++(2M) update
+// (with the replacement of the known region when `ed` is given; as a visit of a program when `pr` is given too).
 static int schedule_step(dws_model* m, float* x, int kind, int S, const float* noise, bool vec, const EditStep* ed,
                          const ProgStep* pr, hipStream_t s) {
     const size_t n = (size_t)m->B * m->d.out_channels * m->L;
@@ -647,14 +765,20 @@ static int schedule_step(dws_model* m, float* x, int kind, int S, const float* n
     const int rc = m->forward(x, nullptr, m->smp_eps.f(), s);
     m->step_idx = nullptr;
     DWS_TRY(rc);
+    // dws_profile_enable("smp_update"): the update kernel of an uncaptured step, by kind
+    ProfileScope prof(kind == DWS_SAMPLER_DDPM ? "smp_update_ddpm" : kind == DWS_SAMPLER_DDIM ? "smp_update_ddim"
+                                                                                             : "smp_update_dpmpp2m", s);
     const int blocks = (int)std::min<size_t>(ceil_div(n, 4 * 256), 4096);
+    float* hist = kind == DWS_SAMPLER_DPMPP2M ? m->sch_hist.f() : nullptr;   // the multistep kind's history (allocated by the caller)
     if (ed && pr) {
 #define DWS_RESAMPLE_LAUNCH(KIND, VEC)                                                                                 \
     hipLaunchKernelGGL((smp_resample_kernel<KIND, VEC>), dim3(blocks), dim3(256), 0, s, x, m->smp_eps.f(),             \
-                       m->sch_tables.f(), ed->table, st, pr->step_of, noise, ed->known, ed->mask, ed->known_noise, n,  \
-                       S, pr->V)
+                       m->sch_tables.f(), ed->table, st, pr->step_of, noise, ed->known, ed->mask, ed->known_noise,     \
+                       hist, n, S, pr->V)
         if (kind == DWS_SAMPLER_DDPM) {
             if (vec) DWS_RESAMPLE_LAUNCH(DWS_SAMPLER_DDPM, true); else DWS_RESAMPLE_LAUNCH(DWS_SAMPLER_DDPM, false);
+        } else if (kind == DWS_SAMPLER_DPMPP2M) {
+            if (vec) DWS_RESAMPLE_LAUNCH(DWS_SAMPLER_DPMPP2M, true); else DWS_RESAMPLE_LAUNCH(DWS_SAMPLER_DPMPP2M, false);
         } else {
             if (vec) DWS_RESAMPLE_LAUNCH(DWS_SAMPLER_DDIM, true); else DWS_RESAMPLE_LAUNCH(DWS_SAMPLER_DDIM, false);
         }
@@ -664,9 +788,11 @@ static int schedule_step(dws_model* m, float* x, int kind, int S, const float* n
     if (ed) {
 #define DWS_EDIT_LAUNCH(KIND, VEC)                                                                                     \
     hipLaunchKernelGGL((smp_edit_kernel<KIND, VEC>), dim3(blocks), dim3(256), 0, s, x, m->smp_eps.f(),                 \
-                       m->sch_tables.f(), ed->table, st, noise, ed->known, ed->mask, ed->known_noise, n, S)
+                       m->sch_tables.f(), ed->table, st, noise, ed->known, ed->mask, ed->known_noise, hist, n, S)
         if (kind == DWS_SAMPLER_DDPM) {
             if (vec) DWS_EDIT_LAUNCH(DWS_SAMPLER_DDPM, true); else DWS_EDIT_LAUNCH(DWS_SAMPLER_DDPM, false);
+        } else if (kind == DWS_SAMPLER_DPMPP2M) {
+            if (vec) DWS_EDIT_LAUNCH(DWS_SAMPLER_DPMPP2M, true); else DWS_EDIT_LAUNCH(DWS_SAMPLER_DPMPP2M, false);
         } else {
             if (vec) DWS_EDIT_LAUNCH(DWS_SAMPLER_DDIM, true); else DWS_EDIT_LAUNCH(DWS_SAMPLER_DDIM, false);
         }
@@ -676,6 +802,12 @@ static int schedule_step(dws_model* m, float* x, int kind, int S, const float* n
     if (kind == DWS_SAMPLER_DDPM)
         hipLaunchKernelGGL(smp_update_kernel, dim3(blocks), dim3(256), 0, s, x, m->smp_eps.f(), m->sch_tables.f(), st,
                            noise, (uint64_t)0, reinterpret_cast<const uint64_t*>(st + 2), n, S);
+    else if (kind == DWS_SAMPLER_DPMPP2M && vec)
+        hipLaunchKernelGGL(smp_dpmpp_kernel<true>, dim3(blocks), dim3(256), 0, s, x, m->smp_eps.f(), hist,
+                           m->sch_tables.f(), st, n, S);
+    else if (kind == DWS_SAMPLER_DPMPP2M)
+        hipLaunchKernelGGL(smp_dpmpp_kernel<false>, dim3(blocks), dim3(256), 0, s, x, m->smp_eps.f(), hist,
+                           m->sch_tables.f(), st, n, S);
     else if (vec)
         hipLaunchKernelGGL(smp_ddim_kernel<true>, dim3(blocks), dim3(256), 0, s, x, m->smp_eps.f(), m->sch_tables.f(),
                            st, noise, n, S);
@@ -694,19 +826,30 @@ static int schedule_step(dws_model* m, float* x, int kind, int S, const float* n
 int sampler_run_schedule(dws_model* m, float* x, int kind, int S, const float* net_steps, const float* coef,
                          const float* noise, uint64_t seed, int init_from_seed, int use_graph,
                          const dws_sampler_edit* e, const SamplerProgram* pg, hipStream_t s) {
-    DWS_CHECK(kind == DWS_SAMPLER_DDPM || kind == DWS_SAMPLER_DDIM, DWS_ERR_INVALID, "sampler: unknown kind %d", kind);
+    DWS_CHECK(kind == DWS_SAMPLER_DDPM || kind == DWS_SAMPLER_DDIM || kind == DWS_SAMPLER_DPMPP2M, DWS_ERR_INVALID,
+              "sampler: unknown kind %d", kind);
     DWS_CHECK(S >= 1, DWS_ERR_INVALID, "sampler: S = %d steps (needs S >= 1)", S);
     DWS_CHECK(net_steps && coef, DWS_ERR_INVALID, "sampler: null net_steps or coefficients");
     for (int i = 0; i < S; ++i)
         DWS_CHECK(std::isfinite(net_steps[i]), DWS_ERR_INVALID, "sampler: net_steps[%d] = %g is not finite", i,
                   (double)net_steps[i]);
-    const int rows = kind == DWS_SAMPLER_DDIM ? 5 : 3;
+    const int rows = kind == DWS_SAMPLER_DDPM ? 3 : 5;
     for (int i = 0; i < rows * S; ++i)
         DWS_CHECK(std::isfinite(coef[i]), DWS_ERR_INVALID, "sampler: coefficient row %d, step %d = %g is not finite",
                   i / S, i % S, (double)coef[i]);
     if (kind == DWS_SAMPLER_DDIM)
         for (int i = 0; i < S; ++i)
             DWS_CHECK(coef[S + i] > 0.f, DWS_ERR_INVALID, "sampler: DDIM k2[%d] = %g (needs k2 > 0)", i, (double)coef[S + i]);
+    if (kind == DWS_SAMPLER_DPMPP2M) {
+        for (int i = 0; i < S; ++i) {
+            DWS_CHECK(coef[S + i] > 0.f, DWS_ERR_INVALID, "sampler: DPM-Solver++ m2[%d] = %g (needs m2 > 0)", i,
+                      (double)coef[S + i]);
+            DWS_CHECK(coef[4 * (size_t)S + i] >= 0.f, DWS_ERR_INVALID, "sampler: DPM-Solver++ m5[%d] = %g (needs m5 >= 0)", i,
+                      (double)coef[4 * (size_t)S + i]);
+        }
+        DWS_CHECK(!noise || pg, DWS_ERR_INVALID,
+                  "sampler: DPM-Solver++ is deterministic; noise is read only by the jump visits of a program run");
+    }
     const int start = e ? e->start_step : S - 1;
     const bool masked = e && e->known && e->mask;
     const bool qsample = e && e->start_mode == DWS_START_QSAMPLE;
@@ -733,8 +876,8 @@ int sampler_run_schedule(dws_model* m, float* x, int kind, int S, const float* n
     if (m->dirty) DWS_TRY(m->commit(s));
     const size_t n = (size_t)m->B * m->d.out_channels * m->L;
 
-    // update tables, keyed on their contents; DDIM's are used as given
-    std::vector<float> h = kind == DWS_SAMPLER_DDIM ? std::vector<float>(coef, coef + 5 * (size_t)S)
+    // update tables, keyed on their contents; DDIM's and DPM-Solver++'s are used as given
+    std::vector<float> h = kind != DWS_SAMPLER_DDPM ? std::vector<float>(coef, coef + 5 * (size_t)S)
                                                     : ddpm_table(coef, coef + S, coef + 2 * (size_t)S, S);
     if (!m->sch_tables.p || h.size() != m->sch_host_tables.size() ||
         std::memcmp(h.data(), m->sch_host_tables.data(), h.size() * 4) != 0) {
@@ -757,8 +900,9 @@ int sampler_run_schedule(dws_model* m, float* x, int kind, int S, const float* n
     }
     DWS_TRY(m->smp_eps.ensure(n * 4));
     m->smp_eps_B = m->B; m->smp_eps_L = m->L;
+    if (kind == DWS_SAMPLER_DPMPP2M) DWS_TRY(m->sch_hist.ensure(n * 4));   // the previous step's x0 (first use of this kind)
     DWS_TRY(m->build_step_table(S, net_steps, s));   // the network's step-only part at net_steps (kept while they stay)
-    DWS_TRY(m->sch_state.ensure(32));
+    DWS_TRY(m->sch_state.ensure(32));                // step, finished blocks, seed (2 words), visit, history-valid word
     int* st = static_cast<int*>(m->sch_state.p);
     const int V = pg ? pg->V : 0;
     const int R = pg ? V : S;     // streams R (a drawn x_T) and 2R + 1 (the q-sample) lie behind the per-visit ones
@@ -846,7 +990,8 @@ int sampler_run_schedule(dws_model* m, float* x, int kind, int S, const float* n
     DWS_TRY(begin(xs, cs));
     const dws_model::SchKey key{m->B, m->L, S, kind, vec ? 1 : 0, m->sch_tables.p, noise, m->smp_eps.p, xs, st,
                                 m->step_table_gen, ed ? ed->table : nullptr, ed ? ed->known : nullptr,
-                                ed ? ed->mask : nullptr, known_noise, V, pr ? m->sch_prog.p : nullptr};
+                                ed ? ed->mask : nullptr, known_noise, V, pr ? m->sch_prog.p : nullptr,
+                                kind == DWS_SAMPLER_DPMPP2M ? m->sch_hist.p : nullptr};
     // the edited step and the resampling step have graphs of their own: the three kinds of call may alternate without a
     // new capture
     hipGraphExec_t& exec = pg ? m->prog_graph : masked ? m->edit_graph : m->sch_graph;

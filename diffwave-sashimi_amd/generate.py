@@ -215,7 +215,7 @@ def _load_clip(dataset_cfg, stem, audio_length, conditional):
 def generate(rank, diffusion_cfg, model_cfg, dataset_cfg, ckpt_iter="max", n_samples=1, name=None, batch_size=None,
              ckpt_smooth=None, mel_path=None, mel_name=None, dataloader=None, exp_root="exp", seed=None,
              written=None, precision=None, sampler="ddpm", steps=None, eta=0.0, known_name=None, keep=None,
-             start_name=None, start_step=None, start_noise=True, resample_jump=None, resample_n=None):
+             start_name=None, start_step=None, start_noise=True, resample_jump=None, resample_n=None, spacing=None):
     """``generate.py:58-200``.  ``ckpt_iter`` may additionally be ``"init"``: seeded random weights
     (no checkpoint), for smoke runs without trained weights.  ``precision`` (not in the reference; CLI:
     ``+engine.precision=bf16x6|f16x3``): the engine's opt-in matrix arithmetic, see ``include/dws.h``.
@@ -223,7 +223,10 @@ def generate(rank, diffusion_cfg, model_cfg, dataset_cfg, ckpt_iter="max", n_sam
     ``sampler`` (not in the reference; CLI ``generate.sampler=...``): ``ddpm`` (default) is the reference's loop,
     including its use of ``diffusion.beta``; ``aligned`` runs the short ``diffusion.beta`` schedule with the network at
     the aligned fractional training steps (``sampling.align_steps``); ``ddim`` runs DDIM over ``steps`` of the T
-    training steps with ``eta`` (default 0).
+    training steps with ``eta`` (default 0); ``dpmpp2m`` runs DPM-Solver++(2M), the second-order multistep solver, over
+    ``steps`` of the T training steps spaced uniformly in log-SNR (``spacing`` = ``logsnr``, the default; the count can
+    come out below ``steps`` where targets collide) or as DDIM spaces them (``uniform``).  It is deterministic: a
+    non-zero ``eta`` is refused.
 
     Editing (not in the reference; with any ``sampler``): ``known_name`` (a wav stem under ``dataset.data_path``) with
     ``keep`` (``[start, end)`` sample spans of it that are kept) inpaints the rest -- every clip of the batch gets the
@@ -233,8 +236,8 @@ def generate(rank, diffusion_cfg, model_cfg, dataset_cfg, ckpt_iter="max", n_sam
     resampling: at every ``resample_jump``-th position the chain goes back up that many steps and down again,
     ``resample_n`` times in all (``sampling.repaint_program``)."""
     from .models import construct_model
-    from .sampling import (calc_diffusion_hyperparams, ddim_steps, program_evaluations, repaint_program, sampling,
-                           sampling_aligned, sampling_ddim, spans_to_mask)
+    from .sampling import (calc_diffusion_hyperparams, ddim_steps, logsnr_steps, program_evaluations, repaint_program,
+                           sampling, sampling_aligned, sampling_ddim, sampling_dpmpp, spans_to_mask)
     from scipy.io.wavfile import write as wavwrite
 
     if known_name is not None and not keep:
@@ -252,21 +255,35 @@ def generate(rank, diffusion_cfg, model_cfg, dataset_cfg, ckpt_iter="max", n_sam
         raise ValueError("generate.resample_jump / generate.resample_n need generate.known_name (resampling harmonises "
                          "an inpainting run)")
     sampler = sampler or "ddpm"
-    if sampler not in ("ddpm", "aligned", "ddim"):
-        raise ValueError(f"generate.sampler={sampler!r}: expected ddpm, aligned or ddim")
+    if sampler not in ("ddpm", "aligned", "ddim", "dpmpp2m"):
+        raise ValueError(f"generate.sampler={sampler!r}: expected ddpm, aligned, ddim or dpmpp2m")
     if sampler == "aligned" and diffusion_cfg.get("beta") is None:
         raise ValueError("generate.sampler=aligned needs diffusion.beta (the short inference schedule, e.g. "
                          "diffusion.beta=[0.0001,0.001,0.01,0.05,0.2,0.5])")
     if sampler == "ddim" and steps is None:
         raise ValueError("generate.sampler=ddim needs generate.steps (the number of DDIM steps, or a list of them)")
+    if sampler == "dpmpp2m":
+        if steps is None:
+            raise ValueError("generate.sampler=dpmpp2m needs generate.steps (the number of steps, or a list of them)")
+        if float(eta or 0.0) != 0.0:
+            raise ValueError(f"generate.eta={eta!r} with generate.sampler=dpmpp2m: the solver is deterministic (eta is "
+                             "DDIM's)")
+        spacing = spacing or "logsnr"
+        if spacing not in ("logsnr", "uniform"):
+            raise ValueError(f"generate.spacing={spacing!r}: expected logsnr or uniform")
+    elif spacing is not None:
+        raise ValueError("generate.spacing belongs to generate.sampler=dpmpp2m")
     if rank is not None and torch.cuda.is_available():
         torch.cuda.set_device(rank % torch.cuda.device_count())
     rank = rank or 0
     local_path, output_directory = local_directory(name, model_cfg, diffusion_cfg, dataset_cfg, "waveforms", exp_root)
     dh = calc_diffusion_hyperparams(**diffusion_cfg, fast=True)
-    if sampler == "ddim":        # DDIM runs on the training schedule (the T-step linspace), never on diffusion.beta
+    if sampler in ("ddim", "dpmpp2m"):   # these run on the training schedule (the T-step linspace), never on diffusion.beta
         dh_train = calc_diffusion_hyperparams(diffusion_cfg["T"], diffusion_cfg["beta_0"], diffusion_cfg["beta_T"])
-        n_evals = len(ddim_steps(dh_train["T"], steps))
+        if sampler == "dpmpp2m" and spacing == "logsnr":
+            n_evals = len(logsnr_steps(dh_train["Alpha_bar"], steps))
+        else:
+            n_evals = len(ddim_steps(dh_train["T"], steps))
     else:
         n_evals = dh["T"]
     if resample_jump is not None:       # checked here, before a model is built
@@ -337,6 +354,8 @@ def generate(rank, diffusion_cfg, model_cfg, dataset_cfg, ckpt_iter="max", n_sam
             out.append(sampling_aligned(net, size, diffusion_cfg, condition=mel, seed=s, **edit))
         elif sampler == "ddim":
             out.append(sampling_ddim(net, size, dh_train, steps, eta=float(eta or 0.0), condition=mel, seed=s, **edit))
+        elif sampler == "dpmpp2m":
+            out.append(sampling_dpmpp(net, size, dh_train, steps, condition=mel, spacing=spacing, seed=s, **edit))
         else:
             out.append(sampling(net, size, dh, condition=mel, seed=s, **edit))
     generated_audio = torch.cat(out, dim=0)
@@ -344,8 +363,8 @@ def generate(rank, diffusion_cfg, model_cfg, dataset_cfg, ckpt_iter="max", n_sam
     print(f"generated {n_samples} samples shape {tuple(generated_audio.shape)} at iteration {ckpt_iter} in "
           f"{time.perf_counter() - t0:.1f} seconds")
     if sampler != "ddpm" or resample_jump is not None:
-        print(f"sampler {sampler}{f' (eta={float(eta or 0.0)})' if sampler == 'ddim' else ''}: {n_evals} network "
-              f"evaluations per batch")
+        note = f" (eta={float(eta or 0.0)})" if sampler == "ddim" else f" ({spacing} spacing)" if sampler == "dpmpp2m" else ""
+        print(f"sampler {sampler}{note}: {n_evals} network evaluations per batch")
     for i in range(n_samples):
         outfile = "{}k_{}.wav".format(ckpt_iter // 1000, n_samples * rank + i)   # `generate.py:189`
         wavwrite(os.path.join(output_directory, outfile), dataset_cfg["sampling_rate"],

@@ -320,7 +320,7 @@ def _run_schedule(net, size, kind, net_steps, coef, condition, x_T, noise, seed,
     steps = np.ascontiguousarray(np.asarray(net_steps, dtype=np.float32).reshape(-1))
     S = steps.shape[0]
     coef = np.ascontiguousarray(np.asarray(coef, dtype=np.float32))
-    if S < 1 or coef.shape != ((5 if kind == _lib.DWS_SAMPLER_DDIM else 3), S):
+    if S < 1 or coef.shape != ((3 if kind == _lib.DWS_SAMPLER_DDPM else 5), S):
         raise ValueError(f"sampler: {S} net steps with coefficient tables of shape {coef.shape}")
     prog = None
     if resample is not None:
@@ -448,6 +448,81 @@ def sampling_ddim(net, size, dh_train, steps, eta=0.0, condition=None, *, x_T=No
     return _run_schedule(net, size, _lib.DWS_SAMPLER_DDIM, np.asarray(tau, dtype=np.float32), coef, condition, x_T,
                          noise, seed, use_graph, edit=edit, levels=_host_table(dh_train["Alpha_bar"])[0][tau],
                          resample=resample)
+
+
+def logsnr_steps(alpha_bar, S):
+    """Sub-sequence of the T training steps spaced uniformly in log-SNR, the spacing a multistep solver needs (uniform
+    in t, ``ddim_steps``, leaves a huge log-SNR gap to the last steps): with ``lam_t = 0.5 log(abar_t / (1 - abar_t))`` in
+    float64 from the float32 ``Alpha_bar``, the sorted, de-duplicated ``argmin_t |lam_t - target|`` over the targets
+    ``linspace(lam_0, lam_{T-1}, S)``.  Contains 0 and T-1 for S >= 2 and may be shorter than S where targets collide:
+    its length is the number of network evaluations.  ``[T-1]`` for S = 1.  ``S`` may also be an explicit increasing
+    list of steps in 0..T-1 (checked as ``ddim_steps`` checks it)."""
+    if isinstance(alpha_bar, torch.Tensor):
+        alpha_bar = alpha_bar.detach().cpu().numpy()
+    ab = np.asarray(alpha_bar, dtype=np.float32).astype(np.float64).reshape(-1)
+    T = ab.shape[0]
+    if isinstance(S, (list, tuple, np.ndarray)):
+        return ddim_steps(T, S)
+    if not _is_int(S) or S < 1 or S > T:
+        raise ValueError(f"logsnr_steps: S = {S!r} steps out of T = {T} (needs an integer in 1..{T})")
+    S = int(S)
+    if S == 1:
+        return [T - 1]
+    lam = 0.5 * np.log(ab / (1.0 - ab))
+    tau = sorted({int(np.argmin(np.abs(lam - target))) for target in np.linspace(lam[0], lam[-1], S)})
+    assert tau[0] == 0 and tau[-1] == T - 1
+    return tau
+
+
+def dpmpp_coefficients(alpha_bar, tau):
+    """Update tables of DPM-Solver++(2M) (Lu et al., 2022: the second-order multistep solver in the data prediction)
+    over the steps ``tau``: float32 [5][S] = m1..m5 with ``a_s = abar[tau_s]``, ``p_s = abar[tau_{s-1}]`` (``p_0 = 1``),
+    ``lam(v) = log(sqrt(v) / sqrt(1 - v))`` and ``h_s = lam(p_s) - lam(a_s)`` (``h_0 = +inf``): ``m1 = sqrt(1-a)``,
+    ``m2 = sqrt(a)``, ``m3 = sqrt((1-p)/(1-a))`` (``m3[0] = 0``), ``m4 = sqrt(p) (-expm1(-h))`` (``m4[0] = 1``),
+    ``m5[s] = h_s / (2 h_{s+1})`` for 1 <= s <= S-2 and 0 otherwise -- the first step of a run (s = S-1) has no history,
+    the last (s = 0) goes to sigma = 0, where the extrapolation is undefined, so both are first order.  float64 from the
+    float32 ``Alpha_bar``, rounded once (the convention of ``ddim_coefficients``).  The engine's step is then
+    ``x0 = (x - m1 eps) / m2; D = x0 + m5 (x0 - x0_prev) where there is history and m5 != 0, else x0; x = m3 x + m4 D``;
+    with ``m5 = 0`` it is DDIM's at eta = 0."""
+    if isinstance(alpha_bar, torch.Tensor):
+        alpha_bar = alpha_bar.detach().cpu().numpy()
+    ab = np.asarray(alpha_bar, dtype=np.float32).astype(np.float64)
+    tau = np.asarray(tau, dtype=np.int64).reshape(-1)
+    S = tau.shape[0]
+    a = ab[tau]
+    p = np.concatenate([[1.0], ab[tau[:-1]]])
+    lam = lambda v: np.log(np.sqrt(v) / np.sqrt(1.0 - v))
+    h = np.concatenate([[np.inf], lam(p[1:]) - lam(a[1:])])
+    m5 = np.zeros(S)
+    m5[1:S - 1] = h[1:S - 1] / (2.0 * h[2:S])
+    m = np.stack([np.sqrt(1.0 - a), np.sqrt(a), np.sqrt((1.0 - p) / (1.0 - a)), np.sqrt(p) * -np.expm1(-h), m5])
+    return m.astype(np.float32)
+
+
+def sampling_dpmpp(net, size, dh_train, steps, condition=None, *, spacing="logsnr", x_T=None, seed=None,
+                   use_graph=True, known=None, mask=None, known_noise=None, x_start=None, start_step=None,
+                   start_noise=None, resample=None, noise=None):
+    """DPM-Solver++(2M) over ``logsnr_steps(Alpha_bar, steps)`` of the training schedule ``dh_train``
+    (``spacing="uniform"``: over ``ddim_steps(T, steps)``; ``steps``: S or an explicit list).  Second order at the cost
+    of DDIM: one network evaluation per step, the previous step's data prediction kept on the device.  Deterministic:
+    ``seed`` drives only a drawn ``x_T``, the known-region noise, the start noise and the jump noise; ``noise`` is
+    accepted only together with ``resample`` ([V, B, C, L], of which the rows of jump visits are read).  The editing
+    arguments and ``resample`` are those of ``sampling`` (levels: ``Alpha_bar[tau]``); the step after a jump and the
+    first step of a partial start are first order.  Not the reference's loop."""
+    if spacing not in ("logsnr", "uniform"):
+        raise ValueError(f"sampling_dpmpp: spacing = {spacing!r} (expected 'logsnr' or 'uniform')")
+    if noise is not None and resample is None:
+        raise ValueError("sampling_dpmpp: the solver is deterministic; noise= is read only by the jump visits of "
+                         "resample=")
+    ab = _host_table(dh_train["Alpha_bar"])[0]
+    tau = logsnr_steps(ab, steps) if spacing == "logsnr" else ddim_steps(dh_train["T"], steps)
+    coef = dpmpp_coefficients(ab, tau)
+    edit = dict(known=known, mask=mask, known_noise=known_noise, x_start=x_start, start_step=start_step,
+                start_noise=start_noise)
+    if resample is None and all(v is None for v in edit.values()):
+        edit = None
+    return _run_schedule(net, size, _lib.DWS_SAMPLER_DPMPP2M, np.asarray(tau, dtype=np.float32), coef, condition, x_T,
+                         noise, seed, use_graph, edit=edit, levels=ab[tau], resample=resample)
 
 
 def sampling_aligned(net, size, diffusion_cfg, condition=None, **kw):

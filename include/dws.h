@@ -263,6 +263,25 @@ int dws_sampler_steps(dws_model* m, float* x, const float* alpha, const float* a
  *              DWS_SAMPLER_DDIM: coef = k1[S] .. k5[S] (sampling.ddim_coefficients, taken as
  *              given); per element, each operation rounded once, in this order:
  *                u = (x - k1 eps) / k2;  x = k3 u + k4 eps;  if s > 0 and k5 > 0: x = x + k5 z
+ *              DWS_SAMPLER_DPMPP2M: DPM-Solver++(2M) (Lu et al., 2022), the second-order multistep
+ *              solver in the data prediction; coef = m1[S] .. m5[S] (sampling.dpmpp_coefficients,
+ *              taken as given).  With a_s the level of step s, p_s = a_{s-1} (p_0 = 1),
+ *              lam(v) = log(sqrt(v) / sqrt(1 - v)) and h_s = lam(p_s) - lam(a_s) (h_0 = +inf):
+ *                m1 = sqrt(1 - a), m2 = sqrt(a), m3 = sqrt((1 - p) / (1 - a)) (m3[0] = 0),
+ *                m4 = sqrt(p) (1 - exp(-h)) (m4[0] = 1), m5[s] = h_s / (2 h_{s+1}) for 1 <= s <= S-2,
+ *                else 0 (the first step has no history; the last goes to sigma = 0 and is first order).
+ *              Per element, each operation rounded once, in this order:
+ *                p = m1 eps;  d = x - p;  x0 = d / m2
+ *                D = x0;  if second:  g = x0 - hist;  e = m5 g;  D = x0 + e
+ *                a = m3 x;  b = m4 D;  x = a + b;  hist = x0
+ *              hist is a model-owned [B, C, L] buffer that holds the previous step's x0 (the network's
+ *              prediction, before any known-region replacement).  second = (the history-valid word
+ *              of the device state != 0) and m5[s] != 0.  The word is 0 at the start of every run, the
+ *              last block of every step of this kind sets it to 1, a jump visit of a program clears
+ *              it (the jump re-noises the state, so the step behind it is first order).  With m5 = 0
+ *              the step is DDIM's at eta = 0.  The solver is deterministic: no z is drawn or read in a
+ *              reverse step, and `noise` must be NULL except in dws_sampler_run_program, where only
+ *              the rows of jump visits are read.
  *   net_steps  HOST float[S];  coef  HOST float[3 or 5][S]
  *   noise      optional DEVICE [S, B, C, L]: noise[s] is z of step s.  NULL -> Philox keyed
  *              by (seed, s, element); a seed-driven x_T uses stream S.  With S = T, the
@@ -272,10 +291,13 @@ int dws_sampler_steps(dws_model* m, float* x, const float* alpha, const float* a
  * from device memory: x_T is copied (or drawn) in before the replays and x_0 copied out
  * after them, so a new seed or a new x needs no new capture.  One graph per (B, L, S, kind,
  * tables, step table, noise pointer); tap "sampler_graphs" counts the graphs a model has
- * instantiated (both entry points).  Bad input (S < 1, non-finite steps or coefficients,
- * DDIM k2 <= 0) -> DWS_ERR_INVALID. */
+ * instantiated (both entry points).  The multistep kind's history buffer is part of that key; whether a
+ * step is second order is decided on the device, so its tables do not depend on the start step.  Bad input
+ * (S < 1, non-finite steps or coefficients, DDIM k2 <= 0, DPM-Solver++ m2 <= 0 or m5 < 0 or a non-NULL
+ * noise outside a program run) -> DWS_ERR_INVALID, before anything is enqueued. */
 #define DWS_SAMPLER_DDPM 0
 #define DWS_SAMPLER_DDIM 1
+#define DWS_SAMPLER_DPMPP2M 2
 int dws_sampler_run_schedule(dws_model* m, float* x, int32_t kind, int32_t S, const float* net_steps,
                              const float* coef, const float* noise, uint64_t seed, int32_t init_from_seed,
                              int32_t use_graph, void* stream);
