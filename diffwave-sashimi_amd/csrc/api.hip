@@ -57,7 +57,7 @@ int dws_model::forward_train(const float*, const float*, float*, hipStream_t) {
     return dws::set_error(DWS_ERR_UNSUPPORTED, "the training forward/backward of this backbone is not built yet");
 }
 
-int dws_model::backward(const float*, hipStream_t) {
+int dws_model::backward(const float*, float*, bool, hipStream_t) {
     return dws::set_error(DWS_ERR_UNSUPPORTED, "the training forward/backward of this backbone is not built yet");
 }
 
@@ -295,12 +295,21 @@ int dws_model_forward_train(dws_model* m, const float* audio, const float* steps
     return m->forward_train(audio, steps, out, (hipStream_t)stream);
 }
 
-int dws_model_backward(dws_model* m, const float* dout, void* stream) {
+int dws_model_backward_input(dws_model* m, const float* dout, float* daudio, int32_t param_grads, void* stream) {
     DWS_CHECK(m && dout, DWS_ERR_INVALID, "dws_model_backward: null argument");
+    DWS_CHECK(param_grads == 0 || param_grads == 1, DWS_ERR_INVALID, "dws_model_backward_input: param_grads = %d (0 or 1)", param_grads);
+    if (!param_grads) {     // data-only: no gradient buffer, sink or group event is involved
+        DWS_CHECK(daudio, DWS_ERR_INVALID, "dws_model_backward_input: a data-only backward (param_grads = 0) needs daudio");
+        return m->backward(dout, daudio, false, (hipStream_t)stream);
+    }
     m->grad_begin();
-    const int rc = m->backward(dout, (hipStream_t)stream);
+    const int rc = m->backward(dout, daudio, true, (hipStream_t)stream);
     if (rc != DWS_OK) { m->in_backward = false; return rc; }
     return m->grad_end((hipStream_t)stream);
+}
+
+int dws_model_backward(dws_model* m, const float* dout, void* stream) {
+    return dws_model_backward_input(m, dout, nullptr, 1, stream);
 }
 
 int dws_model_set_grad_sinks(dws_model* m, int32_t count, const char* const* names, float* const* dsts, const int64_t* numels,

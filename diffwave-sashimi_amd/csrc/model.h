@@ -272,7 +272,9 @@ struct dws_model {
     virtual int read_tap(const char* tap, float* dst, int64_t capacity, hipStream_t s) = 0;
     // training path: forward that keeps what backward needs; backward fills ParamSpec::grad of every parameter
     virtual int forward_train(const float* audio, const float* steps, float* out, hipStream_t s);
-    virtual int backward(const float* dout, hipStream_t s);
+    // daudio (optional): the gradient w.r.t. audio [B, in_channels, L]; param_grads = false (needs daudio): the data path
+    // only -- no ParamSpec::grad is touched, nothing is handed to the sinks
+    virtual int backward(const float* dout, float* daudio, bool param_grads, hipStream_t s);
     float* G(const std::string& name);  // gradient buffer of a parameter (allocated, zeroed on first use)
 };
 

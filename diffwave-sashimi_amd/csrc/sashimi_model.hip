@@ -1350,10 +1350,18 @@ struct SashimiModel : dws_model, S4Workspace {
     // adjoint of the block's chain.  U_f is recomputed here (one R2C of the padded t_u) instead of being kept from the forward:
     // keeping it would cost B H (L+1) 8 bytes per block for the whole step (90 MB per top-stage block of ljspeech_harder, twelve of them)
     // to save one transform of the same size, and it would need an out-of-place spectrum multiply in the forward.
-    int rocfft_conv_backward(SLayer* l, Stage* st, const float* da, float* du, hipStream_t s) {
+    // pg = false (data-only backward): du alone -- R2C(da), the product with conj(K_f), C2R and the epilogue without its row sum.
+    int rocfft_conv_backward(SLayer* l, Stage* st, const float* da, float* du, bool pg, hipStream_t s) {
         ProfileScope ps("long_stage_bwd", s);
         const int H = l->H, Ls = l->L, Lf = Ls + 1, nB = (int)B, rows = nB * H;
         const int Lk = l->Lk, Lt = std::min(Ls, Lk), Lh = Lk / 2 + 1;
+        if (!pg) {
+            DWS_TRY(launch_pad_rows(da, st->U.f(), rows, Ls, s));
+            DWS_TRY(fft.exec(0, 2 * Ls, rows, st->U.p, st->Uf.p, s));       // dA
+            DWS_TRY(launch_conv_adjoint_spec_data(st->Uf.f(), l->Kf.f(), nB, H, Lf, s));
+            DWS_TRY(fft.exec(1, 2 * Ls, rows, st->Uf.p, st->Y.p, s));
+            return launch_conv_adjoint_epi(st->Y.f(), da, P(l->prefix + ".layer.D"), du, nullptr, 0, nB, H, Ls, s);
+        }
         DWS_TRY(dKf.ensure((size_t)H * Lf * 8));
         DWS_TRY(dKt.ensure((size_t)H * 2 * Ls * 4));
         DWS_TRY(dkt.ensure((size_t)2 * H * Lk * 4));
@@ -1414,8 +1422,13 @@ struct SashimiModel : dws_model, S4Workspace {
     }
 
     // Adjoint of forward_train, plan steps in reverse (sashimi.py:143-184,277-313).
-    int backward(const float* dout, hipStream_t s) override {
+    // daudio (optional): the gradient w.r.t. the audio input.  pg = false (data-only, needs daudio): the data path alone, the
+    // same kernels in the same order (daudio has the same bits in both modes) -- no weight / bias gradient, no weight-norm
+    // adjoint, no S4 kernel adjoint (fftcorr / spectrum adjoint / taps adjoint), no LayerNorm parameter sums, no d fc_t(e),
+    // no embedding or conditioner adjoint, no G() access and no flush point.
+    int backward(const float* dout, float* daudio, bool pg, hipStream_t s) override {
         DWS_CHECK(trained_fwd, DWS_ERR_STATE, "backward without a preceding forward_train");
+        DWS_CHECK(pg || daudio, DWS_ERR_INVALID, "backward: a data-only pass needs a destination for the input gradient");
         const int nB = (int)B, nL = (int)L;
         const int nnodes = (int)plan.size() + 1;
         ln_pending.clear();
@@ -1428,23 +1441,25 @@ struct SashimiModel : dws_model, S4Workspace {
             if (l->kind == L_BLOCK) wmax = std::max(wmax, (size_t)2 * l->H * l->H * std::max(1, FF));
             else wmax = std::max(wmax, (size_t)l->H * l->p * l->Hout * std::max(l->p, 1));
         }
-        DWS_TRY(dWfold.ensure(wmax * 4));
-        DWS_TRY(dpt.ensure((size_t)B * pt_total * 4));
-        DWS_TRY(dh2.ensure((size_t)B * Eout * 4)); DWS_TRY(dh1.ensure((size_t)B * Emid * 4));
-        DWS_TRY(dWt_all.ensure((size_t)pt_total * Eout * 4)); DWS_TRY(dbt_all.ensure((size_t)pt_total * 4));
+        if (pg) {
+            DWS_TRY(dWfold.ensure(wmax * 4));
+            DWS_TRY(dpt.ensure((size_t)B * pt_total * 4));
+            DWS_TRY(dh2.ensure((size_t)B * Eout * 4)); DWS_TRY(dh1.ensure((size_t)B * Emid * 4));
+            DWS_TRY(dWt_all.ensure((size_t)pt_total * Eout * 4)); DWS_TRY(dbt_all.ensure((size_t)pt_total * 4));
+        }
 
         // ---- final stage: out = Wz y + bz, y = relu(Wf LN(x) + bf)
         // (1 x D and D x 1 weight gradients also go through the MFMA kernel: its tile is mostly padding there, but the
         // generic FMA kernel took 2.3 ms per call on [B, ., L] = 512000 positions)
-        DWS_TRY(wgrad(dout, ty.f(), Cout, D, nL, 0, G("final_conv.2.conv.weight"), G("final_conv.2.conv.bias"), s));
+        if (pg) DWS_TRY(wgrad(dout, ty.f(), Cout, D, nL, 0, G("final_conv.2.conv.weight"), G("final_conv.2.conv.bias"), s));
         DWS_TRY(launch_final_dy(dout, P("final_conv.2.conv.weight"), ty.f(), dyb.f(), nB, D, Cout, nL, s));
-        { const std::string wn_ = "final_conv.0.conv"; DWS_TRY(wgrad(dyb.f(), nfin.f(), D, D, nL, 0, dWfold.f(), G("final_conv.0.conv.bias"), s, &wn_)); }
+        if (pg) { const std::string wn_ = "final_conv.0.conv"; DWS_TRY(wgrad(dyb.f(), nfin.f(), D, D, nL, 0, dWfold.f(), G("final_conv.0.conv.bias"), s, &wn_)); }
         DWS_TRY(gemm(tAfT.f(), D, D, dyb.f(), dnf.f(), nL, 2, nullptr, nullptr, nullptr, nullptr, nullptr, s));
         {
             const int last = nnodes - 1;
-            DWS_TRY(launch_ln_bwd(node_act(last), dnf.f(), P("norm.m"), P("norm.s"), nullptr, gp[last], 0, ln_slot(),
+            DWS_TRY(launch_ln_bwd(node_act(last), dnf.f(), P("norm.m"), P("norm.s"), nullptr, gp[last], 0, pg ? ln_slot() : nullptr,
                                   nB, D, nL, s));
-            DWS_TRY(ln_scalars("norm", nB * ceil_div(nL, 64), s));
+            if (pg) DWS_TRY(ln_scalars("norm", nB * ceil_div(nL, 64), s));
             written[last] = 1;
         }
 
@@ -1461,17 +1476,17 @@ struct SashimiModel : dws_model, S4Workspace {
                 const int H = l->H, Ls = l->L, nblk = nB * ceil_div(Ls, 64);
                 // ff: out = x1 + W2 gelu(f1) + b2, f1 = W1 n2 + b1
                 DWS_TRY(gemm(l->tA2T.f(), FF * H, H, dy, st->d2.f(), Ls, 5, nullptr, nullptr, nullptr, l->t_f1.f(), nullptr, s));
-                { const std::string wn_ = p + ".ff.ff.2.conv"; DWS_TRY(wgrad(dy, l->t_ge.f(), H, FF * H, Ls, 0, dWfold.f(), G(p + ".ff.ff.2.conv.bias"), s, &wn_)); }
+                if (pg) { const std::string wn_ = p + ".ff.ff.2.conv"; DWS_TRY(wgrad(dy, l->t_ge.f(), H, FF * H, Ls, 0, dWfold.f(), G(p + ".ff.ff.2.conv.bias"), s, &wn_)); }
                 DWS_TRY(gemm(l->tA1T.f(), H, FF * H, st->d2.f(), st->dh.f(), Ls, 2, nullptr, nullptr, nullptr, nullptr, nullptr, s));
-                { const std::string wn_ = p + ".ff.ff.0.conv"; DWS_TRY(wgrad(st->d2.f(), l->t_n2.f(), FF * H, H, Ls, 0, dWfold.f(), G(p + ".ff.ff.0.conv.bias"), s, &wn_)); }
+                if (pg) { const std::string wn_ = p + ".ff.ff.0.conv"; DWS_TRY(wgrad(st->d2.f(), l->t_n2.f(), FF * H, H, Ls, 0, dWfold.f(), G(p + ".ff.ff.0.conv.bias"), s, &wn_)); }
                 // norm2: dx1 = dy + LN'(dn2)
                 // (the GLU adjoint rides on this kernel when it can: d o is written from the d x1 values in registers)
                 const bool glu_fused = ln_bwd_fuses_glu(H);
                 DWS_TRY(launch_ln_bwd(l->t_x1.f(), st->dh.f(), P(p + ".norm2.m"), P(p + ".norm2.s"), dy, st->dx1.f(), 0,
-                                      ln_slot(), nB, H, Ls, s, glu_fused ? l->t_o.f() : nullptr,
+                                      pg ? ln_slot() : nullptr, nB, H, Ls, s, glu_fused ? l->t_o.f() : nullptr,
                                       glu_fused ? st->d2.f() : nullptr));
-                DWS_TRY(ln_scalars(p + ".norm2", nblk, s));
-                if (melBm) {  // x1 = ... + melc: the block's conditioner sees d x1 (`sashimi.py:160-175`)
+                if (pg) DWS_TRY(ln_scalars(p + ".norm2", nblk, s));
+                if (melBm && pg) {  // x1 = ... + melc: the block's conditioner sees d x1 (`sashimi.py:160-175`)
                     const int s0 = d.mel_upsample[0], s1 = d.mel_upsample[1];
                     DWS_TRY(gW0f.ensure((size_t)3 * 2 * s0 * 4)); DWS_TRY(gW1f.ensure((size_t)3 * 2 * s1 * 4));
                     DWS_TRY(gWcf.ensure((size_t)H * MB * 4));
@@ -1487,11 +1502,12 @@ struct SashimiModel : dws_model, S4Workspace {
                 // x1 = x + glu(o), o = Wo gelu(a) + bo
                 if (!glu_fused) DWS_TRY(launch_glu_bwd(st->dx1.f(), l->t_o.f(), st->d2.f(), nB, H, Ls, s));
                 DWS_TRY(gemm(l->tAoT.f(), H, 2 * H, st->d2.f(), st->dh.f(), Ls, 5, nullptr, nullptr, nullptr, l->t_a.f(), nullptr, s));
-                DWS_TRY(wgrad(st->d2.f(), l->t_g.f(), 2 * H, H, Ls, 0, G(p + ".layer.output_linear.0.weight"),
-                              G(p + ".layer.output_linear.0.bias"), s));
+                if (pg)
+                    DWS_TRY(wgrad(st->d2.f(), l->t_g.f(), 2 * H, H, Ls, 0, G(p + ".layer.output_linear.0.weight"),
+                                  G(p + ".layer.output_linear.0.bias"), s));
                 // a = conv(u, K) + D u: du = conv^T(da) + D da; kernel parameters from corr(u, da)
                 if (l->log2m == 0) {    // rocFFT stage (rocfft_conv_backward also writes d fc_t(e) and every S4 kernel gradient)
-                    DWS_TRY(rocfft_conv_backward(l, st, st->dh.f(), st->du.f(), s));
+                    DWS_TRY(rocfft_conv_backward(l, st, st->dh.f(), st->du.f(), pg, s));
                 } else {
                     FftTables* t = tables[l->log2m];
                     FftConvArgs fa{};
@@ -1500,27 +1516,27 @@ struct SashimiModel : dws_model, S4Workspace {
                     fa.kfa = (const c2*)l->kfa_v; fa.kfb = (const c2*)l->kfb_v; fa.kfs = (const c2*)l->kfs_v;
                     fa.B = nB; fa.H = H; fa.L = Ls;
                     // d fc_t(e)[b, h] = sum_l du[b, h, l] leaves with the row (a workgroup owns it) where the plan allows
-                    const bool rs_fused = fftconv_rowsum_supported(l->log2m) && getenv("DWS_NO_ROWSUM_FUSION") == nullptr;
+                    const bool rs_fused = pg && fftconv_rowsum_supported(l->log2m) && getenv("DWS_NO_ROWSUM_FUSION") == nullptr;
                     if (rs_fused) { fa.rowsum = dpt.f() + l->pt_off; fa.rowsum_bstride = (int)pt_total; }
                     DWS_TRY(launch_fftconv(l->log2m, fa, s));
-                    DWS_TRY(kernel_backward(l, st->dh.f(), s));
-                    if (!rs_fused) DWS_TRY(launch_rowsum_bc(st->du.f(), dpt.f() + l->pt_off, pt_total, nB, H, Ls, s));
+                    if (pg) DWS_TRY(kernel_backward(l, st->dh.f(), s));
+                    if (pg && !rs_fused) DWS_TRY(launch_rowsum_bc(st->du.f(), dpt.f() + l->pt_off, pt_total, nB, H, Ls, s));
                 }
                 // u = LN1(x) + fc_t(e): dx = dx1 + LN'(du)
                 DWS_TRY(launch_ln_bwd(x, st->du.f(), P(p + ".norm1.m"), P(p + ".norm1.s"), st->dx1.f(), din, written[e.in_node],
-                                      ln_slot(), nB, H, Ls, s));
-                DWS_TRY(ln_scalars(p + ".norm1", nblk, s));
+                                      pg ? ln_slot() : nullptr, nB, H, Ls, s));
+                if (pg) DWS_TRY(ln_scalars(p + ".norm1", nblk, s));
                 written[e.in_node] = 1;
             } else if (l->kind == L_DOWN) {
                 const int K = l->H * l->p, O = l->Hout;
-                { const std::string wn_ = p + ".linear.conv"; DWS_TRY(wgrad(dy, l->t_xr.f(), O, K, l->Lout, 0, dWfold.f(), G(p + ".linear.conv.bias"), s, &wn_)); }
+                if (pg) { const std::string wn_ = p + ".linear.conv"; DWS_TRY(wgrad(dy, l->t_xr.f(), O, K, l->Lout, 0, dWfold.f(), G(p + ".linear.conv.bias"), s, &wn_)); }
                 DWS_TRY(gemm(l->tApT.f(), K, O, dy, pool_scr.f(), l->Lout, 2, nullptr, nullptr, nullptr, nullptr, nullptr, s));
                 DWS_TRY(launch_pool_rearrange(pool_scr.f(), din, nullptr, 1, written[e.in_node], nB, l->H, l->p, l->Lout, s));
                 written[e.in_node] = 1;
             } else {
                 const int K = l->H, O = l->Hout * l->p;   // xl = Wp x + b, [B][O][L_in]
                 DWS_TRY(launch_pool_rearrange(dy, pool_scr.f(), nullptr, 0, 0, nB, l->Hout, l->p, l->L, s));
-                { const std::string wn_ = p + ".linear.conv"; DWS_TRY(wgrad(pool_scr.f(), x, O, K, l->L, 0, dWfold.f(), G(p + ".linear.conv.bias"), s, &wn_)); }
+                if (pg) { const std::string wn_ = p + ".linear.conv"; DWS_TRY(wgrad(pool_scr.f(), x, O, K, l->L, 0, dWfold.f(), G(p + ".linear.conv.bias"), s, &wn_)); }
                 if (written[e.in_node])
                     DWS_TRY(gemm(l->tApT.f(), K, O, pool_scr.f(), din, l->L, 0, nullptr, nullptr, nullptr, din, nullptr, s));
                 else
@@ -1539,14 +1555,20 @@ struct SashimiModel : dws_model, S4Workspace {
                 }
                 written[e.add_node] = 1;
             }
-            DWS_TRY(grad_point(s));   // staged hand-over: buckets whose last gradient this layer produced leave now
+            if (pg) DWS_TRY(grad_point(s));   // staged hand-over: buckets whose last gradient this layer produced leave now
         }
 
         // ---- init_conv: x0 = relu(Wi audio + bi)
         const size_t nact = (size_t)B * D * L;
         DWS_CHECK(written[0], DWS_ERR_STATE, "backward: no gradient reached the init conv");
+        if (!pg) {   // the ReLU gate rides on the data adjoint: the masked gradient is never written
+            DWS_TRY(launch_init_conv_bwd_data(gp[0], x_init.f(), Wi.f(), daudio, nB, Cin, D, nL, s));
+            DWS_HIP(hipGetLastError());
+            return DWS_OK;
+        }
         DWS_TRY(launch_relu_bwd(gp[0], x_init.f(), nact, s));      // (node 0 is a skip node too: its gradient may live in an adopted buffer)
         { const std::string wn_ = "init_conv.0.conv"; DWS_TRY(wgrad(gp[0], train_audio, D, Cin, nL, 0, dWfold.f(), G("init_conv.0.conv.bias"), s, &wn_)); }
+        if (daudio) DWS_TRY(launch_init_conv_bwd_data(gp[0], nullptr, Wi.f(), daudio, nB, Cin, D, nL, s));
 
         // ---- step embedding: per-block fc_t (stacked), then the shared swish MLP
         DWS_TRY(launch_lin_bwd_w(dpt.f(), h2.f(), dWt_all.f(), dbt_all.f(), nB, Eout, pt_total, s));

@@ -38,6 +38,7 @@ int launch_s4_prep_bwd(const float* C, const float* Bp, const float* P, const fl
 int launch_pad_rows(const float* in, float* out, int rows, int L, hipStream_t s);
 int launch_s4_post_train(const float* yc, const float* u, const float* D, float* pre, float* g, int B, int H, int L,
                          hipStream_t s);
+int launch_conv_adjoint_spec_data(float* daf, const float* kf, int B, int H, int Lf, hipStream_t s);   // daf *= conj(kf) only
 int launch_conv_adjoint_spec(const float* uf, float* daf, const float* kf, float* dkf, int B, int H, int Lf, hipStream_t s);
 int launch_conv_adjoint_epi(const float* yc, const float* da, const float* D, float* du, float* rowsum, int rs_bstride, int B,
                             int H, int L, hipStream_t s);

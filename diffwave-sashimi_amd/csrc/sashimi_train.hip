@@ -89,7 +89,7 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const float* __restrict__ x
         cs[1][col] = ok ? sdx * rs + m * rs * sdy : 0.f;          // ds
     }
     __syncthreads();
-    if (threadIdx.x < 128) {
+    if (partial && threadIdx.x < 128) {     // (null: the data-only backward drops the parameter sums)
         const float v = wave_sum_t(cs[threadIdx.x >> 6][threadIdx.x & 63]);
         // two planes: partial[0][blk] = dm, partial[1][blk] = ds
         if ((threadIdx.x & 63) == 0)
@@ -178,7 +178,7 @@ __global__ __launch_bounds__(64 * PARTS) void ln_bwd_reg_kernel(const float* __r
         cs[1][col] = ok ? sdx * rs + m * rs * sdy : 0.f;          // ds
     }
     __syncthreads();
-    if (threadIdx.x < 128) {
+    if (partial && threadIdx.x < 128) {     // (null: the data-only backward drops the parameter sums)
         const float v = wave_sum_t(cs[threadIdx.x >> 6][threadIdx.x & 63]);
         if ((threadIdx.x & 63) == 0)
             partial[(size_t)(threadIdx.x >> 6) * gridDim.x * gridDim.y + (size_t)blockIdx.y * gridDim.x + blockIdx.x] = v;

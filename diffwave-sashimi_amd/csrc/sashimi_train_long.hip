@@ -72,6 +72,26 @@ __global__ void conv_adjoint_spec_kernel(const float2* __restrict__ uf, float2* 
     dkf[(size_t)h * Lf + k] = acc;
 }
 
+// The data half of it alone (data-only backward): daf[b][h][k] *= conj(kf[h][k]), the same product.
+__global__ void conv_adjoint_spec_data_kernel(float2* __restrict__ daf, const float2* __restrict__ kf, int B, int H, int Lf) {
+    const int k = blockIdx.x * blockDim.x + threadIdx.x;
+    const int h = blockIdx.y;
+    if (k >= Lf) return;
+    const float2 kk = kf[(size_t)h * Lf + k];
+    for (int b = 0; b < B; ++b) {
+        const size_t i = ((size_t)b * H + h) * Lf + k;
+        daf[i] = cmulc_l(kk, daf[i]);
+    }
+}
+
+int launch_conv_adjoint_spec_data(float* daf, const float* kf, int B, int H, int Lf, hipStream_t s) {
+    DWS_CHECK(B > 0 && H > 0 && H <= 65535 && Lf > 0, DWS_ERR_UNSUPPORTED, "conv_adjoint_spec: B=%d H=%d", B, H);
+    ProfileScope ps("conv_adjoint_spec_data", s);
+    hipLaunchKernelGGL(conv_adjoint_spec_data_kernel, dim3(ceil_div(Lf, 256), H), dim3(256), 0, s, (float2*)daf, (const float2*)kf,
+                       B, H, Lf);
+    return DWS_OK;
+}
+
 int launch_conv_adjoint_spec(const float* uf, float* daf, const float* kf, float* dkf, int B, int H, int Lf, hipStream_t s) {
     DWS_CHECK(B > 0 && H > 0 && H <= 65535 && Lf > 0, DWS_ERR_UNSUPPORTED, "conv_adjoint_spec: B=%d H=%d", B, H);
     ProfileScope ps("conv_adjoint_spec", s);
@@ -102,7 +122,7 @@ __global__ __launch_bounds__(256) void conv_adjoint_epi_kernel(const float* __re
     for (int off = 32; off > 0; off >>= 1) acc += __shfl_xor(acc, off);
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
     __syncthreads();
-    if (threadIdx.x == 0) rowsum[(size_t)b * rs_bstride + h] = red[0] + red[1] + red[2] + red[3];
+    if (rowsum && threadIdx.x == 0) rowsum[(size_t)b * rs_bstride + h] = red[0] + red[1] + red[2] + red[3];
 }
 
 int launch_conv_adjoint_epi(const float* yc, const float* da, const float* D, float* du, float* rowsum, int rs_bstride, int B,

@@ -57,6 +57,10 @@ int launch_step_embed(const float* steps, const float* freq, float* emb, int B, 
 int launch_iota_f32(float* out, int n, hipStream_t s);
 int launch_linear_rows(const float* in, const float* W, const float* bias, float* out, int B, int K, int O,
                        int act, hipStream_t s, float* pre_out = nullptr);
+// data adjoint of init_conv, shared by both backbones: daudio[b,ci,l] = sum_c W[c,ci] g[b,c,l] (Cin 1..4, C <= 512);
+// y != nullptr fuses the ReLU gate g * (y > 0) (g is then the gradient of the ReLU's output and is not written back)
+int launch_init_conv_bwd_data(const float* g, const float* y, const float* W, float* daudio, int B, int Cin, int C, int L,
+                              hipStream_t s);
 int launch_init_conv(const float* audio, const float* W, const float* bias, float* x, int B, int Cin, int C, int L,
                      hipStream_t s);
 int launch_wn_bias_tap(const float* Wd_all, const float* part_t, float* Abt, int NL, int B, int C, hipStream_t s);

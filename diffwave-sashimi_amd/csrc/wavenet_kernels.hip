@@ -255,6 +255,51 @@ int launch_init_conv(const float* audio, const float* W, const float* bias, floa
     return DWS_OK;
 }
 
+// Data adjoint of init_conv: daudio[b,ci,l] = sum_c W[c,ci] * g[b,c,l], g the gradient of the ReLU's input.
+// y != nullptr: `g` is the gradient of the ReLU's OUTPUT y and is gated here, g * (y > 0) -- the data-only backward, which
+// never writes the masked gradient.  A thread owns one position (b, l) and every input channel: g is read once, in
+// ascending c (the same sum in both modes); W sits in LDS.
+constexpr int INIT_BWD_MAX_C = 512;
+template <int CIN>
+__global__ __launch_bounds__(256) void init_conv_bwd_data_kernel(const float* __restrict__ g, const float* __restrict__ y,
+                                                                 const float* __restrict__ W, float* __restrict__ daudio,
+                                                                 int C, int L) {
+    __shared__ float w[INIT_BWD_MAX_C * CIN];
+    for (int i = threadIdx.x; i < C * CIN; i += 256) w[i] = W[i];
+    __syncthreads();
+    const int b = blockIdx.y, l = blockIdx.x * 256 + threadIdx.x;
+    if (l >= L) return;
+    const size_t base = (size_t)b * C * L + l;
+    float acc[CIN];
+#pragma unroll
+    for (int ci = 0; ci < CIN; ++ci) acc[ci] = 0.f;
+#pragma unroll 4
+    for (int c = 0; c < C; ++c) {
+        float v = g[base + (size_t)c * L];
+        if (y) v = y[base + (size_t)c * L] > 0.f ? v : 0.f;
+#pragma unroll
+        for (int ci = 0; ci < CIN; ++ci) acc[ci] = fmaf(w[c * CIN + ci], v, acc[ci]);
+    }
+#pragma unroll
+    for (int ci = 0; ci < CIN; ++ci) daudio[((size_t)b * CIN + ci) * L + l] = acc[ci];
+}
+
+int launch_init_conv_bwd_data(const float* g, const float* y, const float* W, float* daudio, int B, int Cin, int C, int L,
+                              hipStream_t s) {
+    DWS_CHECK(Cin >= 1 && Cin <= 4 && C >= 1 && C <= INIT_BWD_MAX_C, DWS_ERR_UNSUPPORTED,
+              "input gradient: in_channels=%d (1..4), channels=%d (up to %d)", Cin, C, INIT_BWD_MAX_C);
+    DWS_CHECK(B > 0 && B <= 65535 && L > 0, DWS_ERR_UNSUPPORTED, "input gradient: B=%d L=%d", B, L);
+    ProfileScope ps("init_conv_bwd_data", s);
+    const dim3 grid(ceil_div(L, 256), B), block(256);
+    switch (Cin) {
+        case 1: hipLaunchKernelGGL(init_conv_bwd_data_kernel<1>, grid, block, 0, s, g, y, W, daudio, C, L); break;
+        case 2: hipLaunchKernelGGL(init_conv_bwd_data_kernel<2>, grid, block, 0, s, g, y, W, daudio, C, L); break;
+        case 3: hipLaunchKernelGGL(init_conv_bwd_data_kernel<3>, grid, block, 0, s, g, y, W, daudio, C, L); break;
+        default: hipLaunchKernelGGL(init_conv_bwd_data_kernel<4>, grid, block, 0, s, g, y, W, daudio, C, L); break;
+    }
+    return DWS_OK;
+}
+
 // ---------------------------------------------------------------------------
 // Fused residual layer, exact-f32 MFMA path
 // ---------------------------------------------------------------------------

@@ -498,25 +498,33 @@ struct WaveNetModel : dws_model {
     }
 
     // Adjoint of run_forward (`models/wavenet.py:82-121,149-165,202-210`), layer by layer in reverse.
-    int backward(const float* dout, hipStream_t s) override {
+    // daudio (optional): the gradient w.r.t. the audio input.  pg = false (data-only, needs daudio): the data path alone, with
+    // the same kernels in the same order (daudio has the same bits in both modes) -- no weight / bias gradient, no weight-norm
+    // adjoint, no d fc_t(e) row sums, no embedding or conditioner adjoint, no G() access and no flush point.
+    int backward(const float* dout, float* daudio, bool pg, hipStream_t s) override {
         DWS_CHECK(trained_fwd, DWS_ERR_STATE, "backward without a preceding forward_train");
+        DWS_CHECK(pg || daudio, DWS_ERR_INVALID, "backward: a data-only pass needs a destination for the input gradient");
         const int nB = (int)B, nL = (int)L;
         const size_t act = (size_t)B * C * L * 4, nact = (size_t)B * C * L;
         DWS_TRY(dxa.ensure(act)); DWS_TRY(dxb.ensure(act)); DWS_TRY(dgb.ensure(act)); DWS_TRY(dresb.ensure(act));
         DWS_TRY(gate.ensure(act));
         DWS_TRY(dHb.ensure(2 * act));
         DWS_TRY(dskip.ensure((size_t)B * S * L * 4)); DWS_TRY(dyb.ensure((size_t)B * S * L * 4));
-        DWS_TRY(dWfold.ensure((size_t)std::max(2 * C * C * 3, std::max((C + S) * C, S * S)) * 4));
-        DWS_TRY(dpt.ensure((size_t)B * NL * C * 4));
-        DWS_TRY(dh2.ensure((size_t)B * Eout * 4)); DWS_TRY(dh1.ensure((size_t)B * Emid * 4));
-        DWS_TRY(dWt_all.ensure((size_t)NL * C * Eout * 4)); DWS_TRY(dbt_all.ensure((size_t)NL * C * 4));
+        if (pg) {
+            DWS_TRY(dWfold.ensure((size_t)std::max(2 * C * C * 3, std::max((C + S) * C, S * S)) * 4));
+            DWS_TRY(dpt.ensure((size_t)B * NL * C * 4));
+            DWS_TRY(dh2.ensure((size_t)B * Eout * 4)); DWS_TRY(dh1.ensure((size_t)B * Emid * 4));
+            DWS_TRY(dWt_all.ensure((size_t)NL * C * Eout * 4)); DWS_TRY(dbt_all.ensure((size_t)NL * C * 4));
+        }
         const float scale = (float)std::sqrt(1.0 / NL);
 
         // ---- final_conv: out = Wz y + bz, y = relu(Wf (skip * scale) + bf)
-        DWS_TRY(wgrad(dout, ty.f(), nullptr, 0, G("final_conv.2.conv.weight"), Cout, S, 1, 1, 1.f, s, G("final_conv.2.conv.bias")));
+        if (pg) DWS_TRY(wgrad(dout, ty.f(), nullptr, 0, G("final_conv.2.conv.weight"), Cout, S, 1, 1, 1.f, s, G("final_conv.2.conv.bias")));
         DWS_TRY(launch_final_dy(dout, P("final_conv.2.conv.weight"), ty.f(), dyb.f(), nB, S, Cout, nL, s));
-        DWS_TRY(wgrad(dyb.f(), skip.f(), nullptr, 0, dWfold.f(), S, S, 1, 1, scale, s, G("final_conv.0.conv.bias")));
-        DWS_TRY(wn_bwd("final_conv.0.conv", dWfold.f(), S, S, s));
+        if (pg) {
+            DWS_TRY(wgrad(dyb.f(), skip.f(), nullptr, 0, dWfold.f(), S, S, 1, 1, scale, s, G("final_conv.0.conv.bias")));
+            DWS_TRY(wn_bwd("final_conv.0.conv", dWfold.f(), S, S, s));
+        }
         if (mfma_bwd) {  // dskip = scale * Wf^T dy, the same for every layer
             if (bwd_pack_version != commit_version) DWS_TRY(pack_bwd(s));
             TapConvArgs f{};
@@ -553,7 +561,7 @@ struct WaveNetModel : dws_model {
                 }
                 DWS_TRY(launch_gate_bwd(dgb.f(), tH[n].f(), dHb.f(), gate.f(), nB, C, nL, s));
             }
-            if (melBm) {  // conditioner of this layer: d melc = dH (`wavenet.py:98-111`)
+            if (melBm && pg) {  // conditioner of this layer: d melc = dH (`wavenet.py:98-111`)
                 const int s0 = d.mel_upsample[0], s1 = d.mel_upsample[1];
                 DWS_TRY(gW0f.ensure((size_t)3 * 2 * s0 * 4)); DWS_TRY(gW1f.ensure((size_t)3 * 2 * s1 * 4));
                 DWS_TRY(gWcf.ensure((size_t)2 * C * MB * 4));
@@ -566,23 +574,25 @@ struct WaveNetModel : dws_model {
                 DWS_TRY(wn_bwd(p + ".mel_conv.conv", gWcf.f(), 2 * C, MB, s));
             }
             // res / skip 1x1 weights and biases (dres = dx' * sqrt(.5))
-            if (dx_out) {
+            if (pg && dx_out) {
                 DWS_TRY(wgrad(dx_out, gate.f(), nullptr, 0, dWfold.f(), C, C, 1, 1, r2, s, G(p + ".res_conv.bias"), r2));
                 DWS_TRY(wn_bwd(p + ".res_conv", dWfold.f(), C, C, s));
-            } else {  // the last layer's residual branch feeds nothing (`wavenet.py:165` uses only the skips)
+            } else if (pg) {  // the last layer's residual branch feeds nothing (`wavenet.py:165` uses only the skips)
                 DWS_HIP(hipMemsetAsync(G(p + ".res_conv.weight_v"), 0, (size_t)C * C * 4, s));
                 DWS_HIP(hipMemsetAsync(G(p + ".res_conv.weight_g"), 0, (size_t)C * 4, s));
                 DWS_HIP(hipMemsetAsync(G(p + ".res_conv.bias"), 0, (size_t)C * 4, s));
             }
-            DWS_TRY(wgrad(dskip.f(), gate.f(), nullptr, 0, dWfold.f(), S, C, 1, 1, 1.f, s, G(p + ".skip_conv.bias")));
-            DWS_TRY(wn_bwd(p + ".skip_conv", dWfold.f(), S, C, s));
-            // dilated conv: weights see h = x + pt (zero padded), input gets the transposed conv
-            DWS_TRY(wgrad(dHb.f(), tx[n].f(), part_t.f() + (size_t)n * C, NL * C, dWfold.f(), 2 * C, C, 3, dil, 1.f, s,
-                          G(p + ".dilated_conv_layer.conv.bias")));
-            DWS_TRY(wn_bwd(p + ".dilated_conv_layer.conv", dWfold.f(), 2 * C, C * 3, s));
-            if (melBm)    // the conditioner's 1x1 bias enters H next to the dilated conv's: same gradient
-                DWS_HIP(hipMemcpyAsync(G(p + ".mel_conv.conv.bias"), G(p + ".dilated_conv_layer.conv.bias"), (size_t)2 * C * 4,
-                                       hipMemcpyDeviceToDevice, s));
+            if (pg) {
+                DWS_TRY(wgrad(dskip.f(), gate.f(), nullptr, 0, dWfold.f(), S, C, 1, 1, 1.f, s, G(p + ".skip_conv.bias")));
+                DWS_TRY(wn_bwd(p + ".skip_conv", dWfold.f(), S, C, s));
+                // dilated conv: weights see h = x + pt (zero padded), input gets the transposed conv
+                DWS_TRY(wgrad(dHb.f(), tx[n].f(), part_t.f() + (size_t)n * C, NL * C, dWfold.f(), 2 * C, C, 3, dil, 1.f, s,
+                              G(p + ".dilated_conv_layer.conv.bias")));
+                DWS_TRY(wn_bwd(p + ".dilated_conv_layer.conv", dWfold.f(), 2 * C, C * 3, s));
+                if (melBm)    // the conditioner's 1x1 bias enters H next to the dilated conv's: same gradient
+                    DWS_HIP(hipMemcpyAsync(G(p + ".mel_conv.conv.bias"), G(p + ".dilated_conv_layer.conv.bias"), (size_t)2 * C * 4,
+                                           hipMemcpyDeviceToDevice, s));
+            }
             if (mfma_bwd) {
                 TapConvArgs q{};
                 q.src0 = dHb.f(); q.K0 = 2 * C; q.A = ATd[n].f(); q.nkg_total = 6 * C / 8; q.M = C; q.T = 3; q.dil = dil;
@@ -597,15 +607,21 @@ struct WaveNetModel : dws_model {
             } else {
                 DWS_TRY(launch_conv_t(dHb.f(), Wd(n), dh, nB, 2 * C, C, nL, 3, dil, 1.f, 0, s));
             }
-            DWS_TRY(launch_rowsum_bc(dh, dpt.f() + (size_t)n * C, NL * C, nB, C, nL, s));  // d fc_t(e)[b, n, c]
+            if (pg) DWS_TRY(launch_rowsum_bc(dh, dpt.f() + (size_t)n * C, NL * C, nB, C, nL, s));  // d fc_t(e)[b, n, c]
             if (dx_out) DWS_TRY(launch_dx_combine(dh, dx_out, nact, s));                   // + dx' * sqrt(.5)
             dx_out = dh;
-            DWS_TRY(grad_point(s));   // staged hand-over: buckets whose last gradient this layer produced leave now
+            if (pg) DWS_TRY(grad_point(s));   // staged hand-over: buckets whose last gradient this layer produced leave now
         }
         // ---- init_conv: x0 = relu(Wi audio + bi)
+        if (!pg) {   // the ReLU gate rides on the data adjoint: the masked gradient is never written
+            DWS_TRY(launch_init_conv_bwd_data(dx_out, tx[0].f(), Wi.f(), daudio, nB, Cin, C, nL, s));
+            DWS_HIP(hipGetLastError());
+            return DWS_OK;
+        }
         DWS_TRY(launch_relu_bwd(dx_out, tx[0].f(), nact, s));
         DWS_TRY(wgrad(dx_out, train_audio, nullptr, 0, dWfold.f(), C, Cin, 1, 1, 1.f, s, G("init_conv.0.conv.bias")));
         DWS_TRY(wn_bwd("init_conv.0.conv", dWfold.f(), C, Cin, s));
+        if (daudio) DWS_TRY(launch_init_conv_bwd_data(dx_out, nullptr, Wi.f(), daudio, nB, Cin, C, nL, s));
 
         // ---- step embedding: per-layer fc_t (stacked), then the shared swish MLP
         DWS_TRY(launch_lin_bwd_w(dpt.f(), h2.f(), dWt_all.f(), dbt_all.f(), nB, Eout, NL * C, s));

@@ -215,7 +215,8 @@ def _load_clip(dataset_cfg, stem, audio_length, conditional):
 def generate(rank, diffusion_cfg, model_cfg, dataset_cfg, ckpt_iter="max", n_samples=1, name=None, batch_size=None,
              ckpt_smooth=None, mel_path=None, mel_name=None, dataloader=None, exp_root="exp", seed=None,
              written=None, precision=None, sampler="ddpm", steps=None, eta=0.0, known_name=None, keep=None,
-             start_name=None, start_step=None, start_noise=True, resample_jump=None, resample_n=None, spacing=None):
+             start_name=None, start_step=None, start_noise=True, resample_jump=None, resample_n=None, spacing=None,
+             guide_name=None, guide_op=None, guide_clip=None, guide_factor=None, guide_scale=None):
     """``generate.py:58-200``.  ``ckpt_iter`` may additionally be ``"init"``: seeded random weights
     (no checkpoint), for smoke runs without trained weights.  ``precision`` (not in the reference; CLI:
     ``+engine.precision=bf16x6|f16x3``): the engine's opt-in matrix arithmetic, see ``include/dws.h``.
@@ -234,11 +235,43 @@ def generate(rank, diffusion_cfg, model_cfg, dataset_cfg, ckpt_iter="max", n_sam
     noised to the step's level first unless ``start_noise`` is false (then the wav is the state as given).
     ``resample_jump`` with ``resample_n`` (both or neither; they need ``known_name``) run the inpainting with RePaint's
     resampling: at every ``resample_jump``-th position the chain goes back up that many steps and down again,
-    ``resample_n`` times in all (``sampling.repaint_program``)."""
+    ``resample_n`` times in all (``sampling.repaint_program``).
+
+    Restoration (not in the reference; ``sampler`` ddpm or ddim, no editing): ``guide_name`` (a wav stem under
+    ``dataset.data_path``, the degraded recording, at ``dataset.sampling_rate``) with ``guide_op`` = ``declip`` (the
+    recording is clipped at ``guide_clip``, default its largest magnitude) or ``lowpass`` (the recording is band-limited:
+    its measurement is the wav low-passed and decimated by ``guide_factor``, default 2) and ``guide_scale`` (the
+    guidance step, required: there is no default that fits every model and operator) runs Diffusion Posterior Sampling,
+    ``sampling.sampling_guided`` -- a forward and a data-only backward of the network per step, every clip of the batch
+    guided by the same recording."""
     from .models import construct_model
-    from .sampling import (calc_diffusion_hyperparams, ddim_steps, logsnr_steps, program_evaluations, repaint_program,
-                           sampling, sampling_aligned, sampling_ddim, sampling_dpmpp, spans_to_mask)
+    from .sampling import (calc_diffusion_hyperparams, ddim_steps, declip_operator, logsnr_steps, lowpass_operator,
+                           program_evaluations, repaint_program, sampling, sampling_aligned, sampling_ddim, sampling_dpmpp,
+                           sampling_guided, spans_to_mask)
     from scipy.io.wavfile import write as wavwrite
+
+    if guide_name is None:
+        given = [k for k, v in (("guide_op", guide_op), ("guide_clip", guide_clip), ("guide_factor", guide_factor),
+                                ("guide_scale", guide_scale)) if v is not None]
+        if given:
+            raise ValueError(f"generate.{given[0]} needs generate.guide_name (the degraded recording)")
+    else:
+        if guide_op not in ("declip", "lowpass"):
+            raise ValueError(f"generate.guide_op={guide_op!r}: expected declip or lowpass")
+        if guide_scale is None:
+            raise ValueError("generate.guide_name needs generate.guide_scale (the guidance step; no default is chosen: it "
+                             "depends on the model and the operator)")
+        if float(guide_scale) == 0.0:
+            raise ValueError("generate.guide_scale=0 is the unguided run: drop generate.guide_name")
+        if guide_op == "declip" and guide_factor is not None:
+            raise ValueError("generate.guide_factor belongs to generate.guide_op=lowpass")
+        if guide_op == "lowpass" and guide_clip is not None:
+            raise ValueError("generate.guide_clip belongs to generate.guide_op=declip")
+        if (sampler or "ddpm") not in ("ddpm", "ddim"):
+            raise ValueError(f"generate.guide_name with generate.sampler={sampler}: guided runs are built for ddpm and ddim")
+        if known_name is not None or start_name is not None or resample_jump is not None:
+            raise ValueError("generate.guide_name does not combine with the editing keys (known_name, start_name, "
+                             "resample_jump)")
 
     if known_name is not None and not keep:
         raise ValueError("generate.known_name needs generate.keep: at least one [start, end) span of kept samples")
@@ -344,13 +377,26 @@ def generate(rank, diffusion_cfg, model_cfg, dataset_cfg, ckpt_iter="max", n_sam
         edit["start_noise"] = None if start_noise else False
     if resample_jump is not None:
         edit["resample"] = (resample_jump, resample_n)
+    guide = None
+    if guide_name is not None:
+        rec = _load_clip(dataset_cfg, guide_name, audio_length, mel is not None).expand(batch_size, 1, audio_length)
+        if guide_op == "declip":
+            op = declip_operator(float(rec.abs().max()) if guide_clip is None else guide_clip)
+            guide = dict(measurement=rec, operator=op, scale=float(guide_scale))
+        else:
+            op = lowpass_operator(2 if guide_factor is None else guide_factor)
+            guide = dict(measurement=op(rec), operator=op, scale=float(guide_scale))
 
     t0 = time.perf_counter()
     out = []
     for i in range(n_samples // batch_size):
         s = None if seed is None else seed + 1000 * rank + i
         size = (batch_size, 1, audio_length)
-        if sampler == "aligned":
+        if guide is not None:
+            ddim = sampler == "ddim"
+            out.append(sampling_guided(net, size, dh_train if ddim else dh, sampler=sampler, steps=steps if ddim else None,
+                                       eta=float(eta or 0.0) if ddim else 0.0, condition=mel, seed=s, **guide))
+        elif sampler == "aligned":
             out.append(sampling_aligned(net, size, diffusion_cfg, condition=mel, seed=s, **edit))
         elif sampler == "ddim":
             out.append(sampling_ddim(net, size, dh_train, steps, eta=float(eta or 0.0), condition=mel, seed=s, **edit))
@@ -362,7 +408,10 @@ def generate(rank, diffusion_cfg, model_cfg, dataset_cfg, ckpt_iter="max", n_sam
     torch.cuda.synchronize()
     print(f"generated {n_samples} samples shape {tuple(generated_audio.shape)} at iteration {ckpt_iter} in "
           f"{time.perf_counter() - t0:.1f} seconds")
-    if sampler != "ddpm" or resample_jump is not None:
+    if guide is not None:
+        print(f"guided sampler {sampler} ({guide_op}, scale {float(guide_scale):g}): {n_evals} network evaluations "
+              f"(each a forward and a data-only backward) per batch")
+    elif sampler != "ddpm" or resample_jump is not None:
         note = f" (eta={float(eta or 0.0)})" if sampler == "ddim" else f" ({spacing} spacing)" if sampler == "dpmpp2m" else ""
         print(f"sampler {sampler}{note}: {n_evals} network evaluations per batch")
     for i in range(n_samples):

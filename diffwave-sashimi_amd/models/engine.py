@@ -4,6 +4,7 @@ import ctypes
 
 import torch
 import torch.nn as nn
+from torch.autograd.function import once_differentiable
 
 from .. import _lib
 
@@ -12,7 +13,14 @@ class _EngineTrainFn(torch.autograd.Function):
     """Differentiable call of the engine (`train.py:221`): forward_train keeps the activations inside
     the dws_model, backward fills the gradient of every raw state-dict tensor, which are handed to
     autograd as the gradients of the module's parameters (so optimizers and the DP all-reduce of
-    ``distributed_util.apply_gradient_allreduce`` work unchanged)."""
+    ``distributed_util.apply_gradient_allreduce`` work unchanged).
+
+    ``audio`` gets a gradient too when it requires one (guided sampling, input-space optimisation): the data adjoint of
+    ``init_conv`` closes the chain of data gradients the backward carries anyway.  When no parameter takes part (the call
+    was made without ``*params``: an ``eval()`` module, frozen parameters) the backward is DATA-ONLY,
+    ``dws_model_backward_input(param_grads=0)``: no parameter gradient is computed or written, the reducer and the
+    gradient sinks are not involved.  ``mel_spec`` and ``diffusion_steps`` never get a gradient (the conditioner's and
+    the embedding's data adjoints towards their inputs are not built), and the backward is once-differentiable."""
 
     @staticmethod
     def forward(ctx, module, audio, steps, mel_spec, *params):
@@ -28,10 +36,13 @@ class _EngineTrainFn(torch.autograd.Function):
         ctx.module, ctx.x, ctx.steps = module, x, steps      # x must stay alive until backward (init_conv adjoint)
         module._train_generation += 1                        # the activations inside the dws_model belong to THIS forward
         ctx.generation = module._train_generation
-        ctx.meta = [(n, tuple(p.shape), p.dtype) for n, p in module.named_parameters()]
+        # (called without parameters: nobody wants their gradients -- the backward is data-only)
+        ctx.meta = [(n, tuple(p.shape), p.dtype) for n, p in module.named_parameters()] if params else []
+        ctx.audio_meta = (tuple(audio.shape), audio.dtype)
         return out
 
     @staticmethod
+    @once_differentiable
     def backward(ctx, dout):
         lib = _lib.load()
         m = ctx.module
@@ -40,6 +51,20 @@ class _EngineTrainFn(torch.autograd.Function):
                                "module before this backward (accumulate gradients with forward/backward pairs)")
         d = dout.detach().to(torch.float32).contiguous()
         n = len(ctx.meta)
+        daudio = None
+        if ctx.needs_input_grad[1]:
+            daudio = torch.empty(ctx.audio_meta[0], device=d.device, dtype=torch.float32)
+        if not any(ctx.needs_input_grad[4:]):
+            if daudio is None:
+                return (None,) * (4 + n)
+            _lib.check(lib.dws_model_backward_input(m._handle, d.data_ptr(), daudio.data_ptr(), 0, _lib.current_stream()))
+            return (None, daudio.to(ctx.audio_meta[1]), None, None) + (None,) * n
+
+        def run_backward():      # (without an input gradient: exactly the call made before the input gradient existed)
+            if daudio is None:
+                _lib.check(lib.dws_model_backward(m._handle, d.data_ptr(), _lib.current_stream()))
+            else:
+                _lib.check(lib.dws_model_backward_input(m._handle, d.data_ptr(), daudio.data_ptr(), 1, _lib.current_stream()))
         # Data-parallel runs (distributed_util.GradientAllReducer): the gradients are written straight into the flat
         # all-reduce buckets -- views handed out per backward, adopted by autograd as p.grad without a copy.  A parameter
         # that still holds a gradient (accumulation over several backwards) gets its own tensor instead: its p.grad may
@@ -82,20 +107,20 @@ class _EngineTrainFn(torch.autograd.Function):
                 m._sink_key = key
             # (no reference to `outs` may be kept: autograd adopts a returned gradient as p.grad only when nobody else holds
             # it, otherwise it clones.  The destinations outlive the sinks anyway: arena slots and `_grad_fallback` tensors.)
-            _lib.check(lib.dws_model_backward(m._handle, d.data_ptr(), _lib.current_stream()))
+            run_backward()
             reducer.engine_backward_done(m, [name for name, _, _ in ctx.meta])
         else:
             if getattr(m, "_sink_key", None) is not None:           # the module left data-parallel mode
                 _lib.check(lib.dws_model_set_grad_sinks(m._handle, 0, None, None, None, None, 0))
                 m._sink_key = None
-            _lib.check(lib.dws_model_backward(m._handle, d.data_ptr(), _lib.current_stream()))
+            run_backward()
             names = (ctypes.c_char_p * n)(*[name.encode() for name, _, _ in ctx.meta])
             dsts = (ctypes.c_void_p * n)(*[g.data_ptr() for g in outs])
             numels = (ctypes.c_int64 * n)(*[g.numel() for g in outs])
             _lib.check(lib.dws_model_get_grads(m._handle, n, names, dsts, numels, _lib.current_stream()))   # one launch
         grads = [(g.to(dtype) if (dtype != torch.float32 or gi >= 0 or reducer is None) else g.clone())
                  for g, gi, (_, _, dtype) in zip(outs, groups_in, ctx.meta)]
-        return (None, None, None, None, *grads)
+        return (None, None if daudio is None else daudio.to(ctx.audio_meta[1]), None, None, *grads)
 
 
 class EngineModule(nn.Module):
@@ -114,6 +139,7 @@ class EngineModule(nn.Module):
         self._mel_key = None
         self._mel_ref = None
         self._train_generation = 0
+        self._mel_expanded = None
 
     # -- handle management ---------------------------------------------------
     def _desc(self):
@@ -216,6 +242,17 @@ class EngineModule(nn.Module):
         _lib.check(lib.dws_model_set_condition(h, mel.data_ptr(), mel.shape[0], mel.shape[2], _lib.current_stream()))
         self._mel_key, self._mel_ref = key, mel_spec
 
+    def _expand_mel(self, mel_spec, B):
+        """One mel for B clips, [1, bands, Tmel] -> [B, bands, Tmel] (the training forward needs a mel per clip).  The
+        expanded tensor is kept with the one it was made from, so that ``_set_condition`` recognises it call after call."""
+        if mel_spec is None or mel_spec.dim() != 3 or mel_spec.shape[0] != 1 or B == 1:
+            return mel_spec
+        key = (mel_spec.data_ptr(), mel_spec._version, tuple(mel_spec.shape), B)
+        kept = self._mel_expanded
+        if kept is None or kept[0] is not mel_spec or kept[1] != key:
+            kept = self._mel_expanded = (mel_spec, key, mel_spec.detach().expand(B, -1, -1).contiguous())
+        return kept[2]
+
     # -- reference surface -----------------------------------------------------
     def forward(self, input_data, mel_spec=None):
         audio, diffusion_steps = input_data
@@ -225,12 +262,18 @@ class EngineModule(nn.Module):
         if audio.dim() != 3:
             raise RuntimeError("audio must be [B, in_channels, L]")
         B, Cin, L = audio.shape
-        if torch.is_grad_enabled() and self.training and any(p.requires_grad for p in self.parameters()):
-            # training call (`train.py:221`): differentiable w.r.t. the parameters
+        train_call = torch.is_grad_enabled() and self.training and any(p.requires_grad for p in self.parameters())
+        if train_call or (torch.is_grad_enabled() and audio.requires_grad):
+            # training call (`train.py:221`): differentiable w.r.t. the parameters -- and, in train() or eval() mode (the nets
+            # have no mode-dependent layer), w.r.t. an `audio` that requires a gradient; then alone, the parameters stay out of
+            # the graph and backward is data-only.  The path has the limits of forward_train (f32 / bf16x6, no segmented S4
+            # stage): the engine's own error is raised, there is no fallback.
             steps = diffusion_steps.detach().to(device=audio.device, dtype=torch.float32).reshape(-1).contiguous()
             if steps.numel() != B:
                 raise RuntimeError(f"diffusion_steps must hold B={B} entries, got {tuple(diffusion_steps.shape)}")
-            return _EngineTrainFn.apply(self, audio, steps, mel_spec, *self.parameters())
+            if audio.requires_grad:
+                mel_spec = self._expand_mel(mel_spec, B)
+            return _EngineTrainFn.apply(self, audio, steps, mel_spec, *(self.parameters() if train_call else ()))
         with torch.no_grad():
             self._train_generation += 1      # an eval forward overwrites the activations of a pending training forward
             self._sync_params(L)

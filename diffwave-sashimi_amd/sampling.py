@@ -536,3 +536,186 @@ def sampling_aligned(net, size, diffusion_cfg, condition=None, **kw):
     T, b0, bT = diffusion_cfg["T"], diffusion_cfg["beta_0"], diffusion_cfg["beta_T"]
     dh = calc_diffusion_hyperparams(T, b0, bT, beta=beta, fast=True)
     return sampling(net, size, dh, condition, net_steps=align_steps(T, b0, bT, beta), **kw)
+
+
+# --------------------------------------------------------------------------- guided runs (not the reference's)
+def declip_operator(c):
+    """Measurement operator of a clipped recording: ``A(x) = x.clamp(-c, c)`` (``c > 0``)."""
+    c = float(c)
+    if not c > 0:
+        raise ValueError(f"declip_operator: c = {c!r} (needs a clipping level > 0)")
+    return lambda x: x.clamp(-c, c)
+
+
+def lowpass_taps(factor, taps=33):
+    """float64 [taps]: sinc of cutoff ``1/factor`` (of Nyquist) under a Hann window without its zero end points,
+    normalised to unit sum."""
+    if not _is_int(factor) or factor < 1:
+        raise ValueError(f"lowpass_operator: factor = {factor!r} (needs an integer >= 1)")
+    if not _is_int(taps) or taps < 1 or int(taps) % 2 == 0:
+        raise ValueError(f"lowpass_operator: taps = {taps!r} (needs an odd integer >= 1)")
+    taps = int(taps)
+    k = np.arange(taps, dtype=np.float64)
+    h = np.sinc((k - (taps - 1) / 2) / int(factor)) * (0.5 - 0.5 * np.cos(2 * np.pi * (k + 1) / (taps + 1)))
+    return h / h.sum()
+
+
+def lowpass_operator(factor, taps=33):
+    """Measurement operator of a band-limited recording: ``A(x)[..., j] = sum_k h[k] x[..., j factor + k - (taps-1)/2]``
+    with ``h = lowpass_taps(factor, taps)`` and zeros outside the clip ("same" padding), i.e. low-pass then decimation by
+    ``factor``: [..., L] -> [..., ceil(L / factor)].  Written with strided slices and sums (differentiable, any device,
+    no convolution library on the path)."""
+    h = lowpass_taps(factor, taps)
+    factor, half = int(factor), (len(h) - 1) // 2
+
+    def A(x):
+        L = x.shape[-1]
+        xp = torch.cat([x.new_zeros(x.shape[:-1] + (half,)), x, x.new_zeros(x.shape[:-1] + (half,))], dim=-1)
+        y = None
+        for k, hk in enumerate(h):
+            term = xp[..., k:k + L:factor] * float(hk)
+            y = term if y is None else y + term
+        return y
+    return A
+
+
+def guided_coefficients(dh, sampler, steps=None, eta=0.0):
+    """Tables of ``sampling_guided``: (net_steps float32 [S], float32 [6][S] = k1, k2, a, b, c, 0/1) with the x0
+    estimate ``u = (x - k1 eps) / k2`` and the unguided update written for both samplers as
+    DDIM ``x = a u + b eps + c z`` (a, b, c = k3, k4, k5 of ``ddim_coefficients``; last row 1) and
+    DDPM ``x = (x - a eps) / b + c z`` (``a = (1 - Alpha) / sqrt(1 - Alpha_bar)``, ``b = sqrt(Alpha)``, ``c = Sigma`` in
+    float32 as the reference's loop forms them; ``k1 = sqrt(1 - Alpha_bar)``, ``k2 = sqrt(Alpha_bar)`` in float64 from the
+    float32 table, rounded once; last row 0)."""
+    T = int(dh["T"])
+    if sampler == "ddim":
+        if steps is None:
+            raise ValueError("sampling_guided: sampler='ddim' needs steps= (the number of DDIM steps, or a list)")
+        tau = ddim_steps(T, steps)
+        k = ddim_coefficients(dh["Alpha_bar"], tau, eta)
+        return np.asarray(tau, dtype=np.float32), np.concatenate([k, np.ones((1, len(tau)), np.float32)])
+    if sampler != "ddpm":
+        raise ValueError(f"sampling_guided: sampler = {sampler!r} (guided runs are built for 'ddpm' and 'ddim'; "
+                         "'dpmpp2m' and 'aligned' are not)")
+    if steps is not None and (not _is_int(steps) or int(steps) != T):
+        raise ValueError(f"sampling_guided: sampler='ddpm' runs the {T} steps of its schedule (steps = {steps!r}); "
+                         "pass a short diffusion.beta schedule or use sampler='ddim'")
+    if float(eta) != 0.0:
+        raise ValueError("sampling_guided: eta is DDIM's")
+    Alpha, Alpha_bar, Sigma = (dh[k].detach().cpu().to(torch.float32) for k in ("Alpha", "Alpha_bar", "Sigma"))
+    ab = Alpha_bar.numpy().astype(np.float64)
+    a = ((1 - Alpha) / torch.sqrt(1 - Alpha_bar)).numpy()
+    k = np.stack([np.sqrt(1.0 - ab).astype(np.float32), np.sqrt(ab).astype(np.float32), a, torch.sqrt(Alpha).numpy(),
+                  Sigma.numpy(), np.zeros(T, np.float32)])
+    return np.arange(T, dtype=np.float32), k.astype(np.float32)
+
+
+def sampling_guided(net, size, diffusion_hyperparams, *, measurement, operator, scale, sampler="ddpm", steps=None,
+                    eta=0.0, condition=None, x_T=None, noise=None, seed=None, residuals=None, **unsupported):
+    """Restoration with a trained model by Diffusion Posterior Sampling (Chung et al., ICLR 2023): a reverse run whose
+    every step is pulled towards a degraded recording ``measurement = operator(x0)``.  ``operator`` is any differentiable
+    torch callable ``A(x0) -> measurement-shaped tensor`` (``declip_operator``, ``lowpass_operator``).  Per step s
+    (S-1 .. 0; tables: ``guided_coefficients``)::
+
+        eps = net((x, t_s))                       # differentiable call, x.requires_grad
+        u   = (x - k1 eps) / k2                   # x0 estimate
+        n_b = || y_b - A(u)_b ||_2                # per clip
+        g   = d(sum_b n_b) / dx                   # autograd through A and u, the network's input gradient through eps
+        x   = update(x, eps, z_s) - scale * g     # update: the unguided step of ``sampling`` / ``sampling_ddim``
+
+    i.e. DPS with zeta_s = (scale / 2) / ||r||.  A clip whose residual is exactly zero gets no guidance term; the
+    guidance is applied at every step, s = 0 included.  ``scale`` must not be zero (that is ``sampling`` /
+    ``sampling_ddim``); no default is offered -- it depends on the operator and the model.
+
+    ``sampler``: ``"ddpm"`` (the loop of ``sampling`` over ``dh``, e.g. a short ``diffusion.beta`` schedule) or
+    ``"ddim"`` (``steps`` of the training schedule ``dh`` with ``eta``).  ``noise``: injected z [S, B, C, L]
+    (``noise[s]`` after step s > 0), ``x_T``: the initial state; otherwise both are drawn -- with an engine model from
+    the Philox streams the plain samplers use (stream s for step s, stream S for ``x_T``; ``seed`` as there), with any
+    other ``net`` from a torch CPU generator seeded with ``seed``.  ``residuals``: a list that receives ``n`` [B] of
+    every step (diagnostics).
+
+    ``net`` is any differentiable callable of the reference surface on any device.  With an engine model every step is
+    a training forward and a DATA-ONLY backward (``dws_model_backward_input``): put the model in ``eval()`` mode, or the
+    full backward runs.  The path has the limits of the training forward (precision f32 / bf16x6, no segmented S4
+    stage); a mel ``[1, bands, Tmel]`` is expanded to the batch.  The loop runs eagerly, one step after the other with
+    no graph capture: each step contains a backward.  Costs a forward plus a backward per step.  The editing arguments
+    (``known`` / ``mask`` ..., ``resample``) are not built for guided runs.  Not the reference's loop."""
+    if unsupported:
+        known = {"known", "mask", "known_noise", "x_start", "start_step", "start_noise", "resample", "net_steps", "spacing"}
+        bad = sorted(unsupported)
+        if set(bad) <= known:
+            raise ValueError(f"sampling_guided: {', '.join(bad)}: editing, resampling and step alignment are not built "
+                             "for guided runs")
+        raise TypeError(f"sampling_guided: unexpected arguments {bad}")
+    try:
+        scale = float(scale)
+    except (TypeError, ValueError):
+        raise ValueError(f"sampling_guided: scale = {scale!r} (needs a number)")
+    if scale == 0.0 or scale != scale:
+        raise ValueError("sampling_guided: scale = 0 is the unguided run: call sampling / sampling_ddim")
+    if not callable(operator):
+        raise ValueError("sampling_guided: operator must be a differentiable callable A(x0)")
+    if len(size) != 3:
+        raise ValueError(f"sampling_guided: size = {tuple(size)!r} (needs (B, C, L))")
+    net_steps, k = guided_coefficients(diffusion_hyperparams, sampler, steps, eta)
+    S = len(net_steps)
+    B, C, L = (int(v) for v in size)
+    size = (B, C, L)
+    if noise is not None and tuple(noise.shape) != (S,) + size:
+        raise ValueError(f"sampling_guided: noise has shape {tuple(noise.shape)}, expected {(S,) + size}")
+    if x_T is not None and tuple(x_T.shape) != size:
+        raise ValueError(f"sampling_guided: x_T has shape {tuple(x_T.shape)}, expected {size}")
+    from .models.engine import EngineModule
+    engine = isinstance(net, EngineModule)
+    if engine:
+        dev = next(net.parameters()).device
+        if dev.type != "cuda":
+            raise RuntimeError("libdws runs on the GPU only: move the model to cuda (there is no CPU fallback)")
+    else:
+        p = next(iter(net.parameters()), None) if hasattr(net, "parameters") else None
+        dev = p.device if p is not None else torch.as_tensor(measurement).device
+    y = torch.as_tensor(measurement).detach().to(device=dev, dtype=torch.float32)
+    if condition is not None:
+        condition = condition.detach().to(dev)
+    if seed is None:
+        seed = int(torch.randint(0, 2 ** 63 - 1, (1,), dtype=torch.int64).item())
+    gen = None
+
+    def draw(stream_id):
+        nonlocal gen
+        if engine:
+            z = torch.empty(size, device=dev, dtype=torch.float32)
+            with torch.cuda.device(dev):
+                _lib.check(_lib.load().dws_philox_normal(z.data_ptr(), z.numel(), seed, stream_id, _lib.current_stream()))
+            return z
+        if gen is None:
+            gen = torch.Generator().manual_seed(seed % (2 ** 63))
+        return torch.randn(size, generator=gen).to(dev)
+
+    x = draw(S) if x_T is None else x_T.detach().to(device=dev, dtype=torch.float32).clone()
+    kw = {} if condition is None else {"mel_spec": condition}
+    for s in range(S - 1, -1, -1):
+        k1, k2, a, b, c, ddim = (float(v) for v in k[:, s])
+        t = torch.full((B, 1), float(net_steps[s]), device=dev, dtype=torch.float32)
+        with torch.enable_grad():
+            xin = x.detach().requires_grad_(True)
+            eps = net((xin, t), **kw)
+            u = (xin - k1 * eps) / k2
+            Au = operator(u)
+            if Au.shape != y.shape:
+                raise ValueError(f"sampling_guided: the operator gives {tuple(Au.shape)}, the measurement is "
+                                 f"{tuple(y.shape)}")
+            r = (y - Au).reshape(B, -1)
+            sq = (r * r).sum(dim=1)
+            live = sq > 0
+            n = torch.where(live, torch.sqrt(torch.where(live, sq, torch.ones_like(sq))), torch.zeros_like(sq))
+            g = torch.autograd.grad(n.sum(), xin)[0] if bool(live.any()) else torch.zeros_like(x)
+        with torch.no_grad():
+            eps = eps.detach()
+            if residuals is not None:
+                residuals.append(n.detach().cpu())
+            x = a * ((x - k1 * eps) / k2) + b * eps if ddim else (x - a * eps) / b
+            if s > 0:
+                z = draw(s) if noise is None else noise[s].detach().to(device=dev, dtype=torch.float32)
+                x = x + c * z
+            x = x - scale * g
+    return x

@@ -191,6 +191,16 @@ int dws_model_forward(dws_model* m, const float* audio, const float* steps, floa
  * `distributed_util.py:97-149`). */
 int dws_model_forward_train(dws_model* m, const float* audio, const float* steps, float* out, void* stream);
 int dws_model_backward(dws_model* m, const float* dout, void* stream);
+/* backward that can also deliver the gradient w.r.t. the AUDIO input (guided sampling, input-space optimisation):
+ * daudio[B, in_channels, L] (device; NULL: not wanted) = d Loss / d audio of the pending forward_train.
+ * param_grads = 1: everything dws_model_backward does (it is this call with daudio == NULL), plus daudio.
+ * param_grads = 0: DATA-ONLY -- the chain of data adjoints alone, the same kernels in the same order (daudio has the same
+ * bits as under param_grads = 1): no weight / bias gradient, no weight-norm adjoint, no S4 kernel adjoint, no LayerNorm
+ * parameter sums, no step-embedding or conditioner adjoint.  No gradient buffer is written, nothing is delivered to
+ * installed sinks and no group event is recorded.  Needs daudio (else DWS_ERR_INVALID).
+ * Preconditions as dws_model_backward: one pending forward_train, precision f32 or bf16x6.  The mel condition and the
+ * diffusion steps get no gradient. */
+int dws_model_backward_input(dws_model* m, const float* dout, float* daudio, int32_t param_grads, void* stream);
 int dws_model_get_grad(dws_model* m, const char* name, float* dst, int64_t numel, void* stream);
 /* The same for `count` parameters in one launch (the autograd wrapper fetches every gradient after backward). */
 int dws_model_get_grads(dws_model* m, int32_t count, const char* const* names, float* const* dsts, const int64_t* numels,
