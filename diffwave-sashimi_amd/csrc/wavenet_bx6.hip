@@ -5,18 +5,23 @@
 //
 // Per tile of 32 pairs (64 positions) and all channels, C/32 waves, a wave owns one (tanh, sigmoid) row-tile pair:
 //   * raw x at the four shifts -d, 0, +d, +2d staged by LDS-DMA exactly as in wavenet_wino.hip (16-byte pieces,
-//     out-of-range shifts read 0 = the conv's zero padding; one contiguous row piece for d <= 16);
+//     out-of-range shifts read 0 = the conv's zero padding; one contiguous row piece for d <= 16), two chunks ahead.
+//     Eight waves under the 3-term split: a chunk is staged by one half of the workgroup, alternating (waves 0..3 | 4..7 =
+//     one wave of every SIMD), so that the other wave of a SIMD has no LDS-DMA piece queued in front of its A fragments;
+//     every other instance: all waves stage every chunk;
 //   * transform pass, all waves together once per chunk of KC channels: t0..t3 (fp32, the same roundings as the
 //     f32 Winograd path), each split into three bf16 terms and stored in the B-fragment order of
 //     v_mfma_f32_32x32x16_bf16: 16-byte items [k-octet][product][term][column], one conflict-free ds_read_b128 per
-//     fragment;
+//     fragment.  The pass is branch-free and cut into seven units that stand between the MFMAs of the previous chunk's
+//     first step (the one wave's copy of its residual rows is a branch of its own ahead of the second step);
 //   * GEMM1: m_j = G_j t_j for the wave's two row tiles; the A fragments of G0..G3 (three bf16 terms each, packed at
-//     commit: 6 bytes per weight) stream from L2 one (k-block, product) step ahead; 12 MFMAs per step;
+//     commit: 6 bytes per weight) stream from L2 one (k-block, product) step ahead, the B fragments from LDS one step
+//     ahead inside a chunk; 12 MFMAs per step;
 //     step embedding + conv bias enter as one extra k-block per product (A = the fp32 correction row of the f32
 //     Winograd path split in registers, B = the Winograd transform of the in-range indicator: exact in bf16);
 //   * gate in registers, split, -> LDS gate tile [k-octet][term][64 columns]; the EXTRA instance adds the mel term and, in
 //     training (precision = "bf16x6"), saves the pre-activations H [B, 2C, L] for the gate adjoint as wavenet_wino.hip does;
-//   * GEMM2 [res; skip] = [Wr; Ws] g with the biases as an extra k-block;
+//   * GEMM2 [res; skip] = [Wr; Ws] g with the biases as an extra k-block; the last layer leaves the res row tile out;
 //   * epilogue: each wave transposes its row tiles through a private 8 KB LDS slot and moves them as row-major
 //     16-byte accesses: x' = (x + res) sqrt(.5) with x re-read (L2-hot: this tile staged it), skip += as load-add-store
 //     (one workgroup owns an element per layer, layers are stream-ordered).  The x / skip tiles are requested before
@@ -40,8 +45,8 @@ namespace dws {
 #define BX6_PF2 2   // 2-term split (6 MFMAs per step)
 #endif
 #define BX6_PF(NT) ((NT) == 2 ? BX6_PF2 : BX6_PF3)
-#ifndef BX6_T_PER_MFMA
-#define BX6_T_PER_MFMA 7   // transform instructions dealt out behind each MFMA of a chunk's first step
+#ifndef BX6_T_SLOTS
+#define BX6_T_SLOTS 0, 2, 3, 4, 6, 7, 9   // the 3-term split's placement of the transform units in a chunk's first step (do_step)
 #endif
 
 typedef float bx6_f32x4 __attribute__((ext_vector_type(4)));
@@ -192,8 +197,13 @@ struct Bx6Tile {
     static constexpr int TR_FLOATS = 32 * 64;     // a wave's transpose slot: one row tile x 64 columns
     static constexpr int LDS_FLOATS = MAIN_FLOATS + WAVES * TR_FLOATS;
     static constexpr int TITEMS = (KC / 4) * NP * 2;        // transform items: (4-channel group, column, product pair)
-    static_assert(C % 32 == 0 && S % C == 0 && C % KC == 0 && KC % 16 == 0 && KC % (2 * WAVES) == 0 &&
-                  (TITEMS % NTH == 0) && LDS_FLOATS * 4 <= 163840, "channel counts");
+    // 3-term split only: the 2-term instance at C = 256 holds three A-fragment sets in flight and sits at 253 registers, the
+    // asymmetric form's second loop body would push it into scratch
+    static constexpr bool HALVES = WAVES == 8 && NT == 3;   // raw chunks staged by alternating halves of the workgroup (see the kernel)
+    static constexpr int SW = HALVES ? WAVES / 2 : WAVES;   // waves that stage one chunk, a pair of adjacent rows per piece
+    static constexpr int NPIECE = KC / (2 * SW);
+    static_assert(C % 32 == 0 && S % C == 0 && C % KC == 0 && KC % 16 == 0 && KC % (2 * SW) == 0 && (SW & (SW - 1)) == 0 &&
+                  (!HALVES || NCB % 2 == 0) && (TITEMS % NTH == 0) && LDS_FLOATS * 4 <= 163840, "channel counts");
 };
 
 template <typename P, int C, int S, bool EXTRA>
@@ -271,7 +281,6 @@ __global__ __launch_bounds__(C * 2, (C >= 128 ? 2 : 1)) void wn_layer_bx6_kernel
     const bool al16 = (L % 4 == 0) && ((((size_t)a.x_in | (size_t)a.x_out | (size_t)a.skip) & 15) == 0);
     const bool contig = al16 && log2d <= 4;
     const bool x4 = contig || (al16 && log2d >= 2);
-    constexpr int RPW = KC / WAVES;                // channel rows per wave and chunk (as pairs of adjacent rows)
     __amdgpu_buffer_rsrc_t rXall = __builtin_amdgcn_make_buffer_rsrc((void*)xb, 0, C * L * 4, 0x00020000);
     const int pbase = (q0 >> log2d) << (log2d + 1);          // first position of the tile's block (d < 32: a multiple of 64)
     const int ob = contig ? 32 + (p - pbase) - dil : l31;    // shift s of this lane's column sits at ob + s * os in a staged row
@@ -308,12 +317,23 @@ __global__ __launch_bounds__(C * 2, (C >= 128 ? 2 : 1)) void wn_layer_bx6_kernel
     const int rot = __builtin_amdgcn_readfirstlane((int)((unsigned)tic % NCB));
 #endif
     auto chunk_of = [&](int cb) { const int c = cb + rot; return c >= NCB ? c - NCB : c; };
-    constexpr int NPIECE = RPW / 2;                // staging requests (row pairs) per wave and chunk
+    // Who stages a chunk.  Eight waves (two per SIMD: waves w and w + 4 share one): chunk cbi is staged by ONE half of the
+    // workgroup, waves 0..3 for even cbi and 4..7 for odd, twice the pieces each.  vmcnt retires in order, so the A fragments
+    // a wave requests behind its LDS-DMA pieces (x: nontemporal, HBM latency) cannot be consumed before those have landed;
+    // the partner wave on the same SIMD has no piece in front of its A stream in that chunk and keeps the matrix pipe busy
+    // meanwhile.  With every wave staging, both waves of every SIMD stood in that wait at the same time.  Fewer waves
+    // (C <= 128: one wave of a workgroup per SIMD, the neighbour is another workgroup at another point of its tile): all stage.
+    constexpr bool HALVES = T::HALVES;
+    constexpr int SW = T::SW;                      // waves that stage one chunk
+    constexpr int NPIECE = T::NPIECE;              // staging requests (row pairs) per staging wave and chunk
+    const int sw = HALVES ? (wave & (SW - 1)) : wave;
+    const int shalf = HALVES ? wave / SW : 0;
+    auto stages = [&](int cbi) { return !HALVES || (cbi & 1) == shalf; };
     auto stage_piece = [&](int cbi, int i) {
         float* xs = Xraw + (cbi & 1) * T::RAW_FLOATS;
         const int cb = chunk_of(cbi);
         {
-            const int cc = 2 * (wave + WAVES * i);
+            const int cc = 2 * (sw + SW * i);
             if (x4) {
                 __builtin_amdgcn_raw_ptr_buffer_load_lds(rXall, xs + cc * 128, 16, voffA, (cb * KC + cc) * L * 4, 0, BX6_NT);
             } else {
@@ -333,55 +353,85 @@ __global__ __launch_bounds__(C * 2, (C >= 128 ? 2 : 1)) void wn_layer_bx6_kernel
 
     // ---- transform pass: raw chunk c1 -> t_j = Winograd input transform, three bf16 terms each, in B-fragment order.
     // Item = (column, group of 4 channels, product pair): 12 LDS reads, 8 transforms, 8 splits, six 8-byte writes.
-    auto transform = [&](int c1) {
+    // No branch in it: the product pair jp of an item is wave-uniform, and a branch on it would cut the pass into basic
+    // blocks of its own in front of the MFMAs.  Pair 0 needs shifts (0, 1, 2), pair 1 shifts (1, 2, 3): the third read
+    // takes a selected address and the two forms differ by selects of the operands (d1 - d3 == d1 + (-d3) bit for bit).
+    // The pass is cut into T_UNITS units that the chunk loop deals out between the MFMAs of a step (do_step), per half
+    // h = 0, 1 of the item's four channels:  R_h: the six LDS reads of the half, issued together;  A_h, B_h: t_a, t_b of
+    // the half, split;  and last W: the LDS writes.  Order R0 A0 B0 R1 A1 B1 W: six raw values are live at a time.
+    constexpr int TK = T::TITEMS / NTH, T_UNITS = 7;
+    struct TState {
+        float d[TK][2][3];
+        v4 pa[TK][NT], pb[TK][NT];
+    };
+    auto transform_unit = [&](int c1, int u, TState& ts) __attribute__((always_inline)) {
         const float* xs = Xraw + (c1 & 1) * T::RAW_FLOATS;
         char* bo = Bop + (c1 & 1) * T::BOP_BYTES;
 #pragma unroll
-        for (int k = 0; k < T::TITEMS / NTH; ++k) {
+        for (int k = 0; k < TK; ++k) {
             const int i = tid + NTH * k;
             const int gi = __builtin_amdgcn_readfirstlane(i >> 6);      // wave-uniform part of the item number
             const int g4 = (gi * 2 + lhi) % (KC / 4);
             const int jp = __builtin_amdgcn_readfirstlane((gi * 2) / (KC / 4));   // KC/4 even: both halves of a wave share jp
-            float ta[4], tb[4];
+            const bool p1 = jp != 0;
+            const int h = u / 3, w = u % 3;          // half of the item, (R, A, B)
+            if (u == T_UNITS - 1) {
+                char* dst = bo + ((((g4 >> 1) * 4 + 2 * jp) * NT) * 32 + l31) * 16 + (g4 & 1) * 8;
 #pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                const float* xr = xs + (g4 * 4 + e) * 128 + ob;
-                const float d1 = xr[os], d2 = xr[2 * os];
-                if (jp == 0) {
-                    const float d0 = xr[0];
-                    ta[e] = d0 - d2; tb[e] = d1 + d2;
-                } else {
-                    const float d3 = xr[3 * os];
-                    ta[e] = d2 - d1; tb[e] = d1 - d3;
+                for (int t = 0; t < NT; ++t) {
+                    *reinterpret_cast<v4*>(dst + t * 512) = ts.pa[k][t];
+                    *reinterpret_cast<v4*>(dst + (NT + t) * 512) = ts.pb[k][t];
                 }
-            }
-            if (P::SCALED) {
+            } else if (w == 0) {
+                const int oa = p1 ? 3 * os : 0;
 #pragma unroll
-                for (int e = 0; e < 4; ++e) { ta[e] *= P::SX; tb[e] *= P::SX; }
-            }
-            v4 pa[NT], pb[NT];
-            P::split4(ta, pa);
-            P::split4(tb, pb);
-            char* dst = bo + ((((g4 >> 1) * 4 + 2 * jp) * NT) * 32 + l31) * 16 + (g4 & 1) * 8;
+                for (int e = 0; e < 2; ++e) {
+                    const float* xr = xs + (g4 * 4 + 2 * h + e) * 128 + ob;
+                    ts.d[k][e][0] = xr[oa];          // d0 (pair 0) or d3 (pair 1)
+                    ts.d[k][e][1] = xr[os];
+                    ts.d[k][e][2] = xr[2 * os];
+                }
+            } else {
+                float t4[4] = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-            for (int t = 0; t < NT; ++t) {
-                *reinterpret_cast<v4*>(dst + t * 512) = pa[t];
-                *reinterpret_cast<v4*>(dst + (NT + t) * 512) = pb[t];
+                for (int e = 0; e < 2; ++e) {
+                    const float da = ts.d[k][e][0], d1 = ts.d[k][e][1], d2 = ts.d[k][e][2];
+                    if (w == 1) t4[2 * h + e] = (p1 ? d2 : da) - (p1 ? d1 : d2);   // d0 - d2 | d2 - d1
+                    else t4[2 * h + e] = d1 + (p1 ? -da : d2);                     // d1 + d2 | d1 - d3
+                    if (P::SCALED) t4[2 * h + e] *= P::SX;
+                }
+                v4 q[NT];
+                P::split4(t4, q);                    // (element by element: the two unused ones fold away)
+#pragma unroll
+                for (int t = 0; t < NT; ++t)
+#pragma unroll
+                    for (int e = 2 * h; e < 2 * h + 2; ++e) {
+                        if (w == 1) ts.pa[k][t][e] = q[t][e];
+                        else ts.pb[k][t][e] = q[t][e];
+                    }
             }
         }
-        // The residual x of this wave's 32 output rows passes through the staging buffers exactly once: the wave keeps a
-        // copy in its (until the epilogue unused) transpose slot, row-major [row][64 columns] as the epilogue reads it --
-        // shifts 0 and +d of a staged row sit at floats 32..95 in both staging forms.  No second read of x from memory.
-        if (al16) {
-            const int ch0 = chunk_of(c1) * KC;
-            if (ch0 / 32 == wave) {
-                const int r0 = ch0 % 32;
+    };
+    auto transform = [&](int c1) {
+        TState ts;
 #pragma unroll
-                for (int i = 0; i < KC / 4; ++i) {
-                    const int rr = (lane >> 4) + 4 * i;
-                    const bx6_f32x4 v = *reinterpret_cast<const bx6_f32x4*>(xs + rr * 128 + 32 + 4 * (lane & 15));
-                    *reinterpret_cast<bx6_f32x4*>(trw + (r0 + rr) * 64 + 4 * (lane & 15)) = v;
-                }
+        for (int u = 0; u < T_UNITS; ++u) transform_unit(c1, u, ts);
+    };
+    // The residual x of this wave's 32 output rows passes through the staging buffers exactly once: the wave keeps a
+    // copy in its (until the epilogue unused) transpose slot, row-major [row][64 columns] as the epilogue reads it --
+    // shifts 0 and +d of a staged row sit at floats 32..95 in both staging forms.  No second read of x from memory.
+    // One wave per chunk has work here, so it is a branch, and it stands apart from the transform: in the chunk loop it
+    // runs ahead of step 1, where it splits no MFMA block that carries transform work.
+    auto keep_residual = [&](int c1) {
+        const int ch0 = chunk_of(c1) * KC;
+        if (al16 && ch0 / 32 == wave) {
+            const float* xs = Xraw + (c1 & 1) * T::RAW_FLOATS;
+            const int r0 = ch0 % 32;
+#pragma unroll
+            for (int i = 0; i < KC / 4; ++i) {
+                const int rr = (lane >> 4) + 4 * i;
+                const bx6_f32x4 v = *reinterpret_cast<const bx6_f32x4*>(xs + rr * 128 + 32 + 4 * (lane & 15));
+                *reinterpret_cast<bx6_f32x4*>(trw + (r0 + rr) * 64 + 4 * (lane & 15)) = v;
             }
         }
     };
@@ -402,8 +452,8 @@ __global__ __launch_bounds__(C * 2, (C >= 128 ? 2 : 1)) void wn_layer_bx6_kernel
 #endif
     };
 
-    stage_dma(0);
-    if (NCB > 1) stage_dma(1);
+    if (stages(0)) stage_dma(0);
+    if (NCB > 1 && stages(1)) stage_dma(1);
     // A fragments run PF (k-block, product) steps ahead of their use, in a ring of four register sets indexed by the
     // step number (compile time: the steps of a chunk are a multiple of four).  One step is 2 NPR MFMAs = 32 NPR matrix-pipe
     // cycles per wave: six products cover an L2 round trip with one step, three products need two.
@@ -413,10 +463,16 @@ __global__ __launch_bounds__(C * 2, (C >= 128 ? 2 : 1)) void wn_layer_bx6_kernel
     for (int s0 = 0; s0 < PF; ++s0) load_a1(a_ring[s0], chunk_of(0) * (KC / 16) + (s0 >> 2), s0 & 3);
     constexpr int NAF = PF * NA;              // A fragment loads in flight behind anything older
     // chunk 0 has landed (this wave's part; the barrier makes it everyone's): all but the loads issued after it -- chunk 1
-    // and the NAF A fragments.  hipcc does not make a barrier wait for LDS-DMA.
-    if (NCB > 1) {
-        if (x4) __builtin_amdgcn_s_waitcnt(0x0F70 | ((RPW / 2 + NAF) & 15) | (((RPW / 2 + NAF) >> 4) << 14));
-        else __builtin_amdgcn_s_waitcnt(0x0F70 | ((2 * RPW + NAF) & 15) | (((2 * RPW + NAF) >> 4) << 14));
+    // and the NAF A fragments.  hipcc does not make a barrier wait for LDS-DMA.  A piece is one request in the 16-byte
+    // forms and four dword requests otherwise.  By halves a wave holds pieces of ONE of the two chunks: the half that staged
+    // chunk 0 has only the A fragments behind it, the other half has no part in chunk 0 and nothing to wait for yet.
+    constexpr int P16 = NPIECE + NAF, P4 = 4 * NPIECE + NAF;
+    static_assert(P4 < 64, "vmcnt is a 6-bit counter");
+    if (HALVES) {
+        if (stages(0)) __builtin_amdgcn_s_waitcnt(0x0F70 | NAF);
+    } else if (NCB > 1) {
+        if (x4) __builtin_amdgcn_s_waitcnt(0x0F70 | (P16 & 15) | ((P16 >> 4) << 14));
+        else __builtin_amdgcn_s_waitcnt(0x0F70 | (P4 & 15) | ((P4 >> 4) << 14));
     } else {
         __builtin_amdgcn_s_waitcnt(0x0F70 | NAF);
     }
@@ -447,14 +503,22 @@ __global__ __launch_bounds__(C * 2, (C >= 128 ? 2 : 1)) void wn_layer_bx6_kernel
         }
     }
     transform(0);
-    __builtin_amdgcn_s_waitcnt(0x0F70 | NAF);  // chunk 1 has landed too (younger: only the NAF A fragments)
+    keep_residual(0);
+    __builtin_amdgcn_s_waitcnt(0x0F70 | NAF);  // chunk 1 has landed too (younger: only the NAF A fragments; either half)
     __syncthreads();                          // transformed chunk 0 visible, raw chunk 1 complete
 
     constexpr int SPC = (KC / 16) * 4;        // (k-block, product) steps per chunk
     // One (k-block, product) step: prefetch of the next step's A fragments, three B fragments from LDS, 12 MFMAs.
-    // WITH_T: the transform pass of the NEXT chunk rides in this step's MFMA stream -- its ~80 VALU / LDS instructions are
-    // dealt out between the 12 MFMAs (an MFMA holds the matrix pipe for 32 cycles; the wave issues other work meanwhile)
-    // instead of standing in front of them with the matrix pipe idle (both waves of a SIMD reach it at the same time).
+    // WITH_T (step 0 of every chunk but the last): the transform pass of the NEXT chunk rides in this step's MFMA stream.  It
+    // has no branch, so it shares the step's basic block, and its seven units stand in program order one behind every
+    // few MFMAs (T_SLOTS), each (MFMA, unit) slice fenced by sched_barrier: the reads of half an item go out behind one
+    // MFMA and return under the next ones (an MFMA holds the matrix pipe for 32 cycles; the wave issues other work
+    // meanwhile), instead of a chain of LDS round trips in front of the MFMAs with the matrix pipe idle (both waves of a
+    // SIMD reach it at the same time).  Step 1 starts with the one wave's residual copy of that chunk (keep_residual).
+    // the MFMA of the step (of 2 NPR) behind which each unit stands: a half's reads have one MFMA or more to return
+    constexpr int T_SLOTS[2][T_UNITS] = {{0, 1, 2, 2, 4, 5, 5}, {BX6_T_SLOTS}};   // [6 | 12 MFMAs per step]
+    constexpr bool B_AHEAD = !(C == 256 && NT == 2);   // (the 2-term instance at C = 256 has no registers left for the second set)
+    v8 bq_ring[2][NT];
     auto do_step = [&](int cb, auto ST, auto WITH_T) {
         constexpr int st = decltype(ST)::value;
         constexpr bool with_t = decltype(WITH_T)::value;
@@ -462,39 +526,43 @@ __global__ __launch_bounds__(C * 2, (C >= 128 ? 2 : 1)) void wn_layer_bx6_kernel
         constexpr int sn = (st + PF) % SPC, itn = sn >> 2, jn = sn & 3;
         const int cbn = cb + (st + PF) / SPC;
         const char* tb = Bop + (cb & 1) * T::BOP_BYTES + lhi * (4 * NT * 512) + l31 * 16;
-#if !defined(BX6_ABL_NO_STAGE) && defined(BX6_STAGE_SPREAD)
-        // (measured and NOT the default: the staging requests of chunk cb + 2 dealt out over the first SPC - PF steps instead
-        // of standing together behind the chunk barrier -- GEMM1 50.4 k -> 54.5 k cycles (f16x3), 76.0 k -> 83.0 k (bf16x6):
-        // an LDS-DMA request in the MFMA stream holds the wave's issue longer than it costs next to the barrier)
-        if (cb + 2 < NCB) {
-            constexpr int NS = (SPC - PF) < 1 ? 1 : (SPC - PF);
-#pragma unroll
-            for (int i = 0; i < NPIECE; ++i)
-                if (i * NS / NPIECE == st) stage_piece(cb + 2, i);
-        }
-#endif
+        if (st == 1 && cb + 1 < NCB) keep_residual(cb + 1);
         if (cbn < NCB) load_a1(a_ring[(st + PF) & 3], chunk_of(cbn) * (KC / 16) + itn, jn);   // (no load left in flight behind the last step)
         __builtin_amdgcn_sched_barrier(0);   // keep the prefetch PF whole steps ahead of its use
-        v8 bq[NT];
+        // B fragments one step ahead inside a chunk (the first step's cannot be asked for before the chunk barrier)
+        v8 (&bq)[NT] = bq_ring[st & 1];
+        if (st == 0 || !B_AHEAD) {
 #pragma unroll
-        for (int t = 0; t < NT; ++t) bq[t] = *reinterpret_cast<const v8*>(tb + ((2 * it * 4 + j) * NT + t) * 512);
-#ifndef BX6_ABL_NO_TRANSFORM
-        if (with_t) transform(cb + 1);
+            for (int t = 0; t < NT; ++t) bq[t] = *reinterpret_cast<const v8*>(tb + ((2 * it * 4 + j) * NT + t) * 512);
+        }
+        if (B_AHEAD && st + 1 < SPC) {
+            constexpr int it1 = (st + 1) >> 2, j1 = (st + 1) & 3;
+#pragma unroll
+            for (int t = 0; t < NT; ++t) bq_ring[(st + 1) & 1][t] = *reinterpret_cast<const v8*>(tb + ((2 * it1 * 4 + j1) * NT + t) * 512);
+            __builtin_amdgcn_sched_barrier(0);
+        }
+#if defined(BX6_ABL_NO_TRANSFORM)
+        constexpr bool ride = false;
+#elif defined(BX6_ABL_NO_INTERLEAVE)
+        constexpr bool ride = false;
+        if (with_t) { transform(cb + 1); __builtin_amdgcn_sched_barrier(0); }
+#else
+        constexpr bool ride = with_t;
 #endif
+        TState ts;
 #pragma unroll
         for (int t = 0; t < NPR; ++t)
 #pragma unroll
-            for (int m = 0; m < 2; ++m)
+            for (int m = 0; m < 2; ++m) {
                 acc[m][j] = P::mfma(a_ring[st & 3][m][P::ia(t)], bq[P::ib(t)], acc[m][j]);
-#ifndef BX6_ABL_NO_INTERLEAVE
-        if (with_t) {
+                if (ride) {
+                    const int i = 2 * t + m;
 #pragma unroll
-            for (int i = 0; i < 2 * NPR; ++i) {
-                __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);            // one MFMA
-                __builtin_amdgcn_sched_group_barrier(0x302, BX6_T_PER_MFMA * 6 / NPR, 0);   // then VALU / DS read / DS write of the transform
+                    for (int u = 0; u < T_UNITS; ++u)
+                        if (T_SLOTS[NPR == 3 ? 0 : 1][u] == i) transform_unit(cb + 1, u, ts);
+                    __builtin_amdgcn_sched_barrier(0);
+                }
             }
-        }
-#endif
     };
     auto do_steps_from1 = [&](int cb) {
         if constexpr (SPC == 4) {
@@ -513,15 +581,16 @@ __global__ __launch_bounds__(C * 2, (C >= 128 ? 2 : 1)) void wn_layer_bx6_kernel
     };
     static_assert((SPC == 4 || SPC == 8) && PF >= 1 && PF <= 3, "steps per chunk, prefetch distance");
     for (int cb = 0; cb < NCB; ++cb) {
-#if !defined(BX6_ABL_NO_STAGE) && !defined(BX6_STAGE_SPREAD)
-        if (cb + 2 < NCB) stage_dma(cb + 2);       // into the raw buffer chunk cb occupied (transformed an iteration ago)
+#ifndef BX6_ABL_NO_STAGE
+        if (cb + 2 < NCB && stages(cb + 2)) stage_dma(cb + 2);   // into the raw buffer chunk cb occupied (transformed an iteration ago)
 #endif
         if (cb + 1 < NCB) do_step(cb, std::integral_constant<int, 0>{}, std::true_type{});
         else do_step(cb, std::integral_constant<int, 0>{}, std::false_type{});
         do_steps_from1(cb);
         stamp(8 + 2 * cb);
         // transformed chunk cb+1 visible after the barrier; the LDS-DMA of chunk cb+2 must have landed too (hipcc does not
-        // count LDS-DMA among the accesses a barrier waits for): the only younger loads are the NAF A fragments of the next steps
+        // count LDS-DMA among the accesses a barrier waits for): the only younger loads are the NAF A fragments of the next steps.
+        // The same count serves a wave that staged nothing in this chunk: all it has in flight are those A fragments.
 #ifndef BX6_ABL_NO_DMA_WAIT     // (timing ablations, wrong results: no wait for the staged chunk / no chunk barrier / no staging)
         __builtin_amdgcn_s_waitcnt(0x0F70 | NAF);
 #endif
@@ -613,60 +682,67 @@ __global__ __launch_bounds__(C * 2, (C >= 128 ? 2 : 1)) void wn_layer_bx6_kernel
     // and its skip tiles, both column tiles
     __amdgpu_buffer_rsrc_t rA2 = __builtin_amdgcn_make_buffer_rsrc((void*)a.A2, 0, (C + S) * C * 2 * NT, 0x00020000);
     v8 c_cur[1 + MS][NT], c_nxt[1 + MS][NT];
-    auto load_a2 = [&](v8 (&dst)[1 + MS][NT], int kb) {
+    auto load_a2 = [&](v8 (&dst)[1 + MS][NT], int kb, int m0) {
 #pragma unroll
-        for (int m = 0; m < 1 + MS; ++m)
+        for (int m = m0; m < 1 + MS; ++m)
 #pragma unroll
             for (int t = 0; t < NT; ++t)
                 dst[m][t] = __builtin_bit_cast(v8, __builtin_amdgcn_raw_buffer_load_b128(rA2, lane16, ((mt2[m] * NKB + kb) * NT + t) * 1024, 0));
     };
     const int rot2 = rot * (KC / 16);          // the same rotation of the k-block order in GEMM2
     auto kblock_of = [&](int kb) { const int k = kb + rot2; return k >= NKB ? k - NKB : k; };
-    load_a2(c_cur, kblock_of(0));
+    // The last layer's residual output feeds nothing (`wavenet.py:165`; the epilogue does not store it): its row tile
+    // m = 0 -- A fragments, MFMAs, bias -- is left out there, by a wave-uniform choice between two instances of the loop.
     bx_f32x16 acc2[1 + MS][2];
-    {
-        const v8 bf = P::bvals(lhi ? 0.f : P::SG, 0.f);      // a row of ones, at the gate operand's scale
-        bx_f32x16 zero;
+    auto gemm2 = [&](auto WITH_RES) {
+        constexpr int M0 = decltype(WITH_RES)::value ? 0 : 1;
+        load_a2(c_cur, kblock_of(0), M0);
+        {
+            const v8 bf = P::bvals(lhi ? 0.f : P::SG, 0.f);      // a row of ones, at the gate operand's scale
+            bx_f32x16 zero;
 #pragma unroll
-        for (int r = 0; r < 16; ++r) zero[r] = 0.f;
+            for (int r = 0; r < 16; ++r) zero[r] = 0.f;
 #pragma unroll
-        for (int m = 0; m < 1 + MS; ++m) {
-            v8 af[NT];
-            P::rank2(av2[m] * ws2, 0.f, lhi == 0, af);
+            for (int m = M0; m < 1 + MS; ++m) {
+                v8 af[NT];
+                P::rank2(av2[m] * ws2, 0.f, lhi == 0, af);
 #pragma unroll
-            for (int n = 0; n < 2; ++n) {
-                acc2[m][n] = zero;
+                for (int n = 0; n < 2; ++n) {
+                    acc2[m][n] = zero;
 #pragma unroll
-                for (int t = NT - 1; t >= 0; --t) acc2[m][n] = P::mfma(af[t], bf, acc2[m][n]);
+                    for (int t = NT - 1; t >= 0; --t) acc2[m][n] = P::mfma(af[t], bf, acc2[m][n]);
+                }
             }
         }
-    }
-    __syncthreads();   // gate tile complete
-    stamp(4);
-    const char* gb = gt + lhi * (NT * 64 * 16) + l31 * 16;
+        __syncthreads();   // gate tile complete
+        stamp(4);
+        const char* gb = gt + lhi * (NT * 64 * 16) + l31 * 16;
 #pragma unroll 2
-    for (int kb = 0; kb < NKB; ++kb) {
-        const int kbn = (kb + 1 < NKB) ? kb + 1 : kb;
-        load_a2(c_nxt, kblock_of(kbn));
-        __builtin_amdgcn_sched_barrier(0);
-        const char* gk = gb + kblock_of(kb) * (2 * NT * 64 * 16);
-        v8 bq[2][NT];
+        for (int kb = 0; kb < NKB; ++kb) {
+            const int kbn = (kb + 1 < NKB) ? kb + 1 : kb;
+            load_a2(c_nxt, kblock_of(kbn), M0);
+            __builtin_amdgcn_sched_barrier(0);
+            const char* gk = gb + kblock_of(kb) * (2 * NT * 64 * 16);
+            v8 bq[2][NT];
 #pragma unroll
-        for (int n = 0; n < 2; ++n)
+            for (int n = 0; n < 2; ++n)
 #pragma unroll
-            for (int t = 0; t < NT; ++t) bq[n][t] = *reinterpret_cast<const v8*>(gk + (t * 64 + n * 32) * 16);
+                for (int t = 0; t < NT; ++t) bq[n][t] = *reinterpret_cast<const v8*>(gk + (t * 64 + n * 32) * 16);
 #pragma unroll
-        for (int t = 0; t < NPR; ++t)
+            for (int t = 0; t < NPR; ++t)
 #pragma unroll
-            for (int m = 0; m < 1 + MS; ++m)
+                for (int m = M0; m < 1 + MS; ++m)
 #pragma unroll
-                for (int n = 0; n < 2; ++n)
-                    acc2[m][n] = P::mfma(c_cur[m][P::ia(t)], bq[n][P::ib(t)], acc2[m][n]);
+                    for (int n = 0; n < 2; ++n)
+                        acc2[m][n] = P::mfma(c_cur[m][P::ia(t)], bq[n][P::ib(t)], acc2[m][n]);
 #pragma unroll
-        for (int m = 0; m < 1 + MS; ++m)
+            for (int m = M0; m < 1 + MS; ++m)
 #pragma unroll
-            for (int t = 0; t < NT; ++t) c_cur[m][t] = c_nxt[m][t];
-    }
+                for (int t = 0; t < NT; ++t) c_cur[m][t] = c_nxt[m][t];
+        }
+    };
+    if (last) gemm2(std::false_type{});
+    else gemm2(std::true_type{});
     stamp(5);
 
     // ---- epilogue

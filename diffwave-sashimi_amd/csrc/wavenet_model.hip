@@ -664,6 +664,14 @@ struct WaveNetModel : dws_model {
             DWS_HIP(hipStreamSynchronize(s));
             return DWS_OK;
         }
+        if (t == "hsave") {   // the gate pre-activations the last forward_train kept for the gate adjoint: [n_layers][B, 2C, L]
+            const size_t per = (size_t)B * 2 * C * L;
+            DWS_CHECK(!tH.empty() && tH[0].p, DWS_ERR_STATE, "tap 'hsave' before a forward_train");
+            DWS_CHECK(capacity >= (int64_t)(NL * per), DWS_ERR_INVALID, "tap buffer too small");
+            for (int n = 0; n < NL; ++n)
+                DWS_HIP(hipMemcpyAsync(dst + n * per, tH[n].p, per * 4, hipMemcpyDeviceToDevice, s));
+            return DWS_OK;
+        }
         if (t == "pre_final") {
             DWS_CHECK(capacity >= B * S * L, DWS_ERR_INVALID, "tap buffer too small");
             DWS_TRY(scratch_out.ensure((size_t)B * Cout * L * 4));

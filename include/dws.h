@@ -224,7 +224,8 @@ int dws_model_grad_ready_seq(dws_model* m, int32_t count, const char* const* nam
 
 /* Debug/parity tap: copy an internal activation into `dst` (device pointer,
  * `capacity` floats).  WaveNet: "pre_final" = ReLU(final_conv[0](skip)) [B,S,L],
- * "skip" [B,S,L], "x" (last residual output) [B,C,L]; the step-only terms: "part_t"
+ * "skip" [B,S,L], "x" (last residual output) [B,C,L], "hsave" [n_layers,B,2C,L] (the gate
+ * pre-activations kept by the last dws_model_forward_train); the step-only terms: "part_t"
  * [B, n_layers*C] / "abt" (per-clip rows of the last forward) and "tab_part_t"
  * [T, n_layers*C] / "tab_abt" (the sampler's step table).  Function-level taps of the last per-clip forward, both
  * models: "emb" [B, embed_dim_in] (`models/utils.py:20-27`), "emb_mlp" [B, embed_dim_out] (the two swish layers), "part_t"
