@@ -27,9 +27,71 @@ dws_model::~dws_model() {
         if (copy_consumed[i]) (void)hipEventDestroy(copy_consumed[i]);
         if (copy_pinned[i]) (void)hipHostFree(copy_pinned[i]);
     }
+    for (int i = 0; i < LABEL_SLOTS; ++i) {
+        if (label_consumed[i]) (void)hipEventDestroy(label_consumed[i]);
+        if (label_pinned[i]) (void)hipHostFree(label_pinned[i]);
+    }
     for (auto& g : grad_groups)
         if (g.ev) (void)hipEventDestroy(g.ev);
     for (auto* p : params) delete p;
+}
+
+int dws_model::set_classes(int32_t K) {
+    // (the table's adjoint runs one grid row per class: K + 1 <= 65535)
+    DWS_CHECK(K >= 1 && K <= 65534, DWS_ERR_INVALID, "dws_model_set_classes: n_classes = %d (needs 1 .. 65534)", K);
+    DWS_CHECK(!params_touched && n_classes == 0, DWS_ERR_STATE,
+              "dws_model_set_classes comes after dws_model_create and before the first set_param / commit, once");
+    DWS_CHECK(!label_param.empty(), DWS_ERR_UNSUPPORTED, "this backbone has no class conditioning");
+    dws::ParamSpec* p = add_param(label_param, {(int64_t)K + 1, (int64_t)d.diffusion_step_embed_dim_out});
+    DWS_TRY(p->buf.ensure(p->nbytes()));
+    DWS_HIP(hipMemset(p->buf.p, 0, p->nbytes()));
+    n_classes = K;
+    if (B > 0) DWS_TRY(reset_labels());
+    return DWS_OK;
+}
+
+int dws_model::reset_labels() {
+    if (n_classes == 0 || B <= 0) return DWS_OK;
+    DWS_HIP(hipDeviceSynchronize());      // (a shape change: nothing in flight may still read the old assignment)
+    DWS_TRY(labels_dev.ensure((size_t)B * 4));
+    std::vector<int32_t> h((size_t)B, n_classes);
+    DWS_HIP(hipMemcpy(labels_dev.p, h.data(), (size_t)B * 4, hipMemcpyHostToDevice));
+    labels_host.clear();
+    ++labels_version;
+    return DWS_OK;
+}
+
+int dws_model::set_labels(const int32_t* labels, int64_t nB, hipStream_t s) {
+    DWS_CHECK(n_classes > 0, DWS_ERR_INVALID, "dws_model_set_labels on a model without classes (dws_model_set_classes)");
+    DWS_CHECK(B > 0, DWS_ERR_STATE, "dws_model_set_labels before dws_model_prepare");
+    DWS_CHECK(nB == B, DWS_ERR_INVALID, "dws_model_set_labels: %lld labels for a prepared batch of %lld", (long long)nB, (long long)B);
+    if (labels)
+        for (int64_t b = 0; b < B; ++b)
+            DWS_CHECK(labels[b] >= 0 && labels[b] <= n_classes, DWS_ERR_INVALID,
+                      "dws_model_set_labels: labels[%lld] = %d (needs 0 .. %d, %d = the null class)", (long long)b, labels[b],
+                      n_classes, n_classes);
+    if (labels ? (labels_host.size() == (size_t)B && std::memcmp(labels_host.data(), labels, (size_t)B * 4) == 0)
+               : (labels_host.empty() && labels_dev.p))
+        return DWS_OK;     // the assignment already installed
+    DWS_CHECK(labels_dev.p && labels_dev.bytes >= (size_t)B * 4, DWS_ERR_STATE, "dws_model_set_labels: no label buffer");
+    // pinned staging, round robin with an event per slot: the host only ever waits for the upload made LABEL_SLOTS calls ago
+    const int slot = label_slot;
+    label_slot = (slot + 1) % LABEL_SLOTS;
+    if (!label_consumed[slot]) DWS_HIP(hipEventCreateWithFlags(&label_consumed[slot], hipEventDisableTiming));
+    else DWS_HIP(hipEventSynchronize(label_consumed[slot]));
+    if (label_pinned_cap[slot] < (size_t)B) {
+        if (label_pinned[slot]) (void)hipHostFree(label_pinned[slot]);
+        label_pinned[slot] = nullptr;
+        label_pinned_cap[slot] = (size_t)B * 2;
+        DWS_HIP(hipHostMalloc((void**)&label_pinned[slot], label_pinned_cap[slot] * 4, hipHostMallocDefault));
+    }
+    for (int64_t b = 0; b < B; ++b) label_pinned[slot][b] = labels ? labels[b] : n_classes;
+    DWS_HIP(hipMemcpyAsync(labels_dev.p, label_pinned[slot], (size_t)B * 4, hipMemcpyHostToDevice, s));
+    DWS_HIP(hipEventRecord(label_consumed[slot], s));
+    if (labels) labels_host.assign(labels, labels + B);
+    else labels_host.clear();
+    ++labels_version;
+    return DWS_OK;
 }
 
 void dws_model::drop_graph() {
@@ -41,6 +103,8 @@ void dws_model::drop_graph() {
     edit_graph = nullptr;
     if (prog_graph) hipGraphExecDestroy(prog_graph);
     prog_graph = nullptr;
+    if (cfg_graph) hipGraphExecDestroy(cfg_graph);
+    cfg_graph = nullptr;
 }
 
 dws::ParamSpec* dws_model::add_param(const std::string& name, std::vector<int64_t> shape, int dtype) {
@@ -257,6 +321,7 @@ int dws_model_set_param(dws_model* m, const char* name, const void* data, const 
                               want.c_str());
     }
     DWS_HIP(hipMemcpyAsync(p->buf.p, data, p->nbytes(), hipMemcpyDefault, (hipStream_t)stream));
+    m->params_touched = true;
     if (dtype == 1) ++m->int_params_version;
     m->dirty = true;
     m->drop_graph();
@@ -271,12 +336,35 @@ int dws_model_set_option(dws_model* m, const char* key, const char* value) {
 
 int dws_model_commit(dws_model* m, void* stream) {
     DWS_CHECK(m, DWS_ERR_INVALID, "null model");
+    m->params_touched = true;
     return m->commit((hipStream_t)stream);
 }
 
 int dws_model_prepare(dws_model* m, int64_t B, int64_t L) {
     DWS_CHECK(m, DWS_ERR_INVALID, "null model");
-    return m->prepare(B, L);
+    const int64_t B0 = m->B, L0 = m->L;
+    DWS_TRY(m->prepare(B, L));
+    if (m->n_classes > 0 && (B0 != m->B || L0 != m->L)) DWS_TRY(m->reset_labels());   // labels belong to a shape
+    return DWS_OK;
+}
+
+int dws_model_set_classes(dws_model* m, int32_t n_classes) {
+    DWS_CHECK(m, DWS_ERR_INVALID, "null model");
+    return m->set_classes(n_classes);
+}
+
+int dws_model_set_labels(dws_model* m, const int32_t* labels, int64_t B, void* stream) {
+    DWS_CHECK(m, DWS_ERR_INVALID, "null model");
+    return m->set_labels(labels, B, (hipStream_t)stream);
+}
+
+int dws_sampler_set_cfg(dws_model* m, int32_t on, float scale) {
+    DWS_CHECK(m, DWS_ERR_INVALID, "null model");
+    DWS_CHECK(!on || (scale == scale && scale - scale == 0.f), DWS_ERR_INVALID, "dws_sampler_set_cfg: scale = %g is not finite",
+              (double)scale);
+    m->cfg_on = on != 0;
+    m->cfg_scale = on ? scale : 0.f;
+    return DWS_OK;
 }
 
 int dws_model_set_condition(dws_model* m, const float* mel, int64_t Bm, int64_t Tmel, void* stream) {
@@ -365,6 +453,7 @@ int dws_model_update_params(dws_model* m, int32_t count, const char* const* name
         jobs[i] = {srcs[i], p->buf.f(), (int64_t)p->numel()};
     }
     DWS_TRY(multi_copy(m, jobs, (hipStream_t)stream));
+    m->params_touched = true;
     m->dirty = true;
     m->drop_graph();
     return DWS_OK;
@@ -435,6 +524,7 @@ int dws_sampler_run(dws_model* m, float* x, const float* alpha, const float* alp
                     int32_t T, const float* noise, uint64_t seed, int32_t init_from_seed, int32_t use_graph,
                     void* stream) {
     DWS_CHECK(m && x, DWS_ERR_INVALID, "dws_sampler_run: null argument");
+    DWS_CHECK(!m->cfg_on, DWS_ERR_UNSUPPORTED, "classifier-free guidance runs on dws_sampler_run_schedule only (dws_sampler_run)");
     return dws::sampler_run(m, x, alpha, alpha_bar, sigma, T, noise, seed, init_from_seed, use_graph,
                             (hipStream_t)stream);
 }
@@ -442,6 +532,7 @@ int dws_sampler_run(dws_model* m, float* x, const float* alpha, const float* alp
 int dws_sampler_steps(dws_model* m, float* x, const float* alpha, const float* alpha_bar, const float* sigma,
                       int32_t T, int32_t t_start, int32_t n_steps, uint64_t seed, int32_t use_graph, void* stream) {
     DWS_CHECK(m && x, DWS_ERR_INVALID, "dws_sampler_steps: null argument");
+    DWS_CHECK(!m->cfg_on, DWS_ERR_UNSUPPORTED, "classifier-free guidance runs on dws_sampler_run_schedule only (dws_sampler_steps)");
     return dws::sampler_steps(m, x, alpha, alpha_bar, sigma, T, t_start, n_steps, seed, use_graph,
                               (hipStream_t)stream);
 }
@@ -458,6 +549,7 @@ int dws_sampler_run_edit(dws_model* m, float* x, int32_t kind, int32_t S, const 
                          const float* noise, uint64_t seed, int32_t init_from_seed, int32_t use_graph,
                          const dws_sampler_edit* edit, void* stream) {
     DWS_CHECK(m && x && edit, DWS_ERR_INVALID, "dws_sampler_run_edit: null argument");
+    DWS_CHECK(!m->cfg_on, DWS_ERR_UNSUPPORTED, "classifier-free guidance runs on dws_sampler_run_schedule only (dws_sampler_run_edit)");
     return dws::sampler_run_schedule(m, x, kind, S, net_steps, coef, noise, seed, init_from_seed, use_graph, edit,
                                      nullptr, (hipStream_t)stream);
 }
@@ -467,6 +559,7 @@ int dws_sampler_run_program(dws_model* m, float* x, int32_t kind, int32_t S, con
                             uint64_t seed, int32_t init_from_seed, int32_t use_graph, const dws_sampler_edit* edit,
                             void* stream) {
     DWS_CHECK(m && x && edit, DWS_ERR_INVALID, "dws_sampler_run_program: null argument");
+    DWS_CHECK(!m->cfg_on, DWS_ERR_UNSUPPORTED, "classifier-free guidance runs on dws_sampler_run_schedule only (dws_sampler_run_program)");
     return dws::sampler_run_program(m, x, kind, S, net_steps, coef, V, visit_step, jump_coef, noise, seed,
                                     init_from_seed, use_graph, edit, (hipStream_t)stream);
 }

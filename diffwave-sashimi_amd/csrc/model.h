@@ -102,6 +102,12 @@ struct PrepBatch {
 };
 
 int launch_iota_f32(float* out, int n, hipStream_t s);   // wavenet_kernels.hip
+// class conditioning (wavenet_kernels.hip): out[r][:] = in[r / rep][:] + table[lab ? lab[r % nlab] : K][:], one fp32 add per
+// element (in place when rep == 1 and out == in); and its adjoint dtable[c][:] = sum over b with lab[b] == c of de[b][:], in
+// ascending b, rows of absent classes exactly zero
+int launch_label_add(const float* in, const float* table, const int32_t* lab, int nlab, int K, float* out, int rows, int rep,
+                     int E, hipStream_t s);
+int launch_label_grad(const float* de, const int32_t* lab, float* dtable, int B, int K, int E, hipStream_t s);
 
 // Key of a sampler step table: the step values it holds (null steps = t = 0..T-1), compared bit for bit.
 struct StepKey {
@@ -226,6 +232,33 @@ struct dws_model {
     hipGraphExec_t prog_graph = nullptr;
     SchKey prog_key{};
     uint64_t step_table_gen = 0;          // bumped by every step-table rebuild (build_step_table)
+    // classifier-free guidance in the schedule step (dws_sampler_set_cfg): the model is prepared for 2 Bc clips, the
+    // first half carries the wanted labels and the second the null class; the update runs on the first half alone.
+    // The guided step is a fourth graph beside the three above; the scale sits in the device state (word 6).
+    bool cfg_on = false;
+    float cfg_scale = 0.f;
+    hipGraphExec_t cfg_graph = nullptr;
+    SchKey cfg_key{};
+
+    // ---- class conditioning (dws_model_set_classes / dws_model_set_labels): one parameter "label_embedding.weight"
+    // [K+1][Eout] beside fc_t1 / fc_t2 (row K = the null class); a clip's row is added to the output of the embedding MLP,
+    // so the label enters the network through the per-block fc_t rows alone.
+    int n_classes = 0;                    // K (0: no class conditioning)
+    bool params_touched = false;          // a set_param / update_params / commit has run: set_classes comes too late
+    std::string label_param;              // the parameter's name in the state_dict layout of the backbone
+    dws::DevBuf labels_dev;               // int32 [B]; all K while no labels are installed
+    std::vector<int32_t> labels_host;     // what labels_dev holds (empty: the null class everywhere)
+    uint64_t labels_version = 0;          // bumped by every change of the assignment (step tables follow it)
+    static constexpr int LABEL_SLOTS = 4; // pinned staging of the upload, as the copy-job tables (COPY_SLOTS)
+    int32_t* label_pinned[LABEL_SLOTS] = {nullptr, nullptr, nullptr, nullptr};
+    size_t label_pinned_cap[LABEL_SLOTS] = {0, 0, 0, 0};
+    hipEvent_t label_consumed[LABEL_SLOTS] = {nullptr, nullptr, nullptr, nullptr};
+    int label_slot = 0;
+    bool labelled() const { return n_classes > 0 && !labels_host.empty(); }
+    const int32_t* labels_ptr() const { return static_cast<const int32_t*>(labels_dev.p); }
+    int set_classes(int32_t K);
+    int set_labels(const int32_t* labels, int64_t nB, hipStream_t s);
+    int reset_labels();                   // after a prepare to another shape: the null class for every clip (blocking)
     int64_t graphs_made = 0;              // tap "sampler_graphs": graphs instantiated by either entry point
 
     // ---- staged gradient hand-over (data-parallel overlap, dws_model_set_grad_sinks): the host names a destination and a

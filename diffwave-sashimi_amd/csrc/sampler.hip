@@ -608,6 +608,43 @@ __global__ void smp_qsample_kernel(float* __restrict__ x, const float* __restric
     }
 }
 
+// Classifier-free guidance (Ho & Salimans, 2021) between the network and the update of a guided step: eps [2 n] holds the
+// network output of the doubled state, the conditional half first; the first half becomes
+//   d = eps_c - eps_u;   g = scale * d;   eps = eps_c + g
+// each operation rounded once (contraction off, plain operators).  scale is word 6 of the sampler state (a float), so a new
+// scale replays the captured step.
+__global__ void smp_set_cfg_scale_kernel(int* st, float scale) { reinterpret_cast<float*>(st)[6] = scale; }
+
+template <bool VEC>
+__global__ void smp_cfg_kernel(float* __restrict__ eps, const int* __restrict__ st, size_t n) {
+#pragma clang fp contract(off)
+    const float scale = *reinterpret_cast<const volatile float*>(st + 6);
+    const float* __restrict__ eu = eps + n;
+    for (size_t g = (size_t)blockIdx.x * blockDim.x + threadIdx.x; g * 4 < n; g += (size_t)gridDim.x * blockDim.x) {
+        if (VEC) {
+            const float4 c = reinterpret_cast<const float4*>(eps)[g], u = reinterpret_cast<const float4*>(eu)[g];
+            float cv[4] = {c.x, c.y, c.z, c.w}, uv[4] = {u.x, u.y, u.z, u.w}, r[4];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const float d = cv[j] - uv[j];
+                const float gd = scale * d;
+                r[j] = cv[j] + gd;
+            }
+            reinterpret_cast<float4*>(eps)[g] = make_float4(r[0], r[1], r[2], r[3]);
+        } else {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const size_t i = g * 4 + j;
+                if (i >= n) break;
+                const float c = eps[i];
+                const float d = c - eu[i];
+                const float gd = scale * d;
+                eps[i] = c + gd;
+            }
+        }
+    }
+}
+
 // c1 = (1 - alpha) / sqrt(1 - alpha_bar), c2 = sqrt(alpha), sigma: [3][T]
 static std::vector<float> ddpm_table(const float* alpha, const float* alpha_bar, const float* sigma, int T) {
     std::vector<float> h(3 * (size_t)T);
@@ -757,14 +794,23 @@ struct ProgStep {
 
 // One reverse step of the schedule: forward at row *st of the step table, then the DDPM, DDIM or DPM-Solver++(2M) update
 // (with the replacement of the known region when `ed` is given; as a visit of a program when `pr` is given too).
+// cfg (no ed / pr): x is the doubled state [2 Bc, C, L]; the guided eps of the first half, the update over the first half's
+// elements alone and the mirror of the first half of the state into the second -- one linear chain.
 static int schedule_step(dws_model* m, float* x, int kind, int S, const float* noise, bool vec, const EditStep* ed,
-                         const ProgStep* pr, hipStream_t s) {
-    const size_t n = (size_t)m->B * m->d.out_channels * m->L;
+                         const ProgStep* pr, hipStream_t s, bool cfg = false) {
+    size_t n = (size_t)m->B * m->d.out_channels * m->L;
     int* st = static_cast<int*>(m->sch_state.p);
     m->step_idx = st;
     const int rc = m->forward(x, nullptr, m->smp_eps.f(), s);
     m->step_idx = nullptr;
     DWS_TRY(rc);
+    if (cfg) {
+        n /= 2;     // the conditional half: what the update below works on
+        ProfileScope prof("smp_cfg", s);
+        const int cb = (int)std::min<size_t>(ceil_div(n, 4 * 256), 4096);
+        if (vec) hipLaunchKernelGGL(smp_cfg_kernel<true>, dim3(cb), dim3(256), 0, s, m->smp_eps.f(), st, n);
+        else hipLaunchKernelGGL(smp_cfg_kernel<false>, dim3(cb), dim3(256), 0, s, m->smp_eps.f(), st, n);
+    }
     // dws_profile_enable("smp_update"): the update kernel of an uncaptured step, by kind
     ProfileScope prof(kind == DWS_SAMPLER_DDPM ? "smp_update_ddpm" : kind == DWS_SAMPLER_DDIM ? "smp_update_ddim"
                                                                                              : "smp_update_dpmpp2m", s);
@@ -814,6 +860,7 @@ static int schedule_step(dws_model* m, float* x, int kind, int S, const float* n
     else
         hipLaunchKernelGGL(smp_ddim_kernel<false>, dim3(blocks), dim3(256), 0, s, x, m->smp_eps.f(), m->sch_tables.f(),
                            st, noise, n, S);
+    if (cfg) DWS_HIP(hipMemcpyAsync(x + n, x, n * 4, hipMemcpyDeviceToDevice, s));   // the second half of the state follows the first
     return DWS_OK;
 }
 
@@ -873,8 +920,13 @@ int sampler_run_schedule(dws_model* m, float* x, int kind, int S, const float* n
     DWS_CHECK(m->B > 0, DWS_ERR_STATE, "sampler before dws_model_prepare");
     DWS_CHECK(m->d.in_channels == m->d.out_channels, DWS_ERR_INVALID,
               "sampler needs in_channels == out_channels (x and eps share a shape, `generate.py:52`)");
+    const bool cfg = m->cfg_on;
+    DWS_CHECK(!cfg || (!e && !pg), DWS_ERR_UNSUPPORTED, "classifier-free guidance is not built for editing or program runs");
+    DWS_CHECK(!cfg || m->B % 2 == 0, DWS_ERR_UNSUPPORTED,
+              "classifier-free guidance needs a model prepared for 2 x Bc clips (prepared batch: %lld)", (long long)m->B);
     if (m->dirty) DWS_TRY(m->commit(s));
-    const size_t n = (size_t)m->B * m->d.out_channels * m->L;
+    const size_t nfull = (size_t)m->B * m->d.out_channels * m->L;    // the network's batch
+    const size_t n = cfg ? nfull / 2 : nfull;                         // what the caller's x, the noise and the update span
 
     // update tables, keyed on their contents; DDIM's and DPM-Solver++'s are used as given
     std::vector<float> h = kind != DWS_SAMPLER_DDPM ? std::vector<float>(coef, coef + 5 * (size_t)S)
@@ -898,9 +950,9 @@ int sampler_run_schedule(dws_model* m, float* x, int kind, int S, const float* n
         DWS_TRY(m->sch_known.ensure(n * 4));
         DWS_TRY(m->sch_mask.ensure((n + 3) / 4 * 4));
     }
-    DWS_TRY(m->smp_eps.ensure(n * 4));
+    DWS_TRY(m->smp_eps.ensure(nfull * 4));
     m->smp_eps_B = m->B; m->smp_eps_L = m->L;
-    if (kind == DWS_SAMPLER_DPMPP2M) DWS_TRY(m->sch_hist.ensure(n * 4));   // the previous step's x0 (first use of this kind)
+    if (kind == DWS_SAMPLER_DPMPP2M) DWS_TRY(m->sch_hist.ensure(nfull * 4));   // the previous step's x0 (first use of this kind)
     DWS_TRY(m->build_step_table(S, net_steps, s));   // the network's step-only part at net_steps (kept while they stay)
     DWS_TRY(m->sch_state.ensure(32));                // step, finished blocks, seed (2 words), visit, history-valid word
     int* st = static_cast<int*>(m->sch_state.p);
@@ -965,6 +1017,60 @@ int sampler_run_schedule(dws_model* m, float* x, int kind, int S, const float* n
         return DWS_OK;
     };
 
+    if (cfg) {
+        // the doubled state lives in the model (sch_x), with and without a graph: x_T goes into both halves, x_0 comes out of
+        // the first.  The guided step is a graph of its own (cfg_graph) beside the plain one.
+        DWS_TRY(m->sch_x.ensure(nfull * 4));
+        float* xs = m->sch_x.f();
+        const bool vec = n % 4 == 0 && aligned(noise);
+        hipStream_t q = s;
+        if (use_graph) {
+            DWS_TRY(ensure_capture_stream(m));
+            q = m->smp_stream;
+            DWS_HIP(hipEventRecord(m->smp_ev_in, s));
+            DWS_HIP(hipStreamWaitEvent(q, m->smp_ev_in, 0));
+        }
+        if (init_from_seed)
+            hipLaunchKernelGGL(smp_fill_normal_kernel, dim3(blocks), dim3(256), 0, q, xs, n, seed, (uint32_t)S);
+        else
+            DWS_HIP(hipMemcpyAsync(xs, x, n * 4, hipMemcpyDeviceToDevice, q));
+        DWS_HIP(hipMemcpyAsync(xs + n, xs, n * 4, hipMemcpyDeviceToDevice, q));
+        DWS_TRY(begin(xs, q));
+        hipLaunchKernelGGL(smp_set_cfg_scale_kernel, dim3(1), dim3(1), 0, q, st, m->cfg_scale);
+        if (!use_graph) {
+            for (int i = 0; i < S; ++i) DWS_TRY(schedule_step(m, xs, kind, S, noise, vec, nullptr, nullptr, q, true));
+        } else {
+            const dws_model::SchKey key{m->B, m->L, S, kind, vec ? 1 : 0, m->sch_tables.p, noise, m->smp_eps.p, xs, st,
+                                        m->step_table_gen, nullptr, nullptr, nullptr, nullptr, 0, nullptr,
+                                        kind == DWS_SAMPLER_DPMPP2M ? m->sch_hist.p : nullptr};
+            if (!m->cfg_graph || !(key == m->cfg_key)) {
+                if (m->cfg_graph) hipGraphExecDestroy(m->cfg_graph);
+                m->cfg_graph = nullptr;
+                hipGraph_t graph = nullptr;
+                DWS_HIP(hipStreamBeginCapture(q, hipStreamCaptureModeThreadLocal));
+                int rc = schedule_step(m, xs, kind, S, noise, vec, nullptr, nullptr, q, true);
+                hipError_t err = hipStreamEndCapture(q, &graph);
+                if (rc != DWS_OK) {
+                    if (graph) hipGraphDestroy(graph);
+                    return rc;
+                }
+                DWS_HIP(err);
+                err = hipGraphInstantiate(&m->cfg_graph, graph, nullptr, nullptr, 0);
+                hipGraphDestroy(graph);
+                DWS_HIP(err);
+                ++m->graphs_made;
+                m->cfg_key = key;
+            }
+            for (int i = 0; i < S; ++i) DWS_HIP(hipGraphLaunch(m->cfg_graph, q));
+        }
+        DWS_HIP(hipMemcpyAsync(x, xs, n * 4, hipMemcpyDeviceToDevice, q));
+        if (use_graph) {
+            DWS_HIP(hipEventRecord(m->smp_ev_out, q));
+            DWS_HIP(hipStreamWaitEvent(s, m->smp_ev_out, 0));
+        }
+        DWS_HIP(hipGetLastError());
+        return DWS_OK;
+    }
     if (!use_graph) {
         const bool vec = n % 4 == 0 && aligned(x) && aligned(noise) && aligned(known_noise);
         if (init_from_seed)

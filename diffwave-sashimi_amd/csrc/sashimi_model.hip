@@ -227,6 +227,7 @@ struct SashimiModel : dws_model, S4Workspace {
         add_param("fc_t1.bias", {Emid});
         add_param("fc_t2.weight", {Eout, Emid});
         add_param("fc_t2.bias", {Eout});
+        label_param = "label_embedding.weight";   // registered by dws_model_set_classes
         // layer plan of `Sashimi.__init__` (sashimi.py:236-268)
         int H = D, L = d.L, idx = 0;
         for (int p : pool) {
@@ -735,7 +736,7 @@ struct SashimiModel : dws_model, S4Workspace {
     OutLN next_ln(Stage* st, const SLayer* next) {
         OutLN o;
         o.m = P(next->prefix + ".norm1.m"); o.s = P(next->prefix + ".norm1.s");
-        o.e = pt_base() + next->pt_off; o.e_stride = pt_bstride(); o.e_step = step_idx; o.e_tstride = pt_total;
+        o.e = pt_base() + next->pt_off; o.e_stride = pt_bstride(); o.e_step = step_idx; o.e_tstride = pt_tstride();
         o.y = st->y.f();
         return o;
     }
@@ -749,7 +750,7 @@ struct SashimiModel : dws_model, S4Workspace {
         if (l->log2m > 0) {
             if (!y_ready)
                 DWS_TRY(launch_ln(x, P(p + ".norm1.m"), P(p + ".norm1.s"), pt_base() + l->pt_off, pt_bstride(), st->y.f(), nB,
-                                  H, Ls, (size_t)Ls, s, step_idx, pt_total));
+                                  H, Ls, (size_t)Ls, s, step_idx, pt_tstride()));
             FftTables* t = tables[l->log2m];
             FftConvArgs fa{};
             fa.u = st->y.f(); fa.g = st->g.f(); fa.D = P(p + ".layer.D");
@@ -762,7 +763,7 @@ struct SashimiModel : dws_model, S4Workspace {
         if (l->seg) {
             if (!y_ready)
                 DWS_TRY(launch_ln(x, P(p + ".norm1.m"), P(p + ".norm1.s"), pt_base() + l->pt_off, pt_bstride(), st->y.f(), nB,
-                                  H, Ls, (size_t)Ls, s, step_idx, pt_total));
+                                  H, Ls, (size_t)Ls, s, step_idx, pt_tstride()));
             FftTables* t = tables[FFTCONV_SEG_LOG2M];
             FftConvSegArgs fa{};
             fa.u = st->y.f(); fa.g = st->g.f(); fa.D = P(p + ".layer.D");
@@ -775,7 +776,7 @@ struct SashimiModel : dws_model, S4Workspace {
             return run_tail(l, st, x, addend, next, s);
         }
         DWS_TRY(launch_ln(x, P(p + ".norm1.m"), P(p + ".norm1.s"), pt_base() + l->pt_off, pt_bstride(), st->U.f(), nB, H, Ls,
-                          (size_t)2 * Ls, s, step_idx, pt_total));
+                          (size_t)2 * Ls, s, step_idx, pt_tstride()));
         {
             ProfileScope ps("rocfft_r2c", s);
             DWS_TRY(fft.exec(0, 2 * Ls, nB * H, st->U.p, st->Uf.p, s));
@@ -876,35 +877,76 @@ struct SashimiModel : dws_model, S4Workspace {
     // everything of the forward that depends on the diffusion step only (`sashimi.py:287-289,151`; a1, a2 of SURVEY 8):
     // embedding -> MLP -> every block's fc_t as one stacked GEMV, for `rows` step values (one wave per output row: a row's
     // result does not depend on how many rows the launch carries)
-    int embed_rows(const float* steps, int rows, float* emb_, float* h1_, float* h2_, float* pt, hipStream_t s) {
+    // Class conditioning (n_classes > 0): the label row joins h2 = the MLP's output before the fc_t rows are formed --
+    // `lab` [nlab] the labels of the clips (null: the null class for every row), in place.
+    int embed_rows(const float* steps, int rows, float* emb_, float* h1_, float* h2_, float* pt, hipStream_t s,
+                   const int32_t* lab = nullptr, int nlab = 1) {
+        DWS_TRY(mlp_rows(steps, rows, emb_, h1_, h2_, s));
+        return label_fc_rows(h2_, rows, 1, h2_, lab, nlab, pt, s);
+    }
+
+    // embedding -> the two swish layers, for `rows` step values
+    int mlp_rows(const float* steps, int rows, float* emb_, float* h1_, float* h2_, hipStream_t s) {
         DWS_TRY(launch_step_embed(steps, freq.f(), emb_, rows, Ein / 2, s));
         DWS_TRY(launch_linear_rows(emb_, P("fc_t1.weight"), P("fc_t1.bias"), h1_, rows, Ein, Emid, 1, s));
-        DWS_TRY(launch_linear_rows(h1_, P("fc_t2.weight"), P("fc_t2.bias"), h2_, rows, Emid, Eout, 1, s));
-        DWS_TRY(launch_linear_rows(h2_, Wt_all.f(), bt_all.f(), pt, rows, Eout, pt_total, 0, s));
-        return DWS_OK;
+        return launch_linear_rows(h1_, P("fc_t2.weight"), P("fc_t2.bias"), h2_, rows, Emid, Eout, 1, s);
+    }
+
+    // e[r] = h2[r / rep] + table[label of clip r % nlab] into e_ (rows * rep rows; e_ == h2_ with rep == 1: in place; without
+    // classes e is h2 itself), then every block's fc_t row of every e row
+    int label_fc_rows(const float* h2_, int rows, int rep, float* e_, const int32_t* lab, int nlab, float* pt, hipStream_t s) {
+        if (n_classes == 0) return launch_linear_rows(h2_, Wt_all.f(), bt_all.f(), pt, rows, Eout, pt_total, 0, s);
+        DWS_TRY(launch_label_add(h2_, P(label_param), lab, nlab, n_classes, e_, rows * rep, rep, Eout, s));
+        return launch_linear_rows(e_, Wt_all.f(), bt_all.f(), pt, rows * rep, Eout, pt_total, 0, s);
     }
 
     // Step table of a sampler run (sampler.hip): every clip of a reverse step is at the same t (`generate.py:50`), so the
     // projections are evaluated once for t = 0..T-1 -- tab_pt [T][pt_total] -- and the captured step's LayerNorm / tail
     // kernels read row *step_idx: no embedding kernels in a replay.
-    DevBuf tab_steps, tab_emb, tab_h1, tab_h2, tab_pt;
+    // With labels installed (dws_model_set_labels) the rows are per (step, clip): tab_pt [T][B][pt_total], built from
+    // e[t, b] = h2[t] + table[y_b] (tab_e) by the same row kernel; the kernels get the matching batch / step strides.  A new
+    // assignment rewrites the rows in place: the buffers, and so the captured graphs, stay.
+    DevBuf de_raw;                        // class conditioning: d e [B][Eout] before the swish factor
+    DevBuf tab_steps, tab_emb, tab_h1, tab_h2, tab_pt, tab_e;
+    int tab_rep = 1;                      // rows per step: B with labels installed, else 1
+    bool tab_labelled = false;            // the rows carry an installed assignment (B = 1: one row per step as without one)
+    uint64_t tab_labels_version = 0;
     int tab_T = 0;
     uint64_t tab_version = ~0ull;
     StepKey tab_key;   // the step VALUES the table holds (same T with other steps must not reuse it)
     const float* pt_base() const { return step_idx ? tab_pt.f() : part_t.f(); }
-    int pt_bstride() const { return step_idx ? 0 : pt_total; }
+    int pt_bstride() const { return (step_idx && tab_rep == 1) ? 0 : pt_total; }
+    int pt_tstride() const { return tab_rep * pt_total; }
     int build_step_table(int T, const float* steps, hipStream_t s) override {
         if (dirty) DWS_TRY(commit(s));
-        if (tab_version == commit_version && tab_key.same(T, steps)) return DWS_OK;
+        const bool per_clip = labelled();
+        const int rep = per_clip ? (int)B : 1;
+        const int32_t* lab = per_clip ? labels_ptr() : nullptr;
+        if (tab_version == commit_version && tab_key.same(T, steps) && tab_rep == rep && tab_labelled == per_clip) {
+            if (n_classes == 0 || tab_labels_version == labels_version) return DWS_OK;
+            // a new label assignment at the same (B, S): the rows are rewritten in place, the graphs stay
+            // (no assignment installed: the rows hold the null class already)
+            if (per_clip) DWS_TRY(label_fc_rows(tab_h2.f(), T, rep, tab_e.f(), lab, (int)B, tab_pt.f(), s));
+            tab_labels_version = labels_version;
+            return DWS_OK;
+        }
         drop_graph();   // a captured step holds pointers into the old table
+        DWS_CHECK(T > 0 && (size_t)T * rep * ((size_t)pt_total + Eout) * 4 <= ((size_t)4 << 30), DWS_ERR_UNSUPPORTED,
+                  "sampler step table: T=%d x %d rows per step exceeds 4 GB", T, rep);
         tab_version = ~0ull;   // invalid until the rebuild has finished
         DWS_TRY(tab_steps.ensure((size_t)T * 4));
         DWS_TRY(tab_emb.ensure((size_t)T * Ein * 4));
         DWS_TRY(tab_h1.ensure((size_t)T * Emid * 4));
         DWS_TRY(tab_h2.ensure((size_t)T * Eout * 4));
-        DWS_TRY(tab_pt.ensure((size_t)T * pt_total * 4));
+        DWS_TRY(tab_pt.ensure((size_t)T * rep * pt_total * 4));
         DWS_TRY(tab_key.upload(T, steps, tab_steps.f(), s));   // steps[t] = float(t) when null, as `generate.py:50` feeds them
-        DWS_TRY(embed_rows(tab_steps.f(), T, tab_emb.f(), tab_h1.f(), tab_h2.f(), tab_pt.f(), s));
+        if (n_classes > 0) DWS_TRY(tab_e.ensure((size_t)T * rep * Eout * 4));   // tab_h2 stays label-free for the rewrites
+        // the MLP once per step, the label rows and the fc_t rows per step or, with labels, per (step, clip)
+        DWS_TRY(mlp_rows(tab_steps.f(), T, tab_emb.f(), tab_h1.f(), tab_h2.f(), s));
+        DWS_TRY(label_fc_rows(tab_h2.f(), T, rep, tab_e.f(), lab, (int)B, tab_pt.f(), s));
+        tab_labelled = per_clip;
+        tab_rep = rep;
+        tab_labels_version = labels_version;
         tab_T = T;
         tab_version = commit_version;
         ++step_table_gen;
@@ -916,10 +958,12 @@ struct SashimiModel : dws_model, S4Workspace {
         DWS_CHECK(B > 0, DWS_ERR_STATE, "forward before prepare");
         trained_fwd = false;   // this forward (eval call, or a step of the sampler) overwrites the activations a pending backward needs
         if (dirty) DWS_TRY(commit(s));
-        DWS_CHECK(!step_idx || (tab_T > 0 && tab_version == commit_version), DWS_ERR_STATE, "step-table forward without a current table");
+        DWS_CHECK(!step_idx || (tab_T > 0 && tab_version == commit_version && (tab_rep == 1 || tab_rep == (int)B)), DWS_ERR_STATE,
+                  "step-table forward without a current table");
         DWS_CHECK(step_idx || steps, DWS_ERR_INVALID, "forward: steps == null");
         n_tail_split = n_tail_f32 = 0;     // tap "split_launches": which arithmetic THIS forward's tails ran
-        if (!step_idx) DWS_TRY(embed_rows(steps, (int)B, emb.f(), h1.f(), h2.f(), part_t.f(), s));
+        if (!step_idx)
+            DWS_TRY(embed_rows(steps, (int)B, emb.f(), h1.f(), h2.f(), part_t.f(), s, n_classes > 0 ? labels_ptr() : nullptr, (int)B));
         std::vector<const float*> stack;  // LIFO skip stack (sashimi.py:293-307)
         const float* x = x_init.f();
         // execution order; a block whose successor is a fused block of the same stage also writes that block's S4 input
@@ -933,7 +977,7 @@ struct SashimiModel : dws_model, S4Workspace {
         bool y_ready = false;
         if (ln_fusion && first && first->kind == L_BLOCK && (first->log2m > 0 || first->seg) && init_conv_ln_supported(Cin)) {
             DWS_TRY(launch_init_conv_ln(audio, Wi.f(), P("init_conv.0.conv.bias"), P(first->prefix + ".norm1.m"),
-                                        P(first->prefix + ".norm1.s"), pt_base() + first->pt_off, pt_bstride(), step_idx, pt_total,
+                                        P(first->prefix + ".norm1.s"), pt_base() + first->pt_off, pt_bstride(), step_idx, pt_tstride(),
                                         x_init.f(), stages[first->stage]->y.f(), (int)B, Cin, D, (int)L, s));
             y_ready = true;
         } else {
@@ -1210,6 +1254,7 @@ struct SashimiModel : dws_model, S4Workspace {
         DWS_TRY(launch_step_embed(steps, freq.f(), emb.f(), nB, Ein / 2, s));
         DWS_TRY(launch_linear_rows(emb.f(), P("fc_t1.weight"), P("fc_t1.bias"), h1.f(), nB, Ein, Emid, 1, s, ta1.f()));
         DWS_TRY(launch_linear_rows(h1.f(), P("fc_t2.weight"), P("fc_t2.bias"), h2.f(), nB, Emid, Eout, 1, s, ta2.f()));
+        if (n_classes > 0) DWS_TRY(launch_label_add(h2.f(), P(label_param), labels_ptr(), nB, n_classes, h2.f(), nB, 1, Eout, s));
         DWS_TRY(launch_linear_rows(h2.f(), Wt_all.f(), bt_all.f(), part_t.f(), nB, Eout, pt_total, 0, s));
         bool ln1_done = false;      // this block's LN1 came out of the previous block's epilogue
         for (size_t i = 0; i < plan.size(); ++i) {
@@ -1579,7 +1624,11 @@ struct SashimiModel : dws_model, S4Workspace {
             unstack_fc_t.add(dbt_all.f() + l->pt_off, G(l->prefix + ".fc_t.bias"), (size_t)l->H);
         }
         DWS_TRY(unstack_fc_t.run(s));
-        DWS_TRY(launch_lin_bwd_x(dpt.f(), Wt_all.f(), ta2.f(), dh2.f(), nB, Eout, pt_total, lin_scratch, s));
+        // with classes also d e itself (before the swish factor), whose per-class sums are the label table's gradient
+        if (n_classes > 0) DWS_TRY(de_raw.ensure((size_t)B * Eout * 4));
+        DWS_TRY(launch_lin_bwd_x(dpt.f(), Wt_all.f(), ta2.f(), dh2.f(), nB, Eout, pt_total, lin_scratch, s,
+                                 n_classes > 0 ? de_raw.f() : nullptr));
+        if (n_classes > 0) DWS_TRY(launch_label_grad(de_raw.f(), labels_ptr(), G(label_param), nB, n_classes, Eout, s));
         DWS_TRY(launch_lin_bwd_w(dh2.f(), h1.f(), G("fc_t2.weight"), G("fc_t2.bias"), nB, Emid, Eout, s));
         DWS_TRY(launch_lin_bwd_x(dh2.f(), P("fc_t2.weight"), ta1.f(), dh1.f(), nB, Emid, Eout, lin_scratch, s));
         DWS_TRY(launch_lin_bwd_w(dh1.f(), emb.f(), G("fc_t1.weight"), G("fc_t1.bias"), nB, Ein, Emid, s));

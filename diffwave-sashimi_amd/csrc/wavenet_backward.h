@@ -22,7 +22,7 @@ int launch_weight_norm_bwd(const float* dW, const float* v, const float* g, floa
                            hipStream_t s);
 int launch_lin_bwd_w(const float* dy, const float* x, float* dW, float* db, int B, int K, int O, hipStream_t s);
 int launch_lin_bwd_x(const float* dy, const float* W, const float* pre, float* dx, int B, int K, int O, DevBuf& part,
-                     hipStream_t s);
+                     hipStream_t s, float* dx_raw = nullptr);
 
 // ---- MFMA adjoints (wavenet_backward_mfma.hip)
 struct TapConvArgs {

@@ -284,12 +284,15 @@ __global__ void lin_bwd_x_partial_kernel(const float* __restrict__ dy, const flo
     part[((size_t)z * gridDim.y + b) * K + k] = (a0 + a1) + (a2 + a3);
 }
 
+// dx_raw (optional): the sum before the swish factor, i.e. the gradient w.r.t. the layer's input itself (the class
+// table's adjoint reads it: d e of e = swish(pre) + table[y])
 __global__ void lin_bwd_x_finish_kernel(const float* __restrict__ part, const float* __restrict__ pre, float* __restrict__ dx,
-                                        int n, int nz) {
+                                        int n, int nz, float* __restrict__ dx_raw) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     float acc = 0.f;
     for (int z = 0; z < nz; ++z) acc += part[(size_t)z * n + i];
+    if (dx_raw) dx_raw[i] = acc;
     if (pre) {
         const float a = pre[i], sg = sigm(a);
         acc *= sg * (1.f + a * (1.f - sg));   // d/da [a sigmoid(a)]
@@ -298,11 +301,11 @@ __global__ void lin_bwd_x_finish_kernel(const float* __restrict__ part, const fl
 }
 
 int launch_lin_bwd_x(const float* dy, const float* W, const float* pre, float* dx, int B, int K, int O, DevBuf& part,
-                     hipStream_t s) {   // part: [nz][B][K] scratch owned by the model
+                     hipStream_t s, float* dx_raw) {   // part: [nz][B][K] scratch owned by the model
     const int ochunk = 128, nz = ceil_div(O, ochunk);
     DWS_TRY(part.ensure((size_t)nz * B * K * 4));
     hipLaunchKernelGGL(lin_bwd_x_partial_kernel, dim3(ceil_div(K, 128), B, nz), dim3(128), 0, s, dy, W, part.f(), K, O, ochunk);
-    hipLaunchKernelGGL(lin_bwd_x_finish_kernel, dim3(ceil_div(B * K, 256)), dim3(256), 0, s, part.f(), pre, dx, B * K, nz);
+    hipLaunchKernelGGL(lin_bwd_x_finish_kernel, dim3(ceil_div(B * K, 256)), dim3(256), 0, s, part.f(), pre, dx, B * K, nz, dx_raw);
     return DWS_OK;
 }
 

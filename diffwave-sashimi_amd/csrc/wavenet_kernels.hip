@@ -181,6 +181,45 @@ int launch_iota_f32(float* out, int n, hipStream_t s) {
     return DWS_OK;
 }
 
+// Class conditioning: the label row joins the output of the embedding MLP, e = swish(fc_t2(..)) + table[y].
+// Row r of `out` takes row r / rep of `in` (rep > 1: one MLP row per step shared by the clips of a labelled step table) and
+// the label of clip r % nlab (lab null: the null class K for every row).  One fp32 add per element.
+__global__ void label_add_kernel(const float* __restrict__ in, const float* __restrict__ table, const int32_t* __restrict__ lab,
+                                 int nlab, int K, float* __restrict__ out, int rows, int rep, int E) {
+    const int r = blockIdx.x;
+    if (r >= rows) return;
+    int y = lab ? lab[r % nlab] : K;
+    y = min(max(y, 0), K);     // (range-checked on the host; never index outside the table)
+    const float* src = in + (size_t)(r / rep) * E;
+    const float* row = table + (size_t)y * E;
+    for (int j = threadIdx.x; j < E; j += blockDim.x) out[(size_t)r * E + j] = src[j] + row[j];
+}
+
+int launch_label_add(const float* in, const float* table, const int32_t* lab, int nlab, int K, float* out, int rows, int rep,
+                     int E, hipStream_t s) {
+    if (rows <= 0) return DWS_OK;
+    hipLaunchKernelGGL(label_add_kernel, dim3(rows), dim3(128), 0, s, in, table, lab, nlab, K, out, rows, rep, E);
+    return DWS_OK;
+}
+
+// Its adjoint: dtable[c][j] = sum_{b : lab[b] == c} de[b][j], summed in ascending b (one fixed order); every row is written,
+// so the rows of classes absent from the batch come out exactly zero.
+__global__ void label_grad_kernel(const float* __restrict__ de, const int32_t* __restrict__ lab, float* __restrict__ dtable,
+                                  int B, int E) {
+    const int c = blockIdx.y;
+    const int j = blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= E) return;
+    float acc = 0.f;
+    for (int b = 0; b < B; ++b)
+        if (lab[b] == c) acc += de[(size_t)b * E + j];
+    dtable[(size_t)c * E + j] = acc;
+}
+
+int launch_label_grad(const float* de, const int32_t* lab, float* dtable, int B, int K, int E, hipStream_t s) {
+    hipLaunchKernelGGL(label_grad_kernel, dim3(ceil_div(E, 128), K + 1), dim3(128), 0, s, de, lab, dtable, B, E);
+    return DWS_OK;
+}
+
 int launch_step_embed(const float* steps, const float* freq, float* emb, int B, int half, hipStream_t s) {
     hipLaunchKernelGGL(step_embed_kernel, dim3(B), dim3(64), 0, s, steps, freq, emb, half);
     return DWS_OK;

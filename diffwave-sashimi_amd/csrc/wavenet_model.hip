@@ -60,6 +60,7 @@ struct WaveNetModel : dws_model {
     bool mfma_bwd = false;
     uint64_t commit_version = 0, bwd_pack_version = ~0ull;
     DevBuf ty, ta1, ta2, dxa, dxb, dskip, dgb, dHb, dresb, dyb, dWfold, dpt, dh2, dh1, demb, dWt_all, dbt_all;
+    DevBuf de_raw;                   // class conditioning: d e [B][Eout] before the swish factor
     bool trained_fwd = false;
 
     explicit WaveNetModel(const dws_model_desc& dd) {
@@ -108,6 +109,7 @@ struct WaveNetModel : dws_model {
         wn("final_conv.0.conv", {S, S, 1});
         add_param("final_conv.2.conv.weight", {Cout, S, 1});
         add_param("final_conv.2.conv.bias", {Cout});
+        label_param = "residual_layer.label_embedding.weight";   // registered by dws_model_set_classes
         A1.resize(NL); Wrs.resize(NL); A2.resize(NL); bias2.resize(NL);
         if (cond) { melW0.resize(NL); melW1.resize(NL); melWc.resize(NL); }
     }
@@ -391,13 +393,34 @@ struct WaveNetModel : dws_model {
     // everything of the forward that depends on the diffusion step only (`wavenet.py:153-155,89`; a1, a2 of SURVEY 8):
     // embedding -> MLP -> every layer's fc_t (one stacked GEMV) -> the layer kernels' correction fragments, for `rows`
     // step values.  Row results do not depend on how many rows a launch carries (one wave per output row).
+    // Class conditioning (n_classes > 0): the label row joins h2 = the MLP's output before the fc_t rows are formed --
+    // `lab` [nlab] the labels of the clips (null: the null class for every row), in place.
     int embed_rows(const float* steps, int rows, float* emb_, float* h1_, float* h2_, float* pt, void* abt, float* pre1,
-                   float* pre2, hipStream_t s) {
+                   float* pre2, hipStream_t s, const int32_t* lab = nullptr, int nlab = 1) {
+        DWS_TRY(mlp_rows(steps, rows, emb_, h1_, h2_, pre1, pre2, s));
+        return label_fc_rows(h2_, rows, 1, h2_, lab, nlab, pt, abt, s);
+    }
+
+    // embedding -> the two swish layers, for `rows` step values
+    int mlp_rows(const float* steps, int rows, float* emb_, float* h1_, float* h2_, float* pre1, float* pre2, hipStream_t s) {
         DWS_TRY(launch_step_embed(steps, freq.f(), emb_, rows, Ein / 2, s));
         DWS_TRY(launch_linear_rows(emb_, P("residual_layer.fc_t1.weight"), P("residual_layer.fc_t1.bias"), h1_, rows, Ein, Emid,
                                    1, s, pre1));
-        DWS_TRY(launch_linear_rows(h1_, P("residual_layer.fc_t2.weight"), P("residual_layer.fc_t2.bias"), h2_, rows, Emid, Eout,
-                                   1, s, pre2));
+        return launch_linear_rows(h1_, P("residual_layer.fc_t2.weight"), P("residual_layer.fc_t2.bias"), h2_, rows, Emid, Eout,
+                                  1, s, pre2);
+    }
+
+    // e[r] = h2[r / rep] + table[label of clip r % nlab] into e_ (rows * rep rows; e_ == h2_ with rep == 1: in place; without
+    // classes e is h2 itself), then the fc_t rows and correction fragments of every e row
+    int label_fc_rows(const float* h2_, int rows, int rep, float* e_, const int32_t* lab, int nlab, float* pt, void* abt,
+                      hipStream_t s) {
+        if (n_classes == 0) return fc_t_rows(h2_, rows, pt, abt, s);
+        DWS_TRY(launch_label_add(h2_, P(label_param), lab, nlab, n_classes, e_, rows * rep, rep, Eout, s));
+        return fc_t_rows(e_, rows * rep, pt, abt, s);
+    }
+
+    // every layer's fc_t on `rows` summed embeddings e [rows][Eout] and the layer kernels' correction fragments
+    int fc_t_rows(const float* h2_, int rows, float* pt, void* abt, hipStream_t s) {
         DWS_TRY(launch_linear_rows(h2_, Wt_all.f(), bt_all.f(), pt, rows, Eout, NL * C, 0, s));
         if (mfma_layer && bf16x3) DWS_TRY(launch_wn_bias_tap_bf16(Wd_all.f(), pt, b1_all.f(), abt, NL, rows, C, s));
         else if (wino_rows()) DWS_TRY(launch_wn_wino_bias(Wd_all.f(), pt, (float*)abt, NL, rows, C, s));
@@ -409,14 +432,36 @@ struct WaveNetModel : dws_model {
     // step-only part of the forward is evaluated ONCE for t = 0..T-1 (or the T step values a few-step sampler hands in)
     // -- tab_pt [T][NL*C], tab_abt [NL][T][abt_row] -- and the captured reverse step reads row *step_idx: no embedding
     // kernels in a replay.
-    DevBuf tab_steps, tab_emb, tab_h1, tab_h2, tab_pt, tab_abt;
+    // With labels installed (dws_model_set_labels) the rows are per (step, clip): tab_pt [T][B][NL*C], tab_abt
+    // [NL][T][B][abt_row], built from e[t, b] = h2[t] + table[y_b] (tab_e) by the same row kernels; the layer kernels get the
+    // matching batch / step strides.  A new assignment rewrites the rows in place: the buffers, and so the captured graphs, stay.
+    DevBuf tab_steps, tab_emb, tab_h1, tab_h2, tab_pt, tab_abt, tab_e;
+    int tab_rep = 1;                      // rows per step: B with labels installed, else 1
+    bool tab_labelled = false;            // the rows carry an installed assignment (B = 1: one row per step as without one)
+    uint64_t tab_labels_version = 0;
     int tab_T = 0;
     uint64_t tab_version = ~0ull;
     StepKey tab_key;   // the step VALUES the table holds (same T with other steps must not reuse it)
     int build_step_table(int T, const float* steps, hipStream_t s) override {
         if (dirty) DWS_TRY(commit(s));
-        if (tab_version == commit_version && tab_key.same(T, steps)) return DWS_OK;
+        const bool per_clip = labelled();
+        const int rep = per_clip ? (int)B : 1;
+        const int32_t* lab = per_clip ? labels_ptr() : nullptr;
+        if (tab_version == commit_version && tab_key.same(T, steps) && tab_rep == rep && tab_labelled == per_clip) {
+            if (n_classes == 0 || tab_labels_version == labels_version) return DWS_OK;
+            // a new label assignment at the same (B, S): the rows are rewritten in place, the graphs stay
+            // (no assignment installed: the rows hold the null class already)
+            if (per_clip) DWS_TRY(label_fc_rows(tab_h2.f(), T, rep, tab_e.f(), lab, (int)B, tab_pt.f(), tab_abt.p, s));
+            tab_labels_version = labels_version;
+            return DWS_OK;
+        }
         drop_graph();   // a captured step holds pointers into the old table
+        if (rep > 1) {
+            const size_t bytes = (size_t)T * rep * ((size_t)NL * C + (mfma_layer ? (size_t)NL * abt_row() : 0) + Eout) * 4;
+            DWS_CHECK(bytes <= ((size_t)4 << 30), DWS_ERR_UNSUPPORTED,
+                      "labelled sampler step table: T=%d x B=%d needs %.2f GB (limit 4 GB): sample fewer steps or clips at a time", T,
+                      rep, bytes / 1e9);
+        }
         {   // the table grows with T x layers x channels (0.06 GB at T = 200, C = 256; 0.3-0.6 GB at T = 1000): bounded, so that
             // a wrong T fails with a message instead of an allocation of whatever size it implies
             const size_t bytes = (size_t)T * ((size_t)NL * C + (mfma_layer ? (size_t)NL * abt_row() : 0) + Ein + Emid + Eout + 1) * 4;
@@ -427,15 +472,21 @@ struct WaveNetModel : dws_model {
         DWS_TRY(tab_emb.ensure((size_t)T * Ein * 4));
         DWS_TRY(tab_h1.ensure((size_t)T * Emid * 4));
         DWS_TRY(tab_h2.ensure((size_t)T * Eout * 4));
-        DWS_TRY(tab_pt.ensure((size_t)T * NL * C * 4));
+        DWS_TRY(tab_pt.ensure((size_t)T * rep * NL * C * 4));
+        if (n_classes > 0) DWS_TRY(tab_e.ensure((size_t)T * rep * Eout * 4));   // tab_h2 stays label-free for the rewrites
         if (mfma_layer) {
-            const size_t n = (size_t)NL * T * abt_row() * 4;
+            const size_t n = (size_t)NL * T * rep * abt_row() * 4;
             DWS_TRY(tab_abt.ensure(n));
             DWS_HIP(hipMemsetAsync(tab_abt.p, 0, n, s));   // unused k entries of the correction k-group stay zero
         }
         tab_version = ~0ull;   // invalid until the rebuild has finished
         DWS_TRY(tab_key.upload(T, steps, tab_steps.f(), s));   // steps[t] = float(t) when null, as `generate.py:50` feeds them
-        DWS_TRY(embed_rows(tab_steps.f(), T, tab_emb.f(), tab_h1.f(), tab_h2.f(), tab_pt.f(), tab_abt.p, nullptr, nullptr, s));
+        // the MLP once per step, the label rows and everything behind them per step or, with labels, per (step, clip)
+        DWS_TRY(mlp_rows(tab_steps.f(), T, tab_emb.f(), tab_h1.f(), tab_h2.f(), nullptr, nullptr, s));
+        DWS_TRY(label_fc_rows(tab_h2.f(), T, rep, tab_e.f(), lab, (int)B, tab_pt.f(), tab_abt.p, s));
+        tab_labelled = per_clip;
+        tab_rep = rep;
+        tab_labels_version = labels_version;
         tab_T = T;
         tab_version = commit_version;
         ++step_table_gen;
@@ -446,13 +497,14 @@ struct WaveNetModel : dws_model {
         DWS_CHECK(B > 0, DWS_ERR_STATE, "forward before prepare");
         if (dirty) DWS_TRY(commit(s));
         const bool tab = step_idx != nullptr && !train;
-        DWS_CHECK(!tab || (tab_T > 0 && tab_version == commit_version), DWS_ERR_STATE, "step-table forward without a current table");
+        DWS_CHECK(!tab || (tab_T > 0 && tab_version == commit_version && (tab_rep == 1 || tab_rep == (int)B)), DWS_ERR_STATE,
+                  "step-table forward without a current table");
         DWS_CHECK(tab || steps, DWS_ERR_INVALID, "forward: steps == null");
         float* xfirst = train ? tx[0].f() : x0.f();
         DWS_TRY(launch_init_conv(audio, Wi.f(), P("init_conv.0.conv.bias"), xfirst, (int)B, Cin, C, (int)L, s));
         if (!tab)
             DWS_TRY(embed_rows(steps, (int)B, emb.f(), h1.f(), h2.f(), part_t.f(), Abt.p, train ? ta1.f() : nullptr,
-                               train ? ta2.f() : nullptr, s));
+                               train ? ta2.f() : nullptr, s, n_classes > 0 ? labels_ptr() : nullptr, (int)B));
         const int arow = abt_row();
         for (int n = 0; n < NL; ++n) {
             const std::string p = "residual_layer.residual_blocks." + std::to_string(n);
@@ -463,8 +515,11 @@ struct WaveNetModel : dws_model {
             a.skip = skip.f();
             a.A1 = A1[n].f(); a.A2 = A2[n].f();
             if (tab) {
-                a.part_t = tab_pt.f() + (size_t)n * C; a.part_t_bstride = 0; a.part_t_tstride = NL * C;
-                a.Abt = mfma_layer ? tab_abt.f() + (size_t)n * tab_T * arow : nullptr; a.abt_bstride = 0; a.abt_tstride = arow;
+                // rows per step (one shared by every clip) or, with labels installed, per (step, clip)
+                const int pb = tab_rep > 1 ? NL * C : 0, ab = tab_rep > 1 ? arow : 0;
+                a.part_t = tab_pt.f() + (size_t)n * C; a.part_t_bstride = pb; a.part_t_tstride = tab_rep * NL * C;
+                a.Abt = mfma_layer ? tab_abt.f() + (size_t)n * tab_T * tab_rep * arow : nullptr; a.abt_bstride = ab;
+                a.abt_tstride = tab_rep * arow;
                 a.step_idx = step_idx;
             } else {
                 a.part_t = part_t.f() + (size_t)n * C; a.part_t_bstride = NL * C;
@@ -632,7 +687,11 @@ struct WaveNetModel : dws_model {
             unstack_fc_t.add(dbt_all.f() + (size_t)n * C, G(p + ".fc_t.bias"), (size_t)C);
         }
         DWS_TRY(unstack_fc_t.run(s));
-        DWS_TRY(launch_lin_bwd_x(dpt.f(), Wt_all.f(), ta2.f(), dh2.f(), nB, Eout, NL * C, lin_scratch, s));   // d(pre-activation 2)
+        // d(pre-activation 2); with classes also d e itself, whose per-class sums are the label table's gradient
+        if (n_classes > 0) DWS_TRY(de_raw.ensure((size_t)B * Eout * 4));
+        DWS_TRY(launch_lin_bwd_x(dpt.f(), Wt_all.f(), ta2.f(), dh2.f(), nB, Eout, NL * C, lin_scratch, s,
+                                 n_classes > 0 ? de_raw.f() : nullptr));
+        if (n_classes > 0) DWS_TRY(launch_label_grad(de_raw.f(), labels_ptr(), G(label_param), nB, n_classes, Eout, s));
         DWS_TRY(launch_lin_bwd_w(dh2.f(), h1.f(), G("residual_layer.fc_t2.weight"), G("residual_layer.fc_t2.bias"), nB, Emid,
                                  Eout, s));
         DWS_TRY(launch_lin_bwd_x(dh2.f(), P("residual_layer.fc_t2.weight"), ta1.f(), dh1.f(), nB, Emid, Eout, lin_scratch, s));
@@ -681,7 +740,8 @@ struct WaveNetModel : dws_model {
         struct { const char* name; const DevBuf* buf; size_t n; } small[] = {
             {"emb", &emb, (size_t)B * Ein}, {"emb_mlp", &h2, (size_t)B * Eout},
             {"part_t", &part_t, (size_t)B * NL * C}, {"abt", &Abt, mfma_layer ? (size_t)NL * B * abt_row() : 0},
-            {"tab_part_t", &tab_pt, (size_t)tab_T * NL * C}, {"tab_abt", &tab_abt, mfma_layer ? (size_t)NL * tab_T * abt_row() : 0}};
+            {"tab_part_t", &tab_pt, (size_t)tab_T * tab_rep * NL * C},
+            {"tab_abt", &tab_abt, mfma_layer ? (size_t)NL * tab_T * tab_rep * abt_row() : 0}};
         for (auto& e : small)
             if (t == e.name) {
                 DWS_CHECK(e.buf->p && e.n > 0 && capacity >= (int64_t)e.n, DWS_ERR_INVALID, "tap '%s': %zu floats, capacity %lld",

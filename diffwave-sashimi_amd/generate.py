@@ -216,7 +216,8 @@ def generate(rank, diffusion_cfg, model_cfg, dataset_cfg, ckpt_iter="max", n_sam
              ckpt_smooth=None, mel_path=None, mel_name=None, dataloader=None, exp_root="exp", seed=None,
              written=None, precision=None, sampler="ddpm", steps=None, eta=0.0, known_name=None, keep=None,
              start_name=None, start_step=None, start_noise=True, resample_jump=None, resample_n=None, spacing=None,
-             guide_name=None, guide_op=None, guide_clip=None, guide_factor=None, guide_scale=None):
+             guide_name=None, guide_op=None, guide_clip=None, guide_factor=None, guide_scale=None, label=None,
+             cfg_scale=None):
     """``generate.py:58-200``.  ``ckpt_iter`` may additionally be ``"init"``: seeded random weights
     (no checkpoint), for smoke runs without trained weights.  ``precision`` (not in the reference; CLI:
     ``+engine.precision=bf16x6|f16x3``): the engine's opt-in matrix arithmetic, see ``include/dws.h``.
@@ -243,8 +244,15 @@ def generate(rank, diffusion_cfg, model_cfg, dataset_cfg, ckpt_iter="max", n_sam
     its measurement is the wav low-passed and decimated by ``guide_factor``, default 2) and ``guide_scale`` (the
     guidance step, required: there is no default that fits every model and operator) runs Diffusion Posterior Sampling,
     ``sampling.sampling_guided`` -- a forward and a data-only backward of the network per step, every clip of the batch
-    guided by the same recording."""
+    guided by the same recording.
+
+    Class-conditional models (``model.n_classes = K``; not in the reference): ``label`` is a class index in 0..K (K = the
+    null class), a list of them cycled over the samples, or ``all`` (= 0..K-1 in turn); the wav names get ``_c{label}``.
+    ``cfg_scale`` adds classifier-free guidance (``sampling``'s ``cfg_scale``: twice the network batch per step); it needs
+    ``label`` and does not combine with the editing or restoration keys.  No trained class-conditional weights exist
+    here: what the samples sound like has not been measured."""
     from .models import construct_model
+    from .models.utils import check_n_classes
     from .sampling import (calc_diffusion_hyperparams, ddim_steps, declip_operator, logsnr_steps, lowpass_operator,
                            program_evaluations, repaint_program, sampling, sampling_aligned, sampling_ddim, sampling_dpmpp,
                            sampling_guided, spans_to_mask)
@@ -273,6 +281,32 @@ def generate(rank, diffusion_cfg, model_cfg, dataset_cfg, ckpt_iter="max", n_sam
             raise ValueError("generate.guide_name does not combine with the editing keys (known_name, start_name, "
                              "resample_jump)")
 
+    n_classes = check_n_classes(model_cfg.get("n_classes"))
+    labels_of = None        # the class of every sample, cycled
+    if label is not None:
+        if not n_classes:
+            raise ValueError("generate.label needs a class-conditional model (model.n_classes)")
+        if isinstance(label, str):
+            if label != "all":
+                raise ValueError(f"generate.label={label!r}: expected a class index, a list of them, or all")
+            labels_of = list(range(n_classes))
+        else:
+            labels_of = list(label) if isinstance(label, (list, tuple)) else [label]
+            if not labels_of or any(isinstance(v, bool) or not isinstance(v, int) or not 0 <= v <= n_classes
+                                    for v in labels_of):
+                raise ValueError(f"generate.label={label!r}: class indices are integers in 0..{n_classes} "
+                                 f"({n_classes} = the null class)")
+    if cfg_scale is not None:
+        if labels_of is None:
+            raise ValueError("generate.cfg_scale needs generate.label (classifier-free guidance steers towards a class)")
+        if isinstance(cfg_scale, (bool, str)) or not np.isfinite(float(cfg_scale)):
+            raise ValueError(f"generate.cfg_scale={cfg_scale!r}: expected a finite number")
+        if guide_name is not None:
+            raise ValueError("generate.cfg_scale does not combine with generate.guide_name (guided runs take "
+                             "generate.label alone)")
+        if known_name is not None or start_name is not None or resample_jump is not None:
+            raise ValueError("generate.cfg_scale does not combine with the editing keys (known_name, start_name, "
+                             "resample_jump)")
     if known_name is not None and not keep:
         raise ValueError("generate.known_name needs generate.keep: at least one [start, end) span of kept samples")
     if keep and known_name is None:
@@ -392,10 +426,15 @@ def generate(rank, diffusion_cfg, model_cfg, dataset_cfg, ckpt_iter="max", n_sam
     for i in range(n_samples // batch_size):
         s = None if seed is None else seed + 1000 * rank + i
         size = (batch_size, 1, audio_length)
+        if labels_of is not None:
+            edit["labels"] = [labels_of[(i * batch_size + b) % len(labels_of)] for b in range(batch_size)]
+            if cfg_scale is not None:
+                edit["cfg_scale"] = float(cfg_scale)
         if guide is not None:
             ddim = sampler == "ddim"
             out.append(sampling_guided(net, size, dh_train if ddim else dh, sampler=sampler, steps=steps if ddim else None,
-                                       eta=float(eta or 0.0) if ddim else 0.0, condition=mel, seed=s, **guide))
+                                       eta=float(eta or 0.0) if ddim else 0.0, condition=mel, seed=s,
+                                       labels=edit.get("labels"), **guide))
         elif sampler == "aligned":
             out.append(sampling_aligned(net, size, diffusion_cfg, condition=mel, seed=s, **edit))
         elif sampler == "ddim":
@@ -416,6 +455,8 @@ def generate(rank, diffusion_cfg, model_cfg, dataset_cfg, ckpt_iter="max", n_sam
         print(f"sampler {sampler}{note}: {n_evals} network evaluations per batch")
     for i in range(n_samples):
         outfile = "{}k_{}.wav".format(ckpt_iter // 1000, n_samples * rank + i)   # `generate.py:189`
+        if labels_of is not None:
+            outfile = outfile[:-4] + f"_c{labels_of[i % len(labels_of)]}.wav"
         wavwrite(os.path.join(output_directory, outfile), dataset_cfg["sampling_rate"],
                  generated_audio[i].squeeze().cpu().numpy().astype(np.float32))
         if written is not None:

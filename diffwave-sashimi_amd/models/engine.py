@@ -28,6 +28,7 @@ class _EngineTrainFn(torch.autograd.Function):
         B, _, L = audio.shape
         module._sync_params(L)
         module._prepare(B, L)
+        module._set_labels(module._call_labels, B)   # (handed over by EngineModule.forward; no tensor, no gradient)
         module._set_condition(mel_spec)      # conditional models: the conditioner's parameters get gradients too
         x = audio.detach().to(torch.float32).contiguous()
         out = torch.empty((B, module.out_channels, L), device=audio.device, dtype=torch.float32)
@@ -140,6 +141,9 @@ class EngineModule(nn.Module):
         self._mel_ref = None
         self._train_generation = 0
         self._mel_expanded = None
+        self.n_classes = 0            # class-conditional models (config key n_classes): set by the subclass
+        self._label_key = ()          # the label assignment the engine holds: () = the null class everywhere
+        self._call_labels = None
 
     # -- handle management ---------------------------------------------------
     def _desc(self):
@@ -153,6 +157,9 @@ class EngineModule(nn.Module):
             _lib.check(lib.dws_model_create(ctypes.byref(desc), ctypes.byref(h)))
             self._handle = h
             self._versions = {}
+            if self.n_classes:        # registers label_embedding.weight: before any parameter is handed over
+                _lib.check(lib.dws_model_set_classes(h, self.n_classes))
+            self._label_key = ()
         return self._handle
 
     def __del__(self):
@@ -222,6 +229,7 @@ class EngineModule(nn.Module):
             _lib.check(_lib.load().dws_model_prepare(self._ensure_handle(), B, L))
             self._shape = (B, L)
             self._mel_key = None
+            self._label_key = ()      # the engine resets the labels of another shape to the null class
 
     def _set_condition(self, mel_spec):
         lib = _lib.load()
@@ -242,6 +250,33 @@ class EngineModule(nn.Module):
         _lib.check(lib.dws_model_set_condition(h, mel.data_ptr(), mel.shape[0], mel.shape[2], _lib.current_stream()))
         self._mel_key, self._mel_ref = key, mel_spec
 
+    def _label_list(self, labels, B):
+        """``labels`` (None, or an integer tensor / sequence [B] on any device) as a tuple of ints in 0..K, checked."""
+        if labels is None:
+            return ()
+        if not self.n_classes:
+            raise ValueError("labels= on a model without classes (set model.n_classes)")
+        t = torch.as_tensor(labels).detach()
+        if t.is_floating_point() or t.is_complex() or t.dtype == torch.bool or t.dim() != 1 or t.numel() != B:
+            raise ValueError(f"labels must be an integer tensor [B={B}], got {t.dtype} {tuple(t.shape)}")
+        key = tuple(int(v) for v in t.cpu().tolist())
+        if any(v < 0 or v > self.n_classes for v in key):
+            raise ValueError(f"labels must lie in 0..{self.n_classes} ({self.n_classes} = the null class), got {list(key)}")
+        return key
+
+    def _set_labels(self, labels, B):
+        """Install the labels of the coming call (cached by content, as the mel is by identity).  None = the null class."""
+        key = self._label_list(labels, B)
+        if not self.n_classes or key == self._label_key:
+            return
+        lib = _lib.load()
+        if key:
+            arr = (ctypes.c_int32 * B)(*key)
+            _lib.check(lib.dws_model_set_labels(self._ensure_handle(), arr, B, _lib.current_stream()))
+        else:
+            _lib.check(lib.dws_model_set_labels(self._ensure_handle(), None, B, _lib.current_stream()))
+        self._label_key = key
+
     def _expand_mel(self, mel_spec, B):
         """One mel for B clips, [1, bands, Tmel] -> [B, bands, Tmel] (the training forward needs a mel per clip).  The
         expanded tensor is kept with the one it was made from, so that ``_set_condition`` recognises it call after call."""
@@ -254,8 +289,10 @@ class EngineModule(nn.Module):
         return kept[2]
 
     # -- reference surface -----------------------------------------------------
-    def forward(self, input_data, mel_spec=None):
+    def forward(self, input_data, mel_spec=None, labels=None):
         audio, diffusion_steps = input_data
+        if labels is not None and not self.n_classes:
+            raise ValueError("labels= on a model without classes (set model.n_classes)")
         if audio.device.type != "cuda":
             raise RuntimeError("libdws runs on the GPU only: move the model and inputs to cuda "
                                "(there is no CPU fallback)")
@@ -273,11 +310,13 @@ class EngineModule(nn.Module):
                 raise RuntimeError(f"diffusion_steps must hold B={B} entries, got {tuple(diffusion_steps.shape)}")
             if audio.requires_grad:
                 mel_spec = self._expand_mel(mel_spec, B)
+            self._call_labels = self._label_list(labels, B) or None
             return _EngineTrainFn.apply(self, audio, steps, mel_spec, *(self.parameters() if train_call else ()))
         with torch.no_grad():
             self._train_generation += 1      # an eval forward overwrites the activations of a pending training forward
             self._sync_params(L)
             self._prepare(B, L)
+            self._set_labels(labels, B)
             self._set_condition(mel_spec)
             x = audio.detach().to(torch.float32).contiguous()
             steps = diffusion_steps.detach().to(device=audio.device, dtype=torch.float32).reshape(-1).contiguous()

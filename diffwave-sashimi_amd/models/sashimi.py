@@ -10,7 +10,8 @@ import torch.nn as nn
 from .. import _lib
 from . import s4_init
 from .engine import EngineModule
-from .utils import ConvParams, LinearParams, ZeroConvParams, _uniform_, upsampler_params
+from .utils import (ConvParams, LinearParams, ZeroConvParams, _uniform_, check_n_classes, classes_suffix,
+                    upsampler_params)
 
 
 class _LNParams(nn.Module):
@@ -98,8 +99,10 @@ class Sashimi(EngineModule):
                  unconditional=False,
                  mel_upsample=[16, 16],
                  L=16000,
+                 n_classes=None,
                  **kwargs):
         super().__init__()
+        self.n_classes = check_n_classes(n_classes)
         self.in_channels, self.out_channels = in_channels, out_channels
         self.L, self.unet, self.d_model, self.n_layers = L, unet, d_model, n_layers
         self.expand, self.ff, self.pool = expand, ff, list(pool)
@@ -117,6 +120,8 @@ class Sashimi(EngineModule):
         self.init_conv = nn.ModuleList([ConvParams(in_channels, d_model, 1)])
         self.fc_t1 = LinearParams(diffusion_step_embed_dim_in, diffusion_step_embed_dim_mid)
         self.fc_t2 = LinearParams(diffusion_step_embed_dim_mid, eo)
+        if self.n_classes:   # class-conditional: e = swish(fc_t2(..)) + label_embedding.weight[y]; row n_classes = the null class
+            self.label_embedding = nn.Embedding(self.n_classes + 1, eo)
 
         def block(H, Ls):
             return _BlockParams(H, Ls, ff, eo, unconditional, self.mel_upsample)
@@ -218,7 +223,7 @@ class Sashimi(EngineModule):
     def name(cls, cfg):
         return "{}_d{}_n{}_pool_{}_expand{}_ff{}".format(
             "unet" if cfg["unet"] else "snet", cfg["d_model"], cfg["n_layers"], len(cfg["pool"]),
-            cfg["expand"], cfg["ff"])
+            cfg["expand"], cfg["ff"]) + classes_suffix(cfg)
 
     def __repr__(self):
         # the reference's __repr__ raises (`sashimi.py:316`: ''.join of ints, missing attribute)

@@ -16,6 +16,21 @@ def calc_diffusion_step_embedding(diffusion_steps, diffusion_step_embed_dim_in):
     return torch.cat((torch.sin(arg), torch.cos(arg)), 1)
 
 
+def check_n_classes(n_classes):
+    """Config key ``n_classes``: absent, null or 0 = no class conditioning (today's model exactly), else an integer K >= 1."""
+    if n_classes is None or (not isinstance(n_classes, bool) and n_classes == 0):
+        return 0
+    if isinstance(n_classes, bool) or int(n_classes) != n_classes or n_classes < 1:
+        raise ValueError(f"model.n_classes = {n_classes!r} (needs an integer >= 1, or null / 0 for none)")
+    return int(n_classes)
+
+
+def classes_suffix(cfg):
+    """``_cls{K}`` of a class-conditional model's run name, so that run directories do not collide."""
+    k = check_n_classes(cfg.get("n_classes") if hasattr(cfg, "get") else getattr(cfg, "n_classes", None))
+    return f"_cls{k}" if k else ""
+
+
 def _uniform_(t, fan_in):
     bound = 1.0 / math.sqrt(fan_in) if fan_in > 0 else 0.0
     with torch.no_grad():

@@ -8,7 +8,8 @@ import torch.nn as nn
 
 from .. import _lib
 from .engine import EngineModule
-from .utils import ConvParams, LinearParams, WNParams, ZeroConvParams, upsampler_params
+from .utils import (ConvParams, LinearParams, WNParams, ZeroConvParams, check_n_classes, classes_suffix,
+                    upsampler_params)
 
 
 class _ResidualBlockParams(nn.Module):
@@ -29,10 +30,12 @@ class _ResidualGroupParams(nn.Module):
     """Parameters of ``Residual_group`` (``models/wavenet.py:124-147``)."""
 
     def __init__(self, res_channels, skip_channels, num_res_layers, embed_in, embed_mid, embed_out,
-                 unconditional, mel_upsample):
+                 unconditional, mel_upsample, n_classes=0):
         super().__init__()
         self.fc_t1 = LinearParams(embed_in, embed_mid)
         self.fc_t2 = LinearParams(embed_mid, embed_out)
+        if n_classes:     # class-conditional: e = swish(fc_t2(..)) + label_embedding.weight[y]; row n_classes = the null class
+            self.label_embedding = nn.Embedding(n_classes + 1, embed_out)
         self.residual_blocks = nn.ModuleList(
             _ResidualBlockParams(res_channels, skip_channels, embed_out, unconditional, mel_upsample)
             for _ in range(num_res_layers))
@@ -46,8 +49,10 @@ class WaveNet(EngineModule):
                  diffusion_step_embed_dim_out=512,
                  unconditional=False,
                  mel_upsample=[16, 16],
+                 n_classes=None,
                  **kwargs):
         super().__init__()
+        self.n_classes = check_n_classes(n_classes)
         self.in_channels = in_channels
         self.out_channels = out_channels
         self.res_channels = res_channels
@@ -60,7 +65,7 @@ class WaveNet(EngineModule):
 
         self.init_conv = nn.ModuleList([ConvParams(in_channels, res_channels, 1)])
         self.residual_layer = _ResidualGroupParams(res_channels, skip_channels, num_res_layers,
-                                                   *self.embed_dims, unconditional, self.mel_upsample)
+                                                   *self.embed_dims, unconditional, self.mel_upsample, self.n_classes)
         # index 1 is the parameter-free ReLU of the reference's nn.Sequential (`wavenet.py:198-200`)
         self.final_conv = nn.ModuleList([ConvParams(skip_channels, skip_channels, 1), nn.Identity(),
                                          ZeroConvParams(skip_channels, out_channels)])
@@ -84,4 +89,4 @@ class WaveNet(EngineModule):
     @classmethod
     def name(cls, cfg):
         # the reference's classmethod reads an undefined `model_cfg` (`wavenet.py:216-220`); this is the intent
-        return "wnet_h{}_d{}".format(cfg["res_channels"], cfg["num_res_layers"])
+        return "wnet_h{}_d{}".format(cfg["res_channels"], cfg["num_res_layers"]) + classes_suffix(cfg)

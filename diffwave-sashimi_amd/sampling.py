@@ -32,16 +32,51 @@ def _host_table(t):
     return a, a.ctypes.data_as(ctypes.POINTER(ctypes.c_float))
 
 
-def _prepare_run(net, size, steps, condition, x_T, noise, seed):
-    """Shared set-up of the sampler entry points: the engine's parameters / shape / condition, the state tensor x
-    (x_T, or to be drawn on the device: init = 1), the injected noise [steps, B, C, L] and the seed."""
+def _check_labels(net, size, labels, cfg_scale, edit=None, resample=None):
+    """Argument checks of ``labels=`` / ``cfg_scale=`` before anything runs (ValueError).  Returns the labels as a tuple
+    of ints (() = none) and the guidance scale as a float (None = no classifier-free guidance)."""
+    if labels is None and cfg_scale is None:
+        return (), None         # (an unlabelled call: the network is not looked at here)
+    B = int(size[0])
+    n_classes = int(getattr(net, "n_classes", 0) or 0)
+    if labels is not None and not n_classes:
+        raise ValueError("sampler: labels= on a model without classes (set model.n_classes)")
+    key = net._label_list(labels, B) if labels is not None else ()
+    if cfg_scale is None:
+        return key, None
+    try:
+        scale = float(cfg_scale)
+    except (TypeError, ValueError):
+        raise ValueError(f"sampler: cfg_scale = {cfg_scale!r} (needs a number)")
+    if not np.isfinite(scale):
+        raise ValueError(f"sampler: cfg_scale = {cfg_scale!r} (needs a finite number)")
+    if labels is None:
+        raise ValueError("sampler: cfg_scale= needs labels= (classifier-free guidance steers towards a class)")
+    if resample is not None:
+        raise ValueError("sampler: cfg_scale= is not built for resampling runs (resample=)")
+    if edit is not None and any(v is not None for v in edit.values()):
+        raise ValueError("sampler: cfg_scale= is not built for editing runs (known / mask / x_start ...)")
+    return key, scale
+
+
+def _prepare_run(net, size, steps, condition, x_T, noise, seed, labels=(), cfg=False):
+    """Shared set-up of the sampler entry points: the engine's parameters / shape / condition / labels, the state tensor
+    x (x_T, or to be drawn on the device: init = 1), the injected noise [steps, B, C, L] and the seed.  ``cfg``: the
+    engine is prepared for 2 B clips -- the labels in the first half, the null class in the second -- while x and the
+    noise keep the caller's B."""
     B, C, L = size
     dev = torch.device("cuda")
     if seed is None:
         seed = int(torch.randint(0, 2 ** 63 - 1, (1,), dtype=torch.int64).item())
     net._train_generation += 1     # the sampler's forwards overwrite the activations of a pending training forward
     net._sync_params(L)
-    net._prepare(B, L)
+    nB = 2 * B if cfg else B
+    net._prepare(nB, L)
+    if cfg:
+        labels = tuple(labels) + (net.n_classes,) * B
+        if condition is not None and condition.dim() == 3 and condition.shape[0] == B and B > 1:
+            condition = torch.cat([condition, condition], dim=0)
+    net._set_labels(list(labels) if labels else None, nB)
     net._set_condition(condition)
     if x_T is None:
         x = torch.empty(size, device=dev, dtype=torch.float32)
@@ -259,8 +294,16 @@ def _check_edit(size, S, x_T, known=None, mask=None, known_noise=None, x_start=N
 
 def sampling(net, size, diffusion_hyperparams, condition=None, *, x_T=None, noise=None, seed=None,
              use_graph=True, net_steps=None, known=None, mask=None, known_noise=None, x_start=None, start_step=None,
-             start_noise=None, resample=None):
+             start_noise=None, resample=None, labels=None, cfg_scale=None):
     """``x_0 = sampling(net, (B, C, L), dh, condition)`` as in ``generate.py:23-55``.
+
+    Class-conditional models (``model.n_classes``; not in the reference), on every sampler of this module:
+      labels     integer tensor / list [B] in 0..K (K = the null class); default: the null class for every clip
+      cfg_scale  classifier-free guidance (Ho & Salimans, 2021): every step evaluates the network on the labelled and
+             on the null-class copy of the state and continues with ``eps_c + cfg_scale * (eps_c - eps_u)`` (0 = the
+             conditional run; costs a network of twice the batch).  Needs ``labels``; not built for the editing and
+             resampling arguments.  Goes through the schedule entry with ``net_steps = 0..T-1`` (bit-identical to
+             ``dws_sampler_run``).
 
     Extra keyword-only arguments (not in the reference):
       x_T    initial state [B,C,L]; default: drawn on the device from the Philox stream
@@ -291,17 +334,20 @@ def sampling(net, size, diffusion_hyperparams, condition=None, *, x_T=None, nois
     assert len(Alpha) == T and len(Alpha_bar) == T and len(Sigma) == T and len(size) == 3
     edit = dict(known=known, mask=mask, known_noise=known_noise, x_start=x_start, start_step=start_step,
                 start_noise=start_noise)
+    lab, scale = _check_labels(net, size, labels, cfg_scale, edit, resample)
     if resample is None and all(v is None for v in edit.values()):
         edit = None
+        if scale is not None and net_steps is None:
+            net_steps = np.arange(T, dtype=np.float32)
     elif net_steps is None:
         net_steps = np.arange(T, dtype=np.float32)
     if net_steps is not None:
         coef = np.stack([_host_table(Alpha)[0], _host_table(Alpha_bar)[0], _host_table(Sigma)[0]])
         return _run_schedule(net, size, _lib.DWS_SAMPLER_DDPM, net_steps, coef, condition, x_T, noise, seed, use_graph,
-                             edit=edit, levels=coef[1], resample=resample)
+                             edit=edit, levels=coef[1], resample=resample, labels=labels, cfg_scale=cfg_scale)
     lib = _lib.load()
     with torch.no_grad():
-        x, init, nz, seed = _prepare_run(net, size, T, condition, x_T, noise, seed)
+        x, init, nz, seed = _prepare_run(net, size, T, condition, x_T, noise, seed, labels=lab)
         a, pa = _host_table(Alpha)
         ab, pab = _host_table(Alpha_bar)
         sg, psg = _host_table(Sigma)
@@ -312,11 +358,12 @@ def sampling(net, size, diffusion_hyperparams, condition=None, *, x_T=None, nois
 
 
 def _run_schedule(net, size, kind, net_steps, coef, condition, x_T, noise, seed, use_graph, edit=None, levels=None,
-                  resample=None):
+                  resample=None, labels=None, cfg_scale=None):
     """``dws_sampler_run_schedule``: S steps s = S-1..0, the network at ``net_steps[s]``, update tables ``coef``.
     ``edit``: the editing arguments of ``sampling`` (-> ``dws_sampler_run_edit``), ``levels`` the run's alpha_bar.
     ``resample``: (jump, resamples) on top of ``edit`` (-> ``dws_sampler_run_program``)."""
     assert len(size) == 3
+    lab, scale = _check_labels(net, size, labels, cfg_scale, edit, resample)
     steps = np.ascontiguousarray(np.asarray(net_steps, dtype=np.float32).reshape(-1))
     S = steps.shape[0]
     coef = np.ascontiguousarray(np.asarray(coef, dtype=np.float32))
@@ -333,8 +380,17 @@ def _run_schedule(net, size, kind, net_steps, coef, condition, x_T, noise, seed,
     lib = _lib.load()
     fp = ctypes.POINTER(ctypes.c_float)
     with torch.no_grad():
-        x, init, nz, seed = _prepare_run(net, size, S if prog is None else len(prog), condition, x_T, noise, seed)
-        if edit is None:
+        x, init, nz, seed = _prepare_run(net, size, S if prog is None else len(prog), condition, x_T, noise, seed,
+                                         labels=lab, cfg=scale is not None)
+        if edit is None and scale is not None:
+            _lib.check(lib.dws_sampler_set_cfg(net._handle, 1, scale))
+            try:
+                _lib.check(lib.dws_sampler_run_schedule(net._handle, x.data_ptr(), kind, S, steps.ctypes.data_as(fp),
+                                                        coef.ctypes.data_as(fp), _lib.ptr(nz), seed, init,
+                                                        1 if use_graph else 0, _lib.current_stream()))
+            finally:
+                _lib.check(lib.dws_sampler_set_cfg(net._handle, 0, 0.0))
+        elif edit is None:
             _lib.check(lib.dws_sampler_run_schedule(net._handle, x.data_ptr(), kind, S, steps.ctypes.data_as(fp),
                                                     coef.ctypes.data_as(fp), _lib.ptr(nz), seed, init,
                                                     1 if use_graph else 0, _lib.current_stream()))
@@ -434,11 +490,11 @@ def ddim_coefficients(alpha_bar, tau, eta):
 
 def sampling_ddim(net, size, dh_train, steps, eta=0.0, condition=None, *, x_T=None, noise=None, seed=None,
                   use_graph=True, known=None, mask=None, known_noise=None, x_start=None, start_step=None,
-                  start_noise=None, resample=None):
+                  start_noise=None, resample=None, labels=None, cfg_scale=None):
     """DDIM over ``ddim_steps(T, steps)`` of the training schedule ``dh_train`` (``steps``: S or an explicit list),
     deterministic for ``eta = 0``.  ``noise``: injected z, [S, B, C, L] (``noise[s]`` is used after step s > 0).
-    The editing arguments and ``resample`` are those of ``sampling`` (levels: ``Alpha_bar[tau]``).  Not the reference's
-    loop."""
+    The editing arguments, ``resample``, ``labels`` and ``cfg_scale`` are those of ``sampling`` (levels:
+    ``Alpha_bar[tau]``).  Not the reference's loop."""
     tau = ddim_steps(dh_train["T"], steps)
     coef = ddim_coefficients(dh_train["Alpha_bar"], tau, eta)
     edit = dict(known=known, mask=mask, known_noise=known_noise, x_start=x_start, start_step=start_step,
@@ -447,7 +503,7 @@ def sampling_ddim(net, size, dh_train, steps, eta=0.0, condition=None, *, x_T=No
         edit = None
     return _run_schedule(net, size, _lib.DWS_SAMPLER_DDIM, np.asarray(tau, dtype=np.float32), coef, condition, x_T,
                          noise, seed, use_graph, edit=edit, levels=_host_table(dh_train["Alpha_bar"])[0][tau],
-                         resample=resample)
+                         resample=resample, labels=labels, cfg_scale=cfg_scale)
 
 
 def logsnr_steps(alpha_bar, S):
@@ -501,14 +557,15 @@ def dpmpp_coefficients(alpha_bar, tau):
 
 def sampling_dpmpp(net, size, dh_train, steps, condition=None, *, spacing="logsnr", x_T=None, seed=None,
                    use_graph=True, known=None, mask=None, known_noise=None, x_start=None, start_step=None,
-                   start_noise=None, resample=None, noise=None):
+                   start_noise=None, resample=None, noise=None, labels=None, cfg_scale=None):
     """DPM-Solver++(2M) over ``logsnr_steps(Alpha_bar, steps)`` of the training schedule ``dh_train``
     (``spacing="uniform"``: over ``ddim_steps(T, steps)``; ``steps``: S or an explicit list).  Second order at the cost
     of DDIM: one network evaluation per step, the previous step's data prediction kept on the device.  Deterministic:
     ``seed`` drives only a drawn ``x_T``, the known-region noise, the start noise and the jump noise; ``noise`` is
     accepted only together with ``resample`` ([V, B, C, L], of which the rows of jump visits are read).  The editing
     arguments and ``resample`` are those of ``sampling`` (levels: ``Alpha_bar[tau]``); the step after a jump and the
-    first step of a partial start are first order.  Not the reference's loop."""
+    first step of a partial start are first order.  ``labels`` / ``cfg_scale`` as in ``sampling``.  Not the reference's
+    loop."""
     if spacing not in ("logsnr", "uniform"):
         raise ValueError(f"sampling_dpmpp: spacing = {spacing!r} (expected 'logsnr' or 'uniform')")
     if noise is not None and resample is None:
@@ -522,7 +579,8 @@ def sampling_dpmpp(net, size, dh_train, steps, condition=None, *, spacing="logsn
     if resample is None and all(v is None for v in edit.values()):
         edit = None
     return _run_schedule(net, size, _lib.DWS_SAMPLER_DPMPP2M, np.asarray(tau, dtype=np.float32), coef, condition, x_T,
-                         noise, seed, use_graph, edit=edit, levels=ab[tau], resample=resample)
+                         noise, seed, use_graph, edit=edit, levels=ab[tau], resample=resample, labels=labels,
+                         cfg_scale=cfg_scale)
 
 
 def sampling_aligned(net, size, diffusion_cfg, condition=None, **kw):
@@ -610,7 +668,8 @@ def guided_coefficients(dh, sampler, steps=None, eta=0.0):
 
 
 def sampling_guided(net, size, diffusion_hyperparams, *, measurement, operator, scale, sampler="ddpm", steps=None,
-                    eta=0.0, condition=None, x_T=None, noise=None, seed=None, residuals=None, **unsupported):
+                    eta=0.0, condition=None, x_T=None, noise=None, seed=None, residuals=None, labels=None,
+                    **unsupported):
     """Restoration with a trained model by Diffusion Posterior Sampling (Chung et al., ICLR 2023): a reverse run whose
     every step is pulled towards a degraded recording ``measurement = operator(x0)``.  ``operator`` is any differentiable
     torch callable ``A(x0) -> measurement-shaped tensor`` (``declip_operator``, ``lowpass_operator``).  Per step s
@@ -638,7 +697,13 @@ def sampling_guided(net, size, diffusion_hyperparams, *, measurement, operator, 
     full backward runs.  The path has the limits of the training forward (precision f32 / bf16x6, no segmented S4
     stage); a mel ``[1, bands, Tmel]`` is expanded to the batch.  The loop runs eagerly, one step after the other with
     no graph capture: each step contains a backward.  Costs a forward plus a backward per step.  The editing arguments
-    (``known`` / ``mask`` ..., ``resample``) are not built for guided runs.  Not the reference's loop."""
+    (``known`` / ``mask`` ..., ``resample``) and ``cfg_scale`` are not built for guided runs; ``labels`` ([B], a
+    class-conditional model) are passed to every network call.  Not the reference's loop."""
+    if unsupported.get("cfg_scale") is not None:
+        raise ValueError("sampling_guided: cfg_scale= is not built for guided runs (labels= alone conditions the run)")
+    unsupported.pop("cfg_scale", None)
+    if labels is not None and not int(getattr(net, "n_classes", 0) or 0):
+        raise ValueError("sampling_guided: labels= on a model without classes (set model.n_classes)")
     if unsupported:
         known = {"known", "mask", "known_noise", "x_start", "start_step", "start_noise", "resample", "net_steps", "spacing"}
         bad = sorted(unsupported)
@@ -693,6 +758,8 @@ def sampling_guided(net, size, diffusion_hyperparams, *, measurement, operator, 
 
     x = draw(S) if x_T is None else x_T.detach().to(device=dev, dtype=torch.float32).clone()
     kw = {} if condition is None else {"mel_spec": condition}
+    if labels is not None:      # class-conditional model: every step's network call carries the labels
+        kw["labels"] = labels
     for s in range(S - 1, -1, -1):
         k1, k2, a, b, c, ddim = (float(v) for v in k[:, s])
         t = torch.full((B, 1), float(net_steps[s]), device=dev, dtype=torch.float32)

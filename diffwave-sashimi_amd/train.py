@@ -42,12 +42,17 @@ def fix_length(t, length):
 
 
 class SpeechCommands(torch.utils.data.Dataset):
-    """``dataloaders/sc.py:46-64``: items are ``(waveform[1,16000] in [-1,1), sample_rate, label)``."""
+    """``dataloaders/sc.py:46-64``: items are ``(waveform[1,16000] in [-1,1), sample_rate, label)``.
 
-    def __init__(self, path, length=16000):
-        self._path, self._length = path, length
+    ``classes``: the sorted names of the sub-folders that hold clips (SC09: ``eight .. zero``).  With
+    ``label_index=True`` (class-conditional training) the label of an item is its index in ``classes`` instead of
+    the folder name."""
+
+    def __init__(self, path, length=16000, label_index=False):
+        self._path, self._length, self._label_index = path, length, label_index
         walker = sorted(str(p) for p in Path(path).glob("**/*.wav"))
         self._walker = [w for w in walker if HASH_DIVIDER in w and EXCEPT_FOLDER not in w]
+        self.classes = sorted({os.path.split(os.path.relpath(w, path))[0] for w in self._walker})
 
     def __getitem__(self, n):
         from scipy.io import wavfile
@@ -62,6 +67,8 @@ class SpeechCommands(torch.utils.data.Dataset):
             x = x.astype(np.float32)
         if x.ndim == 2:
             x = x[:, 0]
+        if self._label_index:
+            label = self.classes.index(label)
         return fix_length(torch.from_numpy(x).unsqueeze(0), self._length), sr, label
 
     def __len__(self):
@@ -99,29 +106,39 @@ class LJSegments(torch.utils.data.Dataset):
 
 
 class SyntheticClips(torch.utils.data.Dataset):
-    """U(-0.3, 0.3) clips (SURVEY.md 8d's synthetic workload) with the sc09 item layout."""
+    """U(-0.3, 0.3) clips (SURVEY.md 8d's synthetic workload) with the sc09 item layout.  ``n_classes = K``
+    (class-conditional smoke runs): item n carries the label ``n % K``."""
 
-    def __init__(self, n_items, length, sampling_rate=16000, seed=0):
-        self.n, self.length, self.sr, self.seed = n_items, length, sampling_rate, seed
+    def __init__(self, n_items, length, sampling_rate=16000, seed=0, n_classes=0):
+        self.n, self.length, self.sr, self.seed, self.n_classes = n_items, length, sampling_rate, seed, n_classes
 
     def __getitem__(self, n):
         g = torch.Generator().manual_seed(self.seed * 1000003 + n)
-        return (torch.rand(1, self.length, generator=g) * 2 - 1) * 0.3, self.sr, "synthetic"
+        label = n % self.n_classes if self.n_classes else "synthetic"
+        return (torch.rand(1, self.length, generator=g) * 2 - 1) * 0.3, self.sr, label
 
     def __len__(self):
         return self.n
 
 
-def dataloader(dataset_cfg, batch_size, num_gpus, unconditional=True, rank=0, num_workers=4):
-    """``dataloaders/__init__.py:6-33``."""
+def dataloader(dataset_cfg, batch_size, num_gpus, unconditional=True, rank=0, num_workers=4, n_classes=0):
+    """``dataloaders/__init__.py:6-33``.  ``n_classes`` (a class-conditional model's ``model.n_classes``): items carry
+    the class index; sc09's folder count must match, ``ljspeech`` has no classes."""
     name = dataset_cfg.get("_name_", "sc09")
+    n_classes = int(n_classes or 0)
     if name == "sc09":
         assert unconditional
-        dataset = SpeechCommands(dataset_cfg["data_path"], dataset_cfg.get("segment_length", 16000))
+        dataset = SpeechCommands(dataset_cfg["data_path"], dataset_cfg.get("segment_length", 16000),
+                                 label_index=n_classes > 0)
+        if n_classes and len(dataset.classes) != n_classes:
+            raise ValueError(f"model.n_classes = {n_classes}, but {dataset_cfg['data_path']} holds {len(dataset.classes)} "
+                             f"class folders ({', '.join(dataset.classes)})")
     elif name == "synthetic":
         dataset = SyntheticClips(dataset_cfg.get("n_items", 64), dataset_cfg.get("segment_length", 16000),
-                                 dataset_cfg.get("sampling_rate", 16000))
+                                 dataset_cfg.get("sampling_rate", 16000), n_classes=n_classes)
     elif name == "ljspeech":
+        if n_classes:
+            raise ValueError("model.n_classes with dataset ljspeech: the dataset has no class labels")
         assert not unconditional
         dataset = LJSegments(**{k: v for k, v in dataset_cfg.items() if k != "_name_"})
     else:
@@ -161,18 +178,28 @@ def optim_param_groups(net, honour_hints=False):
 
 def train(rank, num_gpus, diffusion_cfg, model_cfg, dataset_cfg, generate_cfg, ckpt_iter, n_iters, iters_per_ckpt,
           iters_per_logging, learning_rate, batch_size_per_gpu, name=None, exp_root="exp", num_workers=4, precision=None,
-          honour_optim_hints=False):
-    """``train.py:49-196``."""
+          honour_optim_hints=False, label_dropout=None):
+    """``train.py:49-196``.  With ``model.n_classes`` (class-conditional; not in the reference) every batch's class
+    indices go to the network and ``label_dropout`` (``train.label_dropout``, default 0.1) of them are replaced by the
+    null class, which is what classifier-free guidance needs at sampling time; the in-loop ``generate`` cycles the
+    classes."""
     from .distributed_util import apply_gradient_allreduce, reduce_tensor
     from .models import construct_model
     from .sampling import calc_diffusion_hyperparams
     from .training import training_loss
+    from .models.utils import check_n_classes
 
+    n_classes = check_n_classes(model_cfg.get("n_classes"))
+    if label_dropout is not None and not n_classes:
+        raise ValueError("train.label_dropout needs model.n_classes")
+    label_dropout = float(0.1 if label_dropout is None else label_dropout) if n_classes else 0.0
+    if not 0.0 <= label_dropout < 1.0:
+        raise ValueError(f"train.label_dropout = {label_dropout!r} (needs 0 <= p < 1)")
     local_path, checkpoint_directory = local_directory(name, model_cfg, diffusion_cfg, dataset_cfg, "checkpoint", exp_root)
     log_path = os.path.join(exp_root, local_path, "train_log.jsonl")
     dh = calc_diffusion_hyperparams(**diffusion_cfg, fast=False)
     trainloader = dataloader(dataset_cfg, batch_size_per_gpu, num_gpus, unconditional=model_cfg["unconditional"],
-                             rank=rank, num_workers=num_workers)
+                             rank=rank, num_workers=num_workers, n_classes=n_classes)
     if len(trainloader) == 0:
         raise RuntimeError("the dataset holds fewer clips than one batch")
     print("Data loaded")
@@ -233,7 +260,10 @@ def train(rank, num_gpus, diffusion_cfg, model_cfg, dataset_cfg, generate_cfg, c
                 audio = (data.cuda() / MAX_WAV_VALUE).unsqueeze(1)
                 mel = stft.mel_spectrogram(audio[:, 0])
             optimizer.zero_grad()
-            loss = training_loss(net, loss_fn, audio, dh, mel_spec=mel)
+            if n_classes:    # (the labels stay on the host: the engine takes them from there, nothing waits for the GPU)
+                loss = training_loss(net, loss_fn, audio, dh, mel_spec=mel, labels=data[2], label_dropout=label_dropout)
+            else:
+                loss = training_loss(net, loss_fn, audio, dh, mel_spec=mel)
             reduced_loss = reduce_tensor(loss.data, num_gpus).item() if num_gpus > 1 else loss.item()
             loss.backward()
             optimizer.step()
@@ -249,6 +279,8 @@ def train(rank, num_gpus, diffusion_cfg, model_cfg, dataset_cfg, generate_cfg, c
                     if not model_cfg["unconditional"]:
                         assert generate_cfg.get("mel_name") is not None     # `train.py:170`
                     gen = dict(generate_cfg, ckpt_iter=n_iter)
+                    if n_classes:
+                        gen.setdefault("label", "all")      # the classes in turn over the batch
                     net.eval()
                     wavs = []
                     generate(rank, diffusion_cfg, model_cfg, dataset_cfg, name=name, exp_root=exp_root,

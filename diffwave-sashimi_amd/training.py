@@ -54,14 +54,27 @@ def q_sample(audio, diffusion_steps, Alpha_bar, z):
     return torch.sqrt(ab) * audio + torch.sqrt(1 - ab) * z
 
 
-def training_loss(net, loss_fn, audio, diffusion_hyperparams, mel_spec=None, generator=None):
+def training_loss(net, loss_fn, audio, diffusion_hyperparams, mel_spec=None, generator=None, labels=None,
+                  label_dropout=0.0):
     """``train.py:198-222``: ``t ~ U{0..T-1}``, ``z ~ N(0, I)``, ``loss_fn(net((x_t, t), mel), z)``.
     Steps and noise are drawn on the CPU generator exactly like the reference (then moved, through pinned staging
-    buffers so the host does not stall), so a seeded call consumes the RNG stream in the same order."""
+    buffers so the host does not stall), so a seeded call consumes the RNG stream in the same order.
+
+    ``labels`` (class-conditional models; not in the reference): integer tensor [B], handed to ``net(..., labels=)``.
+    ``label_dropout = p > 0`` trains the null class for classifier-free guidance: the clips where
+    ``torch.rand(B, generator=generator) < p`` get the null class ``net.n_classes``.  The mask is drawn after the draws
+    above and only when ``labels is not None and p > 0``: an unlabelled seeded run consumes the RNG as before."""
     T, Alpha_bar = diffusion_hyperparams["T"], diffusion_hyperparams["Alpha_bar"]
     B, C, L = audio.shape
     diffusion_steps = _stage(torch.randint(T, size=(B, 1, 1), generator=generator), audio.device, "steps")
     z = _stage(torch.normal(0, 1, size=audio.shape, generator=generator), audio.device, "z")
     x_t = q_sample(audio, diffusion_steps, Alpha_bar, z)
+    if labels is not None:
+        labels = torch.as_tensor(labels).detach().cpu().reshape(-1)     # (host side: the engine takes them from the host)
+        if label_dropout > 0:
+            drop = torch.rand(B, generator=generator) < label_dropout
+            labels = torch.where(drop, torch.full_like(labels, int(net.n_classes)), labels)
+        epsilon_theta = net((x_t, diffusion_steps.view(B, 1)), mel_spec=mel_spec, labels=labels)
+        return loss_fn(epsilon_theta, z)
     epsilon_theta = net((x_t, diffusion_steps.view(B, 1)), mel_spec=mel_spec)
     return loss_fn(epsilon_theta, z)

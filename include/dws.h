@@ -163,6 +163,28 @@ int dws_model_update_params(dws_model* m, int32_t count, const char* const* name
  *               = "direct" the direct three-tap form, forward and both adjoints (A/B runs). */
 int dws_model_set_option(dws_model* m, const char* key, const char* value);
 
+/* Class conditioning (class-conditional generation; not in the reference).  Call after dws_model_create and before the
+ * first set_param / update_params / commit (later: DWS_ERR_STATE).  n_classes = K in 1..65534 adds ONE parameter to num_params /
+ * param_info / set_param / update_params / get_grad(s) / gradient sinks: float32 [K+1, diffusion_step_embed_dim_out],
+ * "residual_layer.label_embedding.weight" (WaveNet) or "label_embedding.weight" (SaShiMi), beside fc_t1 / fc_t2.  Row K is
+ * the null class.  For clip b at step t_b with label y_b in 0..K
+ *     e_b = swish(fc_t2(swish(fc_t1(emb(t_b))))) + table[y_b]            (one fp32 add per element)
+ * and every block's fc_t runs on e_b: the label enters through the rows the layer kernels already read.  The path sits
+ * upstream of every precision switch (exact fp32 under bf16x6 too).  Backward: d table[c] = sum_{b : y_b = c} d e_b in
+ * ascending b; rows of classes absent from the batch are exactly zero; a data-only backward does not touch it.
+ * A model without this call is unchanged. */
+int dws_model_set_classes(dws_model* m, int32_t n_classes);
+
+/* The labels of the prepared batch: HOST int32[B], each in 0..K (checked before anything is enqueued; B must be the
+ * prepared batch), or NULL = the null class for every clip.  The upload goes through pinned staging (the host never waits
+ * for the GPU on it).  Labels hold until changed; a dws_model_prepare to another shape resets them to the null class.
+ * A model without classes -> DWS_ERR_INVALID.
+ * Samplers: with labels installed the step table holds rows per (step, clip) (WaveNet's correction fragments then take
+ * n_layers x T x B x row floats: 1.9 GB at 36 layers, T = 200, B = 32, C = 256) built from the summed embedding by the
+ * row kernels of the per-clip forward, so a labelled run is bit-equal to a loop of labelled forwards.  A new assignment at
+ * the same (B, S) rewrites the rows in place and replays the captured graphs (tap "sampler_graphs" does not move). */
+int dws_model_set_labels(dws_model* m, const int32_t* labels, int64_t B, void* stream);
+
 /* Fold / pack everything that depends only on the weights.  Called implicitly
  * by forward when parameters changed since the last commit. */
 int dws_model_commit(dws_model* m, void* stream);
@@ -366,6 +388,19 @@ typedef struct dws_sampler_edit {
 int dws_sampler_run_edit(dws_model* m, float* x, int32_t kind, int32_t S, const float* net_steps,
                          const float* coef, const float* noise, uint64_t seed, int32_t init_from_seed,
                          int32_t use_graph, const dws_sampler_edit* edit, void* stream);
+
+/* Classifier-free guidance (Ho & Salimans, 2021) inside the step of dws_sampler_run_schedule.  on != 0: the model is
+ * prepared for 2 Bc clips and carries labels[2 Bc] -- by convention the wanted classes in the first half and the null class
+ * in the second (the engine does not look at them) -- while x is [Bc, C, L] and noise [S, Bc, C, L].  The state is doubled
+ * inside the model; per step: (1) the network on the doubled state; (2) over the first half of eps, each operation rounded
+ * once, no contraction:   d = eps_c - eps_u;   g = scale * d;   eps = eps_c + g;   (3) the update kernel of the kind,
+ * unchanged, over the first half's Bc C L elements -- Philox element indices, injected noise rows and the multistep
+ * history are those of a plain Bc run (a drawn x_T is stream S over Bc C L elements); (4) a copy of the first half of the
+ * state into the second.  One linear chain of nodes; `scale` lives in the device state, so a new scale, seed, x or label
+ * set replays the graph (a graph of its own beside the others).  scale = 0 is the conditional run.
+ * While on: dws_sampler_run, _steps, _run_edit and _run_program, and an odd prepared batch, return DWS_ERR_UNSUPPORTED.
+ * on == 0 restores every other path bit for bit.  A non-finite scale -> DWS_ERR_INVALID. */
+int dws_sampler_set_cfg(dws_model* m, int32_t on, float scale);
 
 /* RePaint's resampling (Lugmayr et al., CVPR 2022) on the editing entry: a PROGRAM of V visits in place of the countdown
  * s0 .. 0, so that the chain can walk back up a few steps and down again and the generated part is harmonised with the
