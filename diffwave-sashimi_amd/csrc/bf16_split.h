@@ -13,6 +13,13 @@
 // What remains is the rounding of the fp32 accumulation itself, i.e. the error class of an fp32 GEMM.  Six bf16 MFMAs
 // cost 6/16 of the one exact-f32 MFMA they replace (MI355X: bf16 2.5 PFLOP/s, f32 157 TFLOP/s) and, unlike it, do
 // not occupy the VALU pipe.  tests/test_bf16x6_gpu.py measures both paths against a float64 evaluation.
+//
+// The same products can run on v_mfma_f32_16x16x32_bf16 (SplitBf16x3::mfma16): a quarter of the output tile at twice the K,
+// the same flops per cycle.  Its fragments are the SAME 16-byte items (8 consecutive k of one row / column) under another
+// lane -> item map: lane l holds row / column l & 15 and the k-octet l >> 4 of a 32-channel block, where the 32x32x16 form
+// holds row / column l & 31 and the octet l >> 5 of a 16-channel block; no operand is repacked for it (wavenet_bx6.hip).
+// One instruction then sums 32 channels where two summed 16 + 16: the results differ in the last bits, the error class
+// does not.  Under a power-limited clock the chip holds a higher clock on this shape (profiles/r08_ab_bx6_mfma_shape.txt).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -21,6 +28,7 @@ namespace dws {
 typedef __bf16 bx_bf16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bx_bf16x4 __attribute__((ext_vector_type(4)));
 typedef float bx_f32x16 __attribute__((ext_vector_type(16)));
+typedef float bx_f32x4 __attribute__((ext_vector_type(4)));
 
 __device__ __forceinline__ void split3(float x, __bf16& p0, __bf16& p1, __bf16& p2) {
     p0 = (__bf16)x;
@@ -76,13 +84,24 @@ struct SplitBf16x3 {
     __device__ static __forceinline__ bx_f32x16 mfma(const v8& a, const v8& b, const bx_f32x16& c) {
         return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
     }
+    // 16 x 16 output slice, K = 32: lane l holds row / column l & 15, k = 8 (l >> 4) .. + 7; D: row 4 (l >> 4) + reg, column l & 15
+    __device__ static __forceinline__ bx_f32x4 mfma16(const v8& a, const v8& b, const bx_f32x4& c) {
+        return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
+    }
     __device__ static __forceinline__ void split4(const float (&x)[4], v4 (&p)[3]) { split3x4(x, p[0], p[1], p[2]); }
     __device__ static __forceinline__ void split1(float x, v8 (&out)[3], int i) {
         __bf16 a, b, c;
         split3(x, a, b, c);
         out[0][i] = a; out[1][i] = b; out[2][i] = c;
     }
+    // (`lower_half`: the lanes that hold k = 0..7 -- lane >> 5 == 0 for the 32x32x16 shape, lane >> 4 == 0 for 16x16x32)
     __device__ static __forceinline__ void rank2(float v0, float v1, bool lower_half, v8 (&out)[3]) { frag_rank2(v0, v1, lower_half, out); }
+    // the same correction blocks for mfma16: the non-zero lanes are the first k-octet's, lane >> 4 == 0
+    __device__ static __forceinline__ void rank2_16(float v0, float v1, int lane, v8 (&out)[3]) { frag_rank2(v0, v1, (lane >> 4) == 0, out); }
+    __device__ static __forceinline__ v8 bvals_16(float v0, float v1, int lane) {
+        const bool k0 = (lane >> 4) == 0;
+        return bvals(k0 ? v0 : 0.f, k0 ? v1 : 0.f);
+    }
     __device__ static __forceinline__ void bits(float x, unsigned short (&b)[3]) {   // the terms as stored by the packers
         __bf16 p0, p1, p2;
         split3(x, p0, p1, p2);

@@ -84,8 +84,13 @@ int launch_wn_bias_tap_bf16(const float* Wd_all, const float* part_t, const floa
 //   WN_SPLIT_F16X3:  2 fp16 terms per operand, three products, power-of-two operand scaling (22 bits per operand)
 enum { WN_SPLIT_BF16X6 = 0, WN_SPLIT_F16X3 = 1 };
 inline int wn_split_terms(int split) { return split == WN_SPLIT_F16X3 ? 2 : 3; }
+// MFMA shape of the bf16x6 layer at C = S = 256 (every other instance runs 32x32x16 whatever is asked for):
+//   WN_BX6_MFMA_32: v_mfma_f32_32x32x16_bf16 throughout;  WN_BX6_MFMA_G2_16: GEMM2 on v_mfma_f32_16x16x32_bf16;  WN_BX6_MFMA_16: both GEMMs
+enum { WN_BX6_MFMA_32 = 0, WN_BX6_MFMA_G2_16 = 1, WN_BX6_MFMA_16 = 2 };
+constexpr int WN_BX6_MFMA_DEFAULT = WN_BX6_MFMA_16;   // what the A/B decided (profiles/r08_ab_bx6_mfma_shape.txt)
 bool wn_layer_bx6_supported(int C, int S);
-int launch_wn_layer_bx6(int C, int S, const WnLayerArgs& a, int split, hipStream_t s);
+bool wn_layer_bx6_mfma16_supported(int C, int S, int split);
+int launch_wn_layer_bx6(int C, int S, const WnLayerArgs& a, int split, int mfma, hipStream_t s);
 int launch_weight_scale(const float* w, size_t n, const float* bias, int nb, const float* bias_b, int nb_b, float* out, hipStream_t s);   // power of two bringing max(|w|, |bias|/1024) into [1, 2)
 int launch_pack_a1_bx6(const float* w, void* out, int C, int split, const float* scale, hipStream_t s);        // folded [2C][C][3] -> G0..G3 fragments
 int launch_pack_a_bx6(const float* w, void* out, int M, int K, int split, const float* scale, hipStream_t s);  // row-major [M][K] -> fragments

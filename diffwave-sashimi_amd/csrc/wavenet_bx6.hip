@@ -27,6 +27,19 @@
 //     (one workgroup owns an element per layer, layers are stream-ordered).  The x / skip tiles are requested before
 //     the gate stage.  Clips whose rows are not 16-byte aligned take a per-lane dword path.
 //
+// MFMA shape (template parameter MF; set_option("bx6_mfma") / DWS_BX6_MFMA; SplitBf16x3 at C = S = 256 only -- every other instance
+// has the 32x32x16 body above and nothing else).  "16x16x32", the default there: both GEMMs, the gate stage and the epilogue on
+// v_mfma_f32_16x16x32_bf16.  No operand is laid out differently: the packed weights, the transformed chunks, the gate tile and the
+// transpose slots keep their bytes, a fragment is the same 16-byte items under the lane map (row / column lane & 15, k-octet
+// lane >> 4 of a 32-channel block), the transform pass, the staging, the residual copy and every wait count are shared.  A 32 x 32
+// tile is four 16 x 16 slices (row half h, column half c) of four registers, row = 16 h + 4 (lane >> 4) + reg, col = 16 c + (lane & 15).
+// GEMM1 runs a chunk in eight half-steps (product, row tile) of 24 MFMAs, GEMM2 a 32-channel block in two.  The summation order per
+// output element is kept (correction block, chunks in rotated order, products in P::ia / ib order), but one instruction sums 32
+// channels where two summed 16 + 16: results differ in the last bits (tests/test_bx6_mfma_shape_gpu.py), deterministically and
+// independently of the clip's place in the batch.  The shape costs cycles (+ 4.9 % tile span) and wins wall time (- 1.8 % of the step):
+// the chip is power-capped under this kernel and holds 1970 instead of 1838 MHz on it (profiles/r08_ab_bx6_mfma_shape.txt).
+// "gemm2-16x16x32": GEMM2 and the epilogue only (measured: a third of the gain).  "32x32x16": the code as it was, instruction for instruction.
+//
 // Work per launch at C = S = 256, B = 16, L = 16000: 204.5 GFLOP of fp32-equivalent GEMM (the f32 Winograd kernel's
 // executed flops) = 1.227 PFLOP of bf16 MFMA = 0.49 ms at 2.5 PFLOP/s, against 1.30 ms at the fp32 matrix rate.
 #include <cstdlib>
@@ -206,9 +219,43 @@ struct Bx6Tile {
                   (!HALVES || NCB % 2 == 0) && (TITEMS % NTH == 0) && LDS_FLOATS * 4 <= 163840, "channel counts");
 };
 
-template <typename P, int C, int S, bool EXTRA>
+// MF: the MFMA shape.  BX6_MF_32: v_mfma_f32_32x32x16 in both GEMMs (every instance has it);  BX6_MF_G2_16: GEMM2 and the
+// epilogue on v_mfma_f32_16x16x32;  (SplitBf16x3, C = S = 256 only: the headline instances).
+//   BX6_MF_16: GEMM1 and the gate stage on it as well.
+enum { BX6_MF_32 = 0, BX6_MF_G2_16 = 1, BX6_MF_16 = 2 };
+#ifndef BX6_T16_SLOTS
+#define BX6_T16_SLOTS 1, 5, 7, 9, 13, 15, 19   // 16x16x32 GEMM1: the MFMA (of 24) of a chunk's first half-step behind which each transform unit stands
+#endif
+struct Bx6Nothing {};
+// state of the 16x16x32 GEMM2 (nothing at all in a 32x32x16 instance, so that those compile to the code they had)
+template <int MS>
+struct Bx6G2State {
+    float bias[1 + MS][2];              // the bias of row 16 h + r16 of each row tile
+    bx_f32x4 acc[1 + MS][2][2][2];      // [row tile][column tile n][row half h][column half c]
+};
+// the six A fragments of a GEMM1 half-step (row tile, product): [row half h][term], soff = the byte offset of term 0 of the
+// first of the block's two k-blocks
+template <int NT>
+__device__ __forceinline__ int bx6_voff_a1h(int lane) { return ((lane >> 5) * (4 * NT * 64) + ((lane >> 4) & 1) * 32 + (lane & 15)) * 16; }
+template <typename V8, int NT>
+__device__ __forceinline__ void bx6_load_a1h(V8 (&dst)[2][NT], __amdgpu_buffer_rsrc_t r, int voff, int soff) {
+#pragma unroll
+    for (int h = 0; h < 2; ++h)
+#pragma unroll
+        for (int t = 0; t < NT; ++t) dst[h][t] = __builtin_bit_cast(V8, __builtin_amdgcn_raw_buffer_load_b128(r, voff + h * 256, soff + t * 1024, 0));
+}
+// state of the 16x16x32 GEMM1
+template <typename V8, int NT>
+struct Bx6G1State {
+    float av[2][2][4], ab[2][2];        // correction rows of row 16 h + r16 of the two row tiles: [m][h][product], conv bias [m][h]
+    bx_f32x4 acc[2][4][2][2];           // [row tile m][product j][row half h][column half c]
+    V8 ar[2][2][NT];                    // A fragments, ring over the half-steps: [half-step & 1][h][term]
+    int pc[2];                          // first-half position of the lane's column 16 c + r16
+};
+template <typename P, int C, int S, bool EXTRA, int MF = BX6_MF_32>
 __global__ __launch_bounds__(C * 2, (C >= 128 ? 2 : 1)) void wn_layer_bx6_kernel(WnLayerArgs a, int log2d) {
     using T = Bx6Tile<C, S, P::NT>;
+    static_assert(MF == BX6_MF_32 || (P::NT == 3 && !P::SCALED && C == 256 && S == 256), "the 16x16x32 shape: bf16 split, C = S = 256");
     using v8 = typename P::v8;
     using v4 = typename P::v4;
     constexpr int NT = P::NT, NPR = P::NP, NA = 2 * P::NT;   // terms, products per term pair, A fragments per GEMM1 step
@@ -259,8 +306,26 @@ __global__ __launch_bounds__(C * 2, (C >= 128 ? 2 : 1)) void wn_layer_bx6_kernel
     mt2[0] = wave;
 #pragma unroll
     for (int m = 0; m < MS; ++m) mt2[1 + m] = C / 32 + wave * MS + m;
+    [[maybe_unused]] std::conditional_t<MF >= BX6_MF_16, Bx6G1State<v8, NT>, Bx6Nothing> gs1;
+    if constexpr (MF >= BX6_MF_16) {
+        const float* Abt = a.Abt + (size_t)b * a.abt_bstride + step_row_off(a.step_idx, a.abt_tstride);
+#pragma unroll
+        for (int m = 0; m < 2; ++m)
+#pragma unroll
+            for (int h = 0; h < 2; ++h) {
+                const int row = (m ? C / 32 + wave : wave) * 32 + 16 * h + (lane & 15);
+#pragma unroll
+                for (int j = 0; j < 4; ++j) gs1.av[m][h][j] = Abt[j * 2 * C + row];
+                gs1.ab[m][h] = a.bias1[row];
+            }
+#pragma unroll
+        for (int c = 0; c < 2; ++c) {
+            const int qc = q0 + 16 * c + (lane & 15);
+            gs1.pc[c] = ((qc >> log2d) << (log2d + 1)) + (qc & (dil - 1));
+        }
+    }
     float av1[2][4], ab1[2], av2[1 + MS];
-    {
+    if constexpr (MF < BX6_MF_16) {
         const float* Abt = a.Abt + (size_t)b * a.abt_bstride + step_row_off(a.step_idx, a.abt_tstride);
 #pragma unroll
         for (int m = 0; m < 2; ++m) {
@@ -459,8 +524,16 @@ __global__ __launch_bounds__(C * 2, (C >= 128 ? 2 : 1)) void wn_layer_bx6_kernel
     // cycles per wave: six products cover an L2 round trip with one step, three products need two.
     constexpr int PF = BX6_PF(NT);
     v8 a_ring[4][2][NT];
+    // 16x16x32 fragments of (32-channel block kk, product j, row tile m): half h takes rows 16 h + r16 of k-blocks 2 kk + (oct >> 1),
+    // k half oct & 1 -- the bytes of the two 32x32x16 fragments of those k-blocks; every 16-lane group reads 256 contiguous bytes
+    // (16x16x32: the first half-step's six fragments, product 0 of row tile 0 -- bx6_load_a1h)
+    if constexpr (MF >= BX6_MF_16) {
+        static_assert(MF < BX6_MF_16 || (PF == 1 && KC == 32), "one half-step of six fragments ahead: NAF and every vmcnt count as in the 32x32x16 form");
+        bx6_load_a1h<v8, NT>(gs1.ar[0], rA1, bx6_voff_a1h<NT>(lane), ((mt1[0] * NKB + 2 * chunk_of(0)) * 4 + 0) * NT * 1024);
+    } else {
 #pragma unroll
     for (int s0 = 0; s0 < PF; ++s0) load_a1(a_ring[s0], chunk_of(0) * (KC / 16) + (s0 >> 2), s0 & 3);
+    }
     constexpr int NAF = PF * NA;              // A fragment loads in flight behind anything older
     // chunk 0 has landed (this wave's part; the barrier makes it everyone's): all but the loads issued after it -- chunk 1
     // and the NAF A fragments.  hipcc does not make a barrier wait for LDS-DMA.  A piece is one request in the 16-byte
@@ -478,7 +551,35 @@ __global__ __launch_bounds__(C * 2, (C >= 128 ? 2 : 1)) void wn_layer_bx6_kernel
     }
     __syncthreads();
     stamp(1);
-    {   // correction k-block: k = 0 the step-embedding row (x the Winograd transform of the in-range indicator of the four
+    if constexpr (MF >= BX6_MF_16) {   // the same correction block, K = 32: non-zero in the lanes of octet 0; indicator values per column half
+        const bx_f32x4 zero = {0.f, 0.f, 0.f, 0.f};
+        float bi[2][4];
+#pragma unroll
+        for (int c = 0; c < 2; ++c) {
+            const int pc = gs1.pc[c];
+            const float v0 = ((unsigned)(pc - dil) < (unsigned)L) ? 1.f : 0.f;
+            const float v1 = ((unsigned)pc < (unsigned)L) ? 1.f : 0.f;
+            const float v2 = ((unsigned)(pc + dil) < (unsigned)L) ? 1.f : 0.f;
+            const float v3 = ((unsigned)(pc + 2 * dil) < (unsigned)L) ? 1.f : 0.f;
+            bi[c][0] = v0 - v2; bi[c][1] = v1 + v2; bi[c][2] = v2 - v1; bi[c][3] = v1 - v3;
+        }
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+#pragma unroll
+            for (int m = 0; m < 2; ++m)
+#pragma unroll
+                for (int h = 0; h < 2; ++h) {
+                    v8 af[NT];
+                    P::rank2_16(gs1.av[m][h][j] * ws1, j == 1 ? gs1.ab[m][h] * ws1 : 0.f, lane, af);
+#pragma unroll
+                    for (int c = 0; c < 2; ++c) {
+                        const v8 bf = P::bvals_16(bi[c][j] * P::SX, j == 1 ? P::SX : 0.f, lane);
+                        gs1.acc[m][j][h][c] = zero;
+#pragma unroll
+                        for (int t = NT - 1; t >= 0; --t) gs1.acc[m][j][h][c] = P::mfma16(af[t], bf, gs1.acc[m][j][h][c]);
+                    }
+                }
+    } else {   // correction k-block: k = 0 the step-embedding row (x the Winograd transform of the in-range indicator of the four
         // shifts), k = 1 of product 1 the conv bias (m1 enters both outputs of a pair with +1)
         const float v0 = ((unsigned)(p - dil) < (unsigned)L) ? 1.f : 0.f;
         const float v1 = ((unsigned)p < (unsigned)L) ? 1.f : 0.f;
@@ -580,6 +681,76 @@ __global__ __launch_bounds__(C * 2, (C >= 128 ? 2 : 1)) void wn_layer_bx6_kernel
         }
     };
     static_assert((SPC == 4 || SPC == 8) && PF >= 1 && PF <= 3, "steps per chunk, prefetch distance");
+    if constexpr (MF >= BX6_MF_16) {
+        // The chunk (one 32-channel block) in eight half-steps (product j, row tile m): each requests the six A fragments of the
+        // next half-step and issues 24 MFMAs of 16 cycles -- the period, the A ring and the load counts of a 32x32x16 step.  The
+        // six B fragments of a product serve its two half-steps; behind the last use of a term in the second one (the products
+        // run (2,0) (1,1) (0,2) (1,0) (0,1) (0,0): term 2 is free after the third, term 1 after the fifth) the next product's
+        // fragment of that term is read into the same registers; term 0, which the next product's first MFMA needs, alternates
+        // between two register sets and is read at the start of the second half-step.  The transform
+        // units of the next chunk ride in half-step 0 (T16_SLOTS), the residual copy stands ahead of half-step 2.
+        const int r16 = lane & 15, oct = lane >> 4;
+        const int voffa = bx6_voff_a1h<NT>(lane);
+        constexpr int T16_SLOTS[T_UNITS] = {BX6_T16_SLOTS};
+        v8 bq[2][NT], bq0[2][2];   // [column half][term] (terms 1, 2); term 0: [product & 1][column half]
+        auto do_half = [&](int cb, auto HS, auto WITH_T) {
+            constexpr int hs = decltype(HS)::value, j = hs >> 1, m = hs & 1;
+            constexpr bool ride = decltype(WITH_T)::value;
+            const char* tb = Bop + (cb & 1) * T::BOP_BYTES + oct * (4 * NT * 512) + r16 * 16;
+            if (hs == 2 && cb + 1 < NCB) keep_residual(cb + 1);
+            if (hs < 7) bx6_load_a1h<v8, NT>(gs1.ar[(hs + 1) & 1], rA1, voffa, ((mt1[(hs + 1) & 1] * NKB + 2 * chunk_of(cb)) * 4 + ((hs + 1) >> 1)) * NT * 1024);
+            else if (cb + 1 < NCB) bx6_load_a1h<v8, NT>(gs1.ar[0], rA1, voffa, ((mt1[0] * NKB + 2 * chunk_of(cb + 1)) * 4 + 0) * NT * 1024);
+            __builtin_amdgcn_sched_barrier(0);   // keep the prefetch a whole half-step ahead of its use
+            if (hs == 0) {   // (a chunk's first fragments cannot be asked for before the chunk barrier)
+#pragma unroll
+                for (int t = 0; t < NT; ++t)
+#pragma unroll
+                    for (int c = 0; c < 2; ++c) (t ? bq[c][t] : bq0[0][c]) = *reinterpret_cast<const v8*>(tb + (j * NT + t) * 512 + c * 256);
+            }
+            if (m == 1 && j < 3) {   // term 0 of the next product: needed by its first MFMA, so it has a register set of its own
+#pragma unroll
+                for (int c = 0; c < 2; ++c) bq0[(j + 1) & 1][c] = *reinterpret_cast<const v8*>(tb + ((j + 1) * NT) * 512 + c * 256);
+            }
+            TState ts;
+#pragma unroll
+            for (int t = 0; t < NPR; ++t) {
+#pragma unroll
+                for (int h = 0; h < 2; ++h)
+#pragma unroll
+                    for (int c = 0; c < 2; ++c) {
+                        gs1.acc[m][j][h][c] = P::mfma16(gs1.ar[hs & 1][h][P::ia(t)], P::ib(t) ? bq[c][P::ib(t)] : bq0[j & 1][c], gs1.acc[m][j][h][c]);
+                        if (ride) {
+                            const int i = (2 * t + h) * 2 + c;
+#pragma unroll
+                            for (int u = 0; u < T_UNITS; ++u)
+                                if (T16_SLOTS[u] == i) transform_unit(cb + 1, u, ts);
+                            __builtin_amdgcn_sched_barrier(0);
+                        }
+                    }
+                if (m == 1 && j < 3 && (t == 2 || t == 4)) {   // the next product's fragments of the term that has just had its last use
+                    const int term = (t == 2) ? 2 : 1;
+#pragma unroll
+                    for (int c = 0; c < 2; ++c) bq[c][term] = *reinterpret_cast<const v8*>(tb + ((j + 1) * NT + term) * 512 + c * 256);
+                }
+            }
+        };
+        for (int cb = 0; cb < NCB; ++cb) {
+            if (cb + 2 < NCB && stages(cb + 2)) stage_dma(cb + 2);
+            if (cb + 1 < NCB) do_half(cb, std::integral_constant<int, 0>{}, std::true_type{});
+            else do_half(cb, std::integral_constant<int, 0>{}, std::false_type{});
+            do_half(cb, std::integral_constant<int, 1>{}, std::false_type{});
+            do_half(cb, std::integral_constant<int, 2>{}, std::false_type{});
+            do_half(cb, std::integral_constant<int, 3>{}, std::false_type{});
+            do_half(cb, std::integral_constant<int, 4>{}, std::false_type{});
+            do_half(cb, std::integral_constant<int, 5>{}, std::false_type{});
+            do_half(cb, std::integral_constant<int, 6>{}, std::false_type{});
+            do_half(cb, std::integral_constant<int, 7>{}, std::false_type{});
+            stamp(8 + 2 * cb);
+            __builtin_amdgcn_s_waitcnt(0x0F70 | NAF);   // (as below: the LDS-DMA of chunk cb + 2 has landed, only the next half-step's A fragments are younger)
+            __syncthreads();
+            stamp(9 + 2 * cb);
+        }
+    } else {
     for (int cb = 0; cb < NCB; ++cb) {
 #ifndef BX6_ABL_NO_STAGE
         if (cb + 2 < NCB && stages(cb + 2)) stage_dma(cb + 2);   // into the raw buffer chunk cb occupied (transformed an iteration ago)
@@ -599,8 +770,23 @@ __global__ __launch_bounds__(C * 2, (C >= 128 ? 2 : 1)) void wn_layer_bx6_kernel
 #endif
         stamp(9 + 2 * cb);
     }
+    }
     stamp(2);
+    // The tail's lane number.  The both-GEMM 16x16x32 instances hide it from the optimiser here: whatever the tail derives from
+    // it (addresses of the gate tile, the transpose slot, the x / skip rows) is then computed here and not ahead of GEMM1, which
+    // has no register to carry it (256 of 256).
+    int lane_t = lane;
+    if constexpr (MF >= BX6_MF_16) asm volatile("" : "+v"(lane_t));
 
+    // 16x16x32 GEMM2: the bias of row 16 h + r16 of each row tile.  Asked for here and not with the other correction operands:
+    // GEMM1 has no register to carry it (256 of 256), and the gate stage covers the latency.
+    [[maybe_unused]] std::conditional_t<MF >= BX6_MF_G2_16, Bx6G2State<MS>, Bx6Nothing> gs2;
+    if constexpr (MF >= BX6_MF_G2_16) {
+#pragma unroll
+        for (int m = 0; m < 1 + MS; ++m)
+#pragma unroll
+            for (int h = 0; h < 2; ++h) gs2.bias[m][h] = a.bias2[mt2[m] * 32 + 16 * h + (lane_t & 15)];
+    }
     // ---- x and running-skip tiles of this wave's output rows, requested before the gate stage (row-major 16-byte pieces:
     // lane = (row lane>>4 of a group of four rows, column quad lane&15; quads 0..7 = column tile 0, 8..15 = tile 1)
     const int L4 = L * 4;
@@ -610,9 +796,9 @@ __global__ __launch_bounds__(C * 2, (C >= 128 ? 2 : 1)) void wn_layer_bx6_kernel
     const int p0 = ((q0 >> log2d) << (log2d + 1)) + (q0 & (dil - 1));   // position of column 0 of tile 0 (d >= 32: q0 % 32 == 0 keeps it a multiple of 32)
     int voff4;
     {
-        const int n4 = (lane & 15) >> 3;
-        const int pos4 = (contig ? pbase + 32 * n4 : p0 + n4 * dil) + 4 * (lane & 7);
-        voff4 = (pos4 < L) ? ((lane >> 4) * L + pos4) * 4 : 0x7ffffff0;
+        const int n4 = (lane_t & 15) >> 3;
+        const int pos4 = (contig ? pbase + 32 * n4 : p0 + n4 * dil) + 4 * (lane_t & 7);
+        voff4 = (pos4 < L) ? ((lane_t >> 4) * L + pos4) * 4 : 0x7ffffff0;
     }
     // (S = 2C: three row tiles per wave would take 96 registers here -- those instances fetch each tile in the epilogue;
     // they run two workgroups per CU, which cover each other's waits)
@@ -622,7 +808,7 @@ __global__ __launch_bounds__(C * 2, (C >= 128 ? 2 : 1)) void wn_layer_bx6_kernel
     auto load_pre = [&](int m, bx6_f32x4 (&dst)[8]) {
 #pragma unroll
         for (int i = 0; i < 8; ++i) {
-            if (m == 0) dst[i] = *reinterpret_cast<const bx6_f32x4*>(trw + ((lane >> 4) + 4 * i) * 64 + 4 * (lane & 15));
+            if (m == 0) dst[i] = *reinterpret_cast<const bx6_f32x4*>(trw + ((lane_t >> 4) + 4 * i) * 64 + 4 * (lane_t & 15));
             else dst[i] = bx6_load_f4(rSk, voff4s, ((wave * MS + (m - 1)) * 32 + 4 * i) * L4);
         }
     };
@@ -634,6 +820,57 @@ __global__ __launch_bounds__(C * 2, (C >= 128 ? 2 : 1)) void wn_layer_bx6_kernel
 
     // ---- gate: g = tanh(H_t (+mel_t)) * sigmoid(H_s (+mel_s)) for both outputs of every pair, split -> LDS gate tile
     const float* melb = (EXTRA && a.melc) ? a.melc + (size_t)(a.mel_bstride ? b : 0) * 2 * C * L : nullptr;
+    if constexpr (MF >= BX6_MF_16) {
+        // a lane_t holds four consecutive channels 16 h + 4 oct + (0..3) of column 16 c + r16: the 8-byte half oct & 1 of item
+        // [octet wave * 4 + 2 h + (oct >> 1)][term][column]
+        const int r16 = lane_t & 15, oct = lane_t >> 4;
+#pragma unroll
+        for (int c = 0; c < 2; ++c) {
+            const int qc = q0 + 16 * c + r16;
+            const int pc = ((qc >> log2d) << (log2d + 1)) + (qc & (dil - 1));
+            const int gc0 = contig ? pc - pbase : 16 * c + r16, gc1 = contig ? pc - pbase + dil : 32 + 16 * c + r16;
+#pragma unroll
+            for (int h = 0; h < 2; ++h) {
+                float ga[4], gb[4];
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    const int ch = wave * 32 + 16 * h + 4 * oct + e;
+#pragma unroll
+                    for (int n = 0; n < 2; ++n) {
+                        const int pos = pc + n * dil;
+                        float ht, hs;
+                        if (n == 0) {
+                            ht = (gs1.acc[0][0][h][c][e] + gs1.acc[0][1][h][c][e]) + gs1.acc[0][2][h][c][e];
+                            hs = (gs1.acc[1][0][h][c][e] + gs1.acc[1][1][h][c][e]) + gs1.acc[1][2][h][c][e];
+                        } else {
+                            ht = (gs1.acc[0][1][h][c][e] - gs1.acc[0][2][h][c][e]) - gs1.acc[0][3][h][c][e];
+                            hs = (gs1.acc[1][1][h][c][e] - gs1.acc[1][2][h][c][e]) - gs1.acc[1][3][h][c][e];
+                        }
+                        if (EXTRA && melb && pos < L) {
+                            ht += melb[(size_t)ch * L + pos];
+                            hs += melb[(size_t)(C + ch) * L + pos];
+                        }
+                        if (EXTRA && a.hsave && pos < L) {   // training: keep the pre-activations for the gate adjoint (dword stores)
+                            float* __restrict__ hb = a.hsave + (size_t)b * 2 * C * L;
+                            hb[(size_t)ch * L + pos] = ht;
+                            hb[(size_t)(C + ch) * L + pos] = hs;
+                        }
+                        const float g = bx6_gate(ht, hs) * P::SG;
+                        if (n == 0) ga[e] = g; else gb[e] = g;
+                    }
+                }
+                v4 s0[NT], s1[NT];
+                P::split4(ga, s0);
+                P::split4(gb, s1);
+                char* dst = gt + ((wave * 4 + 2 * h + (oct >> 1)) * NT * 64) * 16 + (oct & 1) * 8;
+#pragma unroll
+                for (int t = 0; t < NT; ++t) {
+                    *reinterpret_cast<v4*>(dst + (t * 64 + gc0) * 16) = s0[t];
+                    *reinterpret_cast<v4*>(dst + (t * 64 + gc1) * 16) = s1[t];
+                }
+            }
+        }
+    } else {
 #pragma unroll
     for (int qd = 0; qd < 4; ++qd) {
         float g0[4], g1[4];
@@ -675,6 +912,7 @@ __global__ __launch_bounds__(C * 2, (C >= 128 ? 2 : 1)) void wn_layer_bx6_kernel
             *reinterpret_cast<v4*>(dst + (t * 64 + gcol0) * 16) = s0[t];
             *reinterpret_cast<v4*>(dst + (t * 64 + gcol1) * 16) = s1[t];
         }
+    }
     }
     stamp(3);
 
@@ -741,8 +979,91 @@ __global__ __launch_bounds__(C * 2, (C >= 128 ? 2 : 1)) void wn_layer_bx6_kernel
                 for (int t = 0; t < NT; ++t) c_cur[m][t] = c_nxt[m][t];
         }
     };
-    if (last) gemm2(std::false_type{});
-    else gemm2(std::true_type{});
+    if constexpr (MF >= BX6_MF_G2_16) {
+        // The same GEMM on v_mfma_f32_16x16x32_bf16.  A 32 x 32 tile is four slices (row half h, column half c) of four
+        // registers: row = 16 h + 4 oct + reg, col = 16 c + r16.  A and B are the same 16-byte items read through another lane_t
+        // map: the A fragment of (32-channel block kk, half h) takes rows 16 h + r16 of k-blocks 2 kk + (oct >> 1), k half
+        // oct & 1 -- the two halves read exactly the bytes of the two 32x32x16 fragments of those k-blocks; B takes octet
+        // 4 kk + oct of the gate tile, columns 32 n + 16 c + r16 (octet stride 3072 B = 0 mod 256: each group of ds_read_b128
+        // lanes covers all banks once).  Per output element: bias block, then the 32-channel blocks in the order rotated by
+        // `rot`, then the products -- the 32x32x16 order, but one instruction sums 32 channels where two summed 16 + 16
+        // (last-bit differences).  A block runs as two half-steps (h = 0, 1) of 8 NPR MFMAs; the (1 + MS) NT A fragments of a
+        // half-step are requested one half-step ahead, the B fragments of a block serve both.
+        // (The lambda is defined in these instances only: a generic lambda captures what its body names even where the body
+        // is discarded, and the 32x32x16 instances compile to exactly the code they had without it.)
+        auto gemm2_16 = [&](auto WITH_RES) {
+            const int r16 = lane_t & 15, oct = lane_t >> 4;   // row / column of a 16-wide half, k-octet of a 32-channel block
+            auto& acc2h = gs2.acc;
+            constexpr int M0 = decltype(WITH_RES)::value ? 0 : 1;
+            const int voffa = (oct >> 1) * (NT * 1024) + ((oct & 1) * 32 + r16) * 16;
+            auto load_a2h = [&](v8 (&dst)[1 + MS][NT], int kk, int h) {
+#pragma unroll
+                for (int m = M0; m < 1 + MS; ++m)
+#pragma unroll
+                    for (int t = 0; t < NT; ++t)
+                        dst[m][t] = __builtin_bit_cast(v8, __builtin_amdgcn_raw_buffer_load_b128(rA2, voffa + h * 256, ((mt2[m] * NKB + 2 * kk) * NT + t) * 1024, 0));
+            };
+            auto block_of = [&](int kk) { const int k = kk + rot; return k >= NCB ? k - NCB : k; };
+            static_assert(KC == 32, "GEMM2's rotation counts 32-channel blocks");
+            v8 ah[2][1 + MS][NT];
+            load_a2h(ah[0], block_of(0), 0);
+            {
+                const v8 bf = P::bvals_16(P::SG, 0.f, lane_t);     // a row of ones, at the gate operand's scale
+                const bx_f32x4 zero = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+                for (int m = M0; m < 1 + MS; ++m)
+#pragma unroll
+                    for (int h = 0; h < 2; ++h) {
+                        v8 af[NT];
+                        P::rank2_16(gs2.bias[m][h] * ws2, 0.f, lane_t, af);
+#pragma unroll
+                        for (int n = 0; n < 2; ++n)
+#pragma unroll
+                            for (int c = 0; c < 2; ++c) {
+                                acc2h[m][n][h][c] = zero;
+#pragma unroll
+                                for (int t = NT - 1; t >= 0; --t) acc2h[m][n][h][c] = P::mfma16(af[t], bf, acc2h[m][n][h][c]);
+                            }
+                    }
+            }
+            __syncthreads();   // gate tile complete
+            stamp(4);
+            const char* gb = gt + oct * (NT * 64 * 16) + r16 * 16;
+#pragma unroll 1
+            for (int kk = 0; kk < NCB; ++kk) {
+                const char* gk = gb + block_of(kk) * (4 * NT * 64 * 16);
+                v8 bq[2][2][NT];
+#pragma unroll
+                for (int h = 0; h < 2; ++h) {
+                    if (h == 0) load_a2h(ah[1], block_of(kk), 1);
+                    else load_a2h(ah[0], block_of(kk + 1 < NCB ? kk + 1 : kk), 0);
+                    __builtin_amdgcn_sched_barrier(0);
+                    if (h == 0) {
+#pragma unroll
+                        for (int n = 0; n < 2; ++n)
+#pragma unroll
+                            for (int c = 0; c < 2; ++c)
+#pragma unroll
+                                for (int t = 0; t < NT; ++t) bq[n][c][t] = *reinterpret_cast<const v8*>(gk + (t * 64 + n * 32 + c * 16) * 16);
+                    }
+#pragma unroll
+                    for (int t = 0; t < NPR; ++t)
+#pragma unroll
+                        for (int m = M0; m < 1 + MS; ++m)
+#pragma unroll
+                            for (int n = 0; n < 2; ++n)
+#pragma unroll
+                                for (int c = 0; c < 2; ++c)
+                                    acc2h[m][n][h][c] = P::mfma16(ah[h][m][P::ia(t)], bq[n][c][P::ib(t)], acc2h[m][n][h][c]);
+                }
+            }
+        };
+        if (last) gemm2_16(std::false_type{});
+        else gemm2_16(std::true_type{});
+    } else {
+        if (last) gemm2(std::false_type{});
+        else gemm2(std::true_type{});
+    }
     stamp(5);
 
     // ---- epilogue
@@ -754,30 +1075,82 @@ __global__ __launch_bounds__(C * 2, (C >= 128 ? 2 : 1)) void wn_layer_bx6_kernel
             if (m == 0 && last) continue;   // the last layer's residual output feeds nothing (`wavenet.py:165`)
             if (!PRELOAD || m == 0) load_pre(m, pre[0]);      // (m = 0: the x rows out of the wave's own slot, before it is overwritten)
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+            if constexpr (MF >= BX6_MF_G2_16) {
+                // the four octets of a lane group write rows 4 oct + r, 256 floats = 0 banks apart: the 16-column group of a
+                // row is XORed with (row >> 2) & 3 = oct, which spreads them over the 64 banks; the read-back undoes it
+                const int r16 = lane_t & 15, oct = lane_t >> 4;
+                auto& acc2h = gs2.acc;
+#pragma unroll
+                for (int n = 0; n < 2; ++n)
+#pragma unroll
+                    for (int h = 0; h < 2; ++h)
+#pragma unroll
+                        for (int c = 0; c < 2; ++c)
+#pragma unroll
+                            for (int r = 0; r < 4; ++r) trw[(16 * h + 4 * oct + r) * 64 + ((n * 32 + 16 * c + r16) ^ (oct << 4))] = acc2h[m][n][h][c][r];
+            } else {
 #pragma unroll
             for (int n = 0; n < 2; ++n)
 #pragma unroll
                 for (int r = 0; r < 16; ++r) trw[((r & 3) + 8 * (r >> 2) + 4 * lhi) * 64 + n * 32 + l31] = P::SCALED ? acc2[m][n][r] * inv2 : acc2[m][n][r];
+            }
             // one wave, LDS operations of a wave execute in order: only the compiler has to be kept from moving the reads
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
             const int row0 = (m == 0) ? wave * 32 : (wave * MS + (m - 1)) * 32;
 #pragma unroll
             for (int i = 0; i < 8; ++i) {
-                const bx6_f32x4 v = *reinterpret_cast<const bx6_f32x4*>(trw + ((lane >> 4) + 4 * i) * 64 + 4 * (lane & 15));
+                // (16x16x32: the slot's 16-column groups are XORed with (row >> 2) & 3 = i & 3, see the writes above)
+                const bx6_f32x4 v = *reinterpret_cast<const bx6_f32x4*>(trw + ((lane_t >> 4) + 4 * i) * 64 +
+                                                                        (MF >= BX6_MF_G2_16 ? (4 * (lane_t & 15)) ^ ((i & 3) << 4) : 4 * (lane_t & 15)));
                 bx6_f32x4 o = pre[PRELOAD ? m : 0][i] + v;
                 if (m == 0) o = o * rs;
                 bx6_store_f4(o, m == 0 ? rXo : rSk, voff4, (row0 + 4 * i) * L4);
                 // gfx950 hazard, found by the bit-for-bit determinism test: a VALU write (here the next v_pk_add / v_pk_mul) to
                 // the data registers of a 16-byte buffer store in the slot right behind it changes what the store writes
-                // for the last lanes of each 16-lane group (their last dword) -- hipcc's hazard recognizer leaves the wait
+                // for the last lanes of each 16-lane_t group (their last dword) -- hipcc's hazard recognizer leaves the wait
                 // state out when the store carries an SGPR offset.  One wait state removes it (measured: 0 -> wrong in
                 // 2 of 3 runs, 1 / 2 / 4 / 16 -> never); two are kept.
                 asm volatile("s_nop 1" ::: "memory");
             }
             asm volatile("" ::: "memory");   // the next row tile overwrites the slot
         }
+    } else if constexpr (MF >= BX6_MF_G2_16) {
+        // rows not 16-byte aligned, 16x16x32 accumulators: the lane_t owns columns 16 c + r16 of both column tiles, rows 16 h + 4 oct + reg
+        const int r16 = lane_t & 15, oct = lane_t >> 4;
+        auto& acc2h = gs2.acc;
+#pragma unroll
+        for (int n = 0; n < 2; ++n)
+#pragma unroll
+            for (int c = 0; c < 2; ++c) {
+                const int qc = q0 + 16 * c + r16;
+                const int pc = ((qc >> log2d) << (log2d + 1)) + (qc & (dil - 1));
+                const int pos = contig ? pbase + 32 * n + 16 * c + r16 : pc + n * dil;
+                const int voffc = (pos < L) ? (4 * oct * L + pos) * 4 : 0x7ffffff0;
+#pragma unroll
+                for (int h = 0; h < 2; ++h) {
+                    if (!last) {
+                        const int s0 = (wave * 32 + 16 * h) * L4;
+#pragma unroll
+                        for (int r = 0; r < 4; ++r) {
+                            const float x = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rXall, voffc, s0 + r * L4, 0));
+                            const float v = (x + acc2h[0][n][h][c][r]) * rs;
+                            __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), rXo, voffc, s0 + r * L4, 0);
+                        }
+                    }
+#pragma unroll
+                    for (int m = 0; m < MS; ++m) {
+                        const int s0 = ((wave * MS + m) * 32 + 16 * h) * L4;
+#pragma unroll
+                        for (int r = 0; r < 4; ++r) {
+                            const float old = first ? 0.f : __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rSk, voffc, s0 + r * L4, 0));
+                            const float v = old + acc2h[1 + m][n][h][c][r];
+                            __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), rSk, voffc, s0 + r * L4, 0);
+                        }
+                    }
+                }
+            }
     } else {
-        // rows not 16-byte aligned: per-lane dwords straight from the accumulator layout
+        // rows not 16-byte aligned: per-lane_t dwords straight from the accumulator layout
         int voffn[2];
 #pragma unroll
         for (int n = 0; n < 2; ++n) {
@@ -816,7 +1189,7 @@ __global__ __launch_bounds__(C * 2, (C >= 128 ? 2 : 1)) void wn_layer_bx6_kernel
     }
 }
 
-template <typename P, int C, int S>
+template <typename P, int C, int S, int MF = BX6_MF_32>
 static int launch_bx6_t(const WnLayerArgs& a, int log2d, hipStream_t s) {
     ProfileScope ps(P::NT == 3 ? "wn_layer_bx6" : "wn_layer_f16x3", s);
     using T = Bx6Tile<C, S, P::NT>;
@@ -827,14 +1200,16 @@ static int launch_bx6_t(const WnLayerArgs& a, int log2d, hipStream_t s) {
     static const bool trace = std::getenv("DWS_BX6_TRACE") != nullptr;
     if (trace && !a.melc && !a.hsave) {
         wino_trace_launch(ntiles, T::WAVES, a, s, [&](const WnLayerArgs& at) {
-            hipLaunchKernelGGL((wn_layer_bx6_kernel<P, C, S, false>), dim3(ntiles), dim3(T::NTH), 0, s, at, log2d);
+            hipLaunchKernelGGL((wn_layer_bx6_kernel<P, C, S, false, MF>), dim3(ntiles), dim3(T::NTH), 0, s, at, log2d);
         }, P::NT == 3 ? "bx6" : "f16x3");
         return DWS_OK;
     }
-    if (a.melc || a.hsave) hipLaunchKernelGGL((wn_layer_bx6_kernel<P, C, S, true>), dim3(ntiles), dim3(T::NTH), 0, s, a, log2d);
-    else hipLaunchKernelGGL((wn_layer_bx6_kernel<P, C, S, false>), dim3(ntiles), dim3(T::NTH), 0, s, a, log2d);
+    if (a.melc || a.hsave) hipLaunchKernelGGL((wn_layer_bx6_kernel<P, C, S, true, MF>), dim3(ntiles), dim3(T::NTH), 0, s, a, log2d);
+    else hipLaunchKernelGGL((wn_layer_bx6_kernel<P, C, S, false, MF>), dim3(ntiles), dim3(T::NTH), 0, s, a, log2d);
     return DWS_OK;
 }
+
+bool wn_layer_bx6_mfma16_supported(int C, int S, int split) { return split == WN_SPLIT_BF16X6 && C == 256 && S == 256; }
 
 bool wn_layer_bx6_supported(int C, int S) {
     return (C == 64 && S == 64) || (C == 128 && S == 128) || (C == 128 && S == 256) || (C == 256 && S == 256);
@@ -849,7 +1224,7 @@ static int launch_bx6_p(int C, int S, const WnLayerArgs& a, int log2d, hipStream
     return set_error(DWS_ERR_UNSUPPORTED, "wn_layer_bx6: (C=%d,S=%d) not instantiated", C, S);
 }
 
-int launch_wn_layer_bx6(int C, int S, const WnLayerArgs& a, int split, hipStream_t s) {
+int launch_wn_layer_bx6(int C, int S, const WnLayerArgs& a, int split, int mfma, hipStream_t s) {
     int log2d = 0;
     while ((1 << log2d) < a.dilation) ++log2d;
     DWS_CHECK((1 << log2d) == a.dilation, DWS_ERR_UNSUPPORTED, "wn_layer_bx6: dilation %d is not a power of two", a.dilation);
@@ -861,6 +1236,10 @@ int launch_wn_layer_bx6(int C, int S, const WnLayerArgs& a, int split, hipStream
         DWS_CHECK(a.wscale != nullptr, DWS_ERR_INVALID, "wn_layer_f16x3: no weight scales");
         return launch_bx6_p<SplitF16x2>(C, S, a, log2d, s);
     }
+    // the 16x16x32 shape exists for the instances it was measured on; every other instance has one shape and keeps it
+    if (mfma == WN_BX6_MFMA_G2_16 && wn_layer_bx6_mfma16_supported(C, S, split)) return launch_bx6_t<SplitBf16x3, 256, 256, BX6_MF_G2_16>(a, log2d, s);
+    if (mfma == WN_BX6_MFMA_16 && wn_layer_bx6_mfma16_supported(C, S, split)) return launch_bx6_t<SplitBf16x3, 256, 256, BX6_MF_16>(a, log2d, s);
+    DWS_CHECK(mfma == WN_BX6_MFMA_32 || mfma == WN_BX6_MFMA_G2_16 || mfma == WN_BX6_MFMA_16, DWS_ERR_INVALID, "wn_layer_bx6: unknown MFMA shape %d", mfma);
     return launch_bx6_p<SplitBf16x3>(C, S, a, log2d, s);
 }
 

@@ -160,7 +160,12 @@ int dws_model_update_params(dws_model* m, int32_t count, const char* const* name
  *                          Winograd F(2,3) form along the dilation stride: 8 C^2 instead of 12 C^2 flop per position,
  *                          one extra fp32 rounding in the weights and in the inputs (same 1e-6 class error); the
  *                          training step's data and weight gradients of that convolution run the same pairing
- *               = "direct" the direct three-tap form, forward and both adjoints (A/B runs). */
+ *               = "direct" the direct three-tap form, forward and both adjoints (A/B runs).
+ *   "bx6_mfma" = "16x16x32" (default; initial value from the environment variable DWS_BX6_MFMA) WaveNet, precision bf16x6,
+ *                          res_channels = skip_channels = 256: both GEMMs of the layer kernel on v_mfma_f32_16x16x32_bf16 (the
+ *                          chip holds a higher clock on it); same error class, last bits differ from "32x32x16"
+ *              = "gemm2-16x16x32" only the [res; skip] GEMM and the epilogue on that shape
+ *              = "32x32x16" the v_mfma_f32_32x32x16_bf16 kernel (every other width runs it whatever this says). */
 int dws_model_set_option(dws_model* m, const char* key, const char* value);
 
 /* Class conditioning (class-conditional generation; not in the reference).  Call after dws_model_create and before the
