@@ -1,7 +1,9 @@
 // extern "C" surface of libdws.so for the model and sampler entry points
 // (include/dws.h); the Cauchy entry points live in cauchy_kernels.hip.
 #include <cstring>
+#include <cmath>
 #include "model.h"
+#include "optim.h"
 
 namespace dws {
 struct SamplerProgram;
@@ -495,6 +497,142 @@ static int multi_copy(dws_model* m, std::vector<dws::CopyJob>& jobs, hipStream_t
     DWS_HIP(hipMemcpyAsync(table.p, m->copy_pinned[slot], jobs.size() * sizeof(dws::CopyJob), hipMemcpyHostToDevice, stream));
     DWS_HIP(hipEventRecord(m->copy_consumed[slot], stream));
     return dws::launch_multi_copy((const dws::CopyJob*)table.p, (int)jobs.size(), stream);
+}
+
+// ---- fused optimizer step (optim_kernels.hip) ---------------------------------------------------------------------------
+int dws_optim_chunk(void) { return dws::OPTIM_CHUNK; }
+
+int dws_optim_create(dws_optim** out) {
+    DWS_CHECK(out, DWS_ERR_INVALID, "dws_optim_create: null argument");
+    *out = nullptr;
+    dws_optim* o = new dws_optim();
+    const size_t bytes = dws::OPTIM_MAX_GRID * sizeof(double) + 2 * sizeof(float);
+    int st = o->scratch.ensure(bytes);
+    if (st == DWS_OK && hipMemset(o->scratch.p, 0, bytes) != hipSuccess)
+        st = dws::set_error(DWS_ERR_HIP, "dws_optim_create: hipMemset failed");
+    if (st != DWS_OK) {
+        delete o;
+        return st;
+    }
+    *out = o;
+    return DWS_OK;
+}
+
+int dws_optim_destroy(dws_optim* o) {
+    delete o;
+    return DWS_OK;
+}
+
+// The staging slot of a call: the next one of the ring whose last upload has been consumed (hipEventQuery, no wait); while
+// none is free the ring grows, so the host never waits for the GPU (only a ring of MAX_SLOTS busy slots would).
+static int optim_slot(dws_optim* o, size_t njobs, dws_optim::Slot** out) {
+    const int n = (int)o->ring.size();
+    int pick = -1;
+    for (int k = 0; k < n && pick < 0; ++k) {
+        const int s = (o->next + k) % n;
+        if (hipEventQuery(o->ring[s].consumed) == hipSuccess) pick = s;
+    }
+    (void)hipGetLastError();      // hipErrorNotReady of a busy slot is not an error
+    if (pick < 0) {
+        if (n < dws_optim::MAX_SLOTS) {
+            dws_optim::Slot sl;
+            DWS_HIP(hipEventCreateWithFlags(&sl.consumed, hipEventDisableTiming));
+            o->ring.push_back(sl);
+            pick = n;
+        } else {
+            pick = o->next % n;
+            DWS_HIP(hipEventSynchronize(o->ring[pick].consumed));
+        }
+    }
+    o->next = pick + 1;
+    dws_optim::Slot& sl = o->ring[pick];
+    if (sl.cap < njobs) {
+        if (sl.pinned) (void)hipHostFree(sl.pinned);
+        sl.pinned = nullptr;
+        sl.cap = 0;
+        DWS_HIP(hipHostMalloc(&sl.pinned, njobs * 2 * sizeof(dws::OptimJob), hipHostMallocDefault));
+        sl.cap = njobs * 2;
+    }
+    *out = &sl;
+    return DWS_OK;
+}
+
+int dws_optim_step(dws_optim* o, int32_t count, float* const* params, const float* const* grads, float* const* exp_avg,
+                   float* const* exp_avg_sq, float* const* ema, float* const* mirrors, const int64_t* numels, const double* lr,
+                   const int64_t* step, const double* weight_decay, double beta1, double beta2, double eps, double ema_decay,
+                   double max_grad_norm, float* grad_norm_out, dws_model* model, const char* const* names, void* stream) {
+    DWS_CHECK(o && count >= 0, DWS_ERR_INVALID, "dws_optim_step: null handle or negative count");
+    if (count == 0) return DWS_OK;
+    DWS_CHECK(params && grads && exp_avg && exp_avg_sq && numels && lr && step, DWS_ERR_INVALID, "dws_optim_step: null table");
+    DWS_CHECK(beta1 >= 0.0 && beta1 < 1.0 && beta2 >= 0.0 && beta2 < 1.0 && eps >= 0.0, DWS_ERR_INVALID,
+              "dws_optim_step: betas must lie in [0, 1) and eps must not be negative (got %g, %g, %g)", beta1, beta2, eps);
+    DWS_CHECK(!ema || (ema_decay > 0.0 && ema_decay < 1.0), DWS_ERR_INVALID,
+              "dws_optim_step: ema_decay must lie in (0, 1) with shadows (got %g)", ema_decay);
+    DWS_CHECK(!model || names, DWS_ERR_INVALID, "dws_optim_step: a model needs the parameter names");
+    const bool clip = max_grad_norm > 0.0;
+    std::vector<dws::OptimJob>& jobs = o->jobs;
+    jobs.assign((size_t)count, dws::OptimJob{});
+    int64_t chunks = 0;
+    bool mirrored = false;
+    for (int i = 0; i < count; ++i) {
+        dws::OptimJob& j = jobs[i];
+        DWS_CHECK(params[i] && grads[i] && exp_avg[i] && exp_avg_sq[i], DWS_ERR_INVALID, "dws_optim_step: tensor %d has a null pointer", i);
+        DWS_CHECK(numels[i] > 0 && step[i] >= 1, DWS_ERR_INVALID, "dws_optim_step: tensor %d: numel %lld, step %lld (both must be positive)",
+                  i, (long long)numels[i], (long long)step[i]);
+        j.p = params[i];
+        j.g = grads[i];
+        j.m = exp_avg[i];
+        j.v = exp_avg_sq[i];
+        j.ema = ema ? ema[i] : nullptr;
+        j.mirror = mirrors ? mirrors[i] : nullptr;
+        j.numel = numels[i];
+        if (model && names[i]) {
+            auto it = model->index.find(names[i]);
+            DWS_CHECK(it != model->index.end(), DWS_ERR_INVALID, "unknown parameter '%s'", names[i]);
+            dws::ParamSpec* p = model->params[it->second];
+            DWS_CHECK(p->dtype == 0, DWS_ERR_INVALID, "'%s': the optimizer step takes float32 parameters", names[i]);
+            DWS_CHECK((int64_t)p->numel() == numels[i], DWS_ERR_INVALID, "'%s': parameter has %zu elements, got %lld", names[i],
+                      p->numel(), (long long)numels[i]);
+            DWS_CHECK(p->buf.p, DWS_ERR_STATE, "'%s': the model holds no storage for it yet", names[i]);
+            j.mirror = p->buf.f();
+            mirrored = true;
+        }
+        // bias corrections in double from the integer step
+        const double bc1 = 1.0 - std::pow(beta1, (double)step[i]), bc2 = 1.0 - std::pow(beta2, (double)step[i]);
+        j.step_size = (float)(lr[i] / bc1);
+        j.sqrt_bc2 = (float)std::sqrt(bc2);
+        j.weight_decay = weight_decay ? (float)weight_decay[i] : 0.f;
+        const uintptr_t bits = (uintptr_t)j.p | (uintptr_t)j.g | (uintptr_t)j.m | (uintptr_t)j.v | (uintptr_t)j.ema | (uintptr_t)j.mirror;
+        j.vec = (bits & 15) == 0;
+        DWS_CHECK((bits & 3) == 0, DWS_ERR_INVALID, "dws_optim_step: tensor %d is not 4-byte aligned", i);
+        j.first_chunk = (int32_t)chunks;
+        chunks += (numels[i] + dws::OPTIM_CHUNK - 1) / dws::OPTIM_CHUNK;
+        DWS_CHECK(chunks < (int64_t)1 << 30, DWS_ERR_UNSUPPORTED, "dws_optim_step: more than 2^30 chunks");
+    }
+    hipStream_t s = (hipStream_t)stream;
+    dws_optim::Slot* slot = nullptr;
+    DWS_TRY(optim_slot(o, jobs.size(), &slot));
+    std::memcpy(slot->pinned, jobs.data(), jobs.size() * sizeof(dws::OptimJob));
+    DWS_TRY(o->table.ensure(jobs.size() * 2 * sizeof(dws::OptimJob)));
+    DWS_HIP(hipMemcpyAsync(o->table.p, slot->pinned, jobs.size() * sizeof(dws::OptimJob), hipMemcpyHostToDevice, s));
+    DWS_HIP(hipEventRecord(slot->consumed, s));
+    const dws::OptimJob* table = (const dws::OptimJob*)o->table.p;
+    if (clip || grad_norm_out)
+        DWS_TRY(dws::launch_optim_norm(table, count, (int)chunks, o->partials(), o->counter(), o->norm(), grad_norm_out, s));
+    dws::OptimHyper h;
+    h.om_beta1 = (float)(1.0 - beta1);
+    h.beta2 = (float)beta2;
+    h.om_beta2 = (float)(1.0 - beta2);
+    h.eps = (float)eps;
+    h.ema_w = ema ? (float)(1.0 - ema_decay) : 0.f;
+    h.max_norm = clip ? (float)max_grad_norm : 0.f;
+    DWS_TRY(dws::launch_optim_step(table, count, (int)chunks, h, clip ? o->norm() : nullptr, s));
+    if (mirrored) {      // as dws_model_update_params: the raw store changed
+        model->params_touched = true;
+        model->dirty = true;
+        model->drop_graph();
+    }
+    return DWS_OK;
 }
 
 int dws_model_read_tap(dws_model* m, const char* tap, float* dst, int64_t capacity, void* stream) {

@@ -182,6 +182,23 @@ def smooth_ckpt(path, min_ckpt, max_ckpt):
     return state_dict
 
 
+def weights_key(checkpoint, ema=None, ckpt_smooth=None):
+    """Which entry of a loaded checkpoint dict ``generate`` samples from: ``ema_state_dict`` (written by training runs
+    with ``train.ema_decay``) or ``model_state_dict``.  ``ema`` = None (default): the EMA when the checkpoint has one;
+    True: the EMA, an error when it has none; False: the raw weights.  ``ckpt_smooth`` averages the raw weights of several
+    checkpoints, which ``ema=True`` contradicts (refused); otherwise it takes ``model_state_dict``."""
+    if ema is not None and not isinstance(ema, bool):
+        raise ValueError(f"generate.ema={ema!r}: expected true or false")
+    if ckpt_smooth is not None:
+        if ema:
+            raise ValueError("generate.ema=true does not combine with generate.ckpt_smooth (an average of raw checkpoints)")
+        return "model_state_dict"
+    has = checkpoint is not None and "ema_state_dict" in checkpoint
+    if ema and not has:
+        raise ValueError("generate.ema=true, but the checkpoint holds no ema_state_dict (train with train.ema_decay)")
+    return "ema_state_dict" if (has and ema is not False) else "model_state_dict"
+
+
 # --------------------------------------------------------------------------- generate
 def _load_clip(dataset_cfg, stem, audio_length, conditional):
     """``<dataset.data_path>/<stem>.wav`` as a [1, 1, audio_length] clip in [-1, 1], read as ``train.SpeechCommands``
@@ -217,7 +234,7 @@ def generate(rank, diffusion_cfg, model_cfg, dataset_cfg, ckpt_iter="max", n_sam
              written=None, precision=None, sampler="ddpm", steps=None, eta=0.0, known_name=None, keep=None,
              start_name=None, start_step=None, start_noise=True, resample_jump=None, resample_n=None, spacing=None,
              guide_name=None, guide_op=None, guide_clip=None, guide_factor=None, guide_scale=None, label=None,
-             cfg_scale=None):
+             cfg_scale=None, ema=None):
     """``generate.py:58-200``.  ``ckpt_iter`` may additionally be ``"init"``: seeded random weights
     (no checkpoint), for smoke runs without trained weights.  ``precision`` (not in the reference; CLI:
     ``+engine.precision=bf16x6|f16x3``): the engine's opt-in matrix arithmetic, see ``include/dws.h``.
@@ -250,7 +267,11 @@ def generate(rank, diffusion_cfg, model_cfg, dataset_cfg, ckpt_iter="max", n_sam
     null class), a list of them cycled over the samples, or ``all`` (= 0..K-1 in turn); the wav names get ``_c{label}``.
     ``cfg_scale`` adds classifier-free guidance (``sampling``'s ``cfg_scale``: twice the network batch per step); it needs
     ``label`` and does not combine with the editing or restoration keys.  No trained class-conditional weights exist
-    here: what the samples sound like has not been measured."""
+    here: what the samples sound like has not been measured.
+
+    ``ema`` (not in the reference; CLI ``+generate.ema=true|false``): which weights of the checkpoint are sampled, see
+    ``weights_key``.  The default takes ``ema_state_dict`` when the checkpoint has one (runs trained with
+    ``train.ema_decay``) and ``model_state_dict`` otherwise."""
     from .models import construct_model
     from .models.utils import check_n_classes
     from .sampling import (calc_diffusion_hyperparams, ddim_steps, declip_operator, logsnr_steps, lowpass_operator,
@@ -258,6 +279,8 @@ def generate(rank, diffusion_cfg, model_cfg, dataset_cfg, ckpt_iter="max", n_sam
                            sampling_guided, spans_to_mask)
     from scipy.io.wavfile import write as wavwrite
 
+    if ckpt_smooth is not None or ckpt_iter == "init":     # checked here, before a model is built
+        weights_key(None, ema, ckpt_smooth)
     if guide_name is None:
         given = [k for k, v in (("guide_op", guide_op), ("guide_clip", guide_clip), ("guide_factor", guide_factor),
                                 ("guide_scale", guide_scale)) if v is not None]
@@ -372,9 +395,15 @@ def generate(rank, diffusion_cfg, model_cfg, dataset_cfg, ckpt_iter="max", n_sam
             model_file = os.path.join(ckpt_path, f"{ckpt_iter}.pkl")
             try:
                 checkpoint = torch.load(model_file, map_location="cpu")
-                net.load_state_dict(checkpoint["model_state_dict"])
             except Exception as e:  # the reference raises a bare 'No valid model found' (`generate.py:110-112`)
                 raise Exception(f"No valid model found ({model_file}: {e})")
+            key = weights_key(checkpoint, ema)
+            try:
+                net.load_state_dict(checkpoint[key])
+            except Exception as e:
+                raise Exception(f"No valid model found ({model_file}: {e})")
+            if key == "ema_state_dict":
+                print(f"sampling from the EMA weights of iteration {ckpt_iter} (generate.ema=false: the raw weights)")
         else:                       # `generate.py:113-115`: average of the checkpoints in (ckpt_smooth, ckpt_iter]
             state_dict = smooth_ckpt(ckpt_path, int(ckpt_smooth), ckpt_iter)
             if state_dict is None:

@@ -176,13 +176,47 @@ def optim_param_groups(net, honour_hints=False):
     return groups
 
 
+def optimizer_options(optimizer=None, ema_decay=None, clip_grad_norm=None):
+    """The optimizer keys of the ``train`` group, checked (before any model is built): ``train.optimizer`` = ``torch``
+    (default: ``torch.optim.Adam``, the reference's) or ``engine`` (``optim.EngineAdam``, the fused HIP step);
+    ``train.ema_decay`` = D with 0 < D < 1 and ``train.clip_grad_norm`` = C > 0 both need ``optimizer=engine``.
+    Returns ``(kind, ema_decay or None, clip_grad_norm or None)``."""
+    kind = "torch" if optimizer is None else optimizer
+    if kind not in ("torch", "engine"):
+        raise ValueError(f"train.optimizer={optimizer!r}: expected engine or torch")
+
+    def number(key, v):
+        if isinstance(v, (bool, str)) or not isinstance(v, (int, float)) or not np.isfinite(float(v)):
+            raise ValueError(f"train.{key}={v!r}: expected a number")
+        return float(v)
+    if ema_decay is not None:
+        ema_decay = number("ema_decay", ema_decay)
+        if not 0.0 < ema_decay < 1.0:
+            raise ValueError(f"train.ema_decay={ema_decay!r} (needs 0 < D < 1)")
+        if kind != "engine":
+            raise ValueError("train.ema_decay needs train.optimizer=engine (the EMA is part of the fused step)")
+    if clip_grad_norm is not None:
+        clip_grad_norm = number("clip_grad_norm", clip_grad_norm)
+        if not clip_grad_norm > 0.0:
+            raise ValueError(f"train.clip_grad_norm={clip_grad_norm!r} (needs C > 0)")
+        if kind != "engine":
+            raise ValueError("train.clip_grad_norm needs train.optimizer=engine (the clipping is part of the fused step)")
+    return kind, ema_decay, clip_grad_norm
+
+
 def train(rank, num_gpus, diffusion_cfg, model_cfg, dataset_cfg, generate_cfg, ckpt_iter, n_iters, iters_per_ckpt,
           iters_per_logging, learning_rate, batch_size_per_gpu, name=None, exp_root="exp", num_workers=4, precision=None,
-          honour_optim_hints=False, label_dropout=None):
+          honour_optim_hints=False, label_dropout=None, optimizer=None, ema_decay=None, clip_grad_norm=None):
     """``train.py:49-196``.  With ``model.n_classes`` (class-conditional; not in the reference) every batch's class
     indices go to the network and ``label_dropout`` (``train.label_dropout``, default 0.1) of them are replaced by the
     null class, which is what classifier-free guidance needs at sampling time; the in-loop ``generate`` cycles the
-    classes."""
+    classes.
+
+    ``optimizer`` / ``ema_decay`` / ``clip_grad_norm`` (``+train.optimizer=engine +train.ema_decay=0.9999
+    +train.clip_grad_norm=1.0``; not in the reference): see ``optimizer_options``.  With an EMA the checkpoints also hold
+    ``ema_state_dict`` (the averaged weights in the layout of ``model_state_dict``), which ``generate`` then samples
+    from; a resume restores it, or starts it from the loaded weights when the checkpoint has none."""
+    opt_kind, ema_decay, clip_grad_norm = optimizer_options(optimizer, ema_decay, clip_grad_norm)
     from .distributed_util import apply_gradient_allreduce, reduce_tensor
     from .models import construct_model
     from .sampling import calc_diffusion_hyperparams
@@ -212,7 +246,11 @@ def train(rank, num_gpus, diffusion_cfg, model_cfg, dataset_cfg, generate_cfg, c
     learning_rate = float(learning_rate)
     groups = optim_param_groups(net, str(honour_optim_hints).lower() in ("1", "true"))
     own_lr = [isinstance(g, dict) and "lr" in g for g in groups] if isinstance(groups[0], dict) else [False]
-    optimizer = torch.optim.Adam(groups, lr=learning_rate)
+    if opt_kind == "engine":
+        from .optim import EngineAdam
+        optimizer = EngineAdam(groups, lr=learning_rate, ema_decay=ema_decay, max_grad_norm=clip_grad_norm, module=net)
+    else:
+        optimizer = torch.optim.Adam(groups, lr=learning_rate)
 
     if ckpt_iter == "max":
         ckpt_iter = find_max_epoch(checkpoint_directory)
@@ -226,11 +264,19 @@ def train(rank, num_gpus, diffusion_cfg, model_cfg, dataset_cfg, generate_cfg, c
                 for g, own in zip(optimizer.param_groups, own_lr):    # `train.py:111-112` (one group there); a hinted lr stays
                     if not own:
                         g["lr"] = learning_rate
+            if ema_decay is not None:
+                if "ema_state_dict" in checkpoint:
+                    optimizer.load_ema_state_dict(checkpoint["ema_state_dict"])
+                else:
+                    optimizer.reset_ema()
+                    print(f"checkpoint {ckpt_iter} holds no ema_state_dict: the EMA starts from the loaded weights")
             print(f"Successfully loaded model at iteration {ckpt_iter}")
         except Exception as e:   # the reference swallows the error the same way (`train.py:115-117`)
             print(f"Model checkpoint found at iteration {ckpt_iter}, but was not successfully loaded ({e}) - "
                   "training from scratch.")
             ckpt_iter = -1
+            if ema_decay is not None:
+                optimizer.reset_ema()       # (a partly loaded model: the shadows follow whatever the weights are now)
     else:
         print("No valid checkpoint model found - training from scratch.")
         ckpt_iter = -1
@@ -270,10 +316,15 @@ def train(rank, num_gpus, diffusion_cfg, model_cfg, dataset_cfg, generate_cfg, c
             epoch_loss += reduced_loss
             n_batches += 1
             if n_iter % iters_per_logging == 0:
-                log({"train/loss": reduced_loss, "train/log_loss": float(np.log(reduced_loss))}, n_iter)
+                record = {"train/loss": reduced_loss, "train/log_loss": float(np.log(reduced_loss))}
+                if clip_grad_norm is not None:      # (the norm lives on the device: read at logging iterations only)
+                    record["train/grad_norm"] = float(optimizer.grad_norm)
+                log(record, n_iter)
             if n_iter % iters_per_ckpt == 0 and rank == 0:
-                torch.save({"model_state_dict": net.state_dict(), "optimizer_state_dict": optimizer.state_dict()},
-                           os.path.join(checkpoint_directory, f"{n_iter}.pkl"))
+                saved = {"model_state_dict": net.state_dict(), "optimizer_state_dict": optimizer.state_dict()}
+                if ema_decay is not None:       # (the in-loop generate below samples from it)
+                    saved["ema_state_dict"] = optimizer.ema_state_dict(net)
+                torch.save(saved, os.path.join(checkpoint_directory, f"{n_iter}.pkl"))
                 print(f"model at iteration {n_iter} is saved")
                 if generate_cfg and generate_cfg.get("n_samples", 0):
                     if not model_cfg["unconditional"]:

@@ -249,6 +249,48 @@ int dws_model_set_grad_sinks(dws_model* m, int32_t count, const char* const* nam
 int dws_model_grad_group_wait(dws_model* m, int32_t group, void* waiting_stream);
 int dws_model_grad_ready_seq(dws_model* m, int32_t count, const char* const* names, int32_t* seq_out);
 
+/* ---- Fused optimizer step (not in the reference, whose `train.py:91` builds torch.optim.Adam) --------------------------
+ * ONE pass over a table of `count` float32 tensors that does, per element,
+ *     g'  = coef * g  (+ weight_decay * p)                      coef = 1 without clipping
+ *     m  += (g' - m) (1 - beta1)
+ *     v   = beta2 v + (1 - beta2) g'^2
+ *     p  -= lr / (1 - beta1^t) * m / (sqrt(v) / sqrt(1 - beta2^t) + eps)
+ *     ema = ema + (1 - ema_decay) (p - ema)                     where ema[i] is given
+ *     mirror = p                                                where a mirror is given
+ * i.e. torch.optim.Adam (amsgrad=False, maximize=False, L2 weight decay) operation by operation in fp32 with correctly
+ * rounded division and square root, the EMA shadow as `ema.lerp_(p, 1 - ema_decay)`, and the engine's raw copy of the
+ * parameter.  16 bytes read + 12 written per element, +4 with a mirror, +8 with a shadow.  The bias corrections are formed
+ * in double from the integer step[i]; lr, step and weight_decay are per tensor (parameter groups).
+ *
+ * The handle owns the pinned staging ring of the job table (a slot is reused only after the event behind its upload has
+ * completed; while none is free the ring grows: the host does not wait for the GPU), the device table and the norm scratch.
+ * Two corner cases do wait, and nothing else does: a call that needs a larger device table than the handle has (the first
+ * call, or more tensors than twice any earlier call) frees and reallocates it, which synchronises the device; and a ring
+ * that has grown to 64 slots, all still in flight (the host 64 steps ahead of the GPU), waits for the oldest one.
+ * Calls on one handle must be ordered on one stream.  dws_optim_chunk: tensors are cut into chunks of that many elements
+ * (the grid is capped at 2048 workgroups of 256 threads that loop over the chunks).  A tensor whose every pointer is 16-byte
+ * aligned moves as 16-byte vectors, any other (4-byte aligned views of a flat buffer) element by element.
+ *
+ * ema, mirrors, weight_decay: NULL tables or NULL entries = none.  ema_decay in (0, 1) is needed with shadows.
+ * max_grad_norm > 0: torch.nn.utils.clip_grad_norm_ with the L2 norm over ALL `count` gradients,
+ * coef = min(1, max_grad_norm / (norm + 1e-6)), as a second launch BEFORE the step: per-workgroup partial sums in double, a
+ * fixed-order final sum by the workgroup that finishes last (no floating-point atomics: same bits from run to run), the
+ * norm in a device float the step reads.  The gradients themselves are NOT rewritten (torch scales p.grad in place).  A
+ * non-finite norm propagates into every element, as it does in torch.  grad_norm_out (device float, may be NULL) receives
+ * the norm; given without clipping, the norm launch runs for it alone.  Nothing synchronises with the host.
+ *
+ * model (may be NULL) with names[count]: tensor i with names[i] != NULL is the model's parameter of that name -- its raw
+ * slot becomes the mirror (mirrors[i] is ignored), and the model is marked as dws_model_update_params marks it (the next
+ * forward commits again).  Unknown name, a non-float32 parameter or another element count -> DWS_ERR_INVALID. */
+typedef struct dws_optim dws_optim;
+int dws_optim_create(dws_optim** out);
+int dws_optim_destroy(dws_optim* o);
+int dws_optim_chunk(void);
+int dws_optim_step(dws_optim* o, int32_t count, float* const* params, const float* const* grads, float* const* exp_avg,
+                   float* const* exp_avg_sq, float* const* ema, float* const* mirrors, const int64_t* numels, const double* lr,
+                   const int64_t* step, const double* weight_decay, double beta1, double beta2, double eps, double ema_decay,
+                   double max_grad_norm, float* grad_norm_out, dws_model* model, const char* const* names, void* stream);
+
 /* Debug/parity tap: copy an internal activation into `dst` (device pointer,
  * `capacity` floats).  WaveNet: "pre_final" = ReLU(final_conv[0](skip)) [B,S,L],
  * "skip" [B,S,L], "x" (last residual output) [B,C,L], "hsave" [n_layers,B,2C,L] (the gate

@@ -5,7 +5,8 @@
 
 prints: the step's span, busy time, idle time (gaps between consecutive launches on the device), the gaps grouped by the
 kernel that FOLLOWS them, the small launches (< 12 us) grouped by kernel, and with --seq the whole sequence.
-A step boundary is the optimizer's first multi_tensor_apply launch after a run of non-optimizer launches."""
+A step boundary is the optimizer's first launch after a run of non-optimizer launches: torch's multi_tensor_apply, or the
+engine's own step (train.optimizer=engine: engine_adam_norm_kernel / engine_adam_step_kernel)."""
 import csv
 import sys
 from collections import defaultdict
@@ -24,7 +25,7 @@ def main():
             rows.append((int(r["Start_Timestamp"]), int(r["End_Timestamp"]), r["Kernel_Name"]))
     rows.sort()
     # step boundaries: the first Adam launch after something that is not Adam
-    is_opt = [("multi_tensor_apply" in n) for _, _, n in rows]
+    is_opt = [("multi_tensor_apply" in n or "engine_adam_" in n) for _, _, n in rows]
     bounds = [i for i in range(1, len(rows)) if is_opt[i] and not is_opt[i - 1]]
     # the end of a step = the last consecutive optimizer launch after bounds[k]
     ends = []
