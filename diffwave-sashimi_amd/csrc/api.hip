@@ -99,14 +99,10 @@ int dws_model::set_labels(const int32_t* labels, int64_t nB, hipStream_t s) {
 void dws_model::drop_graph() {
     if (smp_graph) hipGraphExecDestroy(smp_graph);
     smp_graph = nullptr;
-    if (sch_graph) hipGraphExecDestroy(sch_graph);
-    sch_graph = nullptr;
-    if (edit_graph) hipGraphExecDestroy(edit_graph);
-    edit_graph = nullptr;
-    if (prog_graph) hipGraphExecDestroy(prog_graph);
-    prog_graph = nullptr;
-    if (cfg_graph) hipGraphExecDestroy(cfg_graph);
-    cfg_graph = nullptr;
+    for (SchGraph& g : sch_graphs) {
+        if (g.exec) hipGraphExecDestroy(g.exec);
+        g.exec = nullptr;
+    }
 }
 
 dws::ParamSpec* dws_model::add_param(const std::string& name, std::vector<int64_t> shape, int dtype) {

@@ -175,7 +175,6 @@ struct dws_model {
 
     // sampler state (sampler.hip)
     dws::DevBuf smp_tables;   // [3][T] c1, c2, sigma
-    int smp_T = 0;            // length of the uploaded tables
     std::vector<float> smp_host_tables;  // host copy of what is resident (upload skipped when identical)
     dws::DevBuf smp_state;    // int32 step index
     dws::DevBuf smp_eps;      // eps[B, Cout, L]
@@ -199,7 +198,6 @@ struct dws_model {
                                           // int32 history-valid word (DPM-Solver++(2M): sch_hist holds the last step's x0)
     dws::DevBuf sch_x;                    // [B, C, L]
     dws::DevBuf sch_hist;                 // [B, C, L] the previous step's data prediction (DWS_SAMPLER_DPMPP2M; first use)
-    hipGraphExec_t sch_graph = nullptr;
     struct SchKey {
         int64_t B, L;
         int S, kind, vec;
@@ -215,30 +213,30 @@ struct dws_model {
                    edit == o.edit && known == o.known && mask == o.mask && known_noise == o.known_noise && V == o.V &&
                    prog == o.prog && hist == o.hist;
         }
-    } sch_key{};
-    // editing (dws_sampler_run_edit): the step that ends in the replacement of the known region is a graph of its own
-    // beside sch_graph (same state, x, eps and step table), so edited and unedited calls alternate without a capture.
-    // The known clip and the mask are copied into model-owned buffers before the replays, like x into sch_x.
+    };
+    // One captured step per flavour of call (same state, x, eps and step table), so the flavours alternate without a new
+    // capture: the unedited step, the step that ends in the replacement of the known region (dws_sampler_run_edit), the
+    // reverse visit of a program (dws_sampler_run_program) and the guided step (dws_sampler_set_cfg).
+    enum { SCH_PLAIN, SCH_EDIT, SCH_PROG, SCH_CFG, SCH_GRAPHS };
+    struct SchGraph {
+        hipGraphExec_t exec = nullptr;
+        SchKey key{};
+    } sch_graphs[SCH_GRAPHS];
+    // editing: the known clip and the mask are copied into model-owned buffers before the replays, like x into sch_x.
     dws::DevBuf sch_edit;                 // [2][S] q1, q2 of sampling.edit_coefficients
     std::vector<float> sch_host_edit;     // host copy of what is resident
     dws::DevBuf sch_known;                // float [B, C, L]
     dws::DevBuf sch_mask;                 // uint8 [B, C, L] (rounded up to whole groups of four)
-    hipGraphExec_t edit_graph = nullptr;
-    SchKey edit_key{};
-    // resampling (dws_sampler_run_program): the reverse visit of a program is a third graph beside the two above; the
-    // program tables sit in a model-owned buffer keyed on their contents, so a new program of the same V replays it.
+    // resampling: the program tables sit in a model-owned buffer keyed on their contents, so a new program of the same V
+    // replays the held graph.
     dws::DevBuf sch_prog;                 // int32 step_of[V], float ja[V], jb[V], indexed by the visit number
     std::vector<uint32_t> sch_host_prog;  // host copy of what is resident
-    hipGraphExec_t prog_graph = nullptr;
-    SchKey prog_key{};
     uint64_t step_table_gen = 0;          // bumped by every step-table rebuild (build_step_table)
-    // classifier-free guidance in the schedule step (dws_sampler_set_cfg): the model is prepared for 2 Bc clips, the
-    // first half carries the wanted labels and the second the null class; the update runs on the first half alone.
-    // The guided step is a fourth graph beside the three above; the scale sits in the device state (word 6).
+    // classifier-free guidance in the schedule step: the model is prepared for 2 Bc clips, the first half carries the
+    // wanted labels and the second the null class; the update runs on the first half alone.  The scale sits in the
+    // device state (word 6).
     bool cfg_on = false;
     float cfg_scale = 0.f;
-    hipGraphExec_t cfg_graph = nullptr;
-    SchKey cfg_key{};
 
     // ---- class conditioning (dws_model_set_classes / dws_model_set_labels): one parameter "label_embedding.weight"
     // [K+1][Eout] beside fc_t1 / fc_t2 (row K = the null class); a clip's row is added to the output of the embedding MLP,
