@@ -114,6 +114,10 @@ _SIGS = {
                                                ctypes.POINTER(ctypes.c_float), c_f32p, ctypes.c_uint64, ctypes.c_int32,
                                                ctypes.c_int32, ctypes.POINTER(SamplerEdit), ctypes.c_void_p]),
     "dws_philox_normal": (ctypes.c_int, [c_f32p, ctypes.c_int64, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_void_p]),
+    "dws_sampler_set_clip_seeds": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint64), ctypes.c_int64,
+                                                  ctypes.c_void_p]),
+    "dws_philox_normal_clips": (ctypes.c_int, [c_f32p, ctypes.c_int64, ctypes.c_int64, ctypes.POINTER(ctypes.c_uint64),
+                                               ctypes.c_uint32, ctypes.c_void_p]),
     "dws_mel_spectrogram": (ctypes.c_int, [c_f32p, ctypes.c_int64, ctypes.c_int64, c_f32p, c_f32p, ctypes.c_int32,
                                            ctypes.c_int32, ctypes.c_int32, ctypes.c_float, c_f32p, ctypes.c_void_p]),
     "dws_gemm_bf16x6": (ctypes.c_int, [c_f32p] * 3 + [ctypes.c_int64] * 3 + [ctypes.c_void_p]),

@@ -18,6 +18,7 @@ int sampler_run_program(dws_model* m, float* x, int kind, int S, const float* ne
                         const int32_t* visit_step, const float* jump_coef, const float* noise, uint64_t seed,
                         int init_from_seed, int use_graph, const dws_sampler_edit* e, hipStream_t s);
 int philox_normal(float* x, int64_t n, uint64_t seed, uint32_t stream_id, hipStream_t s);
+int philox_normal_clips(float* x, int64_t B, int64_t n_per_clip, const uint64_t* seeds, uint32_t stream_id, hipStream_t s);
 }  // namespace dws
 
 dws_model::~dws_model() {
@@ -32,6 +33,10 @@ dws_model::~dws_model() {
     for (int i = 0; i < LABEL_SLOTS; ++i) {
         if (label_consumed[i]) (void)hipEventDestroy(label_consumed[i]);
         if (label_pinned[i]) (void)hipHostFree(label_pinned[i]);
+    }
+    for (int i = 0; i < SEED_SLOTS; ++i) {
+        if (seed_consumed[i]) (void)hipEventDestroy(seed_consumed[i]);
+        if (seed_pinned[i]) (void)hipHostFree(seed_pinned[i]);
     }
     for (auto& g : grad_groups)
         if (g.ev) (void)hipEventDestroy(g.ev);
@@ -96,13 +101,41 @@ int dws_model::set_labels(const int32_t* labels, int64_t nB, hipStream_t s) {
     return DWS_OK;
 }
 
+// The grid of a per-clip launch has one row per clip: at most 65535 clips.
+int dws_model::set_clip_seeds(const uint64_t* seeds, int64_t nB, hipStream_t s) {
+    if (!seeds) {
+        clip_B = 0;
+        return DWS_OK;
+    }
+    DWS_CHECK(B > 0, DWS_ERR_STATE, "dws_sampler_set_clip_seeds before dws_model_prepare");
+    DWS_CHECK(nB >= 1 && nB <= 65535, DWS_ERR_INVALID, "dws_sampler_set_clip_seeds: %lld seeds (needs 1 .. 65535)", (long long)nB);
+    DWS_TRY(clip_seeds_dev.ensure((size_t)nB * 8));
+    // pinned staging, round robin with an event per slot: the host only ever waits for the upload made SEED_SLOTS calls ago
+    const int slot = seed_slot;
+    seed_slot = (slot + 1) % SEED_SLOTS;
+    if (!seed_consumed[slot]) DWS_HIP(hipEventCreateWithFlags(&seed_consumed[slot], hipEventDisableTiming));
+    else DWS_HIP(hipEventSynchronize(seed_consumed[slot]));
+    if (seed_pinned_cap[slot] < (size_t)nB) {
+        if (seed_pinned[slot]) (void)hipHostFree(seed_pinned[slot]);
+        seed_pinned[slot] = nullptr;
+        seed_pinned_cap[slot] = (size_t)nB * 2;
+        DWS_HIP(hipHostMalloc((void**)&seed_pinned[slot], seed_pinned_cap[slot] * 8, hipHostMallocDefault));
+    }
+    std::memcpy(seed_pinned[slot], seeds, (size_t)nB * 8);
+    DWS_HIP(hipMemcpyAsync(clip_seeds_dev.p, seed_pinned[slot], (size_t)nB * 8, hipMemcpyHostToDevice, s));
+    DWS_HIP(hipEventRecord(seed_consumed[slot], s));
+    clip_B = nB;
+    return DWS_OK;
+}
+
 void dws_model::drop_graph() {
     if (smp_graph) hipGraphExecDestroy(smp_graph);
     smp_graph = nullptr;
-    for (SchGraph& g : sch_graphs) {
-        if (g.exec) hipGraphExecDestroy(g.exec);
-        g.exec = nullptr;
-    }
+    for (auto& flavour : sch_graphs)
+        for (SchGraph& g : flavour) {
+            if (g.exec) hipGraphExecDestroy(g.exec);
+            g.exec = nullptr;
+        }
 }
 
 dws::ParamSpec* dws_model::add_param(const std::string& name, std::vector<int64_t> shape, int dtype) {
@@ -343,6 +376,7 @@ int dws_model_prepare(dws_model* m, int64_t B, int64_t L) {
     const int64_t B0 = m->B, L0 = m->L;
     DWS_TRY(m->prepare(B, L));
     if (m->n_classes > 0 && (B0 != m->B || L0 != m->L)) DWS_TRY(m->reset_labels());   // labels belong to a shape
+    if (B0 != m->B || L0 != m->L) m->clip_B = 0;                                        // and so does a seed table
     return DWS_OK;
 }
 
@@ -363,6 +397,11 @@ int dws_sampler_set_cfg(dws_model* m, int32_t on, float scale) {
     m->cfg_on = on != 0;
     m->cfg_scale = on ? scale : 0.f;
     return DWS_OK;
+}
+
+int dws_sampler_set_clip_seeds(dws_model* m, const uint64_t* seeds, int64_t B, void* stream) {
+    DWS_CHECK(m, DWS_ERR_INVALID, "null model");
+    return m->set_clip_seeds(seeds, B, (hipStream_t)stream);
 }
 
 int dws_model_set_condition(dws_model* m, const float* mel, int64_t Bm, int64_t Tmel, void* stream) {
@@ -659,6 +698,7 @@ int dws_sampler_run(dws_model* m, float* x, const float* alpha, const float* alp
                     void* stream) {
     DWS_CHECK(m && x, DWS_ERR_INVALID, "dws_sampler_run: null argument");
     DWS_CHECK(!m->cfg_on, DWS_ERR_UNSUPPORTED, "classifier-free guidance runs on dws_sampler_run_schedule only (dws_sampler_run)");
+    DWS_CHECK(m->clip_B == 0, DWS_ERR_UNSUPPORTED, "per-clip seeds run on the schedule entries only (dws_sampler_run)");
     return dws::sampler_run(m, x, alpha, alpha_bar, sigma, T, noise, seed, init_from_seed, use_graph,
                             (hipStream_t)stream);
 }
@@ -667,6 +707,7 @@ int dws_sampler_steps(dws_model* m, float* x, const float* alpha, const float* a
                       int32_t T, int32_t t_start, int32_t n_steps, uint64_t seed, int32_t use_graph, void* stream) {
     DWS_CHECK(m && x, DWS_ERR_INVALID, "dws_sampler_steps: null argument");
     DWS_CHECK(!m->cfg_on, DWS_ERR_UNSUPPORTED, "classifier-free guidance runs on dws_sampler_run_schedule only (dws_sampler_steps)");
+    DWS_CHECK(m->clip_B == 0, DWS_ERR_UNSUPPORTED, "per-clip seeds run on the schedule entries only (dws_sampler_steps)");
     return dws::sampler_steps(m, x, alpha, alpha_bar, sigma, T, t_start, n_steps, seed, use_graph,
                               (hipStream_t)stream);
 }
@@ -700,6 +741,11 @@ int dws_sampler_run_program(dws_model* m, float* x, int32_t kind, int32_t S, con
 
 int dws_philox_normal(float* x, int64_t n, uint64_t seed, uint32_t stream_id, void* stream) {
     return dws::philox_normal(x, n, seed, stream_id, (hipStream_t)stream);
+}
+
+int dws_philox_normal_clips(float* x, int64_t B, int64_t n_per_clip, const uint64_t* seeds, uint32_t stream_id,
+                            void* stream) {
+    return dws::philox_normal_clips(x, B, n_per_clip, seeds, stream_id, (hipStream_t)stream);
 }
 
 }  // extern "C"

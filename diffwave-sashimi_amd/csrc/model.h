@@ -207,21 +207,24 @@ struct dws_model {
         int V = 0;                                       // the resampling step's: visits and the program tables
         const void* prog = nullptr;
         const void* hist = nullptr;                      // the multistep kind's history buffer (null for the others)
+        const void* clip_seeds = nullptr;                // the per-clip seed table (null for a scalar-seed step)
         bool operator==(const SchKey& o) const {
             return B == o.B && L == o.L && S == o.S && kind == o.kind && vec == o.vec && tables == o.tables &&
                    noise == o.noise && eps == o.eps && x == o.x && state == o.state && table_gen == o.table_gen &&
                    edit == o.edit && known == o.known && mask == o.mask && known_noise == o.known_noise && V == o.V &&
-                   prog == o.prog && hist == o.hist;
+                   prog == o.prog && hist == o.hist && clip_seeds == o.clip_seeds;
         }
     };
     // One captured step per flavour of call (same state, x, eps and step table), so the flavours alternate without a new
     // capture: the unedited step, the step that ends in the replacement of the known region (dws_sampler_run_edit), the
-    // reverse visit of a program (dws_sampler_run_program) and the guided step (dws_sampler_set_cfg).
+    // reverse visit of a program (dws_sampler_run_program) and the guided step (dws_sampler_set_cfg) -- each once for the
+    // scalar seed ([0]) and once for per-clip seeds ([1]: other kernel instances on a grid row per clip), so the two forms
+    // of seed alternate without a new capture as well.
     enum { SCH_PLAIN, SCH_EDIT, SCH_PROG, SCH_CFG, SCH_GRAPHS };
     struct SchGraph {
         hipGraphExec_t exec = nullptr;
         SchKey key{};
-    } sch_graphs[SCH_GRAPHS];
+    } sch_graphs[SCH_GRAPHS][2];
     // editing: the known clip and the mask are copied into model-owned buffers before the replays, like x into sch_x.
     dws::DevBuf sch_edit;                 // [2][S] q1, q2 of sampling.edit_coefficients
     std::vector<float> sch_host_edit;     // host copy of what is resident
@@ -237,6 +240,17 @@ struct dws_model {
     // device state (word 6).
     bool cfg_on = false;
     float cfg_scale = 0.f;
+    // per-clip seeds (dws_sampler_set_clip_seeds): clip b draws from Philox key clip_seeds[b] with groups numbered inside
+    // the clip, so its noise does not depend on the batch around it.  The table sits in device memory (a new one replays
+    // the captured step) and holds until it is changed or the model is prepared for another shape.
+    dws::DevBuf clip_seeds_dev;           // uint64 [clip_B]
+    int64_t clip_B = 0;                   // clips the table holds (0: off, the scalar seed of the run entries)
+    static constexpr int SEED_SLOTS = 4;  // pinned staging of the upload, as the label assignment (LABEL_SLOTS)
+    uint64_t* seed_pinned[SEED_SLOTS] = {nullptr, nullptr, nullptr, nullptr};
+    size_t seed_pinned_cap[SEED_SLOTS] = {0, 0, 0, 0};
+    hipEvent_t seed_consumed[SEED_SLOTS] = {nullptr, nullptr, nullptr, nullptr};
+    int seed_slot = 0;
+    int set_clip_seeds(const uint64_t* seeds, int64_t nB, hipStream_t s);
 
     // ---- class conditioning (dws_model_set_classes / dws_model_set_labels): one parameter "label_embedding.weight"
     // [K+1][Eout] beside fc_t1 / fc_t2 (row K = the null class); a clip's row is added to the output of the embedding MLP,

@@ -72,8 +72,24 @@ __global__ void smp_set_program_state_kernel(int* st, int t, int v, uint64_t see
 // this one -- no separate one-thread launch per step.
 // hist_valid >= 0: the new value of the history-valid word (1 behind a multistep step); the plain sampler's two-word
 // state passes -1.
-__device__ __forceinline__ void smp_step_advance(int* __restrict__ st, int s, int hist_valid) {
-    if (atomicAdd(reinterpret_cast<unsigned*>(st + 1), 1u) == gridDim.x - 1) {
+// Per-clip seeds (dws_sampler_set_clip_seeds).  A CLIP instance of a drawing kernel runs on a grid with one row per clip:
+// row b works on elements b n_c .. (b + 1) n_c - 1 of every array with the Philox key seeds[b] and counts its groups of
+// four from the start of the clip -- the launch a B = 1 run with the scalar seed seeds[b] makes, B times side by side
+// (n_c = C L elements of a clip; the VEC form needs n_c % 4 == 0, so a group never straddles two clips).  The scalar
+// instances (CLIP = false) read neither field and keep their code.
+struct ClipSeeds {
+    const uint64_t* seeds;       // device [B]
+    size_t n_c;
+};
+
+// blocks of the whole grid: what the last-block counters below count up to
+template <bool CLIP>
+__device__ __forceinline__ unsigned smp_grid_blocks() {
+    return CLIP ? gridDim.x * gridDim.y : gridDim.x;
+}
+
+__device__ __forceinline__ void smp_step_advance(int* __restrict__ st, int s, int hist_valid, unsigned blocks) {
+    if (atomicAdd(reinterpret_cast<unsigned*>(st + 1), 1u) == blocks - 1) {
         st[1] = 0;
         st[0] = s - 1;
         if (hist_valid >= 0) st[5] = hist_valid;
@@ -83,8 +99,8 @@ __device__ __forceinline__ void smp_step_advance(int* __restrict__ st, int s, in
 // The program flavour: the last block moves the program on, visit <- v - 1 and step <- step_of[v - 1] (the row the next
 // visit's network reads; -1 behind the last visit).  hist_valid: 1 behind a multistep reverse visit, 0 behind a jump visit.
 __device__ __forceinline__ void smp_program_advance(int* __restrict__ st, const int* __restrict__ step_of, int v,
-                                                    int hist_valid) {
-    if (atomicAdd(reinterpret_cast<unsigned*>(st + 1), 1u) == gridDim.x - 1) {
+                                                    int hist_valid, unsigned blocks) {
+    if (atomicAdd(reinterpret_cast<unsigned*>(st + 1), 1u) == blocks - 1) {
         st[1] = 0;
         st[4] = v - 1;
         st[0] = v > 0 ? step_of[v - 1] : -1;
@@ -211,17 +227,45 @@ __global__ void smp_fill_normal_kernel(float* __restrict__ x, size_t n, uint64_t
     }
 }
 
+// The per-clip twin: row b = blockIdx.y of x [B, n_c] is smp_fill_normal_kernel(x + b n_c, n_c, seeds[b], stream_id).
+// SEEDS: the model's device table, or a chunk of host seeds travelling by value (dws_philox_normal_clips).
+struct SeedChunk {
+    static constexpr int N = 64;
+    uint64_t s[N];
+    __device__ uint64_t operator[](unsigned b) const { return s[b]; }
+};
+
+template <class SEEDS>
+__global__ void smp_fill_normal_clips_kernel(float* __restrict__ x, size_t n_c, const SEEDS seeds, uint32_t stream_id) {
+    const uint64_t seed = seeds[blockIdx.y];
+    x += (size_t)blockIdx.y * n_c;
+    for (size_t g = (size_t)blockIdx.x * blockDim.x + threadIdx.x; g * 4 < n_c; g += (size_t)gridDim.x * blockDim.x) {
+        float z[4];
+        normal4(seed, stream_id, g, z);
+        smp_store4<false>(x, g, n_c, z);
+    }
+}
+
 // The full-T sampler's update (dws_sampler_run / dws_sampler_steps) and the plain DDPM kind of the schedule sampler:
 // smp_ddpm_elem at step t = *t_dev with tables [3][T] = c1, c2, sigma; z: noise[t] or Philox (seed, t).
 // seed_dev non-null (few-step sampler): the Philox seed is read from device memory instead of `seed`.
+// CLIP (schedule sampler only): n_all elements in all, this grid row's clip with its own seed (ClipSeeds).
+template <bool CLIP>
 __global__ void smp_update_kernel(float* __restrict__ x, const float* __restrict__ eps,
                                   const float* __restrict__ tables, int* __restrict__ t_dev,
-                                  const float* __restrict__ noise, uint64_t seed, const uint64_t* seed_dev, size_t n,
-                                  int T) {
+                                  const float* __restrict__ noise, uint64_t seed, const uint64_t* seed_dev, size_t n_all,
+                                  int T, const ClipSeeds cs) {
     const int t = __builtin_amdgcn_readfirstlane(*(volatile int*)t_dev);
-    if (seed_dev) seed = *(const volatile uint64_t*)seed_dev;
+    if (CLIP) seed = cs.seeds[blockIdx.y];
+    else if (seed_dev) seed = *(const volatile uint64_t*)seed_dev;
     const float c1 = tables[t], c2 = tables[T + t], sg = tables[2 * T + t];
-    const float* nz = noise ? noise + (size_t)t * n : nullptr;
+    const float* nz = noise ? noise + (size_t)t * n_all : nullptr;
+    const size_t n = CLIP ? cs.n_c : n_all;
+    if (CLIP) {
+        const size_t off = (size_t)blockIdx.y * cs.n_c;
+        x += off; eps += off;
+        if (nz) nz += off;
+    }
     for (size_t g = (size_t)blockIdx.x * blockDim.x + threadIdx.x; g * 4 < n; g += (size_t)gridDim.x * blockDim.x) {
         float z[4] = {0.f, 0.f, 0.f, 0.f};
         if (t > 0 && !nz) normal4(seed, (uint32_t)t, g, z);
@@ -233,7 +277,7 @@ __global__ void smp_update_kernel(float* __restrict__ x, const float* __restrict
         }
     }
     __syncthreads();
-    if (threadIdx.x == 0) smp_step_advance(t_dev, t, -1);
+    if (threadIdx.x == 0) smp_step_advance(t_dev, t, -1, smp_grid_blocks<CLIP>());
 }
 
 // One update of the schedule sampler (dws_sampler_run_schedule / _edit / _program), every flavour of it:
@@ -251,6 +295,7 @@ __global__ void smp_update_kernel(float* __restrict__ x, const float* __restrict
 //         Otherwise v = s, R = S and the last block counts the step down.
 //   VEC   every group of 4 is in range and all pointers are 16-byte aligned -> float4 for the floats and the four mask
 //         bytes of a group as one 32-bit load.
+//   CLIP  per-clip seeds (ClipSeeds above): the grid row's clip of every array, its seed in the place of the state's.
 // What every flavour reads travels as plain kernel arguments, the rest in one by-value struct whose fields a flavour
 // that does not need them never loads.  (Plain arguments are fetched ahead of the ordered reads of the state, fields of a
 // struct only behind them; this way the plain DDIM instance is, instruction for instruction, the kernel it took over from.)
@@ -262,6 +307,7 @@ struct StepMore {
     const float* known_noise;
     const int* step_of;          // PROG ...
     int V;
+    ClipSeeds clip;              // CLIP
 };
 
 struct StepArgs {
@@ -272,35 +318,48 @@ struct StepArgs {
     const float* noise;
     size_t n;
     int S;
+    int clips;                   // grid rows of a per-clip launch (0: the scalar-seed instances)
     StepMore more;
 };
 
-template <int KIND, bool EDIT, bool PROG, bool VEC>
+template <int KIND, bool EDIT, bool PROG, bool VEC, bool CLIP>
 __global__ void smp_step_kernel(float* __restrict__ x, const float* __restrict__ eps, const float* __restrict__ tab,
-                                int* __restrict__ st, const float* __restrict__ noise, size_t n, int S, const StepMore m) {
+                                int* __restrict__ st, const float* __restrict__ noise, size_t n_all, int S,
+                                const StepMore m) {
     constexpr bool MULTI = KIND == DWS_SAMPLER_DPMPP2M;
     const int s = __builtin_amdgcn_readfirstlane(*(volatile int*)st);
     const int v = PROG ? __builtin_amdgcn_readfirstlane(*(volatile int*)(st + 4)) : s;
     const int R = PROG ? m.V : S;
-    const uint64_t seed = !MULTI || EDIT ? *(const volatile uint64_t*)(st + 2) : 0;
+    const uint64_t seed = !(!MULTI || EDIT) ? 0 : CLIP ? m.clip.seeds[blockIdx.y] : *(const volatile uint64_t*)(st + 2);
     const int valid = MULTI ? __builtin_amdgcn_readfirstlane(*(volatile int*)(st + 5)) : 0;
     const float k1 = tab[s], k2 = tab[S + s], k3 = tab[2 * S + s];
     const float k4 = KIND != DWS_SAMPLER_DDPM ? tab[3 * S + s] : 0.f, k5 = KIND != DWS_SAMPLER_DDPM ? tab[4 * S + s] : 0.f;
     const bool add = MULTI ? false : KIND == DWS_SAMPLER_DDIM ? (s > 0 && k5 > 0.f) : s > 0;
     const bool second = MULTI && valid != 0 && k5 != 0.f;
     const float q1 = EDIT ? m.edit[s] : 0.f, q2 = EDIT ? m.edit[S + s] : 0.f;
-    const float* nz = noise ? noise + (size_t)v * n : nullptr;
-    const float* kz = EDIT && m.known_noise ? m.known_noise + (size_t)v * n : nullptr;
+    const float* nz = noise ? noise + (size_t)v * n_all : nullptr;
+    const float* kz = EDIT && m.known_noise ? m.known_noise + (size_t)v * n_all : nullptr;
+    // the rows of every array this block works on: all of them, or (CLIP) those of its grid row's clip
+    const size_t n = CLIP ? m.clip.n_c : n_all;
+    const size_t off = CLIP ? (size_t)blockIdx.y * m.clip.n_c : 0;
+    float* hist = MULTI ? m.hist + off : nullptr;
+    const float* y = EDIT ? m.y + off : nullptr;
+    const uint8_t* mask = EDIT ? m.mask + off : nullptr;
+    if (CLIP) {
+        x += off; eps += off;
+        if (nz) nz += off;
+        if (kz) kz += off;
+    }
     for (size_t g = (size_t)blockIdx.x * blockDim.x + threadIdx.x; g * 4 < n; g += (size_t)gridDim.x * blockDim.x) {
         float xv[4] = {0.f, 0.f, 0.f, 0.f}, ev[4] = {0.f, 0.f, 0.f, 0.f}, z[4] = {0.f, 0.f, 0.f, 0.f};
         float yv[4] = {0.f, 0.f, 0.f, 0.f}, zk[4] = {0.f, 0.f, 0.f, 0.f}, hv[4] = {0.f, 0.f, 0.f, 0.f};
         smp_load4<VEC>(x, g, n, xv);
         smp_load4<VEC>(eps, g, n, ev);
         if (add && nz) smp_load4<VEC>(nz, g, n, z);
-        if (second) smp_load4<VEC>(m.hist, g, n, hv);
-        const uint32_t mk = EDIT ? smp_mask4<VEC>(m.mask, g, n) : 0;
+        if (second) smp_load4<VEC>(hist, g, n, hv);
+        const uint32_t mk = EDIT ? smp_mask4<VEC>(mask, g, n) : 0;
         if (mk) {
-            smp_load4<VEC>(m.y, g, n, yv);
+            smp_load4<VEC>(y, g, n, yv);
             if (s > 0 && kz) smp_load4<VEC>(kz, g, n, zk);
         }
         if (add && !nz) normal4(seed, (uint32_t)v, g, z);
@@ -317,12 +376,12 @@ __global__ void smp_step_kernel(float* __restrict__ x, const float* __restrict__
             }
         }
         smp_store4<VEC>(x, g, n, r);
-        if (MULTI) smp_store4<VEC>(m.hist, g, n, hv);
+        if (MULTI) smp_store4<VEC>(hist, g, n, hv);
     }
     __syncthreads();
     if (threadIdx.x == 0) {
-        if (PROG) smp_program_advance(st, m.step_of, v, MULTI ? 1 : -1);
-        else smp_step_advance(st, s, MULTI ? 1 : -1);
+        if (PROG) smp_program_advance(st, m.step_of, v, MULTI ? 1 : -1, smp_grid_blocks<CLIP>());
+        else smp_step_advance(st, s, MULTI ? 1 : -1, smp_grid_blocks<CLIP>());
     }
 }
 
@@ -331,13 +390,20 @@ __global__ void smp_step_kernel(float* __restrict__ x, const float* __restrict__
 //   x = (ja * x) + (jb * z)      ja = jump[v], jb = jump[V + v] (sampling.jump_coefficients)
 // z: noise[v] or Philox stream v in normal4's layout.  No network runs.  The jump re-noises the state, so the last block
 // also clears the history-valid word: the multistep kind's next step is first order.
-template <bool VEC>
+template <bool VEC, bool CLIP>
 __global__ void smp_jump_kernel(float* __restrict__ x, const float* __restrict__ jump, int* __restrict__ st,
-                                const int* __restrict__ step_of, const float* __restrict__ noise, size_t n, int V) {
+                                const int* __restrict__ step_of, const float* __restrict__ noise, size_t n_all, int V,
+                                const ClipSeeds cs) {
     const int v = __builtin_amdgcn_readfirstlane(*(volatile int*)(st + 4));
-    const uint64_t seed = *(const volatile uint64_t*)(st + 2);
+    const uint64_t seed = CLIP ? cs.seeds[blockIdx.y] : *(const volatile uint64_t*)(st + 2);
     const float ja = jump[v], jb = jump[V + v];
-    const float* nz = noise ? noise + (size_t)v * n : nullptr;
+    const float* nz = noise ? noise + (size_t)v * n_all : nullptr;
+    const size_t n = CLIP ? cs.n_c : n_all;
+    if (CLIP) {
+        const size_t off = (size_t)blockIdx.y * cs.n_c;
+        x += off;
+        if (nz) nz += off;
+    }
     for (size_t g = (size_t)blockIdx.x * blockDim.x + threadIdx.x; g * 4 < n; g += (size_t)gridDim.x * blockDim.x) {
         float xv[4] = {0.f, 0.f, 0.f, 0.f}, z[4] = {0.f, 0.f, 0.f, 0.f};
         smp_load4<VEC>(x, g, n, xv);
@@ -348,14 +414,22 @@ __global__ void smp_jump_kernel(float* __restrict__ x, const float* __restrict__
         smp_store4<VEC>(x, g, n, xv);
     }
     __syncthreads();
-    if (threadIdx.x == 0) smp_program_advance(st, step_of, v, 0);
+    if (threadIdx.x == 0) smp_program_advance(st, step_of, v, 0, smp_grid_blocks<CLIP>());
 }
 
 // Partial start in q-sample mode: x holds clean audio and becomes the state at step s0,
 //   x = (n1 * x) + (n2 * z0)      n1 = sqrt(level[s0]), n2 = sqrt(1 - level[s0])
 // z0: the injected tensor or Philox stream `stream_id` (2S + 1).
-__global__ void smp_qsample_kernel(float* __restrict__ x, const float* __restrict__ z0, float n1, float n2, size_t n,
-                                   uint64_t seed, uint32_t stream_id) {
+template <bool CLIP>
+__global__ void smp_qsample_kernel(float* __restrict__ x, const float* __restrict__ z0, float n1, float n2, size_t n_all,
+                                   uint64_t seed, uint32_t stream_id, const ClipSeeds cs) {
+    const size_t n = CLIP ? cs.n_c : n_all;
+    if (CLIP) {
+        const size_t off = (size_t)blockIdx.y * cs.n_c;
+        seed = cs.seeds[blockIdx.y];
+        x += off;
+        if (z0) z0 += off;
+    }
     for (size_t g = (size_t)blockIdx.x * blockDim.x + threadIdx.x; g * 4 < n; g += (size_t)gridDim.x * blockDim.x) {
         float z[4] = {0.f, 0.f, 0.f, 0.f};
         if (!z0) normal4(seed, stream_id, g, z);
@@ -389,6 +463,14 @@ __global__ void smp_cfg_kernel(float* __restrict__ eps, const int* __restrict__ 
 // ---- host side: what the entry points share ----
 static int smp_blocks(size_t n) { return (int)std::min<size_t>(ceil_div(n, 4 * 256), 4096); }
 
+// The grid of a launch over n elements: smp_blocks(n), or -- per-clip seeds, `clips` > 0 rows of n_c elements -- a row of
+// blocks per clip with about as many blocks in all.
+static dim3 smp_grid(size_t n, int clips, size_t n_c) {
+    if (clips == 0) return dim3(smp_blocks(n));
+    const size_t per_clip = std::max<size_t>(4096 / (size_t)clips, 1);
+    return dim3((unsigned)std::min<size_t>(ceil_div(n_c, 4 * 256), per_clip), (unsigned)clips);
+}
+
 // KIND and VEC of a launch as compile-time constants: f(integral_constant<int, kind>, bool_constant<vec>)
 template <class F>
 static void smp_dispatch(int kind, bool vec, F&& f) {
@@ -404,10 +486,16 @@ static void smp_dispatch(int kind, bool vec, F&& f) {
 // The plain flavour has no DDPM instance: that kind's unedited step is smp_update_kernel.
 template <bool EDIT, bool PROG>
 static void smp_launch_step(int kind, bool vec, const StepArgs& a, hipStream_t s) {
+    const dim3 grid = smp_grid(a.n, a.clips, a.more.clip.n_c);
     smp_dispatch(kind, vec, [&](auto K, auto VEC) {
-        if constexpr (EDIT || decltype(K)::value != DWS_SAMPLER_DDPM)
-            hipLaunchKernelGGL((smp_step_kernel<decltype(K)::value, EDIT, PROG, decltype(VEC)::value>), dim3(smp_blocks(a.n)),
-                               dim3(256), 0, s, a.x, a.eps, a.tab, a.st, a.noise, a.n, a.S, a.more);
+        if constexpr (EDIT || decltype(K)::value != DWS_SAMPLER_DDPM) {
+            if (a.clips)
+                hipLaunchKernelGGL((smp_step_kernel<decltype(K)::value, EDIT, PROG, decltype(VEC)::value, true>), grid,
+                                   dim3(256), 0, s, a.x, a.eps, a.tab, a.st, a.noise, a.n, a.S, a.more);
+            else
+                hipLaunchKernelGGL((smp_step_kernel<decltype(K)::value, EDIT, PROG, decltype(VEC)::value, false>), grid,
+                                   dim3(256), 0, s, a.x, a.eps, a.tab, a.st, a.noise, a.n, a.S, a.more);
+        }
     });
 }
 
@@ -495,8 +583,8 @@ static int one_step(dws_model* m, float* x, const float* noise, uint64_t seed, i
     const int st = m->forward(x, nullptr, m->smp_eps.f(), s);
     m->step_idx = nullptr;
     DWS_TRY(st);
-    hipLaunchKernelGGL(smp_update_kernel, dim3(smp_blocks(n)), dim3(256), 0, s, x, m->smp_eps.f(), m->smp_tables.f(),
-                       t_dev, noise, seed, (const uint64_t*)nullptr, n, T);
+    hipLaunchKernelGGL(smp_update_kernel<false>, dim3(smp_blocks(n)), dim3(256), 0, s, x, m->smp_eps.f(), m->smp_tables.f(),
+                       t_dev, noise, seed, (const uint64_t*)nullptr, n, T, ClipSeeds{});
     return DWS_OK;
 }
 
@@ -580,9 +668,12 @@ static int schedule_step(dws_model* m, int kind, bool vec, const StepArgs& a, bo
         smp_launch_step<true, true>(kind, vec, a, s);
     else if (a.more.mask)
         smp_launch_step<true, false>(kind, vec, a, s);
+    else if (kind == DWS_SAMPLER_DDPM && a.clips)
+        hipLaunchKernelGGL(smp_update_kernel<true>, smp_grid(a.n, a.clips, a.more.clip.n_c), dim3(256), 0, s, a.x, a.eps,
+                           a.tab, a.st, a.noise, (uint64_t)0, (const uint64_t*)nullptr, a.n, a.S, a.more.clip);
     else if (kind == DWS_SAMPLER_DDPM)
-        hipLaunchKernelGGL(smp_update_kernel, dim3(smp_blocks(a.n)), dim3(256), 0, s, a.x, a.eps, a.tab, a.st, a.noise,
-                           (uint64_t)0, reinterpret_cast<const uint64_t*>(a.st + 2), a.n, a.S);
+        hipLaunchKernelGGL(smp_update_kernel<false>, dim3(smp_blocks(a.n)), dim3(256), 0, s, a.x, a.eps, a.tab, a.st, a.noise,
+                           (uint64_t)0, reinterpret_cast<const uint64_t*>(a.st + 2), a.n, a.S, ClipSeeds{});
     else
         smp_launch_step<false, false>(kind, vec, a, s);
     if (cfg) DWS_HIP(hipMemcpyAsync(a.x + a.n, a.x, a.n * 4, hipMemcpyDeviceToDevice, s));   // the second half of the state follows the first
@@ -649,9 +740,16 @@ int sampler_run_schedule(dws_model* m, float* x, int kind, int S, const float* n
     DWS_CHECK(!cfg || (!e && !pg), DWS_ERR_UNSUPPORTED, "classifier-free guidance is not built for editing or program runs");
     DWS_CHECK(!cfg || m->B % 2 == 0, DWS_ERR_UNSUPPORTED,
               "classifier-free guidance needs a model prepared for 2 x Bc clips (prepared batch: %lld)", (long long)m->B);
+    // per-clip seeds: one per clip of the sampler state (the first half of a guided run's doubled batch); `seed` is not read
+    const int clips = (int)m->clip_B;
+    DWS_CHECK(clips == 0 || clips == (cfg ? m->B / 2 : m->B), DWS_ERR_INVALID,
+              "sampler: a table of %d clip seeds (dws_sampler_set_clip_seeds) for a sampler state of %lld clips", clips,
+              (long long)(cfg ? m->B / 2 : m->B));
     if (m->dirty) DWS_TRY(m->commit(s));
     const size_t nfull = (size_t)m->B * m->d.out_channels * m->L;    // the network's batch
     const size_t n = cfg ? nfull / 2 : nfull;                         // what the caller's x, the noise and the update span
+    const ClipSeeds clip{clips ? static_cast<const uint64_t*>(m->clip_seeds_dev.p) : nullptr,
+                         clips ? (size_t)m->d.out_channels * m->L : 0};
 
     // update tables, keyed on their contents; DDIM's and DPM-Solver++'s are used as given
     const std::vector<float> h = kind != DWS_SAMPLER_DDPM ? std::vector<float>(coef, coef + 5 * (size_t)S)
@@ -692,13 +790,18 @@ int sampler_run_schedule(dws_model* m, float* x, int kind, int S, const float* n
     if (staged) DWS_TRY(m->sch_x.ensure(nfull * 4));
     float* xr = staged ? m->sch_x.f() : x;
     const auto aligned = [](const void* p) { return ((uintptr_t)p & 15) == 0; };
-    const bool vec = n % 4 == 0 && aligned(noise) && aligned(known_noise) && (staged || aligned(x));   // (the model's buffers come from hipMalloc)
+    // (the model's buffers come from hipMalloc; per clip every clip must begin on a group border)
+    const bool vec = (clips ? clip.n_c : n) % 4 == 0 && aligned(noise) && aligned(known_noise) && (staged || aligned(x));
+    const dim3 grid = smp_grid(n, clips, clip.n_c);     // of every launch here that draws
     hipStream_t q = s;
     if (use_graph) {
         DWS_TRY(engine_after_caller(m, s));
         q = m->smp_stream;
     }
-    if (init_from_seed)
+    if (init_from_seed && clips)
+        hipLaunchKernelGGL(smp_fill_normal_clips_kernel<const uint64_t*>, grid, dim3(256), 0, q, xr, clip.n_c, clip.seeds,
+                           (uint32_t)R);
+    else if (init_from_seed)
         hipLaunchKernelGGL(smp_fill_normal_kernel, dim3(smp_blocks(n)), dim3(256), 0, q, xr, n, seed, (uint32_t)R);
     else if (staged)
         DWS_HIP(hipMemcpyAsync(xr, x, n * 4, hipMemcpyDeviceToDevice, q));
@@ -713,16 +816,22 @@ int sampler_run_schedule(dws_model* m, float* x, int kind, int S, const float* n
         DWS_HIP(hipMemcpyAsync(m->sch_known.p, e->known, n * 4, hipMemcpyDeviceToDevice, q));
         DWS_HIP(hipMemcpyAsync(m->sch_mask.p, e->mask, n, hipMemcpyDeviceToDevice, q));
     }
-    if (qsample)
-        hipLaunchKernelGGL(smp_qsample_kernel, dim3(smp_blocks(n)), dim3(256), 0, q, xr, e->start_noise,
+    if (qsample && clips)
+        hipLaunchKernelGGL(smp_qsample_kernel<true>, grid, dim3(256), 0, q, xr, e->start_noise,
                            e->edit_coef[2 * (size_t)S + start], e->edit_coef[3 * (size_t)S + start], n, seed,
-                           (uint32_t)(2 * R + 1));
+                           (uint32_t)(2 * R + 1), clip);
+    else if (qsample)
+        hipLaunchKernelGGL(smp_qsample_kernel<false>, dim3(smp_blocks(n)), dim3(256), 0, q, xr, e->start_noise,
+                           e->edit_coef[2 * (size_t)S + start], e->edit_coef[3 * (size_t)S + start], n, seed,
+                           (uint32_t)(2 * R + 1), ClipSeeds{});
     if (cfg) hipLaunchKernelGGL(smp_set_cfg_scale_kernel, dim3(1), dim3(1), 0, q, st, m->cfg_scale);
 
     StepArgs a{};
     a.x = xr; a.eps = m->smp_eps.f(); a.tab = m->sch_tables.f(); a.st = st; a.noise = noise; a.n = n; a.S = S;
+    a.clips = clips;
     StepMore& more = a.more;
     more.V = V;
+    more.clip = clip;
     more.hist = kind == DWS_SAMPLER_DPMPP2M ? m->sch_hist.f() : nullptr;
     if (masked) {
         more.edit = m->sch_edit.f(); more.y = m->sch_known.f(); more.mask = static_cast<const uint8_t*>(m->sch_mask.p);
@@ -736,8 +845,10 @@ int sampler_run_schedule(dws_model* m, float* x, int kind, int S, const float* n
         }
         for (int i = 0; i < V; ++i) {
             if (pg->visit_step[i] >= 0) DWS_TRY(reverse());
-            else if (vec) hipLaunchKernelGGL(smp_jump_kernel<true>, dim3(smp_blocks(n)), dim3(256), 0, q, xr, jump, st, step_of, noise, n, V);
-            else hipLaunchKernelGGL(smp_jump_kernel<false>, dim3(smp_blocks(n)), dim3(256), 0, q, xr, jump, st, step_of, noise, n, V);
+            else if (clips && vec) hipLaunchKernelGGL((smp_jump_kernel<true, true>), grid, dim3(256), 0, q, xr, jump, st, step_of, noise, n, V, clip);
+            else if (clips) hipLaunchKernelGGL((smp_jump_kernel<false, true>), grid, dim3(256), 0, q, xr, jump, st, step_of, noise, n, V, clip);
+            else if (vec) hipLaunchKernelGGL((smp_jump_kernel<true, false>), grid, dim3(256), 0, q, xr, jump, st, step_of, noise, n, V, clip);
+            else hipLaunchKernelGGL((smp_jump_kernel<false, false>), grid, dim3(256), 0, q, xr, jump, st, step_of, noise, n, V, clip);
         }
         return DWS_OK;
     };
@@ -745,12 +856,14 @@ int sampler_run_schedule(dws_model* m, float* x, int kind, int S, const float* n
     if (!use_graph) {
         DWS_TRY(walk(step));
     } else {
-        // the edited, the resampling and the guided step have graphs of their own beside the plain one: the four kinds of
-        // call may alternate without a new capture
+        // the edited, the resampling and the guided step have graphs of their own beside the plain one, and each of the
+        // four one per form of seed (the per-clip step is other kernel instances on another grid): the kinds of call may
+        // alternate without a new capture
         dws_model::SchGraph& have = m->sch_graphs[cfg ? dws_model::SCH_CFG : pg ? dws_model::SCH_PROG
-                                                  : masked ? dws_model::SCH_EDIT : dws_model::SCH_PLAIN];
+                                                  : masked ? dws_model::SCH_EDIT : dws_model::SCH_PLAIN][clips ? 1 : 0];
         const dws_model::SchKey key{m->B, m->L, S, kind, vec ? 1 : 0, a.tab, noise, a.eps, xr, st, m->step_table_gen,
-                                    more.edit, more.y, more.mask, known_noise, V, pg ? m->sch_prog.p : nullptr, more.hist};
+                                    more.edit, more.y, more.mask, known_noise, V, pg ? m->sch_prog.p : nullptr, more.hist,
+                                    clip.seeds};
         DWS_TRY(capture_step(m, q, have.exec, key == have.key, step));
         have.key = key;
         DWS_TRY(walk([&]() -> int {
@@ -803,6 +916,24 @@ int philox_normal(float* x, int64_t n, uint64_t seed, uint32_t stream_id, hipStr
     DWS_CHECK(x && n >= 0, DWS_ERR_INVALID, "dws_philox_normal: null x or n = %lld", (long long)n);
     if (n == 0) return DWS_OK;
     hipLaunchKernelGGL(smp_fill_normal_kernel, dim3(smp_blocks((size_t)n)), dim3(256), 0, s, x, (size_t)n, seed, stream_id);
+    DWS_HIP(hipGetLastError());
+    return DWS_OK;
+}
+
+// dws_philox_normal_clips: row b of x [B, n_per_clip] is dws_philox_normal(n_per_clip, seeds[b], stream_id).  The HOST
+// seeds travel as kernel arguments, SeedChunk::N clips per launch: no device table, nothing the host waits for.
+int philox_normal_clips(float* x, int64_t B, int64_t n_per_clip, const uint64_t* seeds, uint32_t stream_id, hipStream_t s) {
+    DWS_CHECK(x && seeds && B >= 0 && n_per_clip >= 0, DWS_ERR_INVALID,
+              "dws_philox_normal_clips: null x or seeds, or B = %lld, n_per_clip = %lld", (long long)B, (long long)n_per_clip);
+    if (B == 0 || n_per_clip == 0) return DWS_OK;
+    const size_t n_c = (size_t)n_per_clip;
+    for (int64_t b0 = 0; b0 < B; b0 += SeedChunk::N) {
+        const int rows = (int)std::min<int64_t>(SeedChunk::N, B - b0);
+        SeedChunk chunk{};
+        std::memcpy(chunk.s, seeds + b0, (size_t)rows * 8);
+        hipLaunchKernelGGL(smp_fill_normal_clips_kernel<SeedChunk>, smp_grid(n_c * rows, rows, n_c), dim3(256), 0, s,
+                           x + (size_t)b0 * n_c, n_c, chunk, stream_id);
+    }
     DWS_HIP(hipGetLastError());
     return DWS_OK;
 }

@@ -200,6 +200,40 @@ def weights_key(checkpoint, ema=None, ckpt_smooth=None):
 
 
 # --------------------------------------------------------------------------- generate
+def clip_plan(n_samples, batch_size, rank=0, num_ranks=1, clip_seeds=False, clips=None, seed=None):
+    """Which global clips one rank generates under ``generate.clip_seeds``, as a list of batches (lists of global clip
+    numbers ``k``, the number in the wav's name).  Without ``clips``: clip i of rank r is ``k = n_samples r + i``, in
+    batches of ``batch_size`` (which divides ``n_samples``).  With ``clips`` (a list of global clip numbers): rank r of N
+    takes ``clips[r::N]`` in batches of up to ``batch_size`` -- the last may be smaller, a rank may get none.  Pure host
+    arithmetic.  ``clips`` without ``clip_seeds`` and ``clip_seeds`` without ``seed`` are refused (ValueError)."""
+    if isinstance(clip_seeds, str) or clip_seeds not in (None, False, True, 0, 1):
+        raise ValueError(f"generate.clip_seeds={clip_seeds!r}: expected true or false")
+    if clips is not None and not clip_seeds:
+        raise ValueError("generate.clips needs generate.clip_seeds=true (only per-clip seeds make a clip reproducible on "
+                         "its own)")
+    if not clip_seeds:
+        return None
+    if seed is None or isinstance(seed, bool) or not isinstance(seed, int):
+        raise ValueError("generate.clip_seeds needs generate.seed (an integer: the clips' seeds are derived from it)")
+    rank, num_ranks = int(rank or 0), int(num_ranks or 1)
+    if rank < 0 or (clips is not None and rank >= num_ranks):
+        raise ValueError(f"clip_plan: rank {rank} of {num_ranks}")
+    if isinstance(batch_size, bool) or not isinstance(batch_size, int) or batch_size < 1:
+        raise ValueError(f"generate.batch_size={batch_size!r}: expected an integer >= 1")
+    if clips is None:
+        if n_samples % batch_size != 0:
+            raise ValueError(f"generate.batch_size={batch_size} does not divide generate.n_samples={n_samples}")
+        mine = [n_samples * rank + i for i in range(n_samples)]
+    else:
+        clips = list(clips) if isinstance(clips, (list, tuple)) else [clips]
+        if not clips or any(isinstance(k, bool) or not isinstance(k, int) or k < 0 for k in clips):
+            raise ValueError(f"generate.clips={clips!r}: expected a list of global clip numbers (integers >= 0)")
+        if len(set(clips)) != len(clips):
+            raise ValueError(f"generate.clips={clips!r}: a clip is named twice")
+        mine = clips[rank::num_ranks]
+    return [mine[i:i + batch_size] for i in range(0, len(mine), batch_size)]
+
+
 def _load_clip(dataset_cfg, stem, audio_length, conditional):
     """``<dataset.data_path>/<stem>.wav`` as a [1, 1, audio_length] clip in [-1, 1], read as ``train.SpeechCommands``
     reads one (int16 / 32768, int32 / 2^31, float as it is; first channel).  Unconditional: fitted to the segment the
@@ -234,7 +268,7 @@ def generate(rank, diffusion_cfg, model_cfg, dataset_cfg, ckpt_iter="max", n_sam
              written=None, precision=None, sampler="ddpm", steps=None, eta=0.0, known_name=None, keep=None,
              start_name=None, start_step=None, start_noise=True, resample_jump=None, resample_n=None, spacing=None,
              guide_name=None, guide_op=None, guide_clip=None, guide_factor=None, guide_scale=None, label=None,
-             cfg_scale=None, ema=None):
+             cfg_scale=None, ema=None, clip_seeds=None, clips=None, num_ranks=None):
     """``generate.py:58-200``.  ``ckpt_iter`` may additionally be ``"init"``: seeded random weights
     (no checkpoint), for smoke runs without trained weights.  ``precision`` (not in the reference; CLI:
     ``+engine.precision=bf16x6|f16x3``): the engine's opt-in matrix arithmetic, see ``include/dws.h``.
@@ -271,16 +305,26 @@ def generate(rank, diffusion_cfg, model_cfg, dataset_cfg, ckpt_iter="max", n_sam
 
     ``ema`` (not in the reference; CLI ``+generate.ema=true|false``): which weights of the checkpoint are sampled, see
     ``weights_key``.  The default takes ``ema_state_dict`` when the checkpoint has one (runs trained with
-    ``train.ema_decay``) and ``model_state_dict`` otherwise."""
+    ``train.ema_decay``) and ``model_state_dict`` otherwise.
+
+    Reproducible clips (not in the reference; with every ``sampler`` and the editing, resampling, label / CFG and guide
+    keys): ``clip_seeds=true`` (needs ``seed``) seeds every clip on its own -- global clip ``k = n_samples rank + i``, the
+    number in its wav name, draws from ``sampling.clip_seeds(seed, k, 1)`` and, with ``label``, has the class
+    ``labels[k % len(labels)]`` -- so ``{iter}k_{k}.wav`` is the same file for any ``batch_size`` dividing ``n_samples``
+    and any number of ranks (``num_ranks``: the processes of the run, one per GPU) that produces clip k.  ``clips``
+    (a list of global clip numbers; needs ``clip_seeds``) generates only these, under their usual names: rank r of N takes
+    ``clips[r::N]`` in batches of up to ``batch_size`` (``clip_plan``).  Returns the audio of the clips this rank made."""
     from .models import construct_model
     from .models.utils import check_n_classes
     from .sampling import (calc_diffusion_hyperparams, ddim_steps, declip_operator, logsnr_steps, lowpass_operator,
                            program_evaluations, repaint_program, sampling, sampling_aligned, sampling_ddim, sampling_dpmpp,
                            sampling_guided, spans_to_mask)
+    from .sampling import clip_seeds as seeds_of_clips
     from scipy.io.wavfile import write as wavwrite
 
     if ckpt_smooth is not None or ckpt_iter == "init":     # checked here, before a model is built
         weights_key(None, ema, ckpt_smooth)
+    plan = clip_plan(n_samples, n_samples if batch_size is None else batch_size, rank, num_ranks, clip_seeds, clips, seed)
     if guide_name is None:
         given = [k for k, v in (("guide_op", guide_op), ("guide_clip", guide_clip), ("guide_factor", guide_factor),
                                 ("guide_scale", guide_scale)) if v is not None]
@@ -414,7 +458,7 @@ def generate(rank, diffusion_cfg, model_cfg, dataset_cfg, ckpt_iter="max", n_sam
 
     if batch_size is None:
         batch_size = n_samples
-    assert n_samples % batch_size == 0
+    assert plan is not None or n_samples % batch_size == 0
     if mel_name is not None:
         if mel_path is not None:      # pre-generated spectrogram (`generate.py:135-141`)
             try:
@@ -452,18 +496,28 @@ def generate(rank, diffusion_cfg, model_cfg, dataset_cfg, ckpt_iter="max", n_sam
 
     t0 = time.perf_counter()
     out = []
-    for i in range(n_samples // batch_size):
-        s = None if seed is None else seed + 1000 * rank + i
-        size = (batch_size, 1, audio_length)
+    # the global clip numbers of every batch: the plan of generate.clip_seeds, or this rank's n_samples in order
+    batches = plan if plan is not None else [[n_samples * rank + i * batch_size + b for b in range(batch_size)]
+                                             for i in range(n_samples // batch_size)]
+    numbers = [k for batch in batches for k in batch]
+    for i, batch in enumerate(batches):
+        size = (len(batch), 1, audio_length)
+        if plan is not None:    # a seed and a class per clip, both functions of the global clip number alone
+            s = [seeds_of_clips(seed, k, 1)[0] for k in batch]
+            class_of = [k % len(labels_of) for k in batch] if labels_of is not None else None
+        else:
+            s = None if seed is None else seed + 1000 * rank + i
+            class_of = [(i * batch_size + b) % len(labels_of) for b in range(batch_size)] if labels_of is not None else None
         if labels_of is not None:
-            edit["labels"] = [labels_of[(i * batch_size + b) % len(labels_of)] for b in range(batch_size)]
+            edit["labels"] = [labels_of[c] for c in class_of]
             if cfg_scale is not None:
                 edit["cfg_scale"] = float(cfg_scale)
         if guide is not None:
             ddim = sampler == "ddim"
+            guide_b = dict(guide, measurement=guide["measurement"][:len(batch)])
             out.append(sampling_guided(net, size, dh_train if ddim else dh, sampler=sampler, steps=steps if ddim else None,
                                        eta=float(eta or 0.0) if ddim else 0.0, condition=mel, seed=s,
-                                       labels=edit.get("labels"), **guide))
+                                       labels=edit.get("labels"), **guide_b))
         elif sampler == "aligned":
             out.append(sampling_aligned(net, size, diffusion_cfg, condition=mel, seed=s, **edit))
         elif sampler == "ddim":
@@ -472,9 +526,9 @@ def generate(rank, diffusion_cfg, model_cfg, dataset_cfg, ckpt_iter="max", n_sam
             out.append(sampling_dpmpp(net, size, dh_train, steps, condition=mel, spacing=spacing, seed=s, **edit))
         else:
             out.append(sampling(net, size, dh, condition=mel, seed=s, **edit))
-    generated_audio = torch.cat(out, dim=0)
+    generated_audio = torch.cat(out, dim=0) if out else torch.empty(0, 1, audio_length, device="cuda")
     torch.cuda.synchronize()
-    print(f"generated {n_samples} samples shape {tuple(generated_audio.shape)} at iteration {ckpt_iter} in "
+    print(f"generated {len(numbers)} samples shape {tuple(generated_audio.shape)} at iteration {ckpt_iter} in "
           f"{time.perf_counter() - t0:.1f} seconds")
     if guide is not None:
         print(f"guided sampler {sampler} ({guide_op}, scale {float(guide_scale):g}): {n_evals} network evaluations "
@@ -482,10 +536,10 @@ def generate(rank, diffusion_cfg, model_cfg, dataset_cfg, ckpt_iter="max", n_sam
     elif sampler != "ddpm" or resample_jump is not None:
         note = f" (eta={float(eta or 0.0)})" if sampler == "ddim" else f" ({spacing} spacing)" if sampler == "dpmpp2m" else ""
         print(f"sampler {sampler}{note}: {n_evals} network evaluations per batch")
-    for i in range(n_samples):
-        outfile = "{}k_{}.wav".format(ckpt_iter // 1000, n_samples * rank + i)   # `generate.py:189`
+    for i, k in enumerate(numbers):
+        outfile = "{}k_{}.wav".format(ckpt_iter // 1000, k)   # `generate.py:189`: k = n_samples * rank + i
         if labels_of is not None:
-            outfile = outfile[:-4] + f"_c{labels_of[i % len(labels_of)]}.wav"
+            outfile = outfile[:-4] + f"_c{labels_of[(k if plan is not None else i) % len(labels_of)]}.wav"
         wavwrite(os.path.join(output_directory, outfile), dataset_cfg["sampling_rate"],
                  generated_audio[i].squeeze().cpu().numpy().astype(np.float32))
         if written is not None:
@@ -496,6 +550,7 @@ def generate(rank, diffusion_cfg, model_cfg, dataset_cfg, ckpt_iter="max", n_sam
 def _worker(rank, cfg, exp_root):
     gen = dict(cfg.get("generate", {}))
     gen.setdefault("precision", (cfg.get("engine") or {}).get("precision"))
+    gen.setdefault("num_ranks", max(torch.cuda.device_count(), 1))     # main() starts one process per GPU
     generate(rank, dict(cfg["diffusion"]), dict(cfg["model"]), dict(cfg["dataset"]), exp_root=exp_root, **gen)
 
 

@@ -1,6 +1,7 @@
 """Reverse-diffusion driver with the reference's surface (``generate.py:23-55``,
 ``utils.py:121-151``) on top of ``dws_sampler_run`` (one step captured as a
 hipGraph and replayed T times; schedule, step index and RNG on the device)."""
+import contextlib
 import ctypes
 
 import numpy as np
@@ -57,6 +58,62 @@ def _check_labels(net, size, labels, cfg_scale, edit=None, resample=None):
     if edit is not None and any(v is not None for v in edit.values()):
         raise ValueError("sampler: cfg_scale= is not built for editing runs (known / mask / x_start ...)")
     return key, scale
+
+
+_MASK64 = (1 << 64) - 1
+_GOLDEN64 = 0x9E3779B97F4A7C15
+
+
+def _splitmix64(z):
+    """The splitmix64 finaliser (Steele, Lea & Flood, 2014) of a 64-bit integer, in host integer arithmetic."""
+    z = (z + _GOLDEN64) & _MASK64
+    z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & _MASK64
+    z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & _MASK64
+    return z ^ (z >> 31)
+
+
+def clip_seeds(seed, first, count):
+    """Per-clip seeds of a run: a list of ``count`` ints in 0 .. 2^64-1; entry j, for the global clip ``k = first + j``,
+    is ``splitmix64((seed + 0x9E3779B97F4A7C15 (k + 1)) mod 2^64)``.  A clip's seed depends on the run's seed and the
+    clip's global number alone, and runs with neighbouring seeds do not share clip streams (``seed + 1000 r + i`` would).
+    Pass the list as ``seed=`` to any sampler of this module."""
+    if not _is_int(seed) or not _is_int(first) or not _is_int(count) or int(first) < 0 or int(count) < 0:
+        raise ValueError(f"clip_seeds: seed = {seed!r}, first = {first!r}, count = {count!r} (needs integers, "
+                         "first >= 0, count >= 0)")
+    seed, first = int(seed), int(first)
+    return [_splitmix64((seed + _GOLDEN64 * (first + j + 1)) & _MASK64) for j in range(int(count))]
+
+
+def seed_list(seed, B):
+    """The per-clip form of ``seed=``, checked on the host (ValueError): None for None or an int (the scalar seed of the
+    whole batch), otherwise a list of ``B`` ints in 0 .. 2^64-1 from a sequence or a 1-D integer tensor / array."""
+    if seed is None or isinstance(seed, (int, np.integer)) and not isinstance(seed, bool):
+        return None
+    if isinstance(seed, (torch.Tensor, np.ndarray)):
+        if seed.ndim != 1 or (seed.dtype.is_floating_point if isinstance(seed, torch.Tensor) else seed.dtype.kind not in "iu"):
+            raise ValueError(f"sampler: seed= of shape {tuple(seed.shape)} and dtype {seed.dtype} (a per-clip seed table "
+                             "is a 1-D integer tensor)")
+        seed = seed.tolist()
+    try:
+        vals = list(seed)
+    except TypeError:
+        raise ValueError(f"sampler: seed = {seed!r} (needs an int, or a sequence of one int per clip)")
+    if len(vals) != int(B):
+        raise ValueError(f"sampler: {len(vals)} clip seeds for a batch of {int(B)} clips")
+    for b, v in enumerate(vals):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 0 <= int(v) <= _MASK64:
+            raise ValueError(f"sampler: clip seed {b} = {v!r} (needs an integer in 0 .. 2^64-1)")
+    return [int(v) for v in vals]
+
+
+def _set_clip_seeds(net, seeds):
+    """Install (a list) or drop (None) the engine's per-clip seed table on the current stream."""
+    lib = _lib.load()
+    if seeds is None:
+        _lib.check(lib.dws_sampler_set_clip_seeds(net._handle, None, 0, _lib.current_stream()))
+    else:
+        table = (ctypes.c_uint64 * len(seeds))(*seeds)
+        _lib.check(lib.dws_sampler_set_clip_seeds(net._handle, table, len(seeds), _lib.current_stream()))
 
 
 def _prepare_run(net, size, steps, condition, x_T, noise, seed, labels=(), cfg=False):
@@ -309,7 +366,10 @@ def sampling(net, size, diffusion_hyperparams, condition=None, *, x_T=None, nois
       x_T    initial state [B,C,L]; default: drawn on the device from the Philox stream
       noise  injected variance noise [T,B,C,L] (``noise[t]`` is added after step t>0) -- parity mode
       seed   Philox seed for the on-device RNG (default: a fresh draw from torch's CPU generator per call, so
-             successive unseeded calls differ -- as the reference's do -- and ``torch.manual_seed`` still governs)
+             successive unseeded calls differ -- as the reference's do -- and ``torch.manual_seed`` still governs).
+             A sequence / 1-D integer tensor of B values in 0 .. 2^64-1 (``clip_seeds``) seeds every clip on its own:
+             clip b is then bit-equal to the B = 1 run with ``seed = seed[b]``, whatever the batch around it (with
+             ``cfg_scale`` B is the caller's B).  Goes through the schedule entry with ``net_steps = 0..T-1``.
       net_steps  float[T]: the network sees ``net_steps[t]`` at step t instead of t, with the DDPM update of ``dh``
              unchanged (e.g. ``align_steps`` for DiffWave's fast schedule; ``dws_sampler_run_schedule``).  Not the
              reference's loop.
@@ -335,9 +395,10 @@ def sampling(net, size, diffusion_hyperparams, condition=None, *, x_T=None, nois
     edit = dict(known=known, mask=mask, known_noise=known_noise, x_start=x_start, start_step=start_step,
                 start_noise=start_noise)
     lab, scale = _check_labels(net, size, labels, cfg_scale, edit, resample)
+    per_clip = seed_list(seed, size[0]) is not None
     if resample is None and all(v is None for v in edit.values()):
         edit = None
-        if scale is not None and net_steps is None:
+        if (scale is not None or per_clip) and net_steps is None:
             net_steps = np.arange(T, dtype=np.float32)
     elif net_steps is None:
         net_steps = np.arange(T, dtype=np.float32)
@@ -364,6 +425,7 @@ def _run_schedule(net, size, kind, net_steps, coef, condition, x_T, noise, seed,
     ``resample``: (jump, resamples) on top of ``edit`` (-> ``dws_sampler_run_program``)."""
     assert len(size) == 3
     lab, scale = _check_labels(net, size, labels, cfg_scale, edit, resample)
+    seeds = seed_list(seed, size[0])
     steps = np.ascontiguousarray(np.asarray(net_steps, dtype=np.float32).reshape(-1))
     S = steps.shape[0]
     coef = np.ascontiguousarray(np.asarray(coef, dtype=np.float32))
@@ -379,9 +441,12 @@ def _run_schedule(net, size, kind, net_steps, coef, condition, x_T, noise, seed,
             x_T = x_start
     lib = _lib.load()
     fp = ctypes.POINTER(ctypes.c_float)
-    with torch.no_grad():
-        x, init, nz, seed = _prepare_run(net, size, S if prog is None else len(prog), condition, x_T, noise, seed,
-                                         labels=lab, cfg=scale is not None)
+    with torch.no_grad(), contextlib.ExitStack() as cleanup:
+        x, init, nz, seed = _prepare_run(net, size, S if prog is None else len(prog), condition, x_T, noise,
+                                         seed if seeds is None else 0, labels=lab, cfg=scale is not None)
+        if seeds is not None:     # per-clip seeds hold for this run alone: the engine's table is dropped behind it
+            _set_clip_seeds(net, seeds)
+            cleanup.callback(_set_clip_seeds, net, None)
         if edit is None and scale is not None:
             _lib.check(lib.dws_sampler_set_cfg(net._handle, 1, scale))
             try:
@@ -689,8 +754,9 @@ def sampling_guided(net, size, diffusion_hyperparams, *, measurement, operator, 
     ``"ddim"`` (``steps`` of the training schedule ``dh`` with ``eta``).  ``noise``: injected z [S, B, C, L]
     (``noise[s]`` after step s > 0), ``x_T``: the initial state; otherwise both are drawn -- with an engine model from
     the Philox streams the plain samplers use (stream s for step s, stream S for ``x_T``; ``seed`` as there), with any
-    other ``net`` from a torch CPU generator seeded with ``seed``.  ``residuals``: a list that receives ``n`` [B] of
-    every step (diagnostics).
+    other ``net`` from a torch CPU generator seeded with ``seed``.  ``seed`` may be a list of B per-clip seeds as in
+    ``sampling`` (``dws_philox_normal_clips``; with another ``net`` one generator per clip): clip b then draws the noise
+    of the B = 1 run with ``seed[b]``.  ``residuals``: a list that receives ``n`` [B] of every step (diagnostics).
 
     ``net`` is any differentiable callable of the reference surface on any device.  With an engine model every step is
     a training forward and a DATA-ONLY backward (``dws_model_backward_input``): put the model in ``eval()`` mode, or the
@@ -741,6 +807,7 @@ def sampling_guided(net, size, diffusion_hyperparams, *, measurement, operator, 
     y = torch.as_tensor(measurement).detach().to(device=dev, dtype=torch.float32)
     if condition is not None:
         condition = condition.detach().to(dev)
+    seeds = seed_list(seed, B)
     if seed is None:
         seed = int(torch.randint(0, 2 ** 63 - 1, (1,), dtype=torch.int64).item())
     gen = None
@@ -750,8 +817,17 @@ def sampling_guided(net, size, diffusion_hyperparams, *, measurement, operator, 
         if engine:
             z = torch.empty(size, device=dev, dtype=torch.float32)
             with torch.cuda.device(dev):
-                _lib.check(_lib.load().dws_philox_normal(z.data_ptr(), z.numel(), seed, stream_id, _lib.current_stream()))
+                if seeds is None:
+                    _lib.check(_lib.load().dws_philox_normal(z.data_ptr(), z.numel(), seed, stream_id,
+                                                             _lib.current_stream()))
+                else:
+                    _lib.check(_lib.load().dws_philox_normal_clips(z.data_ptr(), B, C * L, (ctypes.c_uint64 * B)(*seeds),
+                                                                   stream_id, _lib.current_stream()))
             return z
+        if seeds is not None:     # a generator per clip, each drawing its clip as the scalar form draws a B = 1 batch
+            if gen is None:
+                gen = [torch.Generator().manual_seed(k % (2 ** 63)) for k in seeds]
+            return torch.cat([torch.randn((1, C, L), generator=g) for g in gen]).to(dev)
         if gen is None:
             gen = torch.Generator().manual_seed(seed % (2 ** 63))
         return torch.randn(size, generator=gen).to(dev)

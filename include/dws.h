@@ -495,6 +495,36 @@ int dws_sampler_run_program(dws_model* m, float* x, int32_t kind, int32_t S, con
  * gives elements 4g .. 4g+3.  For checking the stream assignment of a seeded run from outside. */
 int dws_philox_normal(float* x, int64_t n, uint64_t seed, uint32_t stream_id, void* stream);
 
+/* Per-clip seeds: a clip's noise depends on (its own seed, the stream, the element's position inside the clip) alone --
+ * not on the batch size, the clip's place in the batch or the number of devices a run is spread over.  seeds: HOST
+ * uint64[B], or NULL = off (the scalar `seed` of the run entries, every path bit for bit as without this call).  The table
+ * goes through pinned staging into a model-owned device buffer on `stream` (the host does not wait for the GPU) and holds
+ * until it is changed; dws_model_prepare to another shape drops it.  While it is on, the `seed` argument of
+ * dws_sampler_run_schedule, _run_edit and _run_program is ignored, and B must be the number of clips of the sampler state
+ * -- the prepared batch, or half of it under dws_sampler_set_cfg (the noise covers the first half's Bc clips) -- else the
+ * run entry returns DWS_ERR_INVALID before anything is enqueued.
+ *
+ * Numbering, with n_c = C L: element e in 0 .. n_c-1 of clip b is component e % 4 of normal4(seeds[b], stream, e / 4);
+ * the stream ids are those above (s, S, S + 1 + s, 2S + 1; v, V, V + 1 + v, 2V + 1 in a program run).  So clip b of a
+ * per-clip run is bit-equal to the scalar-seed run at B = 1 with seed = seeds[b].  Every kernel that draws (x_T, the
+ * update noise, the known-region noise, the jump noise, the start noise) has a per-clip instance that runs on a grid with
+ * one row per clip, each row with its clip's seed and its groups counted from the clip's first element; with
+ * n_c % 4 == 0 (and 16-byte aligned noise tensors) a group is one float4 per array and the four mask bytes one word as
+ * before, otherwise the element-wise path runs bounded by n_c.  The scalar-seed instances are not touched.
+ *
+ * The captured steps read the table from device memory: a new table replays the graph.  The per-clip step is a graph of
+ * its own beside the scalar-seed one of its flavour (still one linear chain of nodes), so calls of the two forms alternate
+ * on one model without a new capture once both have run.
+ * While on: dws_sampler_run and dws_sampler_steps return DWS_ERR_UNSUPPORTED (dws_sampler_run_schedule with
+ * net_steps = 0 .. T-1 is bit-identical to dws_sampler_run).  B outside 1 .. 65535 -> DWS_ERR_INVALID; before
+ * dws_model_prepare -> DWS_ERR_STATE. */
+int dws_sampler_set_clip_seeds(dws_model* m, const uint64_t* seeds, int64_t B, void* stream);
+
+/* The per-clip twin of dws_philox_normal: row b of x[B, n_per_clip] (DEVICE) = dws_philox_normal(n_per_clip, seeds[b],
+ * stream_id), seeds HOST uint64[B].  The seeds travel as kernel arguments; the host does not wait for the GPU. */
+int dws_philox_normal_clips(float* x, int64_t B, int64_t n_per_clip, const uint64_t* seeds, uint32_t stream_id,
+                            void* stream);
+
 /* Mel-spectrogram front-end of the vocoding path: TacotronSTFT.mel_spectrogram
  * (`dataloaders/stft.py:196-244`) as called by Mel2Samp.get_mel (`dataloaders/mel2samp.py:76-82`) and
  * generate.py:147-153.  audio [B][T] in [-1, 1]; window [n_fft] (the Hann window, centre-padded to
