@@ -22,25 +22,14 @@ int philox_normal_clips(float* x, int64_t B, int64_t n_per_clip, const uint64_t*
 }  // namespace dws
 
 dws_model::~dws_model() {
-    drop_graph();
-    if (smp_ev_in) hipEventDestroy(smp_ev_in);
-    if (smp_ev_out) hipEventDestroy(smp_ev_out);
-    if (smp_stream) hipStreamDestroy(smp_stream);
-    for (int i = 0; i < COPY_SLOTS; ++i) {
-        if (copy_consumed[i]) (void)hipEventDestroy(copy_consumed[i]);
-        if (copy_pinned[i]) (void)hipHostFree(copy_pinned[i]);
-    }
-    for (int i = 0; i < LABEL_SLOTS; ++i) {
-        if (label_consumed[i]) (void)hipEventDestroy(label_consumed[i]);
-        if (label_pinned[i]) (void)hipHostFree(label_pinned[i]);
-    }
-    for (int i = 0; i < SEED_SLOTS; ++i) {
-        if (seed_consumed[i]) (void)hipEventDestroy(seed_consumed[i]);
-        if (seed_pinned[i]) (void)hipHostFree(seed_pinned[i]);
-    }
-    for (auto& g : grad_groups)
-        if (g.ev) (void)hipEventDestroy(g.ev);
     for (auto* p : params) delete p;
+}
+
+dws::ParamSpec* dws_model::find(const char* name, bool state_dict) const {
+    auto it = index.find(name);
+    if (it != index.end()) return params[it->second];
+    dws::set_error(DWS_ERR_INVALID, state_dict ? "unexpected key '%s' in state_dict" : "unknown parameter '%s'", name);
+    return nullptr;
 }
 
 int dws_model::set_classes(int32_t K) {
@@ -81,20 +70,11 @@ int dws_model::set_labels(const int32_t* labels, int64_t nB, hipStream_t s) {
                : (labels_host.empty() && labels_dev.p))
         return DWS_OK;     // the assignment already installed
     DWS_CHECK(labels_dev.p && labels_dev.bytes >= (size_t)B * 4, DWS_ERR_STATE, "dws_model_set_labels: no label buffer");
-    // pinned staging, round robin with an event per slot: the host only ever waits for the upload made LABEL_SLOTS calls ago
-    const int slot = label_slot;
-    label_slot = (slot + 1) % LABEL_SLOTS;
-    if (!label_consumed[slot]) DWS_HIP(hipEventCreateWithFlags(&label_consumed[slot], hipEventDisableTiming));
-    else DWS_HIP(hipEventSynchronize(label_consumed[slot]));
-    if (label_pinned_cap[slot] < (size_t)B) {
-        if (label_pinned[slot]) (void)hipHostFree(label_pinned[slot]);
-        label_pinned[slot] = nullptr;
-        label_pinned_cap[slot] = (size_t)B * 2;
-        DWS_HIP(hipHostMalloc((void**)&label_pinned[slot], label_pinned_cap[slot] * 4, hipHostMallocDefault));
-    }
-    for (int64_t b = 0; b < B; ++b) label_pinned[slot][b] = labels ? labels[b] : n_classes;
-    DWS_HIP(hipMemcpyAsync(labels_dev.p, label_pinned[slot], (size_t)B * 4, hipMemcpyHostToDevice, s));
-    DWS_HIP(hipEventRecord(label_consumed[slot], s));
+    int32_t* h = nullptr;
+    DWS_TRY(label_ring.acquire((size_t)B * 4, (void**)&h));
+    for (int64_t b = 0; b < B; ++b) h[b] = labels ? labels[b] : n_classes;
+    DWS_HIP(hipMemcpyAsync(labels_dev.p, h, (size_t)B * 4, hipMemcpyHostToDevice, s));
+    DWS_TRY(label_ring.commit(s));
     if (labels) labels_host.assign(labels, labels + B);
     else labels_host.clear();
     ++labels_version;
@@ -104,38 +84,19 @@ int dws_model::set_labels(const int32_t* labels, int64_t nB, hipStream_t s) {
 // The grid of a per-clip launch has one row per clip: at most 65535 clips.
 int dws_model::set_clip_seeds(const uint64_t* seeds, int64_t nB, hipStream_t s) {
     if (!seeds) {
-        clip_B = 0;
+        smp.clip_B = 0;
         return DWS_OK;
     }
     DWS_CHECK(B > 0, DWS_ERR_STATE, "dws_sampler_set_clip_seeds before dws_model_prepare");
     DWS_CHECK(nB >= 1 && nB <= 65535, DWS_ERR_INVALID, "dws_sampler_set_clip_seeds: %lld seeds (needs 1 .. 65535)", (long long)nB);
-    DWS_TRY(clip_seeds_dev.ensure((size_t)nB * 8));
-    // pinned staging, round robin with an event per slot: the host only ever waits for the upload made SEED_SLOTS calls ago
-    const int slot = seed_slot;
-    seed_slot = (slot + 1) % SEED_SLOTS;
-    if (!seed_consumed[slot]) DWS_HIP(hipEventCreateWithFlags(&seed_consumed[slot], hipEventDisableTiming));
-    else DWS_HIP(hipEventSynchronize(seed_consumed[slot]));
-    if (seed_pinned_cap[slot] < (size_t)nB) {
-        if (seed_pinned[slot]) (void)hipHostFree(seed_pinned[slot]);
-        seed_pinned[slot] = nullptr;
-        seed_pinned_cap[slot] = (size_t)nB * 2;
-        DWS_HIP(hipHostMalloc((void**)&seed_pinned[slot], seed_pinned_cap[slot] * 8, hipHostMallocDefault));
-    }
-    std::memcpy(seed_pinned[slot], seeds, (size_t)nB * 8);
-    DWS_HIP(hipMemcpyAsync(clip_seeds_dev.p, seed_pinned[slot], (size_t)nB * 8, hipMemcpyHostToDevice, s));
-    DWS_HIP(hipEventRecord(seed_consumed[slot], s));
-    clip_B = nB;
+    DWS_TRY(smp.clip_seeds.ensure((size_t)nB * 8));
+    void* h = nullptr;
+    DWS_TRY(smp.seed_ring.acquire((size_t)nB * 8, &h));
+    std::memcpy(h, seeds, (size_t)nB * 8);
+    DWS_HIP(hipMemcpyAsync(smp.clip_seeds.p, h, (size_t)nB * 8, hipMemcpyHostToDevice, s));
+    DWS_TRY(smp.seed_ring.commit(s));
+    smp.clip_B = nB;
     return DWS_OK;
-}
-
-void dws_model::drop_graph() {
-    if (smp_graph) hipGraphExecDestroy(smp_graph);
-    smp_graph = nullptr;
-    for (auto& flavour : sch_graphs)
-        for (SchGraph& g : flavour) {
-            if (g.exec) hipGraphExecDestroy(g.exec);
-            g.exec = nullptr;
-        }
 }
 
 dws::ParamSpec* dws_model::add_param(const std::string& name, std::vector<int64_t> shape, int dtype) {
@@ -143,7 +104,7 @@ dws::ParamSpec* dws_model::add_param(const std::string& name, std::vector<int64_
     p->name = name;
     p->shape = std::move(shape);
     p->dtype = dtype;
-    index[name] = (int)params.size();
+    p->index = index[name] = (int)params.size();
     params.push_back(p);
     return p;
 }
@@ -174,8 +135,6 @@ float* dws_model::G(const std::string& name) {
 
 int dws_model::set_grad_sinks(int32_t count, const char* const* names, float* const* dsts, const int64_t* numels,
                               const int32_t* groups, int32_t ngroups) {
-    for (auto& g : grad_groups)
-        if (g.ev) (void)hipEventDestroy(g.ev);
     grad_groups.clear();
     grad_group_of.assign(params.size(), -1);
     grad_sink.assign(params.size(), nullptr);
@@ -185,17 +144,15 @@ int dws_model::set_grad_sinks(int32_t count, const char* const* names, float* co
     if (count == 0) { grad_touch.clear(); return DWS_OK; }
     grad_groups.resize((size_t)ngroups);
     for (int i = 0; i < count; ++i) {
-        auto it = index.find(names[i]);
-        DWS_CHECK(it != index.end(), DWS_ERR_INVALID, "unknown parameter '%s'", names[i]);
-        dws::ParamSpec* p = params[it->second];
+        dws::ParamSpec* p = find(names[i]);
+        if (!p) return DWS_ERR_INVALID;
         DWS_CHECK(p->dtype == 0 && (int64_t)p->numel() == numels[i] && dsts[i], DWS_ERR_INVALID,
                   "'%s': gradient sink of %lld elements for a tensor of %zu", names[i], (long long)numels[i], p->numel());
         DWS_CHECK(groups[i] >= 0 && groups[i] < ngroups, DWS_ERR_INVALID, "'%s': group %d of %d", names[i], groups[i], ngroups);
-        grad_group_of[it->second] = groups[i];
-        grad_sink[it->second] = dsts[i];
-        grad_groups[groups[i]].params.push_back(it->second);
+        grad_group_of[p->index] = groups[i];
+        grad_sink[p->index] = dsts[i];
+        grad_groups[groups[i]].params.push_back(p->index);
     }
-    for (auto& g : grad_groups) DWS_HIP(hipEventCreateWithFlags(&g.ev, hipEventDisableTiming));
     return DWS_OK;
 }
 
@@ -218,7 +175,7 @@ int dws_model::grad_flush(GradGroup& g, hipStream_t s) {
         g.copy.add(src, grad_sink[pi], p->numel());
     }
     DWS_TRY(g.copy.run(s));
-    DWS_HIP(hipEventRecord(g.ev, s));
+    DWS_TRY(g.ev.record(s));
     g.flushed = true;
     g.touched_after_flush = false;
     return DWS_OK;
@@ -331,16 +288,14 @@ int dws_model_param_info(const dws_model* m, int i, const char** name, int64_t* 
 int dws_model_set_param(dws_model* m, const char* name, const void* data, const int64_t* shape, int ndim, int dtype,
                         void* stream) {
     DWS_CHECK(m && name && data && shape, DWS_ERR_INVALID, "dws_model_set_param: null argument");
-    auto it = m->index.find(name);
-    if (it == m->index.end() && name[0] == '_' && name[1] == '_') {
+    if (!m->index.count(name) && name[0] == '_' && name[1] == '_') {
         // host-computed tables ("__omega.<L>", "__z.<L>": FFT nodes of an S4 kernel length the model was not
         // configured with, e.g. a checkpoint trained at another l_max) are registered on first sight
         dws::ParamSpec* np_ = m->add_param(name, std::vector<int64_t>(shape, shape + ndim), dtype);
         DWS_TRY(np_->buf.ensure(np_->nbytes()));
-        it = m->index.find(name);
     }
-    DWS_CHECK(it != m->index.end(), DWS_ERR_INVALID, "unexpected key '%s' in state_dict", name);
-    dws::ParamSpec* p = m->params[it->second];
+    dws::ParamSpec* p = m->find(name, true);
+    if (!p) return DWS_ERR_INVALID;
     DWS_CHECK(dtype == p->dtype, DWS_ERR_INVALID, "'%s': dtype %d, expected %d", name, dtype, p->dtype);
     bool same = (int)p->shape.size() == ndim;
     for (int k = 0; same && k < ndim; ++k) same = p->shape[k] == shape[k];
@@ -376,7 +331,7 @@ int dws_model_prepare(dws_model* m, int64_t B, int64_t L) {
     const int64_t B0 = m->B, L0 = m->L;
     DWS_TRY(m->prepare(B, L));
     if (m->n_classes > 0 && (B0 != m->B || L0 != m->L)) DWS_TRY(m->reset_labels());   // labels belong to a shape
-    if (B0 != m->B || L0 != m->L) m->clip_B = 0;                                        // and so does a seed table
+    if (B0 != m->B || L0 != m->L) m->smp.clip_B = 0;                                        // and so does a seed table
     return DWS_OK;
 }
 
@@ -394,8 +349,8 @@ int dws_sampler_set_cfg(dws_model* m, int32_t on, float scale) {
     DWS_CHECK(m, DWS_ERR_INVALID, "null model");
     DWS_CHECK(!on || (scale == scale && scale - scale == 0.f), DWS_ERR_INVALID, "dws_sampler_set_cfg: scale = %g is not finite",
               (double)scale);
-    m->cfg_on = on != 0;
-    m->cfg_scale = on ? scale : 0.f;
+    m->smp.cfg_on = on != 0;
+    m->smp.cfg_scale = on ? scale : 0.f;
     return DWS_OK;
 }
 
@@ -448,7 +403,7 @@ int dws_model_grad_group_wait(dws_model* m, int32_t group, void* waiting_stream)
     DWS_CHECK(m && group >= 0 && (size_t)group < m->grad_groups.size(), DWS_ERR_INVALID, "dws_model_grad_group_wait: group %d of %zu",
               group, m ? m->grad_groups.size() : (size_t)0);
     DWS_CHECK(m->grad_groups[group].flushed, DWS_ERR_STATE, "dws_model_grad_group_wait: no backward has handed group %d over", group);
-    DWS_HIP(hipStreamWaitEvent((hipStream_t)waiting_stream, m->grad_groups[group].ev, 0));
+    DWS_TRY(m->grad_groups[group].ev.make_wait((hipStream_t)waiting_stream));
     return DWS_OK;
 }
 
@@ -456,18 +411,17 @@ int dws_model_grad_ready_seq(dws_model* m, int32_t count, const char* const* nam
     DWS_CHECK(m && names && seq_out && count >= 0, DWS_ERR_INVALID, "dws_model_grad_ready_seq: null argument");
     DWS_CHECK(!m->grad_touch_prev.empty(), DWS_ERR_STATE, "dws_model_grad_ready_seq: no backward with gradient sinks has run");
     for (int i = 0; i < count; ++i) {
-        auto it = m->index.find(names[i]);
-        DWS_CHECK(it != m->index.end(), DWS_ERR_INVALID, "unknown parameter '%s'", names[i]);
-        seq_out[i] = m->grad_touch_prev[it->second];
+        const dws::ParamSpec* p = m->find(names[i]);
+        if (!p) return DWS_ERR_INVALID;
+        seq_out[i] = m->grad_touch_prev[p->index];
     }
     return DWS_OK;
 }
 
 int dws_model_get_grad(dws_model* m, const char* name, float* dst, int64_t numel, void* stream) {
     DWS_CHECK(m && name && dst, DWS_ERR_INVALID, "dws_model_get_grad: null argument");
-    auto it = m->index.find(name);
-    DWS_CHECK(it != m->index.end(), DWS_ERR_INVALID, "unknown parameter '%s'", name);
-    dws::ParamSpec* p = m->params[it->second];
+    dws::ParamSpec* p = m->find(name);
+    if (!p) return DWS_ERR_INVALID;
     DWS_CHECK(p->dtype == 0 && (int64_t)p->numel() == numel, DWS_ERR_INVALID, "'%s': grad has %zu elements, got %lld", name,
               p->numel(), (long long)numel);
     float* g = m->G(name);
@@ -483,9 +437,8 @@ int dws_model_update_params(dws_model* m, int32_t count, const char* const* name
     if (count == 0) return DWS_OK;
     std::vector<dws::CopyJob> jobs((size_t)count);
     for (int i = 0; i < count; ++i) {
-        auto it = m->index.find(names[i]);
-        DWS_CHECK(it != m->index.end(), DWS_ERR_INVALID, "unexpected key '%s' in state_dict", names[i]);
-        dws::ParamSpec* p = m->params[it->second];
+        dws::ParamSpec* p = m->find(names[i], true);
+        if (!p) return DWS_ERR_INVALID;
         DWS_CHECK(p->dtype == 0 && srcs[i], DWS_ERR_INVALID, "'%s': update_params takes float32 device tensors", names[i]);
         jobs[i] = {srcs[i], p->buf.f(), (int64_t)p->numel()};
     }
@@ -502,9 +455,8 @@ int dws_model_get_grads(dws_model* m, int32_t count, const char* const* names, f
     if (count == 0) return DWS_OK;
     std::vector<dws::CopyJob> jobs((size_t)count);
     for (int i = 0; i < count; ++i) {
-        auto it = m->index.find(names[i]);
-        DWS_CHECK(it != m->index.end(), DWS_ERR_INVALID, "unknown parameter '%s'", names[i]);
-        dws::ParamSpec* p = m->params[it->second];
+        dws::ParamSpec* p = m->find(names[i]);
+        if (!p) return DWS_ERR_INVALID;
         DWS_CHECK(p->dtype == 0 && (int64_t)p->numel() == numels[i], DWS_ERR_INVALID, "'%s': grad has %zu elements, got %lld",
                   names[i], p->numel(), (long long)numels[i]);
         float* g = m->G(names[i]);
@@ -514,23 +466,17 @@ int dws_model_get_grads(dws_model* m, int32_t count, const char* const* names, f
     return multi_copy(m, jobs, (hipStream_t)stream);
 }
 
-// One kernel for a list of device-to-device copies.  The job table travels through a pinned staging buffer so nothing
-// blocks the host; an event per staging slot guards its reuse.  The device-side table is written and read in stream order.
+// One kernel for a list of device-to-device copies.  The job table travels through the pinned staging ring so nothing
+// blocks the host.  The device-side table is written and read in stream order.
 static int multi_copy(dws_model* m, std::vector<dws::CopyJob>& jobs, hipStream_t stream) {
-    const int slot = m->copy_slot;
-    m->copy_slot = (slot + 1) % dws_model::COPY_SLOTS;
-    if (!m->copy_consumed[slot]) DWS_HIP(hipEventCreateWithFlags(&m->copy_consumed[slot], hipEventDisableTiming));
-    else DWS_HIP(hipEventSynchronize(m->copy_consumed[slot]));
-    if (m->copy_pinned_cap[slot] < jobs.size()) {
-        if (m->copy_pinned[slot]) (void)hipHostFree(m->copy_pinned[slot]);
-        m->copy_pinned_cap[slot] = jobs.size() * 2;
-        DWS_HIP(hipHostMalloc(&m->copy_pinned[slot], m->copy_pinned_cap[slot] * sizeof(dws::CopyJob), hipHostMallocDefault));
-    }
-    std::memcpy(m->copy_pinned[slot], jobs.data(), jobs.size() * sizeof(dws::CopyJob));
+    const size_t bytes = jobs.size() * sizeof(dws::CopyJob);
+    void* h = nullptr;
+    DWS_TRY(m->copy_ring.acquire(bytes, &h));
+    std::memcpy(h, jobs.data(), bytes);
     dws::DevBuf& table = m->copy_table;
-    DWS_TRY(table.ensure(jobs.size() * 2 * sizeof(dws::CopyJob)));
-    DWS_HIP(hipMemcpyAsync(table.p, m->copy_pinned[slot], jobs.size() * sizeof(dws::CopyJob), hipMemcpyHostToDevice, stream));
-    DWS_HIP(hipEventRecord(m->copy_consumed[slot], stream));
+    DWS_TRY(table.ensure(bytes * 2));
+    DWS_HIP(hipMemcpyAsync(table.p, h, bytes, hipMemcpyHostToDevice, stream));
+    DWS_TRY(m->copy_ring.commit(stream));
     return dws::launch_multi_copy((const dws::CopyJob*)table.p, (int)jobs.size(), stream);
 }
 
@@ -555,40 +501,6 @@ int dws_optim_create(dws_optim** out) {
 
 int dws_optim_destroy(dws_optim* o) {
     delete o;
-    return DWS_OK;
-}
-
-// The staging slot of a call: the next one of the ring whose last upload has been consumed (hipEventQuery, no wait); while
-// none is free the ring grows, so the host never waits for the GPU (only a ring of MAX_SLOTS busy slots would).
-static int optim_slot(dws_optim* o, size_t njobs, dws_optim::Slot** out) {
-    const int n = (int)o->ring.size();
-    int pick = -1;
-    for (int k = 0; k < n && pick < 0; ++k) {
-        const int s = (o->next + k) % n;
-        if (hipEventQuery(o->ring[s].consumed) == hipSuccess) pick = s;
-    }
-    (void)hipGetLastError();      // hipErrorNotReady of a busy slot is not an error
-    if (pick < 0) {
-        if (n < dws_optim::MAX_SLOTS) {
-            dws_optim::Slot sl;
-            DWS_HIP(hipEventCreateWithFlags(&sl.consumed, hipEventDisableTiming));
-            o->ring.push_back(sl);
-            pick = n;
-        } else {
-            pick = o->next % n;
-            DWS_HIP(hipEventSynchronize(o->ring[pick].consumed));
-        }
-    }
-    o->next = pick + 1;
-    dws_optim::Slot& sl = o->ring[pick];
-    if (sl.cap < njobs) {
-        if (sl.pinned) (void)hipHostFree(sl.pinned);
-        sl.pinned = nullptr;
-        sl.cap = 0;
-        DWS_HIP(hipHostMalloc(&sl.pinned, njobs * 2 * sizeof(dws::OptimJob), hipHostMallocDefault));
-        sl.cap = njobs * 2;
-    }
-    *out = &sl;
     return DWS_OK;
 }
 
@@ -622,9 +534,8 @@ int dws_optim_step(dws_optim* o, int32_t count, float* const* params, const floa
         j.mirror = mirrors ? mirrors[i] : nullptr;
         j.numel = numels[i];
         if (model && names[i]) {
-            auto it = model->index.find(names[i]);
-            DWS_CHECK(it != model->index.end(), DWS_ERR_INVALID, "unknown parameter '%s'", names[i]);
-            dws::ParamSpec* p = model->params[it->second];
+            dws::ParamSpec* p = model->find(names[i]);
+            if (!p) return DWS_ERR_INVALID;
             DWS_CHECK(p->dtype == 0, DWS_ERR_INVALID, "'%s': the optimizer step takes float32 parameters", names[i]);
             DWS_CHECK((int64_t)p->numel() == numels[i], DWS_ERR_INVALID, "'%s': parameter has %zu elements, got %lld", names[i],
                       p->numel(), (long long)numels[i]);
@@ -645,12 +556,13 @@ int dws_optim_step(dws_optim* o, int32_t count, float* const* params, const floa
         DWS_CHECK(chunks < (int64_t)1 << 30, DWS_ERR_UNSUPPORTED, "dws_optim_step: more than 2^30 chunks");
     }
     hipStream_t s = (hipStream_t)stream;
-    dws_optim::Slot* slot = nullptr;
-    DWS_TRY(optim_slot(o, jobs.size(), &slot));
-    std::memcpy(slot->pinned, jobs.data(), jobs.size() * sizeof(dws::OptimJob));
-    DWS_TRY(o->table.ensure(jobs.size() * 2 * sizeof(dws::OptimJob)));
-    DWS_HIP(hipMemcpyAsync(o->table.p, slot->pinned, jobs.size() * sizeof(dws::OptimJob), hipMemcpyHostToDevice, s));
-    DWS_HIP(hipEventRecord(slot->consumed, s));
+    const size_t bytes = jobs.size() * sizeof(dws::OptimJob);
+    void* staged = nullptr;
+    DWS_TRY(o->ring.acquire(bytes, &staged));
+    std::memcpy(staged, jobs.data(), bytes);
+    DWS_TRY(o->table.ensure(bytes * 2));
+    DWS_HIP(hipMemcpyAsync(o->table.p, staged, bytes, hipMemcpyHostToDevice, s));
+    DWS_TRY(o->ring.commit(s));
     const dws::OptimJob* table = (const dws::OptimJob*)o->table.p;
     if (clip || grad_norm_out)
         DWS_TRY(dws::launch_optim_norm(table, count, (int)chunks, o->partials(), o->counter(), o->norm(), grad_norm_out, s));
@@ -674,18 +586,18 @@ int dws_model_read_tap(dws_model* m, const char* tap, float* dst, int64_t capaci
     DWS_CHECK(m && tap && dst, DWS_ERR_INVALID, "dws_model_read_tap: null argument");
     if (std::strcmp(tap, "sampler_eps") == 0) {     // the network output of the sampler's last reverse step
         const int64_t n = m->B * m->d.out_channels * m->L;
-        DWS_CHECK(m->smp_eps.p && capacity >= n, DWS_ERR_INVALID, "tap sampler_eps: no sampler step has run, or capacity %lld < %lld",
+        DWS_CHECK(m->smp.eps.p && capacity >= n, DWS_ERR_INVALID, "tap sampler_eps: no sampler step has run, or capacity %lld < %lld",
                   (long long)capacity, (long long)n);
         // the buffer is sized by the last sampler step: after a prepare() to a larger shape it no longer matches
-        DWS_CHECK(m->smp_eps.bytes >= (size_t)n * 4 && m->smp_eps_B == m->B && m->smp_eps_L == m->L, DWS_ERR_STATE,
+        DWS_CHECK(m->smp.eps.bytes >= (size_t)n * 4 && m->smp.eps_B == m->B && m->smp.eps_L == m->L, DWS_ERR_STATE,
                   "tap sampler_eps: the last sampler step ran at B=%lld L=%lld, the model is prepared for B=%lld L=%lld",
-                  (long long)m->smp_eps_B, (long long)m->smp_eps_L, (long long)m->B, (long long)m->L);
-        DWS_HIP(hipMemcpyAsync(dst, m->smp_eps.p, (size_t)n * 4, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+                  (long long)m->smp.eps_B, (long long)m->smp.eps_L, (long long)m->B, (long long)m->L);
+        DWS_HIP(hipMemcpyAsync(dst, m->smp.eps.p, (size_t)n * 4, hipMemcpyDeviceToDevice, (hipStream_t)stream));
         return DWS_OK;
     }
     if (std::strcmp(tap, "sampler_graphs") == 0) {  // number of sampler graphs this model has instantiated (one float)
         DWS_CHECK(capacity >= 1, DWS_ERR_INVALID, "tap buffer too small");
-        const float v = (float)m->graphs_made;
+        const float v = (float)m->smp.graphs_made;
         DWS_HIP(hipMemcpyAsync(dst, &v, 4, hipMemcpyHostToDevice, (hipStream_t)stream));
         DWS_HIP(hipStreamSynchronize((hipStream_t)stream));
         return DWS_OK;
@@ -697,8 +609,8 @@ int dws_sampler_run(dws_model* m, float* x, const float* alpha, const float* alp
                     int32_t T, const float* noise, uint64_t seed, int32_t init_from_seed, int32_t use_graph,
                     void* stream) {
     DWS_CHECK(m && x, DWS_ERR_INVALID, "dws_sampler_run: null argument");
-    DWS_CHECK(!m->cfg_on, DWS_ERR_UNSUPPORTED, "classifier-free guidance runs on dws_sampler_run_schedule only (dws_sampler_run)");
-    DWS_CHECK(m->clip_B == 0, DWS_ERR_UNSUPPORTED, "per-clip seeds run on the schedule entries only (dws_sampler_run)");
+    DWS_CHECK(!m->smp.cfg_on, DWS_ERR_UNSUPPORTED, "classifier-free guidance runs on dws_sampler_run_schedule only (dws_sampler_run)");
+    DWS_CHECK(m->smp.clip_B == 0, DWS_ERR_UNSUPPORTED, "per-clip seeds run on the schedule entries only (dws_sampler_run)");
     return dws::sampler_run(m, x, alpha, alpha_bar, sigma, T, noise, seed, init_from_seed, use_graph,
                             (hipStream_t)stream);
 }
@@ -706,8 +618,8 @@ int dws_sampler_run(dws_model* m, float* x, const float* alpha, const float* alp
 int dws_sampler_steps(dws_model* m, float* x, const float* alpha, const float* alpha_bar, const float* sigma,
                       int32_t T, int32_t t_start, int32_t n_steps, uint64_t seed, int32_t use_graph, void* stream) {
     DWS_CHECK(m && x, DWS_ERR_INVALID, "dws_sampler_steps: null argument");
-    DWS_CHECK(!m->cfg_on, DWS_ERR_UNSUPPORTED, "classifier-free guidance runs on dws_sampler_run_schedule only (dws_sampler_steps)");
-    DWS_CHECK(m->clip_B == 0, DWS_ERR_UNSUPPORTED, "per-clip seeds run on the schedule entries only (dws_sampler_steps)");
+    DWS_CHECK(!m->smp.cfg_on, DWS_ERR_UNSUPPORTED, "classifier-free guidance runs on dws_sampler_run_schedule only (dws_sampler_steps)");
+    DWS_CHECK(m->smp.clip_B == 0, DWS_ERR_UNSUPPORTED, "per-clip seeds run on the schedule entries only (dws_sampler_steps)");
     return dws::sampler_steps(m, x, alpha, alpha_bar, sigma, T, t_start, n_steps, seed, use_graph,
                               (hipStream_t)stream);
 }
@@ -724,7 +636,7 @@ int dws_sampler_run_edit(dws_model* m, float* x, int32_t kind, int32_t S, const 
                          const float* noise, uint64_t seed, int32_t init_from_seed, int32_t use_graph,
                          const dws_sampler_edit* edit, void* stream) {
     DWS_CHECK(m && x && edit, DWS_ERR_INVALID, "dws_sampler_run_edit: null argument");
-    DWS_CHECK(!m->cfg_on, DWS_ERR_UNSUPPORTED, "classifier-free guidance runs on dws_sampler_run_schedule only (dws_sampler_run_edit)");
+    DWS_CHECK(!m->smp.cfg_on, DWS_ERR_UNSUPPORTED, "classifier-free guidance runs on dws_sampler_run_schedule only (dws_sampler_run_edit)");
     return dws::sampler_run_schedule(m, x, kind, S, net_steps, coef, noise, seed, init_from_seed, use_graph, edit,
                                      nullptr, (hipStream_t)stream);
 }
@@ -734,7 +646,7 @@ int dws_sampler_run_program(dws_model* m, float* x, int32_t kind, int32_t S, con
                             uint64_t seed, int32_t init_from_seed, int32_t use_graph, const dws_sampler_edit* edit,
                             void* stream) {
     DWS_CHECK(m && x && edit, DWS_ERR_INVALID, "dws_sampler_run_program: null argument");
-    DWS_CHECK(!m->cfg_on, DWS_ERR_UNSUPPORTED, "classifier-free guidance runs on dws_sampler_run_schedule only (dws_sampler_run_program)");
+    DWS_CHECK(!m->smp.cfg_on, DWS_ERR_UNSUPPORTED, "classifier-free guidance runs on dws_sampler_run_schedule only (dws_sampler_run_program)");
     return dws::sampler_run_program(m, x, kind, S, net_steps, coef, V, visit_step, jump_coef, noise, seed,
                                     init_from_seed, use_graph, edit, (hipStream_t)stream);
 }

@@ -22,6 +22,7 @@
 #include <vector>
 
 #include "fftconv.h"
+#include "host_util.h"
 
 #include "fft_core.h"
 
@@ -830,18 +831,6 @@ bool fftconv_supported(int L, int* log2m) {
     return true;
 }
 
-static int cu_count() {
-    static int n_dev[DWS_MAX_DEVICES] = {};
-    int& n = n_dev[current_device_slot()];
-    if (!n) {
-        int dev = 0;
-        hipDeviceProp_t prop;
-        if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) n = prop.multiProcessorCount;
-        if (n <= 0) n = 256;
-    }
-    return n;
-}
-
 // DWS_FFT_TRACE=1: the launch runs the stamped instance, waits, and prints the mean ticks per phase (one line per traced row
 // index: a workgroup's first row starts cold, the later ones show the steady state) on stderr -- the per-phase budget of a
 // row.  s_memtime is per XCD: only differences inside one wave / workgroup are formed.
@@ -854,24 +843,15 @@ static int fft_trace_launch(FftConvArgs a, int nwg, hipStream_t s) {
     auto kern = fused ? fftconv_kernel<LOG2M, C::THREADS, true, C::FUSED> : fftconv_kernel<LOG2M, C::THREADS, true>;
     constexpr int NP = FftPlan<LOG2M>::N16 - 1;
     const int T4 = (FftPlan<LOG2M>::TAIL4 && !fused) ? 1 : 0, NST = 3 + NP + T4 + 1 + T4 + NP + 2;   // fused: the pair stage carries both tails
-    static bool attr_dev[DWS_MAX_DEVICES] = {};
-    bool& attr = attr_dev[current_device_slot()];
-    if (!attr) {
-        DWS_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)C::LDS));
-        attr = true;
-    }
+    DWS_TRY((fused ? kernel_setup<fftconv_kernel<LOG2M, C::THREADS, true, C::FUSED>>(C::LDS)
+                   : kernel_setup<fftconv_kernel<LOG2M, C::THREADS, true>>(C::LDS)));
     constexpr int WAVES = C::THREADS / 64, PER = FFT_TRACE_ROWS * FFT_TRACE_SLOTS;
     // stamps per row: start, loads, top, the plan's further radix-16 passes, (tail), pointwise, (tail), inverse passes, bottom, barrier
-    const size_t n = (size_t)nwg * WAVES * PER;
-    unsigned long long* d = nullptr;
-    DWS_HIP(hipMalloc(&d, n * 8));
-    DWS_HIP(hipMemsetAsync(d, 0, n * 8, s));
-    a.trace = d;
-    hipLaunchKernelGGL(kern, dim3(nwg), dim3(C::THREADS), C::LDS, s, a);
-    DWS_HIP(hipStreamSynchronize(s));
-    std::vector<unsigned long long> h(n);
-    DWS_HIP(hipMemcpy(h.data(), d, n * 8, hipMemcpyDeviceToHost));
-    DWS_HIP(hipFree(d));
+    const std::vector<unsigned long long> h = capture_stamps((size_t)nwg * WAVES * PER, s, [&](unsigned long long* d) {
+        a.trace = d;
+        hipLaunchKernelGGL(kern, dim3(nwg), dim3(C::THREADS), C::LDS, s, a);
+    });
+    DWS_CHECK(!h.empty(), DWS_ERR_HIP, "fft trace: could not allocate the stamps");
     for (int ri = 0; ri < FFT_TRACE_ROWS; ++ri) {
         double ph[FFT_TRACE_SLOTS] = {0}, life = 0, span = 0;
         long waves = 0, wgs = 0;
@@ -916,18 +896,9 @@ static int launch_fc(const FftConvArgs& a_in, hipStream_t s) {
     } else {
         DWS_CHECK(a_in.rowsum == nullptr, DWS_ERR_UNSUPPORTED, "fftconv: row sums need an even plan (log2 M = %d)", LOG2M);
     }
-    static bool attr_dev[DWS_MAX_DEVICES] = {};
-    bool& attr = attr_dev[current_device_slot()];
-    if (!attr) {
-        if constexpr (!FftPlan<LOG2M>::ODD)
-            DWS_HIP(hipFuncSetAttribute((const void*)fftconv_kernel<LOG2M, C::THREADS, false, C::FUSED, true>,
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)C::LDS));
-        DWS_HIP(hipFuncSetAttribute((const void*)fftconv_kernel<LOG2M, C::THREADS, false, C::FUSED>,
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)C::LDS));
-        DWS_HIP(hipFuncSetAttribute((const void*)fftconv_kernel<LOG2M, C::THREADS>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    (int)C::LDS));
-        attr = true;
-    }
+    if constexpr (!FftPlan<LOG2M>::ODD) DWS_TRY((kernel_setup<fftconv_kernel<LOG2M, C::THREADS, false, C::FUSED, true>>(C::LDS)));
+    DWS_TRY((kernel_setup<fftconv_kernel<LOG2M, C::THREADS, false, C::FUSED>>(C::LDS)));
+    DWS_TRY((kernel_setup<fftconv_kernel<LOG2M, C::THREADS>>(C::LDS)));
     const FftConvArgs& a = a_in;
     // one resident workgroup per LDS slot of every CU walks several rows (RowSchedule); small rows: one row per block
     // (the persistent schedule from M = 4096 / 1024 up: 32.0-32.2 vs 31.7-31.9 us and 16.4 vs 16.3 us, no gain)
@@ -952,52 +923,28 @@ static int launch_fcorr(const FftCorrArgs& a, hipStream_t s) {
     static const bool old = std::getenv("DWS_FFTCORR_OLD") != nullptr;      // same-box A/B: the scattered pair stage of rounds 1-5
     if constexpr (!FftPlan<LOG2M>::ODD) {
         if (!old && !half) {
-            auto kern = fftcorr_blk_kernel<LOG2M>;
-            static bool attrb_dev[DWS_MAX_DEVICES] = {};
-            bool& attrb = attrb_dev[current_device_slot()];
-            if (!attrb) {
-                DWS_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)C::LDS));
-                attrb = true;
-            }
-            hipLaunchKernelGGL(kern, dim3(a.H, ceil_div(a.B, a.bchunk)), dim3(C::M / 16), C::LDS, s, a);
+            DWS_TRY(kernel_setup<fftcorr_blk_kernel<LOG2M>>(C::LDS));
+            hipLaunchKernelGGL(fftcorr_blk_kernel<LOG2M>, dim3(a.H, ceil_div(a.B, a.bchunk)), dim3(C::M / 16), C::LDS, s, a);
             return DWS_OK;
         }
     }
     if (LOG2M >= 14 && half) {
         constexpr int TH = C::THREADS > 512 ? 512 : C::THREADS;
-        auto kern = fftcorr_kernel<LOG2M, TH>;
-        static bool attr_dev[DWS_MAX_DEVICES] = {};
-    bool& attr = attr_dev[current_device_slot()];
-        if (!attr) {
-            DWS_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)C::LDS));
-            attr = true;
-        }
-        hipLaunchKernelGGL(kern, dim3(a.H, ceil_div(a.B, a.bchunk)), dim3(TH), C::LDS, s, a);
+        DWS_TRY((kernel_setup<fftcorr_kernel<LOG2M, TH>>(C::LDS)));
+        hipLaunchKernelGGL((fftcorr_kernel<LOG2M, TH>), dim3(a.H, ceil_div(a.B, a.bchunk)), dim3(TH), C::LDS, s, a);
         return DWS_OK;
     }
     constexpr int TH = C::THREADS;
-    auto kern = fftcorr_kernel<LOG2M, TH>;
-    static bool attr_dev[DWS_MAX_DEVICES] = {};
-    bool& attr = attr_dev[current_device_slot()];
-    if (!attr) {
-        DWS_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)C::LDS));
-        attr = true;
-    }
-    hipLaunchKernelGGL(kern, dim3(a.H, ceil_div(a.B, a.bchunk)), dim3(TH), C::LDS, s, a);
+    DWS_TRY((kernel_setup<fftcorr_kernel<LOG2M, TH>>(C::LDS)));
+    hipLaunchKernelGGL((fftcorr_kernel<LOG2M, TH>), dim3(a.H, ceil_div(a.B, a.bchunk)), dim3(TH), C::LDS, s, a);
     return DWS_OK;
 }
 
 template <int LOG2M>
 static int launch_rf(const float* in, float* out, const float* tw, const float* twn, int H, hipStream_t s) {
     using C = FcCfg<LOG2M>;
-    auto kern = rfft_rows_kernel<LOG2M, C::THREADS>;
-    static bool attr_dev[DWS_MAX_DEVICES] = {};
-    bool& attr = attr_dev[current_device_slot()];
-    if (!attr) {
-        DWS_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)C::LDS));
-        attr = true;
-    }
-    hipLaunchKernelGGL(kern, dim3(H), dim3(C::THREADS), C::LDS, s, in, (::float2*)out, (const ::float2*)tw,
+    DWS_TRY((kernel_setup<rfft_rows_kernel<LOG2M, C::THREADS>>(C::LDS)));
+    hipLaunchKernelGGL((rfft_rows_kernel<LOG2M, C::THREADS>), dim3(H), dim3(C::THREADS), C::LDS, s, in, (::float2*)out, (const ::float2*)tw,
                        (const ::float2*)twn);
     return DWS_OK;
 }
@@ -1058,14 +1005,8 @@ int launch_fftconv_seg(const FftConvSegArgs& a, hipStream_t s) {
     using C = FcCfg<FFTCONV_SEG_LOG2M>;
     constexpr int TH = 512, S = 1 << FFTCONV_SEG_LOG2M;
     ProfileScope ps("fftconv_seg", s);
-    auto kern = fftconv_seg_kernel<FFTCONV_SEG_LOG2M, TH>;
-    static bool attr_dev[DWS_MAX_DEVICES] = {};
-    bool& attr = attr_dev[current_device_slot()];
-    if (!attr) {
-        DWS_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)C::LDS));
-        attr = true;
-    }
-    hipLaunchKernelGGL(kern, dim3(a.B * a.H, ceil_div(a.L, S)), dim3(TH), C::LDS, s, a);
+    DWS_TRY((kernel_setup<fftconv_seg_kernel<FFTCONV_SEG_LOG2M, TH>>(C::LDS)));
+    hipLaunchKernelGGL((fftconv_seg_kernel<FFTCONV_SEG_LOG2M, TH>), dim3(a.B * a.H, ceil_div(a.L, S)), dim3(TH), C::LDS, s, a);
     return DWS_OK;
 }
 

@@ -47,19 +47,11 @@ int launch_optim_step(const OptimJob* table_dev, int njobs, int nchunks, const O
 
 // The handle of dws_optim_create: staging ring of the job table, the device table, the norm scratch.
 struct dws_optim {
-    struct Slot {
-        void* pinned = nullptr;
-        size_t cap = 0;              // in jobs
-        hipEvent_t consumed = nullptr;   // recorded behind the upload that read `pinned`
-    };
-    static constexpr int MAX_SLOTS = 64;
-    std::vector<Slot> ring;
-    int next = 0;
-    dws::DevBuf table;               // OptimJob[]: written and read in stream order
+    dws::StagingRing ring{64};       // (64 slots: the host never waits for the GPU, however far ahead it runs)
+    dws::DevBuf table;              // OptimJob[]: written and read in stream order
     dws::DevBuf scratch;             // double partials[OPTIM_MAX_GRID], float norm, uint32 counter
     std::vector<dws::OptimJob> jobs; // host scratch of a call
     double* partials() const { return static_cast<double*>(scratch.p); }
     float* norm() const { return reinterpret_cast<float*>(partials() + dws::OPTIM_MAX_GRID); }
     unsigned* counter() const { return reinterpret_cast<unsigned*>(norm() + 1); }
-    ~dws_optim();
 };

@@ -177,10 +177,3 @@ int launch_optim_step(const OptimJob* table_dev, int njobs, int nchunks, const O
 }
 
 }  // namespace dws
-
-dws_optim::~dws_optim() {
-    for (auto& sl : ring) {
-        if (sl.consumed) (void)hipEventDestroy(sl.consumed);
-        if (sl.pinned) (void)hipHostFree(sl.pinned);
-    }
-}

@@ -499,35 +499,17 @@ static void smp_launch_step(int kind, bool vec, const StepArgs& a, hipStream_t s
     });
 }
 
-// The device copy of a table is keyed on its CONTENTS (the same size with another schedule must not reuse it): uploaded
-// only when `src` differs from `have`, the host copy of what is resident.
-template <class T>
-static int upload_if_changed(DevBuf& dev, std::vector<T>& have, const T* src, size_t count, hipStream_t s) {
-    if (dev.p && have.size() == count && std::memcmp(src, have.data(), count * sizeof(T)) == 0) return DWS_OK;
-    DWS_TRY(dev.ensure(count * sizeof(T)));
-    DWS_HIP(hipMemcpyAsync(dev.p, src, count * sizeof(T), hipMemcpyHostToDevice, s));
-    DWS_HIP(hipStreamSynchronize(s));
-    have.assign(src, src + count);
-    return DWS_OK;
-}
-
 // The caller's stream may be the legacy null stream, which cannot be captured: capture and replay on an engine-owned
-// stream that is ordered after / before the caller's stream with events.
-static int engine_after_caller(dws_model* m, hipStream_t s) {
-    if (!m->smp_stream) {
-        DWS_HIP(hipStreamCreateWithFlags(&m->smp_stream, hipStreamNonBlocking));
-        DWS_HIP(hipEventCreateWithFlags(&m->smp_ev_in, hipEventDisableTiming));
-        DWS_HIP(hipEventCreateWithFlags(&m->smp_ev_out, hipEventDisableTiming));
-    }
-    DWS_HIP(hipEventRecord(m->smp_ev_in, s));
-    DWS_HIP(hipStreamWaitEvent(m->smp_stream, m->smp_ev_in, 0));
-    return DWS_OK;
+// stream (*engine) that is ordered after / before the caller's stream with events.
+static int engine_after_caller(dws_model* m, hipStream_t s, hipStream_t* engine) {
+    DWS_TRY(m->smp.stream.get(engine));
+    DWS_TRY(m->smp.ev_in.record(s));
+    return m->smp.ev_in.make_wait(*engine);
 }
 
 static int caller_after_engine(dws_model* m, hipStream_t s) {
-    DWS_HIP(hipEventRecord(m->smp_ev_out, m->smp_stream));
-    DWS_HIP(hipStreamWaitEvent(s, m->smp_ev_out, 0));
-    return DWS_OK;
+    DWS_TRY(m->smp.ev_out.record(m->smp.stream.s));
+    return m->smp.ev_out.make_wait(s);
 }
 
 // `exec` becomes the graph of one step: kept when `reuse` says the held one still fits, otherwise captured from what
@@ -549,7 +531,7 @@ static int capture_step(dws_model* m, hipStream_t cs, hipGraphExec_t& exec, bool
     err = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
     hipGraphDestroy(graph);
     DWS_HIP(err);
-    ++m->graphs_made;
+    ++m->smp.graphs_made;
     return DWS_OK;
 }
 
@@ -571,19 +553,19 @@ static std::vector<float> ddpm_table(const float* alpha, const float* alpha_bar,
 static int upload_tables(dws_model* m, const float* alpha, const float* alpha_bar, const float* sigma, int T,
                          hipStream_t s) {
     const std::vector<float> h = ddpm_table(alpha, alpha_bar, sigma, T);
-    DWS_TRY(m->smp_state.ensure(8));
-    return upload_if_changed(m->smp_tables, m->smp_host_tables, h.data(), h.size(), s);
+    DWS_TRY(m->smp.state.ensure(8));
+    return upload_if_changed(m->smp.tables, m->smp.host_tables, h.data(), h.size(), s);
 }
 
 static int one_step(dws_model* m, float* x, const float* noise, uint64_t seed, int T, hipStream_t s) {
     const size_t n = (size_t)m->B * m->d.out_channels * m->L;
-    int* t_dev = static_cast<int*>(m->smp_state.p);
+    int* t_dev = static_cast<int*>(m->smp.state.p);
     // every clip is at step t (`generate.py:50`): the network reads row t of the step table built at sampler entry
     m->step_idx = t_dev;
-    const int st = m->forward(x, nullptr, m->smp_eps.f(), s);
+    const int st = m->forward(x, nullptr, m->smp.eps.f(), s);
     m->step_idx = nullptr;
     DWS_TRY(st);
-    hipLaunchKernelGGL(smp_update_kernel<false>, dim3(smp_blocks(n)), dim3(256), 0, s, x, m->smp_eps.f(), m->smp_tables.f(),
+    hipLaunchKernelGGL(smp_update_kernel<false>, dim3(smp_blocks(n)), dim3(256), 0, s, x, m->smp.eps.f(), m->smp.tables.f(),
                        t_dev, noise, seed, (const uint64_t*)nullptr, n, T, ClipSeeds{});
     return DWS_OK;
 }
@@ -596,10 +578,10 @@ static int run_steps(dws_model* m, float* x, int T, int t_start, int n_steps, co
     DWS_CHECK(t_start < T && n_steps >= 0 && t_start - n_steps >= -1, DWS_ERR_INVALID, "bad step range");
     if (m->dirty) DWS_TRY(m->commit(s));
     const size_t n = (size_t)m->B * m->d.out_channels * m->L;
-    DWS_TRY(m->smp_eps.ensure(n * 4));
-    m->smp_eps_B = m->B; m->smp_eps_L = m->L;
+    DWS_TRY(m->smp.eps.ensure(n * 4));
+    m->smp.eps_B = m->B; m->smp.eps_L = m->L;
     DWS_TRY(m->build_step_table(T, nullptr, s));   // step-only part of the network for t = 0..T-1 (kept while weights and T stay)
-    int* t_dev = static_cast<int*>(m->smp_state.p);
+    int* t_dev = static_cast<int*>(m->smp.state.p);
 
     if (!use_graph) {
         hipLaunchKernelGGL(smp_set_step_kernel, dim3(1), dim3(1), 0, s, t_dev, t_start);
@@ -607,15 +589,15 @@ static int run_steps(dws_model* m, float* x, int T, int t_start, int n_steps, co
         DWS_HIP(hipGetLastError());
         return DWS_OK;
     }
-    DWS_TRY(engine_after_caller(m, s));
-    hipStream_t cs = m->smp_stream;
+    hipStream_t cs = nullptr;
+    DWS_TRY(engine_after_caller(m, s, &cs));
     hipLaunchKernelGGL(smp_set_step_kernel, dim3(1), dim3(1), 0, cs, t_dev, t_start);
-    const bool reuse = m->smp_graph && m->g_B == m->B && m->g_L == m->L && m->g_T == T && m->g_x == x &&
-                       m->g_noise == noise && m->g_seed == seed;
+    const bool reuse = m->smp.graph && m->smp.g_B == m->B && m->smp.g_L == m->L && m->smp.g_T == T && m->smp.g_x == x &&
+                       m->smp.g_noise == noise && m->smp.g_seed == seed;
     if (!reuse) m->drop_graph();    // this step bakes in x, the noise and the seed: a new one retires every held graph
-    DWS_TRY(capture_step(m, cs, m->smp_graph, reuse, [&] { return one_step(m, x, noise, seed, T, cs); }));
-    m->g_B = m->B; m->g_L = m->L; m->g_T = T; m->g_x = x; m->g_noise = noise; m->g_seed = seed;
-    for (int i = 0; i < n_steps; ++i) DWS_HIP(hipGraphLaunch(m->smp_graph, cs));
+    DWS_TRY(capture_step(m, cs, m->smp.graph, reuse, [&] { return one_step(m, x, noise, seed, T, cs); }));
+    m->smp.g_B = m->B; m->smp.g_L = m->L; m->smp.g_T = T; m->smp.g_x = x; m->smp.g_noise = noise; m->smp.g_seed = seed;
+    for (int i = 0; i < n_steps; ++i) DWS_HIP(hipGraphLaunch(m->smp.graph, cs));
     return caller_after_engine(m, s);
 }
 
@@ -653,13 +635,13 @@ struct SamplerProgram {
 // linear chain.
 static int schedule_step(dws_model* m, int kind, bool vec, const StepArgs& a, bool cfg, hipStream_t s) {
     m->step_idx = a.st;
-    const int rc = m->forward(a.x, nullptr, m->smp_eps.f(), s);
+    const int rc = m->forward(a.x, nullptr, m->smp.eps.f(), s);
     m->step_idx = nullptr;
     DWS_TRY(rc);
     if (cfg) {
         ProfileScope prof("smp_cfg", s);
-        if (vec) hipLaunchKernelGGL(smp_cfg_kernel<true>, dim3(smp_blocks(a.n)), dim3(256), 0, s, m->smp_eps.f(), a.st, a.n);
-        else hipLaunchKernelGGL(smp_cfg_kernel<false>, dim3(smp_blocks(a.n)), dim3(256), 0, s, m->smp_eps.f(), a.st, a.n);
+        if (vec) hipLaunchKernelGGL(smp_cfg_kernel<true>, dim3(smp_blocks(a.n)), dim3(256), 0, s, m->smp.eps.f(), a.st, a.n);
+        else hipLaunchKernelGGL(smp_cfg_kernel<false>, dim3(smp_blocks(a.n)), dim3(256), 0, s, m->smp.eps.f(), a.st, a.n);
     }
     // dws_profile_enable("smp_update"): the update kernel of an uncaptured step, by kind
     ProfileScope prof(kind == DWS_SAMPLER_DDPM ? "smp_update_ddpm" : kind == DWS_SAMPLER_DDIM ? "smp_update_ddim"
@@ -736,36 +718,36 @@ int sampler_run_schedule(dws_model* m, float* x, int kind, int S, const float* n
     DWS_CHECK(m->B > 0, DWS_ERR_STATE, "sampler before dws_model_prepare");
     DWS_CHECK(m->d.in_channels == m->d.out_channels, DWS_ERR_INVALID,
               "sampler needs in_channels == out_channels (x and eps share a shape, `generate.py:52`)");
-    const bool cfg = m->cfg_on;
+    const bool cfg = m->smp.cfg_on;
     DWS_CHECK(!cfg || (!e && !pg), DWS_ERR_UNSUPPORTED, "classifier-free guidance is not built for editing or program runs");
     DWS_CHECK(!cfg || m->B % 2 == 0, DWS_ERR_UNSUPPORTED,
               "classifier-free guidance needs a model prepared for 2 x Bc clips (prepared batch: %lld)", (long long)m->B);
     // per-clip seeds: one per clip of the sampler state (the first half of a guided run's doubled batch); `seed` is not read
-    const int clips = (int)m->clip_B;
+    const int clips = (int)m->smp.clip_B;
     DWS_CHECK(clips == 0 || clips == (cfg ? m->B / 2 : m->B), DWS_ERR_INVALID,
               "sampler: a table of %d clip seeds (dws_sampler_set_clip_seeds) for a sampler state of %lld clips", clips,
               (long long)(cfg ? m->B / 2 : m->B));
     if (m->dirty) DWS_TRY(m->commit(s));
     const size_t nfull = (size_t)m->B * m->d.out_channels * m->L;    // the network's batch
     const size_t n = cfg ? nfull / 2 : nfull;                         // what the caller's x, the noise and the update span
-    const ClipSeeds clip{clips ? static_cast<const uint64_t*>(m->clip_seeds_dev.p) : nullptr,
+    const ClipSeeds clip{clips ? static_cast<const uint64_t*>(m->smp.clip_seeds.p) : nullptr,
                          clips ? (size_t)m->d.out_channels * m->L : 0};
 
     // update tables, keyed on their contents; DDIM's and DPM-Solver++'s are used as given
     const std::vector<float> h = kind != DWS_SAMPLER_DDPM ? std::vector<float>(coef, coef + 5 * (size_t)S)
                                                           : ddpm_table(coef, coef + S, coef + 2 * (size_t)S, S);
-    DWS_TRY(upload_if_changed(m->sch_tables, m->sch_host_tables, h.data(), h.size(), s));
+    DWS_TRY(upload_if_changed(m->smp.sch_tables, m->smp.sch_host_tables, h.data(), h.size(), s));
     if (masked) {   // q1, q2 beside them, keyed the same way (n1, n2 stay on the host: arguments of the q-sample kernel)
-        DWS_TRY(upload_if_changed(m->sch_edit, m->sch_host_edit, e->edit_coef, 2 * (size_t)S, s));
-        DWS_TRY(m->sch_known.ensure(n * 4));
-        DWS_TRY(m->sch_mask.ensure((n + 3) / 4 * 4));
+        DWS_TRY(upload_if_changed(m->smp.sch_edit, m->smp.sch_host_edit, e->edit_coef, 2 * (size_t)S, s));
+        DWS_TRY(m->smp.sch_known.ensure(n * 4));
+        DWS_TRY(m->smp.sch_mask.ensure((n + 3) / 4 * 4));
     }
-    DWS_TRY(m->smp_eps.ensure(nfull * 4));
-    m->smp_eps_B = m->B; m->smp_eps_L = m->L;
-    if (kind == DWS_SAMPLER_DPMPP2M) DWS_TRY(m->sch_hist.ensure(nfull * 4));   // the previous step's x0 (first use of this kind)
+    DWS_TRY(m->smp.eps.ensure(nfull * 4));
+    m->smp.eps_B = m->B; m->smp.eps_L = m->L;
+    if (kind == DWS_SAMPLER_DPMPP2M) DWS_TRY(m->smp.sch_hist.ensure(nfull * 4));   // the previous step's x0 (first use of this kind)
     DWS_TRY(m->build_step_table(S, net_steps, s));   // the network's step-only part at net_steps (kept while they stay)
-    DWS_TRY(m->sch_state.ensure(32));                // step, finished blocks, seed (2 words), visit, history-valid word
-    int* st = static_cast<int*>(m->sch_state.p);
+    DWS_TRY(m->smp.sch_state.ensure(32));                // step, finished blocks, seed (2 words), visit, history-valid word
+    int* st = static_cast<int*>(m->smp.sch_state.p);
     const int V = pg ? pg->V : 0;
     const int R = pg ? V : S;     // streams R (a drawn x_T) and 2R + 1 (the q-sample) lie behind the per-visit ones
     if (pg) {   // step_of[V] and ja[V], jb[V] in one model-owned buffer, keyed on their contents
@@ -776,10 +758,10 @@ int sampler_run_schedule(dws_model* m, float* x, int kind, int S, const float* n
             std::memcpy(&hp[V + v], &pg->jump_coef[v], 4);
             std::memcpy(&hp[2 * (size_t)V + v], &pg->jump_coef[V + v], 4);
         }
-        DWS_TRY(upload_if_changed(m->sch_prog, m->sch_host_prog, hp.data(), hp.size(), s));
+        DWS_TRY(upload_if_changed(m->smp.sch_prog, m->smp.sch_host_prog, hp.data(), hp.size(), s));
     }
-    const int* step_of = pg ? static_cast<const int*>(m->sch_prog.p) : nullptr;
-    const float* jump = pg ? m->sch_prog.f() + V : nullptr;
+    const int* step_of = pg ? static_cast<const int*>(m->smp.sch_prog.p) : nullptr;
+    const float* jump = pg ? m->smp.sch_prog.f() + V : nullptr;
     const float* known_noise = masked ? e->known_noise : nullptr;
 
     // The state the steps work on: the caller's x on the caller's stream, or -- with a graph, and for the doubled state of
@@ -787,17 +769,14 @@ int sampler_run_schedule(dws_model* m, float* x, int kind, int S, const float* n
     // the state word, so a new x or seed (or known clip, mask, start step) replays the same graph.  Graphs are captured
     // and replayed on the engine's stream.
     const bool staged = use_graph || cfg;
-    if (staged) DWS_TRY(m->sch_x.ensure(nfull * 4));
-    float* xr = staged ? m->sch_x.f() : x;
+    if (staged) DWS_TRY(m->smp.sch_x.ensure(nfull * 4));
+    float* xr = staged ? m->smp.sch_x.f() : x;
     const auto aligned = [](const void* p) { return ((uintptr_t)p & 15) == 0; };
     // (the model's buffers come from hipMalloc; per clip every clip must begin on a group border)
     const bool vec = (clips ? clip.n_c : n) % 4 == 0 && aligned(noise) && aligned(known_noise) && (staged || aligned(x));
     const dim3 grid = smp_grid(n, clips, clip.n_c);     // of every launch here that draws
     hipStream_t q = s;
-    if (use_graph) {
-        DWS_TRY(engine_after_caller(m, s));
-        q = m->smp_stream;
-    }
+    if (use_graph) DWS_TRY(engine_after_caller(m, s, &q));
     if (init_from_seed && clips)
         hipLaunchKernelGGL(smp_fill_normal_clips_kernel<const uint64_t*>, grid, dim3(256), 0, q, xr, clip.n_c, clip.seeds,
                            (uint32_t)R);
@@ -813,8 +792,8 @@ int sampler_run_schedule(dws_model* m, float* x, int kind, int S, const float* n
     else
         hipLaunchKernelGGL(smp_set_state_kernel, dim3(1), dim3(1), 0, q, st, start, seed);
     if (masked) {
-        DWS_HIP(hipMemcpyAsync(m->sch_known.p, e->known, n * 4, hipMemcpyDeviceToDevice, q));
-        DWS_HIP(hipMemcpyAsync(m->sch_mask.p, e->mask, n, hipMemcpyDeviceToDevice, q));
+        DWS_HIP(hipMemcpyAsync(m->smp.sch_known.p, e->known, n * 4, hipMemcpyDeviceToDevice, q));
+        DWS_HIP(hipMemcpyAsync(m->smp.sch_mask.p, e->mask, n, hipMemcpyDeviceToDevice, q));
     }
     if (qsample && clips)
         hipLaunchKernelGGL(smp_qsample_kernel<true>, grid, dim3(256), 0, q, xr, e->start_noise,
@@ -824,17 +803,17 @@ int sampler_run_schedule(dws_model* m, float* x, int kind, int S, const float* n
         hipLaunchKernelGGL(smp_qsample_kernel<false>, dim3(smp_blocks(n)), dim3(256), 0, q, xr, e->start_noise,
                            e->edit_coef[2 * (size_t)S + start], e->edit_coef[3 * (size_t)S + start], n, seed,
                            (uint32_t)(2 * R + 1), ClipSeeds{});
-    if (cfg) hipLaunchKernelGGL(smp_set_cfg_scale_kernel, dim3(1), dim3(1), 0, q, st, m->cfg_scale);
+    if (cfg) hipLaunchKernelGGL(smp_set_cfg_scale_kernel, dim3(1), dim3(1), 0, q, st, m->smp.cfg_scale);
 
     StepArgs a{};
-    a.x = xr; a.eps = m->smp_eps.f(); a.tab = m->sch_tables.f(); a.st = st; a.noise = noise; a.n = n; a.S = S;
+    a.x = xr; a.eps = m->smp.eps.f(); a.tab = m->smp.sch_tables.f(); a.st = st; a.noise = noise; a.n = n; a.S = S;
     a.clips = clips;
     StepMore& more = a.more;
     more.V = V;
     more.clip = clip;
-    more.hist = kind == DWS_SAMPLER_DPMPP2M ? m->sch_hist.f() : nullptr;
+    more.hist = kind == DWS_SAMPLER_DPMPP2M ? m->smp.sch_hist.f() : nullptr;
     if (masked) {
-        more.edit = m->sch_edit.f(); more.y = m->sch_known.f(); more.mask = static_cast<const uint8_t*>(m->sch_mask.p);
+        more.edit = m->smp.sch_edit.f(); more.y = m->smp.sch_known.f(); more.mask = static_cast<const uint8_t*>(m->smp.sch_mask.p);
         more.known_noise = known_noise; more.step_of = step_of;
     }
     // the walk: `reverse` enqueues one reverse step on q; a jump visit is a launch of its own between them
@@ -859,10 +838,10 @@ int sampler_run_schedule(dws_model* m, float* x, int kind, int S, const float* n
         // the edited, the resampling and the guided step have graphs of their own beside the plain one, and each of the
         // four one per form of seed (the per-clip step is other kernel instances on another grid): the kinds of call may
         // alternate without a new capture
-        dws_model::SchGraph& have = m->sch_graphs[cfg ? dws_model::SCH_CFG : pg ? dws_model::SCH_PROG
-                                                  : masked ? dws_model::SCH_EDIT : dws_model::SCH_PLAIN][clips ? 1 : 0];
-        const dws_model::SchKey key{m->B, m->L, S, kind, vec ? 1 : 0, a.tab, noise, a.eps, xr, st, m->step_table_gen,
-                                    more.edit, more.y, more.mask, known_noise, V, pg ? m->sch_prog.p : nullptr, more.hist,
+        SamplerState::SchGraph& have = m->smp.sch_graphs[cfg ? SamplerState::SCH_CFG : pg ? SamplerState::SCH_PROG
+                                                  : masked ? SamplerState::SCH_EDIT : SamplerState::SCH_PLAIN][clips ? 1 : 0];
+        const SamplerState::SchKey key{m->B, m->L, S, kind, vec ? 1 : 0, a.tab, noise, a.eps, xr, st, m->step_table_gen,
+                                    more.edit, more.y, more.mask, known_noise, V, pg ? m->smp.sch_prog.p : nullptr, more.hist,
                                     clip.seeds};
         DWS_TRY(capture_step(m, q, have.exec, key == have.key, step));
         have.key = key;

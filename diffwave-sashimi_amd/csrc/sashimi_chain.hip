@@ -23,6 +23,7 @@
 #include <cstdlib>
 #include <vector>
 
+#include "host_util.h"
 #include "sashimi.h"
 #include "sashimi_mfma.h"
 
@@ -347,16 +348,11 @@ template <typename F>
 static void chain_trace_launch(int H, int nwg, int waves, S4TailArgs a, hipStream_t s, F launch) {
     static const char* names[9] = {"", "issue g,x loads", "GEMM-o (incl. load wait)", "GLU+res+LN2", "GEMM-1", "GELU (+skip request)",
                                    "GEMM-2", "out stores", "next LN1 + stores"};
-    unsigned long long* d = nullptr;
-    const size_t n = (size_t)nwg * waves * 16;
-    if (hipMalloc(&d, n * 8) != hipSuccess) return;
-    (void)hipMemsetAsync(d, 0, n * 8, s);
-    a.trace = d;
-    launch(a);
-    (void)hipStreamSynchronize(s);
-    std::vector<unsigned long long> h(n);
-    (void)hipMemcpy(h.data(), d, n * 8, hipMemcpyDeviceToHost);
-    (void)hipFree(d);
+    const std::vector<unsigned long long> h = capture_stamps((size_t)nwg * waves * 16, s, [&](unsigned long long* d) {
+        a.trace = d;
+        launch(a);
+    });
+    if (h.empty()) return;
     double ph[9] = {0}, life = 0;
     size_t cnt = 0;
     for (size_t w = 0; w < (size_t)nwg * waves; ++w) {
@@ -380,18 +376,9 @@ static int launch_chain_t(const S4TailArgs& a, hipStream_t s) {
     using T = ChainCfg<H, 2>;
     ProfileScope ps("s4_tail_mfma_chain", s);
     const size_t lds = (size_t)T::LDS_FLOATS * 4;
-    static int slots_dev[DWS_MAX_DEVICES] = {};
-    int& slots = slots_dev[current_device_slot()];
-    if (slots == 0) {
-        DWS_HIP(hipFuncSetAttribute((const void*)s4_tail_chain_kernel<H, 2, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        DWS_HIP(hipFuncSetAttribute((const void*)s4_tail_chain_kernel<H, 2, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        int dev = 0, ncu = 0, per_cu = 0;
-        DWS_HIP(hipGetDevice(&dev));
-        DWS_HIP(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev));
-        DWS_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, s4_tail_chain_kernel<H, 2, true>, T::THREADS, lds));
-        DWS_CHECK(ncu > 0 && per_cu > 0, DWS_ERR_HIP, "s4_tail_chain: occupancy query returned %d x %d", ncu, per_cu);
-        slots = ncu * per_cu;
-    }
+    int slots = 0;
+    DWS_TRY((kernel_setup<s4_tail_chain_kernel<H, 2, true>>(lds, &slots, T::THREADS, "s4_tail_chain")));
+    DWS_TRY((kernel_setup<s4_tail_chain_kernel<H, 2, false>>(lds)));
     const int ntiles = a.B * ceil_div(a.L, 32);
     const int grid = std::min(slots, ceil_div(ntiles, T::WAVES));
     static const bool trace = std::getenv("DWS_CHAIN_TRACE") != nullptr;

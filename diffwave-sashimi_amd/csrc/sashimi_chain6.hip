@@ -26,6 +26,7 @@
 #include <vector>
 
 #include "bf16_split.h"
+#include "host_util.h"
 #include "sashimi.h"
 #include "sashimi_mfma.h"
 #include "wavenet.h"
@@ -635,17 +636,10 @@ template <typename P>
 static int launch_wide6_p(const S4TailArgs& a, hipStream_t s) {
     using T = Wide6Cfg<128, 2, P::NT>;
     ProfileScope ps(P::NT == 3 ? "s4_tail_mfma_wide6" : "s4_tail_mfma_wide_f16x3", s);
-    static int ncu_dev[DWS_MAX_DEVICES] = {};
-    int& ncu = ncu_dev[current_device_slot()];
-    if (ncu == 0) {
-        DWS_HIP(hipFuncSetAttribute((const void*)s4_tail_wide6_kernel<P, 128, 2, true>, hipFuncAttributeMaxDynamicSharedMemorySize, T::LDS_BYTES));
-        DWS_HIP(hipFuncSetAttribute((const void*)s4_tail_wide6_kernel<P, 128, 2, false>, hipFuncAttributeMaxDynamicSharedMemorySize, T::LDS_BYTES));
-        int dev = 0;
-        DWS_HIP(hipGetDevice(&dev));
-        DWS_HIP(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev));
-    }
+    DWS_TRY((kernel_setup<s4_tail_wide6_kernel<P, 128, 2, true>>(T::LDS_BYTES)));
+    DWS_TRY((kernel_setup<s4_tail_wide6_kernel<P, 128, 2, false>>(T::LDS_BYTES)));
     const int ntiles = a.B * ceil_div(a.L, 128);
-    const int grid = std::min(ncu, ntiles);
+    const int grid = std::min(cu_count(), ntiles);
     if (a.ynext) hipLaunchKernelGGL((s4_tail_wide6_kernel<P, 128, 2, true>), dim3(grid), dim3(T::THREADS), T::LDS_BYTES, s, a);
     else hipLaunchKernelGGL((s4_tail_wide6_kernel<P, 128, 2, false>), dim3(grid), dim3(T::THREADS), T::LDS_BYTES, s, a);
     return DWS_OK;
@@ -664,16 +658,11 @@ template <typename F>
 static void chain6_trace_launch(int H, int nwg, int waves, S4TailArgs a, hipStream_t s, F launch) {
     static const char* names[9] = {"", "issue g,x loads", "GEMM-o (incl. load wait, split of g)", "GLU+res+LN2", "GEMM-1 (incl. split of y)",
                                    "GELU (+skip request)", "GEMM-2 (incl. split of u)", "out stores", "next LN1 + stores"};
-    unsigned long long* d = nullptr;
-    const size_t n = (size_t)nwg * waves * 16;
-    if (hipMalloc(&d, n * 8) != hipSuccess) return;
-    (void)hipMemsetAsync(d, 0, n * 8, s);
-    a.trace = d;
-    launch(a);
-    (void)hipStreamSynchronize(s);
-    std::vector<unsigned long long> h(n);
-    (void)hipMemcpy(h.data(), d, n * 8, hipMemcpyDeviceToHost);
-    (void)hipFree(d);
+    const std::vector<unsigned long long> h = capture_stamps((size_t)nwg * waves * 16, s, [&](unsigned long long* d) {
+        a.trace = d;
+        launch(a);
+    });
+    if (h.empty()) return;
     double ph[9] = {0}, life = 0;
     size_t cnt = 0;
     for (size_t w = 0; w < (size_t)nwg * waves; ++w) {
@@ -695,18 +684,9 @@ static int launch_chain6_t(const S4TailArgs& a, hipStream_t s) {
     using T = Chain6Cfg<H, 2, P::NT>;
     ProfileScope ps(P::NT == 3 ? "s4_tail_mfma_chain6" : "s4_tail_mfma_chain_f16x3", s);
     const size_t lds = (size_t)T::LDS_BYTES;
-    static int slots_dev[DWS_MAX_DEVICES] = {};
-    int& slots = slots_dev[current_device_slot()];
-    if (slots == 0) {
-        DWS_HIP(hipFuncSetAttribute((const void*)s4_tail_chain6_kernel<P, H, 2, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        DWS_HIP(hipFuncSetAttribute((const void*)s4_tail_chain6_kernel<P, H, 2, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        int dev = 0, ncu = 0, per_cu = 0;
-        DWS_HIP(hipGetDevice(&dev));
-        DWS_HIP(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev));
-        DWS_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, s4_tail_chain6_kernel<P, H, 2, true>, T::THREADS, lds));
-        DWS_CHECK(ncu > 0 && per_cu > 0, DWS_ERR_HIP, "s4_tail_chain6: occupancy query returned %d x %d", ncu, per_cu);
-        slots = ncu * per_cu;
-    }
+    int slots = 0;
+    DWS_TRY((kernel_setup<s4_tail_chain6_kernel<P, H, 2, true>>(lds, &slots, T::THREADS, "s4_tail_chain6")));
+    DWS_TRY((kernel_setup<s4_tail_chain6_kernel<P, H, 2, false>>(lds)));
     const int ntiles = a.B * ceil_div(a.L, 32);
     const int grid = std::min(slots, ceil_div(ntiles, T::WAVES));
     static const bool trace = std::getenv("DWS_CHAIN_TRACE") != nullptr;

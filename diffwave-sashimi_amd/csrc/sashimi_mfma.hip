@@ -17,6 +17,7 @@
 #include <cstdio>
 #include <vector>
 
+#include "host_util.h"
 #include "sashimi.h"
 #include "sashimi_mfma.h"
 #include "bf16_split.h"
@@ -592,16 +593,11 @@ template <typename F>
 static void tail_trace_launch(int H, int nwg, int waves, S4TailArgs a, hipStream_t s, F launch) {
     static const char* names[16] = {"", "staging", "GEMM-o", "barrier", "GLU+res", "barrier", "LN2 stats", "GEMM-1 q0", "GELU q0",
                                     "GEMM-2 q0", "GEMM-1 q1", "GELU q1", "GEMM-2 q1", "acc->tile", "out stores", "next LN1"};
-    unsigned long long* d = nullptr;
-    const size_t n = (size_t)nwg * waves * 16;
-    if (hipMalloc(&d, n * 8) != hipSuccess) return;
-    hipMemsetAsync(d, 0, n * 8, s);
-    a.trace = d;
-    launch(a);
-    hipStreamSynchronize(s);
-    std::vector<unsigned long long> h(n);
-    hipMemcpy(h.data(), d, n * 8, hipMemcpyDeviceToHost);
-    hipFree(d);
+    const std::vector<unsigned long long> h = capture_stamps((size_t)nwg * waves * 16, s, [&](unsigned long long* d) {
+        a.trace = d;
+        launch(a);
+    });
+    if (h.empty()) return;
     double ph[16] = {0}, span = 0, wgspan = 0;
     for (int g = 0; g < nwg; ++g) {
         unsigned long long g0 = ~0ull, g1 = 0;
@@ -627,13 +623,7 @@ static int launch_tail_split_t(const S4TailArgs& a, hipStream_t s) {
     ProfileScope ps(SP::NT == 3 ? "s4_tail_mfma_tile6" : "s4_tail_mfma_tile_f16x3", s);
     const int ntl = ceil_div(a.L, T::P);
     const size_t lds = (size_t)T::LDS_FLOATS * 4;
-    static bool attr_set_dev[DWS_MAX_DEVICES] = {};
-    bool& attr_set = attr_set_dev[current_device_slot()];
-    if (!attr_set) {
-        DWS_HIP(hipFuncSetAttribute((const void*)s4_tail_mfma_kernel<H, WM, WN, NT, 2, true, OCC, false, SP>,
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        attr_set = true;
-    }
+    DWS_TRY((kernel_setup<s4_tail_mfma_kernel<H, WM, WN, NT, 2, true, OCC, false, SP>>(lds)));
     hipLaunchKernelGGL((s4_tail_mfma_kernel<H, WM, WN, NT, 2, true, OCC, false, SP>), dim3(a.B * ntl), dim3(T::THREADS), lds, s, a);
     return DWS_OK;
 }
@@ -645,15 +635,8 @@ static int launch_tail_t(const S4TailArgs& a, hipStream_t s) {
     const int ntl = ceil_div(a.L, T::P);
     const size_t lds = (size_t)T::LDS_FLOATS * 4;
     const bool no_vec = getenv("DWS_TAIL_NO_VEC") != nullptr;   // (read per launch: tests switch it inside one process)
-    static bool attr_set_dev[DWS_MAX_DEVICES] = {};
-    bool& attr_set = attr_set_dev[current_device_slot()];
-    if (!attr_set) {
-        DWS_HIP(hipFuncSetAttribute((const void*)s4_tail_mfma_kernel<H, WM, WN, NT, 2, true, OCC, KGU>,
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        DWS_HIP(hipFuncSetAttribute((const void*)s4_tail_mfma_kernel<H, WM, WN, NT, 2, false, OCC, KGU>,
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        attr_set = true;
-    }
+    DWS_TRY((kernel_setup<s4_tail_mfma_kernel<H, WM, WN, NT, 2, true, OCC, KGU>>(lds)));
+    DWS_TRY((kernel_setup<s4_tail_mfma_kernel<H, WM, WN, NT, 2, false, OCC, KGU>>(lds)));
     static const bool trace = getenv("DWS_TAIL_TRACE") != nullptr;
     if (trace && (a.L & 3) == 0 && !no_vec && a.ynext) {
         tail_trace_launch(H, a.B * ntl, T::THREADS / 64, a, s, [&](const S4TailArgs& at) {

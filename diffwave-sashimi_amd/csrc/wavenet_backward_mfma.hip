@@ -1063,23 +1063,13 @@ int launch_wgrad_mfma(const WgradArgs& a_in, int T, float scale, float* dW, hipS
     const dim3 grid(ceil_div(a.O, 128), ceil_div(a.C, 128), T * a.nsplit);
     if (dma4) {
         constexpr int lds = 2 * 2 * 128 * 64 * 4;
-        static bool attr4_dev[DWS_MAX_DEVICES] = {};
-    bool& attr4 = attr4_dev[current_device_slot()];
-        if (!attr4) {
-            DWS_HIP(hipFuncSetAttribute((const void*)wgrad_dma4_kernel<0>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-            DWS_HIP(hipFuncSetAttribute((const void*)wgrad_dma4_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-            attr4 = true;
-        }
+        DWS_TRY(kernel_setup<wgrad_dma4_kernel<0>>(lds));
+        DWS_TRY(kernel_setup<wgrad_dma4_kernel<1>>(lds));
         if (a.split == 1) hipLaunchKernelGGL(wgrad_dma4_kernel<1>, grid, dim3(512), lds, s, a);
         else hipLaunchKernelGGL(wgrad_dma4_kernel<0>, grid, dim3(512), lds, s, a);
     } else if (T == 1 && !a.xact && !a.addc && !no_dma) {
         constexpr int lds = 2 * 2 * 128 * 66 * 4;
-        static bool attr_dev[DWS_MAX_DEVICES] = {};
-    bool& attr = attr_dev[current_device_slot()];
-        if (!attr) {
-            DWS_HIP(hipFuncSetAttribute((const void*)wgrad_dma_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-            attr = true;
-        }
+        DWS_TRY(kernel_setup<wgrad_dma_kernel>(lds));
         hipLaunchKernelGGL(wgrad_dma_kernel, grid, dim3(512), lds, s, a);
     } else if (T == 3) {
         hipLaunchKernelGGL(wgrad_mfma_kernel<3>, grid, dim3(256), 0, s, a);

@@ -15,6 +15,7 @@
 // beside the gate tile), the res rows last; all tile streams carry the nontemporal hint.
 #include <cstdlib>
 
+#include "host_util.h"
 #include "wavenet.h"
 
 namespace dws {
@@ -591,15 +592,8 @@ static int launch_bx3_t(const WnLayerArgs& a, hipStream_t s) {
     using T = Bx3Tile<C, S, PP, WV>;
     ProfileScope ps("wn_layer_bf16x3", s);
     const size_t lds = (size_t)T::LDS_FLOATS * 4;
-    static bool attr_dev[DWS_MAX_DEVICES] = {};
-    bool& attr = attr_dev[current_device_slot()];
-    if (!attr) {
-        DWS_HIP(hipFuncSetAttribute((const void*)wn_layer_bf16x3_kernel<C, S, PP, WV, true>,
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        DWS_HIP(hipFuncSetAttribute((const void*)wn_layer_bf16x3_kernel<C, S, PP, WV, false>,
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        attr = true;
-    }
+    DWS_TRY((kernel_setup<wn_layer_bf16x3_kernel<C, S, PP, WV, true>>(lds)));
+    DWS_TRY((kernel_setup<wn_layer_bf16x3_kernel<C, S, PP, WV, false>>(lds)));
     const dim3 grid(a.B * ceil_div(a.L, T::P));
     if ((a.L & 3) == 0)
         hipLaunchKernelGGL((wn_layer_bf16x3_kernel<C, S, PP, WV, true>), grid, dim3(T::THREADS), lds, s, a);

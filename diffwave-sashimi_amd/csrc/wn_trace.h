@@ -5,6 +5,7 @@
 #include <cstdlib>
 #include <vector>
 
+#include "host_util.h"
 #include "wavenet.h"
 
 namespace dws {
@@ -12,16 +13,11 @@ namespace dws {
 // DWS_WINO_TRACE=1 (tools only): stamp the phases of every wave of the first traced launch and print a summary
 template <typename F>
 static void wino_trace_launch(int nwg, int waves, WnLayerArgs a, hipStream_t s, F launch, const char* tag = "wino") {
-    unsigned long long* d = nullptr;
-    const size_t n = (size_t)nwg * waves * 32;
-    if (hipMalloc(&d, n * 8) != hipSuccess) return;
-    (void)hipMemsetAsync(d, 0, n * 8, s);
-    a.trace = d;
-    launch(a);
-    (void)hipStreamSynchronize(s);
-    std::vector<unsigned long long> h(n);
-    (void)hipMemcpy(h.data(), d, n * 8, hipMemcpyDeviceToHost);
-    (void)hipFree(d);
+    const std::vector<unsigned long long> h = capture_stamps((size_t)nwg * waves * 32, s, [&](unsigned long long* d) {
+        a.trace = d;
+        launch(a);
+    });
+    if (h.empty()) return;
     double ph[8] = {0};
     static double chunk[8][32];
     for (auto& c : chunk) for (double& v : c) v = 0;
