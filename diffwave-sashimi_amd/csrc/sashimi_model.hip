@@ -1665,6 +1665,29 @@ struct SashimiModel : dws_model, S4Workspace {
                 DWS_HIP(hipMemcpyAsync(dst, e.buf->p, e.n * 4, hipMemcpyDeviceToDevice, s));
                 return DWS_OK;
             }
+        // the conditioner as set_condition left it: "melc:<block prefix>" = that block's [Bm][H][L_stage],
+        // "mel_u0" / "mel_u1" = the upsampled mels of the block processed LAST (the scratch is shared)
+        if (t == "mel_u0" || t == "mel_u1") {
+            DWS_CHECK(melBm > 0, DWS_ERR_STATE, "tap '%s' before a set_condition with a mel", tap);
+            const int T0 = mel_upsampled_len(mel_T, d.mel_upsample[0]), T1 = mel_upsampled_len(T0, d.mel_upsample[1]);
+            const DevBuf& src = t == "mel_u0" ? mel_u0 : mel_u1;
+            const size_t n = (size_t)melBm * MB * (t == "mel_u0" ? T0 : T1);
+            DWS_CHECK(src.p && capacity >= (int64_t)n, DWS_ERR_INVALID, "tap '%s': %zu floats, capacity %lld", tap, n,
+                      (long long)capacity);
+            DWS_HIP(hipMemcpyAsync(dst, src.p, n * 4, hipMemcpyDeviceToDevice, s));
+            return DWS_OK;
+        }
+        if (t.rfind("melc:", 0) == 0) {
+            DWS_CHECK(melBm > 0, DWS_ERR_STATE, "tap '%s' before a set_condition with a mel", tap);
+            for (auto* l : all)
+                if (l->kind == L_BLOCK && l->prefix == t.substr(5)) {
+                    const size_t n = (size_t)melBm * l->H * l->L;
+                    DWS_CHECK(l->melc.p && capacity >= (int64_t)n, DWS_ERR_INVALID, "tap '%s': %zu floats, capacity %lld", tap, n,
+                              (long long)capacity);
+                    DWS_HIP(hipMemcpyAsync(dst, l->melc.p, n * 4, hipMemcpyDeviceToDevice, s));
+                    return DWS_OK;
+                }
+        }
         if (t.rfind("k:", 0) == 0) {  // S4 kernel of the block with this prefix: L * k, k = [2][H][L] (s4.py:796-805)
             if (dirty) DWS_TRY(commit(s));
             for (auto* l : all)

@@ -753,6 +753,17 @@ struct WaveNetModel : dws_model {
             DWS_TRY(scratch_out.ensure((size_t)B * Cout * L * 4));
             return final_stage(scratch_out.f(), dst, s);
         }
+        if (t == "melc" || t == "mel_u0" || t == "mel_u1") {   // the conditioner as set_condition left it
+            DWS_CHECK(melBm > 0, DWS_ERR_STATE, "tap '%s' before a set_condition with a mel", tap);
+            const int T0 = mel_upsampled_len(mel_T, d.mel_upsample[0]), T1 = mel_upsampled_len(T0, d.mel_upsample[1]);
+            // melc: every layer's [Bm][2C][L]; mel_u0 / mel_u1: the upsampled mels of the LAST layer (the scratch is shared)
+            const DevBuf& src = t == "melc" ? melc : t == "mel_u0" ? mel_u0 : mel_u1;
+            const size_t n = t == "melc" ? (size_t)NL * melBm * 2 * C * L : (size_t)melBm * MB * (t == "mel_u0" ? T0 : T1);
+            DWS_CHECK(src.p && capacity >= (int64_t)n, DWS_ERR_INVALID, "tap '%s': %zu floats, capacity %lld", tap, n,
+                      (long long)capacity);
+            DWS_HIP(hipMemcpyAsync(dst, src.p, n * 4, hipMemcpyDeviceToDevice, s));
+            return DWS_OK;
+        }
         // step-only terms: the per-clip rows of the last forward and the sampler's step table (parity / debugging)
         struct { const char* name; const DevBuf* buf; size_t n; } small[] = {
             {"emb", &emb, (size_t)B * Ein}, {"emb_mlp", &h2, (size_t)B * Eout},

@@ -308,8 +308,7 @@ class EngineModule(nn.Module):
             steps = diffusion_steps.detach().to(device=audio.device, dtype=torch.float32).reshape(-1).contiguous()
             if steps.numel() != B:
                 raise RuntimeError(f"diffusion_steps must hold B={B} entries, got {tuple(diffusion_steps.shape)}")
-            if audio.requires_grad:
-                mel_spec = self._expand_mel(mel_spec, B)
+            mel_spec = self._expand_mel(mel_spec, B)      # one mel shared by the batch: forward_train takes a mel per clip
             self._call_labels = self._label_list(labels, B) or None
             return _EngineTrainFn.apply(self, audio, steps, mel_spec, *(self.parameters() if train_call else ()))
         with torch.no_grad():

@@ -299,7 +299,11 @@ int dws_optim_step(dws_optim* o, int32_t count, float* const* params, const floa
  * [T, n_layers*C] / "tab_abt" (the sampler's step table).  Function-level taps of the last per-clip forward, both
  * models: "emb" [B, embed_dim_in] (`models/utils.py:20-27`), "emb_mlp" [B, embed_dim_out] (the two swish layers), "part_t"
  * (every block's fc_t row); SaShiMi also "nfin" [B, d_model, L] = the final TransposedLayerNorm, "out:<layer prefix>" the
- * output of a layer and "k:<block prefix>" its S4 kernel.  Both models:
+ * output of a layer and "k:<block prefix>" its S4 kernel.  The mel conditioner as the last dws_model_set_condition
+ * with a mel left it (Bm = that mel's batch, 1 or B; DWS_ERR_STATE while no mel is installed): WaveNet "melc"
+ * [n_layers, Bm, 2C, L] = the term every layer adds to its gate pre-activations, SaShiMi "melc:<block prefix>"
+ * [Bm, H, L_stage] of that block; both models "mel_u0" [Bm, mel_bands, T0] / "mel_u1" [Bm, mel_bands, T1] = the two
+ * upsampled mels (untruncated) of the layer / block processed last (the last one in execution order).  Both models:
  * "sampler_eps" = the network output of the sampler's last reverse step [B,Cout,L]. */
 int dws_model_read_tap(dws_model* m, const char* tap, float* dst, int64_t capacity, void* stream);
 
