@@ -120,6 +120,9 @@ _SIGS = {
                                                ctypes.c_uint32, ctypes.c_void_p]),
     "dws_mel_spectrogram": (ctypes.c_int, [c_f32p, ctypes.c_int64, ctypes.c_int64, c_f32p, c_f32p, ctypes.c_int32,
                                            ctypes.c_int32, ctypes.c_int32, ctypes.c_float, c_f32p, ctypes.c_void_p]),
+    "dws_mel_spectrogram_backward": (ctypes.c_int, [c_f32p, ctypes.c_int64, ctypes.c_int64, c_f32p, c_f32p, ctypes.c_int32,
+                                                    ctypes.c_int32, ctypes.c_int32, ctypes.c_float, c_f32p, c_f32p, c_f32p,
+                                                    ctypes.c_void_p]),
     "dws_gemm_bf16x6": (ctypes.c_int, [c_f32p] * 3 + [ctypes.c_int64] * 3 + [ctypes.c_void_p]),
     "dws_gemm_f16x3": (ctypes.c_int, [c_f32p] * 3 + [ctypes.c_int64] * 3 + [ctypes.c_float] * 2 + [ctypes.c_void_p]),
     "dws_profile_enable": (ctypes.c_int, [ctypes.c_char_p]),

@@ -54,7 +54,137 @@ __global__ __launch_bounds__(256) void mel_frame_kernel(const float* __restrict_
     }
 }
 
+// Adjoint, stage 1 of 2: one workgroup per (frame, clip).  Re/Im of the frame are recomputed exactly as
+// mel_frame_kernel computes them (same tables, same fmaf order, same wave reduction of the mel rows), then
+//   ds_m = g[m,f] / s_m  (0 where s_m <= clip),   dmag_k = sum_m W[m,k] ds_m  (ascending m),
+//   dRe_k = dmag_k Re_k / mag_k,  dIm_k = dmag_k Im_k / mag_k  (both 0 where mag_k == 0),
+//   ws[b,f,i] = w[i] sum_k (dRe_k cos(2 pi i k / N) + dIm_k sin(2 pi i k / N))  (ascending k).
+// Nothing is accumulated across workgroups here: the overlap-add is mel_gather_kernel's.
+__global__ __launch_bounds__(256) void mel_frame_backward_kernel(const float* __restrict__ audio, const float* __restrict__ window,
+                                                                 const float* __restrict__ basis, const float* __restrict__ dout,
+                                                                 float* __restrict__ ws, int T, int n_fft, int hop, int n_mels,
+                                                                 int n_frames, float clip) {
+    extern __shared__ float lds[];
+    float* frame = lds;                 // [n_fft]
+    float* ct = frame + n_fft;          // [n_fft]
+    float* st = ct + n_fft;             // [n_fft]
+    float* mag = st + n_fft;            // [n_fft/2 + 1]
+    const int f = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
+    const int half = n_fft / 2, nb = half + 1;
+    float* re = mag + nb;               // [nb] Re_k, then dRe_k
+    float* im = re + nb;                // [nb] Im_k, then dIm_k
+    float* ds = im + nb;                // [n_mels]
+    const float* a = audio + (size_t)b * T;
+    for (int i = tid; i < n_fft; i += 256) {
+        int j = f * hop + i - half;
+        if (j < 0) j = -j;
+        if (j >= T) j = 2 * (T - 1) - j;
+        frame[i] = a[j] * window[i];
+        float s, c;
+        sincospif(2.f * (float)i / (float)n_fft, &s, &c);
+        ct[i] = c;
+        st[i] = s;
+    }
+    __syncthreads();
+    const int mask = n_fft - 1;
+    for (int k = tid; k < nb; k += 256) {
+        float r = 0.f, q = 0.f;
+        int ph = 0;
+        for (int i = 0; i < n_fft; ++i) {
+            const float v = frame[i];
+            r = fmaf(v, ct[ph], r);
+            q = fmaf(v, st[ph], q);
+            ph = (ph + k) & mask;
+        }
+        re[k] = r;
+        im[k] = q;
+        mag[k] = sqrtf(r * r + q * q);
+    }
+    __syncthreads();
+    const int wave = tid >> 6, lane = tid & 63;
+    for (int m = wave; m < n_mels; m += 4) {
+        const float* w = basis + (size_t)m * nb;
+        float s = 0.f;
+        for (int k = lane; k < nb; k += 64) s = fmaf(w[k], mag[k], s);
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off);
+        // the clamp passes no gradient at or below `clip` (the tie s == clip counts as clamped)
+        if (lane == 0) ds[m] = s > clip ? dout[((size_t)b * n_mels + m) * n_frames + f] / s : 0.f;
+    }
+    __syncthreads();
+    for (int k = tid; k < nb; k += 256) {
+        float dmag = 0.f;
+        for (int m = 0; m < n_mels; ++m) dmag = fmaf(basis[(size_t)m * nb + k], ds[m], dmag);
+        const float mk = mag[k];
+        const float t = mk > 0.f ? dmag / mk : 0.f;      // |z| has no gradient at 0: a silent bin contributes exactly 0
+        re[k] = t * re[k];
+        im[k] = t * im[k];
+    }
+    __syncthreads();
+    float* o = ws + ((size_t)b * n_frames + f) * n_fft;
+    for (int i = tid; i < n_fft; i += 256) {
+        float acc = 0.f;
+        int ph = 0;
+        for (int k = 0; k < nb; ++k) {
+            acc = fmaf(re[k], ct[ph], acc);
+            acc = fmaf(im[k], st[ph], acc);
+            ph = (ph + i) & mask;
+        }
+        o[i] = window[i] * acc;
+    }
+}
+
+// Adjoint, stage 2 of 2: one thread per sample.  Sample j sits at padded position j + N/2 and, through the reflect
+// padding, at N/2 - j (j = 1 .. N/2) and at N/2 + 2(T-1) - j (j = T-1-N/2 .. T-2); every frame covering one of these
+// positions contributed ws[b,f,position - f hop].  Summed in a fixed order: the direct position, then the left
+// reflection, then the right one, each in ascending frame order.
+__device__ __forceinline__ float mel_gather_position(const float* __restrict__ wsb, int p, int n_fft, int hop, int n_frames, float acc) {
+    int lo = p - n_fft + 1;
+    lo = lo <= 0 ? 0 : (lo + hop - 1) / hop;
+    int hi = p / hop;
+    if (hi > n_frames - 1) hi = n_frames - 1;
+    for (int f = lo; f <= hi; ++f) acc += wsb[(size_t)f * n_fft + (p - f * hop)];
+    return acc;
+}
+
+__global__ __launch_bounds__(256) void mel_gather_kernel(const float* __restrict__ ws, float* __restrict__ daudio, int T,
+                                                         int n_fft, int hop, int n_frames) {
+    const int j = blockIdx.x * 256 + threadIdx.x, b = blockIdx.y;
+    if (j >= T) return;
+    const int half = n_fft / 2;
+    const float* wsb = ws + (size_t)b * n_frames * n_fft;
+    float acc = mel_gather_position(wsb, j + half, n_fft, hop, n_frames, 0.f);
+    if (j >= 1 && j <= half) acc = mel_gather_position(wsb, half - j, n_fft, hop, n_frames, acc);
+    if (j <= T - 2 && j >= T - 1 - half) acc = mel_gather_position(wsb, half + 2 * (T - 1) - j, n_fft, hop, n_frames, acc);
+    daudio[(size_t)b * T + j] = acc;
+}
+
 }  // namespace dws
+
+extern "C" int dws_mel_spectrogram_backward(const float* audio, int64_t B, int64_t T, const float* window,
+                                            const float* mel_basis, int32_t n_fft, int32_t hop, int32_t n_mels, float clip,
+                                            const float* dout, float* daudio, float* workspace, void* stream) {
+    using namespace dws;
+    DWS_CHECK(audio && window && mel_basis && dout && daudio, DWS_ERR_INVALID, "dws_mel_spectrogram_backward: null argument");
+    DWS_CHECK(workspace, DWS_ERR_INVALID, "dws_mel_spectrogram_backward: null workspace ([B][T/hop+1][n_fft] floats)");
+    DWS_CHECK(B > 0 && hop > 0 && n_mels > 0, DWS_ERR_INVALID, "dws_mel_spectrogram_backward: bad shape");
+    DWS_CHECK(n_fft >= 64 && n_fft <= 4096 && (n_fft & (n_fft - 1)) == 0, DWS_ERR_UNSUPPORTED,
+              "dws_mel_spectrogram_backward: filter_length %d (powers of two 64..4096 are built)", n_fft);
+    DWS_CHECK(T > n_fft / 2, DWS_ERR_INVALID,
+              "dws_mel_spectrogram_backward: reflect padding needs T > filter_length/2 (`stft.py:127-131`)");
+    const int n_frames = (int)(T / hop) + 1;
+    const size_t lds = ((size_t)3 * n_fft + 3 * (size_t)(n_fft / 2 + 1) + (size_t)n_mels) * 4;
+    DWS_CHECK(lds <= 160 * 1024, DWS_ERR_UNSUPPORTED, "dws_mel_spectrogram_backward: %d mel bands at filter_length %d need %zu "
+              "bytes of LDS (160 KiB per workgroup)", n_mels, n_fft, lds);
+    DWS_HIP(hipFuncSetAttribute((const void*)mel_frame_backward_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL(mel_frame_backward_kernel, dim3(n_frames, (unsigned)B), dim3(256), lds, (hipStream_t)stream, audio,
+                       window, mel_basis, dout, workspace, (int)T, n_fft, hop, n_mels, n_frames, clip);
+    DWS_HIP(hipGetLastError());
+    hipLaunchKernelGGL(mel_gather_kernel, dim3((unsigned)((T + 255) / 256), (unsigned)B), dim3(256), 0, (hipStream_t)stream,
+                       workspace, daudio, (int)T, n_fft, hop, n_frames);
+    DWS_HIP(hipGetLastError());
+    return DWS_OK;
+}
 
 extern "C" int dws_mel_spectrogram(const float* audio, int64_t B, int64_t T, const float* window, const float* mel_basis,
                                    int32_t n_fft, int32_t hop, int32_t n_mels, float clip, float* out, void* stream) {

@@ -268,7 +268,7 @@ def generate(rank, diffusion_cfg, model_cfg, dataset_cfg, ckpt_iter="max", n_sam
              written=None, precision=None, sampler="ddpm", steps=None, eta=0.0, known_name=None, keep=None,
              start_name=None, start_step=None, start_noise=True, resample_jump=None, resample_n=None, spacing=None,
              guide_name=None, guide_op=None, guide_clip=None, guide_factor=None, guide_scale=None, label=None,
-             cfg_scale=None, ema=None, clip_seeds=None, clips=None, num_ranks=None):
+             cfg_scale=None, ema=None, clip_seeds=None, clips=None, num_ranks=None, report_mel=None, mel_errors=None):
     """``generate.py:58-200``.  ``ckpt_iter`` may additionally be ``"init"``: seeded random weights
     (no checkpoint), for smoke runs without trained weights.  ``precision`` (not in the reference; CLI:
     ``+engine.precision=bf16x6|f16x3``): the engine's opt-in matrix arithmetic, see ``include/dws.h``.
@@ -295,7 +295,14 @@ def generate(rank, diffusion_cfg, model_cfg, dataset_cfg, ckpt_iter="max", n_sam
     its measurement is the wav low-passed and decimated by ``guide_factor``, default 2) and ``guide_scale`` (the
     guidance step, required: there is no default that fits every model and operator) runs Diffusion Posterior Sampling,
     ``sampling.sampling_guided`` -- a forward and a data-only backward of the network per step, every clip of the batch
-    guided by the same recording.
+    guided by the same recording.  ``guide_op=mel`` guides towards a mel spectrogram through ``sampling.mel_operator``
+    (the engine's log-mel and its HIP adjoint; ``guide_clip`` / ``guide_factor`` are refused): with ``guide_name`` the
+    measurement is the engine's mel of that wav -- 80 bands at ``dataset.sampling_rate``, ``filter_length`` /
+    ``hop_length`` / ``win_length`` / ``mel_fmin`` / ``mel_fmax`` from ``dataset`` where present, else 1024 / 256 / 1024,
+    0 and min(8000, sampling_rate / 2); without ``guide_name``, on a mel-conditional run (``mel_name``) only, it is the
+    conditioning mel itself, which keeps a vocoder on its mel.  ``report_mel=true`` (mel-conditional runs, any sampler)
+    prints per batch the mean absolute difference between the engine's log-mel of the generated clips and the
+    conditioning mel (over the frames of the condition), and appends it to ``mel_errors`` where that is a list.
 
     Class-conditional models (``model.n_classes = K``; not in the reference): ``label`` is a class index in 0..K (K = the
     null class), a list of them cycled over the samples, or ``all`` (= 0..K-1 in turn); the wav names get ``_c{label}``.
@@ -317,36 +324,45 @@ def generate(rank, diffusion_cfg, model_cfg, dataset_cfg, ckpt_iter="max", n_sam
     from .models import construct_model
     from .models.utils import check_n_classes
     from .sampling import (calc_diffusion_hyperparams, ddim_steps, declip_operator, logsnr_steps, lowpass_operator,
-                           program_evaluations, repaint_program, sampling, sampling_aligned, sampling_ddim, sampling_dpmpp,
-                           sampling_guided, spans_to_mask)
+                           mel_operator, program_evaluations, repaint_program, sampling, sampling_aligned, sampling_ddim,
+                           sampling_dpmpp, sampling_guided, spans_to_mask)
     from .sampling import clip_seeds as seeds_of_clips
     from scipy.io.wavfile import write as wavwrite
 
     if ckpt_smooth is not None or ckpt_iter == "init":     # checked here, before a model is built
         weights_key(None, ema, ckpt_smooth)
     plan = clip_plan(n_samples, n_samples if batch_size is None else batch_size, rank, num_ranks, clip_seeds, clips, seed)
-    if guide_name is None:
+    # guide_op=mel on a mel-conditional run needs no recording: the measurement is the conditioning mel itself
+    guided = guide_name is not None or (guide_op == "mel" and mel_name is not None)
+    guide_key = "generate.guide_name" if guide_name is not None else "generate.guide_op=mel"
+    if not guided:
         given = [k for k, v in (("guide_op", guide_op), ("guide_clip", guide_clip), ("guide_factor", guide_factor),
                                 ("guide_scale", guide_scale)) if v is not None]
         if given:
             raise ValueError(f"generate.{given[0]} needs generate.guide_name (the degraded recording)")
     else:
-        if guide_op not in ("declip", "lowpass"):
-            raise ValueError(f"generate.guide_op={guide_op!r}: expected declip or lowpass")
+        if guide_op not in ("declip", "lowpass", "mel"):
+            raise ValueError(f"generate.guide_op={guide_op!r}: expected declip, lowpass or mel")
         if guide_scale is None:
-            raise ValueError("generate.guide_name needs generate.guide_scale (the guidance step; no default is chosen: it "
+            raise ValueError(f"{guide_key} needs generate.guide_scale (the guidance step; no default is chosen: it "
                              "depends on the model and the operator)")
         if float(guide_scale) == 0.0:
-            raise ValueError("generate.guide_scale=0 is the unguided run: drop generate.guide_name")
-        if guide_op == "declip" and guide_factor is not None:
+            raise ValueError(f"generate.guide_scale=0 is the unguided run: drop {guide_key}")
+        if guide_op != "lowpass" and guide_factor is not None:
             raise ValueError("generate.guide_factor belongs to generate.guide_op=lowpass")
-        if guide_op == "lowpass" and guide_clip is not None:
+        if guide_op != "declip" and guide_clip is not None:
             raise ValueError("generate.guide_clip belongs to generate.guide_op=declip")
         if (sampler or "ddpm") not in ("ddpm", "ddim"):
-            raise ValueError(f"generate.guide_name with generate.sampler={sampler}: guided runs are built for ddpm and ddim")
+            raise ValueError(f"{guide_key} with generate.sampler={sampler}: guided runs are built for ddpm and ddim")
         if known_name is not None or start_name is not None or resample_jump is not None:
-            raise ValueError("generate.guide_name does not combine with the editing keys (known_name, start_name, "
+            raise ValueError(f"{guide_key} does not combine with the editing keys (known_name, start_name, "
                              "resample_jump)")
+    if report_mel is not None:
+        if not isinstance(report_mel, bool):
+            raise ValueError(f"generate.report_mel={report_mel!r}: expected true or false")
+        if report_mel and mel_name is None:
+            raise ValueError("generate.report_mel needs a mel-conditional run (generate.mel_name: the error is measured "
+                             "against the conditioning mel)")
 
     n_classes = check_n_classes(model_cfg.get("n_classes"))
     labels_of = None        # the class of every sample, cycled
@@ -368,8 +384,8 @@ def generate(rank, diffusion_cfg, model_cfg, dataset_cfg, ckpt_iter="max", n_sam
             raise ValueError("generate.cfg_scale needs generate.label (classifier-free guidance steers towards a class)")
         if isinstance(cfg_scale, (bool, str)) or not np.isfinite(float(cfg_scale)):
             raise ValueError(f"generate.cfg_scale={cfg_scale!r}: expected a finite number")
-        if guide_name is not None:
-            raise ValueError("generate.cfg_scale does not combine with generate.guide_name (guided runs take "
+        if guided:
+            raise ValueError(f"generate.cfg_scale does not combine with {guide_key} (guided runs take "
                              "generate.label alone)")
         if known_name is not None or start_name is not None or resample_jump is not None:
             raise ValueError("generate.cfg_scale does not combine with the editing keys (known_name, start_name, "
@@ -484,10 +500,24 @@ def generate(rank, diffusion_cfg, model_cfg, dataset_cfg, ckpt_iter="max", n_sam
         edit["start_noise"] = None if start_noise else False
     if resample_jump is not None:
         edit["resample"] = (resample_jump, resample_n)
+    mel_of = None       # log-mel of a [B, 1, L] batch on the engine, cut to the frames of the conditioning mel
+    if guide_op == "mel" or report_mel:
+        sr = dataset_cfg["sampling_rate"]
+        stft_kw = dict(filter_length=1024, hop_length=256, win_length=1024, mel_fmin=0.0, mel_fmax=min(8000.0, sr / 2.0))
+        stft_kw.update({k: dataset_cfg[k] for k in stft_kw if k in dataset_cfg})
+        mel_A = mel_operator(sampling_rate=sr, n_mel_channels=80, **stft_kw)
+        # a run of mel frames x hop samples has one frame more than its conditioning mel: the last one is not compared
+        mel_of = mel_A if mel is None else (lambda x: mel_A(x)[..., :mel.shape[-1]])
     guide = None
-    if guide_name is not None:
+    if guide_name is None and guided:
+        guide = dict(measurement=mel.detach().to(torch.float32).expand(batch_size, -1, -1), operator=mel_of,
+                     scale=float(guide_scale))
+    elif guided:
         rec = _load_clip(dataset_cfg, guide_name, audio_length, mel is not None).expand(batch_size, 1, audio_length)
-        if guide_op == "declip":
+        if guide_op == "mel":
+            guide = dict(measurement=mel_of(rec[:1].cuda()).expand(batch_size, -1, -1), operator=mel_of,
+                         scale=float(guide_scale))
+        elif guide_op == "declip":
             op = declip_operator(float(rec.abs().max()) if guide_clip is None else guide_clip)
             guide = dict(measurement=rec, operator=op, scale=float(guide_scale))
         else:
@@ -526,6 +556,11 @@ def generate(rank, diffusion_cfg, model_cfg, dataset_cfg, ckpt_iter="max", n_sam
             out.append(sampling_dpmpp(net, size, dh_train, steps, condition=mel, spacing=spacing, seed=s, **edit))
         else:
             out.append(sampling(net, size, dh, condition=mel, seed=s, **edit))
+        if report_mel:
+            err = float((mel_of(out[-1]) - mel).abs().mean())
+            print(f"batch {i} mel error: mean |log-mel(generated) - condition| = {err:.4f}")
+            if mel_errors is not None:
+                mel_errors.append(err)
     generated_audio = torch.cat(out, dim=0) if out else torch.empty(0, 1, audio_length, device="cuda")
     torch.cuda.synchronize()
     print(f"generated {len(numbers)} samples shape {tuple(generated_audio.shape)} at iteration {ckpt_iter} in "

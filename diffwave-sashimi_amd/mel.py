@@ -56,6 +56,57 @@ def padded_hann(win_length, filter_length):
     return np.pad(w, (lpad, filter_length - win_length - lpad)).astype(np.float32)
 
 
+MEL_CLIP = 1e-5             # `stft.py:222-224`: log(clamp(., 1e-5))
+
+
+def _mel_forward(y, win, basis, n_fft, hop, n_mels):
+    B, T = y.shape
+    out = torch.empty(B, n_mels, T // hop + 1, device=y.device, dtype=torch.float32)
+    with torch.cuda.device(y.device):
+        _lib.check(_lib.load().dws_mel_spectrogram(y.data_ptr(), B, T, win.data_ptr(), basis.data_ptr(), n_fft, hop, n_mels,
+                                                   MEL_CLIP, out.data_ptr(), _lib.current_stream()))
+    return out
+
+
+class _MelBackward(torch.autograd.Function):
+    """``dws_mel_spectrogram_backward`` as a node of its own, so that differentiating it (a second-order request) is
+    an error with a name instead of a silent zero."""
+
+    @staticmethod
+    def forward(ctx, g, y, win, basis, n_fft, hop, n_mels):
+        B, T = y.shape
+        g = g.to(torch.float32).contiguous()
+        dy = torch.empty_like(y)
+        ws = torch.empty(B, T // hop + 1, n_fft, device=y.device, dtype=torch.float32)      # the engine allocates nothing
+        with torch.cuda.device(y.device):
+            _lib.check(_lib.load().dws_mel_spectrogram_backward(y.data_ptr(), B, T, win.data_ptr(), basis.data_ptr(), n_fft,
+                                                                hop, n_mels, MEL_CLIP, g.data_ptr(), dy.data_ptr(),
+                                                                ws.data_ptr(), _lib.current_stream()))
+        return dy
+
+    @staticmethod
+    def backward(ctx, *_):
+        raise RuntimeError("mel_spectrogram: the second derivative is not built (dws_mel_spectrogram_backward is a "
+                           "first-order adjoint; there is no double backward)")
+
+
+class _MelSpectrogram(torch.autograd.Function):
+    """log-mel of ``y`` [B, T] (cuda, float32, contiguous): ``dws_mel_spectrogram`` forwards,
+    ``dws_mel_spectrogram_backward`` (include/dws.h: zero gradient where a DFT magnitude is exactly 0, where torch
+    autograd through sqrt gives NaN) backwards."""
+
+    @staticmethod
+    def forward(ctx, y, win, basis, n_fft, hop, n_mels):
+        ctx.save_for_backward(y, win, basis)
+        ctx.dims = (n_fft, hop, n_mels)
+        return _mel_forward(y, win, basis, n_fft, hop, n_mels)
+
+    @staticmethod
+    def backward(ctx, g):
+        y, win, basis = ctx.saved_tensors
+        return _MelBackward.apply(g, y, win, basis, *ctx.dims), None, None, None, None, None
+
+
 class TacotronSTFT:
     """``dataloaders/stft.py:196-244``; ``mel_spectrogram(y)`` runs on the GPU ``y`` lives on."""
 
@@ -68,21 +119,33 @@ class TacotronSTFT:
         self.window = torch.from_numpy(padded_hann(win_length, filter_length))
         self._dev = {}
 
+    def _tables(self, device):
+        if device not in self._dev:
+            self._dev[device] = (self.window.to(device), self.mel_basis.to(device))
+        return self._dev[device]
+
+    def differentiable_mel(self, y):
+        """``y`` [B, T] (cuda, any range) -> log-mel [B, n_mel_channels, T // hop + 1] through ``_MelSpectrogram``:
+        differentiable in ``y`` where it requires grad, the plain kernel call (the same bits) where it does not."""
+        if y.device.type != "cuda":
+            raise RuntimeError("libdws runs on the GPU only: move the waveform to cuda (there is no CPU fallback)")
+        if y.dim() != 2:
+            raise ValueError(f"mel_spectrogram: the waveform has shape {tuple(y.shape)}, expected [B, T]")
+        win, basis = self._tables(y.device)
+        dims = (self.filter_length, self.hop_length, self.n_mel_channels)
+        if y.requires_grad and torch.is_grad_enabled():
+            return _MelSpectrogram.apply(y.to(torch.float32).contiguous(), win, basis, *dims)
+        return _mel_forward(y.detach().to(torch.float32).contiguous(), win, basis, *dims)
+
     def mel_spectrogram(self, y):
-        """``y`` [B, T] in [-1, 1] (cuda) -> log-mel [B, n_mel_channels, T // hop + 1]."""
+        """``y`` [B, T] in [-1, 1] (cuda) -> log-mel [B, n_mel_channels, T // hop + 1].  Where ``y`` requires grad the
+        result carries a ``grad_fn`` (the reference detaches; the adjoint is ``dws_mel_spectrogram_backward``: first
+        order only, and a zero gradient where torch autograd through ``sqrt(0)`` would give NaN); otherwise this is the
+        plain kernel call."""
         if y.device.type != "cuda":
             raise RuntimeError("libdws runs on the GPU only: move the waveform to cuda (there is no CPU fallback)")
         assert float(y.min()) >= -1 and float(y.max()) <= 1            # `stft.py:233-234`
-        y = y.detach().to(torch.float32).contiguous()
-        B, T = y.shape
-        if y.device not in self._dev:
-            self._dev[y.device] = (self.window.to(y.device), self.mel_basis.to(y.device))
-        win, basis = self._dev[y.device]
-        out = torch.empty(B, self.n_mel_channels, T // self.hop_length + 1, device=y.device, dtype=torch.float32)
-        _lib.check(_lib.load().dws_mel_spectrogram(y.data_ptr(), B, T, win.data_ptr(), basis.data_ptr(),
-                                                   self.filter_length, self.hop_length, self.n_mel_channels, 1e-5,
-                                                   out.data_ptr(), _lib.current_stream()))
-        return out
+        return self.differentiable_mel(y)
 
 
 def load_wav_to_torch(full_path):

@@ -702,6 +702,34 @@ def lowpass_operator(factor, taps=33):
     return A
 
 
+def mel_operator(stft=None, **stft_kwargs):
+    """Measurement operator of a mel spectrogram: ``A(x) = log-mel(x)`` on the engine (``dws_mel_spectrogram``, adjoint
+    ``dws_mel_spectrogram_backward``), [B, 1, L] or [B, L] -> [B, n_mel_channels, L // hop_length + 1].  ``stft`` is a
+    ``mel.TacotronSTFT``, or give the keywords it takes (``filter_length``, ``hop_length``, ``win_length``,
+    ``n_mel_channels``, ``sampling_rate``, ``mel_fmin``, ``mel_fmax``).  Unlike ``TacotronSTFT.mel_spectrogram`` there is
+    no [-1, 1] assertion: x0 estimates leave that range, and the check would be a host synchronisation per step.  GPU
+    tensors only (no CPU fallback).  Where a DFT magnitude is exactly zero its gradient is taken as 0 (torch autograd
+    through a restated transform returns NaN there); first order only."""
+    from .mel import TacotronSTFT
+    if stft is None:
+        stft = TacotronSTFT(**stft_kwargs)
+    elif stft_kwargs:
+        raise ValueError(f"mel_operator: give a TacotronSTFT or its keywords, not both (got {sorted(stft_kwargs)} too)")
+    elif not isinstance(stft, TacotronSTFT):
+        raise ValueError(f"mel_operator: stft = {type(stft).__name__} (needs a mel.TacotronSTFT or its keywords)")
+
+    def A(x):
+        if x.dim() == 3:
+            if x.shape[1] != 1:
+                raise ValueError(f"mel_operator: the waveform has shape {tuple(x.shape)}, expected [B, 1, L] or [B, L]")
+            x = x[:, 0]
+        elif x.dim() != 2:
+            raise ValueError(f"mel_operator: the waveform has shape {tuple(x.shape)}, expected [B, 1, L] or [B, L]")
+        return stft.differentiable_mel(x)
+    A.stft = stft
+    return A
+
+
 def guided_coefficients(dh, sampler, steps=None, eta=0.0):
     """Tables of ``sampling_guided``: (net_steps float32 [S], float32 [6][S] = k1, k2, a, b, c, 0/1) with the x0
     estimate ``u = (x - k1 eps) / k2`` and the unguided update written for both samplers as
@@ -737,7 +765,9 @@ def sampling_guided(net, size, diffusion_hyperparams, *, measurement, operator, 
                     **unsupported):
     """Restoration with a trained model by Diffusion Posterior Sampling (Chung et al., ICLR 2023): a reverse run whose
     every step is pulled towards a degraded recording ``measurement = operator(x0)``.  ``operator`` is any differentiable
-    torch callable ``A(x0) -> measurement-shaped tensor`` (``declip_operator``, ``lowpass_operator``).  Per step s
+    torch callable ``A(x0) -> measurement-shaped tensor`` (``declip_operator``, ``lowpass_operator``, or ``mel_operator``:
+    the engine's own log-mel with its HIP adjoint, for a measurement that is a mel spectrogram -- e.g. the conditioning
+    mel of a vocoder run; engine models / cuda tensors only).  Per step s
     (S-1 .. 0; tables: ``guided_coefficients``)::
 
         eps = net((x, t_s))                       # differentiable call, x.requires_grad

@@ -537,6 +537,32 @@ int dws_philox_normal_clips(float* x, int64_t B, int64_t n_per_clip, const uint6
 int dws_mel_spectrogram(const float* audio, int64_t B, int64_t T, const float* window, const float* mel_basis,
                         int32_t n_fft, int32_t hop, int32_t n_mels, float clip, float* out, void* stream);
 
+/* The adjoint of dws_mel_spectrogram (not in the reference, whose TacotronSTFT detaches its input): daudio [B][T]
+ * (overwritten) = d<dout, out>/d audio for a cotangent dout [B][n_mels][T/hop + 1].  With N = n_fft, w the window, W the
+ * filterbank, rho the reflect map of the forward (j < 0 -> -j, j >= T -> 2(T-1) - j), the forward is
+ *     frame_f[i] = w[i] x[rho(f hop + i - N/2)]
+ *     Re_k = sum_i frame_f[i] cos(2 pi i k / N),   Im_k = sum_i frame_f[i] sin(2 pi i k / N),   k = 0 .. N/2
+ *     mag_k = sqrt(Re_k^2 + Im_k^2),   s_m = sum_k W[m,k] mag_k,   out[m,f] = log(max(s_m, clip))
+ * and the adjoint computed here
+ *     ds_m   = dout[m,f] / s_m  if s_m > clip  else 0
+ *     dmag_k = sum_m W[m,k] ds_m
+ *     dRe_k  = dmag_k Re_k / mag_k,   dIm_k = dmag_k Im_k / mag_k          (both 0 where mag_k == 0)
+ *     dframe_f[i] = sum_k (dRe_k cos(2 pi i k / N) + dIm_k sin(2 pi i k / N))
+ *     daudio[j] = sum over all (f, i) with rho(f hop + i - N/2) = j  of  w[i] dframe_f[i].
+ * Zero magnitude: mag_k == 0 contributes exactly 0 -- a deliberate difference from torch autograd, which returns NaN
+ * there (sqrt has no gradient at 0); a silent frame gives a zero gradient, not NaN.  Clamp tie: s_m == clip counts as
+ * clamped (gradient 0).  Re, Im and s_m are recomputed with the forward's own arithmetic, so the clamp decision is the
+ * forward's.  The overlap-add is a gather in a fixed order (per sample: its direct position, its left reflection, its
+ * right reflection, each in ascending frame order) with no atomics: the result is bitwise reproducible, and clip b's
+ * gradient does not depend on B or on b.
+ * workspace: DEVICE [B][T/hop + 1][n_fft] floats owned by the caller (overwritten; the library allocates nothing per
+ * call).  Same limits and error codes as dws_mel_spectrogram (null pointer, workspace included, or B, hop, n_mels < 1 or
+ * T <= n_fft/2: DWS_ERR_INVALID; n_fft not a power of two in 64..4096: DWS_ERR_UNSUPPORTED), and DWS_ERR_UNSUPPORTED
+ * where 3 n_fft + 3 (n_fft/2 + 1) + n_mels floats exceed the 160 KiB of LDS of a workgroup. */
+int dws_mel_spectrogram_backward(const float* audio, int64_t B, int64_t T, const float* window, const float* mel_basis,
+                                 int32_t n_fft, int32_t hop, int32_t n_mels, float clip, const float* dout, float* daudio,
+                                 float* workspace, void* stream);
+
 /* The arithmetic of precision="bf16x6" alone (accuracy tests; not a tuned GEMM): C[M][N] = A[M][K] . B[K][N], row-major
  * fp32 device tensors, every operand split into three bf16 terms in registers, six bf16 MFMA products per term pair
  * accumulated in fp32 -- exactly what the bf16x6 layer kernels execute per k-block.  M, N multiples of 32, K of 16. */
