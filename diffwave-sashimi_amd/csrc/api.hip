@@ -81,6 +81,12 @@ int dws_model::set_labels(const int32_t* labels, int64_t nB, hipStream_t s) {
     return DWS_OK;
 }
 
+// Backbones without per-clip lengths (SaShiMi: its stage buffers need a mask in front of every S4 convolution).
+int dws_model::set_lengths(const int32_t* lengths, const int32_t*, int64_t, hipStream_t) {
+    if (!lengths) return DWS_OK;
+    return dws::set_error(DWS_ERR_UNSUPPORTED, "per-clip lengths (dws_model_set_lengths) are built for the WaveNet backbone only");
+}
+
 // The grid of a per-clip launch has one row per clip: at most 65535 clips.
 int dws_model::set_clip_seeds(const uint64_t* seeds, int64_t nB, hipStream_t s) {
     if (!seeds) {
@@ -345,10 +351,16 @@ int dws_model_set_labels(dws_model* m, const int32_t* labels, int64_t B, void* s
     return m->set_labels(labels, B, (hipStream_t)stream);
 }
 
+int dws_model_set_lengths(dws_model* m, const int32_t* lengths, const int32_t* mel_frames, int64_t B, void* stream) {
+    DWS_CHECK(m, DWS_ERR_INVALID, "null model");
+    return m->set_lengths(lengths, mel_frames, B, (hipStream_t)stream);
+}
+
 int dws_sampler_set_cfg(dws_model* m, int32_t on, float scale) {
     DWS_CHECK(m, DWS_ERR_INVALID, "null model");
     DWS_CHECK(!on || (scale == scale && scale - scale == 0.f), DWS_ERR_INVALID, "dws_sampler_set_cfg: scale = %g is not finite",
               (double)scale);
+    DWS_CHECK(!on || !m->ragged(), DWS_ERR_UNSUPPORTED, "classifier-free guidance with per-clip lengths (dws_model_set_lengths) is not built");
     m->smp.cfg_on = on != 0;
     m->smp.cfg_scale = on ? scale : 0.f;
     return DWS_OK;

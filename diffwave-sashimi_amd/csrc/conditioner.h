@@ -4,8 +4,9 @@
 #include "model.h"
 
 namespace dws {
+// valid (device int32 [Bm], nullable) / vmul: clip bm reads only its first valid[bm] * vmul input columns (ragged batches)
 int launch_mel_upsample(const float* in, const float* W, const float* bias, float* out, int Bm, int M, int Tin,
-                        int Tout, int s, float slope, hipStream_t st);
+                        int Tout, int s, float slope, hipStream_t st, const int32_t* valid = nullptr, int vmul = 1);
 int launch_conv1x1_trunc(const float* in, const float* W, const float* bias, float* out, int Bm, int K, int O,
                          int Lin, int L, hipStream_t st);
 // Adjoint of one upsampler (training).  `out` = the layer's activation [B][M][Tout]; `dout` = gradient w.r.t. it with

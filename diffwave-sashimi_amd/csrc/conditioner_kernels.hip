@@ -7,23 +7,32 @@
 
 namespace dws {
 
+// Ragged batches (dws_model_set_lengths): clip bm reads only its first valid[bm] * vmul input columns (the clip's own mel
+// frames, or what the first upsampler makes of them); the others count as zero whatever they hold -- the sums then run over
+// exactly the terms they have when the clip's mel is conditioned alone.  valid == null: all Tin columns.
+__device__ __forceinline__ int mel_valid_cols(const int32_t* __restrict__ valid, int bm, int vmul, int Tin) {
+    if (!valid) return Tin;
+    return (int)min((int64_t)Tin, (int64_t)max(valid[bm], 0) * vmul);
+}
+
 // ConvTranspose2d(1,1,(3,2s), stride=(1,s), padding=(1,s/2)) + leaky_relu(slope):
 //   out[m, x] = bias + sum_{ky<3} sum_{ix} in[m + 1 - ky, ix] * W[ky, x + s/2 - ix*s]
 // with 0 <= x + s/2 - ix*s < 2s  (SURVEY.md appendix B).  Output width
 // (Tin-1)*s - 2*(s/2) + 2s.
 __global__ void mel_upsample_kernel(const float* __restrict__ in, const float* __restrict__ W,
                                     const float* __restrict__ bias, float* __restrict__ out, int M, int Tin,
-                                    int Tout, int s, float slope) {
+                                    int Tout, int s, float slope, const int32_t* __restrict__ valid, int vmul) {
     const int bm = blockIdx.z, m = blockIdx.y;
     const float* inb = in + (size_t)bm * M * Tin;
     const int pad = s / 2, kw = 2 * s;
+    const int Tv = mel_valid_cols(valid, bm, vmul, Tin);   // ragged batches: columns >= Tv of this clip count as zero
     for (int x = blockIdx.x * blockDim.x + threadIdx.x; x < Tout; x += gridDim.x * blockDim.x) {
         float acc = bias[0];
         // ix*s <= x + pad  and  ix*s > x + pad - 2s
         const int hi = (x + pad) / s;
         for (int ix = hi; ix >= 0 && ix > hi - 3; --ix) {
             const int kx = x + pad - ix * s;
-            if (kx < 0 || kx >= kw || ix >= Tin) continue;
+            if (kx < 0 || kx >= kw || ix >= Tv) continue;
 #pragma unroll
             for (int ky = 0; ky < 3; ++ky) {
                 const int iy = m + 1 - ky;
@@ -42,8 +51,10 @@ __global__ void mel_upsample_kernel(const float* __restrict__ in, const float* _
 // bit-identical results.
 __global__ __launch_bounds__(256) void mel_upsample_pow2_kernel(const float* __restrict__ in, const float* __restrict__ W,
                                                                 const float* __restrict__ bias, float* __restrict__ out,
-                                                                int M, int Tin, int Tout, int log2s, float slope) {
+                                                                int M, int Tin, int Tout, int log2s, float slope,
+                                                                const int32_t* __restrict__ valid, int vmul) {
     const int bm = blockIdx.z, m = blockIdx.y, s = 1 << log2s, pad = s >> 1, kw = 2 * s;
+    const int Tv = mel_valid_cols(valid, bm, vmul, Tin);
     const float* inb = in + (size_t)bm * M * Tin;
     const float b0 = bias[0];
     // rows m+1, m, m-1 (ky = 0, 1, 2); a row outside [0, M) contributes nothing
@@ -58,13 +69,13 @@ __global__ __launch_bounds__(256) void mel_upsample_pow2_kernel(const float* __r
         if (x >= Tout) break;
         const int xp = x + pad, ixa = xp >> log2s, kxa = xp & (s - 1);
         float acc = b0;
-        if (ixa < Tin) {
+        if (ixa < Tv) {
             if (r0) acc = fmaf(i0[ixa], W[kxa], acc);
             acc = fmaf(i1[ixa], W[kw + kxa], acc);
             if (r2) acc = fmaf(i2[ixa], W[2 * kw + kxa], acc);
         }
         const int ixb = ixa - 1, kxb = kxa + s;
-        if (ixb >= 0 && ixb < Tin) {
+        if (ixb >= 0 && ixb < Tv) {
             if (r0) acc = fmaf(i0[ixb], W[kxb], acc);
             acc = fmaf(i1[ixb], W[kw + kxb], acc);
             if (r2) acc = fmaf(i2[ixb], W[2 * kw + kxb], acc);
@@ -74,17 +85,19 @@ __global__ __launch_bounds__(256) void mel_upsample_pow2_kernel(const float* __r
 }
 
 int launch_mel_upsample(const float* in, const float* W, const float* bias, float* out, int Bm, int M, int Tin,
-                        int Tout, int s, float slope, hipStream_t st) {
+                        int Tout, int s, float slope, hipStream_t st, const int32_t* valid, int vmul) {
     static const bool generic = getenv("DWS_MEL_UPSAMPLE_GENERIC") != nullptr;
     if (!generic && s >= 2 && (s & (s - 1)) == 0) {
         int log2s = 0;
         while ((1 << log2s) < s) ++log2s;
         dim3 grid(ceil_div(Tout, 1024), M, Bm);
-        hipLaunchKernelGGL(mel_upsample_pow2_kernel, grid, dim3(256), 0, st, in, W, bias, out, M, Tin, Tout, log2s, slope);
+        hipLaunchKernelGGL(mel_upsample_pow2_kernel, grid, dim3(256), 0, st, in, W, bias, out, M, Tin, Tout, log2s, slope,
+                           valid, vmul);
         return DWS_OK;
     }
     dim3 grid(min(ceil_div(Tout, 256), 1024), M, Bm);
-    hipLaunchKernelGGL(mel_upsample_kernel, grid, dim3(256), 0, st, in, W, bias, out, M, Tin, Tout, s, slope);
+    hipLaunchKernelGGL(mel_upsample_kernel, grid, dim3(256), 0, st, in, W, bias, out, M, Tin, Tout, s, slope, valid,
+                       vmul);
     return DWS_OK;
 }
 

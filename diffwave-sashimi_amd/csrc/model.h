@@ -59,6 +59,11 @@ struct PrepBatch {
 };
 
 int launch_iota_f32(float* out, int n, hipStream_t s);   // wavenet_kernels.hip
+// ragged batches (wavenet_kernels.hip): x[b, c, len_b .. min(L, len_b + reach)) = v for every row (b, c) of x [B, C, L],
+// len_b = lengths[b] (device), stores only; reach < 0: the whole tail.  v = 0.0f, or (pt given) -pt[b * pt_bstride + c
+// (+ *step_idx * pt_tstride)]: the value that makes the next layer's h = x + fc_t(e) zero.
+int launch_wn_mask_tail(float* x, const int32_t* lengths, int B, int C, int L, int reach, const float* pt, int pt_bstride,
+                        const int* step_idx, int pt_tstride, hipStream_t s);
 // class conditioning (wavenet_kernels.hip): out[r][:] = in[r / rep][:] + table[lab ? lab[r % nlab] : K][:], one fp32 add per
 // element (in place when rep == 1 and out == in); and its adjoint dtable[c][:] = sum over b with lab[b] == c of de[b][:], in
 // ascending b, rows of absent classes exactly zero
@@ -145,6 +150,17 @@ struct dws_model {
     int set_classes(int32_t K);
     int set_labels(const int32_t* labels, int64_t nB, hipStream_t s);
     int reset_labels();                   // after a prepare to another shape: the null class for every clip (blocking)
+
+    // ---- ragged batches (dws_model_set_lengths): per-clip lengths and mel frame counts of the prepared batch in one
+    // model-owned device table, int32 [2][B] = lengths, frames.  The kernels that seal the padding read it from device
+    // memory, so a new table at the same shape replays a captured step.
+    dws::DevBuf lengths_dev;
+    std::vector<int32_t> lengths_host, frames_host;   // what lengths_dev holds (empty: off)
+    dws::StagingRing length_ring{4};      // pinned staging of the upload
+    bool ragged() const { return !lengths_host.empty(); }
+    const int32_t* lengths_ptr() const { return static_cast<const int32_t*>(lengths_dev.p); }
+    const int32_t* frames_ptr() const { return lengths_ptr() + B; }
+    virtual int set_lengths(const int32_t* lengths, const int32_t* mel_frames, int64_t nB, hipStream_t s);
 
     // ---- staged gradient hand-over (data-parallel overlap, dws_model_set_grad_sinks): the host names a destination and a
     // GROUP (its all-reduce bucket) per parameter; backward() copies a group's gradients to their destinations (one launch)

@@ -21,6 +21,7 @@ struct SamplerState {
     const void* g_x = nullptr;
     const void* g_noise = nullptr;
     uint64_t g_seed = 0;
+    bool g_ragged = false;           // captured with per-clip lengths on (the step then holds the sealing launches)
     // ---- few-step sampler (dws_sampler_run_schedule): tables, state, x and graph of its own -- the two entry points never
     // replay each other's graph.  Its graph updates sch_x in place and reads the seed from sch_state, so neither the
     // caller's x nor the seed is baked in.
@@ -40,8 +41,9 @@ struct SamplerState {
         const void* prog = nullptr;
         const void* hist = nullptr;                      // the multistep kind's history buffer (null for the others)
         const void* clip_seeds = nullptr;                // the per-clip seed table (null for a scalar-seed step)
+        const void* lengths = nullptr;                   // the per-clip length table (null: lengths off)
         bool operator==(const SchKey& o) const {
-            return B == o.B && L == o.L && S == o.S && kind == o.kind && vec == o.vec && tables == o.tables &&
+            return lengths == o.lengths && B == o.B && L == o.L && S == o.S && kind == o.kind && vec == o.vec && tables == o.tables &&
                    noise == o.noise && eps == o.eps && x == o.x && state == o.state && table_gen == o.table_gen &&
                    edit == o.edit && known == o.known && mask == o.mask && known_noise == o.known_noise && V == o.V &&
                    prog == o.prog && hist == o.hist && clip_seeds == o.clip_seeds;
@@ -56,7 +58,9 @@ struct SamplerState {
     struct SchGraph {
         hipGraphExec_t exec = nullptr;
         SchKey key{};
-    } sch_graphs[SCH_GRAPHS][2];
+    } sch_graphs[SCH_GRAPHS][4];     // [form of seed + 2 * per-clip lengths on]: a step with lengths on holds the launches
+                                     // that seal the padding (it reads the length table from device memory: a new table
+                                     // replays it), so lengths on / off alternate without a new capture as the rest does
     // editing: the known clip and the mask are copied into model-owned buffers before the replays, like x into sch_x.
     DevBuf sch_edit;                      // [2][S] q1, q2 of sampling.edit_coefficients
     std::vector<float> sch_host_edit;     // host copy of what is resident

@@ -535,6 +535,13 @@ static int capture_step(dws_model* m, hipStream_t cs, hipGraphExec_t& exec, bool
     return DWS_OK;
 }
 
+// Per-clip lengths (dws_model_set_lengths): behind the last step of a run the returned state holds exactly 0.0f past
+// every clip's own end.  The steps need nothing: the update is pointwise and the network seals its own padding.
+static int seal_result(dws_model* m, float* x, hipStream_t s) {
+    if (!m->ragged()) return DWS_OK;
+    return launch_wn_mask_tail(x, m->lengths_ptr(), (int)m->B, m->d.out_channels, (int)m->L, -1, nullptr, 0, nullptr, 0, s);
+}
+
 // c1 = (1 - alpha) / sqrt(1 - alpha_bar), c2 = sqrt(alpha), sigma: [3][T]
 static std::vector<float> ddpm_table(const float* alpha, const float* alpha_bar, const float* sigma, int T) {
     std::vector<float> h(3 * (size_t)T);
@@ -586,6 +593,7 @@ static int run_steps(dws_model* m, float* x, int T, int t_start, int n_steps, co
     if (!use_graph) {
         hipLaunchKernelGGL(smp_set_step_kernel, dim3(1), dim3(1), 0, s, t_dev, t_start);
         for (int i = 0; i < n_steps; ++i) DWS_TRY(one_step(m, x, noise, seed, T, s));
+        DWS_TRY(seal_result(m, x, s));
         DWS_HIP(hipGetLastError());
         return DWS_OK;
     }
@@ -593,11 +601,13 @@ static int run_steps(dws_model* m, float* x, int T, int t_start, int n_steps, co
     DWS_TRY(engine_after_caller(m, s, &cs));
     hipLaunchKernelGGL(smp_set_step_kernel, dim3(1), dim3(1), 0, cs, t_dev, t_start);
     const bool reuse = m->smp.graph && m->smp.g_B == m->B && m->smp.g_L == m->L && m->smp.g_T == T && m->smp.g_x == x &&
-                       m->smp.g_noise == noise && m->smp.g_seed == seed;
+                       m->smp.g_noise == noise && m->smp.g_seed == seed && m->smp.g_ragged == m->ragged();
     if (!reuse) m->drop_graph();    // this step bakes in x, the noise and the seed: a new one retires every held graph
     DWS_TRY(capture_step(m, cs, m->smp.graph, reuse, [&] { return one_step(m, x, noise, seed, T, cs); }));
     m->smp.g_B = m->B; m->smp.g_L = m->L; m->smp.g_T = T; m->smp.g_x = x; m->smp.g_noise = noise; m->smp.g_seed = seed;
+    m->smp.g_ragged = m->ragged();
     for (int i = 0; i < n_steps; ++i) DWS_HIP(hipGraphLaunch(m->smp.graph, cs));
+    DWS_TRY(seal_result(m, x, cs));
     return caller_after_engine(m, s);
 }
 
@@ -839,10 +849,11 @@ int sampler_run_schedule(dws_model* m, float* x, int kind, int S, const float* n
         // four one per form of seed (the per-clip step is other kernel instances on another grid): the kinds of call may
         // alternate without a new capture
         SamplerState::SchGraph& have = m->smp.sch_graphs[cfg ? SamplerState::SCH_CFG : pg ? SamplerState::SCH_PROG
-                                                  : masked ? SamplerState::SCH_EDIT : SamplerState::SCH_PLAIN][clips ? 1 : 0];
+                                                  : masked ? SamplerState::SCH_EDIT : SamplerState::SCH_PLAIN]
+                                                 [(clips ? 1 : 0) + (m->ragged() ? 2 : 0)];
         const SamplerState::SchKey key{m->B, m->L, S, kind, vec ? 1 : 0, a.tab, noise, a.eps, xr, st, m->step_table_gen,
                                     more.edit, more.y, more.mask, known_noise, V, pg ? m->smp.sch_prog.p : nullptr, more.hist,
-                                    clip.seeds};
+                                    clip.seeds, m->ragged() ? m->lengths_dev.p : nullptr};
         DWS_TRY(capture_step(m, q, have.exec, key == have.key, step));
         have.key = key;
         DWS_TRY(walk([&]() -> int {
@@ -850,6 +861,7 @@ int sampler_run_schedule(dws_model* m, float* x, int kind, int S, const float* n
             return DWS_OK;
         }));
     }
+    DWS_TRY(seal_result(m, xr, q));
     if (staged) DWS_HIP(hipMemcpyAsync(x, xr, n * 4, hipMemcpyDeviceToDevice, q));
     if (use_graph) DWS_TRY(caller_after_engine(m, s));
     DWS_HIP(hipGetLastError());

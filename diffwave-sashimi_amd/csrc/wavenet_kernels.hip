@@ -294,6 +294,43 @@ int launch_init_conv(const float* audio, const float* W, const float* bias, floa
     return DWS_OK;
 }
 
+// ---------------------------------------------------------------------------
+// Ragged batches (dws_model_set_lengths): seal the padding of x [B, C, L] behind a clip's own end.  One wave per row
+// (b, c) rewrites x[b, c, len_b .. min(L, len_b + reach)) with v: 0.0f for a tensor handed back to the caller, or
+// -fc_t(e)[b, c] of the layer that reads x next -- that layer convolves h = x + fc_t(e) zero-padded at the clip's end, so
+// the padding must hold the value that makes h zero (x + (-x) is exact), not zero itself.  Stores only: whatever the
+// padding held, a NaN included, is gone.  16-byte stores where the address allows, dwords at both ragged edges.
+// A clip with len_b == L has an empty range.
+// ---------------------------------------------------------------------------
+__global__ __launch_bounds__(64) void wn_mask_tail_kernel(float* __restrict__ x, const int32_t* __restrict__ lengths,
+                                                          const float* __restrict__ pt, int pt_bstride,
+                                                          const int* __restrict__ step_idx, int pt_tstride, int C, int L,
+                                                          int reach) {
+    const int b = blockIdx.y, c = blockIdx.x, lane = threadIdx.x;
+    const int len = min(max(lengths[b], 0), L);
+    const int end = reach < 0 ? L : (int)min((int64_t)L, (int64_t)len + reach);
+    if (len >= end) return;
+    const float v = pt ? -pt[(size_t)b * pt_bstride + c + step_row_off(step_idx, pt_tstride)] : 0.f;
+    float* row = x + ((size_t)b * C + c) * L;
+    // dwords up to the first 16-byte border at or behind len, float4 groups, dwords of the last partial group
+    const int head = (int)((4 - (((uintptr_t)(row + len) >> 2) & 3)) & 3);
+    const int a0 = min(len + head, end);
+    const int nvec = (end - a0) >> 2;
+    for (int i = len + lane; i < a0; i += 64) row[i] = v;
+    float4* q = reinterpret_cast<float4*>(row + a0);
+    const float4 v4 = make_float4(v, v, v, v);
+    for (int k = lane; k < nvec; k += 64) q[k] = v4;
+    for (int i = a0 + 4 * nvec + lane; i < end; i += 64) row[i] = v;
+}
+
+int launch_wn_mask_tail(float* x, const int32_t* lengths, int B, int C, int L, int reach, const float* pt, int pt_bstride,
+                        const int* step_idx, int pt_tstride, hipStream_t s) {
+    ProfileScope ps("wn_mask_tail", s);
+    DWS_CHECK(B >= 1 && B <= 65535, DWS_ERR_UNSUPPORTED, "per-clip lengths: B = %d (the grid has one row per clip: 1 .. 65535)", B);
+    hipLaunchKernelGGL(wn_mask_tail_kernel, dim3(C, B), dim3(64), 0, s, x, lengths, pt, pt_bstride, step_idx, pt_tstride, C, L, reach);
+    return DWS_OK;
+}
+
 // Data adjoint of init_conv: daudio[b,ci,l] = sum_c W[c,ci] * g[b,c,l], g the gradient of the ReLU's input.
 // y != nullptr: `g` is the gradient of the ReLU's OUTPUT y and is gated here, g * (y > 0) -- the data-only backward, which
 // never writes the masked gradient.  A thread owns one position (b, l) and every input channel: g is read once, in

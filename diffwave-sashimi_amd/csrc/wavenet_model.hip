@@ -319,7 +319,7 @@ struct WaveNetModel : dws_model {
     int prepare(int64_t nB, int64_t nL) override {
         DWS_CHECK(nB > 0 && nL > 0, DWS_ERR_INVALID, "prepare: B=%lld L=%lld", (long long)nB, (long long)nL);
         DWS_CHECK(nB * nL * (int64_t)std::max(2 * C, S) < (int64_t)1 << 40, DWS_ERR_UNSUPPORTED, "workspace too large");
-        if (nB != B || nL != L) { drop_graph(); melBm = 0; trained_fwd = false; }
+        if (nB != B || nL != L) { drop_graph(); melBm = 0; trained_fwd = false; lengths_host.clear(); frames_host.clear(); }
         if ((L == 0 || wino_fits(L)) != wino_fits(nL)) dirty = true;   // the layer kernel (and with it the A1 / Abt layout) changes
         B = nB; L = nL;
         const size_t act = (size_t)B * C * L * 4;
@@ -344,26 +344,102 @@ struct WaveNetModel : dws_model {
         DWS_CHECK(cond, DWS_ERR_INVALID, "set_condition on an unconditional model (`wavenet.py:99`)");
         DWS_CHECK(B > 0, DWS_ERR_STATE, "set_condition before prepare");
         DWS_CHECK(Bm == 1 || Bm == B, DWS_ERR_INVALID, "mel batch %lld must be 1 or B=%lld", (long long)Bm, (long long)B);
+        if (ragged()) DWS_TRY(check_ragged_mel(frames_host.data(), Bm, Tmel));
         if (dirty) DWS_TRY(commit(s));
         const int s0 = d.mel_upsample[0], s1 = d.mel_upsample[1];
         const int T0 = mel_upsampled_len((int)Tmel, s0), T1 = mel_upsampled_len(T0, s1);
         DWS_CHECK(T1 >= L, DWS_ERR_INVALID, "upsampled mel length %d < L=%lld (`wavenet.py:105`)", T1, (long long)L);
+        // (the kept copy first: with per-clip lengths on, the terms are evaluated from it, here and again by set_lengths)
+        if (mel != mel_in.p) {
+            DWS_TRY(mel_in.ensure((size_t)Bm * MB * Tmel * 4));
+            DWS_HIP(hipMemcpyAsync(mel_in.p, mel, (size_t)Bm * MB * Tmel * 4, hipMemcpyDeviceToDevice, s));
+        }
+        mel_T = (int)Tmel;
+        melBm = 0;   // (invalid while a launch below can still fail)
+        DWS_TRY(eval_condition(mel, Bm, s));
+        melBm = Bm;
+        return DWS_OK;
+    }
+
+    // a mel beside per-clip lengths: one mel per clip, and every clip's frames inside it
+    int check_ragged_mel(const int32_t* frames, int64_t Bm, int64_t Tmel) const {
+        DWS_CHECK(Bm == B, DWS_ERR_INVALID, "a shared mel (Bm = %lld) with per-clip lengths: a ragged batch has a mel per clip",
+                  (long long)Bm);
+        for (int64_t b = 0; b < B; ++b)
+            DWS_CHECK(frames[b] <= Tmel, DWS_ERR_INVALID, "mel_frames[%lld] = %d frames, the mel holds %lld", (long long)b,
+                      frames[b], (long long)Tmel);
+        return DWS_OK;
+    }
+
+    // the conditioner terms of every layer from `mel` [Bm][MB][mel_T].  Per-clip lengths on: clip b's mel frames >= frames_b
+    // and the first upsampler's output at positions >= s0 frames_b count as zero -- the second upsampler would otherwise
+    // read leaky_relu(bias + ..) != 0 there for the last s1 / 2 samples of the clip.  melc is pointwise in the position.
+    int eval_condition(const float* mel, int64_t Bm, hipStream_t s) {
+        const int s0 = d.mel_upsample[0], s1 = d.mel_upsample[1];
+        const int T0 = mel_upsampled_len(mel_T, s0), T1 = mel_upsampled_len(T0, s1);
+        const int32_t* fr = ragged() ? frames_ptr() : nullptr;
         DWS_TRY(mel_u0.ensure((size_t)Bm * MB * T0 * 4));
         DWS_TRY(mel_u1.ensure((size_t)Bm * MB * T1 * 4));
         DWS_TRY(melc.ensure((size_t)NL * Bm * 2 * C * L * 4));
         for (int n = 0; n < NL; ++n) {
             const std::string p = "residual_layer.residual_blocks." + std::to_string(n);
             DWS_TRY(launch_mel_upsample(mel, melW0[n].f(), P(p + ".upsample_conv2d.0.bias"), mel_u0.f(), (int)Bm, MB,
-                                        (int)Tmel, T0, s0, 0.4f, s));
+                                        mel_T, T0, s0, 0.4f, s, fr, 1));
             DWS_TRY(launch_mel_upsample(mel_u0.f(), melW1[n].f(), P(p + ".upsample_conv2d.1.bias"), mel_u1.f(), (int)Bm,
-                                        MB, T0, T1, s1, 0.4f, s));
+                                        MB, T0, T1, s1, 0.4f, s, fr, s0));
             DWS_TRY(launch_conv1x1_trunc(mel_u1.f(), melWc[n].f(), P(p + ".mel_conv.conv.bias"),
                                          melc.f() + (size_t)n * Bm * 2 * C * L, (int)Bm, MB, 2 * C, T1, (int)L, s));
         }
-        DWS_TRY(mel_in.ensure((size_t)Bm * MB * Tmel * 4));
-        DWS_HIP(hipMemcpyAsync(mel_in.p, mel, (size_t)Bm * MB * Tmel * 4, hipMemcpyDeviceToDevice, s));
-        mel_T = (int)Tmel;
-        melBm = Bm;
+        return DWS_OK;
+    }
+
+    int set_lengths(const int32_t* lengths, const int32_t* mel_frames, int64_t nB, hipStream_t s) override {
+        if (!lengths) {
+            if (!ragged()) return DWS_OK;
+            lengths_host.clear(); frames_host.clear();
+            if (dirty && melBm > 0) DWS_TRY(commit(s));   // (drops the installed mel: nothing to re-evaluate below)
+            if (melBm > 0) {   // the terms were built under the old frame counts
+                const int64_t Bm = melBm;
+                melBm = 0;
+                DWS_TRY(eval_condition(mel_in.f(), Bm, s));
+                melBm = Bm;
+            }
+            return DWS_OK;
+        }
+        DWS_CHECK(B > 0, DWS_ERR_STATE, "dws_model_set_lengths before dws_model_prepare");
+        DWS_CHECK(nB == B, DWS_ERR_INVALID, "dws_model_set_lengths: %lld lengths for a prepared batch of %lld", (long long)nB, (long long)B);
+        DWS_CHECK(!smp.cfg_on, DWS_ERR_UNSUPPORTED, "per-clip lengths are not built for classifier-free guidance (dws_sampler_set_cfg is on)");
+        const int64_t hop = cond ? (int64_t)d.mel_upsample[0] * d.mel_upsample[1] : 1;
+        std::vector<int32_t> fr((size_t)B, 1);
+        for (int64_t b = 0; b < B; ++b) {
+            DWS_CHECK(lengths[b] >= 1 && lengths[b] <= L, DWS_ERR_INVALID, "dws_model_set_lengths: lengths[%lld] = %d (needs 1 .. L = %lld)",
+                      (long long)b, lengths[b], (long long)L);
+            if (!cond) continue;
+            const int64_t f = mel_frames ? mel_frames[b] : (lengths[b] + hop - 1) / hop;
+            DWS_CHECK(f >= 1 && f <= INT32_MAX && hop * f >= lengths[b], DWS_ERR_INVALID,
+                      "dws_model_set_lengths: mel_frames[%lld] = %lld frames of %lld samples for a clip of %d", (long long)b,
+                      (long long)f, (long long)hop, lengths[b]);
+            fr[b] = (int32_t)f;
+        }
+        if (melBm > 0) DWS_TRY(check_ragged_mel(fr.data(), melBm, mel_T));
+        if (lengths_host.size() == (size_t)B && std::memcmp(lengths_host.data(), lengths, (size_t)B * 4) == 0 && frames_host == fr)
+            return DWS_OK;     // the table already installed
+        if (dirty && melBm > 0) DWS_TRY(commit(s));   // (drops the installed mel: nothing to re-evaluate below)
+        DWS_TRY(lengths_dev.ensure((size_t)B * 8));
+        int32_t* h = nullptr;
+        DWS_TRY(length_ring.acquire((size_t)B * 8, (void**)&h));
+        std::memcpy(h, lengths, (size_t)B * 4);
+        std::memcpy(h + B, fr.data(), (size_t)B * 4);
+        DWS_HIP(hipMemcpyAsync(lengths_dev.p, h, (size_t)B * 8, hipMemcpyHostToDevice, s));
+        DWS_TRY(length_ring.commit(s));
+        lengths_host.assign(lengths, lengths + B);
+        frames_host = fr;
+        if (melBm > 0) {   // a forward never runs with conditioner terms built for other lengths
+            const int64_t Bm = melBm;
+            melBm = 0;
+            DWS_TRY(eval_condition(mel_in.f(), Bm, s));
+            melBm = Bm;
+        }
         return DWS_OK;
     }
 
@@ -383,6 +459,7 @@ struct WaveNetModel : dws_model {
 
     int forward_train(const float* audio, const float* steps, float* out, hipStream_t s) override {
         DWS_CHECK(B > 0, DWS_ERR_STATE, "forward before prepare");
+        DWS_CHECK(!ragged(), DWS_ERR_UNSUPPORTED, "training with per-clip lengths (dws_model_set_lengths) is not built");
         DWS_CHECK(!bf16x3 && !f16x3 && (!bf16x6 || mfma_bwd), DWS_ERR_UNSUPPORTED,
                   "training runs with precision=f32, or bf16x6 where the MFMA adjoints run (no bf16x3 / f16x3 backward is built)");
         DWS_CHECK(melBm == 0 || (melBm == B && mfma_bwd), DWS_ERR_UNSUPPORTED,
@@ -523,6 +600,20 @@ struct WaveNetModel : dws_model {
             DWS_TRY(embed_rows(steps, (int)B, emb.f(), h1.f(), h2.f(), part_t.f(), Abt.p, train ? ta1.f() : nullptr,
                                train ? ta2.f() : nullptr, s, n_classes > 0 ? labels_ptr() : nullptr, (int)B));
         const int arow = abt_row();
+        // Ragged batches: x, about to be read by layer n, is sealed behind every clip's own end -- the reach of a valid
+        // output of that layer is its dilation (taps l - d, l, l + d; the residual update is pointwise; in the Winograd pair
+        // (p, p + d) the fourth input x[p + 2d] enters m3 alone, hence only the output at p + d), and the value is
+        // -fc_t(e) of layer n, which makes the layer's zero-padded input h = x + fc_t(e) zero there (wn_mask_tail_kernel).
+        static const bool full_tail = std::getenv("DWS_RAGGED_FULL_TAIL") != nullptr;   // A/B of the two reach choices
+        const auto seal = [&](float* x, int n) -> int {
+            const int reach = full_tail ? -1 : 1 << (n % cycle);
+            if (tab)
+                return launch_wn_mask_tail(x, lengths_ptr(), (int)B, C, (int)L, reach, tab_pt.f() + (size_t)n * C,
+                                           tab_rep > 1 ? NL * C : 0, step_idx, tab_rep * NL * C, s);
+            return launch_wn_mask_tail(x, lengths_ptr(), (int)B, C, (int)L, reach, part_t.f() + (size_t)n * C, NL * C, nullptr, 0, s);
+        };
+        const bool rag = ragged() && !train;
+        if (rag) DWS_TRY(seal(xfirst, 0));
         for (int n = 0; n < NL; ++n) {
             const std::string p = "residual_layer.residual_blocks." + std::to_string(n);
             WnLayerArgs a{};
@@ -557,8 +648,11 @@ struct WaveNetModel : dws_model {
             else if (wino()) DWS_TRY(launch_wn_layer_wino(C, S, a, s));
             else if (mfma_layer) DWS_TRY(launch_wn_layer_mfma(C, S, a, s));
             else DWS_TRY(launch_wn_layer_generic(C, S, a, s));
+            if (rag && n + 1 < NL) DWS_TRY(seal(a.x_out, n + 1));
         }
         DWS_TRY(final_stage(out, train ? ty.f() : nullptr, s));
+        // the tensor handed back holds exactly 0.0f behind every clip's end (the skip sums there are padding)
+        if (rag) DWS_TRY(launch_wn_mask_tail(out, lengths_ptr(), (int)B, Cout, (int)L, -1, nullptr, 0, nullptr, 0, s));
         DWS_HIP(hipGetLastError());
         return DWS_OK;
     }

@@ -234,6 +234,40 @@ def clip_plan(n_samples, batch_size, rank=0, num_ranks=1, clip_seeds=False, clip
     return [mine[i:i + batch_size] for i in range(0, len(mine), batch_size)]
 
 
+def ragged_plan(frame_counts, batch_size):
+    """Batches of a list of utterances of different lengths (``generate.mel_names``): the indices ``k`` into
+    ``frame_counts`` sorted by length, longest first (equal lengths keep their order in the list), cut into batches of at
+    most ``batch_size`` -- a batch runs at the length of its first utterance, so sorting keeps the padded share small.
+    Every index appears exactly once.  Pure host arithmetic."""
+    if isinstance(batch_size, bool) or not isinstance(batch_size, int) or batch_size < 1:
+        raise ValueError(f"generate.batch_size={batch_size!r}: expected an integer >= 1")
+    counts = list(frame_counts)
+    if any(isinstance(f, bool) or not isinstance(f, (int, np.integer)) or f < 1 for f in counts):
+        raise ValueError(f"ragged_plan: frame counts are integers >= 1, got {counts!r}")
+    order = sorted(range(len(counts)), key=lambda k: -int(counts[k]))     # (sorted is stable)
+    return [order[i:i + batch_size] for i in range(0, len(order), batch_size)]
+
+
+def _check_mel_names(mel_names, mel_name, clip_seeds, seed, **others):
+    """Argument checks of ``generate.mel_names`` before a model is built (ValueError).  Returns the list of stems."""
+    if mel_name is not None:
+        raise ValueError("generate.mel_names and generate.mel_name exclude each other (a list of utterances, or one)")
+    names = list(mel_names) if isinstance(mel_names, (list, tuple)) else [mel_names]
+    if not names or any(not isinstance(n, str) or not n for n in names):
+        raise ValueError(f"generate.mel_names={mel_names!r}: expected a list of wav stems")
+    if len(set(names)) != len(names):
+        raise ValueError(f"generate.mel_names={mel_names!r}: an utterance is named twice")
+    if isinstance(clip_seeds, str) or clip_seeds not in (None, False, True, 0, 1):
+        raise ValueError(f"generate.clip_seeds={clip_seeds!r}: expected true or false")
+    if clip_seeds and (seed is None or isinstance(seed, bool) or not isinstance(seed, int)):
+        raise ValueError("generate.clip_seeds needs generate.seed (an integer: the clips' seeds are derived from it)")
+    given = sorted(k for k, v in others.items() if v is not None)
+    if given:
+        raise ValueError(f"generate.mel_names does not combine with generate.{given[0]} (ragged batches run the plain "
+                         "samplers: no editing, restoration, labels or clip selection)")
+    return names
+
+
 def _load_clip(dataset_cfg, stem, audio_length, conditional):
     """``<dataset.data_path>/<stem>.wav`` as a [1, 1, audio_length] clip in [-1, 1], read as ``train.SpeechCommands``
     reads one (int16 / 32768, int32 / 2^31, float as it is; first channel).  Unconditional: fitted to the segment the
@@ -268,7 +302,8 @@ def generate(rank, diffusion_cfg, model_cfg, dataset_cfg, ckpt_iter="max", n_sam
              written=None, precision=None, sampler="ddpm", steps=None, eta=0.0, known_name=None, keep=None,
              start_name=None, start_step=None, start_noise=True, resample_jump=None, resample_n=None, spacing=None,
              guide_name=None, guide_op=None, guide_clip=None, guide_factor=None, guide_scale=None, label=None,
-             cfg_scale=None, ema=None, clip_seeds=None, clips=None, num_ranks=None, report_mel=None, mel_errors=None):
+             cfg_scale=None, ema=None, clip_seeds=None, clips=None, num_ranks=None, report_mel=None, mel_errors=None,
+             mel_names=None):
     """``generate.py:58-200``.  ``ckpt_iter`` may additionally be ``"init"``: seeded random weights
     (no checkpoint), for smoke runs without trained weights.  ``precision`` (not in the reference; CLI:
     ``+engine.precision=bf16x6|f16x3``): the engine's opt-in matrix arithmetic, see ``include/dws.h``.
@@ -318,7 +353,19 @@ def generate(rank, diffusion_cfg, model_cfg, dataset_cfg, ckpt_iter="max", n_sam
     keys): ``clip_seeds=true`` (needs ``seed``) seeds every clip on its own -- global clip ``k = n_samples rank + i``, the
     number in its wav name, draws from ``sampling.clip_seeds(seed, k, 1)`` and, with ``label``, has the class
     ``labels[k % len(labels)]`` -- so ``{iter}k_{k}.wav`` is the same file for any ``batch_size`` dividing ``n_samples``
-    and any number of ranks (``num_ranks``: the processes of the run, one per GPU) that produces clip k.  ``clips``
+    and any number of ranks (``num_ranks``: the processes of the run, one per GPU) that produces clip k.
+
+    Ragged batches (not in the reference; mel-conditional WaveNet): ``mel_names`` is a LIST of utterances (wav stems, as
+    ``mel_name`` names one; the two exclude each other), each vocoded once.  ``ragged_plan`` sorts them longest first and
+    cuts batches of at most ``batch_size`` (default: all in one); ranks take the batches round-robin.  A batch runs at
+    the length of its longest utterance with the per-clip ``lengths`` of ``sampling`` -- every utterance comes out as it
+    would alone, none sees another's or its own padding -- and each wav is written trimmed to ``frames x hop_length``
+    samples as ``{iter//1000}k_{stem}.wav``.  With ``clip_seeds=true`` the seed of utterance k (its place in the list) is
+    ``sampling.clip_seeds(seed, k, 1)``, so the same file comes out at any ``batch_size`` up to the arithmetic of the
+    kernel path (the padded length L_max of its batch selects kernels and sets the edge indicators of the Winograd
+    correction rows; not bit for bit).  Per batch ``L_max``, the lengths and the padded share are printed: a padded
+    position still costs its full time.  Does not combine with the editing, restoration, label and ``clips`` keys.
+    Returns the list of the trimmed clips [1, len_k] in the order of ``mel_names`` (None for another rank's).  ``clips``
     (a list of global clip numbers; needs ``clip_seeds``) generates only these, under their usual names: rank r of N takes
     ``clips[r::N]`` in batches of up to ``batch_size`` (``clip_plan``).  Returns the audio of the clips this rank made."""
     from .models import construct_model
@@ -331,7 +378,15 @@ def generate(rank, diffusion_cfg, model_cfg, dataset_cfg, ckpt_iter="max", n_sam
 
     if ckpt_smooth is not None or ckpt_iter == "init":     # checked here, before a model is built
         weights_key(None, ema, ckpt_smooth)
-    plan = clip_plan(n_samples, n_samples if batch_size is None else batch_size, rank, num_ranks, clip_seeds, clips, seed)
+    if mel_names is not None:
+        mel_names = _check_mel_names(mel_names, mel_name, clip_seeds, seed, known_name=known_name, start_name=start_name,
+                                     resample_jump=resample_jump, guide_name=guide_name, guide_op=guide_op, label=label,
+                                     cfg_scale=cfg_scale, clips=clips, report_mel=report_mel)
+        if model_cfg.get("unconditional"):
+            raise ValueError("generate.mel_names needs a mel-conditional model (model.unconditional=false)")
+        plan = None
+    else:
+        plan = clip_plan(n_samples, n_samples if batch_size is None else batch_size, rank, num_ranks, clip_seeds, clips, seed)
     # guide_op=mel on a mel-conditional run needs no recording: the measurement is the conditioning mel itself
     guided = guide_name is not None or (guide_op == "mel" and mel_name is not None)
     guide_key = "generate.guide_name" if guide_name is not None else "generate.guide_op=mel"
@@ -471,6 +526,57 @@ def generate(rank, diffusion_cfg, model_cfg, dataset_cfg, ckpt_iter="max", n_sam
             net.load_state_dict(state_dict)
     output_directory = os.path.join(output_directory, str(ckpt_iter))
     os.makedirs(output_directory, mode=0o775, exist_ok=True)
+
+    if mel_names is not None:
+        # ---- ragged batches: every utterance once, batches of the plan at their own L_max with per-clip lengths
+        hop = dataset_cfg["hop_length"]
+        mels = []
+        for stem in mel_names:
+            if mel_path is not None:
+                try:
+                    mels.append(torch.load(os.path.join(mel_path, f"{stem}.wav.pt")).to(torch.float32).cuda())
+                except Exception:
+                    raise Exception(f"No ground truth mel spectrogram found ({stem})")
+            else:
+                from .mel import Mel2Samp, load_wav_to_torch
+                keys = ("filter_length", "hop_length", "win_length", "sampling_rate", "mel_fmin", "mel_fmax")
+                _mel = Mel2Samp(**{k: dataset_cfg[k] for k in keys if k in dataset_cfg})
+                audio, sr = load_wav_to_torch(os.path.join(str(dataset_cfg["data_path"]), f"{stem}.wav"))
+                mels.append(_mel.get_mel(audio).to(torch.float32).cuda())
+        frames = [int(m.shape[-1]) for m in mels]
+        batches = ragged_plan(frames, len(mel_names) if batch_size is None else batch_size)
+        clips_out = [None] * len(mel_names)
+        t0 = time.perf_counter()
+        for i, batch in list(enumerate(batches))[rank % max(int(num_ranks or 1), 1)::max(int(num_ranks or 1), 1)]:
+            lens = [frames[k] * hop for k in batch]
+            Tmax, Lmax = frames[batch[0]], lens[0]
+            mel = torch.zeros(len(batch), mels[0].shape[0], Tmax, device="cuda", dtype=torch.float32)
+            for b, k in enumerate(batch):
+                mel[b, :, :frames[k]] = mels[k]
+            size = (len(batch), 1, Lmax)
+            s = [seeds_of_clips(seed, k, 1)[0] for k in batch] if clip_seeds else (None if seed is None else seed + i)
+            print(f"batch {i}: L_max = {Lmax}, lengths = {lens}, padded share = "
+                  f"{1.0 - sum(lens) / float(len(batch) * Lmax):.3f}")
+            if sampler == "aligned":
+                x = sampling_aligned(net, size, diffusion_cfg, condition=mel, seed=s, lengths=lens)
+            elif sampler == "ddim":
+                x = sampling_ddim(net, size, dh_train, steps, eta=float(eta or 0.0), condition=mel, seed=s, lengths=lens)
+            elif sampler == "dpmpp2m":
+                x = sampling_dpmpp(net, size, dh_train, steps, condition=mel, spacing=spacing, seed=s, lengths=lens)
+            else:
+                x = sampling(net, size, dh, condition=mel, seed=s, lengths=lens)
+            for b, k in enumerate(batch):
+                clips_out[k] = x[b, :, :lens[b]].clone()
+        torch.cuda.synchronize()
+        made = [k for k, c in enumerate(clips_out) if c is not None]
+        print(f"generated {len(made)} utterances of {len(mel_names)} at iteration {ckpt_iter} in "
+              f"{time.perf_counter() - t0:.1f} seconds ({n_evals} network evaluations per batch)")
+        for k in made:
+            outfile = os.path.join(output_directory, "{}k_{}.wav".format(ckpt_iter // 1000, mel_names[k]))
+            wavwrite(outfile, dataset_cfg["sampling_rate"], clips_out[k].squeeze(0).cpu().numpy().astype(np.float32))
+            if written is not None:
+                written.append(outfile)
+        return clips_out
 
     if batch_size is None:
         batch_size = n_samples

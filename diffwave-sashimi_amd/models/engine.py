@@ -144,6 +144,7 @@ class EngineModule(nn.Module):
         self.n_classes = 0            # class-conditional models (config key n_classes): set by the subclass
         self._label_key = ()          # the label assignment the engine holds: () = the null class everywhere
         self._call_labels = None
+        self._length_key = ()         # the per-clip lengths the engine holds: () = off
 
     # -- handle management ---------------------------------------------------
     def _desc(self):
@@ -230,6 +231,7 @@ class EngineModule(nn.Module):
             self._shape = (B, L)
             self._mel_key = None
             self._label_key = ()      # the engine resets the labels of another shape to the null class
+            self._length_key = ()     # and drops the per-clip lengths
 
     def _set_condition(self, mel_spec):
         lib = _lib.load()
@@ -277,6 +279,47 @@ class EngineModule(nn.Module):
             _lib.check(lib.dws_model_set_labels(self._ensure_handle(), None, B, _lib.current_stream()))
         self._label_key = key
 
+    @staticmethod
+    def _length_list(lengths, name="lengths"):
+        """``lengths`` (None, or an integer tensor / sequence [B] on any device) as a tuple of ints.  Only the form is
+        checked here (ValueError); the values are checked by the engine against the prepared shape (RuntimeError)."""
+        if lengths is None:
+            return ()
+        t = torch.as_tensor(lengths).detach()
+        if t.is_floating_point() or t.is_complex() or t.dtype == torch.bool or t.dim() != 1 or t.numel() < 1:
+            raise ValueError(f"{name} must be an integer tensor or sequence [B], got {t.dtype} {tuple(t.shape)}")
+        key = tuple(int(v) for v in t.cpu().tolist())
+        if any(v < -2 ** 31 or v >= 2 ** 31 for v in key):
+            raise ValueError(f"{name} must fit 32-bit integers, got {list(key)}")
+        return key
+
+    def _set_lengths(self, lengths, mel_spec=None, mel_frames=None):
+        """Install the per-clip lengths of the coming call (None = off), cached by content as the labels are.  Comes
+        before ``_set_condition(mel_spec)``: the engine checks a mel against the lengths it holds and the lengths against
+        the mel it holds, so when both change the old mel is dropped first."""
+        key = self._length_list(lengths)
+        frames = self._length_list(mel_frames, "mel_frames")
+        if frames and not key:
+            raise ValueError("mel_frames= needs lengths=")
+        if frames and len(frames) != len(key):
+            raise ValueError(f"mel_frames holds {len(frames)} entries, lengths {len(key)}")
+        full = (key, frames) if key else ()
+        if full == self._length_key:
+            return
+        lib = _lib.load()
+        h = self._ensure_handle()
+        if self._mel_key is not None and mel_spec is not self._mel_ref:
+            _lib.check(lib.dws_model_set_condition(h, 0, 0, 0, _lib.current_stream()))
+            self._mel_key = self._mel_ref = None
+        if key:
+            n = len(key)
+            arr = (ctypes.c_int32 * n)(*key)
+            fr = (ctypes.c_int32 * n)(*frames) if frames else None
+            _lib.check(lib.dws_model_set_lengths(h, arr, fr, n, _lib.current_stream()))
+        else:
+            _lib.check(lib.dws_model_set_lengths(h, None, None, 0, _lib.current_stream()))
+        self._length_key = full
+
     def _expand_mel(self, mel_spec, B):
         """One mel for B clips, [1, bands, Tmel] -> [B, bands, Tmel] (the training forward needs a mel per clip).  The
         expanded tensor is kept with the one it was made from, so that ``_set_condition`` recognises it call after call."""
@@ -289,7 +332,11 @@ class EngineModule(nn.Module):
         return kept[2]
 
     # -- reference surface -----------------------------------------------------
-    def forward(self, input_data, mel_spec=None, labels=None):
+    def forward(self, input_data, mel_spec=None, labels=None, lengths=None, mel_frames=None):
+        """``lengths`` (WaveNet; not in the reference): an int sequence / tensor [B], clip b is ``lengths[b] <= L`` samples
+        long and the rest of its row is padding -- over ``[0, lengths[b])`` the output is what the clip gives alone at its
+        own length, nothing stored in the padding (of ``audio`` or of ``mel_spec`` behind ``mel_frames[b]`` frames, default
+        ``ceil(lengths[b] / hop)``) reaches it, and the output holds 0.0 there.  Evaluation calls only."""
         audio, diffusion_steps = input_data
         if labels is not None and not self.n_classes:
             raise ValueError("labels= on a model without classes (set model.n_classes)")
@@ -301,6 +348,10 @@ class EngineModule(nn.Module):
         B, Cin, L = audio.shape
         train_call = torch.is_grad_enabled() and self.training and any(p.requires_grad for p in self.parameters())
         if train_call or (torch.is_grad_enabled() and audio.requires_grad):
+            if lengths is not None:
+                raise NotImplementedError("lengths= (ragged batches) is built for evaluation calls: no training forward, "
+                                          "no input gradient")
+            self._set_lengths(None, mel_spec)
             # training call (`train.py:221`): differentiable w.r.t. the parameters -- and, in train() or eval() mode (the nets
             # have no mode-dependent layer), w.r.t. an `audio` that requires a gradient; then alone, the parameters stay out of
             # the graph and backward is data-only.  The path has the limits of forward_train (f32 / bf16x6, no segmented S4
@@ -316,6 +367,7 @@ class EngineModule(nn.Module):
             self._sync_params(L)
             self._prepare(B, L)
             self._set_labels(labels, B)
+            self._set_lengths(lengths, mel_spec, mel_frames)
             self._set_condition(mel_spec)
             x = audio.detach().to(torch.float32).contiguous()
             steps = diffusion_steps.detach().to(device=audio.device, dtype=torch.float32).reshape(-1).contiguous()

@@ -64,6 +64,21 @@ _MASK64 = (1 << 64) - 1
 _GOLDEN64 = 0x9E3779B97F4A7C15
 
 
+def _check_lengths(net, size, lengths, cfg_scale):
+    """Argument checks of ``lengths=`` before anything runs (ValueError).  Returns the lengths as a tuple of ints, or
+    None.  The values themselves (1 .. L, one per clip) are checked by the engine."""
+    if lengths is None:
+        return None
+    if cfg_scale is not None:
+        raise ValueError("sampler: lengths= (ragged batches) is not built for classifier-free guidance (cfg_scale=)")
+    if not hasattr(net, "_set_lengths"):
+        raise ValueError("sampler: lengths= needs an engine model")
+    key = net._length_list(lengths)
+    if len(key) != size[0]:
+        raise ValueError(f"sampler: lengths holds {len(key)} entries for a batch of {size[0]}")
+    return key
+
+
 def _splitmix64(z):
     """The splitmix64 finaliser (Steele, Lea & Flood, 2014) of a 64-bit integer, in host integer arithmetic."""
     z = (z + _GOLDEN64) & _MASK64
@@ -116,7 +131,7 @@ def _set_clip_seeds(net, seeds):
         _lib.check(lib.dws_sampler_set_clip_seeds(net._handle, table, len(seeds), _lib.current_stream()))
 
 
-def _prepare_run(net, size, steps, condition, x_T, noise, seed, labels=(), cfg=False):
+def _prepare_run(net, size, steps, condition, x_T, noise, seed, labels=(), cfg=False, lengths=None):
     """Shared set-up of the sampler entry points: the engine's parameters / shape / condition / labels, the state tensor
     x (x_T, or to be drawn on the device: init = 1), the injected noise [steps, B, C, L] and the seed.  ``cfg``: the
     engine is prepared for 2 B clips -- the labels in the first half, the null class in the second -- while x and the
@@ -134,6 +149,7 @@ def _prepare_run(net, size, steps, condition, x_T, noise, seed, labels=(), cfg=F
         if condition is not None and condition.dim() == 3 and condition.shape[0] == B and B > 1:
             condition = torch.cat([condition, condition], dim=0)
     net._set_labels(list(labels) if labels else None, nB)
+    net._set_lengths(lengths, condition)     # (None: off -- lengths hold for the run they are given to)
     net._set_condition(condition)
     if x_T is None:
         x = torch.empty(size, device=dev, dtype=torch.float32)
@@ -351,7 +367,7 @@ def _check_edit(size, S, x_T, known=None, mask=None, known_noise=None, x_start=N
 
 def sampling(net, size, diffusion_hyperparams, condition=None, *, x_T=None, noise=None, seed=None,
              use_graph=True, net_steps=None, known=None, mask=None, known_noise=None, x_start=None, start_step=None,
-             start_noise=None, resample=None, labels=None, cfg_scale=None):
+             start_noise=None, resample=None, labels=None, cfg_scale=None, lengths=None):
     """``x_0 = sampling(net, (B, C, L), dh, condition)`` as in ``generate.py:23-55``.
 
     Class-conditional models (``model.n_classes``; not in the reference), on every sampler of this module:
@@ -361,6 +377,17 @@ def sampling(net, size, diffusion_hyperparams, condition=None, *, x_T=None, nois
              conditional run; costs a network of twice the batch).  Needs ``labels``; not built for the editing and
              resampling arguments.  Goes through the schedule entry with ``net_steps = 0..T-1`` (bit-identical to
              ``dws_sampler_run``).
+
+    Ragged batches (WaveNet; ``dws_model_set_lengths``), on ``sampling``, ``sampling_aligned``, ``sampling_ddim`` and
+    ``sampling_dpmpp``:
+      lengths    int sequence / tensor [B] with 1 <= lengths[b] <= L: clip b is that long, the rest of its row is
+             padding.  Over ``[0, lengths[b])`` the run is the clip's own run at that length (the network never sees the
+             padding: of the state, of ``condition`` behind ``ceil(lengths[b] / hop)`` mel frames, of injected noise);
+             the returned ``x`` holds 0.0 in the padding.  Combines with per-clip ``seed=[...]``, ``labels``,
+             ``known`` / ``mask``, ``x_start`` / ``start_step`` and ``resample``; refused together with ``cfg_scale`` and
+             on ``sampling_guided``.  With a SCALAR seed a clip's noise depends on L (the Philox element index runs over
+             the whole padded batch), so a short clip is reproducible across batch compositions only with per-clip
+             seeds, whose numbering is the position inside the clip.  A padded position still costs its full time.
 
     Extra keyword-only arguments (not in the reference):
       x_T    initial state [B,C,L]; default: drawn on the device from the Philox stream
@@ -394,6 +421,7 @@ def sampling(net, size, diffusion_hyperparams, condition=None, *, x_T=None, nois
     assert len(Alpha) == T and len(Alpha_bar) == T and len(Sigma) == T and len(size) == 3
     edit = dict(known=known, mask=mask, known_noise=known_noise, x_start=x_start, start_step=start_step,
                 start_noise=start_noise)
+    lengths = _check_lengths(net, size, lengths, cfg_scale)
     lab, scale = _check_labels(net, size, labels, cfg_scale, edit, resample)
     per_clip = seed_list(seed, size[0]) is not None
     if resample is None and all(v is None for v in edit.values()):
@@ -405,10 +433,11 @@ def sampling(net, size, diffusion_hyperparams, condition=None, *, x_T=None, nois
     if net_steps is not None:
         coef = np.stack([_host_table(Alpha)[0], _host_table(Alpha_bar)[0], _host_table(Sigma)[0]])
         return _run_schedule(net, size, _lib.DWS_SAMPLER_DDPM, net_steps, coef, condition, x_T, noise, seed, use_graph,
-                             edit=edit, levels=coef[1], resample=resample, labels=labels, cfg_scale=cfg_scale)
+                             edit=edit, levels=coef[1], resample=resample, labels=labels, cfg_scale=cfg_scale,
+                             lengths=lengths)
     lib = _lib.load()
     with torch.no_grad():
-        x, init, nz, seed = _prepare_run(net, size, T, condition, x_T, noise, seed, labels=lab)
+        x, init, nz, seed = _prepare_run(net, size, T, condition, x_T, noise, seed, labels=lab, lengths=lengths)
         a, pa = _host_table(Alpha)
         ab, pab = _host_table(Alpha_bar)
         sg, psg = _host_table(Sigma)
@@ -419,11 +448,12 @@ def sampling(net, size, diffusion_hyperparams, condition=None, *, x_T=None, nois
 
 
 def _run_schedule(net, size, kind, net_steps, coef, condition, x_T, noise, seed, use_graph, edit=None, levels=None,
-                  resample=None, labels=None, cfg_scale=None):
+                  resample=None, labels=None, cfg_scale=None, lengths=None):
     """``dws_sampler_run_schedule``: S steps s = S-1..0, the network at ``net_steps[s]``, update tables ``coef``.
     ``edit``: the editing arguments of ``sampling`` (-> ``dws_sampler_run_edit``), ``levels`` the run's alpha_bar.
     ``resample``: (jump, resamples) on top of ``edit`` (-> ``dws_sampler_run_program``)."""
     assert len(size) == 3
+    lengths = _check_lengths(net, size, lengths, cfg_scale)
     lab, scale = _check_labels(net, size, labels, cfg_scale, edit, resample)
     seeds = seed_list(seed, size[0])
     steps = np.ascontiguousarray(np.asarray(net_steps, dtype=np.float32).reshape(-1))
@@ -443,7 +473,8 @@ def _run_schedule(net, size, kind, net_steps, coef, condition, x_T, noise, seed,
     fp = ctypes.POINTER(ctypes.c_float)
     with torch.no_grad(), contextlib.ExitStack() as cleanup:
         x, init, nz, seed = _prepare_run(net, size, S if prog is None else len(prog), condition, x_T, noise,
-                                         seed if seeds is None else 0, labels=lab, cfg=scale is not None)
+                                         seed if seeds is None else 0, labels=lab, cfg=scale is not None,
+                                         lengths=lengths)
         if seeds is not None:     # per-clip seeds hold for this run alone: the engine's table is dropped behind it
             _set_clip_seeds(net, seeds)
             cleanup.callback(_set_clip_seeds, net, None)
@@ -555,7 +586,7 @@ def ddim_coefficients(alpha_bar, tau, eta):
 
 def sampling_ddim(net, size, dh_train, steps, eta=0.0, condition=None, *, x_T=None, noise=None, seed=None,
                   use_graph=True, known=None, mask=None, known_noise=None, x_start=None, start_step=None,
-                  start_noise=None, resample=None, labels=None, cfg_scale=None):
+                  start_noise=None, resample=None, labels=None, cfg_scale=None, lengths=None):
     """DDIM over ``ddim_steps(T, steps)`` of the training schedule ``dh_train`` (``steps``: S or an explicit list),
     deterministic for ``eta = 0``.  ``noise``: injected z, [S, B, C, L] (``noise[s]`` is used after step s > 0).
     The editing arguments, ``resample``, ``labels`` and ``cfg_scale`` are those of ``sampling`` (levels:
@@ -568,7 +599,7 @@ def sampling_ddim(net, size, dh_train, steps, eta=0.0, condition=None, *, x_T=No
         edit = None
     return _run_schedule(net, size, _lib.DWS_SAMPLER_DDIM, np.asarray(tau, dtype=np.float32), coef, condition, x_T,
                          noise, seed, use_graph, edit=edit, levels=_host_table(dh_train["Alpha_bar"])[0][tau],
-                         resample=resample, labels=labels, cfg_scale=cfg_scale)
+                         resample=resample, labels=labels, cfg_scale=cfg_scale, lengths=lengths)
 
 
 def logsnr_steps(alpha_bar, S):
@@ -622,7 +653,7 @@ def dpmpp_coefficients(alpha_bar, tau):
 
 def sampling_dpmpp(net, size, dh_train, steps, condition=None, *, spacing="logsnr", x_T=None, seed=None,
                    use_graph=True, known=None, mask=None, known_noise=None, x_start=None, start_step=None,
-                   start_noise=None, resample=None, noise=None, labels=None, cfg_scale=None):
+                   start_noise=None, resample=None, noise=None, labels=None, cfg_scale=None, lengths=None):
     """DPM-Solver++(2M) over ``logsnr_steps(Alpha_bar, steps)`` of the training schedule ``dh_train``
     (``spacing="uniform"``: over ``ddim_steps(T, steps)``; ``steps``: S or an explicit list).  Second order at the cost
     of DDIM: one network evaluation per step, the previous step's data prediction kept on the device.  Deterministic:
@@ -645,7 +676,7 @@ def sampling_dpmpp(net, size, dh_train, steps, condition=None, *, spacing="logsn
         edit = None
     return _run_schedule(net, size, _lib.DWS_SAMPLER_DPMPP2M, np.asarray(tau, dtype=np.float32), coef, condition, x_T,
                          noise, seed, use_graph, edit=edit, levels=ab[tau], resample=resample, labels=labels,
-                         cfg_scale=cfg_scale)
+                         cfg_scale=cfg_scale, lengths=lengths)
 
 
 def sampling_aligned(net, size, diffusion_cfg, condition=None, **kw):
@@ -795,6 +826,10 @@ def sampling_guided(net, size, diffusion_hyperparams, *, measurement, operator, 
     no graph capture: each step contains a backward.  Costs a forward plus a backward per step.  The editing arguments
     (``known`` / ``mask`` ..., ``resample``) and ``cfg_scale`` are not built for guided runs; ``labels`` ([B], a
     class-conditional model) are passed to every network call.  Not the reference's loop."""
+    if unsupported.get("lengths") is not None:
+        raise ValueError("sampling_guided: lengths= (ragged batches) is not built for guided runs: every step is a "
+                         "training forward")
+    unsupported.pop("lengths", None)
     if unsupported.get("cfg_scale") is not None:
         raise ValueError("sampling_guided: cfg_scale= is not built for guided runs (labels= alone conditions the run)")
     unsupported.pop("cfg_scale", None)

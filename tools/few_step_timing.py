@@ -10,7 +10,9 @@ the per-step time of the plain sampler's captured step (dws_sampler_steps) and t
 Capture + instantiate alone: `capture_cost`.  `--legs edit_c4,edit_c2` (not in the default list): the unedited schedule
 call against the same call with a half-clip continuation mask (dws_sampler_run_edit), alternating in one process.
 `--legs resample_c4` (not in the default list either): that edited call against the same call with resample=(2, 2)
-(dws_sampler_run_program: 10 network evaluations and 2 jumps for S = 6), alternating in one process."""
+(dws_sampler_run_program: 10 network evaluations and 2 jumps for S = 6), alternating in one process.
+`--legs ragged_c2` (not in the default list): config 2 under bf16x6, the DDIM step without lengths, with
+lengths = [L] * B and with a spread of lengths down to L / 2, alternating in one process (`ragged_leg`)."""
 import argparse
 import json
 import os
@@ -235,6 +237,48 @@ def resample_leg(name, cfg_name, precision, S, repeats, jump=2, resamples=2):
     return rec
 
 
+def ragged_leg(name, cfg_name, precision, S, repeats):
+    """The cost of per-clip lengths (dws_model_set_lengths) per step: in one process and alternating, the DDIM call
+    without lengths (the yardstick: it launches exactly the kernels it launched before the feature), with
+    lengths = [L] * B (every sealing launch is in the step and finds an empty range) and with a spread of lengths from L
+    down to L / 2 (a quarter of the batch is padding); every call a new seed.  Per step = call / S.  The sealing kernel
+    rewrites only the next layer's dilation behind a clip's end; DWS_RAGGED_FULL_TAIL=1 in the environment of the process
+    makes it rewrite the whole tail instead (the A/B of the two forms: run the leg once with and once without)."""
+    from benchlib.configs import CONFIGS, build_model
+    from diffwave_sashimi_amd.sampling import calc_diffusion_hyperparams, sampling_ddim
+    cfg = CONFIGS[cfg_name]
+    dev = torch.device("cuda")
+    net = build_model(cfg, dev)
+    if precision != "f32":
+        net.set_option("precision", precision)
+    B, L = cfg["B"], cfg["L"]
+    size = (B, 1, L)
+    d = cfg["diffusion"]
+    dh = calc_diffusion_hyperparams(d["T"], d["beta_0"], d["beta_T"])
+    spread = [L - (L // 2) * b // max(B - 1, 1) for b in range(B)]
+    variants = {"plain": None, "full_lengths": [L] * B, "spread_lengths": spread}
+    call = lambda seed, lens: sampling_ddim(net, size, dh, S, 0.0, None, seed=seed, lengths=lens)
+    for lens in variants.values():                          # warm-up: code objects, step table, both graphs
+        call(1, lens), call(2, lens)
+    times = {k: [] for k in variants}
+    for i in range(repeats):
+        for k, lens in variants.items():
+            times[k].append(_clock(lambda: call(100 + i, lens)) / S)
+    med = {k: statistics.median(v) for k, v in times.items()}
+    rec = dict(leg=name, config=cfg_name, precision=precision, S=S, B=B, L=L,
+               reach="full tail" if os.environ.get("DWS_RAGGED_FULL_TAIL") else "next dilation",
+               padded_share_spread=round(1.0 - sum(spread) / float(B * L), 4),
+               per_step={k: _stats(v) for k, v in times.items()},
+               full_minus_plain_ms=round(med["full_lengths"] - med["plain"], 4),
+               spread_minus_plain_ms=round(med["spread_lengths"] - med["plain"], 4),
+               spread_over_plain=round(med["spread_lengths"] / med["plain"], 5),
+               plain_spread_ms=round(max(times["plain"]) - min(times["plain"]), 4),
+               graphs_after_repeats=int(net.read_tap("sampler_graphs", (1,)).item()))
+    del net
+    torch.cuda.empty_cache()
+    return rec
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--repeats", type=int, default=5)
@@ -252,6 +296,8 @@ def main():
                                     args.repeats),
         "resample_c4": lambda: resample_leg("config4 aligned S=6 f32, continuation, resample=(2,2)",
                                             "unet_d32_n6_T50_cond", "f32", 6, args.repeats),
+        "ragged_c2": lambda: ragged_leg("config2 DDIM S=10 bf16x6, per-clip lengths", "wnet_h256_d36_T200", "bf16x6", 10,
+                                        args.repeats),
         "capture": lambda: [capture_cost("unet_d32_n6_T50_cond", "f32", "ddim", 6, args.repeats),
                             capture_cost("wnet_h256_d36_T200", "bf16x6", "ddim", 50, args.repeats)],
     }
