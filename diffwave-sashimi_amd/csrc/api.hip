@@ -81,10 +81,61 @@ int dws_model::set_labels(const int32_t* labels, int64_t nB, hipStream_t s) {
     return DWS_OK;
 }
 
-// Backbones without per-clip lengths (SaShiMi: its stage buffers need a mask in front of every S4 convolution).
-int dws_model::set_lengths(const int32_t* lengths, const int32_t*, int64_t, hipStream_t) {
-    if (!lengths) return DWS_OK;
-    return dws::set_error(DWS_ERR_UNSUPPORTED, "per-clip lengths (dws_model_set_lengths) are built for the WaveNet backbone only");
+// Per-clip lengths of the prepared batch (dws_model_set_lengths), for both backbones: host validation, the int32 [2][B]
+// device table (lengths, mel frames) through the pinned ring, and the conditioner terms evaluated again from the kept mel
+// whenever the table changes -- a forward never runs with terms built for other lengths.
+int dws_model::check_ragged_mel(const int32_t* frames, int64_t Bm, int64_t Tmel) const {
+    DWS_CHECK(Bm == B, DWS_ERR_INVALID, "a shared mel (Bm = %lld) with per-clip lengths: a ragged batch has a mel per clip",
+              (long long)Bm);
+    for (int64_t b = 0; b < B; ++b)
+        DWS_CHECK(frames[b] <= Tmel, DWS_ERR_INVALID, "mel_frames[%lld] = %d frames, the mel holds %lld", (long long)b,
+                  frames[b], (long long)Tmel);
+    return DWS_OK;
+}
+
+int dws_model::set_lengths(const int32_t* lengths, const int32_t* mel_frames, int64_t nB, hipStream_t s) {
+    if (!lengths) {
+        if (!ragged()) return DWS_OK;
+        lengths_host.clear(); frames_host.clear();
+        if (dirty && cond_batch() > 0) DWS_TRY(commit(s));   // (drops the installed mel: nothing to re-evaluate below)
+        if (cond_batch() > 0) DWS_TRY(reeval_condition(s));  // the terms were built under the old frame counts
+        return DWS_OK;
+    }
+    DWS_CHECK(B > 0, DWS_ERR_STATE, "dws_model_set_lengths before dws_model_prepare");
+    DWS_CHECK(nB == B, DWS_ERR_INVALID, "dws_model_set_lengths: %lld lengths for a prepared batch of %lld", (long long)nB, (long long)B);
+    DWS_CHECK(!smp.cfg_on, DWS_ERR_UNSUPPORTED, "per-clip lengths are not built for classifier-free guidance (dws_sampler_set_cfg is on)");
+    int64_t hop = 0, mult = 1;
+    DWS_TRY(ragged_rule(&hop, &mult));
+    std::vector<int32_t> fr((size_t)B, 1);
+    for (int64_t b = 0; b < B; ++b) {
+        // (SaShiMi: the clip's length at a pooled stage is lengths[b] / the factors above it, an integer only then)
+        DWS_CHECK(lengths[b] % mult == 0, DWS_ERR_UNSUPPORTED,
+                  "dws_model_set_lengths: lengths[%lld] = %d is not a multiple of %lld, the product of the pooling factors",
+                  (long long)b, lengths[b], (long long)mult);
+        DWS_CHECK(lengths[b] >= 1 && lengths[b] <= L, DWS_ERR_INVALID, "dws_model_set_lengths: lengths[%lld] = %d (needs 1 .. L = %lld)",
+                  (long long)b, lengths[b], (long long)L);
+        if (hop == 0) continue;
+        const int64_t f = mel_frames ? mel_frames[b] : (lengths[b] + hop - 1) / hop;
+        DWS_CHECK(f >= 1 && f <= INT32_MAX && hop * f >= lengths[b], DWS_ERR_INVALID,
+                  "dws_model_set_lengths: mel_frames[%lld] = %lld frames of %lld samples for a clip of %d", (long long)b,
+                  (long long)f, (long long)hop, lengths[b]);
+        fr[b] = (int32_t)f;
+    }
+    if (cond_batch() > 0) DWS_TRY(check_ragged_mel(fr.data(), cond_batch(), cond_frames()));
+    if (lengths_host.size() == (size_t)B && std::memcmp(lengths_host.data(), lengths, (size_t)B * 4) == 0 && frames_host == fr)
+        return DWS_OK;     // the table already installed
+    if (dirty && cond_batch() > 0) DWS_TRY(commit(s));   // (drops the installed mel: nothing to re-evaluate below)
+    DWS_TRY(lengths_dev.ensure((size_t)B * 8));
+    int32_t* h = nullptr;
+    DWS_TRY(length_ring.acquire((size_t)B * 8, (void**)&h));
+    std::memcpy(h, lengths, (size_t)B * 4);
+    std::memcpy(h + B, fr.data(), (size_t)B * 4);
+    DWS_HIP(hipMemcpyAsync(lengths_dev.p, h, (size_t)B * 8, hipMemcpyHostToDevice, s));
+    DWS_TRY(length_ring.commit(s));
+    lengths_host.assign(lengths, lengths + B);
+    frames_host = fr;
+    if (cond_batch() > 0) DWS_TRY(reeval_condition(s));
+    return DWS_OK;
 }
 
 // The grid of a per-clip launch has one row per clip: at most 65535 clips.

@@ -24,6 +24,10 @@ struct FftConvArgs {
     float* rowsum;      // also rowsum[b * rowsum_bstride + h] = sum_l g[b,h,l] (the adjoint pass: d fc_t(e)[b,h] = sum_l du[b,h,l],
     int rowsum_bstride; //   `sashimi.py:151`); even plans only (fftconv_rowsum_supported): a workgroup owns the whole row
     unsigned long long* trace;   // DWS_FFT_TRACE=1 only: s_memtime stamps [workgroup][wave][row][slot] (fftconv_kernels.hip)
+    // ragged batches (dws_model_set_lengths; null = off, the kernel as it is without them): row (b, h) is convolved as if u
+    // were zero on [lengths[b] / len_div, L) -- sealed on the load side, whatever the padding of u holds (sampling path only)
+    const int32_t* lengths;      // [B] device table
+    int len_div;                 // the pooling factors above this stage
 };
 
 // dK_f partials of the convolution's kernel gradient: part[bs][h][k] = sum_{b in chunk bs} conj(U_b[k]) * dA_b[k],
@@ -53,6 +57,10 @@ struct FftConvSegArgs {
     const c2* kfb[3];
     const c2* kfs[3];  // [H][3]
     int B, H, L;
+    // ragged batches, as in FftConvArgs (null = off); skip_pad: a workgroup whose output segment lies wholly behind its
+    // clip's end returns at once -- that part of g then keeps whatever it held
+    const int32_t* lengths;
+    int len_div, skip_pad;
 };
 constexpr int FFTCONV_SEG_LOG2M = 14;
 bool fftconv_seg_supported(int L, int taps);

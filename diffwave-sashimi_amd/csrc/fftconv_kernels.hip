@@ -188,9 +188,11 @@ __device__ __forceinline__ void fft_inverse(c2* X, const c2* tw, const FftTw<LOG
 // the rest of the M-point row is zero.  Even sizes: the top radix-16 pass runs on registers (a thread's 16 points are
 // g + (M/16) r, of which r >= 8 are padding and never loaded) and only its result goes to LDS; odd sizes stage the row
 // in LDS first.  The caller must have passed a barrier since the last read of X.
+// half_last (ragged batches): the row ends in the middle of its last packed point n_valid - 1, whose second sample counts as
+// zero -- a select on the loaded value, so that nothing stored behind the row's end, a NaN included, enters the transform.
 template <int LOG2M, int NG, class ST = NoStamp>
 __device__ __forceinline__ void fft_forward_global(c2* X, const c2* __restrict__ src, int n_valid, const c2* tw,
-                                                   const FftTw<LOG2M, NG>& W, int tid, ST&& st = ST()) {
+                                                   const FftTw<LOG2M, NG>& W, int tid, ST&& st = ST(), bool half_last = false) {
     constexpr int M = 1 << LOG2M, G = M / 16, THREADS = G / NG;
     if constexpr (!FftPlan<LOG2M>::ODD) {
 #pragma unroll
@@ -199,7 +201,10 @@ __device__ __forceinline__ void fft_forward_global(c2* X, const c2* __restrict__
             const int g = tid + i * THREADS;
             c2 x[16];
 #pragma unroll
-            for (int r = 0; r < 8; ++r) x[r] = (g + G * r < n_valid) ? src[g + G * r] : mk(0.f, 0.f);
+            for (int r = 0; r < 8; ++r) {
+                x[r] = (g + G * r < n_valid) ? src[g + G * r] : mk(0.f, 0.f);
+                if (half_last && g + G * r == n_valid - 1) x[r].y = 0.f;
+            }
 #pragma unroll
             for (int r = 8; r < 16; ++r) x[r] = mk(0.f, 0.f);
             if (i == 0) st.loads_landed();
@@ -211,7 +216,11 @@ __device__ __forceinline__ void fft_forward_global(c2* X, const c2* __restrict__
         st();
         fft_forward_from<LOG2M, NG, 1>(X, tw, W, tid, st);
     } else {
-        for (int j = tid; j < M; j += THREADS) X[pidx(j)] = (j < n_valid) ? src[j] : mk(0.f, 0.f);
+        for (int j = tid; j < M; j += THREADS) {
+            c2 v = (j < n_valid) ? src[j] : mk(0.f, 0.f);
+            if (half_last && j == n_valid - 1) v.y = 0.f;
+            X[pidx(j)] = v;
+        }
         __syncthreads();
         fft_forward<LOG2M, NG>(X, tw, W, tid);
     }
@@ -238,10 +247,15 @@ struct RowSchedule {
 // instead of eight and nine.
 // RSUM (training, the adjoint pass): the row's sum over its L outputs leaves with it (FftConvArgs::rowsum) -- the values are in
 // registers in the bottom pass, a separate rowsum_bc launch read the whole tensor again (1.5 ms of a C5 step).
-template <int LOG2M, int THREADS, bool TRACE = false, bool FUSED = false, bool RSUM = false>
+// RAG (ragged batches, FftConvArgs::lengths): the row's valid length Lv = min(L, lengths[b] / len_div) bounds what the forward
+// transform LOADS -- the descriptor ends at Lv rounded up to a whole packed point, and an odd Lv zeroes the second sample of
+// the last point by a select in registers.  The D u term, the GELU and the stores keep the whole row: what they add lands
+// behind the clip's end only.  The instances without it are the kernel as it was.
+template <int LOG2M, int THREADS, bool TRACE = false, bool FUSED = false, bool RSUM = false, bool RAG = false>
 __global__ __launch_bounds__(THREADS) void fftconv_kernel(FftConvArgs a) {
     using P = FftPlan<LOG2M>;
     static_assert(!TRACE || !P::ODD, "phase stamps: even sizes only");
+    static_assert(!RAG || (!TRACE && !RSUM), "per-clip lengths: the sampling path");
     static_assert(!FUSED || (P::TAIL4 && !P::ODD && THREADS == (1 << LOG2M) / 16), "fused tail: shape");
     constexpr int M = 1 << LOG2M;
     constexpr bool DIRECT = !P::ODD;
@@ -277,6 +291,8 @@ __global__ __launch_bounds__(THREADS) void fftconv_kernel(FftConvArgs a) {
         const int h = row / a.B, b = row % a.B;
         const size_t off = ((size_t)b * a.H + h) * L;
         const c2* __restrict__ u2 = reinterpret_cast<const c2*>(a.u + off);
+        int Lv = L;       // (uniform over the workgroup: scalar registers)
+        if constexpr (RAG) Lv = min(L, max(a.lengths[b] / a.len_div, 0));
         if constexpr (TRACE) {
             st.slot = ri < FFT_TRACE_ROWS ? a.trace + (((size_t)blockIdx.x * (THREADS / 64) + __builtin_amdgcn_readfirstlane(tid >> 6)) * FFT_TRACE_ROWS + ri) *
                                                           FFT_TRACE_SLOTS
@@ -290,11 +306,16 @@ __global__ __launch_bounds__(THREADS) void fftconv_kernel(FftConvArgs a) {
         if constexpr (DIRECT) {
             static_assert(NG == 1, "one block of 16 positions per thread");
             // top pass on registers (fft_forward_global's); buffer loads: a point beyond the row's L/2 comes back as zero
-            __amdgpu_buffer_rsrc_t rU = __builtin_amdgcn_make_buffer_rsrc((void*)(a.u + off), 0, L * 4, 0x00020000);
+            // (RAG: whole packed points only, (Lv + 1) / 2 of them <= L / 2 -- no 8-byte load straddles the descriptor's end)
+            __amdgpu_buffer_rsrc_t rU = __builtin_amdgcn_make_buffer_rsrc((void*)(a.u + off), 0, RAG ? ((Lv + 1) >> 1) * 8 : L * 4, 0x00020000);
             c2 x[16];
 #pragma unroll
             for (int r = 0; r < 8; ++r)
                 x[r] = __builtin_bit_cast(c2, __builtin_amdgcn_raw_buffer_load_b64(rU, (tid + (M / 16) * r) * 8, 0, 0));
+            if constexpr (RAG) {
+#pragma unroll
+                for (int r = 0; r < 8; ++r) x[r].y = (2 * (tid + (M / 16) * r) + 1 < Lv) ? x[r].y : 0.f;
+            }
             const c2 ph1 = fwd_twiddle<LOG2M, 1, !FUSED>(a.tw, opaque(tid));   // the next pass's base twiddle, a pass ahead
             __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
@@ -316,7 +337,7 @@ __global__ __launch_bounds__(THREADS) void fftconv_kernel(FftConvArgs a) {
                                                     a.kfs + (size_t)h * 3, opaque(tid), csign, &pre);
             if constexpr (FUSED) th_inv = FftTw<LOG2M, 1>::template theta_at<P::N16 - 1>(a.tw, opaque(tid));
         } else {
-            fft_forward_global<LOG2M, NG>(X, u2, Lc, a.tw, W, tid, st);
+            fft_forward_global<LOG2M, NG>(X, u2, RAG ? (Lv + 1) >> 1 : Lc, a.tw, W, tid, st, RAG && (Lv & 1));
             static_assert(NG == 1, "one block of 16 positions per thread");
             pass_tail_pointwise<LOG2M, true, false>(X, a.tw, a.twp, a.kfa + (size_t)h * (M / 2), a.kfb + (size_t)h * (M / 2),
                                                     a.kfs + (size_t)h * 3, opaque(tid), csign);
@@ -664,6 +685,11 @@ __global__ __launch_bounds__(THREADS) void fftconv_seg_kernel(FftConvSegArgs a) 
     const int L = a.L, nseg = (L + S - 1) / S;
     const size_t off = ((size_t)b * a.H + h) * L;
     const c2* __restrict__ u2 = reinterpret_cast<const c2*>(a.u + off);   // L even: samples (2i, 2i+1)
+    // ragged batches: the row counts as zero from Lv on (uniform over the workgroup).  An output segment wholly behind it
+    // is padding: the whole workgroup leaves here, before its first barrier.
+    const int Lv = a.lengths ? min(L, max(a.lengths[b] / a.len_div, 0)) : L;
+    if (a.skip_pad && j * S >= Lv) return;
+    const int Lvc = (Lv + 1) >> 1;     // packed points that hold a valid sample; the last one only its first when Lv is odd
     FftTw<LOG2M, NG> W;
     W.load(a.tw, tid0);
     c2 ya[NP], yb[NP];
@@ -676,8 +702,9 @@ __global__ __launch_bounds__(THREADS) void fftconv_seg_kernel(FftConvSegArgs a) 
         const int sj = j + (t == 0 ? 0 : t == 1 ? -1 : 1);
         if (sj < 0 || sj >= nseg) continue;        // uniform over the block
         int tid = opaque(tid0);
-        const int c0 = sj * (S / 2), cn = min(S / 2, L / 2 - c0);   // packed points of this segment that exist
-        fft_forward_global<LOG2M, NG>(X, u2 + c0, cn, a.tw, W, tid);
+        const int c0 = sj * (S / 2), cn = min(S / 2, Lvc - c0);   // packed points of this segment that exist (and are valid)
+        if (cn <= 0) continue;                     // wholly behind the clip's end: contributes zero (uniform too)
+        fft_forward_global<LOG2M, NG>(X, u2 + c0, cn, a.tw, W, tid, NoStamp(), (Lv & 1) && c0 + cn == Lvc);
         tid = opaque(tid0);
         const c2* __restrict__ kfa = a.kfa[t] + (size_t)h * (M / 2);
         const c2* __restrict__ kfb = a.kfb[t] + (size_t)h * (M / 2);
@@ -900,6 +927,14 @@ static int launch_fc(const FftConvArgs& a_in, hipStream_t s) {
     DWS_TRY((kernel_setup<fftconv_kernel<LOG2M, C::THREADS, false, C::FUSED>>(C::LDS)));
     DWS_TRY((kernel_setup<fftconv_kernel<LOG2M, C::THREADS>>(C::LDS)));
     const FftConvArgs& a = a_in;
+    if (a.lengths) {     // ragged batches: the length-aware instance of the same plan; without a table the kernels above, untouched
+        DWS_CHECK(!a.rowsum && !a.pre && !a.conj_k && !a.no_act && a.len_div >= 1, DWS_ERR_UNSUPPORTED,
+                  "fftconv: per-clip lengths are built for the sampling path (len_div = %d)", a.len_div);
+        DWS_TRY((kernel_setup<fftconv_kernel<LOG2M, C::THREADS, false, C::FUSED, false, true>>(C::LDS)));
+        DWS_TRY((kernel_setup<fftconv_kernel<LOG2M, C::THREADS, false, false, false, true>>(C::LDS)));
+        kern = fused ? fftconv_kernel<LOG2M, C::THREADS, false, C::FUSED, false, true>
+                     : fftconv_kernel<LOG2M, C::THREADS, false, false, false, true>;
+    }
     // one resident workgroup per LDS slot of every CU walks several rows (RowSchedule); small rows: one row per block
     // (the persistent schedule from M = 4096 / 1024 up: 32.0-32.2 vs 31.7-31.9 us and 16.4 vs 16.3 us, no gain)
     const int rows = a.B * a.H;
@@ -907,7 +942,7 @@ static int launch_fc(const FftConvArgs& a_in, hipStream_t s) {
     const int nwg = (std::min(rows, LOG2M >= 13 ? slots : rows) + 7) / 8 * 8;
     if constexpr (!FftPlan<LOG2M>::ODD) {
         static const bool trace = getenv("DWS_FFT_TRACE") != nullptr;
-        if (trace) return fft_trace_launch<LOG2M>(a, nwg, s);
+        if (trace && !a.lengths) return fft_trace_launch<LOG2M>(a, nwg, s);
     }
     hipLaunchKernelGGL(kern, dim3(nwg), dim3(C::THREADS), C::LDS, s, a);
     return DWS_OK;

@@ -64,6 +64,9 @@ int launch_iota_f32(float* out, int n, hipStream_t s);   // wavenet_kernels.hip
 // (+ *step_idx * pt_tstride)]: the value that makes the next layer's h = x + fc_t(e) zero.
 int launch_wn_mask_tail(float* x, const int32_t* lengths, int B, int C, int L, int reach, const float* pt, int pt_bstride,
                         const int* step_idx, int pt_tstride, hipStream_t s);
+// the same kernel on rows `row_stride` floats apart whose clip ends at lengths[b] / div (a pooled SaShiMi stage; the
+// zero-padded rocFFT input rows): x[(b C + c) row_stride + (lengths[b] / div .. L)) = 0.0f
+int launch_mask_tail_rows(float* x, const int32_t* lengths, int B, int C, int L, size_t row_stride, int div, hipStream_t s);
 // class conditioning (wavenet_kernels.hip): out[r][:] = in[r / rep][:] + table[lab ? lab[r % nlab] : K][:], one fp32 add per
 // element (in place when rep == 1 and out == in); and its adjoint dtable[c][:] = sum over b with lab[b] == c of de[b][:], in
 // ascending b, rows of absent classes exactly zero
@@ -160,7 +163,17 @@ struct dws_model {
     bool ragged() const { return !lengths_host.empty(); }
     const int32_t* lengths_ptr() const { return static_cast<const int32_t*>(lengths_dev.p); }
     const int32_t* frames_ptr() const { return lengths_ptr() + B; }
-    virtual int set_lengths(const int32_t* lengths, const int32_t* mel_frames, int64_t nB, hipStream_t s);
+    // validation, pinned-ring upload and re-evaluation of the conditioner terms, shared by the backbones (api.hip)
+    int set_lengths(const int32_t* lengths, const int32_t* mel_frames, int64_t nB, hipStream_t s);
+    // a mel beside per-clip lengths: one mel per clip, and every clip's frames inside it
+    int check_ragged_mel(const int32_t* frames, int64_t Bm, int64_t Tmel) const;
+    // what set_lengths asks of a backbone: the samples per mel frame (0: unconditional) and the number every length must
+    // be a multiple of (SaShiMi: the product of its pooling factors; 1: any length) ...
+    virtual int ragged_rule(int64_t* hop, int64_t* multiple) const = 0;
+    // ... the installed mel (batch, frames; 0: none) and its conditioner terms evaluated again from the kept copy
+    virtual int64_t cond_batch() const = 0;
+    virtual int64_t cond_frames() const = 0;
+    virtual int reeval_condition(hipStream_t s) = 0;
 
     // ---- staged gradient hand-over (data-parallel overlap, dws_model_set_grad_sinks): the host names a destination and a
     // GROUP (its all-reduce bucket) per parameter; backward() copies a group's gradients to their destinations (one launch)

@@ -621,7 +621,7 @@ struct SashimiModel : dws_model, S4Workspace {
         for (int p : pool) span *= p;
         DWS_CHECK(nL % span == 0, DWS_ERR_INVALID, "sashimi: input length %lld is not divisible by the pooling factors (%d)",
                   (long long)nL, span);
-        if (nB != B || nL != L) { drop_graph(); melBm = 0; trained_fwd = false; }
+        if (nB != B || nL != L) { drop_graph(); melBm = 0; trained_fwd = false; lengths_host.clear(); frames_host.clear(); }
         if (nL != L) {
             // variable-length run (s4.py:1387): every stage length scales with the input; the S4 kernels keep their
             // own length (the `L` buffers) and contribute min(run, l_max) taps per direction
@@ -681,31 +681,74 @@ struct SashimiModel : dws_model, S4Workspace {
         DWS_CHECK(cond, DWS_ERR_INVALID, "set_condition on an unconditional model (`sashimi.py:161`)");
         DWS_CHECK(B > 0, DWS_ERR_STATE, "set_condition before prepare");
         DWS_CHECK(Bm == 1 || Bm == B, DWS_ERR_INVALID, "mel batch %lld must be 1 or B=%lld", (long long)Bm, (long long)B);
+        if (ragged()) DWS_TRY(check_ragged_mel(frames_host.data(), Bm, Tmel));
         if (dirty) DWS_TRY(commit(s));
+        const int T0 = mel_upsampled_len((int)Tmel, d.mel_upsample[0]), T1 = mel_upsampled_len(T0, d.mel_upsample[1]);
+        // pooled stages take the FIRST L_stage upsampled frames (sashimi.py:170-172): a truncation
+        for (auto* l : all)
+            DWS_CHECK(l->kind != L_BLOCK || T1 >= l->L, DWS_ERR_INVALID, "upsampled mel length %d < L=%d (`sashimi.py:169`)", T1, l->L);
+        // (the kept copy first: with per-clip lengths on, the terms are evaluated from it, here and again by set_lengths)
+        if (mel != mel_in.p) {
+            DWS_TRY(mel_in.ensure((size_t)Bm * MB * Tmel * 4));
+            DWS_HIP(hipMemcpyAsync(mel_in.p, mel, (size_t)Bm * MB * Tmel * 4, hipMemcpyDeviceToDevice, s));
+        }
+        mel_T = (int)Tmel;
+        melBm = 0;   // (invalid while a launch below can still fail)
+        DWS_TRY(eval_condition(mel, Bm, s));
+        melBm = Bm;
+        return DWS_OK;
+    }
+
+    // the conditioner terms of every block from `mel` [Bm][MB][mel_T].  Per-clip lengths on: clip b's mel frames >= frames_b
+    // and the first upsampler's output at positions >= s0 frames_b count as zero, as in the WaveNet model -- the second
+    // upsampler would otherwise read leaky_relu(bias + ..) != 0 there for the last s1 / 2 samples of the clip.  The 1x1 is
+    // pointwise and a pooled stage takes the first L_stage columns: clip b's stage reads columns < len_b / div of the
+    // upsampling of its own frames.
+    int eval_condition(const float* mel, int64_t Bm, hipStream_t s) {
         const int s0 = d.mel_upsample[0], s1 = d.mel_upsample[1];
-        const int T0 = mel_upsampled_len((int)Tmel, s0), T1 = mel_upsampled_len(T0, s1);
+        const int T0 = mel_upsampled_len(mel_T, s0), T1 = mel_upsampled_len(T0, s1);
+        const int32_t* fr = ragged() ? frames_ptr() : nullptr;
         DevBuf& u0 = mel_u0;
         DevBuf& u1 = mel_u1;
         DWS_TRY(u0.ensure((size_t)Bm * MB * T0 * 4));
         DWS_TRY(u1.ensure((size_t)Bm * MB * T1 * 4));
         for (auto* l : all) {
             if (l->kind != L_BLOCK) continue;
-            // pooled stages take the FIRST L_stage upsampled frames (sashimi.py:170-172): a truncation
-            DWS_CHECK(T1 >= l->L, DWS_ERR_INVALID, "upsampled mel length %d < L=%d (`sashimi.py:169`)", T1, l->L);
             DWS_TRY(l->melc.ensure((size_t)Bm * l->H * l->L * 4));
             DWS_TRY(launch_mel_upsample(mel, l->melW0.f(), P(l->prefix + ".upsample_conv2d.0.bias"), u0.f(), (int)Bm, MB,
-                                        (int)Tmel, T0, s0, 0.4f, s));
+                                        mel_T, T0, s0, 0.4f, s, fr, 1));
             DWS_TRY(launch_mel_upsample(u0.f(), l->melW1.f(), P(l->prefix + ".upsample_conv2d.1.bias"), u1.f(), (int)Bm, MB,
-                                        T0, T1, s1, 0.4f, s));
+                                        T0, T1, s1, 0.4f, s, fr, s0));
             DWS_TRY(launch_conv1x1_trunc(u1.f(), l->melWc.f(), P(l->prefix + ".mel_conv.conv.bias"), l->melc.f(), (int)Bm,
                                          MB, l->H, T1, l->L, s));
         }
-        DWS_TRY(mel_in.ensure((size_t)Bm * MB * Tmel * 4));
-        DWS_HIP(hipMemcpyAsync(mel_in.p, mel, (size_t)Bm * MB * Tmel * 4, hipMemcpyDeviceToDevice, s));
-        mel_T = (int)Tmel;
+        return DWS_OK;
+    }
+
+    // dws_model::set_lengths (api.hip): every length a multiple of the pooling factors' product -- the clip's length at a
+    // pooled stage is lengths[b] / (the factors above it); frames of hop samples; the terms again from the kept mel
+    int pool_span() const {
+        int span = 1;
+        for (int p : pool) span *= p;
+        return span;
+    }
+    int ragged_rule(int64_t* hop, int64_t* multiple) const override {
+        *hop = cond ? (int64_t)d.mel_upsample[0] * d.mel_upsample[1] : 0;
+        *multiple = pool_span();
+        return DWS_OK;
+    }
+    int64_t cond_batch() const override { return melBm; }
+    int64_t cond_frames() const override { return mel_T; }
+    int reeval_condition(hipStream_t s) override {
+        const int64_t Bm = melBm;
+        melBm = 0;
+        DWS_TRY(eval_condition(mel_in.f(), Bm, s));
         melBm = Bm;
         return DWS_OK;
     }
+    // forward(): the length table and a stage's divisor for the S4 convolutions (null while lengths are off)
+    const int32_t* conv_lengths() const { return ragged() ? lengths_ptr() : nullptr; }
+    int stage_div(const SLayer* l) const { return (int)(L / l->L); }
 
     // The tail of `l` can also produce the S4 input of the block that runs next (LN1 + step embedding fused into its
     // epilogue) when that block sits on the same stage and both run the fused paths.
@@ -757,6 +800,7 @@ struct SashimiModel : dws_model, S4Workspace {
             fa.tw = (const c2*)t->tw.p; fa.twp = (const c2*)t->twp.p;
             fa.kfa = (const c2*)l->kfa_v; fa.kfb = (const c2*)l->kfb_v; fa.kfs = (const c2*)l->kfs_v;
             fa.B = nB; fa.H = H; fa.L = Ls;
+            fa.lengths = conv_lengths(); fa.len_div = stage_div(l);
             DWS_TRY(launch_fftconv(l->log2m, fa, s));
             return run_tail(l, st, x, addend, next, s);
         }
@@ -772,11 +816,16 @@ struct SashimiModel : dws_model, S4Workspace {
             fa.kfa[1] = (const c2*)l->kfa_c.p; fa.kfb[1] = (const c2*)l->kfb_c.p; fa.kfs[1] = (const c2*)l->kfs_c.p;
             fa.kfa[2] = (const c2*)l->kfa_a.p; fa.kfb[2] = (const c2*)l->kfb_a.p; fa.kfs[2] = (const c2*)l->kfs_a.p;
             fa.B = nB; fa.H = H; fa.L = Ls;
+            // (DWS_RAGGED_SEG_NO_SKIP=1: workgroups of wholly padded output segments run too -- the same-box A/B)
+            static const bool skip_pad = getenv("DWS_RAGGED_SEG_NO_SKIP") == nullptr;
+            fa.lengths = conv_lengths(); fa.len_div = stage_div(l); fa.skip_pad = (fa.lengths && skip_pad) ? 1 : 0;
             DWS_TRY(launch_fftconv_seg(fa, s));
             return run_tail(l, st, x, addend, next, s);
         }
         DWS_TRY(launch_ln(x, P(p + ".norm1.m"), P(p + ".norm1.s"), pt_base() + l->pt_off, pt_bstride(), st->U.f(), nB, H, Ls,
                           (size_t)2 * Ls, s, step_idx, pt_tstride()));
+        // ragged batches: the transform's input rows sealed behind each clip's own end (stores: whatever the LayerNorm wrote there)
+        if (ragged()) DWS_TRY(launch_mask_tail_rows(st->U.f(), lengths_ptr(), nB, H, Ls, (size_t)2 * Ls, stage_div(l), s));
         {
             ProfileScope ps("rocfft_r2c", s);
             DWS_TRY(fft.exec(0, 2 * Ls, nB * H, st->U.p, st->Uf.p, s));
@@ -1022,6 +1071,8 @@ struct SashimiModel : dws_model, S4Workspace {
         }
         last_x = x;
         DWS_TRY(final_stage(x, out, nullptr, s, final_ln_fused));
+        // ragged batches: exact 0.0f behind every clip's own end, whatever the padded positions computed
+        if (ragged()) DWS_TRY(launch_wn_mask_tail(out, lengths_ptr(), (int)B, Cout, (int)L, -1, nullptr, 0, nullptr, 0, s));
         DWS_HIP(hipGetLastError());
         return DWS_OK;
     }
@@ -1242,6 +1293,7 @@ struct SashimiModel : dws_model, S4Workspace {
 
     int forward_train(const float* audio, const float* steps, float* out, hipStream_t s) override {
         DWS_CHECK(B > 0, DWS_ERR_STATE, "forward before prepare");
+        DWS_CHECK(!ragged(), DWS_ERR_UNSUPPORTED, "training with per-clip lengths (dws_model_set_lengths) is not built");
         DWS_CHECK(!f16x3, DWS_ERR_UNSUPPORTED,
                   "training runs with precision=f32 or bf16x6 (gradients span too many binades for the fixed scales of the fp16 split)");
         keep_cauchy = true;

@@ -301,17 +301,19 @@ int launch_init_conv(const float* audio, const float* W, const float* bias, floa
 // the padding must hold the value that makes h zero (x + (-x) is exact), not zero itself.  Stores only: whatever the
 // padding held, a NaN included, is gone.  16-byte stores where the address allows, dwords at both ragged edges.
 // A clip with len_b == L has an empty range.
+// Rows are `row_stride` floats apart and the clip ends at lengths[b] / div: L and 1 for a WaveNet tensor; a pooled SaShiMi
+// stage has div = the pooling factors above it, its rocFFT input rows are 2 L apart.
 // ---------------------------------------------------------------------------
 __global__ __launch_bounds__(64) void wn_mask_tail_kernel(float* __restrict__ x, const int32_t* __restrict__ lengths,
                                                           const float* __restrict__ pt, int pt_bstride,
                                                           const int* __restrict__ step_idx, int pt_tstride, int C, int L,
-                                                          int reach) {
+                                                          int reach, size_t row_stride, int div) {
     const int b = blockIdx.y, c = blockIdx.x, lane = threadIdx.x;
-    const int len = min(max(lengths[b], 0), L);
+    const int len = min(max(lengths[b] / div, 0), L);
     const int end = reach < 0 ? L : (int)min((int64_t)L, (int64_t)len + reach);
     if (len >= end) return;
     const float v = pt ? -pt[(size_t)b * pt_bstride + c + step_row_off(step_idx, pt_tstride)] : 0.f;
-    float* row = x + ((size_t)b * C + c) * L;
+    float* row = x + ((size_t)b * C + c) * row_stride;
     // dwords up to the first 16-byte border at or behind len, float4 groups, dwords of the last partial group
     const int head = (int)((4 - (((uintptr_t)(row + len) >> 2) & 3)) & 3);
     const int a0 = min(len + head, end);
@@ -327,7 +329,16 @@ int launch_wn_mask_tail(float* x, const int32_t* lengths, int B, int C, int L, i
                         const int* step_idx, int pt_tstride, hipStream_t s) {
     ProfileScope ps("wn_mask_tail", s);
     DWS_CHECK(B >= 1 && B <= 65535, DWS_ERR_UNSUPPORTED, "per-clip lengths: B = %d (the grid has one row per clip: 1 .. 65535)", B);
-    hipLaunchKernelGGL(wn_mask_tail_kernel, dim3(C, B), dim3(64), 0, s, x, lengths, pt, pt_bstride, step_idx, pt_tstride, C, L, reach);
+    hipLaunchKernelGGL(wn_mask_tail_kernel, dim3(C, B), dim3(64), 0, s, x, lengths, pt, pt_bstride, step_idx, pt_tstride, C, L, reach,
+                       (size_t)L, 1);
+    return DWS_OK;
+}
+
+int launch_mask_tail_rows(float* x, const int32_t* lengths, int B, int C, int L, size_t row_stride, int div, hipStream_t s) {
+    ProfileScope ps("wn_mask_tail", s);
+    DWS_CHECK(B >= 1 && B <= 65535, DWS_ERR_UNSUPPORTED, "per-clip lengths: B = %d (the grid has one row per clip: 1 .. 65535)", B);
+    DWS_CHECK(div >= 1 && row_stride >= (size_t)L, DWS_ERR_INVALID, "mask_tail_rows: div = %d, row stride %zu < L = %d", div, row_stride, L);
+    hipLaunchKernelGGL(wn_mask_tail_kernel, dim3(C, B), dim3(64), 0, s, x, lengths, nullptr, 0, nullptr, 0, C, L, -1, row_stride, div);
     return DWS_OK;
 }
 

@@ -361,16 +361,6 @@ struct WaveNetModel : dws_model {
         return DWS_OK;
     }
 
-    // a mel beside per-clip lengths: one mel per clip, and every clip's frames inside it
-    int check_ragged_mel(const int32_t* frames, int64_t Bm, int64_t Tmel) const {
-        DWS_CHECK(Bm == B, DWS_ERR_INVALID, "a shared mel (Bm = %lld) with per-clip lengths: a ragged batch has a mel per clip",
-                  (long long)Bm);
-        for (int64_t b = 0; b < B; ++b)
-            DWS_CHECK(frames[b] <= Tmel, DWS_ERR_INVALID, "mel_frames[%lld] = %d frames, the mel holds %lld", (long long)b,
-                      frames[b], (long long)Tmel);
-        return DWS_OK;
-    }
-
     // the conditioner terms of every layer from `mel` [Bm][MB][mel_T].  Per-clip lengths on: clip b's mel frames >= frames_b
     // and the first upsampler's output at positions >= s0 frames_b count as zero -- the second upsampler would otherwise
     // read leaky_relu(bias + ..) != 0 there for the last s1 / 2 samples of the clip.  melc is pointwise in the position.
@@ -393,53 +383,19 @@ struct WaveNetModel : dws_model {
         return DWS_OK;
     }
 
-    int set_lengths(const int32_t* lengths, const int32_t* mel_frames, int64_t nB, hipStream_t s) override {
-        if (!lengths) {
-            if (!ragged()) return DWS_OK;
-            lengths_host.clear(); frames_host.clear();
-            if (dirty && melBm > 0) DWS_TRY(commit(s));   // (drops the installed mel: nothing to re-evaluate below)
-            if (melBm > 0) {   // the terms were built under the old frame counts
-                const int64_t Bm = melBm;
-                melBm = 0;
-                DWS_TRY(eval_condition(mel_in.f(), Bm, s));
-                melBm = Bm;
-            }
-            return DWS_OK;
-        }
-        DWS_CHECK(B > 0, DWS_ERR_STATE, "dws_model_set_lengths before dws_model_prepare");
-        DWS_CHECK(nB == B, DWS_ERR_INVALID, "dws_model_set_lengths: %lld lengths for a prepared batch of %lld", (long long)nB, (long long)B);
-        DWS_CHECK(!smp.cfg_on, DWS_ERR_UNSUPPORTED, "per-clip lengths are not built for classifier-free guidance (dws_sampler_set_cfg is on)");
-        const int64_t hop = cond ? (int64_t)d.mel_upsample[0] * d.mel_upsample[1] : 1;
-        std::vector<int32_t> fr((size_t)B, 1);
-        for (int64_t b = 0; b < B; ++b) {
-            DWS_CHECK(lengths[b] >= 1 && lengths[b] <= L, DWS_ERR_INVALID, "dws_model_set_lengths: lengths[%lld] = %d (needs 1 .. L = %lld)",
-                      (long long)b, lengths[b], (long long)L);
-            if (!cond) continue;
-            const int64_t f = mel_frames ? mel_frames[b] : (lengths[b] + hop - 1) / hop;
-            DWS_CHECK(f >= 1 && f <= INT32_MAX && hop * f >= lengths[b], DWS_ERR_INVALID,
-                      "dws_model_set_lengths: mel_frames[%lld] = %lld frames of %lld samples for a clip of %d", (long long)b,
-                      (long long)f, (long long)hop, lengths[b]);
-            fr[b] = (int32_t)f;
-        }
-        if (melBm > 0) DWS_TRY(check_ragged_mel(fr.data(), melBm, mel_T));
-        if (lengths_host.size() == (size_t)B && std::memcmp(lengths_host.data(), lengths, (size_t)B * 4) == 0 && frames_host == fr)
-            return DWS_OK;     // the table already installed
-        if (dirty && melBm > 0) DWS_TRY(commit(s));   // (drops the installed mel: nothing to re-evaluate below)
-        DWS_TRY(lengths_dev.ensure((size_t)B * 8));
-        int32_t* h = nullptr;
-        DWS_TRY(length_ring.acquire((size_t)B * 8, (void**)&h));
-        std::memcpy(h, lengths, (size_t)B * 4);
-        std::memcpy(h + B, fr.data(), (size_t)B * 4);
-        DWS_HIP(hipMemcpyAsync(lengths_dev.p, h, (size_t)B * 8, hipMemcpyHostToDevice, s));
-        DWS_TRY(length_ring.commit(s));
-        lengths_host.assign(lengths, lengths + B);
-        frames_host = fr;
-        if (melBm > 0) {   // a forward never runs with conditioner terms built for other lengths
-            const int64_t Bm = melBm;
-            melBm = 0;
-            DWS_TRY(eval_condition(mel_in.f(), Bm, s));
-            melBm = Bm;
-        }
+    // dws_model::set_lengths (api.hip): any length; frames of hop samples; the terms again from the kept mel
+    int ragged_rule(int64_t* hop, int64_t* multiple) const override {
+        *hop = cond ? (int64_t)d.mel_upsample[0] * d.mel_upsample[1] : 0;
+        *multiple = 1;
+        return DWS_OK;
+    }
+    int64_t cond_batch() const override { return melBm; }
+    int64_t cond_frames() const override { return mel_T; }
+    int reeval_condition(hipStream_t s) override {
+        const int64_t Bm = melBm;
+        melBm = 0;
+        DWS_TRY(eval_condition(mel_in.f(), Bm, s));
+        melBm = Bm;
         return DWS_OK;
     }
 

@@ -268,6 +268,21 @@ def _check_mel_names(mel_names, mel_name, clip_seeds, seed, **others):
     return names
 
 
+def _check_ragged_hop(model_cfg, dataset_cfg):
+    """``generate.mel_names`` on SaShiMi, before a model is built (ValueError): an utterance is ``frames x hop_length``
+    samples long, and SaShiMi takes per-clip lengths that are multiples of the product of its pooling factors only (a
+    pooled stage holds length / factor samples) -- so the hop must be such a multiple.  WaveNet takes any hop."""
+    if model_cfg.get("_name_") != "sashimi":
+        return
+    from .models.sashimi import pool_span
+    span = pool_span(model_cfg.get("pool", [4, 4]))
+    hop = dataset_cfg["hop_length"]
+    if isinstance(hop, bool) or not isinstance(hop, (int, np.integer)) or hop < 1 or hop % span:
+        raise ValueError(f"generate.mel_names with model=sashimi: dataset.hop_length={hop!r} is not a multiple of {span}, "
+                         f"the product of model.pool={list(model_cfg.get('pool', [4, 4]))} (utterances of frames x hop "
+                         "samples must divide through every pooling stage)")
+
+
 def _load_clip(dataset_cfg, stem, audio_length, conditional):
     """``<dataset.data_path>/<stem>.wav`` as a [1, 1, audio_length] clip in [-1, 1], read as ``train.SpeechCommands``
     reads one (int16 / 32768, int32 / 2^31, float as it is; first channel).  Unconditional: fitted to the segment the
@@ -355,7 +370,8 @@ def generate(rank, diffusion_cfg, model_cfg, dataset_cfg, ckpt_iter="max", n_sam
     ``labels[k % len(labels)]`` -- so ``{iter}k_{k}.wav`` is the same file for any ``batch_size`` dividing ``n_samples``
     and any number of ranks (``num_ranks``: the processes of the run, one per GPU) that produces clip k.
 
-    Ragged batches (not in the reference; mel-conditional WaveNet): ``mel_names`` is a LIST of utterances (wav stems, as
+    Ragged batches (not in the reference; mel-conditional WaveNet or SaShiMi, the latter with ``hop_length`` a multiple
+    of the product of ``model.pool``): ``mel_names`` is a LIST of utterances (wav stems, as
     ``mel_name`` names one; the two exclude each other), each vocoded once.  ``ragged_plan`` sorts them longest first and
     cuts batches of at most ``batch_size`` (default: all in one); ranks take the batches round-robin.  A batch runs at
     the length of its longest utterance with the per-clip ``lengths`` of ``sampling`` -- every utterance comes out as it
@@ -384,6 +400,7 @@ def generate(rank, diffusion_cfg, model_cfg, dataset_cfg, ckpt_iter="max", n_sam
                                      cfg_scale=cfg_scale, clips=clips, report_mel=report_mel)
         if model_cfg.get("unconditional"):
             raise ValueError("generate.mel_names needs a mel-conditional model (model.unconditional=false)")
+        _check_ragged_hop(model_cfg, dataset_cfg)
         plan = None
     else:
         plan = clip_plan(n_samples, n_samples if batch_size is None else batch_size, rank, num_ranks, clip_seeds, clips, seed)

@@ -293,11 +293,25 @@ class EngineModule(nn.Module):
             raise ValueError(f"{name} must fit 32-bit integers, got {list(key)}")
         return key
 
+    _length_multiple = 1              # every per-clip length is a multiple of it (SaShiMi: the product of its pooling factors)
+
+    def _lengths_checked(self, lengths):
+        """``_length_list(lengths)``, and the one rule on the values that needs no prepared shape: a length that is not a
+        multiple of ``_length_multiple`` is refused as the engine refuses it (NotImplementedError), before anything is
+        enqueued."""
+        key = self._length_list(lengths)
+        m = int(self._length_multiple)
+        bad = [v for v in key if v % m]
+        if bad:
+            raise NotImplementedError(f"lengths= {bad} on {type(self).__name__}: every per-clip length must be a multiple of "
+                                      f"{m}, the product of the pooling factors (a pooled stage holds length / factor samples)")
+        return key
+
     def _set_lengths(self, lengths, mel_spec=None, mel_frames=None):
         """Install the per-clip lengths of the coming call (None = off), cached by content as the labels are.  Comes
         before ``_set_condition(mel_spec)``: the engine checks a mel against the lengths it holds and the lengths against
         the mel it holds, so when both change the old mel is dropped first."""
-        key = self._length_list(lengths)
+        key = self._lengths_checked(lengths)
         frames = self._length_list(mel_frames, "mel_frames")
         if frames and not key:
             raise ValueError("mel_frames= needs lengths=")
@@ -333,10 +347,11 @@ class EngineModule(nn.Module):
 
     # -- reference surface -----------------------------------------------------
     def forward(self, input_data, mel_spec=None, labels=None, lengths=None, mel_frames=None):
-        """``lengths`` (WaveNet; not in the reference): an int sequence / tensor [B], clip b is ``lengths[b] <= L`` samples
+        """``lengths`` (not in the reference): an int sequence / tensor [B], clip b is ``lengths[b] <= L`` samples
         long and the rest of its row is padding -- over ``[0, lengths[b])`` the output is what the clip gives alone at its
         own length, nothing stored in the padding (of ``audio`` or of ``mel_spec`` behind ``mel_frames[b]`` frames, default
-        ``ceil(lengths[b] / hop)``) reaches it, and the output holds 0.0 there.  Evaluation calls only."""
+        ``ceil(lengths[b] / hop)``) reaches it, and the output holds 0.0 there.  SaShiMi: every length is a multiple of the
+        product of the pooling factors (NotImplementedError otherwise).  Evaluation calls only."""
         audio, diffusion_steps = input_data
         if labels is not None and not self.n_classes:
             raise ValueError("labels= on a model without classes (set model.n_classes)")
@@ -362,6 +377,7 @@ class EngineModule(nn.Module):
             mel_spec = self._expand_mel(mel_spec, B)      # one mel shared by the batch: forward_train takes a mel per clip
             self._call_labels = self._label_list(labels, B) or None
             return _EngineTrainFn.apply(self, audio, steps, mel_spec, *(self.parameters() if train_call else ()))
+        self._lengths_checked(lengths)       # (before anything is enqueued)
         with torch.no_grad():
             self._train_generation += 1      # an eval forward overwrites the activations of a pending training forward
             self._sync_params(L)

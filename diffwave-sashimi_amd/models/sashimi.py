@@ -90,6 +90,14 @@ class _PoolParams(nn.Module):
         self.linear = ConvParams(d_in, d_out, 1)
 
 
+def pool_span(pool):
+    """The product of the pooling factors: what a run length, and every per-clip length of a ragged batch, is a multiple of."""
+    span = 1
+    for p in pool:
+        span *= int(p)
+    return span
+
+
 class Sashimi(EngineModule):
     def __init__(self, in_channels=1, out_channels=1,
                  d_model=64, n_layers=8, pool=[4, 4], expand=2, ff=2, unet=True,
@@ -146,6 +154,7 @@ class Sashimi(EngineModule):
         self.norm = _LNParams()
         self.final_conv = nn.ModuleList([ConvParams(d_model, d_model, 1), nn.Identity(),
                                          ZeroConvParams(d_model, out_channels)])
+        self._length_multiple = pool_span(self.pool)     # per-clip lengths (lengths=): whole samples at every pooled stage
         self._nodes = {}
         self._L_host = {}     # id(kernel) -> ((data_ptr, version) of its L buffer, value): see _kernel_L
 

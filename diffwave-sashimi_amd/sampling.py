@@ -73,7 +73,7 @@ def _check_lengths(net, size, lengths, cfg_scale):
         raise ValueError("sampler: lengths= (ragged batches) is not built for classifier-free guidance (cfg_scale=)")
     if not hasattr(net, "_set_lengths"):
         raise ValueError("sampler: lengths= needs an engine model")
-    key = net._length_list(lengths)
+    key = net._lengths_checked(lengths)      # (SaShiMi: a multiple of the pooling factors' product, NotImplementedError)
     if len(key) != size[0]:
         raise ValueError(f"sampler: lengths holds {len(key)} entries for a batch of {size[0]}")
     return key
@@ -378,7 +378,7 @@ def sampling(net, size, diffusion_hyperparams, condition=None, *, x_T=None, nois
              resampling arguments.  Goes through the schedule entry with ``net_steps = 0..T-1`` (bit-identical to
              ``dws_sampler_run``).
 
-    Ragged batches (WaveNet; ``dws_model_set_lengths``), on ``sampling``, ``sampling_aligned``, ``sampling_ddim`` and
+    Ragged batches (both backbones; ``dws_model_set_lengths``), on ``sampling``, ``sampling_aligned``, ``sampling_ddim`` and
     ``sampling_dpmpp``:
       lengths    int sequence / tensor [B] with 1 <= lengths[b] <= L: clip b is that long, the rest of its row is
              padding.  Over ``[0, lengths[b])`` the run is the clip's own run at that length (the network never sees the

@@ -190,20 +190,26 @@ int dws_model_set_classes(dws_model* m, int32_t n_classes);
  * the same (B, S) rewrites the rows in place and replays the captured graphs (tap "sampler_graphs" does not move). */
 int dws_model_set_labels(dws_model* m, const int32_t* labels, int64_t B, void* stream);
 
-/* Ragged batches (WaveNet): clip b of the prepared [B, ., L] batch is len_b <= L samples long, the rest is padding.
+/* Ragged batches (both backbones): clip b of the prepared [B, ., L] batch is len_b <= L samples long, the rest is padding.
  * lengths: HOST int32[B] with 1 <= len_b <= L, or NULL = off (every path bit for bit as without this call).  mel_frames:
  * HOST int32[B] or NULL; on a conditional model NULL means ceil(len_b / (s0 s1)); needs 1 <= frames_b and
  * s0 s1 frames_b >= len_b (and frames_b <= Tmel of an installed mel; dws_model_set_condition checks the same).
  * Contract: over [0, len_b) clip b's output is what the network gives for that clip alone at L = len_b, up to the
  * arithmetic of the kernel path; nothing stored at positions >= len_b (audio, mel frames >= frames_b, injected noise,
  * internal buffers, NaN included) reaches a valid position; `out` of dws_model_forward and `x` of every sampler entry hold
- * exactly 0.0f there.  How: behind init_conv and every residual layer but the last a store-only kernel (wn_mask_tail)
+ * exactly 0.0f there.  How, WaveNet: behind init_conv and every residual layer but the last a store-only kernel (wn_mask_tail)
  * rewrites x[b, c, len_b .. len_b + d) (d = the next layer's dilation) to -fc_t(e)[b, c] of the next layer, so that the
  * dilated convolution's zero-padded input h = x + fc_t(e) is 0 there as it is past the end of a clip run alone; the
  * conditioner treats mel frames >= frames_b and first-upsampler positions >= s0 frames_b as zero.  A padded position still
  * costs its full layer time.
+ * SaShiMi: every op but the S4 convolution is pointwise in the (pooled) position, so the three convolutions seal their own
+ * INPUT on the load side: row (b, h) of a stage is convolved as if it were zero on [len_b / div, L_stage), div = the product
+ * of the pooling factors above the stage (the fused in-LDS FFT through its load descriptor and a select on the last packed
+ * point, the segmented kernel through its segment bounds -- a workgroup whose output segment is wholly padding returns at
+ * once --, the rocFFT path through a store-only launch on its input rows); `out` is zeroed behind each clip's end.  Every
+ * length must be a multiple of the product of the pooling factors (else DWS_ERR_UNSUPPORTED): len_b / div is an integer.
  * All checks precede any enqueue: B must be the prepared batch (DWS_ERR_INVALID); before dws_model_prepare ->
- * DWS_ERR_STATE; SaShiMi -> DWS_ERR_UNSUPPORTED; a shared mel (Bm == 1) with lengths -> DWS_ERR_INVALID.  The table goes
+ * DWS_ERR_STATE; a shared mel (Bm == 1) with lengths -> DWS_ERR_INVALID.  The table goes
  * through pinned staging into a model-owned device buffer (the host never waits for the GPU), holds until changed, and is
  * dropped by a dws_model_prepare to another shape.  With a mel installed the conditioner terms are re-evaluated from the
  * engine's copy of the mel under the new frame counts.  The sampler's captured steps contain the mask launches and read

@@ -12,7 +12,9 @@ call against the same call with a half-clip continuation mask (dws_sampler_run_e
 `--legs resample_c4` (not in the default list either): that edited call against the same call with resample=(2, 2)
 (dws_sampler_run_program: 10 network evaluations and 2 jumps for S = 6), alternating in one process.
 `--legs ragged_c2` (not in the default list): config 2 under bf16x6, the DDIM step without lengths, with
-lengths = [L] * B and with a spread of lengths down to L / 2, alternating in one process (`ragged_leg`)."""
+lengths = [L] * B and with a spread of lengths down to L / 2, alternating in one process (`ragged_leg`).
+`--legs ragged_c4` (not in the default list): the same three variants on config 4 (SaShiMi, a mel per clip) under bf16x6,
+then at L = 40000, where the top stage runs the segmented convolution (`ragged_sashimi_leg`)."""
 import argparse
 import json
 import os
@@ -279,6 +281,56 @@ def ragged_leg(name, cfg_name, precision, S, repeats):
     return rec
 
 
+def ragged_sashimi_leg(name, cfg_name, precision, S, repeats, L_long=40000):
+    """The cost of per-clip lengths on SaShiMi per step: in one process and alternating, the DDIM call without lengths (the
+    yardstick: the kernels it launched before the feature, the length-aware instances are not dispatched), with
+    lengths = [L] * B (the length-aware convolutions, every row whole) and with a spread of lengths from L down to L / 2 in
+    multiples of 256; every call a new seed, a mel per clip.  Then the plain and the spread call at L = L_long, where the top
+    stage runs the segmented convolution, whose workgroups of wholly padded output segments return at once --
+    DWS_RAGGED_SEG_NO_SKIP=1 in the environment of the process makes them run (the A/B of the two forms: run the leg once
+    with and once without)."""
+    from benchlib.configs import CONFIGS, build_model
+    from diffwave_sashimi_amd.sampling import calc_diffusion_hyperparams, sampling_ddim
+    cfg = CONFIGS[cfg_name]
+    dev = torch.device("cuda")
+    net = build_model(cfg, dev)
+    if precision != "f32":
+        net.set_option("precision", precision)
+    B = cfg["B"]
+    d = cfg["diffusion"]
+    dh = calc_diffusion_hyperparams(d["T"], d["beta_0"], d["beta_T"])
+    rec = dict(leg=name, config=cfg_name, precision=precision, S=S, B=B,
+               padded_segments="run" if os.environ.get("DWS_RAGGED_SEG_NO_SKIP") else "return at once", runs=[])
+    for L in (cfg["L"], L_long):
+        size = (B, 1, L)
+        g = torch.Generator().manual_seed(2)
+        mel = (torch.rand(B, 80, (L + 255) // 256, generator=g) * 13.5 - 11.5).to(dev)
+        spread = [L if b == 0 else max(L // 2, (L - (L // 2) * b // max(B - 1, 1)) // 256 * 256) for b in range(B)]
+        variants = {"plain": None, "full_lengths": [L] * B, "spread_lengths": spread}
+        if L == L_long:
+            del variants["full_lengths"]
+        call = lambda seed, lens: sampling_ddim(net, size, dh, S, 0.0, mel, seed=seed, lengths=lens)
+        for lens in variants.values():                      # warm-up: code objects, kernels of this length, step table, graphs
+            call(1, lens), call(2, lens)
+        times = {k: [] for k in variants}
+        for i in range(repeats):
+            for k, lens in variants.items():
+                times[k].append(_clock(lambda: call(100 + i, lens)) / S)
+        med = {k: statistics.median(v) for k, v in times.items()}
+        run = dict(L=L, padded_share_spread=round(1.0 - sum(spread) / float(B * L), 4),
+                   per_step={k: _stats(v) for k, v in times.items()},
+                   spread_minus_plain_ms=round(med["spread_lengths"] - med["plain"], 4),
+                   spread_over_plain=round(med["spread_lengths"] / med["plain"], 5),
+                   plain_spread_ms=round(max(times["plain"]) - min(times["plain"]), 4),
+                   graphs_after_repeats=int(net.read_tap("sampler_graphs", (1,)).item()))
+        if "full_lengths" in med:
+            run["full_minus_plain_ms"] = round(med["full_lengths"] - med["plain"], 4)
+        rec["runs"].append(run)
+    del net
+    torch.cuda.empty_cache()
+    return rec
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--repeats", type=int, default=5)
@@ -298,6 +350,8 @@ def main():
                                             "unet_d32_n6_T50_cond", "f32", 6, args.repeats),
         "ragged_c2": lambda: ragged_leg("config2 DDIM S=10 bf16x6, per-clip lengths", "wnet_h256_d36_T200", "bf16x6", 10,
                                         args.repeats),
+        "ragged_c4": lambda: ragged_sashimi_leg("config4 DDIM S=6 bf16x6, per-clip lengths", "unet_d32_n6_T50_cond", "bf16x6", 6,
+                                                args.repeats),
         "capture": lambda: [capture_cost("unet_d32_n6_T50_cond", "f32", "ddim", 6, args.repeats),
                             capture_cost("wnet_h256_d36_T200", "bf16x6", "ddim", 50, args.repeats)],
     }
