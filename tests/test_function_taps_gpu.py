@@ -11,6 +11,9 @@
                                                                  switched off vs oracle.sashimi.ff(LN2(x))
   a14 S4.forward (`models/s4.py:1376-1437`)                      tests/test_s4_convolution_gpu.py: the same tap with the tail
                                                                  made transparent vs a float64 convolution, every FFT plan
+  a14^T its adjoint (fftconv with conj_k, fftcorr, rocFFT)        tests/test_s4_convolution_adjoint_gpu.py: audio.grad and the
+                                                                 parameter gradients of the same block with both ReLUs held
+                                                                 open vs float64 autograd, every FFT plan, batch chunks
   a16 mel conditioner (`wavenet.py:98-111`, `sashimi.py:160-175`) tests/test_conditioner_gpu.py: taps "mel_u0", "mel_u1", "melc" /
                                                                  "melc:<block>" vs the float64 oracle, power-of-two and generic strides
 """
