@@ -76,6 +76,7 @@ _SIGS = {
                                                ctypes.c_void_p]),
     "dws_model_forward": (ctypes.c_int, [ctypes.c_void_p, c_f32p, c_f32p, c_f32p, ctypes.c_void_p]),
     "dws_model_forward_train": (ctypes.c_int, [ctypes.c_void_p, c_f32p, c_f32p, c_f32p, ctypes.c_void_p]),
+    "dws_model_forward_input": (ctypes.c_int, [ctypes.c_void_p, c_f32p, c_f32p, c_f32p, ctypes.c_void_p]),
     "dws_model_backward": (ctypes.c_int, [ctypes.c_void_p, c_f32p, ctypes.c_void_p]),
     "dws_model_backward_input": (ctypes.c_int, [ctypes.c_void_p, c_f32p, c_f32p, ctypes.c_int32, ctypes.c_void_p]),
     "dws_model_get_grad": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_char_p, c_f32p, ctypes.c_int64, ctypes.c_void_p]),

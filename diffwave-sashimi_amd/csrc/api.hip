@@ -438,6 +438,11 @@ int dws_model_forward_train(dws_model* m, const float* audio, const float* steps
     return m->forward_train(audio, steps, out, (hipStream_t)stream);
 }
 
+int dws_model_forward_input(dws_model* m, const float* audio, const float* steps, float* out, void* stream) {
+    DWS_CHECK(m && audio && steps && out, DWS_ERR_INVALID, "dws_model_forward_input: null argument");
+    return m->forward_input(audio, steps, out, (hipStream_t)stream);
+}
+
 int dws_model_backward_input(dws_model* m, const float* dout, float* daudio, int32_t param_grads, void* stream) {
     DWS_CHECK(m && dout, DWS_ERR_INVALID, "dws_model_backward: null argument");
     DWS_CHECK(param_grads == 0 || param_grads == 1, DWS_ERR_INVALID, "dws_model_backward_input: param_grads = %d (0 or 1)", param_grads);

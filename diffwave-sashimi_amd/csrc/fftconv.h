@@ -61,10 +61,19 @@ struct FftConvSegArgs {
     // clip's end returns at once -- that part of g then keeps whatever it held
     const int32_t* lengths;
     int len_div, skip_pad;
+    float* pre;            // launch_fftconv_seg_train only: [B,H,L] the pre-activation conv + D u (FftConvArgs::pre)
 };
 constexpr int FFTCONV_SEG_LOG2M = 14;
 bool fftconv_seg_supported(int L, int taps);
 int launch_fftconv_seg(const FftConvSegArgs& a, hipStream_t s);
+// Training forward of a segmented stage (data-only pair): the sampling instance's arithmetic with one more store, a.pre.
+// Per-clip lengths are the sampling path's: a.lengths must be null.
+int launch_fftconv_seg_train(const FftConvSegArgs& a, hipStream_t s);
+// Its adjoint: a.g = conv^T(a.u) + D a.u, no GELU, from the SAME three spectra as the forward (a.kfa / kfb / kfs as handed
+// to launch_fftconv_seg).  The adjoint of the two-sided convolution is the convolution with the time-reversed kernel:
+// segment j takes conj(full), its left neighbour conj(anti-causal'), its right neighbour conj(causal') -- the shift factor
+// (-1)^k is real, and lag 0 (kept in the causal half) never reaches a neighbour segment.  a.lengths must be null.
+int launch_fftconv_seg_adjoint(const FftConvSegArgs& a, hipStream_t s);
 // which = 0: both halves (== launch_s4_twosided_pow2), 1: causal taps only, 2: anti-causal taps only
 int launch_s4_twosided_pow2_part(const float* k, float* K, int H, int Lt, int Nf, int Lk, int which, hipStream_t s);
 // sign_alt: multiply bin k by (-1)^k

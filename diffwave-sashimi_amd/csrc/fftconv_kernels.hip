@@ -675,7 +675,12 @@ __global__ __launch_bounds__((1 << LOG2M) / 16) void fftcorr_blk_kernel(FftCorrA
 // go through the forward transform; their real-row bins times the matching kernel spectrum accumulate in registers
 // (16 pairs per thread at 512 threads); the sum is re-packed into LDS, inverse-transformed, and its first half is output
 // segment j (+ D u, GELU).  Twice the transform work of a short row, 16-20 bytes of HBM traffic per sample.
-template <int LOG2M, int THREADS>
+// MODE (compile time; SEG_SAMPLE is the kernel as it was): SEG_TRAIN also stores the pre-activation conv + D u into a.pre
+// (the training forward of the data-only pair); SEG_ADJOINT multiplies by the CONJUGATED spectra and skips the GELU --
+// du = conv^T(da) + D da, the launcher hands the causal' / anti-causal' spectra over swapped.  Per-clip lengths exist in
+// SEG_SAMPLE only.
+enum { SEG_SAMPLE = 0, SEG_TRAIN = 1, SEG_ADJOINT = 2 };
+template <int LOG2M, int THREADS, int MODE = SEG_SAMPLE>
 __global__ __launch_bounds__(THREADS) void fftconv_seg_kernel(FftConvSegArgs a) {
     constexpr int M = 1 << LOG2M, S = M, NP = M / 2 / THREADS;
     constexpr int NG = M / 16 / THREADS;
@@ -687,8 +692,11 @@ __global__ __launch_bounds__(THREADS) void fftconv_seg_kernel(FftConvSegArgs a) 
     const c2* __restrict__ u2 = reinterpret_cast<const c2*>(a.u + off);   // L even: samples (2i, 2i+1)
     // ragged batches: the row counts as zero from Lv on (uniform over the workgroup).  An output segment wholly behind it
     // is padding: the whole workgroup leaves here, before its first barrier.
-    const int Lv = a.lengths ? min(L, max(a.lengths[b] / a.len_div, 0)) : L;
-    if (a.skip_pad && j * S >= Lv) return;
+    int Lv = L;
+    if constexpr (MODE == SEG_SAMPLE) {
+        Lv = a.lengths ? min(L, max(a.lengths[b] / a.len_div, 0)) : L;
+        if (a.skip_pad && j * S >= Lv) return;
+    }
     const int Lvc = (Lv + 1) >> 1;     // packed points that hold a valid sample; the last one only its first when Lv is odd
     FftTw<LOG2M, NG> W;
     W.load(a.tw, tid0);
@@ -714,15 +722,15 @@ __global__ __launch_bounds__(THREADS) void fftconv_seg_kernel(FftConvSegArgs a) 
             const int q = tid + i * THREADS;
             if (q == 0) {
                 const c2 z0 = X[pidx(0)];
-                y0 = fmaf(z0.x + z0.y, kfs[0].x, y0);
+                y0 = fmaf(z0.x + z0.y, kfs[0].x, y0);      // (bins 0 and M of a real kernel are real: conjugation leaves them)
                 yM = fmaf(z0.x - z0.y, kfs[1].x, yM);
-                yh = cadd(yh, cmul_(cconj(X[pidx(1)]), kfs[2]));
+                yh = cadd(yh, cmul_(cconj(X[pidx(1)]), MODE == SEG_ADJOINT ? cconj(kfs[2]) : kfs[2]));
             } else {
                 const int p = 2 * q, pm = brev(M - brev(p, LOG2M), LOG2M);
                 c2 ak, am;
                 pair_bins(X[pidx(p)], X[pidx(pm)], a.twp[q], ak, am);
-                ya[i] = cadd(ya[i], cmul_(ak, kfa[q]));
-                yb[i] = cadd(yb[i], cmul_(am, kfb[q]));
+                ya[i] = cadd(ya[i], cmul_(ak, MODE == SEG_ADJOINT ? cconj(kfa[q]) : kfa[q]));
+                yb[i] = cadd(yb[i], cmul_(am, MODE == SEG_ADJOINT ? cconj(kfb[q]) : kfb[q]));
             }
         }
         __syncthreads();
@@ -751,7 +759,17 @@ __global__ __launch_bounds__(THREADS) void fftconv_seg_kernel(FftConvSegArgs a) 
     const int c0 = j * (S / 2), cn = min(S / 2, L / 2 - c0);
     for (int i = tid0; i < cn; i += THREADS) {
         const c2 y = X[pidx(i)], uu = u2[c0 + i];
-        g2[c0 + i] = mk(gelu_f(fmaf(y.x, scale, Dh * uu.x)), gelu_f(fmaf(y.y, scale, Dh * uu.y)));
+        if constexpr (MODE == SEG_SAMPLE) {
+            g2[c0 + i] = mk(gelu_f(fmaf(y.x, scale, Dh * uu.x)), gelu_f(fmaf(y.y, scale, Dh * uu.y)));
+        } else {
+            const c2 v = mk(fmaf(y.x, scale, Dh * uu.x), fmaf(y.y, scale, Dh * uu.y));
+            if constexpr (MODE == SEG_TRAIN) {
+                reinterpret_cast<c2*>(a.pre + off)[c0 + i] = v;
+                g2[c0 + i] = mk(gelu_f(v.x), gelu_f(v.y));
+            } else {
+                g2[c0 + i] = v;
+            }
+        }
     }
 }
 
@@ -1044,6 +1062,26 @@ int launch_fftconv_seg(const FftConvSegArgs& a, hipStream_t s) {
     hipLaunchKernelGGL((fftconv_seg_kernel<FFTCONV_SEG_LOG2M, TH>), dim3(a.B * a.H, ceil_div(a.L, S)), dim3(TH), C::LDS, s, a);
     return DWS_OK;
 }
+
+template <int MODE>
+static int launch_fcseg_train(FftConvSegArgs a, hipStream_t s) {
+    using C = FcCfg<FFTCONV_SEG_LOG2M>;
+    constexpr int TH = 512, S = 1 << FFTCONV_SEG_LOG2M;
+    DWS_CHECK(!a.lengths && !a.skip_pad, DWS_ERR_STATE, "fftconv_seg: per-clip lengths are the sampling instance's");
+    DWS_CHECK(MODE != SEG_TRAIN || a.pre, DWS_ERR_STATE, "fftconv_seg: the training forward needs a pre-activation buffer");
+    DWS_CHECK(fftconv_seg_supported(a.L, 0), DWS_ERR_STATE, "fftconv_seg: row of %d samples", a.L);
+    if (MODE == SEG_ADJOINT) {      // the time-reversed kernel: its causal half is the conjugate of the anti-causal one
+        std::swap(a.kfa[1], a.kfa[2]);
+        std::swap(a.kfb[1], a.kfb[2]);
+        std::swap(a.kfs[1], a.kfs[2]);
+    }
+    ProfileScope ps(MODE == SEG_ADJOINT ? "fftconv_seg_adjoint" : "fftconv_seg_train", s);
+    DWS_TRY((kernel_setup<fftconv_seg_kernel<FFTCONV_SEG_LOG2M, TH, MODE>>(C::LDS)));
+    hipLaunchKernelGGL((fftconv_seg_kernel<FFTCONV_SEG_LOG2M, TH, MODE>), dim3(a.B * a.H, ceil_div(a.L, S)), dim3(TH), C::LDS, s, a);
+    return DWS_OK;
+}
+int launch_fftconv_seg_train(const FftConvSegArgs& a, hipStream_t s) { return launch_fcseg_train<SEG_TRAIN>(a, s); }
+int launch_fftconv_seg_adjoint(const FftConvSegArgs& a, hipStream_t s) { return launch_fcseg_train<SEG_ADJOINT>(a, s); }
 
 // Host-built twiddle tables (double precision, rounded once):
 //   tw[k]  = exp(-2 pi i k / M),  k < M/2        (FFT passes)

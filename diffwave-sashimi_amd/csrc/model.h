@@ -221,6 +221,10 @@ struct dws_model {
     virtual int read_tap(const char* tap, float* dst, int64_t capacity, hipStream_t s) = 0;
     // training path: forward that keeps what backward needs; backward fills ParamSpec::grad of every parameter
     virtual int forward_train(const float* audio, const float* steps, float* out, hipStream_t s);
+    // the training forward of a data-only backward (dws_model_forward_input); a backbone without limits of its own: forward_train
+    virtual int forward_input(const float* audio, const float* steps, float* out, hipStream_t s) {
+        return forward_train(audio, steps, out, s);
+    }
     // daudio (optional): the gradient w.r.t. audio [B, in_channels, L]; param_grads = false (needs daudio): the data path
     // only -- no ParamSpec::grad is touched, nothing is handed to the sinks
     virtual int backward(const float* dout, float* daudio, bool param_grads, hipStream_t s);

@@ -111,6 +111,7 @@ struct SashimiModel : dws_model, S4Workspace {
     std::vector<KGroup*> kgroups;     // training commits: blocks grouped by shape (build_kernels_stacked)
     bool kernels_stacked = false;     // the last commit generated the kernels group by group
     bool trained_fwd = false;
+    bool input_only = false;          // the pending training forward came from forward_input: a data-only backward alone may follow
     const float* train_audio = nullptr;
     DevBuf mel_in;                    // copy of the installed mel [Bm][MB][Tmel] (conditioner adjoint)
     DevBuf mel_u0, mel_u1;            // upsampler scratch of set_condition (kept: no allocation / wait per utterance)
@@ -786,6 +787,19 @@ struct SashimiModel : dws_model, S4Workspace {
     DevBuf zero_row;     // [max H] zeros: the "step embedding" of the final norm
     bool final_ln_fused = false;   // set by forward(): the last block's tail wrote norm(x) into nfin
 
+    // a segmented block's tables, three spectra and shape (u, g and the mode's own fields are the caller's)
+    FftConvSegArgs seg_args(const SLayer* l) {
+        FftTables* t = tables[FFTCONV_SEG_LOG2M];
+        FftConvSegArgs fa{};
+        fa.D = P(l->prefix + ".layer.D");
+        fa.tw = (const c2*)t->tw.p; fa.twp = (const c2*)t->twp.p;
+        fa.kfa[0] = (const c2*)l->own.kfa.p; fa.kfb[0] = (const c2*)l->own.kfb.p; fa.kfs[0] = (const c2*)l->own.kfs.p;
+        fa.kfa[1] = (const c2*)l->kfa_c.p; fa.kfb[1] = (const c2*)l->kfb_c.p; fa.kfs[1] = (const c2*)l->kfs_c.p;
+        fa.kfa[2] = (const c2*)l->kfa_a.p; fa.kfb[2] = (const c2*)l->kfb_a.p; fa.kfs[2] = (const c2*)l->kfs_a.p;
+        fa.B = (int)B; fa.H = l->H; fa.L = l->L;
+        return fa;
+    }
+
     int run_block(SLayer* l, const float* x, const float* addend, bool y_ready, const OutLN* next, hipStream_t s) {
         Stage* st = stages[l->stage];
         const int H = l->H, Ls = l->L, nB = (int)B;
@@ -808,14 +822,8 @@ struct SashimiModel : dws_model, S4Workspace {
             if (!y_ready)
                 DWS_TRY(launch_ln(x, P(p + ".norm1.m"), P(p + ".norm1.s"), pt_base() + l->pt_off, pt_bstride(), st->y.f(), nB,
                                   H, Ls, (size_t)Ls, s, step_idx, pt_tstride()));
-            FftTables* t = tables[FFTCONV_SEG_LOG2M];
-            FftConvSegArgs fa{};
-            fa.u = st->y.f(); fa.g = st->g.f(); fa.D = P(p + ".layer.D");
-            fa.tw = (const c2*)t->tw.p; fa.twp = (const c2*)t->twp.p;
-            fa.kfa[0] = (const c2*)l->own.kfa.p; fa.kfb[0] = (const c2*)l->own.kfb.p; fa.kfs[0] = (const c2*)l->own.kfs.p;
-            fa.kfa[1] = (const c2*)l->kfa_c.p; fa.kfb[1] = (const c2*)l->kfb_c.p; fa.kfs[1] = (const c2*)l->kfs_c.p;
-            fa.kfa[2] = (const c2*)l->kfa_a.p; fa.kfb[2] = (const c2*)l->kfb_a.p; fa.kfs[2] = (const c2*)l->kfs_a.p;
-            fa.B = nB; fa.H = H; fa.L = Ls;
+            FftConvSegArgs fa = seg_args(l);
+            fa.u = st->y.f(); fa.g = st->g.f();
             // (DWS_RAGGED_SEG_NO_SKIP=1: workgroups of wholly padded output segments run too -- the same-box A/B)
             static const bool skip_pad = getenv("DWS_RAGGED_SEG_NO_SKIP") == nullptr;
             fa.lengths = conv_lengths(); fa.len_div = stage_div(l); fa.skip_pad = (fa.lengths && skip_pad) ? 1 : 0;
@@ -1232,16 +1240,30 @@ struct SashimiModel : dws_model, S4Workspace {
                                       inner, s);
     }
 
-    int train_supported() {
+    // what every training forward asks of the installed condition
+    int train_condition_ok() {
         DWS_CHECK(melBm == 0 || melBm == B, DWS_ERR_UNSUPPORTED,
                   "mel-conditional training needs one mel per clip (got %lld for B=%lld)", (long long)melBm, (long long)B);
         DWS_CHECK(!cond || melBm > 0, DWS_ERR_STATE, "conditional model: install the mel (set_condition) before forward_train");
+        return DWS_OK;
+    }
+
+    // forward_train: every block at its kernel's own length on the fused convolution or rocFFT -- what the PARAMETER gradients
+    // are built for (fftcorr, the spectrum / taps adjoints, the stacked groups).  The data-only pair (forward_input) has
+    // no such limit.
+    int train_supported() {
+        DWS_TRY(train_condition_ok());
         for (auto* l : all) {
             if (l->kind == L_BLOCK) {
                 // (a stage runs the fused LDS convolution or rocFFT; the segmented path needs kernels shorter than the stage)
-                DWS_CHECK(!l->seg, DWS_ERR_UNSUPPORTED, "sashimi training does not run the segmented convolution (stage L=%d)", l->L);
+                DWS_CHECK(!l->seg, DWS_ERR_UNSUPPORTED,
+                          "sashimi training does not run the segmented convolution (stage L=%d): parameter gradients are built "
+                          "on the fused and rocFFT stages; input gradients alone (eval() mode, dws_model_forward_input) run here",
+                          l->L);
                 DWS_CHECK(l->Lk == l->L, DWS_ERR_UNSUPPORTED,
-                          "sashimi training runs at the kernels' own length (stage runs at %d, kernel length %d)", l->L, l->Lk);
+                          "sashimi training runs at the kernels' own length (stage runs at %d, kernel length %d): parameter gradients "
+                          "are not built at another; input gradients alone (eval() mode, dws_model_forward_input) run at any length",
+                          l->L, l->Lk);
             }
         }
         return DWS_OK;   // channel counts that are not multiples of 32 train on the plain-FMA GEMM (row_major)
@@ -1261,7 +1283,7 @@ struct SashimiModel : dws_model, S4Workspace {
         for (auto* l : all) {
             if (l->kind == L_BLOCK) {
                 const size_t n = (size_t)B * l->H * l->L * 4;
-                if (l->log2m == 0) {    // rocFFT stage: padded rows, spectra, plans (prepare() made them for this B already)
+                if (l->log2m == 0 && !l->seg) {    // rocFFT stage: padded rows, spectra, plans (prepare() made them for this B already)
                     Stage* st = stages[l->stage];
                     DWS_TRY(ensure_rocfft_stage(st));
                     DWS_TRY(st->Gf.ensure((size_t)B * st->H * (st->L + 1) * 8));
@@ -1292,13 +1314,36 @@ struct SashimiModel : dws_model, S4Workspace {
     }
 
     int forward_train(const float* audio, const float* steps, float* out, hipStream_t s) override {
+        return train_forward(audio, steps, out, false, s);
+    }
+
+    // The training forward for a data-only backward (dws_model_forward_input).  Where forward_train runs -- every block at its
+    // kernel's own length -- this IS forward_train.  Otherwise (a run shorter or longer than the kernels, a stage on the
+    // segmented convolution) the commit stays the sampling path's: per-block chains at Lt = min(L, Lk) taps (build_kernel),
+    // and every block's convolution keeps its pre-activation on the route the sampler takes at this length.
+    int forward_input(const float* audio, const float* steps, float* out, hipStream_t s) override {
+        DWS_CHECK(B > 0, DWS_ERR_STATE, "forward before prepare");
+        bool own_length = true;
+        for (auto* l : all) {
+            if (l->kind != L_BLOCK) continue;
+            int64_t Lk = 0;
+            DWS_TRY(kernel_len(l, s, &Lk));
+            if (Lk != l->L) own_length = false;      // (at Lk == L > 16384 the stage leaves the segmented path: resolve_segmented_stages)
+        }
+        DWS_TRY(train_forward(audio, steps, out, !own_length, s));
+        input_only = true;
+        return DWS_OK;
+    }
+
+    int train_forward(const float* audio, const float* steps, float* out, bool any_length, hipStream_t s) {
         DWS_CHECK(B > 0, DWS_ERR_STATE, "forward before prepare");
         DWS_CHECK(!ragged(), DWS_ERR_UNSUPPORTED, "training with per-clip lengths (dws_model_set_lengths) is not built");
         DWS_CHECK(!f16x3, DWS_ERR_UNSUPPORTED,
                   "training runs with precision=f32 or bf16x6 (gradients span too many binades for the fixed scales of the fp16 split)");
-        keep_cauchy = true;
+        if (!any_length) keep_cauchy = true;
         if (dirty) DWS_TRY(commit(s));
-        DWS_TRY(train_supported());
+        if (any_length) DWS_TRY(train_condition_ok());
+        else DWS_TRY(train_supported());
         DWS_TRY(ensure_train_buffers());
         if (train_pack_version != commit_version) DWS_TRY(pack_train(s));
         const int nB = (int)B;
@@ -1331,6 +1376,10 @@ struct SashimiModel : dws_model, S4Workspace {
                     fa.kfa = (const c2*)l->kfa_v; fa.kfb = (const c2*)l->kfb_v; fa.kfs = (const c2*)l->kfs_v;
                     fa.B = nB; fa.H = H; fa.L = Ls;
                     DWS_TRY(launch_fftconv(l->log2m, fa, s));
+                } else if (l->seg) {      // (forward_input only)
+                    FftConvSegArgs fa = seg_args(l);
+                    fa.u = l->t_u.f(); fa.g = l->t_g.f(); fa.pre = l->t_a.f();
+                    DWS_TRY(launch_fftconv_seg_train(fa, s));
                 } else {
                     DWS_TRY(rocfft_conv_forward(l, st, s));
                 }
@@ -1376,6 +1425,7 @@ struct SashimiModel : dws_model, S4Workspace {
         DWS_HIP(hipGetLastError());
         train_audio = audio;
         trained_fwd = true;
+        input_only = false;      // (forward_input sets it)
         return DWS_OK;
     }
 
@@ -1525,6 +1575,9 @@ struct SashimiModel : dws_model, S4Workspace {
     // no embedding or conditioner adjoint, no G() access and no flush point.
     int backward(const float* dout, float* daudio, bool pg, hipStream_t s) override {
         DWS_CHECK(trained_fwd, DWS_ERR_STATE, "backward without a preceding forward_train");
+        DWS_CHECK(!pg || !input_only, DWS_ERR_STATE,
+                  "backward: the pending forward is dws_model_forward_input, which keeps what a data-only backward needs "
+                  "(param_grads = 0); parameter gradients need dws_model_forward_train");
         DWS_CHECK(pg || daudio, DWS_ERR_INVALID, "backward: a data-only pass needs a destination for the input gradient");
         const int nB = (int)B, nL = (int)L;
         const int nnodes = (int)plan.size() + 1;
@@ -1603,7 +1656,11 @@ struct SashimiModel : dws_model, S4Workspace {
                     DWS_TRY(wgrad(st->d2.f(), l->t_g.f(), 2 * H, H, Ls, 0, G(p + ".layer.output_linear.0.weight"),
                                   G(p + ".layer.output_linear.0.bias"), s));
                 // a = conv(u, K) + D u: du = conv^T(da) + D da; kernel parameters from corr(u, da)
-                if (l->log2m == 0) {    // rocFFT stage (rocfft_conv_backward also writes d fc_t(e) and every S4 kernel gradient)
+                if (l->seg) {           // segmented stage (forward_input: pg is off): the same kernel on the conjugated spectra
+                    FftConvSegArgs fa = seg_args(l);
+                    fa.u = st->dh.f(); fa.g = st->du.f();
+                    DWS_TRY(launch_fftconv_seg_adjoint(fa, s));
+                } else if (l->log2m == 0) {    // rocFFT stage (rocfft_conv_backward also writes d fc_t(e) and every S4 kernel gradient)
                     DWS_TRY(rocfft_conv_backward(l, st, st->dh.f(), st->du.f(), pg, s));
                 } else {
                     FftTables* t = tables[l->log2m];

@@ -17,9 +17,10 @@ class _EngineTrainFn(torch.autograd.Function):
 
     ``audio`` gets a gradient too when it requires one (guided sampling, input-space optimisation): the data adjoint of
     ``init_conv`` closes the chain of data gradients the backward carries anyway.  When no parameter takes part (the call
-    was made without ``*params``: an ``eval()`` module, frozen parameters) the backward is DATA-ONLY,
-    ``dws_model_backward_input(param_grads=0)``: no parameter gradient is computed or written, the reducer and the
-    gradient sinks are not involved.  ``mel_spec`` and ``diffusion_steps`` never get a gradient (the conditioner's and
+    was made without ``*params``: an ``eval()`` module, frozen parameters) the forward is ``dws_model_forward_input`` and
+    the backward is DATA-ONLY, ``dws_model_backward_input(param_grads=0)``: no parameter gradient is computed or written,
+    the reducer and the gradient sinks are not involved, and a SaShiMi model runs at any length (``forward_train`` itself
+    at the kernels' own).  ``mel_spec`` and ``diffusion_steps`` never get a gradient (the conditioner's and
     the embedding's data adjoints towards their inputs are not built), and the backward is once-differentiable."""
 
     @staticmethod
@@ -32,8 +33,10 @@ class _EngineTrainFn(torch.autograd.Function):
         module._set_condition(mel_spec)      # conditional models: the conditioner's parameters get gradients too
         x = audio.detach().to(torch.float32).contiguous()
         out = torch.empty((B, module.out_channels, L), device=audio.device, dtype=torch.float32)
-        _lib.check(lib.dws_model_forward_train(module._handle, x.data_ptr(), steps.data_ptr(), out.data_ptr(),
-                                               _lib.current_stream()))
+        # called without parameters (an eval() module, frozen parameters): the forward of a data-only backward, which a
+        # SaShiMi model also runs at a length other than its kernels' own and on segmented stages
+        entry = lib.dws_model_forward_train if params else lib.dws_model_forward_input
+        _lib.check(entry(module._handle, x.data_ptr(), steps.data_ptr(), out.data_ptr(), _lib.current_stream()))
         ctx.module, ctx.x, ctx.steps = module, x, steps      # x must stay alive until backward (init_conv adjoint)
         module._train_generation += 1                        # the activations inside the dws_model belong to THIS forward
         ctx.generation = module._train_generation
@@ -369,8 +372,9 @@ class EngineModule(nn.Module):
             self._set_lengths(None, mel_spec)
             # training call (`train.py:221`): differentiable w.r.t. the parameters -- and, in train() or eval() mode (the nets
             # have no mode-dependent layer), w.r.t. an `audio` that requires a gradient; then alone, the parameters stay out of
-            # the graph and backward is data-only.  The path has the limits of forward_train (f32 / bf16x6, no segmented S4
-            # stage): the engine's own error is raised, there is no fallback.
+            # the graph and backward is data-only.  The path has the limits of forward_train (f32 / bf16x6; with parameters
+            # in the graph SaShiMi runs at its kernels' own length, no segmented S4 stage -- the data-only pair runs at any
+            # length): the engine's own error is raised, there is no fallback.
             steps = diffusion_steps.detach().to(device=audio.device, dtype=torch.float32).reshape(-1).contiguous()
             if steps.numel() != B:
                 raise RuntimeError(f"diffusion_steps must hold B={B} entries, got {tuple(diffusion_steps.shape)}")

@@ -820,9 +820,13 @@ def sampling_guided(net, size, diffusion_hyperparams, *, measurement, operator, 
     of the B = 1 run with ``seed[b]``.  ``residuals``: a list that receives ``n`` [B] of every step (diagnostics).
 
     ``net`` is any differentiable callable of the reference surface on any device.  With an engine model every step is
-    a training forward and a DATA-ONLY backward (``dws_model_backward_input``): put the model in ``eval()`` mode, or the
-    full backward runs.  The path has the limits of the training forward (precision f32 / bf16x6, no segmented S4
-    stage); a mel ``[1, bands, Tmel]`` is expanded to the batch.  The loop runs eagerly, one step after the other with
+    a training forward and a DATA-ONLY backward (``dws_model_forward_input`` / ``dws_model_backward_input``): put the
+    model in ``eval()`` mode, or the full backward runs.  In ``eval()`` mode ``L`` is free for both backbones: a SaShiMi
+    model runs shorter and longer than its kernels' ``l_max`` (truncated / clamped taps) and on stages beyond 16384
+    samples (the segmented convolution and its adjoint) -- a recording or a mel of any length, within the pooling
+    factors' product.  In ``train()`` mode a SaShiMi model raises ``NotImplementedError`` at any other length than its
+    kernels' own: parameter gradients are not built there.  Precision f32 / bf16x6; a mel ``[1, bands, Tmel]`` is
+    expanded to the batch.  The loop runs eagerly, one step after the other with
     no graph capture: each step contains a backward.  Costs a forward plus a backward per step.  The editing arguments
     (``known`` / ``mask`` ..., ``resample``) and ``cfg_scale`` are not built for guided runs; ``labels`` ([B], a
     class-conditional model) are passed to every network call.  Not the reference's loop."""

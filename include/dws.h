@@ -255,6 +255,17 @@ int dws_model_backward(dws_model* m, const float* dout, void* stream);
  * Preconditions as dws_model_backward: one pending forward_train, precision f32 or bf16x6.  The mel condition and the
  * diffusion steps get no gradient. */
 int dws_model_backward_input(dws_model* m, const float* dout, float* daudio, int32_t param_grads, void* stream);
+/* The training forward of a DATA-ONLY backward (guided sampling, `audio.grad` of an eval() module): arguments, preconditions
+ * (precision f32 or bf16x6, one mel per clip, no per-clip lengths) and output as dws_model_forward_train.
+ * Where dws_model_forward_train is accepted this IS that call: the same commit, launches and bits.  A SaShiMi model that
+ * dws_model_forward_train refuses only because the run length is not its kernels' own (`L` buffers != stage length) or
+ * because a stage runs the segmented convolution is accepted here: the commit stays the sampling path's (per-block kernel
+ * chains at min(L, l_max) taps per direction) and every block's S4 convolution runs on the route the sampler takes at this
+ * length -- the fused LDS FFT, the segmented kernel (an instance that also stores the pre-activation; its adjoint is the
+ * same kernel on the conjugated spectra with the causal' / anti-causal' ones swapped) or rocFFT.  WaveNet: forward_train.
+ * Afterwards dws_model_backward_input(param_grads = 0) is valid; dws_model_backward and param_grads = 1 return
+ * DWS_ERR_STATE (no parameter gradient is built at another length or on the segmented path, and none is kept for here). */
+int dws_model_forward_input(dws_model* m, const float* audio, const float* steps, float* out, void* stream);
 int dws_model_get_grad(dws_model* m, const char* name, float* dst, int64_t numel, void* stream);
 /* The same for `count` parameters in one launch (the autograd wrapper fetches every gradient after backward). */
 int dws_model_get_grads(dws_model* m, int32_t count, const char* const* names, float* const* dsts, const int64_t* numels,
