@@ -5,6 +5,12 @@
   a1  calc_diffusion_step_embedding (`models/utils.py:20-27`)    tap "emb"      vs tests/golden/embedding.npz
   a2  embedding MLP + every block's fc_t (`wavenet.py:153-155,89`, `sashimi.py:287-289,151`)
                                                                  taps "emb_mlp", "part_t" vs the oracle
+  a4  Residual_block.forward (`models/wavenet.py:82-121`)        tests/test_wavenet_layer_gpu.py: taps "x", "skip", "hsave" of a layer
+                                                                 isolated as the last / a middle layer of a network vs the float64
+                                                                 oracle, per position class, every forward kernel family
+  a4^T its adjoint (tapconv / tapwino / wgrad kernels, conv_t)   tests/test_wavenet_layer_adjoint_gpu.py: audio.grad and the layer's
+                                                                 own gradients with both ReLUs held open vs float64 autograd,
+                                                                 dense / head / tail cotangents, full and data-only backward
   a7  TransposedLN (`models/sashimi.py:17-20`)                   tap "nfin"     vs s4_parts.npz ln/*  (the fixture's
                                                                  tensors go through the HIP LayerNorm)
   a9  FF (`models/sashimi.py:60-75`)                             taps "out:<block>" of a block whose S4 branch is
