@@ -119,10 +119,12 @@ _SIGS = {
     "dws_philox_normal": (ctypes.c_int, [c_f32p, ctypes.c_int64, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_void_p]),
     "dws_sampler_set_clip_seeds": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint64), ctypes.c_int64,
                                                   ctypes.c_void_p]),
+    "dws_sampler_set_prior": (ctypes.c_int, [ctypes.c_void_p, c_f32p, ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p]),
     "dws_philox_normal_clips": (ctypes.c_int, [c_f32p, ctypes.c_int64, ctypes.c_int64, ctypes.POINTER(ctypes.c_uint64),
                                                ctypes.c_uint32, ctypes.c_void_p]),
     "dws_mel_spectrogram": (ctypes.c_int, [c_f32p, ctypes.c_int64, ctypes.c_int64, c_f32p, c_f32p, ctypes.c_int32,
                                            ctypes.c_int32, ctypes.c_int32, ctypes.c_float, c_f32p, ctypes.c_void_p]),
+    "dws_prior_std_from_mel": (ctypes.c_int, [c_f32p] + [ctypes.c_int64] * 5 + [ctypes.c_float] * 3 + [c_f32p, ctypes.c_void_p]),
     "dws_mel_spectrogram_backward": (ctypes.c_int, [c_f32p, ctypes.c_int64, ctypes.c_int64, c_f32p, c_f32p, ctypes.c_int32,
                                                     ctypes.c_int32, ctypes.c_int32, ctypes.c_float, c_f32p, c_f32p, c_f32p,
                                                     ctypes.c_void_p]),

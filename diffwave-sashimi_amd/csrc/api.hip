@@ -156,6 +156,25 @@ int dws_model::set_clip_seeds(const uint64_t* seeds, int64_t nB, hipStream_t s) 
     return DWS_OK;
 }
 
+// The table of the adaptive prior: device to device into a model-owned buffer at the shape of the sampler state.
+int dws_model::set_prior(const float* sigma, int64_t nB, int64_t n_per_clip, hipStream_t s) {
+    if (!sigma) {
+        smp.prior_on = false;
+        return DWS_OK;
+    }
+    DWS_CHECK(B > 0, DWS_ERR_STATE, "dws_sampler_set_prior before dws_model_prepare");
+    DWS_CHECK(!smp.cfg_on, DWS_ERR_UNSUPPORTED, "an adaptive prior with classifier-free guidance (dws_sampler_set_cfg is on) is not built");
+    DWS_CHECK(nB == B && n_per_clip == d.out_channels * L, DWS_ERR_INVALID,
+              "dws_sampler_set_prior: a table of [%lld, %lld] for a sampler state of [%lld, %lld]", (long long)nB,
+              (long long)n_per_clip, (long long)B, (long long)(d.out_channels * L));
+    const size_t bytes = (size_t)nB * n_per_clip * 4;
+    DWS_TRY(smp.prior.ensure(bytes));
+    DWS_HIP(hipMemcpyAsync(smp.prior.p, sigma, bytes, hipMemcpyDeviceToDevice, s));
+    smp.prior_B = nB; smp.prior_n = n_per_clip;
+    smp.prior_on = true;
+    return DWS_OK;
+}
+
 dws::ParamSpec* dws_model::add_param(const std::string& name, std::vector<int64_t> shape, int dtype) {
     auto* p = new dws::ParamSpec();
     p->name = name;
@@ -389,6 +408,7 @@ int dws_model_prepare(dws_model* m, int64_t B, int64_t L) {
     DWS_TRY(m->prepare(B, L));
     if (m->n_classes > 0 && (B0 != m->B || L0 != m->L)) DWS_TRY(m->reset_labels());   // labels belong to a shape
     if (B0 != m->B || L0 != m->L) m->smp.clip_B = 0;                                        // and so does a seed table
+    if (B0 != m->B || L0 != m->L) m->smp.prior_on = false;                                  // and the table of a prior
     return DWS_OK;
 }
 
@@ -412,6 +432,7 @@ int dws_sampler_set_cfg(dws_model* m, int32_t on, float scale) {
     DWS_CHECK(!on || (scale == scale && scale - scale == 0.f), DWS_ERR_INVALID, "dws_sampler_set_cfg: scale = %g is not finite",
               (double)scale);
     DWS_CHECK(!on || !m->ragged(), DWS_ERR_UNSUPPORTED, "classifier-free guidance with per-clip lengths (dws_model_set_lengths) is not built");
+    DWS_CHECK(!on || !m->smp.prior_on, DWS_ERR_UNSUPPORTED, "classifier-free guidance with an adaptive prior (dws_sampler_set_prior) is not built");
     m->smp.cfg_on = on != 0;
     m->smp.cfg_scale = on ? scale : 0.f;
     return DWS_OK;
@@ -420,6 +441,11 @@ int dws_sampler_set_cfg(dws_model* m, int32_t on, float scale) {
 int dws_sampler_set_clip_seeds(dws_model* m, const uint64_t* seeds, int64_t B, void* stream) {
     DWS_CHECK(m, DWS_ERR_INVALID, "null model");
     return m->set_clip_seeds(seeds, B, (hipStream_t)stream);
+}
+
+int dws_sampler_set_prior(dws_model* m, const float* sigma, int64_t B, int64_t n_per_clip, void* stream) {
+    DWS_CHECK(m, DWS_ERR_INVALID, "null model");
+    return m->set_prior(sigma, B, n_per_clip, (hipStream_t)stream);
 }
 
 int dws_model_set_condition(dws_model* m, const float* mel, int64_t Bm, int64_t Tmel, void* stream) {
@@ -679,6 +705,7 @@ int dws_sampler_run(dws_model* m, float* x, const float* alpha, const float* alp
     DWS_CHECK(m && x, DWS_ERR_INVALID, "dws_sampler_run: null argument");
     DWS_CHECK(!m->smp.cfg_on, DWS_ERR_UNSUPPORTED, "classifier-free guidance runs on dws_sampler_run_schedule only (dws_sampler_run)");
     DWS_CHECK(m->smp.clip_B == 0, DWS_ERR_UNSUPPORTED, "per-clip seeds run on the schedule entries only (dws_sampler_run)");
+    DWS_CHECK(!m->smp.prior_on, DWS_ERR_UNSUPPORTED, "an adaptive prior runs on the schedule entries only (dws_sampler_run)");
     return dws::sampler_run(m, x, alpha, alpha_bar, sigma, T, noise, seed, init_from_seed, use_graph,
                             (hipStream_t)stream);
 }
@@ -688,6 +715,7 @@ int dws_sampler_steps(dws_model* m, float* x, const float* alpha, const float* a
     DWS_CHECK(m && x, DWS_ERR_INVALID, "dws_sampler_steps: null argument");
     DWS_CHECK(!m->smp.cfg_on, DWS_ERR_UNSUPPORTED, "classifier-free guidance runs on dws_sampler_run_schedule only (dws_sampler_steps)");
     DWS_CHECK(m->smp.clip_B == 0, DWS_ERR_UNSUPPORTED, "per-clip seeds run on the schedule entries only (dws_sampler_steps)");
+    DWS_CHECK(!m->smp.prior_on, DWS_ERR_UNSUPPORTED, "an adaptive prior runs on the schedule entries only (dws_sampler_steps)");
     return dws::sampler_steps(m, x, alpha, alpha_bar, sigma, T, t_start, n_steps, seed, use_graph,
                               (hipStream_t)stream);
 }

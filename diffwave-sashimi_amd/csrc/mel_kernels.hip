@@ -159,7 +159,90 @@ __global__ __launch_bounds__(256) void mel_gather_kernel(const float* __restrict
     daudio[(size_t)b * T + j] = acc;
 }
 
+// Adaptive prior (PriorGrad, Lee et al., ICLR 2022): the per-sample standard deviation read off the frame energy of a
+// log-mel m [B, bands, frames],
+//   energy[b, f] = sqrt(sum_k exp(m[b, k, f])),  sigma_f = clamp((energy - e_min) / (e_max - e_min), std_min, 1),
+//   sigma[b, 0, l] = sigma_f[b, l / hop]          l = 0 .. L - 1.
+// One workgroup per (PRIOR_FRAMES frames, clip).  Lane f of the first wave owns a frame (neighbouring lanes read
+// neighbouring frames of a band row) and adds its bands in a fixed order: band k into partial sum k % 8 in ascending k,
+// then the tree ((p0 + p1) + (p2 + p3)) + ((p4 + p5) + (p6 + p7)).  A frame's value so depends on its own column alone,
+// not on B or the launch shape.  All 256 threads then write the frames' span of the row: single floats up to the first
+// 16-byte border of the output, float4 from there, single floats behind the last whole group.
+constexpr int PRIOR_FRAMES = 64;
+
+__global__ __launch_bounds__(256) void prior_std_kernel(const float* __restrict__ mel, float* __restrict__ sigma, int bands,
+                                                        int64_t frames, int64_t hop, int64_t L, float e_min, float e_max,
+                                                        float std_min) {
+    __shared__ float sf[PRIOR_FRAMES];
+    const int64_t f0 = (int64_t)blockIdx.x * PRIOR_FRAMES;
+    const int b = blockIdx.y, tid = threadIdx.x;
+    if (tid < PRIOR_FRAMES) {
+        float v = 0.f;
+        const int64_t f = f0 + tid;
+        if (f < frames) {
+            const float* col = mel + (size_t)b * bands * frames + f;
+            // eight partial sums, band k into partial k % 8 in ascending k, then one fixed tree: for 80 bands a value
+            // passes through 13 additions, not the 80 of one running sum, and collects that much less rounding
+            float part[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+            int k = 0;
+            for (; k + 8 <= bands; k += 8) {
+#pragma unroll
+                for (int j = 0; j < 8; ++j) part[j] += expf(col[(size_t)(k + j) * frames]);
+            }
+#pragma unroll
+            for (int j = 0; j < 8; ++j)
+                if (k + j < bands) part[j] += expf(col[(size_t)(k + j) * frames]);
+            const float acc = ((part[0] + part[1]) + (part[2] + part[3])) + ((part[4] + part[5]) + (part[6] + part[7]));
+            const float e = (sqrtf(acc) - e_min) / (e_max - e_min);
+            v = fminf(fmaxf(e, std_min), 1.0f);
+        }
+        sf[tid] = v;
+    }
+    __syncthreads();
+    const int64_t lo = f0 * hop;                                                   // this block's span [lo, hi) of the row
+    const int64_t hi = (f0 + PRIOR_FRAMES) * hop < L ? (f0 + PRIOR_FRAMES) * hop : L;
+    if (lo >= hi) return;
+    float* row = sigma + (size_t)b * L;
+    const bool base16 = ((uintptr_t)sigma & 15) == 0;
+    // first element at or behind lo whose address is a 16-byte border (every element when the base is not aligned: no body)
+    int64_t head = base16 ? lo + (int64_t)((4 - (((size_t)b * L + lo) & 3)) & 3) : hi;
+    if (head > hi) head = hi;
+    const int64_t groups = (hi - head) / 4, tail = head + groups * 4;
+    for (int64_t i = lo + tid; i < head; i += 256) row[i] = sf[i / hop - f0];
+    for (int64_t g = tid; g < groups; g += 256) {
+        const int64_t i = head + g * 4;
+        *reinterpret_cast<float4*>(row + i) =
+            make_float4(sf[i / hop - f0], sf[(i + 1) / hop - f0], sf[(i + 2) / hop - f0], sf[(i + 3) / hop - f0]);
+    }
+    for (int64_t i = tail + tid; i < hi; i += 256) row[i] = sf[i / hop - f0];
+}
+
 }  // namespace dws
+
+extern "C" int dws_prior_std_from_mel(const float* mel, int64_t B, int64_t bands, int64_t frames, int64_t hop, int64_t L,
+                                      float e_min, float e_max, float std_min, float* sigma, void* stream) {
+    using namespace dws;
+    DWS_CHECK(mel && sigma, DWS_ERR_INVALID, "dws_prior_std_from_mel: null argument");
+    DWS_CHECK(B > 0 && B <= 65535 && bands > 0 && bands <= INT32_MAX && frames > 0 && hop > 0, DWS_ERR_INVALID,
+              "dws_prior_std_from_mel: bad shape (B = %lld, bands = %lld, frames = %lld, hop = %lld)", (long long)B,
+              (long long)bands, (long long)frames, (long long)hop);
+    DWS_CHECK(frames <= INT64_MAX / hop && L >= 1 && L <= frames * hop, DWS_ERR_INVALID,
+              "dws_prior_std_from_mel: L = %lld (needs 1 .. frames * hop = %lld * %lld)", (long long)L, (long long)frames,
+              (long long)hop);
+    DWS_CHECK(e_min == e_min && e_max - e_max == 0.f && e_min - e_min == 0.f && e_max > e_min, DWS_ERR_INVALID,
+              "dws_prior_std_from_mel: energy range %g .. %g (needs finite values, e_max > e_min)", (double)e_min,
+              (double)e_max);
+    DWS_CHECK(std_min > 0.f && std_min <= 1.f, DWS_ERR_INVALID, "dws_prior_std_from_mel: std_min = %g (needs 0 < std_min <= 1)",
+              (double)std_min);
+    // frames whose span lies wholly behind L write nothing: launch only the blocks that hold a sample
+    const int64_t used = (L + hop - 1) / hop;
+    const int64_t blocks = (used + PRIOR_FRAMES - 1) / PRIOR_FRAMES;
+    DWS_CHECK(blocks <= INT32_MAX, DWS_ERR_INVALID, "dws_prior_std_from_mel: %lld frames", (long long)used);
+    hipLaunchKernelGGL(prior_std_kernel, dim3((unsigned)blocks, (unsigned)B), dim3(256), 0, (hipStream_t)stream, mel, sigma,
+                       (int)bands, frames, hop, L, e_min, e_max, std_min);
+    DWS_HIP(hipGetLastError());
+    return DWS_OK;
+}
 
 extern "C" int dws_mel_spectrogram_backward(const float* audio, int64_t B, int64_t T, const float* window,
                                             const float* mel_basis, int32_t n_fft, int32_t hop, int32_t n_mels, float clip,

@@ -137,6 +137,7 @@ struct dws_model {
     const int* step_idx = nullptr;       // set by the sampler around forward(): step-table mode, row *step_idx (device memory)
     uint64_t step_table_gen = 0;         // bumped by every step-table rebuild (build_step_table)
     int set_clip_seeds(const uint64_t* seeds, int64_t nB, hipStream_t s);
+    int set_prior(const float* sigma, int64_t nB, int64_t n_per_clip, hipStream_t s);
 
     // ---- class conditioning (dws_model_set_classes / dws_model_set_labels): one parameter "label_embedding.weight"
     // [K+1][Eout] beside fc_t1 / fc_t2 (row K = the null class); a clip's row is added to the output of the embedding MLP,

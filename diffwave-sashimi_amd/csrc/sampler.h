@@ -42,8 +42,9 @@ struct SamplerState {
         const void* hist = nullptr;                      // the multistep kind's history buffer (null for the others)
         const void* clip_seeds = nullptr;                // the per-clip seed table (null for a scalar-seed step)
         const void* lengths = nullptr;                   // the per-clip length table (null: lengths off)
+        const void* prior = nullptr;                     // the adaptive prior's table (null: N(0, I))
         bool operator==(const SchKey& o) const {
-            return lengths == o.lengths && B == o.B && L == o.L && S == o.S && kind == o.kind && vec == o.vec && tables == o.tables &&
+            return prior == o.prior && lengths == o.lengths && B == o.B && L == o.L && S == o.S && kind == o.kind && vec == o.vec && tables == o.tables &&
                    noise == o.noise && eps == o.eps && x == o.x && state == o.state && table_gen == o.table_gen &&
                    edit == o.edit && known == o.known && mask == o.mask && known_noise == o.known_noise && V == o.V &&
                    prog == o.prog && hist == o.hist && clip_seeds == o.clip_seeds;
@@ -58,7 +59,7 @@ struct SamplerState {
     struct SchGraph {
         hipGraphExec_t exec = nullptr;
         SchKey key{};
-    } sch_graphs[SCH_GRAPHS][4];     // [form of seed + 2 * per-clip lengths on]: a step with lengths on holds the launches
+    } sch_graphs[SCH_GRAPHS][8];     // [form of seed + 2 * per-clip lengths on + 4 * adaptive prior on]: a step with lengths on holds the launches
                                      // that seal the padding (it reads the length table from device memory: a new table
                                      // replays it), so lengths on / off alternate without a new capture as the rest does
     // editing: the known clip and the mask are copied into model-owned buffers before the replays, like x into sch_x.
@@ -81,6 +82,13 @@ struct SamplerState {
     DevBuf clip_seeds;                    // uint64 [clip_B]
     int64_t clip_B = 0;                   // clips the table holds (0: off, the scalar seed of the run entries)
     StagingRing seed_ring{4};             // pinned staging of the table's upload
+    // adaptive prior (dws_sampler_set_prior; PriorGrad, Lee et al., ICLR 2022): the run ends in N(0, diag(prior^2)) -- every
+    // standard-normal number a schedule run consumes, drawn or injected, is multiplied by the table at its position first
+    // (the PRIOR kernel instances).  The table sits in device memory at the shape of the sampler state (a new one replays
+    // the captured step) and holds until it is changed or the model is prepared for another shape.
+    DevBuf prior;                         // float [prior_B, prior_n]
+    int64_t prior_B = 0, prior_n = 0;     // n = C L elements per clip
+    bool prior_on = false;
     int64_t graphs_made = 0;              // tap "sampler_graphs": graphs instantiated by either entry point
 
     SamplerState() = default;

@@ -211,6 +211,22 @@ __device__ __forceinline__ float smp_mix_elem(float a, float x, float b, float z
     return p + q;
 }
 
+// adaptive prior (dws_sampler_set_prior): n = sigma z, one product of its own; n then stands where z stood
+__device__ __forceinline__ float smp_prior_elem(float sg, float z) {
+#pragma clang fp contract(off)
+    return sg * z;
+}
+
+// PRIOR instances of the drawing kernels: z <- sigma z over a group, sigma at the group's own positions of the table
+// [B, C L] (the shape of the state, so it is indexed like x).  Injected and drawn numbers alike.
+template <bool VEC>
+__device__ __forceinline__ void smp_prior4(const float* __restrict__ prior, size_t g, size_t n, float z[4]) {
+    float sg[4] = {0.f, 0.f, 0.f, 0.f};
+    smp_load4<VEC>(prior, g, n, sg);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) z[j] = smp_prior_elem(sg[j], z[j]);
+}
+
 // classifier-free guidance: eps_c + scale (eps_c - eps_u)
 __device__ __forceinline__ float smp_cfg_elem(float c, float u, float scale) {
 #pragma clang fp contract(off)
@@ -219,10 +235,14 @@ __device__ __forceinline__ float smp_cfg_elem(float c, float u, float scale) {
     return c + gd;
 }
 
-__global__ void smp_fill_normal_kernel(float* __restrict__ x, size_t n, uint64_t seed, uint32_t stream_id) {
+// PRIOR: x = sigma z with prior [n] (the drawn x_T of a run with an adaptive prior).
+template <bool PRIOR>
+__global__ void smp_fill_normal_kernel(float* __restrict__ x, size_t n, uint64_t seed, uint32_t stream_id,
+                                       const float* __restrict__ prior) {
     for (size_t g = (size_t)blockIdx.x * blockDim.x + threadIdx.x; g * 4 < n; g += (size_t)gridDim.x * blockDim.x) {
         float z[4];
         normal4(seed, stream_id, g, z);
+        if (PRIOR) smp_prior4<false>(prior, g, n, z);
         smp_store4<false>(x, g, n, z);
     }
 }
@@ -235,13 +255,16 @@ struct SeedChunk {
     __device__ uint64_t operator[](unsigned b) const { return s[b]; }
 };
 
-template <class SEEDS>
-__global__ void smp_fill_normal_clips_kernel(float* __restrict__ x, size_t n_c, const SEEDS seeds, uint32_t stream_id) {
+template <class SEEDS, bool PRIOR>
+__global__ void smp_fill_normal_clips_kernel(float* __restrict__ x, size_t n_c, const SEEDS seeds, uint32_t stream_id,
+                                             const float* __restrict__ prior) {
     const uint64_t seed = seeds[blockIdx.y];
     x += (size_t)blockIdx.y * n_c;
+    if (PRIOR) prior += (size_t)blockIdx.y * n_c;
     for (size_t g = (size_t)blockIdx.x * blockDim.x + threadIdx.x; g * 4 < n_c; g += (size_t)gridDim.x * blockDim.x) {
         float z[4];
         normal4(seed, stream_id, g, z);
+        if (PRIOR) smp_prior4<false>(prior, g, n_c, z);
         smp_store4<false>(x, g, n_c, z);
     }
 }
@@ -250,11 +273,12 @@ __global__ void smp_fill_normal_clips_kernel(float* __restrict__ x, size_t n_c, 
 // smp_ddpm_elem at step t = *t_dev with tables [3][T] = c1, c2, sigma; z: noise[t] or Philox (seed, t).
 // seed_dev non-null (few-step sampler): the Philox seed is read from device memory instead of `seed`.
 // CLIP (schedule sampler only): n_all elements in all, this grid row's clip with its own seed (ClipSeeds).
-template <bool CLIP>
+// PRIOR (schedule sampler only): z <- prior z, prior [n_all] (dws_sampler_set_prior).
+template <bool CLIP, bool PRIOR>
 __global__ void smp_update_kernel(float* __restrict__ x, const float* __restrict__ eps,
                                   const float* __restrict__ tables, int* __restrict__ t_dev,
                                   const float* __restrict__ noise, uint64_t seed, const uint64_t* seed_dev, size_t n_all,
-                                  int T, const ClipSeeds cs) {
+                                  int T, const ClipSeeds cs, const float* __restrict__ prior) {
     const int t = __builtin_amdgcn_readfirstlane(*(volatile int*)t_dev);
     if (CLIP) seed = cs.seeds[blockIdx.y];
     else if (seed_dev) seed = *(const volatile uint64_t*)seed_dev;
@@ -265,15 +289,20 @@ __global__ void smp_update_kernel(float* __restrict__ x, const float* __restrict
         const size_t off = (size_t)blockIdx.y * cs.n_c;
         x += off; eps += off;
         if (nz) nz += off;
+        if (PRIOR) prior += off;
     }
     for (size_t g = (size_t)blockIdx.x * blockDim.x + threadIdx.x; g * 4 < n; g += (size_t)gridDim.x * blockDim.x) {
         float z[4] = {0.f, 0.f, 0.f, 0.f};
         if (t > 0 && !nz) normal4(seed, (uint32_t)t, g, z);
+        if (PRIOR && t > 0) {
+            if (nz) smp_load4<false>(nz, g, n, z);
+            smp_prior4<false>(prior, g, n, z);
+        }
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             const size_t i = g * 4 + j;
             if (i >= n) break;
-            x[i] = smp_ddpm_elem(x[i], eps[i], t > 0 && nz ? nz[i] : z[j], c1, c2, sg, t > 0);
+            x[i] = smp_ddpm_elem(x[i], eps[i], !PRIOR && t > 0 && nz ? nz[i] : z[j], c1, c2, sg, t > 0);
         }
     }
     __syncthreads();
@@ -296,6 +325,8 @@ __global__ void smp_update_kernel(float* __restrict__ x, const float* __restrict
 //   VEC   every group of 4 is in range and all pointers are 16-byte aligned -> float4 for the floats and the four mask
 //         bytes of a group as one 32-bit load.
 //   CLIP  per-clip seeds (ClipSeeds above): the grid row's clip of every array, its seed in the place of the state's.
+//   PRIOR adaptive prior (dws_sampler_set_prior): z and zk, injected or drawn, are multiplied by prior [B, C L] at their
+//         own positions (smp_prior_elem) before the update reads them.  The other instances never load the field.
 // What every flavour reads travels as plain kernel arguments, the rest in one by-value struct whose fields a flavour
 // that does not need them never loads.  (Plain arguments are fetched ahead of the ordered reads of the state, fields of a
 // struct only behind them; this way the plain DDIM instance is, instruction for instruction, the kernel it took over from.)
@@ -308,6 +339,7 @@ struct StepMore {
     const int* step_of;          // PROG ...
     int V;
     ClipSeeds clip;              // CLIP
+    const float* prior;          // PRIOR
 };
 
 struct StepArgs {
@@ -322,7 +354,7 @@ struct StepArgs {
     StepMore more;
 };
 
-template <int KIND, bool EDIT, bool PROG, bool VEC, bool CLIP>
+template <int KIND, bool EDIT, bool PROG, bool VEC, bool CLIP, bool PRIOR>
 __global__ void smp_step_kernel(float* __restrict__ x, const float* __restrict__ eps, const float* __restrict__ tab,
                                 int* __restrict__ st, const float* __restrict__ noise, size_t n_all, int S,
                                 const StepMore m) {
@@ -345,6 +377,7 @@ __global__ void smp_step_kernel(float* __restrict__ x, const float* __restrict__
     float* hist = MULTI ? m.hist + off : nullptr;
     const float* y = EDIT ? m.y + off : nullptr;
     const uint8_t* mask = EDIT ? m.mask + off : nullptr;
+    const float* prior = PRIOR ? m.prior + off : nullptr;
     if (CLIP) {
         x += off; eps += off;
         if (nz) nz += off;
@@ -364,6 +397,15 @@ __global__ void smp_step_kernel(float* __restrict__ x, const float* __restrict__
         }
         if (add && !nz) normal4(seed, (uint32_t)v, g, z);
         if (mk && s > 0 && !kz) normal4(seed, (uint32_t)(R + 1 + v), g, zk);
+        if (PRIOR && (add || (mk && s > 0))) {
+            float sg[4] = {0.f, 0.f, 0.f, 0.f};
+            smp_load4<VEC>(prior, g, n, sg);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                z[j] = smp_prior_elem(sg[j], z[j]);
+                zk[j] = smp_prior_elem(sg[j], zk[j]);
+            }
+        }
         float r[4];
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
@@ -390,10 +432,10 @@ __global__ void smp_step_kernel(float* __restrict__ x, const float* __restrict__
 //   x = (ja * x) + (jb * z)      ja = jump[v], jb = jump[V + v] (sampling.jump_coefficients)
 // z: noise[v] or Philox stream v in normal4's layout.  No network runs.  The jump re-noises the state, so the last block
 // also clears the history-valid word: the multistep kind's next step is first order.
-template <bool VEC, bool CLIP>
+template <bool VEC, bool CLIP, bool PRIOR>
 __global__ void smp_jump_kernel(float* __restrict__ x, const float* __restrict__ jump, int* __restrict__ st,
                                 const int* __restrict__ step_of, const float* __restrict__ noise, size_t n_all, int V,
-                                const ClipSeeds cs) {
+                                const ClipSeeds cs, const float* __restrict__ prior) {
     const int v = __builtin_amdgcn_readfirstlane(*(volatile int*)(st + 4));
     const uint64_t seed = CLIP ? cs.seeds[blockIdx.y] : *(const volatile uint64_t*)(st + 2);
     const float ja = jump[v], jb = jump[V + v];
@@ -403,12 +445,14 @@ __global__ void smp_jump_kernel(float* __restrict__ x, const float* __restrict__
         const size_t off = (size_t)blockIdx.y * cs.n_c;
         x += off;
         if (nz) nz += off;
+        if (PRIOR) prior += off;
     }
     for (size_t g = (size_t)blockIdx.x * blockDim.x + threadIdx.x; g * 4 < n; g += (size_t)gridDim.x * blockDim.x) {
         float xv[4] = {0.f, 0.f, 0.f, 0.f}, z[4] = {0.f, 0.f, 0.f, 0.f};
         smp_load4<VEC>(x, g, n, xv);
         if (nz) smp_load4<VEC>(nz, g, n, z);
         else normal4(seed, (uint32_t)v, g, z);
+        if (PRIOR) smp_prior4<VEC>(prior, g, n, z);
 #pragma unroll
         for (int j = 0; j < 4; ++j) xv[j] = smp_mix_elem(ja, xv[j], jb, z[j]);
         smp_store4<VEC>(x, g, n, xv);
@@ -420,24 +464,29 @@ __global__ void smp_jump_kernel(float* __restrict__ x, const float* __restrict__
 // Partial start in q-sample mode: x holds clean audio and becomes the state at step s0,
 //   x = (n1 * x) + (n2 * z0)      n1 = sqrt(level[s0]), n2 = sqrt(1 - level[s0])
 // z0: the injected tensor or Philox stream `stream_id` (2S + 1).
-template <bool CLIP>
+template <bool CLIP, bool PRIOR>
 __global__ void smp_qsample_kernel(float* __restrict__ x, const float* __restrict__ z0, float n1, float n2, size_t n_all,
-                                   uint64_t seed, uint32_t stream_id, const ClipSeeds cs) {
+                                   uint64_t seed, uint32_t stream_id, const ClipSeeds cs, const float* __restrict__ prior) {
     const size_t n = CLIP ? cs.n_c : n_all;
     if (CLIP) {
         const size_t off = (size_t)blockIdx.y * cs.n_c;
         seed = cs.seeds[blockIdx.y];
         x += off;
         if (z0) z0 += off;
+        if (PRIOR) prior += off;
     }
     for (size_t g = (size_t)blockIdx.x * blockDim.x + threadIdx.x; g * 4 < n; g += (size_t)gridDim.x * blockDim.x) {
         float z[4] = {0.f, 0.f, 0.f, 0.f};
         if (!z0) normal4(seed, stream_id, g, z);
+        if (PRIOR) {
+            if (z0) smp_load4<false>(z0, g, n, z);
+            smp_prior4<false>(prior, g, n, z);
+        }
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             const size_t i = g * 4 + j;
             if (i >= n) break;
-            x[i] = smp_mix_elem(n1, x[i], n2, z0 ? z0[i] : z[j]);
+            x[i] = smp_mix_elem(n1, x[i], n2, !PRIOR && z0 ? z0[i] : z[j]);
         }
     }
 }
@@ -489,12 +538,22 @@ static void smp_launch_step(int kind, bool vec, const StepArgs& a, hipStream_t s
     const dim3 grid = smp_grid(a.n, a.clips, a.more.clip.n_c);
     smp_dispatch(kind, vec, [&](auto K, auto VEC) {
         if constexpr (EDIT || decltype(K)::value != DWS_SAMPLER_DDPM) {
-            if (a.clips)
-                hipLaunchKernelGGL((smp_step_kernel<decltype(K)::value, EDIT, PROG, decltype(VEC)::value, true>), grid,
-                                   dim3(256), 0, s, a.x, a.eps, a.tab, a.st, a.noise, a.n, a.S, a.more);
-            else
-                hipLaunchKernelGGL((smp_step_kernel<decltype(K)::value, EDIT, PROG, decltype(VEC)::value, false>), grid,
-                                   dim3(256), 0, s, a.x, a.eps, a.tab, a.st, a.noise, a.n, a.S, a.more);
+            const auto launch = [&](auto CLIP, auto PRIOR) {
+                hipLaunchKernelGGL((smp_step_kernel<decltype(K)::value, EDIT, PROG, decltype(VEC)::value,
+                                                    decltype(CLIP)::value, decltype(PRIOR)::value>),
+                                   grid, dim3(256), 0, s, a.x, a.eps, a.tab, a.st, a.noise, a.n, a.S, a.more);
+            };
+            // (the multistep kind draws no update noise: unedited, its prior instance would be the plain one, and is not built)
+            constexpr bool HAS_PRIOR = EDIT || decltype(K)::value != DWS_SAMPLER_DPMPP2M;
+            bool prior = false;
+            if constexpr (HAS_PRIOR) {
+                prior = a.more.prior != nullptr;
+                if (prior && a.clips) launch(std::true_type{}, std::true_type{});
+                else if (prior) launch(std::false_type{}, std::true_type{});
+            }
+            if (prior) return;
+            if (a.clips) launch(std::true_type{}, std::false_type{});
+            else launch(std::false_type{}, std::false_type{});
         }
     });
 }
@@ -572,8 +631,8 @@ static int one_step(dws_model* m, float* x, const float* noise, uint64_t seed, i
     const int st = m->forward(x, nullptr, m->smp.eps.f(), s);
     m->step_idx = nullptr;
     DWS_TRY(st);
-    hipLaunchKernelGGL(smp_update_kernel<false>, dim3(smp_blocks(n)), dim3(256), 0, s, x, m->smp.eps.f(), m->smp.tables.f(),
-                       t_dev, noise, seed, (const uint64_t*)nullptr, n, T, ClipSeeds{});
+    hipLaunchKernelGGL((smp_update_kernel<false, false>), dim3(smp_blocks(n)), dim3(256), 0, s, x, m->smp.eps.f(),
+                       m->smp.tables.f(), t_dev, noise, seed, (const uint64_t*)nullptr, n, T, ClipSeeds{}, (const float*)nullptr);
     return DWS_OK;
 }
 
@@ -617,7 +676,8 @@ int sampler_run(dws_model* m, float* x, const float* alpha, const float* alpha_b
     DWS_TRY(upload_tables(m, alpha, alpha_bar, sigma, T, s));
     if (init_from_seed) {
         const size_t n = (size_t)m->B * m->d.in_channels * m->L;
-        hipLaunchKernelGGL(smp_fill_normal_kernel, dim3(smp_blocks(n)), dim3(256), 0, s, x, n, seed, (uint32_t)T);
+        hipLaunchKernelGGL(smp_fill_normal_kernel<false>, dim3(smp_blocks(n)), dim3(256), 0, s, x, n, seed, (uint32_t)T,
+                           (const float*)nullptr);
     }
     return run_steps(m, x, T, T - 1, T, noise, seed, use_graph, s);
 }
@@ -660,12 +720,19 @@ static int schedule_step(dws_model* m, int kind, bool vec, const StepArgs& a, bo
         smp_launch_step<true, true>(kind, vec, a, s);
     else if (a.more.mask)
         smp_launch_step<true, false>(kind, vec, a, s);
-    else if (kind == DWS_SAMPLER_DDPM && a.clips)
-        hipLaunchKernelGGL(smp_update_kernel<true>, smp_grid(a.n, a.clips, a.more.clip.n_c), dim3(256), 0, s, a.x, a.eps,
-                           a.tab, a.st, a.noise, (uint64_t)0, (const uint64_t*)nullptr, a.n, a.S, a.more.clip);
-    else if (kind == DWS_SAMPLER_DDPM)
-        hipLaunchKernelGGL(smp_update_kernel<false>, dim3(smp_blocks(a.n)), dim3(256), 0, s, a.x, a.eps, a.tab, a.st, a.noise,
-                           (uint64_t)0, reinterpret_cast<const uint64_t*>(a.st + 2), a.n, a.S, ClipSeeds{});
+    else if (kind == DWS_SAMPLER_DDPM) {
+        const dim3 grid = smp_grid(a.n, a.clips, a.more.clip.n_c);
+        const uint64_t* seed_dev = a.clips ? nullptr : reinterpret_cast<const uint64_t*>(a.st + 2);
+        const ClipSeeds cs = a.clips ? a.more.clip : ClipSeeds{};
+        const auto launch = [&](auto CLIP, auto PRIOR) {
+            hipLaunchKernelGGL((smp_update_kernel<decltype(CLIP)::value, decltype(PRIOR)::value>), grid, dim3(256), 0, s, a.x,
+                               a.eps, a.tab, a.st, a.noise, (uint64_t)0, seed_dev, a.n, a.S, cs, a.more.prior);
+        };
+        if (a.clips && a.more.prior) launch(std::true_type{}, std::true_type{});
+        else if (a.clips) launch(std::true_type{}, std::false_type{});
+        else if (a.more.prior) launch(std::false_type{}, std::true_type{});
+        else launch(std::false_type{}, std::false_type{});
+    }
     else
         smp_launch_step<false, false>(kind, vec, a, s);
     if (cfg) DWS_HIP(hipMemcpyAsync(a.x + a.n, a.x, a.n * 4, hipMemcpyDeviceToDevice, s));   // the second half of the state follows the first
@@ -737,6 +804,13 @@ int sampler_run_schedule(dws_model* m, float* x, int kind, int S, const float* n
     DWS_CHECK(clips == 0 || clips == (cfg ? m->B / 2 : m->B), DWS_ERR_INVALID,
               "sampler: a table of %d clip seeds (dws_sampler_set_clip_seeds) for a sampler state of %lld clips", clips,
               (long long)(cfg ? m->B / 2 : m->B));
+    // adaptive prior: a table at the shape of the sampler state; every noise site below scales its z by it
+    DWS_CHECK(!cfg || !m->smp.prior_on, DWS_ERR_UNSUPPORTED,
+              "classifier-free guidance with an adaptive prior (dws_sampler_set_prior) is not built");
+    DWS_CHECK(!m->smp.prior_on || (m->smp.prior_B == m->B && m->smp.prior_n == m->d.out_channels * m->L), DWS_ERR_INVALID,
+              "sampler: a prior table of [%lld, %lld] (dws_sampler_set_prior) for a sampler state of [%lld, %lld]",
+              (long long)m->smp.prior_B, (long long)m->smp.prior_n, (long long)m->B, (long long)(m->d.out_channels * m->L));
+    const float* prior = m->smp.prior_on ? m->smp.prior.f() : nullptr;
     if (m->dirty) DWS_TRY(m->commit(s));
     const size_t nfull = (size_t)m->B * m->d.out_channels * m->L;    // the network's batch
     const size_t n = cfg ? nfull / 2 : nfull;                         // what the caller's x, the noise and the update span
@@ -787,11 +861,16 @@ int sampler_run_schedule(dws_model* m, float* x, int kind, int S, const float* n
     const dim3 grid = smp_grid(n, clips, clip.n_c);     // of every launch here that draws
     hipStream_t q = s;
     if (use_graph) DWS_TRY(engine_after_caller(m, s, &q));
-    if (init_from_seed && clips)
-        hipLaunchKernelGGL(smp_fill_normal_clips_kernel<const uint64_t*>, grid, dim3(256), 0, q, xr, clip.n_c, clip.seeds,
-                           (uint32_t)R);
+    if (init_from_seed && clips && prior)
+        hipLaunchKernelGGL((smp_fill_normal_clips_kernel<const uint64_t*, true>), grid, dim3(256), 0, q, xr, clip.n_c,
+                           clip.seeds, (uint32_t)R, prior);
+    else if (init_from_seed && clips)
+        hipLaunchKernelGGL((smp_fill_normal_clips_kernel<const uint64_t*, false>), grid, dim3(256), 0, q, xr, clip.n_c,
+                           clip.seeds, (uint32_t)R, prior);
+    else if (init_from_seed && prior)
+        hipLaunchKernelGGL(smp_fill_normal_kernel<true>, dim3(smp_blocks(n)), dim3(256), 0, q, xr, n, seed, (uint32_t)R, prior);
     else if (init_from_seed)
-        hipLaunchKernelGGL(smp_fill_normal_kernel, dim3(smp_blocks(n)), dim3(256), 0, q, xr, n, seed, (uint32_t)R);
+        hipLaunchKernelGGL(smp_fill_normal_kernel<false>, dim3(smp_blocks(n)), dim3(256), 0, q, xr, n, seed, (uint32_t)R, prior);
     else if (staged)
         DWS_HIP(hipMemcpyAsync(xr, x, n * 4, hipMemcpyDeviceToDevice, q));
     if (cfg) DWS_HIP(hipMemcpyAsync(xr + n, xr, n * 4, hipMemcpyDeviceToDevice, q));    // x_T into both halves
@@ -805,14 +884,17 @@ int sampler_run_schedule(dws_model* m, float* x, int kind, int S, const float* n
         DWS_HIP(hipMemcpyAsync(m->smp.sch_known.p, e->known, n * 4, hipMemcpyDeviceToDevice, q));
         DWS_HIP(hipMemcpyAsync(m->smp.sch_mask.p, e->mask, n, hipMemcpyDeviceToDevice, q));
     }
-    if (qsample && clips)
-        hipLaunchKernelGGL(smp_qsample_kernel<true>, grid, dim3(256), 0, q, xr, e->start_noise,
-                           e->edit_coef[2 * (size_t)S + start], e->edit_coef[3 * (size_t)S + start], n, seed,
-                           (uint32_t)(2 * R + 1), clip);
-    else if (qsample)
-        hipLaunchKernelGGL(smp_qsample_kernel<false>, dim3(smp_blocks(n)), dim3(256), 0, q, xr, e->start_noise,
-                           e->edit_coef[2 * (size_t)S + start], e->edit_coef[3 * (size_t)S + start], n, seed,
-                           (uint32_t)(2 * R + 1), ClipSeeds{});
+    if (qsample) {
+        const auto launch = [&](auto CLIP, auto PRIOR) {
+            hipLaunchKernelGGL((smp_qsample_kernel<decltype(CLIP)::value, decltype(PRIOR)::value>), grid, dim3(256), 0, q, xr,
+                               e->start_noise, e->edit_coef[2 * (size_t)S + start], e->edit_coef[3 * (size_t)S + start], n,
+                               seed, (uint32_t)(2 * R + 1), clip, prior);
+        };
+        if (clips && prior) launch(std::true_type{}, std::true_type{});
+        else if (clips) launch(std::true_type{}, std::false_type{});
+        else if (prior) launch(std::false_type{}, std::true_type{});
+        else launch(std::false_type{}, std::false_type{});
+    }
     if (cfg) hipLaunchKernelGGL(smp_set_cfg_scale_kernel, dim3(1), dim3(1), 0, q, st, m->smp.cfg_scale);
 
     StepArgs a{};
@@ -821,11 +903,19 @@ int sampler_run_schedule(dws_model* m, float* x, int kind, int S, const float* n
     StepMore& more = a.more;
     more.V = V;
     more.clip = clip;
+    more.prior = prior;
     more.hist = kind == DWS_SAMPLER_DPMPP2M ? m->smp.sch_hist.f() : nullptr;
     if (masked) {
         more.edit = m->smp.sch_edit.f(); more.y = m->smp.sch_known.f(); more.mask = static_cast<const uint8_t*>(m->smp.sch_mask.p);
         more.known_noise = known_noise; more.step_of = step_of;
     }
+    const auto jump_launch = [&](auto PRIOR) {
+        constexpr bool P = decltype(PRIOR)::value;
+        if (clips && vec) hipLaunchKernelGGL((smp_jump_kernel<true, true, P>), grid, dim3(256), 0, q, xr, jump, st, step_of, noise, n, V, clip, prior);
+        else if (clips) hipLaunchKernelGGL((smp_jump_kernel<false, true, P>), grid, dim3(256), 0, q, xr, jump, st, step_of, noise, n, V, clip, prior);
+        else if (vec) hipLaunchKernelGGL((smp_jump_kernel<true, false, P>), grid, dim3(256), 0, q, xr, jump, st, step_of, noise, n, V, clip, prior);
+        else hipLaunchKernelGGL((smp_jump_kernel<false, false, P>), grid, dim3(256), 0, q, xr, jump, st, step_of, noise, n, V, clip, prior);
+    };
     // the walk: `reverse` enqueues one reverse step on q; a jump visit is a launch of its own between them
     const auto walk = [&](const auto& reverse) -> int {
         if (!pg) {
@@ -834,10 +924,8 @@ int sampler_run_schedule(dws_model* m, float* x, int kind, int S, const float* n
         }
         for (int i = 0; i < V; ++i) {
             if (pg->visit_step[i] >= 0) DWS_TRY(reverse());
-            else if (clips && vec) hipLaunchKernelGGL((smp_jump_kernel<true, true>), grid, dim3(256), 0, q, xr, jump, st, step_of, noise, n, V, clip);
-            else if (clips) hipLaunchKernelGGL((smp_jump_kernel<false, true>), grid, dim3(256), 0, q, xr, jump, st, step_of, noise, n, V, clip);
-            else if (vec) hipLaunchKernelGGL((smp_jump_kernel<true, false>), grid, dim3(256), 0, q, xr, jump, st, step_of, noise, n, V, clip);
-            else hipLaunchKernelGGL((smp_jump_kernel<false, false>), grid, dim3(256), 0, q, xr, jump, st, step_of, noise, n, V, clip);
+            else if (prior) jump_launch(std::true_type{});
+            else jump_launch(std::false_type{});
         }
         return DWS_OK;
     };
@@ -846,14 +934,15 @@ int sampler_run_schedule(dws_model* m, float* x, int kind, int S, const float* n
         DWS_TRY(walk(step));
     } else {
         // the edited, the resampling and the guided step have graphs of their own beside the plain one, and each of the
-        // four one per form of seed (the per-clip step is other kernel instances on another grid): the kinds of call may
-        // alternate without a new capture
+        // four one per form of seed (the per-clip step is other kernel instances on another grid) and per prior on / off
+        // (the PRIOR instances; the table sits in a model-owned buffer, so a new one replays the step): the kinds of call
+        // may alternate without a new capture
         SamplerState::SchGraph& have = m->smp.sch_graphs[cfg ? SamplerState::SCH_CFG : pg ? SamplerState::SCH_PROG
                                                   : masked ? SamplerState::SCH_EDIT : SamplerState::SCH_PLAIN]
-                                                 [(clips ? 1 : 0) + (m->ragged() ? 2 : 0)];
+                                                 [(clips ? 1 : 0) + (m->ragged() ? 2 : 0) + (prior ? 4 : 0)];
         const SamplerState::SchKey key{m->B, m->L, S, kind, vec ? 1 : 0, a.tab, noise, a.eps, xr, st, m->step_table_gen,
                                     more.edit, more.y, more.mask, known_noise, V, pg ? m->smp.sch_prog.p : nullptr, more.hist,
-                                    clip.seeds, m->ragged() ? m->lengths_dev.p : nullptr};
+                                    clip.seeds, m->ragged() ? m->lengths_dev.p : nullptr, prior};
         DWS_TRY(capture_step(m, q, have.exec, key == have.key, step));
         have.key = key;
         DWS_TRY(walk([&]() -> int {
@@ -906,7 +995,8 @@ int sampler_run_program(dws_model* m, float* x, int kind, int S, const float* ne
 int philox_normal(float* x, int64_t n, uint64_t seed, uint32_t stream_id, hipStream_t s) {
     DWS_CHECK(x && n >= 0, DWS_ERR_INVALID, "dws_philox_normal: null x or n = %lld", (long long)n);
     if (n == 0) return DWS_OK;
-    hipLaunchKernelGGL(smp_fill_normal_kernel, dim3(smp_blocks((size_t)n)), dim3(256), 0, s, x, (size_t)n, seed, stream_id);
+    hipLaunchKernelGGL(smp_fill_normal_kernel<false>, dim3(smp_blocks((size_t)n)), dim3(256), 0, s, x, (size_t)n, seed, stream_id,
+                       (const float*)nullptr);
     DWS_HIP(hipGetLastError());
     return DWS_OK;
 }
@@ -922,8 +1012,8 @@ int philox_normal_clips(float* x, int64_t B, int64_t n_per_clip, const uint64_t*
         const int rows = (int)std::min<int64_t>(SeedChunk::N, B - b0);
         SeedChunk chunk{};
         std::memcpy(chunk.s, seeds + b0, (size_t)rows * 8);
-        hipLaunchKernelGGL(smp_fill_normal_clips_kernel<SeedChunk>, smp_grid(n_c * rows, rows, n_c), dim3(256), 0, s,
-                           x + (size_t)b0 * n_c, n_c, chunk, stream_id);
+        hipLaunchKernelGGL((smp_fill_normal_clips_kernel<SeedChunk, false>), smp_grid(n_c * rows, rows, n_c), dim3(256), 0, s,
+                           x + (size_t)b0 * n_c, n_c, chunk, stream_id, (const float*)nullptr);
     }
     DWS_HIP(hipGetLastError());
     return DWS_OK;

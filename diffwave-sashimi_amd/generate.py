@@ -159,9 +159,10 @@ def local_directory(name, model_cfg, diffusion_cfg, dataset_cfg, output_director
     return local_path, output_directory
 
 
-def smooth_ckpt(path, min_ckpt, max_ckpt):
+def smooth_ckpt(path, min_ckpt, max_ckpt, priors=None):
     """``utils.py:47-74,154-166`` (experimental in the reference): running arithmetic mean of the
-    ``model_state_dict`` of every checkpoint with ``min_ckpt < iteration <= max_ckpt``."""
+    ``model_state_dict`` of every checkpoint with ``min_ckpt < iteration <= max_ckpt``.  ``priors``: a list that receives
+    ``(iteration, prior entry or None)`` of every checkpoint that went into the mean."""
     ckpts = []
     for f in os.listdir(path):
         if len(f) > 4 and f.endswith(".pkl"):
@@ -175,9 +176,12 @@ def smooth_ckpt(path, min_ckpt, max_ckpt):
     for n, it in enumerate(sorted(ckpts)):
         model_path = os.path.join(path, f"{it}.pkl")
         try:
-            sd = torch.load(model_path, map_location="cpu")["model_state_dict"]
+            checkpoint = torch.load(model_path, map_location="cpu")
+            sd = checkpoint["model_state_dict"]
         except Exception:
             raise Exception(f"No valid model found at iteration {it}, path {model_path}")
+        if priors is not None:
+            priors.append((it, checkpoint.get("prior")))
         state_dict = sd if state_dict is None else {k: (state_dict[k] * n + sd[k]) / (n + 1) for k in sd}
     return state_dict
 
@@ -268,6 +272,74 @@ def _check_mel_names(mel_names, mel_name, clip_seeds, seed, **others):
     return names
 
 
+PRIOR_KEYS = ("energy_max", "energy_min", "std_min")
+
+
+def prior_settings(prior, energy_max=None, energy_min=None, std_min=None, unconditional=False, where="generate"):
+    """The adaptive-prior keys of a CLI run (``+{where}.prior=energy +{where}.prior_energy_max=E
+    [+{where}.prior_energy_min=0 +{where}.prior_std_min=0.1]``), checked before a model is built (ValueError).  Returns
+    None (no key given), ``"none"`` (``prior=none``: N(0, I) whatever the checkpoint says) or the dict
+    ``{"kind": "energy", "energy_max", "energy_min", "std_min"}`` of ``mel.prior_std_from_mel``'s settings."""
+    from .mel import _check_prior_range
+    given = [k for k, v in (("prior_energy_max", energy_max), ("prior_energy_min", energy_min), ("prior_std_min", std_min))
+             if v is not None]
+    if prior is None or prior == "none":
+        if given:
+            raise ValueError(f"{where}.{given[0]} needs {where}.prior=energy")
+        return prior
+    if prior != "energy":
+        raise ValueError(f"{where}.prior={prior!r}: expected energy or none")
+    if unconditional:
+        raise ValueError(f"{where}.prior=energy needs a mel-conditional model (model.unconditional=false): the prior is "
+                         "read off the conditioning mel")
+    if energy_max is None:
+        raise ValueError(f"{where}.prior=energy needs {where}.prior_energy_max (the largest frame energy of the dataset, "
+                         "mel.mel_energy; no default is chosen: it depends on the dataset)")
+    if any(isinstance(v, (bool, str)) for v in (energy_max, energy_min, std_min)):
+        raise ValueError(f"{where}.prior_energy_max / prior_energy_min / prior_std_min: expected numbers")
+    e_min, e_max, s_min = _check_prior_range(energy_max, 0.0 if energy_min is None else energy_min,
+                                             0.1 if std_min is None else std_min)
+    return {"kind": "energy", "energy_max": e_max, "energy_min": e_min, "std_min": s_min}
+
+
+def prior_hop(model_cfg, dataset_cfg):
+    """Samples per mel frame of the prior: ``prod(model.mel_upsample)``, which must be ``dataset.hop_length`` (the run
+    length is ``frames x hop_length``) -- ValueError otherwise."""
+    hop = int(np.prod([int(v) for v in model_cfg.get("mel_upsample", [16, 16])]))
+    if dataset_cfg.get("hop_length") != hop:
+        raise ValueError(f"adaptive prior: dataset.hop_length={dataset_cfg.get('hop_length')!r} is not the product of "
+                         f"model.mel_upsample={list(model_cfg.get('mel_upsample', [16, 16]))} = {hop} (sigma repeats a "
+                         "frame's value over the samples the conditioner upsamples it to)")
+    return hop
+
+
+def same_prior(a, b):
+    """Two ``prior`` entries (None: N(0, I)) name the same prior."""
+    if a is None or b is None:
+        return a is None and b is None
+    return a.get("kind") == b.get("kind") and all(k in a and k in b and float(a[k]) == float(b[k]) for k in PRIOR_KEYS)
+
+
+def resolve_prior(settings, entry, given=()):
+    """The prior a ``generate`` run uses: ``settings`` (``prior_settings``) against the checkpoint's ``prior`` entry (None:
+    it has none).  ``"none"`` -> None; no keys -> the entry; keys that contradict the entry -> ValueError (``given``: the
+    value keys the run spelled out; the others follow the entry)."""
+    if settings == "none":
+        return None
+    if entry is not None and (not isinstance(entry, dict) or entry.get("kind") != "energy"
+                              or any(k not in entry for k in PRIOR_KEYS)):
+        raise ValueError(f"the checkpoint's prior entry {entry!r} is not one this version writes")
+    if settings is None:
+        return None if entry is None else dict(entry)
+    if entry is None:
+        return settings
+    for k in PRIOR_KEYS:
+        if k in given and float(entry[k]) != float(settings[k]):
+            raise ValueError(f"generate.prior_{k}={settings[k]!r} contradicts the checkpoint, which was trained with "
+                             f"{k}={entry[k]!r} (drop the key, or generate.prior=none for N(0, I))")
+    return dict(entry)
+
+
 def _check_ragged_hop(model_cfg, dataset_cfg):
     """``generate.mel_names`` on SaShiMi, before a model is built (ValueError): an utterance is ``frames x hop_length``
     samples long, and SaShiMi takes per-clip lengths that are multiples of the product of its pooling factors only (a
@@ -318,7 +390,7 @@ def generate(rank, diffusion_cfg, model_cfg, dataset_cfg, ckpt_iter="max", n_sam
              start_name=None, start_step=None, start_noise=True, resample_jump=None, resample_n=None, spacing=None,
              guide_name=None, guide_op=None, guide_clip=None, guide_factor=None, guide_scale=None, label=None,
              cfg_scale=None, ema=None, clip_seeds=None, clips=None, num_ranks=None, report_mel=None, mel_errors=None,
-             mel_names=None):
+             mel_names=None, prior=None, prior_energy_max=None, prior_energy_min=None, prior_std_min=None):
     """``generate.py:58-200``.  ``ckpt_iter`` may additionally be ``"init"``: seeded random weights
     (no checkpoint), for smoke runs without trained weights.  ``precision`` (not in the reference; CLI:
     ``+engine.precision=bf16x6|f16x3``): the engine's opt-in matrix arithmetic, see ``include/dws.h``.
@@ -383,7 +455,16 @@ def generate(rank, diffusion_cfg, model_cfg, dataset_cfg, ckpt_iter="max", n_sam
     position still costs its full time.  Does not combine with the editing, restoration, label and ``clips`` keys.
     Returns the list of the trimmed clips [1, len_k] in the order of ``mel_names`` (None for another rank's).  ``clips``
     (a list of global clip numbers; needs ``clip_seeds``) generates only these, under their usual names: rank r of N takes
-    ``clips[r::N]`` in batches of up to ``batch_size`` (``clip_plan``).  Returns the audio of the clips this rank made."""
+    ``clips[r::N]`` in batches of up to ``batch_size`` (``clip_plan``).  Returns the audio of the clips this rank made.
+
+    Adaptive prior (not in the reference; PriorGrad, Lee et al., ICLR 2022; mel-conditional models, every ``sampler``,
+    ``mel_name`` and ``mel_names``, with the clip-seed, editing, resampling and guide keys): ``prior=energy`` with
+    ``prior_energy_max`` (required) and ``prior_energy_min`` (0) / ``prior_std_min`` (0.1) runs from
+    N(0, diag(sigma^2)), sigma = ``mel.prior_std_from_mel`` of the conditioning mel, the ``prior_std`` of the samplers.
+    Without these keys a checkpoint's ``prior`` entry (written by ``train.prior=energy``) is used and printed;
+    ``prior=none`` forces N(0, I); value keys that contradict the entry and ``cfg_scale`` with a prior raise ValueError.
+    A model must have been trained with the prior it is sampled with.  What the samples sound like has not been
+    measured."""
     from .models import construct_model
     from .models.utils import check_n_classes
     from .sampling import (calc_diffusion_hyperparams, ddim_steps, declip_operator, logsnr_steps, lowpass_operator,
@@ -394,6 +475,15 @@ def generate(rank, diffusion_cfg, model_cfg, dataset_cfg, ckpt_iter="max", n_sam
 
     if ckpt_smooth is not None or ckpt_iter == "init":     # checked here, before a model is built
         weights_key(None, ema, ckpt_smooth)
+    prior_cfg = prior_settings(prior, prior_energy_max, prior_energy_min, prior_std_min, model_cfg.get("unconditional"))
+    prior_given = [k for k, v in zip(PRIOR_KEYS, (prior_energy_max, prior_energy_min, prior_std_min)) if v is not None]
+    if isinstance(prior_cfg, dict) and cfg_scale is not None:
+        raise ValueError("generate.cfg_scale does not combine with generate.prior=energy (classifier-free guidance with an "
+                         "adaptive prior is not built)")
+    if isinstance(prior_cfg, dict):
+        prior_hop(model_cfg, dataset_cfg)
+    if isinstance(prior_cfg, dict) and mel_name is None and mel_names is None:
+        raise ValueError("generate.prior=energy needs generate.mel_name or generate.mel_names (the conditioning mel)")
     if mel_names is not None:
         mel_names = _check_mel_names(mel_names, mel_name, clip_seeds, seed, known_name=known_name, start_name=start_name,
                                      resample_jump=resample_jump, guide_name=guide_name, guide_op=guide_op, label=label,
@@ -517,6 +607,7 @@ def generate(rank, diffusion_cfg, model_cfg, dataset_cfg, ckpt_iter="max", n_sam
         net.set_option("precision", precision)     # NotImplementedError where the engine has no such kernels for this model
 
     ckpt_path = os.path.join(exp_root, local_path, "checkpoint")
+    prior_entry = None      # what the checkpoint was trained with
     if ckpt_iter == "init":
         ckpt_iter = 0
     else:
@@ -536,11 +627,35 @@ def generate(rank, diffusion_cfg, model_cfg, dataset_cfg, ckpt_iter="max", n_sam
                 raise Exception(f"No valid model found ({model_file}: {e})")
             if key == "ema_state_dict":
                 print(f"sampling from the EMA weights of iteration {ckpt_iter} (generate.ema=false: the raw weights)")
+            prior_entry = checkpoint.get("prior")
         else:                       # `generate.py:113-115`: average of the checkpoints in (ckpt_smooth, ckpt_iter]
-            state_dict = smooth_ckpt(ckpt_path, int(ckpt_smooth), ckpt_iter)
+            entries = []
+            state_dict = smooth_ckpt(ckpt_path, int(ckpt_smooth), ckpt_iter, priors=entries)
             if state_dict is None:
                 raise Exception(f"No checkpoints in ({ckpt_smooth}, {ckpt_iter}] under {ckpt_path}")
+            odd = [it for it, e in entries if not same_prior(e, entries[0][1])]
+            if odd:     # weights trained towards different priors have no common one to be sampled from
+                raise ValueError(f"generate.ckpt_smooth: the checkpoints in ({ckpt_smooth}, {ckpt_iter}] were trained with "
+                                 f"different priors (iteration {entries[0][0]}: {entries[0][1]!r}, iteration {odd[0]}: "
+                                 f"{dict(entries)[odd[0]]!r})")
+            prior_entry = entries[0][1]
             net.load_state_dict(state_dict)
+    prior_cfg = resolve_prior(prior_cfg, prior_entry, prior_given)
+    if prior_cfg is not None:
+        if cfg_scale is not None:
+            raise ValueError("generate.cfg_scale does not combine with the adaptive prior of the checkpoint "
+                             "(generate.prior=none samples from N(0, I))")
+        hop_of_prior = prior_hop(model_cfg, dataset_cfg)
+        print("adaptive prior{}: energy_max={energy_max:g} energy_min={energy_min:g} std_min={std_min:g}".format(
+            " (the checkpoint's prior entry)" if prior is None else "", **prior_cfg))
+
+    def sigma_of(mel, L):       # the prior's standard deviation [B, 1, L] of a conditioning mel, or nothing
+        if prior_cfg is None or mel is None:
+            return {}
+        from .mel import prior_std_from_mel
+        return {"prior_std": prior_std_from_mel(mel.to(device="cuda", dtype=torch.float32), hop_of_prior, L,
+                                                **{k: prior_cfg[k] for k in PRIOR_KEYS})}
+
     output_directory = os.path.join(output_directory, str(ckpt_iter))
     os.makedirs(output_directory, mode=0o775, exist_ok=True)
 
@@ -574,14 +689,15 @@ def generate(rank, diffusion_cfg, model_cfg, dataset_cfg, ckpt_iter="max", n_sam
             s = [seeds_of_clips(seed, k, 1)[0] for k in batch] if clip_seeds else (None if seed is None else seed + i)
             print(f"batch {i}: L_max = {Lmax}, lengths = {lens}, padded share = "
                   f"{1.0 - sum(lens) / float(len(batch) * Lmax):.3f}")
+            pr = sigma_of(mel, Lmax)     # (each frame on its own: a clip's sigma is what it is alone; its padding is unused)
             if sampler == "aligned":
-                x = sampling_aligned(net, size, diffusion_cfg, condition=mel, seed=s, lengths=lens)
+                x = sampling_aligned(net, size, diffusion_cfg, condition=mel, seed=s, lengths=lens, **pr)
             elif sampler == "ddim":
-                x = sampling_ddim(net, size, dh_train, steps, eta=float(eta or 0.0), condition=mel, seed=s, lengths=lens)
+                x = sampling_ddim(net, size, dh_train, steps, eta=float(eta or 0.0), condition=mel, seed=s, lengths=lens, **pr)
             elif sampler == "dpmpp2m":
-                x = sampling_dpmpp(net, size, dh_train, steps, condition=mel, spacing=spacing, seed=s, lengths=lens)
+                x = sampling_dpmpp(net, size, dh_train, steps, condition=mel, spacing=spacing, seed=s, lengths=lens, **pr)
             else:
-                x = sampling(net, size, dh, condition=mel, seed=s, lengths=lens)
+                x = sampling(net, size, dh, condition=mel, seed=s, lengths=lens, **pr)
             for b, k in enumerate(batch):
                 clips_out[k] = x[b, :, :lens[b]].clone()
         torch.cuda.synchronize()
@@ -647,6 +763,7 @@ def generate(rank, diffusion_cfg, model_cfg, dataset_cfg, ckpt_iter="max", n_sam
             op = lowpass_operator(2 if guide_factor is None else guide_factor)
             guide = dict(measurement=op(rec), operator=op, scale=float(guide_scale))
 
+    prior_one = sigma_of(mel, audio_length)     # [1, 1, L]: every clip of a batch shares the mel
     t0 = time.perf_counter()
     out = []
     # the global clip numbers of every batch: the plan of generate.clip_seeds, or this rank's n_samples in order
@@ -665,12 +782,14 @@ def generate(rank, diffusion_cfg, model_cfg, dataset_cfg, ckpt_iter="max", n_sam
             edit["labels"] = [labels_of[c] for c in class_of]
             if cfg_scale is not None:
                 edit["cfg_scale"] = float(cfg_scale)
+        if prior_one:
+            edit["prior_std"] = prior_one["prior_std"].expand(len(batch), 1, audio_length)
         if guide is not None:
             ddim = sampler == "ddim"
             guide_b = dict(guide, measurement=guide["measurement"][:len(batch)])
             out.append(sampling_guided(net, size, dh_train if ddim else dh, sampler=sampler, steps=steps if ddim else None,
                                        eta=float(eta or 0.0) if ddim else 0.0, condition=mel, seed=s,
-                                       labels=edit.get("labels"), **guide_b))
+                                       labels=edit.get("labels"), prior_std=edit.get("prior_std"), **guide_b))
         elif sampler == "aligned":
             out.append(sampling_aligned(net, size, diffusion_cfg, condition=mel, seed=s, **edit))
         elif sampler == "ddim":

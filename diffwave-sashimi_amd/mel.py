@@ -68,6 +68,67 @@ def _mel_forward(y, win, basis, n_fft, hop, n_mels):
     return out
 
 
+def mel_energy(mel):
+    """Frame energy of a log-mel [B, bands, frames] (natural log, ``TacotronSTFT.mel_spectrogram``):
+    ``sqrt(sum_k exp(mel[b, k, f]))`` -> [B, frames], in the mel's dtype on its device.  The largest value over a
+    dataset is the ``energy_max`` of ``prior_std_from_mel``."""
+    if not isinstance(mel, torch.Tensor) or mel.dim() != 3:
+        raise ValueError(f"mel_energy: the mel has shape {tuple(getattr(mel, 'shape', ()))!r}, expected [B, bands, frames]")
+    return torch.sqrt(torch.exp(mel).sum(dim=1))
+
+
+def _check_prior_range(energy_max, energy_min, std_min):
+    """(e_min, e_max, std_min) as floats, or ValueError."""
+    try:
+        e_max, e_min, s_min = float(energy_max), float(energy_min), float(std_min)
+    except (TypeError, ValueError):
+        raise ValueError(f"prior: energy_max = {energy_max!r}, energy_min = {energy_min!r}, std_min = {std_min!r} "
+                         "(need numbers)")
+    if not (np.isfinite(e_max) and np.isfinite(e_min) and e_max > e_min):
+        raise ValueError(f"prior: energy range {e_min!r} .. {e_max!r} (needs finite values, energy_max > energy_min)")
+    if not 0.0 < s_min <= 1.0:
+        raise ValueError(f"prior: std_min = {std_min!r} (needs 0 < std_min <= 1)")
+    return e_min, e_max, s_min
+
+
+def prior_std_from_mel(mel, hop, L=None, *, energy_max, energy_min=0.0, std_min=0.1):
+    """Standard deviation of the adaptive prior (PriorGrad: Lee et al., ICLR 2022) from a clip's own conditioning mel::
+
+        energy[b, f]   = sqrt(sum_k exp(mel[b, k, f]))
+        sigma_f[b, f]  = clamp((energy[b, f] - energy_min) / (energy_max - energy_min), std_min, 1)
+        sigma[b, 0, l] = sigma_f[b, l // hop]          l = 0 .. L-1   (default L = frames * hop)
+
+    ``mel`` [B, bands, frames] is the engine's log-mel, ``hop`` the samples per frame (``prod(mel_upsample)``).  Each
+    frame stands on its own: a clip's sigma does not depend on the batch around it.  Returns float32 [B, 1, L] on the
+    mel's device: a cuda mel runs ``dws_prior_std_from_mel``, a CPU mel a plain torch evaluation.  ``energy_max`` is
+    required: it is a property of the dataset (the largest ``mel_energy`` over it), and none is at hand to take a default
+    from; ``std_min = 0.1`` is the paper's.  Bad arguments raise ValueError before anything runs."""
+    if not isinstance(mel, torch.Tensor) or mel.dim() != 3 or not mel.dtype.is_floating_point:
+        raise ValueError(f"prior_std_from_mel: the mel has shape {tuple(getattr(mel, 'shape', ()))!r}, expected a float "
+                         "tensor [B, bands, frames]")
+    e_min, e_max, s_min = _check_prior_range(energy_max, energy_min, std_min)
+    B, bands, frames = (int(v) for v in mel.shape)
+    if isinstance(hop, bool) or int(hop) != hop or int(hop) < 1:
+        raise ValueError(f"prior_std_from_mel: hop = {hop!r} (needs an integer >= 1)")
+    hop = int(hop)
+    if B < 1 or bands < 1 or frames < 1:
+        raise ValueError(f"prior_std_from_mel: empty mel {tuple(mel.shape)}")
+    L = frames * hop if L is None else L
+    if isinstance(L, bool) or int(L) != L or not 1 <= int(L) <= frames * hop:
+        raise ValueError(f"prior_std_from_mel: L = {L!r} (needs 1 .. frames * hop = {frames * hop})")
+    L = int(L)
+    mel = mel.detach().to(torch.float32)
+    if mel.device.type != "cuda":
+        sf = ((mel_energy(mel) - e_min) / (e_max - e_min)).clamp(s_min, 1.0)
+        return sf.repeat_interleave(hop, dim=1)[:, None, :L].contiguous()
+    mel = mel.contiguous()
+    out = torch.empty(B, 1, L, device=mel.device, dtype=torch.float32)
+    with torch.cuda.device(mel.device):
+        _lib.check(_lib.load().dws_prior_std_from_mel(mel.data_ptr(), B, bands, frames, hop, L, e_min, e_max, s_min,
+                                                      out.data_ptr(), _lib.current_stream()))
+    return out
+
+
 class _MelBackward(torch.autograd.Function):
     """``dws_mel_spectrogram_backward`` as a node of its own, so that differentiating it (a second-order request) is
     an error with a name instead of a silent zero."""

@@ -79,6 +79,41 @@ def _check_lengths(net, size, lengths, cfg_scale):
     return key
 
 
+def _check_prior(size, prior_std, cfg_scale=None, lengths=None):
+    """Argument checks of ``prior_std=`` before anything runs (ValueError).  Returns the table as a detached float32
+    tensor expanded to ``size`` (on the device it came on), or None.  With ``lengths`` only the positions of each clip
+    below its own length are looked at; the padding of the returned table holds 1."""
+    if prior_std is None:
+        return None
+    if cfg_scale is not None:
+        raise ValueError("sampler: prior_std= (adaptive prior) is not built for classifier-free guidance (cfg_scale=)")
+    B, C, L = (int(v) for v in size)
+    if not isinstance(prior_std, torch.Tensor):
+        prior_std = torch.as_tensor(np.asarray(prior_std, dtype=np.float32))
+    t = prior_std.detach()
+    if tuple(t.shape) not in ((B, 1, L), (B, C, L)) or not t.dtype.is_floating_point:
+        raise ValueError(f"sampler: prior_std of shape {tuple(t.shape)} and dtype {t.dtype} (needs a float tensor "
+                         f"[{B}, 1, {L}] or [{B}, {C}, {L}])")
+    t = t.to(torch.float32).expand(B, C, L)
+    if lengths is not None:
+        valid = torch.arange(L, device=t.device)[None, None, :] < torch.as_tensor(list(lengths), device=t.device)[:, None, None]
+        t = torch.where(valid, t, torch.ones_like(t))
+    if not bool((torch.isfinite(t) & (t > 0)).all()):
+        raise ValueError("sampler: prior_std must be finite and > 0 at every position (a standard deviation; "
+                         "prior_std_from_mel clamps at std_min)")
+    return t.contiguous()
+
+
+def _set_prior(net, sigma):
+    """Install (a cuda float32 tensor [B, C, L]) or drop (None) the engine's prior table on the current stream."""
+    lib = _lib.load()
+    if sigma is None:
+        _lib.check(lib.dws_sampler_set_prior(net._handle, None, 0, 0, _lib.current_stream()))
+    else:
+        _lib.check(lib.dws_sampler_set_prior(net._handle, sigma.data_ptr(), sigma.shape[0], sigma.shape[1] * sigma.shape[2],
+                                             _lib.current_stream()))
+
+
 def _splitmix64(z):
     """The splitmix64 finaliser (Steele, Lea & Flood, 2014) of a 64-bit integer, in host integer arithmetic."""
     z = (z + _GOLDEN64) & _MASK64
@@ -367,8 +402,18 @@ def _check_edit(size, S, x_T, known=None, mask=None, known_noise=None, x_start=N
 
 def sampling(net, size, diffusion_hyperparams, condition=None, *, x_T=None, noise=None, seed=None,
              use_graph=True, net_steps=None, known=None, mask=None, known_noise=None, x_start=None, start_step=None,
-             start_noise=None, resample=None, labels=None, cfg_scale=None, lengths=None):
+             start_noise=None, resample=None, labels=None, cfg_scale=None, lengths=None, prior_std=None):
     """``x_0 = sampling(net, (B, C, L), dh, condition)`` as in ``generate.py:23-55``.
+
+    Adaptive prior (PriorGrad: Lee et al., ICLR 2022; ``dws_sampler_set_prior``), on every sampler of this module:
+      prior_std  float tensor [B, 1, L] or [B, C, L], finite and > 0 (``mel.prior_std_from_mel``): the run ends in
+             N(0, diag(prior_std^2)) instead of N(0, I).  Every standard-normal number the run consumes -- drawn from
+             Philox or injected (``noise``, ``known_noise``, ``start_noise`` stay standard normal) -- is multiplied by
+             ``prior_std`` at its position, one fp32 product of its own, before the unchanged update reads it; an
+             injected ``x_T`` is a state and is taken as given.  The network must have been trained for it
+             (``training_loss(prior_std=)``).  Combines with ``seed=[...]``, ``lengths``, ``labels``, the editing
+             arguments and ``resample``; refused with ``cfg_scale``.  Goes through the schedule entry with
+             ``net_steps = 0..T-1``; the table holds for this run and is dropped behind it.
 
     Class-conditional models (``model.n_classes``; not in the reference), on every sampler of this module:
       labels     integer tensor / list [B] in 0..K (K = the null class); default: the null class for every clip
@@ -422,11 +467,13 @@ def sampling(net, size, diffusion_hyperparams, condition=None, *, x_T=None, nois
     edit = dict(known=known, mask=mask, known_noise=known_noise, x_start=x_start, start_step=start_step,
                 start_noise=start_noise)
     lengths = _check_lengths(net, size, lengths, cfg_scale)
+    if prior_std is not None and cfg_scale is not None:      # (the table itself is checked by _run_schedule, where it goes)
+        _check_prior(size, prior_std, cfg_scale)
     lab, scale = _check_labels(net, size, labels, cfg_scale, edit, resample)
     per_clip = seed_list(seed, size[0]) is not None
     if resample is None and all(v is None for v in edit.values()):
         edit = None
-        if (scale is not None or per_clip) and net_steps is None:
+        if (scale is not None or per_clip or prior_std is not None) and net_steps is None:
             net_steps = np.arange(T, dtype=np.float32)
     elif net_steps is None:
         net_steps = np.arange(T, dtype=np.float32)
@@ -434,7 +481,7 @@ def sampling(net, size, diffusion_hyperparams, condition=None, *, x_T=None, nois
         coef = np.stack([_host_table(Alpha)[0], _host_table(Alpha_bar)[0], _host_table(Sigma)[0]])
         return _run_schedule(net, size, _lib.DWS_SAMPLER_DDPM, net_steps, coef, condition, x_T, noise, seed, use_graph,
                              edit=edit, levels=coef[1], resample=resample, labels=labels, cfg_scale=cfg_scale,
-                             lengths=lengths)
+                             lengths=lengths, prior_std=prior_std)
     lib = _lib.load()
     with torch.no_grad():
         x, init, nz, seed = _prepare_run(net, size, T, condition, x_T, noise, seed, labels=lab, lengths=lengths)
@@ -448,12 +495,13 @@ def sampling(net, size, diffusion_hyperparams, condition=None, *, x_T=None, nois
 
 
 def _run_schedule(net, size, kind, net_steps, coef, condition, x_T, noise, seed, use_graph, edit=None, levels=None,
-                  resample=None, labels=None, cfg_scale=None, lengths=None):
+                  resample=None, labels=None, cfg_scale=None, lengths=None, prior_std=None):
     """``dws_sampler_run_schedule``: S steps s = S-1..0, the network at ``net_steps[s]``, update tables ``coef``.
     ``edit``: the editing arguments of ``sampling`` (-> ``dws_sampler_run_edit``), ``levels`` the run's alpha_bar.
     ``resample``: (jump, resamples) on top of ``edit`` (-> ``dws_sampler_run_program``)."""
     assert len(size) == 3
     lengths = _check_lengths(net, size, lengths, cfg_scale)
+    prior = _check_prior(size, prior_std, cfg_scale, lengths)
     lab, scale = _check_labels(net, size, labels, cfg_scale, edit, resample)
     seeds = seed_list(seed, size[0])
     steps = np.ascontiguousarray(np.asarray(net_steps, dtype=np.float32).reshape(-1))
@@ -478,6 +526,10 @@ def _run_schedule(net, size, kind, net_steps, coef, condition, x_T, noise, seed,
         if seeds is not None:     # per-clip seeds hold for this run alone: the engine's table is dropped behind it
             _set_clip_seeds(net, seeds)
             cleanup.callback(_set_clip_seeds, net, None)
+        if prior is not None:     # and so does the prior
+            prior = prior.to(x.device)
+            _set_prior(net, prior)
+            cleanup.callback(_set_prior, net, None)
         if edit is None and scale is not None:
             _lib.check(lib.dws_sampler_set_cfg(net._handle, 1, scale))
             try:
@@ -586,10 +638,10 @@ def ddim_coefficients(alpha_bar, tau, eta):
 
 def sampling_ddim(net, size, dh_train, steps, eta=0.0, condition=None, *, x_T=None, noise=None, seed=None,
                   use_graph=True, known=None, mask=None, known_noise=None, x_start=None, start_step=None,
-                  start_noise=None, resample=None, labels=None, cfg_scale=None, lengths=None):
+                  start_noise=None, resample=None, labels=None, cfg_scale=None, lengths=None, prior_std=None):
     """DDIM over ``ddim_steps(T, steps)`` of the training schedule ``dh_train`` (``steps``: S or an explicit list),
     deterministic for ``eta = 0``.  ``noise``: injected z, [S, B, C, L] (``noise[s]`` is used after step s > 0).
-    The editing arguments, ``resample``, ``labels`` and ``cfg_scale`` are those of ``sampling`` (levels:
+    The editing arguments, ``resample``, ``labels``, ``cfg_scale`` and ``prior_std`` are those of ``sampling`` (levels:
     ``Alpha_bar[tau]``).  Not the reference's loop."""
     tau = ddim_steps(dh_train["T"], steps)
     coef = ddim_coefficients(dh_train["Alpha_bar"], tau, eta)
@@ -599,7 +651,7 @@ def sampling_ddim(net, size, dh_train, steps, eta=0.0, condition=None, *, x_T=No
         edit = None
     return _run_schedule(net, size, _lib.DWS_SAMPLER_DDIM, np.asarray(tau, dtype=np.float32), coef, condition, x_T,
                          noise, seed, use_graph, edit=edit, levels=_host_table(dh_train["Alpha_bar"])[0][tau],
-                         resample=resample, labels=labels, cfg_scale=cfg_scale, lengths=lengths)
+                         resample=resample, labels=labels, cfg_scale=cfg_scale, lengths=lengths, prior_std=prior_std)
 
 
 def logsnr_steps(alpha_bar, S):
@@ -653,15 +705,17 @@ def dpmpp_coefficients(alpha_bar, tau):
 
 def sampling_dpmpp(net, size, dh_train, steps, condition=None, *, spacing="logsnr", x_T=None, seed=None,
                    use_graph=True, known=None, mask=None, known_noise=None, x_start=None, start_step=None,
-                   start_noise=None, resample=None, noise=None, labels=None, cfg_scale=None, lengths=None):
+                   start_noise=None, resample=None, noise=None, labels=None, cfg_scale=None, lengths=None,
+                   prior_std=None):
     """DPM-Solver++(2M) over ``logsnr_steps(Alpha_bar, steps)`` of the training schedule ``dh_train``
     (``spacing="uniform"``: over ``ddim_steps(T, steps)``; ``steps``: S or an explicit list).  Second order at the cost
     of DDIM: one network evaluation per step, the previous step's data prediction kept on the device.  Deterministic:
     ``seed`` drives only a drawn ``x_T``, the known-region noise, the start noise and the jump noise; ``noise`` is
     accepted only together with ``resample`` ([V, B, C, L], of which the rows of jump visits are read).  The editing
     arguments and ``resample`` are those of ``sampling`` (levels: ``Alpha_bar[tau]``); the step after a jump and the
-    first step of a partial start are first order.  ``labels`` / ``cfg_scale`` as in ``sampling``.  Not the reference's
-    loop."""
+    first step of a partial start are first order.  ``labels`` / ``cfg_scale`` as in ``sampling``; ``prior_std`` as
+    there too: with no update noise it scales a drawn ``x_T`` and the known-region, start and jump noise.  Not the
+    reference's loop."""
     if spacing not in ("logsnr", "uniform"):
         raise ValueError(f"sampling_dpmpp: spacing = {spacing!r} (expected 'logsnr' or 'uniform')")
     if noise is not None and resample is None:
@@ -676,7 +730,7 @@ def sampling_dpmpp(net, size, dh_train, steps, condition=None, *, spacing="logsn
         edit = None
     return _run_schedule(net, size, _lib.DWS_SAMPLER_DPMPP2M, np.asarray(tau, dtype=np.float32), coef, condition, x_T,
                          noise, seed, use_graph, edit=edit, levels=ab[tau], resample=resample, labels=labels,
-                         cfg_scale=cfg_scale, lengths=lengths)
+                         cfg_scale=cfg_scale, lengths=lengths, prior_std=prior_std)
 
 
 def sampling_aligned(net, size, diffusion_cfg, condition=None, **kw):
@@ -793,7 +847,7 @@ def guided_coefficients(dh, sampler, steps=None, eta=0.0):
 
 def sampling_guided(net, size, diffusion_hyperparams, *, measurement, operator, scale, sampler="ddpm", steps=None,
                     eta=0.0, condition=None, x_T=None, noise=None, seed=None, residuals=None, labels=None,
-                    **unsupported):
+                    prior_std=None, **unsupported):
     """Restoration with a trained model by Diffusion Posterior Sampling (Chung et al., ICLR 2023): a reverse run whose
     every step is pulled towards a degraded recording ``measurement = operator(x0)``.  ``operator`` is any differentiable
     torch callable ``A(x0) -> measurement-shaped tensor`` (``declip_operator``, ``lowpass_operator``, or ``mel_operator``:
@@ -829,7 +883,11 @@ def sampling_guided(net, size, diffusion_hyperparams, *, measurement, operator, 
     expanded to the batch.  The loop runs eagerly, one step after the other with
     no graph capture: each step contains a backward.  Costs a forward plus a backward per step.  The editing arguments
     (``known`` / ``mask`` ..., ``resample``) and ``cfg_scale`` are not built for guided runs; ``labels`` ([B], a
-    class-conditional model) are passed to every network call.  Not the reference's loop."""
+    class-conditional model) are passed to every network call.  ``prior_std`` ([B, 1, L] or [B, C, L], finite, > 0): the
+    adaptive prior of ``sampling`` -- every z, drawn or injected, is multiplied by it (one product of its own) before
+    ``c z`` is formed, and so is a drawn initial state; it works with any ``net``.  Not the reference's loop."""
+    if unsupported.get("cfg_scale") is not None and prior_std is not None:
+        raise ValueError("sampling_guided: prior_std= (adaptive prior) is not built for classifier-free guidance (cfg_scale=)")
     if unsupported.get("lengths") is not None:
         raise ValueError("sampling_guided: lengths= (ragged batches) is not built for guided runs: every step is a "
                          "training forward")
@@ -864,6 +922,7 @@ def sampling_guided(net, size, diffusion_hyperparams, *, measurement, operator, 
         raise ValueError(f"sampling_guided: noise has shape {tuple(noise.shape)}, expected {(S,) + size}")
     if x_T is not None and tuple(x_T.shape) != size:
         raise ValueError(f"sampling_guided: x_T has shape {tuple(x_T.shape)}, expected {size}")
+    prior = _check_prior(size, prior_std)
     from .models.engine import EngineModule
     engine = isinstance(net, EngineModule)
     if engine:
@@ -880,6 +939,9 @@ def sampling_guided(net, size, diffusion_hyperparams, *, measurement, operator, 
     if seed is None:
         seed = int(torch.randint(0, 2 ** 63 - 1, (1,), dtype=torch.int64).item())
     gen = None
+    if prior is not None:
+        prior = prior.to(dev)
+    scaled = (lambda z: z) if prior is None else (lambda z: prior * z)     # n = sigma z stands where z stood
 
     def draw(stream_id):
         nonlocal gen
@@ -901,7 +963,7 @@ def sampling_guided(net, size, diffusion_hyperparams, *, measurement, operator, 
             gen = torch.Generator().manual_seed(seed % (2 ** 63))
         return torch.randn(size, generator=gen).to(dev)
 
-    x = draw(S) if x_T is None else x_T.detach().to(device=dev, dtype=torch.float32).clone()
+    x = scaled(draw(S)) if x_T is None else x_T.detach().to(device=dev, dtype=torch.float32).clone()
     kw = {} if condition is None else {"mel_spec": condition}
     if labels is not None:      # class-conditional model: every step's network call carries the labels
         kw["labels"] = labels
@@ -927,7 +989,7 @@ def sampling_guided(net, size, diffusion_hyperparams, *, measurement, operator, 
                 residuals.append(n.detach().cpu())
             x = a * ((x - k1 * eps) / k2) + b * eps if ddim else (x - a * eps) / b
             if s > 0:
-                z = draw(s) if noise is None else noise[s].detach().to(device=dev, dtype=torch.float32)
+                z = scaled(draw(s) if noise is None else noise[s].detach().to(device=dev, dtype=torch.float32))
                 x = x + c * z
             x = x - scale * g
     return x

@@ -26,7 +26,8 @@ import numpy as np
 import torch
 import torch.nn as nn
 
-from .generate import find_max_epoch, generate, load_config, local_directory
+from .generate import (PRIOR_KEYS, find_max_epoch, generate, load_config, local_directory, prior_hop, prior_settings,
+                       same_prior)
 
 HASH_DIVIDER, EXCEPT_FOLDER = "_nohash_", "_background_noise_"   # `dataloaders/sc.py:15-16`
 
@@ -204,9 +205,14 @@ def optimizer_options(optimizer=None, ema_decay=None, clip_grad_norm=None):
     return kind, ema_decay, clip_grad_norm
 
 
+class PriorMismatch(ValueError):
+    """A resume whose ``train.prior`` keys differ from the checkpoint's ``prior`` entry."""
+
+
 def train(rank, num_gpus, diffusion_cfg, model_cfg, dataset_cfg, generate_cfg, ckpt_iter, n_iters, iters_per_ckpt,
           iters_per_logging, learning_rate, batch_size_per_gpu, name=None, exp_root="exp", num_workers=4, precision=None,
-          honour_optim_hints=False, label_dropout=None, optimizer=None, ema_decay=None, clip_grad_norm=None):
+          honour_optim_hints=False, label_dropout=None, optimizer=None, ema_decay=None, clip_grad_norm=None, prior=None,
+          prior_energy_max=None, prior_energy_min=None, prior_std_min=None):
     """``train.py:49-196``.  With ``model.n_classes`` (class-conditional; not in the reference) every batch's class
     indices go to the network and ``label_dropout`` (``train.label_dropout``, default 0.1) of them are replaced by the
     null class, which is what classifier-free guidance needs at sampling time; the in-loop ``generate`` cycles the
@@ -215,8 +221,20 @@ def train(rank, num_gpus, diffusion_cfg, model_cfg, dataset_cfg, generate_cfg, c
     ``optimizer`` / ``ema_decay`` / ``clip_grad_norm`` (``+train.optimizer=engine +train.ema_decay=0.9999
     +train.clip_grad_norm=1.0``; not in the reference): see ``optimizer_options``.  With an EMA the checkpoints also hold
     ``ema_state_dict`` (the averaged weights in the layout of ``model_state_dict``), which ``generate`` then samples
-    from; a resume restores it, or starts it from the loaded weights when the checkpoint has none."""
+    from; a resume restores it, or starts it from the loaded weights when the checkpoint has none.
+
+    ``prior`` (``+train.prior=energy +train.prior_energy_max=E [+train.prior_energy_min=0 +train.prior_std_min=0.1]``; not
+    in the reference; mel-conditional models): the adaptive prior of PriorGrad (Lee et al., ICLR 2022).  Every batch is
+    noised towards N(0, diag(sigma^2)) with sigma = ``mel.prior_std_from_mel`` of its own mel segment and trained on the
+    Sigma^-1-weighted loss (``training_loss(prior_std=)``); the checkpoints get a ``prior`` entry with the four values,
+    which ``generate`` -- the in-loop one too -- picks up.  A resume must name the prior the checkpoint was trained with
+    (none for a checkpoint without an entry): anything else raises ``PriorMismatch`` (a ValueError).  What such a model
+    sounds like has not been measured."""
     opt_kind, ema_decay, clip_grad_norm = optimizer_options(optimizer, ema_decay, clip_grad_norm)
+    prior_cfg = prior_settings(prior, prior_energy_max, prior_energy_min, prior_std_min, model_cfg.get("unconditional"),
+                               where="train")
+    prior_cfg = prior_cfg if isinstance(prior_cfg, dict) else None
+    prior_h = prior_hop(model_cfg, dataset_cfg) if prior_cfg is not None else None
     from .distributed_util import apply_gradient_allreduce, reduce_tensor
     from .models import construct_model
     from .sampling import calc_diffusion_hyperparams
@@ -258,6 +276,10 @@ def train(rank, num_gpus, diffusion_cfg, model_cfg, dataset_cfg, generate_cfg, c
     if ckpt_iter >= 0:
         try:
             checkpoint = torch.load(os.path.join(checkpoint_directory, f"{ckpt_iter}.pkl"), map_location="cpu")
+            if not same_prior(checkpoint.get("prior"), prior_cfg):
+                raise PriorMismatch(f"checkpoint {ckpt_iter} was trained with the prior {checkpoint.get('prior')!r}, this run "
+                                    f"asks for {prior_cfg!r}: resume with the same train.prior keys (weights trained "
+                                    "towards one prior are not a start for another)")
             net.load_state_dict(checkpoint["model_state_dict"])
             if "optimizer_state_dict" in checkpoint:
                 optimizer.load_state_dict(checkpoint["optimizer_state_dict"])
@@ -271,6 +293,8 @@ def train(rank, num_gpus, diffusion_cfg, model_cfg, dataset_cfg, generate_cfg, c
                     optimizer.reset_ema()
                     print(f"checkpoint {ckpt_iter} holds no ema_state_dict: the EMA starts from the loaded weights")
             print(f"Successfully loaded model at iteration {ckpt_iter}")
+        except PriorMismatch:    # (not a checkpoint that failed to load: a run that would silently change its loss)
+            raise
         except Exception as e:   # the reference swallows the error the same way (`train.py:115-117`)
             print(f"Model checkpoint found at iteration {ckpt_iter}, but was not successfully loaded ({e}) - "
                   "training from scratch.")
@@ -306,7 +330,13 @@ def train(rank, num_gpus, diffusion_cfg, model_cfg, dataset_cfg, generate_cfg, c
                 audio = (data.cuda() / MAX_WAV_VALUE).unsqueeze(1)
                 mel = stft.mel_spectrogram(audio[:, 0])
             optimizer.zero_grad()
-            if n_classes:    # (the labels stay on the host: the engine takes them from there, nothing waits for the GPU)
+            if prior_cfg is not None:
+                from .mel import prior_std_from_mel
+                sigma = prior_std_from_mel(mel, prior_h, audio.shape[-1],
+                                           **{k: prior_cfg[k] for k in PRIOR_KEYS})
+                more = dict(labels=data[2], label_dropout=label_dropout) if n_classes else {}
+                loss = training_loss(net, loss_fn, audio, dh, mel_spec=mel, prior_std=sigma, **more)
+            elif n_classes:    # (the labels stay on the host: the engine takes them from there, nothing waits for the GPU)
                 loss = training_loss(net, loss_fn, audio, dh, mel_spec=mel, labels=data[2], label_dropout=label_dropout)
             else:
                 loss = training_loss(net, loss_fn, audio, dh, mel_spec=mel)
@@ -324,6 +354,8 @@ def train(rank, num_gpus, diffusion_cfg, model_cfg, dataset_cfg, generate_cfg, c
                 saved = {"model_state_dict": net.state_dict(), "optimizer_state_dict": optimizer.state_dict()}
                 if ema_decay is not None:       # (the in-loop generate below samples from it)
                     saved["ema_state_dict"] = optimizer.ema_state_dict(net)
+                if prior_cfg is not None:       # (generate samples from the prior the weights were trained with)
+                    saved["prior"] = dict(prior_cfg)
                 torch.save(saved, os.path.join(checkpoint_directory, f"{n_iter}.pkl"))
                 print(f"model at iteration {n_iter} is saved")
                 if generate_cfg and generate_cfg.get("n_samples", 0):

@@ -562,6 +562,32 @@ int dws_philox_normal(float* x, int64_t n, uint64_t seed, uint32_t stream_id, vo
  * dws_model_prepare -> DWS_ERR_STATE. */
 int dws_sampler_set_clip_seeds(dws_model* m, const uint64_t* seeds, int64_t B, void* stream);
 
+/* Adaptive prior (PriorGrad: Lee et al., ICLR 2022): the run ends in N(0, diag(sigma^2)) instead of N(0, I).  sigma: DEVICE
+ * float[B, n_per_clip] at the shape of the sampler state (n_per_clip = C L; a [B, 1, L] table of a C > 1 model is expanded
+ * by the caller), every value finite and > 0 over the positions a run keeps -- or NULL = off, every path bit for bit as
+ * without this call.  The table is copied into a model-owned device buffer on `stream` and holds until it is changed;
+ * dws_model_prepare to another shape drops it.
+ *
+ * While it is on, every standard-normal number z a schedule run consumes is replaced by n = sigma * z at its own
+ * position -- ONE fp32 product of its own, rounded once, never contracted into what follows -- and n stands exactly where
+ * z stood; the update formulas are unchanged.  This holds for numbers drawn from Philox and for INJECTED ones (`noise`,
+ * `known_noise`, `start_noise` stay standard normal by contract) at every noise site: the drawn x_T (an injected x_T is a
+ * state and is taken as given), the update noise of DDPM and of DDIM with eta > 0, the known-region noise of an edited
+ * step, the jump visits of a program and the q-sample start.  DPM-Solver++(2M) draws no update noise: only its drawn x_T
+ * (and, edited, its known-region, jump and start noise) changes.  So a run with the table on equals the run without it that
+ * is handed x_T = fp32(sigma z_S) and noise[s] = fp32(sigma z_s), bit for bit.  It combines with per-clip seeds (the
+ * table's row b belongs to clip b) and per-clip lengths (the update is pointwise: a value past a clip's end reaches no
+ * valid position).
+ *
+ * The scaling kernels are instances of their own (a PRIOR template flag); with no table installed the existing instances
+ * run as they are.  The captured steps read the table from the model-owned buffer: a new table of the same shape replays
+ * the graph.  The step with a prior is a graph of its own beside the one without, per flavour, form of seed and lengths
+ * on / off: the forms alternate on one model without a new capture once each has run.
+ * While on: dws_sampler_run and dws_sampler_steps return DWS_ERR_UNSUPPORTED, and so does dws_sampler_set_cfg(on); with
+ * guidance on, this call returns DWS_ERR_UNSUPPORTED (guidance with a prior is not built).  B or n_per_clip other than the
+ * prepared state's -> DWS_ERR_INVALID; before dws_model_prepare -> DWS_ERR_STATE. */
+int dws_sampler_set_prior(dws_model* m, const float* sigma, int64_t B, int64_t n_per_clip, void* stream);
+
 /* The per-clip twin of dws_philox_normal: row b of x[B, n_per_clip] (DEVICE) = dws_philox_normal(n_per_clip, seeds[b],
  * stream_id), seeds HOST uint64[B].  The seeds travel as kernel arguments; the host does not wait for the GPU. */
 int dws_philox_normal_clips(float* x, int64_t B, int64_t n_per_clip, const uint64_t* seeds, uint32_t stream_id,
@@ -574,6 +600,20 @@ int dws_philox_normal_clips(float* x, int64_t B, int64_t n_per_clip, const uint6
  * [B][n_mels][T/hop + 1] = log(max(mel_basis . |STFT|, clip)).  All pointers are device pointers. */
 int dws_mel_spectrogram(const float* audio, int64_t B, int64_t T, const float* window, const float* mel_basis,
                         int32_t n_fft, int32_t hop, int32_t n_mels, float clip, float* out, void* stream);
+
+/* The standard deviation of the adaptive prior from a clip's own conditioning mel (PriorGrad, Lee et al., ICLR 2022, as
+ * formulated for a mel-conditional vocoder).  mel [B][bands][frames] is the log-mel above (natural log); with hop samples
+ * per frame
+ *   energy[b, f]  = sqrt(sum_k exp(mel[b, k, f]))                 (fp32, in a fixed order: band k into partial sum k % 8
+ *                                                                  in ascending k, then ((p0+p1)+(p2+p3))+((p4+p5)+(p6+p7)))
+ *   sigma_f[b, f] = clamp((energy[b, f] - e_min) / (e_max - e_min), std_min, 1)
+ *   sigma[b, 0, l] = sigma_f[b, l / hop]                          l = 0 .. L-1
+ * Each frame is evaluated on its own: no statistic is taken over the batch or the utterance, so a clip's row does not
+ * depend on B.  sigma is [B][1][L]; the repeat by hop is written with 16-byte stores where the address allows.  All
+ * pointers are device pointers.  L outside 1 .. frames * hop, e_max <= e_min or not finite, std_min outside (0, 1] ->
+ * DWS_ERR_INVALID. */
+int dws_prior_std_from_mel(const float* mel, int64_t B, int64_t bands, int64_t frames, int64_t hop, int64_t L, float e_min,
+                           float e_max, float std_min, float* sigma, void* stream);
 
 /* The adjoint of dws_mel_spectrogram (not in the reference, whose TacotronSTFT detaches its input): daudio [B][T]
  * (overwritten) = d<dout, out>/d audio for a cotangent dout [B][n_mels][T/hop + 1].  With N = n_fft, w the window, W the
