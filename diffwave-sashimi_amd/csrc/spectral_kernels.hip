@@ -1,0 +1,212 @@
+// Objective spectral distances between two batches of waveforms x (generated) and y (reference), one fused launch per
+// STFT resolution: Parallel WaveGAN's multi-resolution STFT terms (spectral convergence, log-magnitude L1), the
+// log-spectral distance, and -- where a mel filterbank is passed -- the log-mel L1 and a mel-cepstral distortion.  No
+// spectrogram goes to memory: a workgroup owns frame f of clip b of BOTH signals and writes six partial sums.
+//
+// Framing and transform are mel_frame_kernel's (reflect-pad by n_fft/2, windowed direct DFT, a thread owns bins
+// k = tid, tid + 256, ...), with two changes: the reflection is about the clip's OWN end len_b (a ragged batch: nothing
+// behind len_b is read, so the padding may hold anything), and the frames of x and y sit interleaved in LDS next to an
+// interleaved (cos, sin) table, so one 8-byte table read and one 8-byte frame read feed four FMAs.
+//
+// Reduction, in a fixed order: a thread adds its bins in ascending k (fp32), a wave adds its lanes by an xor tree
+// (fp32), thread 0 adds the four waves in wave order (double).  The mel terms take ln() and the cepstral products in
+// double: with x = y / 2 the band differences are then ln 2 to the last bit and the distortion cancels to 1e-16, where
+// fp32 logs would leave 1e-5 dB of rounding noise.  spectral_clip_sum_kernel adds a clip's frames in ascending order in
+// double.  A clip's six numbers depend on its own samples and length alone.
+#include "dws_common.h"
+
+namespace dws {
+
+constexpr int SPEC_Q = 6;                 // sc_num, sc_den, mag_abs, lsd, mel_abs, mcd
+constexpr float SPEC_FLOOR = 1e-7f;       // Parallel WaveGAN: |X| = sqrt(max(re^2 + im^2, 1e-7))
+
+// frames of clip b: 0 where the length is not one the host admitted (never the case after dws_spectral_distance's
+// checks; the guard keeps every index inside the row whatever the device array holds)
+__device__ __forceinline__ int spectral_clip_frames(const int* __restrict__ lengths, int b, int T, int half, int hop, int& len) {
+    len = lengths ? lengths[b] : T;
+    return (len > half && len <= T) ? len / hop + 1 : 0;
+}
+
+__global__ __launch_bounds__(256) void spectral_frame_kernel(const float* __restrict__ x, const float* __restrict__ y,
+                                                             const int* __restrict__ lengths, const float* __restrict__ window,
+                                                             const float* __restrict__ basis, const double* __restrict__ cep,
+                                                             double* __restrict__ ws, int T, int n_fft, int hop, int n_mels,
+                                                             int n_cep, int f_max, float clip) {
+    extern __shared__ double lds64[];
+    const int f = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
+    const int half = n_fft / 2, nb = half + 1;
+    int len;
+    if (f >= spectral_clip_frames(lengths, b, T, half, hop, len)) return;      // the whole workgroup, before any barrier
+    double* red = lds64;                                   // [4 waves][4]
+    double* dl = red + 16;                                 // [n_mels] logmel(Y) - logmel(X)
+    double* c2 = dl + n_mels;                              // [n_cep]  squared cepstral differences
+    float2* fr = reinterpret_cast<float2*>(c2 + n_cep);    // [n_fft]  (x, y) windowed
+    float2* tab = fr + n_fft;                              // [n_fft]  (cos, sin)(2 pi j / n_fft)
+    float* magx = reinterpret_cast<float*>(tab + n_fft);   // [nb] unfloored |X|, with a filterbank only
+    float* magy = magx + nb;                               // [nb]
+    const float* xa = x + (size_t)b * T;
+    const float* ya = y + (size_t)b * T;
+    for (int i = tid; i < n_fft; i += 256) {
+        int j = f * hop + i - half;      // reflect (no edge repeat) about the clip's own ends; len > half keeps j in [0, len)
+        if (j < 0) j = -j;
+        if (j >= len) j = 2 * (len - 1) - j;
+        const float w = window[i];
+        fr[i] = make_float2(xa[j] * w, ya[j] * w);
+        float s, c;
+        sincospif(2.f * (float)i / (float)n_fft, &s, &c);
+        tab[i] = make_float2(c, s);
+    }
+    __syncthreads();
+    const int mask = n_fft - 1;          // n_fft is a power of two
+    float a_num = 0.f, a_den = 0.f, a_abs = 0.f, a_lsd = 0.f;
+    for (int k = tid; k < nb; k += 256) {
+        float xr = 0.f, xi = 0.f, yr = 0.f, yi = 0.f;
+        int ph = 0;
+        for (int i = 0; i < n_fft; ++i) {
+            const float2 v = fr[i];
+            const float2 t = tab[ph];
+            xr = fmaf(v.x, t.x, xr);
+            xi = fmaf(v.x, t.y, xi);
+            yr = fmaf(v.y, t.x, yr);
+            yi = fmaf(v.y, t.y, yi);
+            ph = (ph + k) & mask;
+        }
+        const float px = xr * xr + xi * xi, py = yr * yr + yi * yi;
+        if (basis) {
+            magx[k] = sqrtf(px);
+            magy[k] = sqrtf(py);
+        }
+        const float qx = px < SPEC_FLOOR ? SPEC_FLOOR : px;      // (a NaN passes: fmaxf would hide it)
+        const float qy = py < SPEC_FLOOR ? SPEC_FLOOR : py;
+        const float mx = sqrtf(qx), my = sqrtf(qy);
+        const float d = my - mx;
+        a_num = fmaf(d, d, a_num);
+        a_den = fmaf(my, my, a_den);
+        const float l = 0.5f * (logf(qy) - logf(qx));            // ln|Y| - ln|X|
+        a_abs += fabsf(l);
+        a_lsd = fmaf(l, l, a_lsd);
+    }
+    const int wave = tid >> 6, lane = tid & 63;
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        a_num += __shfl_xor(a_num, off);
+        a_den += __shfl_xor(a_den, off);
+        a_abs += __shfl_xor(a_abs, off);
+        a_lsd += __shfl_xor(a_lsd, off);
+    }
+    if (lane == 0) {
+        red[wave * 4 + 0] = (double)a_num;
+        red[wave * 4 + 1] = (double)a_den;
+        red[wave * 4 + 2] = (double)a_abs;
+        red[wave * 4 + 3] = (double)a_lsd;
+    }
+    __syncthreads();                     // red, and magx / magy
+    double* o = ws + ((size_t)b * f_max + f) * SPEC_Q;
+    if (tid == 0) {
+        double r[4];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) r[q] = ((red[q] + red[4 + q]) + red[8 + q]) + red[12 + q];
+        o[0] = r[0];
+        o[1] = r[1];
+        o[2] = r[2];
+        // sqrt(mean_k (log10|Y|^2 - log10|X|^2)^2) = (2 / ln 10) sqrt(mean_k (ln|Y| - ln|X|)^2)
+        o[3] = 0.86858896380650365530 * sqrt(r[3] / (double)nb);
+        if (!basis) {
+            o[4] = 0.0;
+            o[5] = 0.0;
+        }
+    }
+    if (!basis) return;                  // (a kernel argument: the whole workgroup)
+    for (int m = wave; m < n_mels; m += 4) {
+        const float* w = basis + (size_t)m * nb;
+        float sx = 0.f, sy = 0.f;
+        for (int k = lane; k < nb; k += 64) {
+            const float wk = w[k];
+            sx = fmaf(wk, magx[k], sx);
+            sy = fmaf(wk, magy[k], sy);
+        }
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) {
+            sx += __shfl_xor(sx, off);
+            sy += __shfl_xor(sy, off);
+        }
+        if (lane == 0) dl[m] = log((double)(sy < clip ? clip : sy)) - log((double)(sx < clip ? clip : sx));
+    }
+    __syncthreads();
+    if (tid < n_cep) {
+        const double* row = cep + (size_t)tid * n_mels;
+        double c = 0.0;
+        for (int m = 0; m < n_mels; ++m) c = fma(row[m], dl[m], c);
+        c2[tid] = c * c;
+    }
+    __syncthreads();
+    if (tid == 0) {
+        double s = 0.0;
+        for (int m = 0; m < n_mels; ++m) s += fabs(dl[m]);
+        o[4] = s;
+        double e = 0.0;
+        for (int d = 0; d < n_cep; ++d) e += c2[d];
+        o[5] = sqrt(e);
+    }
+}
+
+// One thread per (clip, quantity): the clip's frames in ascending order, in double.
+__global__ __launch_bounds__(64) void spectral_clip_sum_kernel(const double* __restrict__ ws, const int* __restrict__ lengths,
+                                                               double* __restrict__ out, int T, int n_fft, int hop, int f_max) {
+    const int b = blockIdx.x, q = threadIdx.x;
+    if (q >= SPEC_Q) return;
+    int len;
+    const int nf = spectral_clip_frames(lengths, b, T, n_fft / 2, hop, len);
+    const double* p = ws + (size_t)b * f_max * SPEC_Q + q;
+    double s = 0.0;
+    for (int f = 0; f < nf; ++f) s += p[(size_t)f * SPEC_Q];
+    out[(size_t)b * SPEC_Q + q] = s;
+}
+
+}  // namespace dws
+
+extern "C" int64_t dws_spectral_distance_workspace(int64_t B, int64_t T, int32_t hop) {
+    if (B < 1 || T < 1 || hop < 1 || T > INT32_MAX || B > 65535) return 0;
+    return B * (T / hop + 1) * dws::SPEC_Q * (int64_t)sizeof(double);
+}
+
+extern "C" int dws_spectral_distance(const float* x, const float* y, int64_t B, int64_t T, const int32_t* lengths,
+                                     const int32_t* lengths_host, const float* window, int32_t n_fft, int32_t hop,
+                                     const float* mel_basis, int32_t n_mels, float clip, const double* cep, int32_t n_cep,
+                                     double* workspace, double* out, void* stream) {
+    using namespace dws;
+    DWS_CHECK(x && y && window && out, DWS_ERR_INVALID, "dws_spectral_distance: null argument");
+    DWS_CHECK(workspace, DWS_ERR_INVALID, "dws_spectral_distance: null workspace (dws_spectral_distance_workspace bytes)");
+    DWS_CHECK(n_fft >= 64 && n_fft <= 2048 && (n_fft & (n_fft - 1)) == 0, DWS_ERR_INVALID,
+              "dws_spectral_distance: n_fft = %d (powers of two 64..2048)", n_fft);
+    DWS_CHECK(B > 0 && B <= 65535 && hop > 0 && T > 0 && T <= INT32_MAX - n_fft, DWS_ERR_INVALID,
+              "dws_spectral_distance: bad shape (B = %lld, T = %lld, hop = %d)", (long long)B, (long long)T, hop);
+    DWS_CHECK((lengths == nullptr) == (lengths_host == nullptr), DWS_ERR_INVALID,
+              "dws_spectral_distance: lengths (device) and lengths_host (the same numbers on the host) come together");
+    if (lengths_host) {
+        for (int64_t b = 0; b < B; ++b)
+            DWS_CHECK(lengths_host[b] > n_fft / 2 && lengths_host[b] <= T, DWS_ERR_INVALID,
+                      "dws_spectral_distance: clip %lld has %d samples (n_fft = %d needs %d .. T = %lld)", (long long)b,
+                      lengths_host[b], n_fft, n_fft / 2 + 1, (long long)T);
+    } else {
+        DWS_CHECK(T > n_fft / 2, DWS_ERR_INVALID, "dws_spectral_distance: T = %lld (n_fft = %d needs at least %d samples)",
+                  (long long)T, n_fft, n_fft / 2 + 1);
+    }
+    DWS_CHECK(mel_basis ? (n_mels > 0 && n_mels <= 4096) : (n_mels == 0 && cep == nullptr), DWS_ERR_INVALID,
+              "dws_spectral_distance: n_mels = %d %s a filterbank (a cepstral table needs one)", n_mels,
+              mel_basis ? "with" : "without");
+    DWS_CHECK(cep ? (n_cep > 0 && n_cep <= 256) : n_cep == 0, DWS_ERR_INVALID,
+              "dws_spectral_distance: n_cep = %d %s a cepstral table (1..256 rows, one thread each)", n_cep,
+              cep ? "with" : "without");
+    const int f_max = (int)(T / hop) + 1;
+    const size_t lds = (size_t)(16 + n_mels + n_cep) * 8 + (size_t)n_fft * 16 + (mel_basis ? (size_t)(n_fft / 2 + 1) * 8 : 0);
+    DWS_CHECK(lds <= 160 * 1024, DWS_ERR_INVALID, "dws_spectral_distance: %zu bytes of LDS (160 KiB per workgroup)", lds);
+    DWS_HIP(hipFuncSetAttribute((const void*)spectral_frame_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL(spectral_frame_kernel, dim3((unsigned)f_max, (unsigned)B), dim3(256), lds, (hipStream_t)stream, x, y,
+                       lengths, window, mel_basis, cep, workspace, (int)T, n_fft, hop, n_mels, n_cep, f_max, clip);
+    DWS_HIP(hipGetLastError());
+    hipLaunchKernelGGL(spectral_clip_sum_kernel, dim3((unsigned)B), dim3(64), 0, (hipStream_t)stream, workspace, lengths, out,
+                       (int)T, n_fft, hop, f_max);
+    DWS_HIP(hipGetLastError());
+    return DWS_OK;
+}

@@ -1,0 +1,175 @@
+"""Objective metrics of a directory of generated wavs against a directory of recordings (not in the reference).
+
+    python -m diffwave_sashimi_amd.evaluate --generated exp/<run>/waveforms/<iter> --reference /data/LJSpeech/wavs \
+        --config-dir /path/to/configs experiment=ljspeech --json metrics.json
+
+Files are paired by wav stem; a generated stem with ``generate``'s ``{n}k_`` prefix (``0k_LJ001-0001``) matches
+``LJ001-0001`` when the plain stem has no partner.  Every pair is trimmed to its shorter member (a vocoded clip is
+``frames x hop_length`` samples long, up to one hop more than its recording) and goes through
+``metrics.spectral_metrics`` in ragged batches, longest first.  One table row per metric is printed -- mean, standard
+deviation, 95 % interval of the mean, n -- and ``--json`` receives the per-file values.
+
+The STFT keys (``--sampling-rate``, ``--filter-length``, ``--hop-length``, ``--win-length``, ``--mel-fmin``,
+``--mel-fmax``) set the transform of ``ls_mae`` / ``lsd`` / ``mcd``; with ``--config-dir`` they are read from the
+composed config's ``dataset`` (``key=value`` overrides as for ``generate``), and a key spelled out wins.
+"""
+import argparse
+import json
+import math
+import os
+import re
+import sys
+
+import numpy as np
+import torch
+
+from . import metrics as _metrics
+
+STFT_KEYS = ("sampling_rate", "filter_length", "hop_length", "win_length", "mel_fmin", "mel_fmax")
+STFT_DEFAULTS = dict(sampling_rate=22050, filter_length=1024, hop_length=256, win_length=1024, mel_fmin=0.0, mel_fmax=8000.0)
+_PREFIX = re.compile(r"^\d+k_(.+)$")
+
+
+def _stems(directory):
+    if not os.path.isdir(directory):
+        raise ValueError(f"evaluate: {directory} is not a directory")
+    return sorted(f[:-4] for f in os.listdir(directory) if f.endswith(".wav"))
+
+
+def pair_files(generated_dir, reference_dir):
+    """``(pairs, unpaired_generated, unpaired_reference)``: ``pairs`` is a sorted list of ``(generated stem, reference
+    stem)``.  A generated stem pairs with the reference of the same name; one without such a partner and of the form
+    ``{n}k_{stem}`` pairs with ``{stem}``.  A reference that two generated files claim is an error (ValueError)."""
+    gen, ref = _stems(generated_dir), set(_stems(reference_dir))
+    pairs, lone, taken = [], [], {}
+    for g in gen:
+        m = _PREFIX.match(g)
+        r = g if g in ref else (m.group(1) if m and m.group(1) in ref else None)
+        if r is None:
+            lone.append(g)
+            continue
+        if r in taken:
+            raise ValueError(f"evaluate: {taken[r]}.wav and {g}.wav both pair with the reference {r}.wav")
+        taken[r] = g
+        pairs.append((g, r))
+    return pairs, lone, sorted(ref - set(taken))
+
+
+def load_wav(path, sampling_rate):
+    """A wav as float32 [T]: int16 scaled by 1/32768, float as it is, the first channel; ValueError on another rate or
+    sample type."""
+    from scipy.io import wavfile
+    sr, x = wavfile.read(path)
+    if sr != sampling_rate:
+        raise ValueError(f"evaluate: {path} has sampling rate {sr}, expected {sampling_rate}")
+    if x.dtype == np.int16:
+        x = x.astype(np.float32) / 32768.0
+    elif x.dtype.kind == "f":
+        x = x.astype(np.float32)
+    else:
+        raise ValueError(f"evaluate: {path} holds {x.dtype} samples (int16 and float wavs are read)")
+    if x.ndim == 2:
+        x = x[:, 0]
+    return torch.from_numpy(np.ascontiguousarray(x))
+
+
+def load_pairs(generated_dir, reference_dir, pairs, sampling_rate, hop_length):
+    """The wavs of ``pairs`` as a list of ``(x, y)`` float32 [len] tensors, each trimmed to its shorter member; a pair
+    whose lengths differ by more than ``hop_length`` is not the same utterance (ValueError)."""
+    out = []
+    for g, r in pairs:
+        x = load_wav(os.path.join(generated_dir, g + ".wav"), sampling_rate)
+        y = load_wav(os.path.join(reference_dir, r + ".wav"), sampling_rate)
+        if abs(x.shape[0] - y.shape[0]) > hop_length:
+            raise ValueError(f"evaluate: {g}.wav has {x.shape[0]} samples and {r}.wav {y.shape[0]}: more than one hop "
+                             f"({hop_length}) apart")
+        n = min(x.shape[0], y.shape[0])
+        out.append((x[:n], y[:n]))
+    return out
+
+
+def evaluate_pairs(clips, stft, batch_size=16, device=None, resolutions=_metrics.MR_STFT_RESOLUTIONS, n_cep=13):
+    """``spectral_metrics`` of a list of ``(x, y)`` clips of different lengths: sorted longest first and cut into
+    batches of ``batch_size`` (``generate.ragged_plan``), each batch at its longest length with ``lengths=``.  Returns a
+    list of dicts of floats in the order of ``clips``.  Without a GPU the metric call raises (there is no CPU path)."""
+    from .generate import ragged_plan
+    if device is None:
+        device = "cuda" if torch.cuda.is_available() else "cpu"
+    rows = [None] * len(clips)
+    lens = [int(x.shape[0]) for x, _ in clips]
+    for batch in ragged_plan(lens, batch_size) if clips else []:
+        T = lens[batch[0]]
+        x, y = torch.zeros(len(batch), T), torch.zeros(len(batch), T)
+        for b, k in enumerate(batch):
+            x[b, :lens[k]], y[b, :lens[k]] = clips[k]
+        m = _metrics.spectral_metrics(x.to(device), y.to(device), [lens[k] for k in batch], stft=stft,
+                                      resolutions=resolutions, n_cep=n_cep)
+        for b, k in enumerate(batch):
+            rows[k] = {key: float(v[b]) for key, v in m.items()}
+    return rows
+
+
+def summarise(rows):
+    """Per metric ``(mean, standard deviation, half width of the 95 % interval of the mean, n)``: the sample standard
+    deviation (n - 1) and the normal interval 1.96 s / sqrt(n); both 0 for a single file."""
+    out = {}
+    for key in (rows[0] if rows else {}):
+        v = np.array([r[key] for r in rows], dtype=np.float64)
+        sd = float(v.std(ddof=1)) if len(v) > 1 else 0.0
+        out[key] = (float(v.mean()), sd, 1.96 * sd / math.sqrt(len(v)), len(v))
+    return out
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--generated", required=True, help="directory of generated wavs")
+    ap.add_argument("--reference", required=True, help="directory of the recordings")
+    ap.add_argument("--config-dir", help="Hydra-style config tree: the STFT keys are read from its dataset")
+    for k in STFT_KEYS:
+        ap.add_argument("--" + k.replace("_", "-"), type=int if k.endswith("length") or k == "sampling_rate" else float)
+    ap.add_argument("--batch-size", type=int, default=16)
+    ap.add_argument("--json", help="write the per-file values here")
+    ap.add_argument("--strict", action="store_true", help="an unpaired file is an error")
+    ap.add_argument("overrides", nargs="*", help="key=value overrides of --config-dir, e.g. experiment=ljspeech")
+    args = ap.parse_args(argv)
+    if args.overrides and not args.config_dir:
+        raise ValueError("evaluate: key=value overrides need --config-dir")
+    keys = dict(STFT_DEFAULTS)
+    if args.config_dir:
+        from .generate import load_config
+        ds = load_config(args.config_dir, args.overrides).get("dataset") or {}
+        keys.update({k: ds[k] for k in STFT_KEYS if k in ds})
+    keys.update({k: getattr(args, k) for k in STFT_KEYS if getattr(args, k) is not None})
+    if args.batch_size < 1:
+        raise ValueError(f"evaluate: --batch-size {args.batch_size}: expected an integer >= 1")
+
+    pairs, lone_gen, lone_ref = pair_files(args.generated, args.reference)
+    for name, lone in (("generated", lone_gen), ("reference", lone_ref)):
+        if lone:
+            print(f"unpaired {name} files ({len(lone)}): " + " ".join(s + ".wav" for s in lone))
+    if args.strict and (lone_gen or lone_ref):
+        raise ValueError(f"evaluate: --strict: {len(lone_gen)} generated and {len(lone_ref)} reference files have no partner")
+    if not pairs:
+        raise ValueError(f"evaluate: no generated wav under {args.generated} pairs with a wav under {args.reference}")
+    clips = load_pairs(args.generated, args.reference, pairs, keys["sampling_rate"], keys["hop_length"])
+    from .mel import TacotronSTFT
+    stft = TacotronSTFT(filter_length=keys["filter_length"], hop_length=keys["hop_length"], win_length=keys["win_length"],
+                        sampling_rate=keys["sampling_rate"], mel_fmin=keys["mel_fmin"], mel_fmax=keys["mel_fmax"])
+    rows = evaluate_pairs(clips, stft, args.batch_size)
+    summary = summarise(rows)
+    print(f"{'metric':<20}{'mean':>12}{'std':>12}{'95% +-':>12}{'n':>6}")
+    for key, (mean, sd, ci, n) in summary.items():
+        print(f"{key:<20}{mean:>12.6f}{sd:>12.6f}{ci:>12.6f}{n:>6d}")
+    if args.json:
+        record = {"stft": keys,
+                  "files": [dict(generated=g + ".wav", reference=r + ".wav", samples=int(c[0].shape[0]), **row)
+                            for (g, r), c, row in zip(pairs, clips, rows)],
+                  "summary": {k: dict(mean=m, std=s, ci95=c, n=n) for k, (m, s, c, n) in summary.items()},
+                  "unpaired_generated": lone_gen, "unpaired_reference": lone_ref}
+        with open(args.json, "w") as f:
+            json.dump(record, f, indent=1)
+    return rows
+
+
+if __name__ == "__main__":
+    main(sys.argv[1:])

@@ -383,6 +383,29 @@ def _load_clip(dataset_cfg, stem, audio_length, conditional):
     return t.unsqueeze(0)
 
 
+def _report_metrics(i, audio, stems, numbers, lens, dataset_cfg, rows):
+    """``generate.report_metrics``: the clips of batch ``i`` (``audio`` [B, 1, L] on the GPU, clip b its first
+    ``lens[b]`` samples, made from the mel of ``stems[b]``) against their source wavs, each pair trimmed to its shorter
+    member.  Prints the batch means and appends one dict per clip to ``rows`` where that is a list."""
+    from .mel import MAX_WAV_VALUE, TacotronSTFT, load_wav_to_torch
+    from .metrics import METRICS, spectral_metrics
+    keys = ("filter_length", "hop_length", "win_length", "sampling_rate", "mel_fmin", "mel_fmax")
+    stft = TacotronSTFT(**{k: dataset_cfg[k] for k in keys if k in dataset_cfg})
+    sources = {s: load_wav_to_torch(os.path.join(str(dataset_cfg["data_path"]), f"{s}.wav"))[0] / MAX_WAV_VALUE
+               for s in set(stems)}
+    n = [min(int(lens[b]), int(sources[s].shape[0])) for b, s in enumerate(stems)]
+    x = audio[:, 0, :max(n)].to(torch.float32)
+    y = torch.zeros(len(stems), max(n), dtype=torch.float32)
+    for b, s in enumerate(stems):
+        y[b, :n[b]] = sources[s][:n[b]]
+    m = spectral_metrics(x, y.to(x.device), n, stft=stft)
+    print(f"batch {i} metrics: " + "  ".join(f"{k} = {float(m[k].mean()):.4f}" for k in METRICS) +
+          f"  (mcd in dB; means of {len(stems)} clips against their source wavs)")
+    if rows is not None:
+        for b, s in enumerate(stems):
+            rows.append(dict({k: float(v[b]) for k, v in m.items()}, name=s, clip=numbers[b]))
+
+
 @torch.no_grad()
 def generate(rank, diffusion_cfg, model_cfg, dataset_cfg, ckpt_iter="max", n_samples=1, name=None, batch_size=None,
              ckpt_smooth=None, mel_path=None, mel_name=None, dataloader=None, exp_root="exp", seed=None,
@@ -390,7 +413,8 @@ def generate(rank, diffusion_cfg, model_cfg, dataset_cfg, ckpt_iter="max", n_sam
              start_name=None, start_step=None, start_noise=True, resample_jump=None, resample_n=None, spacing=None,
              guide_name=None, guide_op=None, guide_clip=None, guide_factor=None, guide_scale=None, label=None,
              cfg_scale=None, ema=None, clip_seeds=None, clips=None, num_ranks=None, report_mel=None, mel_errors=None,
-             mel_names=None, prior=None, prior_energy_max=None, prior_energy_min=None, prior_std_min=None):
+             mel_names=None, prior=None, prior_energy_max=None, prior_energy_min=None, prior_std_min=None,
+             report_metrics=None, metric_rows=None):
     """``generate.py:58-200``.  ``ckpt_iter`` may additionally be ``"init"``: seeded random weights
     (no checkpoint), for smoke runs without trained weights.  ``precision`` (not in the reference; CLI:
     ``+engine.precision=bf16x6|f16x3``): the engine's opt-in matrix arithmetic, see ``include/dws.h``.
@@ -425,6 +449,13 @@ def generate(rank, diffusion_cfg, model_cfg, dataset_cfg, ckpt_iter="max", n_sam
     conditioning mel itself, which keeps a vocoder on its mel.  ``report_mel=true`` (mel-conditional runs, any sampler)
     prints per batch the mean absolute difference between the engine's log-mel of the generated clips and the
     conditioning mel (over the frames of the condition), and appends it to ``mel_errors`` where that is a list.
+
+    Objective metrics (not in the reference; ``mel_name`` / ``mel_names`` runs whose mel is computed from
+    ``<dataset.data_path>/<stem>.wav``, any sampler): ``report_metrics=true`` compares every written clip with its source
+    wav through ``metrics.spectral_metrics`` (the pair trimmed to the recording's length; the log-mel terms at
+    ``dataset``'s transform), prints per batch the means of ``mr_stft / ls_mae / lsd / mcd`` and appends one dict per clip
+    (``name``, ``clip`` and every metric) to ``metric_rows`` where that is a list.  With ``mel_path`` tensors (there is no
+    source wav) and on unconditional runs it is a ValueError.
 
     Class-conditional models (``model.n_classes = K``; not in the reference): ``label`` is a class index in 0..K (K = the
     null class), a list of them cycled over the samples, or ``all`` (= 0..K-1 in turn); the wav names get ``_c{label}``.
@@ -525,6 +556,16 @@ def generate(rank, diffusion_cfg, model_cfg, dataset_cfg, ckpt_iter="max", n_sam
         if report_mel and mel_name is None:
             raise ValueError("generate.report_mel needs a mel-conditional run (generate.mel_name: the error is measured "
                              "against the conditioning mel)")
+
+    if report_metrics is not None:
+        if not isinstance(report_metrics, bool):
+            raise ValueError(f"generate.report_metrics={report_metrics!r}: expected true or false")
+        if report_metrics and (model_cfg.get("unconditional") or (mel_name is None and mel_names is None)):
+            raise ValueError("generate.report_metrics needs a mel-conditional run (generate.mel_name or generate.mel_names: "
+                             "the clips are compared with the wavs their mels were computed from)")
+        if report_metrics and mel_path is not None:
+            raise ValueError("generate.report_metrics does not combine with generate.mel_path (pre-computed mel tensors "
+                             "have no source wav to compare with)")
 
     n_classes = check_n_classes(model_cfg.get("n_classes"))
     labels_of = None        # the class of every sample, cycled
@@ -700,6 +741,8 @@ def generate(rank, diffusion_cfg, model_cfg, dataset_cfg, ckpt_iter="max", n_sam
                 x = sampling(net, size, dh, condition=mel, seed=s, lengths=lens, **pr)
             for b, k in enumerate(batch):
                 clips_out[k] = x[b, :, :lens[b]].clone()
+            if report_metrics:
+                _report_metrics(i, x, [mel_names[k] for k in batch], batch, lens, dataset_cfg, metric_rows)
         torch.cuda.synchronize()
         made = [k for k, c in enumerate(clips_out) if c is not None]
         print(f"generated {len(made)} utterances of {len(mel_names)} at iteration {ckpt_iter} in "
@@ -803,6 +846,9 @@ def generate(rank, diffusion_cfg, model_cfg, dataset_cfg, ckpt_iter="max", n_sam
             print(f"batch {i} mel error: mean |log-mel(generated) - condition| = {err:.4f}")
             if mel_errors is not None:
                 mel_errors.append(err)
+        if report_metrics:
+            _report_metrics(i, out[-1], [mel_name] * len(batch), batch, [audio_length] * len(batch), dataset_cfg,
+                            metric_rows)
     generated_audio = torch.cat(out, dim=0) if out else torch.empty(0, 1, audio_length, device="cuda")
     torch.cuda.synchronize()
     print(f"generated {len(numbers)} samples shape {tuple(generated_audio.shape)} at iteration {ckpt_iter} in "

@@ -1,0 +1,214 @@
+"""Objective audio metrics between generated and reference waveforms on the HIP engine (not in the reference).
+
+``spectral_metrics(x, y)`` compares two batches of time-aligned waveforms and returns, per clip,
+
+* ``mr_stft``: Parallel WaveGAN's multi-resolution STFT distance (Yamamoto et al., ICASSP 2020), the mean over the
+  resolutions of spectral convergence + log-magnitude L1 -- and both terms per resolution, ``sc_{n_fft}_{hop}_{win}`` /
+  ``mag_{n_fft}_{hop}_{win}``;
+* ``ls_mae``: the mean absolute difference of the engine's log-mel spectrograms (PriorGrad's LS-MAE);
+* ``lsd``: the log-spectral distance, the mean over frames of ``sqrt(mean_k (log10|Y|^2 - log10|X|^2)^2)``;
+* ``mcd``: a mel-cepstral distortion in dB (Kubichek 1993), see ``spectral_metrics``.
+
+The transform and every sum run in ``dws_spectral_distance`` (``csrc/spectral_kernels.hip``), one fused launch per
+resolution; this module builds the constant tables, checks the arguments and divides the sums.  There is no CPU path.
+"""
+import ctypes
+import math
+
+import numpy as np
+import torch
+
+from . import _lib
+from .mel import MEL_CLIP, TacotronSTFT, padded_hann
+
+# (n_fft, hop, win) of Parallel WaveGAN's multi-resolution STFT loss
+MR_STFT_RESOLUTIONS = ((1024, 120, 600), (2048, 240, 1200), (512, 50, 240))
+N_FFT_MIN, N_FFT_MAX = 64, 2048
+SUMS = ("sc_num", "sc_den", "mag_abs", "lsd_sum", "mel_abs", "mcd_sum")      # the columns of ``spectral_sums``
+MCD_DB = 10.0 * math.sqrt(2.0) / math.log(10.0)
+
+_default = None
+_windows = {}       # (device, n_fft, win) -> window [n_fft]
+_ceps = {}          # (device, n_cep, n_mels) -> D [n_cep, n_mels] (float64)
+
+
+def default_stft():
+    """The ``TacotronSTFT()`` of the defaults (LJSpeech's transform), built once."""
+    global _default
+    if _default is None:
+        _default = TacotronSTFT()
+    return _default
+
+
+def cepstral_table(n_cep, n_mels):
+    """``D[d-1, k] = sqrt(2 / K) cos(pi d (k + 1/2) / K)``, ``d = 1 .. n_cep``, ``K = n_mels``: rows 1 .. n_cep of the
+    orthonormal DCT-II (row 0, the frame's level, is left out as in every MCD).  float64 ``[n_cep, n_mels]``."""
+    d = torch.arange(1, n_cep + 1, dtype=torch.float64)[:, None]
+    k = torch.arange(n_mels, dtype=torch.float64)[None, :]
+    return math.sqrt(2.0 / n_mels) * torch.cos(math.pi * d * (k + 0.5) / n_mels)
+
+
+def _is_int(v):
+    return isinstance(v, (int, np.integer)) and not isinstance(v, bool)
+
+
+def check_resolution(n_fft, hop, win, lengths):
+    """ValueError unless ``(n_fft, hop, win)`` is a resolution the kernel runs on clips of these ``lengths`` (host
+    integers): ``n_fft`` a power of two in 64 .. 2048, ``1 <= win <= n_fft``, ``hop >= 1``, every clip at least
+    ``n_fft / 2 + 1`` samples long (reflect padding; nothing is clamped)."""
+    res = f"resolution (n_fft={n_fft!r}, hop={hop!r}, win={win!r})"
+    if not (_is_int(n_fft) and _is_int(hop) and _is_int(win)):
+        raise ValueError(f"spectral_metrics: {res}: expected three integers")
+    if not (N_FFT_MIN <= n_fft <= N_FFT_MAX) or n_fft & (n_fft - 1):
+        raise ValueError(f"spectral_metrics: {res}: n_fft must be a power of two in {N_FFT_MIN} .. {N_FFT_MAX}")
+    if not 1 <= win <= n_fft:
+        raise ValueError(f"spectral_metrics: {res}: win must be in 1 .. n_fft")
+    if hop < 1:
+        raise ValueError(f"spectral_metrics: {res}: hop must be at least 1")
+    for b, n in enumerate(lengths):
+        if n < n_fft // 2 + 1:
+            raise ValueError(f"spectral_metrics: {res}: clip {b} has {n} samples, reflect padding needs at least "
+                             f"n_fft/2 + 1 = {n_fft // 2 + 1}")
+
+
+def _pair(x, y, lengths):
+    """Shape checks of a pair of batches (ValueError): the two as [B, T] views and the host lengths."""
+    for name, t in (("x", x), ("y", y)):
+        if not isinstance(t, torch.Tensor) or not t.dtype.is_floating_point or t.dim() not in (2, 3) or \
+                (t.dim() == 3 and t.shape[1] != 1):
+            raise ValueError(f"spectral_metrics: {name} has shape {tuple(getattr(t, 'shape', ()))!r}, expected a float "
+                             "tensor [B, T] or [B, 1, T]")
+    x = x[:, 0] if x.dim() == 3 else x
+    y = y[:, 0] if y.dim() == 3 else y
+    if x.shape != y.shape or x.shape[0] < 1 or x.shape[1] < 1:
+        raise ValueError(f"spectral_metrics: x {tuple(x.shape)} and y {tuple(y.shape)} must be two equal non-empty batches")
+    B, T = (int(v) for v in x.shape)
+    if lengths is None:
+        return x, y, None, [T] * B
+    host = lengths.detach().cpu().tolist() if isinstance(lengths, torch.Tensor) else list(lengths)
+    if len(host) != B or (isinstance(lengths, torch.Tensor) and lengths.dim() != 1):
+        raise ValueError(f"spectral_metrics: lengths has {len(host)} entries for a batch of {B} clips")
+    if any(not _is_int(n) or not 1 <= n <= T for n in host):
+        raise ValueError(f"spectral_metrics: lengths = {host!r}: expected integers in 1 .. T = {T}")
+    return x, y, [int(n) for n in host], [int(n) for n in host]
+
+
+def _need_gpu(x, y):
+    if x.device.type != "cuda" or y.device != x.device:
+        raise RuntimeError("libdws runs on the GPU only: move both waveforms to one cuda device (there is no CPU fallback)")
+
+
+def _window(device, n_fft, win):
+    key = (device, n_fft, win)
+    if key not in _windows:
+        _windows[key] = torch.from_numpy(padded_hann(win, n_fft)).to(device)
+    return _windows[key]
+
+
+def _cep(device, n_cep, n_mels):
+    key = (device, n_cep, n_mels)
+    if key not in _ceps:
+        _ceps[key] = cepstral_table(n_cep, n_mels).to(device).contiguous()
+    return _ceps[key]
+
+
+def _run(x, y, host, n_fft, hop, win, basis, cep):
+    """One ``dws_spectral_distance`` call on checked arguments: float64 [B, 6] on the device."""
+    lib = _lib.load()
+    B, T = x.shape
+    dev = x.device
+    out = torch.empty(B, len(SUMS), device=dev, dtype=torch.float64)
+    ws = torch.empty(lib.dws_spectral_distance_workspace(B, T, hop) // 8, device=dev, dtype=torch.float64)
+    if host is None:
+        dev_len = host_len = None
+    else:
+        host_len = (ctypes.c_int32 * B)(*host)
+        dev_len = torch.tensor(host, dtype=torch.int32).to(dev)
+    n_mels = 0 if basis is None else int(basis.shape[0])
+    n_cep = 0 if cep is None else int(cep.shape[0])
+    with torch.cuda.device(dev):
+        _lib.check(lib.dws_spectral_distance(x.data_ptr(), y.data_ptr(), B, T, _lib.ptr(dev_len), host_len,
+                                             _window(dev, n_fft, win).data_ptr(), n_fft, hop, _lib.ptr(basis), n_mels,
+                                             MEL_CLIP, _lib.ptr(cep), n_cep, ws.data_ptr(), out.data_ptr(),
+                                             _lib.current_stream()))
+    return out
+
+
+def spectral_sums(x, y, lengths=None, *, n_fft, hop, win, mel_basis=None, n_cep=0):
+    """The six sums of ``dws_spectral_distance`` (include/dws.h) at one resolution, columns ``SUMS``: float64 [B, 6] on
+    the CPU.  ``mel_basis`` [n_mels, n_fft/2 + 1] adds ``mel_abs`` and, with ``n_cep`` > 0, ``mcd_sum``.  A clip's row
+    depends on its own samples and length alone, bit for bit.  Arguments are checked first (ValueError), then the
+    device (RuntimeError)."""
+    x, y, host, lens = _pair(x, y, lengths)
+    check_resolution(n_fft, hop, win, lens)
+    if mel_basis is not None and tuple(mel_basis.shape) != (mel_basis.shape[0], n_fft // 2 + 1):
+        raise ValueError(f"spectral_sums: mel_basis {tuple(mel_basis.shape)} does not have n_fft/2 + 1 = {n_fft // 2 + 1} columns")
+    if not _is_int(n_cep) or n_cep < 0 or n_cep > 256 or (n_cep and mel_basis is None):
+        raise ValueError(f"spectral_sums: n_cep = {n_cep!r} (0 .. 256, and a mel_basis with it)")
+    _need_gpu(x, y)
+    x = x.detach().to(torch.float32).contiguous()
+    y = y.detach().to(torch.float32).contiguous()
+    basis = None if mel_basis is None else mel_basis.to(device=x.device, dtype=torch.float32).contiguous()
+    cep = _cep(x.device, n_cep, int(basis.shape[0])) if n_cep else None
+    return _run(x, y, host, n_fft, hop, win, basis, cep).cpu()
+
+
+def resolution_key(res):
+    return "{}_{}_{}".format(*res)
+
+
+def spectral_metrics(x, y, lengths=None, *, stft=None, resolutions=MR_STFT_RESOLUTIONS, n_cep=13):
+    """Objective distances of generated ``x`` from reference ``y`` ([B, T] or [B, 1, T], cuda), clip by clip; ``lengths``
+    (B integers) marks ragged batches: clip b is its first ``lengths[b]`` samples, nothing behind them is read.  Returns a
+    dict of float64 [B] CPU tensors:
+
+    ``sc_{n_fft}_{hop}_{win}``, ``mag_{n_fft}_{hop}_{win}`` for each of ``resolutions`` (default: Parallel WaveGAN's three):
+    spectral convergence ``sqrt(sum (|Y|-|X|)^2 / sum |Y|^2)`` and the mean ``|ln|Y| - ln|X||`` over bins and frames,
+    magnitudes floored at ``sqrt(1e-7)``; ``mr_stft``: the mean over the resolutions of ``sc + mag``.
+
+    From one more pass at ``stft``'s own ``filter_length / hop_length / win_length`` with its mel filterbank (default
+    ``TacotronSTFT()``): ``ls_mae``, the mean ``|logmel(Y) - logmel(X)|`` over bands and frames (what
+    ``generate.report_mel`` prints, for pairs of waveforms); ``lsd``, the mean over frames of the root mean square over bins
+    of ``log10|Y|^2 - log10|X|^2``; ``mcd = (10 sqrt 2 / ln 10) mean_f ||D (logmel(Y)_f - logmel(X)_f)||`` in dB with
+    ``D = cepstral_table(n_cep, n_mels)``.
+
+    ``mcd`` is an MFCC-style distortion of TIME-ALIGNED signals on the engine's own log-mel: there is no dynamic time
+    warping and no SPTK mel-cepstral analysis, so its absolute values are not those of the papers that report MCD (PriorGrad
+    among them); it orders systems evaluated with this function.  Every frame of a clip counts (``f = 0 .. len // hop``).
+
+    Arguments are checked before anything runs: a resolution the kernel does not build or a clip shorter than
+    ``n_fft / 2 + 1`` raises ValueError naming the resolution and the clip; CPU tensors raise RuntimeError."""
+    stft = default_stft() if stft is None else stft
+    x, y, host, lens = _pair(x, y, lengths)
+    resolutions = [tuple(r) for r in resolutions]
+    if not resolutions or any(len(r) != 3 for r in resolutions):
+        raise ValueError(f"spectral_metrics: resolutions = {resolutions!r}: expected (n_fft, hop, win) triples")
+    own = (stft.filter_length, stft.hop_length, stft.win_length)
+    for r in resolutions + [own]:
+        check_resolution(*r, lens)
+    if not _is_int(n_cep) or not 1 <= n_cep <= min(256, stft.n_mel_channels - 1):
+        raise ValueError(f"spectral_metrics: n_cep = {n_cep!r} (1 .. min(256, n_mel_channels - 1))")
+    _need_gpu(x, y)
+    x = x.detach().to(torch.float32).contiguous()
+    y = y.detach().to(torch.float32).contiguous()
+    out = {}
+    total = 0.0
+    for r in resolutions:
+        n_fft, hop, _ = r
+        s = _run(x, y, host, *r, None, None).cpu()
+        frames = torch.tensor([n // hop + 1 for n in lens], dtype=torch.float64)
+        sc = torch.sqrt(s[:, 0] / s[:, 1])
+        mag = s[:, 2] / (frames * (n_fft // 2 + 1))
+        out["sc_" + resolution_key(r)], out["mag_" + resolution_key(r)] = sc, mag
+        total = total + sc + mag
+    out["mr_stft"] = total / len(resolutions)
+    _, basis = stft._tables(x.device)
+    s = _run(x, y, host, *own, basis, _cep(x.device, n_cep, stft.n_mel_channels)).cpu()
+    frames = torch.tensor([n // own[1] + 1 for n in lens], dtype=torch.float64)
+    out["ls_mae"] = s[:, 4] / (frames * stft.n_mel_channels)
+    out["lsd"] = s[:, 3] / frames
+    out["mcd"] = MCD_DB * s[:, 5] / frames
+    return out
+
+
+METRICS = ("mr_stft", "ls_mae", "lsd", "mcd")       # the four headline numbers, in the order they are printed

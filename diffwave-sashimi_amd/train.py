@@ -5,7 +5,9 @@ config tree + ``key=value`` overrides, ``exp/<run>/checkpoint/<iter>.pkl`` holdi
 ``{'model_state_dict', 'optimizer_state_dict'}``, resume from ``train.ckpt_iter`` (``max`` = newest),
 Adam at ``train.learning_rate``, one process per GPU with ``apply_gradient_allreduce`` (RCCL), rank-0
 checkpoints followed by an in-loop ``generate`` call.  wandb is replaced by a JSON-lines log
-(``exp/<run>/train_log.jsonl``, same keys: ``train/loss``, ``train/log_loss``, ``train/loss_epoch``).
+(``exp/<run>/train_log.jsonl``, same keys: ``train/loss``, ``train/log_loss``, ``train/loss_epoch``).  With
+``+generate.report_metrics=true`` the in-loop ``generate`` compares its clips with their source wavs and the log gets
+``val/mr_stft``, ``val/ls_mae``, ``val/lsd`` and ``val/mcd`` at that iteration (``metrics.py``).
 
     python -m diffwave_sashimi_amd.train --config-dir /path/to/configs experiment=sc09 model=sashimi \
         dataset.data_path=/data/sc09 train.batch_size_per_gpu=32
@@ -366,10 +368,16 @@ def train(rank, num_gpus, diffusion_cfg, model_cfg, dataset_cfg, generate_cfg, c
                         gen.setdefault("label", "all")      # the classes in turn over the batch
                     net.eval()
                     wavs = []
+                    rows = [] if gen.get("report_metrics") else None      # generate.report_metrics: metrics.py
+                    if rows is not None:
+                        gen["metric_rows"] = rows
                     generate(rank, diffusion_cfg, model_cfg, dataset_cfg, name=name, exp_root=exp_root,
                              written=wavs, **gen)
                     net.train()
                     log({"val/audio": wavs}, n_iter)     # the reference logs the clips to wandb (`train.py:180-183`)
+                    if rows:        # the means over the clips just written, against their source wavs
+                        log({"val/" + k: float(np.mean([r[k] for r in rows]))
+                             for k in ("mr_stft", "ls_mae", "lsd", "mcd")}, n_iter)
             n_iter += 1
             if n_iter >= n_iters + 1:
                 break

@@ -641,6 +641,42 @@ int dws_mel_spectrogram_backward(const float* audio, int64_t B, int64_t T, const
                                  int32_t n_fft, int32_t hop, int32_t n_mels, float clip, const float* dout, float* daudio,
                                  float* workspace, void* stream);
 
+/* Objective spectral distances between two batches of waveforms (not in the reference): x (generated) and y
+ * (reference), both DEVICE float32 [B][T], compared at ONE STFT resolution in one fused launch -- no spectrogram goes to
+ * memory.  Framing is dws_mel_spectrogram's (= torch.stft(center=True, pad_mode="reflect")) with a length per clip: with
+ * len_b = lengths[b] (T where lengths is null), N = n_fft, w = window [N] (DEVICE; a periodic Hann window of win <= N
+ * points centred in N), rho_b the reflect map about the clip's OWN ends (j < 0 -> -j, j >= len_b -> 2(len_b-1) - j),
+ *     frame_f[i] = w[i] s[rho_b(f hop + i - N/2)]          f = 0 .. len_b / hop,   s = x or y
+ *     Re_k, Im_k = sum_i frame_f[i] (cos, sin)(2 pi i k / N)                        k = 0 .. N/2   (K = N/2 + 1 bins)
+ *     |S|_k = sqrt(max(Re_k^2 + Im_k^2, 1e-7))                                      (Parallel WaveGAN's floor)
+ * out [B][6] (DEVICE, double) receives the clip's sums over its frames (and bins):
+ *     out[b][0] = sum (|Y| - |X|)^2          out[b][1] = sum |Y|^2                  (spectral convergence = sqrt(0 / 1))
+ *     out[b][2] = sum |ln|Y| - ln|X||                                               (log-magnitude L1)
+ *     out[b][3] = sum_f sqrt(mean_k (log10|Y|^2 - log10|X|^2)^2)                    (log-spectral distance)
+ * With mel_basis [n_mels][K] (DEVICE, float32) and m(S)_f = ln(max(mel_basis . sqrt(Re^2 + Im^2), clip)) -- unfloored
+ * magnitudes, the formula of dws_mel_spectrogram --
+ *     out[b][4] = sum |m(Y) - m(X)|                                                 (over bands and frames)
+ * and with cep [n_cep][n_mels] (DEVICE, DOUBLE; needs mel_basis; n_cep <= 256)
+ *     out[b][5] = sum_f || cep . (m(Y)_f - m(X)_f) ||_2 ;
+ * out[b][4] / out[b][5] are 0 without the respective table (null pointer, and then n_mels / n_cep = 0).
+ * Order of summation: bins within a thread ascending (thread t owns k = t, t + 256, ...), lanes of a wave by an xor tree
+ * (fp32), the four waves in wave order, then a clip's frames in ascending order (double); the band logarithms and the
+ * cepstral products are taken in double.  The result is bitwise reproducible, and clip b's six numbers depend on its own
+ * len_b samples alone: not on B, T, b or on anything stored behind len_b (which is never read and may be NaN).
+ * lengths: DEVICE int32 [B] or null; lengths_host: the same numbers on the HOST (both or neither) -- they are checked
+ * there, nothing waits for the GPU.  workspace: DEVICE, dws_spectral_distance_workspace(B, T, hop) bytes
+ * ([B][T/hop + 1][6] doubles) owned by the caller (overwritten; the library allocates nothing per call).
+ * DWS_ERR_INVALID: a null x, y, window, workspace or out; n_fft not a power of two in 64 .. 2048; hop < 1; B outside
+ * 1 .. 65535; a len_b outside n_fft/2 + 1 .. T (reflect padding; no length is clamped); tables and counts that do not
+ * match as stated above. */
+int dws_spectral_distance(const float* x, const float* y, int64_t B, int64_t T, const int32_t* lengths,
+                          const int32_t* lengths_host, const float* window, int32_t n_fft, int32_t hop,
+                          const float* mel_basis, int32_t n_mels, float clip, const double* cep, int32_t n_cep,
+                          double* workspace, double* out, void* stream);
+
+/* Bytes of dws_spectral_distance's workspace; 0 for a shape it refuses. */
+int64_t dws_spectral_distance_workspace(int64_t B, int64_t T, int32_t hop);
+
 /* The arithmetic of precision="bf16x6" alone (accuracy tests; not a tuned GEMM): C[M][N] = A[M][K] . B[K][N], row-major
  * fp32 device tensors, every operand split into three bf16 terms in registers, six bf16 MFMA products per term pair
  * accumulated in fp32 -- exactly what the bf16x6 layer kernels execute per k-block.  M, N multiples of 32, K of 16. */

@@ -1,0 +1,67 @@
+"""Time of the objective-metrics kernel per STFT resolution ("Objective metrics"), and beside it
+the float32 ``torch.stft`` restatement of the same sums (tests/spectral_reference.py: ``sums(..., dtype=float32)``) on
+the same inputs on the same GPU.
+
+    python tools/metrics_times.py [--batch 16] [--samples 160000] [--repeats 20]
+
+One JSON line per pass (Parallel WaveGAN's three resolutions and the mel pass of ``TacotronSTFT()``): the median over
+--repeats of one ``dws_spectral_distance`` call between two events (tables cached, workspace allocation included, no
+copy to the host), the same for the restatement, and the largest relative difference of the two results.
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--batch", type=int, default=16)
+    ap.add_argument("--samples", type=int, default=160000)
+    ap.add_argument("--repeats", type=int, default=20)
+    args = ap.parse_args()
+    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+    import torch
+    from diffwave_sashimi_amd import metrics
+    from tests import spectral_reference as ref
+    dev = torch.device("cuda")
+    gen = torch.Generator().manual_seed(1)
+    y = (torch.randn(args.batch, args.samples, generator=gen) * 0.1).to(dev)
+    x = y + (torch.randn(args.batch, args.samples, generator=gen) * 0.02).to(dev)
+    stft = metrics.default_stft()
+    basis = stft._tables(dev)[1]
+    passes = [(r, None, 0) for r in metrics.MR_STFT_RESOLUTIONS] + \
+             [((stft.filter_length, stft.hop_length, stft.win_length), basis, 13)]
+
+    def timed(fn):
+        fn()
+        torch.cuda.synchronize()
+        ms = []
+        for _ in range(args.repeats):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            out = fn()
+            e1.record()
+            torch.cuda.synchronize()
+            ms.append(e0.elapsed_time(e1))
+        return statistics.median(ms), min(ms), out
+
+    total_k = total_t = 0.0
+    for (n_fft, hop, win), b, n_cep in passes:
+        cep = metrics._cep(dev, n_cep, b.shape[0]) if n_cep else None
+        k_ms, k_min, k_out = timed(lambda: metrics._run(x, y, None, n_fft, hop, win, b, cep))
+        t_ms, t_min, t_out = timed(lambda: ref.sums(x, y, n_fft, hop, win, basis=b, n_cep=n_cep, dtype=torch.float32))
+        cols = 6 if n_cep else 4
+        rel = float(((k_out[:, :cols] - t_out[:, :cols].double()).abs() / t_out[:, :cols].double().abs()).max())
+        total_k, total_t = total_k + k_ms, total_t + t_ms
+        print(json.dumps(dict(n_fft=n_fft, hop=hop, win=win, mel=b is not None, B=args.batch, T=args.samples,
+                              kernel_ms_median=round(k_ms, 3), kernel_ms_min=round(k_min, 3),
+                              torch_stft_f32_ms_median=round(t_ms, 3), torch_stft_f32_ms_min=round(t_min, 3),
+                              max_rel_diff=rel)), flush=True)
+    print(json.dumps(dict(all_passes=True, kernel_ms=round(total_k, 3), torch_stft_f32_ms=round(total_t, 3),
+                          audio_seconds_at_22050=round(args.batch * args.samples / 22050.0, 2))), flush=True)
+
+
+if __name__ == "__main__":
+    main()
