@@ -18,7 +18,8 @@
 //     commit: 6 bytes per weight) stream from L2 one (k-block, product) step ahead, the B fragments from LDS one step
 //     ahead inside a chunk; 12 MFMAs per step;
 //     step embedding + conv bias enter as one extra k-block per product (A = the fp32 correction row of the f32
-//     Winograd path split in registers, B = the Winograd transform of the in-range indicator: exact in bf16);
+//     Winograd path split in registers, B = the Winograd transform of the in-range indicator: exact in bf16; the 16x16x32
+//     shape below: as the accumulators' fp32 start values instead);
 //   * gate in registers, split, -> LDS gate tile [k-octet][term][64 columns]; the EXTRA instance adds the mel term and, in
 //     training (precision = "bf16x6"), saves the pre-activations H [B, 2C, L] for the gate adjoint as wavenet_wino.hip does;
 //   * GEMM2 [res; skip] = [Wr; Ws] g with the biases as an extra k-block; the last layer leaves the res row tile out;
@@ -33,8 +34,12 @@
 // transpose slots keep their bytes, a fragment is the same 16-byte items under the lane map (row / column lane & 15, k-octet
 // lane >> 4 of a 32-channel block), the transform pass, the staging, the residual copy and every wait count are shared.  A 32 x 32
 // tile is four 16 x 16 slices (row half h, column half c) of four registers, row = 16 h + 4 (lane >> 4) + reg, col = 16 c + (lane & 15).
-// GEMM1 runs a chunk in eight half-steps (product, row tile) of 24 MFMAs, GEMM2 a 32-channel block in two.  The summation order per
-// output element is kept (correction block, chunks in rotated order, products in P::ia / ib order), but one instruction sums 32
+// GEMM1 runs a chunk in eight half-steps (product, row tile) of 24 MFMAs, GEMM2 a 32-channel block in two.  The correction k-blocks
+// are not MFMAs on this shape (K = 32 would spend 96 + 48 of them per tile on two non-zero k entries): every accumulator register
+// STARTS at the block's value as a rank-1 fp32 expression, one rounding -- GEMM1: correction row x indicator transform (+ conv bias in
+// product 1), formed under the first staging wait from 16-byte loads of four consecutive rows; GEMM2: the bias itself (bit-equal to
+// the block) (profiles/r09_ab_bx6_accumulator_start.txt, tests/test_bx6_accumulator_start_gpu.py).  The summation order per
+// output element is kept (start value, chunks in rotated order, products in P::ia / ib order), but one instruction sums 32
 // channels where two summed 16 + 16: results differ in the last bits (tests/test_bx6_mfma_shape_gpu.py), deterministically and
 // independently of the clip's place in the batch.  The shape costs cycles (+ 4.9 % tile span) and wins wall time (- 1.8 % of the step):
 // the chip is power-capped under this kernel and holds 1970 instead of 1838 MHz on it (profiles/r08_ab_bx6_mfma_shape.txt).
@@ -230,7 +235,7 @@ struct Bx6Nothing {};
 // state of the 16x16x32 GEMM2 (nothing at all in a 32x32x16 instance, so that those compile to the code they had)
 template <int MS>
 struct Bx6G2State {
-    float bias[1 + MS][2];              // the bias of row 16 h + r16 of each row tile
+    bx_f32x4 bias[1 + MS][2];           // the biases in accumulator layout: rows 16 h + 4 (lane >> 4) + (0..3) of each row tile
     bx_f32x4 acc[1 + MS][2][2][2];      // [row tile][column tile n][row half h][column half c]
 };
 // the six A fragments of a GEMM1 half-step (row tile, product): [row half h][term], soff = the byte offset of term 0 of the
@@ -247,10 +252,11 @@ __device__ __forceinline__ void bx6_load_a1h(V8 (&dst)[2][NT], __amdgpu_buffer_r
 // state of the 16x16x32 GEMM1
 template <typename V8, int NT>
 struct Bx6G1State {
-    float av[2][2][4], ab[2][2];        // correction rows of row 16 h + r16 of the two row tiles: [m][h][product], conv bias [m][h]
+    // correction rows in accumulator layout, rows 16 h + 4 (lane >> 4) + (0..3) of the two row tiles: [m][h][product], conv bias
+    // [m][h].  Dead once the start values are formed (ahead of the first chunk barrier).
+    bx_f32x4 av[2][2][4], ab[2][2];
     bx_f32x4 acc[2][4][2][2];           // [row tile m][product j][row half h][column half c]
     V8 ar[2][2][NT];                    // A fragments, ring over the half-steps: [half-step & 1][h][term]
-    int pc[2];                          // first-half position of the lane's column 16 c + r16
 };
 template <typename P, int C, int S, bool EXTRA, int MF = BX6_MF_32>
 __global__ __launch_bounds__(C * 2, (C >= 128 ? 2 : 1)) void wn_layer_bx6_kernel(WnLayerArgs a, int log2d) {
@@ -308,21 +314,19 @@ __global__ __launch_bounds__(C * 2, (C >= 128 ? 2 : 1)) void wn_layer_bx6_kernel
     for (int m = 0; m < MS; ++m) mt2[1 + m] = C / 32 + wave * MS + m;
     [[maybe_unused]] std::conditional_t<MF >= BX6_MF_16, Bx6G1State<v8, NT>, Bx6Nothing> gs1;
     if constexpr (MF >= BX6_MF_16) {
+        // 16x16x32: the correction rows are the accumulators' start values (below), so they are fetched in accumulator layout,
+        // four consecutive rows per 16-byte load.  Every row block starts a multiple of four floats into Abt / bias1, and the
+        // launcher checks that both bases and both Abt strides keep 16 bytes (per-clip rows and step-table rows alike).
         const float* Abt = a.Abt + (size_t)b * a.abt_bstride + step_row_off(a.step_idx, a.abt_tstride);
 #pragma unroll
         for (int m = 0; m < 2; ++m)
 #pragma unroll
             for (int h = 0; h < 2; ++h) {
-                const int row = (m ? C / 32 + wave : wave) * 32 + 16 * h + (lane & 15);
+                const int row = (m ? C / 32 + wave : wave) * 32 + 16 * h + 4 * (lane >> 4);
 #pragma unroll
-                for (int j = 0; j < 4; ++j) gs1.av[m][h][j] = Abt[j * 2 * C + row];
-                gs1.ab[m][h] = a.bias1[row];
+                for (int j = 0; j < 4; ++j) gs1.av[m][h][j] = *reinterpret_cast<const bx_f32x4*>(Abt + j * 2 * C + row);
+                gs1.ab[m][h] = *reinterpret_cast<const bx_f32x4*>(a.bias1 + row);
             }
-#pragma unroll
-        for (int c = 0; c < 2; ++c) {
-            const int qc = q0 + 16 * c + (lane & 15);
-            gs1.pc[c] = ((qc >> log2d) << (log2d + 1)) + (qc & (dil - 1));
-        }
     }
     float av1[2][4], ab1[2], av2[1 + MS];
     if constexpr (MF < BX6_MF_16) {
@@ -517,8 +521,19 @@ __global__ __launch_bounds__(C * 2, (C >= 128 ? 2 : 1)) void wn_layer_bx6_kernel
 #endif
     };
 
+    if constexpr (MF >= BX6_MF_16) {
+        // 16x16x32: the first half-step's six A fragments (product 0 of row tile 0 -- bx6_load_a1h) are requested AHEAD of the
+        // wave's LDS-DMA pieces, and the pieces as one sequence (by halves, more than one chunk: every wave stages exactly one of
+        // chunks 0 and 1).  The correction rows are then older than six L2-served fragments and the pieces, whatever the staging
+        // form: the wait in front of the start values (below) leaves those outstanding and does not wait for the staged x.
+        static_assert(T::HALVES && NCB > 1 && BX6_PF(NT) == 1 && KC == 32,
+                      "a wave stages chunk 0 or chunk 1; one half-step of six fragments ahead: NAF and the chunk loop's vmcnt counts as in the 32x32x16 form");
+        bx6_load_a1h<v8, NT>(gs1.ar[0], rA1, bx6_voff_a1h<NT>(lane), ((mt1[0] * NKB + 2 * chunk_of(0)) * 4 + 0) * NT * 1024);
+        stage_dma(shalf);
+    } else {
     if (stages(0)) stage_dma(0);
     if (NCB > 1 && stages(1)) stage_dma(1);
+    }
     // A fragments run PF (k-block, product) steps ahead of their use, in a ring of four register sets indexed by the
     // step number (compile time: the steps of a chunk are a multiple of four).  One step is 2 NPR MFMAs = 32 NPR matrix-pipe
     // cycles per wave: six products cover an L2 round trip with one step, three products need two.
@@ -526,11 +541,8 @@ __global__ __launch_bounds__(C * 2, (C >= 128 ? 2 : 1)) void wn_layer_bx6_kernel
     v8 a_ring[4][2][NT];
     // 16x16x32 fragments of (32-channel block kk, product j, row tile m): half h takes rows 16 h + r16 of k-blocks 2 kk + (oct >> 1),
     // k half oct & 1 -- the bytes of the two 32x32x16 fragments of those k-blocks; every 16-lane group reads 256 contiguous bytes
-    // (16x16x32: the first half-step's six fragments, product 0 of row tile 0 -- bx6_load_a1h)
-    if constexpr (MF >= BX6_MF_16) {
-        static_assert(MF < BX6_MF_16 || (PF == 1 && KC == 32), "one half-step of six fragments ahead: NAF and every vmcnt count as in the 32x32x16 form");
-        bx6_load_a1h<v8, NT>(gs1.ar[0], rA1, bx6_voff_a1h<NT>(lane), ((mt1[0] * NKB + 2 * chunk_of(0)) * 4 + 0) * NT * 1024);
-    } else {
+    // (16x16x32: requested above)
+    if constexpr (MF < BX6_MF_16) {
 #pragma unroll
     for (int s0 = 0; s0 < PF; ++s0) load_a1(a_ring[s0], chunk_of(0) * (KC / 16) + (s0 >> 2), s0 & 3);
     }
@@ -541,22 +553,18 @@ __global__ __launch_bounds__(C * 2, (C >= 128 ? 2 : 1)) void wn_layer_bx6_kernel
     // chunk 0 has only the A fragments behind it, the other half has no part in chunk 0 and nothing to wait for yet.
     constexpr int P16 = NPIECE + NAF, P4 = 4 * NPIECE + NAF;
     static_assert(P4 < 64, "vmcnt is a 6-bit counter");
-    if (HALVES) {
-        if (stages(0)) __builtin_amdgcn_s_waitcnt(0x0F70 | NAF);
-    } else if (NCB > 1) {
-        if (x4) __builtin_amdgcn_s_waitcnt(0x0F70 | (P16 & 15) | ((P16 >> 4) << 14));
-        else __builtin_amdgcn_s_waitcnt(0x0F70 | (P4 & 15) | ((P4 >> 4) << 14));
-    } else {
-        __builtin_amdgcn_s_waitcnt(0x0F70 | NAF);
-    }
-    __syncthreads();
-    stamp(1);
-    if constexpr (MF >= BX6_MF_16) {   // the same correction block, K = 32: non-zero in the lanes of octet 0; indicator values per column half
-        const bx_f32x4 zero = {0.f, 0.f, 0.f, 0.f};
+    if constexpr (MF >= BX6_MF_16) {
+        // Start values of the accumulators: what the correction k-block summed -- the step-embedding row times the Winograd
+        // transform of the in-range indicator of the four shifts (exact small integers, per column half), plus the conv bias in
+        // product 1 (m1 enters both outputs of a pair with +1) -- is a rank-1 fp32 expression per register, one rounding each.
+        // The rows were the kernel's first requests (vmcnt retires in order: the compiler's waits in front of these FMAs count
+        // the six A fragments behind them and leave the younger LDS-DMA pieces alone), so this runs under the first staging
+        // wait and not behind the chunk barrier.
         float bi[2][4];
 #pragma unroll
         for (int c = 0; c < 2; ++c) {
-            const int pc = gs1.pc[c];
+            const int qc = q0 + 16 * c + (lane & 15);
+            const int pc = ((qc >> log2d) << (log2d + 1)) + (qc & (dil - 1));   // first-half position of the lane's column 16 c + r16
             const float v0 = ((unsigned)(pc - dil) < (unsigned)L) ? 1.f : 0.f;
             const float v1 = ((unsigned)pc < (unsigned)L) ? 1.f : 0.f;
             const float v2 = ((unsigned)(pc + dil) < (unsigned)L) ? 1.f : 0.f;
@@ -568,18 +576,36 @@ __global__ __launch_bounds__(C * 2, (C >= 128 ? 2 : 1)) void wn_layer_bx6_kernel
 #pragma unroll
             for (int m = 0; m < 2; ++m)
 #pragma unroll
-                for (int h = 0; h < 2; ++h) {
-                    v8 af[NT];
-                    P::rank2_16(gs1.av[m][h][j] * ws1, j == 1 ? gs1.ab[m][h] * ws1 : 0.f, lane, af);
+                for (int h = 0; h < 2; ++h)
 #pragma unroll
-                    for (int c = 0; c < 2; ++c) {
-                        const v8 bf = P::bvals_16(bi[c][j] * P::SX, j == 1 ? P::SX : 0.f, lane);
-                        gs1.acc[m][j][h][c] = zero;
+                    for (int c = 0; c < 2; ++c)
 #pragma unroll
-                        for (int t = NT - 1; t >= 0; --t) gs1.acc[m][j][h][c] = P::mfma16(af[t], bf, gs1.acc[m][j][h][c]);
-                    }
-                }
-    } else {   // correction k-block: k = 0 the step-embedding row (x the Winograd transform of the in-range indicator of the four
+                        for (int r = 0; r < 4; ++r)
+                            gs1.acc[m][j][h][c][r] = j == 1 ? __builtin_fmaf(gs1.av[m][h][j][r], bi[c][j], gs1.ab[m][h][r])
+                                                            : gs1.av[m][h][j][r] * bi[c][j];
+        // (opaque to the optimiser, or it sinks the FMAs to their first use, behind the barrier and transform(0))
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+#pragma unroll
+            for (int m = 0; m < 2; ++m)
+#pragma unroll
+                for (int h = 0; h < 2; ++h)
+#pragma unroll
+                    for (int c = 0; c < 2; ++c) asm volatile("" : "+v"(gs1.acc[m][j][h][c]));
+    }
+    if constexpr (MF >= BX6_MF_16) {   // (the pieces are this wave's youngest requests here)
+        if (stages(0)) __builtin_amdgcn_s_waitcnt(0x0F70);
+    } else if (HALVES) {
+        if (stages(0)) __builtin_amdgcn_s_waitcnt(0x0F70 | NAF);
+    } else if (NCB > 1) {
+        if (x4) __builtin_amdgcn_s_waitcnt(0x0F70 | (P16 & 15) | ((P16 >> 4) << 14));
+        else __builtin_amdgcn_s_waitcnt(0x0F70 | (P4 & 15) | ((P4 >> 4) << 14));
+    } else {
+        __builtin_amdgcn_s_waitcnt(0x0F70 | NAF);
+    }
+    __syncthreads();
+    stamp(1);
+    if constexpr (MF < BX6_MF_16) {   // correction k-block: k = 0 the step-embedding row (x the Winograd transform of the in-range indicator of the four
         // shifts), k = 1 of product 1 the conv bias (m1 enters both outputs of a pair with +1)
         const float v0 = ((unsigned)(p - dil) < (unsigned)L) ? 1.f : 0.f;
         const float v1 = ((unsigned)p < (unsigned)L) ? 1.f : 0.f;
@@ -605,7 +631,9 @@ __global__ __launch_bounds__(C * 2, (C >= 128 ? 2 : 1)) void wn_layer_bx6_kernel
     }
     transform(0);
     keep_residual(0);
-    __builtin_amdgcn_s_waitcnt(0x0F70 | NAF);  // chunk 1 has landed too (younger: only the NAF A fragments; either half)
+    // chunk 1 has landed too (younger: only the NAF A fragments; either half.  16x16x32: nothing is younger than the pieces yet)
+    if constexpr (MF >= BX6_MF_16) __builtin_amdgcn_s_waitcnt(0x0F70);
+    else __builtin_amdgcn_s_waitcnt(0x0F70 | NAF);
     __syncthreads();                          // transformed chunk 0 visible, raw chunk 1 complete
 
     constexpr int SPC = (KC / 16) * 4;        // (k-block, product) steps per chunk
@@ -778,14 +806,15 @@ __global__ __launch_bounds__(C * 2, (C >= 128 ? 2 : 1)) void wn_layer_bx6_kernel
     int lane_t = lane;
     if constexpr (MF >= BX6_MF_16) asm volatile("" : "+v"(lane_t));
 
-    // 16x16x32 GEMM2: the bias of row 16 h + r16 of each row tile.  Asked for here and not with the other correction operands:
-    // GEMM1 has no register to carry it (256 of 256), and the gate stage covers the latency.
+    // 16x16x32 GEMM2: the biases in accumulator layout (one 16-byte load per row tile and half: rows 16 h + 4 oct + (0..3)), the
+    // accumulators' start values.  Asked for here and not with the other correction operands: GEMM1 has no register to carry
+    // them, and the gate stage covers the latency.
     [[maybe_unused]] std::conditional_t<MF >= BX6_MF_G2_16, Bx6G2State<MS>, Bx6Nothing> gs2;
     if constexpr (MF >= BX6_MF_G2_16) {
 #pragma unroll
         for (int m = 0; m < 1 + MS; ++m)
 #pragma unroll
-            for (int h = 0; h < 2; ++h) gs2.bias[m][h] = a.bias2[mt2[m] * 32 + 16 * h + (lane_t & 15)];
+            for (int h = 0; h < 2; ++h) gs2.bias[m][h] = *reinterpret_cast<const bx_f32x4*>(a.bias2 + mt2[m] * 32 + 16 * h + 4 * (lane_t >> 4));
     }
     // ---- x and running-skip tiles of this wave's output rows, requested before the gate stage (row-major 16-byte pieces:
     // lane = (row lane>>4 of a group of four rows, column quad lane&15; quads 0..7 = column tile 0, 8..15 = tile 1)
@@ -985,7 +1014,7 @@ __global__ __launch_bounds__(C * 2, (C >= 128 ? 2 : 1)) void wn_layer_bx6_kernel
         // map: the A fragment of (32-channel block kk, half h) takes rows 16 h + r16 of k-blocks 2 kk + (oct >> 1), k half
         // oct & 1 -- the two halves read exactly the bytes of the two 32x32x16 fragments of those k-blocks; B takes octet
         // 4 kk + oct of the gate tile, columns 32 n + 16 c + r16 (octet stride 3072 B = 0 mod 256: each group of ds_read_b128
-        // lanes covers all banks once).  Per output element: bias block, then the 32-channel blocks in the order rotated by
+        // lanes covers all banks once).  Per output element: the bias as start value, then the 32-channel blocks in the order rotated by
         // `rot`, then the products -- the 32x32x16 order, but one instruction sums 32 channels where two summed 16 + 16
         // (last-bit differences).  A block runs as two half-steps (h = 0, 1) of 8 NPR MFMAs; the (1 + MS) NT A fragments of a
         // half-step are requested one half-step ahead, the B fragments of a block serve both.
@@ -1007,25 +1036,16 @@ __global__ __launch_bounds__(C * 2, (C >= 128 ? 2 : 1)) void wn_layer_bx6_kernel
             static_assert(KC == 32, "GEMM2's rotation counts 32-channel blocks");
             v8 ah[2][1 + MS][NT];
             load_a2h(ah[0], block_of(0), 0);
-            {
-                const v8 bf = P::bvals_16(P::SG, 0.f, lane_t);     // a row of ones, at the gate operand's scale
-                const bx_f32x4 zero = {0.f, 0.f, 0.f, 0.f};
+            // start values: the bias of the register's row, the same for every column (bit for bit what the bias k-block left:
+            // the three terms of a split sum to the fp32 value exactly)
 #pragma unroll
-                for (int m = M0; m < 1 + MS; ++m)
+            for (int m = M0; m < 1 + MS; ++m)
 #pragma unroll
-                    for (int h = 0; h < 2; ++h) {
-                        v8 af[NT];
-                        P::rank2_16(gs2.bias[m][h] * ws2, 0.f, lane_t, af);
+                for (int n = 0; n < 2; ++n)
 #pragma unroll
-                        for (int n = 0; n < 2; ++n)
+                    for (int h = 0; h < 2; ++h)
 #pragma unroll
-                            for (int c = 0; c < 2; ++c) {
-                                acc2h[m][n][h][c] = zero;
-#pragma unroll
-                                for (int t = NT - 1; t >= 0; --t) acc2h[m][n][h][c] = P::mfma16(af[t], bf, acc2h[m][n][h][c]);
-                            }
-                    }
-            }
+                        for (int c = 0; c < 2; ++c) acc2h[m][n][h][c] = gs2.bias[m][h];
             __syncthreads();   // gate tile complete
             stamp(4);
             const char* gb = gt + oct * (NT * 64 * 16) + r16 * 16;
@@ -1235,6 +1255,13 @@ int launch_wn_layer_bx6(int C, int S, const WnLayerArgs& a, int split, int mfma,
         DWS_CHECK(a.hsave == nullptr, DWS_ERR_UNSUPPORTED, "wn_layer_f16x3: the training forward runs with precision=f32 or bf16x6");
         DWS_CHECK(a.wscale != nullptr, DWS_ERR_INVALID, "wn_layer_f16x3: no weight scales");
         return launch_bx6_p<SplitF16x2>(C, S, a, log2d, s);
+    }
+    // the 16x16x32 instances fetch the correction rows and the biases as 16-byte groups of four rows (accumulator layout)
+    if ((mfma == WN_BX6_MFMA_G2_16 || mfma == WN_BX6_MFMA_16) && wn_layer_bx6_mfma16_supported(C, S, split)) {
+        DWS_CHECK(((size_t)a.bias2 & 15) == 0, DWS_ERR_UNSUPPORTED, "wn_layer_bx6: bias2 is not 16-byte aligned");
+        if (mfma == WN_BX6_MFMA_16)
+            DWS_CHECK((((size_t)a.Abt | (size_t)a.bias1) & 15) == 0 && a.abt_bstride % 4 == 0 && a.abt_tstride % 4 == 0, DWS_ERR_UNSUPPORTED,
+                      "wn_layer_bx6: Abt / bias1 rows are not 16-byte aligned (strides %d, %d floats)", a.abt_bstride, a.abt_tstride);
     }
     // the 16x16x32 shape exists for the instances it was measured on; every other instance has one shape and keeps it
     if (mfma == WN_BX6_MFMA_G2_16 && wn_layer_bx6_mfma16_supported(C, S, split)) return launch_bx6_t<SplitBf16x3, 256, 256, BX6_MF_G2_16>(a, log2d, s);
