@@ -163,7 +163,165 @@ __global__ __launch_bounds__(64) void spectral_clip_sum_kernel(const double* __r
     out[(size_t)b * SPEC_Q + q] = s;
 }
 
+// Adjoint of the two Parallel WaveGAN terms (sums 0 .. 2) with respect to x, stage 1 of 2: one workgroup per (frame,
+// clip).  Re/Im of x and y are recomputed exactly as spectral_frame_kernel computes them (same interleaved frames, same
+// table, same fmaf order), so every floor decision is the forward's.  With c0, c1 = coef[b][0], coef[b][1]
+//   dmag_k = -(c0 (|Y|_k - |X|_k) + c1 sgn(ln|Y|_k - ln|X|_k) / |X|_k)     where p_x >= 1e-7, else 0   (sgn(0) = 0)
+//   dRe_k = dmag_k Re_k / |X|_k,   dIm_k = dmag_k Im_k / |X|_k
+//   ws[b,f,i] = w[i] sum_k (dRe_k cos(2 pi i k / N) + dIm_k sin(2 pi i k / N))      (k = 0 .. N/2 ascending)
+// Nothing is accumulated across workgroups: the overlap-add is spectral_gather_kernel's.
+//
+// LDS: the forward's 16 N bytes and 8 K bytes of (dRe, dIm).  The inverse stage mirrors the transform's access pattern
+// with the roles swapped: the (dRe, dIm) row is one address for the whole wave (a broadcast), the table is read at
+// (i k) & (N - 1) with a lane stride of k float2 -- conflict-free for odd k, 2^m-way where k = 2^m (odd) until the lanes
+// start to share addresses; the same cost profile as the forward's table reads at lane stride i, so the inverse runs at
+// the forward's LDS rate with half its FMAs per read pair.
+__global__ __launch_bounds__(256) void spectral_frame_backward_kernel(const float* __restrict__ x, const float* __restrict__ y,
+                                                                      const int* __restrict__ lengths,
+                                                                      const float* __restrict__ window,
+                                                                      const double* __restrict__ coef, float* __restrict__ ws,
+                                                                      int T, int n_fft, int hop, int f_max) {
+    extern __shared__ double lds64[];
+    const int f = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
+    const int half = n_fft / 2, nb = half + 1;
+    int len;
+    if (f >= spectral_clip_frames(lengths, b, T, half, hop, len)) return;      // the whole workgroup, before any barrier
+    float2* fr = reinterpret_cast<float2*>(lds64);         // [n_fft]  (x, y) windowed
+    float2* tab = fr + n_fft;                              // [n_fft]  (cos, sin)(2 pi j / n_fft)
+    float2* dri = tab + n_fft;                             // [nb]     (dRe, dIm)
+    const float* xa = x + (size_t)b * T;
+    const float* ya = y + (size_t)b * T;
+    for (int i = tid; i < n_fft; i += 256) {
+        int j = f * hop + i - half;
+        if (j < 0) j = -j;
+        if (j >= len) j = 2 * (len - 1) - j;
+        const float w = window[i];
+        fr[i] = make_float2(xa[j] * w, ya[j] * w);
+        float s, c;
+        sincospif(2.f * (float)i / (float)n_fft, &s, &c);
+        tab[i] = make_float2(c, s);
+    }
+    __syncthreads();
+    const int mask = n_fft - 1;
+    const float c0 = (float)coef[(size_t)b * 2], c1 = (float)coef[(size_t)b * 2 + 1];
+    for (int k = tid; k < nb; k += 256) {
+        float xr = 0.f, xi = 0.f, yr = 0.f, yi = 0.f;
+        int ph = 0;
+        for (int i = 0; i < n_fft; ++i) {
+            const float2 v = fr[i];
+            const float2 t = tab[ph];
+            xr = fmaf(v.x, t.x, xr);
+            xi = fmaf(v.x, t.y, xi);
+            yr = fmaf(v.y, t.x, yr);
+            yi = fmaf(v.y, t.y, yi);
+            ph = (ph + k) & mask;
+        }
+        const float px = xr * xr + xi * xi, py = yr * yr + yi * yi;
+        float2 d = make_float2(0.f, 0.f);
+        if (px >= SPEC_FLOOR) {          // the floor passes no gradient below it (the tie counts as passed: clamp_min's rule)
+            const float qy = py < SPEC_FLOOR ? SPEC_FLOOR : py;
+            const float mx = sqrtf(px), my = sqrtf(qy);
+            const float l = 0.5f * (logf(qy) - logf(px));
+            const float sg = l > 0.f ? 1.f : (l < 0.f ? -1.f : 0.f);
+            const float t = -(c0 * (my - mx) + c1 * sg / mx) / mx;
+            d = make_float2(t * xr, t * xi);
+        }
+        dri[k] = d;
+    }
+    __syncthreads();
+    float* o = ws + ((size_t)b * f_max + f) * n_fft;
+    for (int i = tid; i < n_fft; i += 256) {
+        float acc = 0.f;
+        int ph = 0;
+        for (int k = 0; k < nb; ++k) {
+            const float2 d = dri[k];
+            const float2 t = tab[ph];
+            acc = fmaf(d.x, t.x, acc);
+            acc = fmaf(d.y, t.y, acc);
+            ph = (ph + i) & mask;
+        }
+        o[i] = window[i] * acc;
+    }
+}
+
+// Every frame of the clip that covers padded position p, in ascending order, added to acc.
+__device__ __forceinline__ float spectral_gather_position(const float* __restrict__ wsb, int p, int n_fft, int hop, int nf, float acc) {
+    int lo = p - n_fft + 1;
+    lo = lo <= 0 ? 0 : (lo + hop - 1) / hop;
+    int hi = p / hop;
+    if (hi > nf - 1) hi = nf - 1;
+    for (int f = lo; f <= hi; ++f) acc += wsb[(size_t)f * n_fft + (p - f * hop)];
+    return acc;
+}
+
+// Adjoint, stage 2 of 2: one thread per sample.  Sample j < len_b sits at padded position j + N/2 and, through the
+// reflection about the clip's OWN ends, at N/2 - j (j = 1 .. N/2) and at N/2 + 2 (len_b - 1) - j
+// (j = len_b - 1 - N/2 .. len_b - 2) -- at len_b <= N/2 + 1 at both at once.  Summed in a fixed order: the direct
+// position, the left reflection, the right reflection, each in ascending frame order; a sample no frame covers
+// (hop > N) gets exactly 0.  Behind len_b: exactly 0 without `accumulate`, untouched with it.
+__global__ __launch_bounds__(256) void spectral_gather_kernel(const float* __restrict__ ws, const int* __restrict__ lengths,
+                                                              float* __restrict__ dx, int T, int n_fft, int hop, int f_max,
+                                                              int accumulate) {
+    const int j = blockIdx.x * 256 + threadIdx.x, b = blockIdx.y;
+    if (j >= T) return;
+    const int half = n_fft / 2;
+    int len;
+    const int nf = spectral_clip_frames(lengths, b, T, half, hop, len);
+    float* o = dx + (size_t)b * T + j;
+    if (nf == 0 || j >= len) {
+        if (!accumulate) *o = 0.f;
+        return;
+    }
+    const float* wsb = ws + (size_t)b * f_max * n_fft;
+    float acc = spectral_gather_position(wsb, j + half, n_fft, hop, nf, 0.f);
+    if (j >= 1 && j <= half) acc = spectral_gather_position(wsb, half - j, n_fft, hop, nf, acc);
+    if (j <= len - 2 && j >= len - 1 - half) acc = spectral_gather_position(wsb, half + 2 * (len - 1) - j, n_fft, hop, nf, acc);
+    *o = accumulate ? *o + acc : acc;
+}
+
 }  // namespace dws
+
+extern "C" int64_t dws_spectral_loss_backward_workspace(int64_t B, int64_t T, int32_t n_fft, int32_t hop) {
+    if (B < 1 || T < 1 || hop < 1 || T > INT32_MAX || B > 65535 || n_fft < 64 || n_fft > 2048 || (n_fft & (n_fft - 1)))
+        return 0;
+    return B * (T / hop + 1) * (int64_t)n_fft * (int64_t)sizeof(float);
+}
+
+extern "C" int dws_spectral_loss_backward(const float* x, const float* y, int64_t B, int64_t T, const int32_t* lengths,
+                                          const int32_t* lengths_host, const float* window, int32_t n_fft, int32_t hop,
+                                          const double* coef, float* dx, int32_t accumulate, float* workspace, void* stream) {
+    using namespace dws;
+    DWS_CHECK(x && y && window && coef && dx, DWS_ERR_INVALID, "dws_spectral_loss_backward: null argument");
+    DWS_CHECK(workspace, DWS_ERR_INVALID,
+              "dws_spectral_loss_backward: null workspace (dws_spectral_loss_backward_workspace bytes)");
+    DWS_CHECK(n_fft >= 64 && n_fft <= 2048 && (n_fft & (n_fft - 1)) == 0, DWS_ERR_INVALID,
+              "dws_spectral_loss_backward: n_fft = %d (powers of two 64..2048)", n_fft);
+    DWS_CHECK(B > 0 && B <= 65535 && hop > 0 && T > 0 && T <= INT32_MAX - n_fft, DWS_ERR_INVALID,
+              "dws_spectral_loss_backward: bad shape (B = %lld, T = %lld, hop = %d)", (long long)B, (long long)T, hop);
+    DWS_CHECK((lengths == nullptr) == (lengths_host == nullptr), DWS_ERR_INVALID,
+              "dws_spectral_loss_backward: lengths (device) and lengths_host (the same numbers on the host) come together");
+    if (lengths_host) {
+        for (int64_t b = 0; b < B; ++b)
+            DWS_CHECK(lengths_host[b] > n_fft / 2 && lengths_host[b] <= T, DWS_ERR_INVALID,
+                      "dws_spectral_loss_backward: clip %lld has %d samples (n_fft = %d needs %d .. T = %lld)", (long long)b,
+                      lengths_host[b], n_fft, n_fft / 2 + 1, (long long)T);
+    } else {
+        DWS_CHECK(T > n_fft / 2, DWS_ERR_INVALID,
+                  "dws_spectral_loss_backward: T = %lld (n_fft = %d needs at least %d samples)", (long long)T, n_fft,
+                  n_fft / 2 + 1);
+    }
+    const int f_max = (int)(T / hop) + 1;
+    const size_t lds = (size_t)n_fft * 16 + (size_t)(n_fft / 2 + 1) * 8;
+    DWS_HIP(hipFuncSetAttribute((const void*)spectral_frame_backward_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                (int)lds));
+    hipLaunchKernelGGL(spectral_frame_backward_kernel, dim3((unsigned)f_max, (unsigned)B), dim3(256), lds, (hipStream_t)stream,
+                       x, y, lengths, window, coef, workspace, (int)T, n_fft, hop, f_max);
+    DWS_HIP(hipGetLastError());
+    hipLaunchKernelGGL(spectral_gather_kernel, dim3((unsigned)((T + 255) / 256), (unsigned)B), dim3(256), 0,
+                       (hipStream_t)stream, workspace, lengths, dx, (int)T, n_fft, hop, f_max, accumulate);
+    DWS_HIP(hipGetLastError());
+    return DWS_OK;
+}
 
 extern "C" int64_t dws_spectral_distance_workspace(int64_t B, int64_t T, int32_t hop) {
     if (B < 1 || T < 1 || hop < 1 || T > INT32_MAX || B > 65535) return 0;

@@ -11,6 +11,9 @@
 
 The transform and every sum run in ``dws_spectral_distance`` (``csrc/spectral_kernels.hip``), one fused launch per
 resolution; this module builds the constant tables, checks the arguments and divides the sums.  There is no CPU path.
+
+``mr_stft_loss(x, y)`` is ``mr_stft`` as a training loss: float32 [B] on the device, differentiable in ``x`` through
+``dws_spectral_loss_backward`` (the hand-written adjoint of the two terms; DESIGN.md section 4, "Spectral loss").
 """
 import ctypes
 import math
@@ -112,8 +115,9 @@ def _cep(device, n_cep, n_mels):
     return _ceps[key]
 
 
-def _run(x, y, host, n_fft, hop, win, basis, cep):
-    """One ``dws_spectral_distance`` call on checked arguments: float64 [B, 6] on the device."""
+def _run(x, y, host, n_fft, hop, win, basis, cep, dev_len=None):
+    """One ``dws_spectral_distance`` call on checked arguments: float64 [B, 6] on the device.  ``dev_len``: ``host`` as an
+    int32 device tensor where the caller already holds one."""
     lib = _lib.load()
     B, T = x.shape
     dev = x.device
@@ -123,7 +127,7 @@ def _run(x, y, host, n_fft, hop, win, basis, cep):
         dev_len = host_len = None
     else:
         host_len = (ctypes.c_int32 * B)(*host)
-        dev_len = torch.tensor(host, dtype=torch.int32).to(dev)
+        dev_len = torch.tensor(host, dtype=torch.int32).to(dev) if dev_len is None else dev_len
     n_mels = 0 if basis is None else int(basis.shape[0])
     n_cep = 0 if cep is None else int(cep.shape[0])
     with torch.cuda.device(dev):
@@ -212,3 +216,132 @@ def spectral_metrics(x, y, lengths=None, *, stft=None, resolutions=MR_STFT_RESOL
 
 
 METRICS = ("mr_stft", "ls_mae", "lsd", "mcd")       # the four headline numbers, in the order they are printed
+
+
+def check_resolutions(resolutions, lengths, what="spectral_metrics"):
+    """``resolutions`` as a list of checked (n_fft, hop, win) triples (``check_resolution`` on clips of these host
+    ``lengths``), or ValueError."""
+    try:
+        resolutions = [tuple(r) for r in resolutions]
+    except TypeError:
+        raise ValueError(f"{what}: resolutions = {resolutions!r}: expected (n_fft, hop, win) triples")
+    if not resolutions or any(len(r) != 3 for r in resolutions):
+        raise ValueError(f"{what}: resolutions = {resolutions!r}: expected (n_fft, hop, win) triples")
+    for r in resolutions:
+        check_resolution(*r, lengths)
+    return resolutions
+
+
+def check_loss_weights(sc_weight, mag_weight, what="mr_stft_loss"):
+    """(sc_weight, mag_weight) as floats: both finite and >= 0, not both 0; or ValueError."""
+    out = []
+    for name, v in (("sc_weight", sc_weight), ("mag_weight", mag_weight)):
+        if isinstance(v, (bool, str)) or not isinstance(v, (int, float, np.integer, np.floating)) or \
+                not math.isfinite(float(v)) or float(v) < 0.0:
+            raise ValueError(f"{what}: {name} = {v!r} (needs a finite number >= 0)")
+        out.append(float(v))
+    if out[0] == 0.0 and out[1] == 0.0:
+        raise ValueError(f"{what}: sc_weight and mag_weight are both 0: there is nothing to compute")
+    return out[0], out[1]
+
+
+def _loss_value(x, y, host, dev_len, frames, resolutions, sc_weight, mag_weight):
+    """The loss per clip (float32 [B], device) and the float64 sums [R][B, 6] behind it.  Divided on the device in double,
+    in ``spectral_metrics``' order: nothing goes to the host."""
+    sums, total = [], 0.0
+    for r, fr in zip(resolutions, frames):
+        s = _run(x, y, host, *r, None, None, dev_len=dev_len)
+        sums.append(s)
+        sc = torch.sqrt(s[:, 0] / s[:, 1])
+        mag = s[:, 2] / (fr * (r[0] // 2 + 1))
+        total = total + sc_weight * sc + mag_weight * mag
+    return (total / len(resolutions)).to(torch.float32), sums
+
+
+class _MrStftBackward(torch.autograd.Function):
+    """``dws_spectral_loss_backward`` over the resolutions as a node of its own, so that differentiating it (a
+    second-order request) is an error with a name instead of a silent zero."""
+
+    @staticmethod
+    def forward(ctx, g, x, y, dev_len, sums, cfg):
+        host, frames, resolutions, sc_weight, mag_weight = cfg
+        lib = _lib.load()
+        B, T = x.shape
+        dev = x.device
+        host_len = None if host is None else (ctypes.c_int32 * B)(*host)
+        g = g.to(torch.float64) / len(resolutions)
+        dx = torch.empty_like(x)
+        sums = sums.unbind(0)
+        with torch.cuda.device(dev):
+            for n, (r, fr, s) in enumerate(zip(resolutions, frames, sums)):
+                n_fft, hop, win = r
+                # sc = sqrt(num / den): d sc / d|X| = -(|Y| - |X|) / sqrt(num den); an exact match (num == 0) gets 0, not
+                # the NaN of 0 / 0 -- as the mel adjoint does for a zero magnitude
+                root = torch.sqrt(s[:, 0] * s[:, 1])
+                c_sc = torch.where(s[:, 0] == 0, torch.zeros_like(root), g * sc_weight / root)
+                c_mag = g * mag_weight / (fr * (n_fft // 2 + 1))
+                coef = torch.stack((c_sc, c_mag), dim=1).contiguous()
+                ws = torch.empty(lib.dws_spectral_loss_backward_workspace(B, T, n_fft, hop) // 4, device=dev,
+                                 dtype=torch.float32)                                  # the engine allocates nothing
+                _lib.check(lib.dws_spectral_loss_backward(x.data_ptr(), y.data_ptr(), B, T, _lib.ptr(dev_len), host_len,
+                                                          _window(dev, n_fft, win).data_ptr(), n_fft, hop, coef.data_ptr(),
+                                                          dx.data_ptr(), int(n > 0), ws.data_ptr(), _lib.current_stream()))
+        return dx
+
+    @staticmethod
+    def backward(ctx, *_):
+        raise RuntimeError("mr_stft_loss: the second derivative is not built (dws_spectral_loss_backward is a first-order "
+                           "adjoint; there is no double backward)")
+
+
+class _MrStftLoss(torch.autograd.Function):
+    """The loss of ``x`` [B, T] (cuda, float32, contiguous) against ``y``: ``dws_spectral_distance`` per resolution
+    forwards, ``dws_spectral_loss_backward`` backwards (the first resolution overwrites, the others accumulate)."""
+
+    @staticmethod
+    def forward(ctx, x, y, dev_len, cfg):
+        host, frames, resolutions, sc_weight, mag_weight = cfg
+        value, sums = _loss_value(x, y, host, dev_len, frames, resolutions, sc_weight, mag_weight)
+        ctx.save_for_backward(x, y, dev_len, torch.stack(sums))
+        ctx.cfg = cfg
+        return value
+
+    @staticmethod
+    def backward(ctx, g):
+        x, y, dev_len, sums = ctx.saved_tensors
+        return _MrStftBackward.apply(g, x, y, dev_len, sums, ctx.cfg), None, None, None
+
+
+def mr_stft_loss(x, y, lengths=None, *, resolutions=MR_STFT_RESOLUTIONS, sc_weight=1.0, mag_weight=1.0):
+    """Parallel WaveGAN's multi-resolution STFT loss of generated ``x`` against reference ``y`` ([B, T] or [B, 1, T],
+    cuda), per clip: the mean over ``resolutions`` of ``sc_weight * sc + mag_weight * mag`` with ``sc`` / ``mag`` as in
+    ``spectral_metrics`` (whose ``mr_stft`` this is at weights 1).  float32 [B] on x's device, differentiable in ``x``:
+    the adjoint is ``dws_spectral_loss_backward`` (include/dws.h), first order only.  ``lengths`` as in
+    ``spectral_metrics``: the gradient behind a clip's length is exactly 0, and nothing there is read.
+
+    Zero-gradient conventions (torch autograd gives NaN in the first case): a clip whose spectral-convergence numerator
+    is exactly 0 (``x`` equal to ``y``) gets no gradient from that term; a bin of X below the magnitude floor passes none.
+
+    ``y.requires_grad`` is a ValueError (the gradient with respect to the reference is not built), as are weights that are
+    negative, not finite or both 0.  Arguments are checked first (ValueError), then the device (RuntimeError).  Where
+    ``x`` does not require grad this is the plain forward."""
+    x, y, host, lens = _pair(x, y, lengths)
+    resolutions = check_resolutions(resolutions, lens, "mr_stft_loss")
+    sc_weight, mag_weight = check_loss_weights(sc_weight, mag_weight)
+    if y.requires_grad:
+        raise ValueError("mr_stft_loss: y requires grad, and the gradient with respect to the reference is not built "
+                         "(pass y.detach())")
+    _need_gpu(x, y)
+    y = y.detach().to(torch.float32).contiguous()
+    dev = x.device
+    if host is None:
+        dev_len = None
+        frames = [float(lens[0] // r[1] + 1) for r in resolutions]
+    else:
+        dev_len = torch.tensor(host, dtype=torch.int32).to(dev)
+        frames = [torch.tensor([n // r[1] + 1 for n in lens], dtype=torch.float64).to(dev) for r in resolutions]
+    cfg = (host, frames, resolutions, sc_weight, mag_weight)
+    if x.requires_grad and torch.is_grad_enabled():
+        return _MrStftLoss.apply(x.to(torch.float32).contiguous(), y, dev_len, cfg)
+    return _loss_value(x.detach().to(torch.float32).contiguous(), y, host, dev_len, frames, resolutions, sc_weight,
+                       mag_weight)[0]

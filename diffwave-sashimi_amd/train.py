@@ -214,7 +214,8 @@ class PriorMismatch(ValueError):
 def train(rank, num_gpus, diffusion_cfg, model_cfg, dataset_cfg, generate_cfg, ckpt_iter, n_iters, iters_per_ckpt,
           iters_per_logging, learning_rate, batch_size_per_gpu, name=None, exp_root="exp", num_workers=4, precision=None,
           honour_optim_hints=False, label_dropout=None, optimizer=None, ema_decay=None, clip_grad_norm=None, prior=None,
-          prior_energy_max=None, prior_energy_min=None, prior_std_min=None):
+          prior_energy_max=None, prior_energy_min=None, prior_std_min=None, stft_weight=None, stft_max_step=None,
+          stft_resolutions=None):
     """``train.py:49-196``.  With ``model.n_classes`` (class-conditional; not in the reference) every batch's class
     indices go to the network and ``label_dropout`` (``train.label_dropout``, default 0.1) of them are replaced by the
     null class, which is what classifier-free guidance needs at sampling time; the in-loop ``generate`` cycles the
@@ -231,8 +232,19 @@ def train(rank, num_gpus, diffusion_cfg, model_cfg, dataset_cfg, generate_cfg, c
     Sigma^-1-weighted loss (``training_loss(prior_std=)``); the checkpoints get a ``prior`` entry with the four values,
     which ``generate`` -- the in-loop one too -- picks up.  A resume must name the prior the checkpoint was trained with
     (none for a checkpoint without an entry): anything else raises ``PriorMismatch`` (a ValueError).  What such a model
-    sounds like has not been measured."""
+    sounds like has not been measured.
+
+    ``stft_weight`` (``+train.stft_weight=W [+train.stft_max_step=K] [+train.stft_resolutions=[[n_fft,hop,win],...]]``;
+    not in the reference; one audio channel): adds W times Parallel WaveGAN's multi-resolution STFT loss of the denoised
+    estimate x0_hat against the clean audio, on the clips whose step is below K (``training_loss(stft_weight=)``).
+    ``train/eps_loss`` and ``train/stft_loss`` join ``train/loss`` in the log; the checkpoints get a ``stft_loss`` entry
+    with the three values, which a resume prints (it is information, not a condition: a run may change or drop the
+    term).  The term is local to a rank.  What it does for audio quality has not been measured."""
     opt_kind, ema_decay, clip_grad_norm = optimizer_options(optimizer, ema_decay, clip_grad_norm)
+    from .training import stft_loss_options
+    stft_cfg = stft_loss_options(stft_weight, stft_max_step, stft_resolutions, diffusion_cfg.get("T"), where="train")
+    if stft_cfg is not None and model_cfg.get("in_channels", 1) != 1:
+        raise ValueError(f"train.stft_weight needs model.in_channels = 1 (got {model_cfg.get('in_channels')!r})")
     prior_cfg = prior_settings(prior, prior_energy_max, prior_energy_min, prior_std_min, model_cfg.get("unconditional"),
                                where="train")
     prior_cfg = prior_cfg if isinstance(prior_cfg, dict) else None
@@ -283,6 +295,9 @@ def train(rank, num_gpus, diffusion_cfg, model_cfg, dataset_cfg, generate_cfg, c
                                     f"asks for {prior_cfg!r}: resume with the same train.prior keys (weights trained "
                                     "towards one prior are not a start for another)")
             net.load_state_dict(checkpoint["model_state_dict"])
+            if "stft_loss" in checkpoint or stft_cfg is not None:
+                print(f"checkpoint {ckpt_iter} was trained with stft_loss = {checkpoint.get('stft_loss')!r}, this run "
+                      f"trains with {stft_cfg!r}")
             if "optimizer_state_dict" in checkpoint:
                 optimizer.load_state_dict(checkpoint["optimizer_state_dict"])
                 for g, own in zip(optimizer.param_groups, own_lr):    # `train.py:111-112` (one group there); a hinted lr stays
@@ -332,7 +347,17 @@ def train(rank, num_gpus, diffusion_cfg, model_cfg, dataset_cfg, generate_cfg, c
                 audio = (data.cuda() / MAX_WAV_VALUE).unsqueeze(1)
                 mel = stft.mel_spectrogram(audio[:, 0])
             optimizer.zero_grad()
-            if prior_cfg is not None:
+            if stft_cfg is not None:
+                parts = {}
+                more = dict(labels=data[2], label_dropout=label_dropout) if n_classes else {}
+                if prior_cfg is not None:
+                    from .mel import prior_std_from_mel
+                    more["prior_std"] = prior_std_from_mel(mel, prior_h, audio.shape[-1],
+                                                           **{k: prior_cfg[k] for k in PRIOR_KEYS})
+                loss = training_loss(net, loss_fn, audio, dh, mel_spec=mel, stft_weight=stft_cfg["weight"],
+                                     stft_max_step=stft_cfg["max_step"], stft_resolutions=stft_cfg["resolutions"],
+                                     parts=parts, **more)
+            elif prior_cfg is not None:
                 from .mel import prior_std_from_mel
                 sigma = prior_std_from_mel(mel, prior_h, audio.shape[-1],
                                            **{k: prior_cfg[k] for k in PRIOR_KEYS})
@@ -351,6 +376,9 @@ def train(rank, num_gpus, diffusion_cfg, model_cfg, dataset_cfg, generate_cfg, c
                 record = {"train/loss": reduced_loss, "train/log_loss": float(np.log(reduced_loss))}
                 if clip_grad_norm is not None:      # (the norm lives on the device: read at logging iterations only)
                     record["train/grad_norm"] = float(optimizer.grad_norm)
+                if stft_cfg is not None:            # (rank 0's own terms: the spectral term is local to a rank)
+                    record["train/eps_loss"] = float(parts["eps"])
+                    record["train/stft_loss"] = float(parts["stft"])
                 log(record, n_iter)
             if n_iter % iters_per_ckpt == 0 and rank == 0:
                 saved = {"model_state_dict": net.state_dict(), "optimizer_state_dict": optimizer.state_dict()}
@@ -358,6 +386,8 @@ def train(rank, num_gpus, diffusion_cfg, model_cfg, dataset_cfg, generate_cfg, c
                     saved["ema_state_dict"] = optimizer.ema_state_dict(net)
                 if prior_cfg is not None:       # (generate samples from the prior the weights were trained with)
                     saved["prior"] = dict(prior_cfg)
+                if stft_cfg is not None:        # (informational: what the loss of these weights held)
+                    saved["stft_loss"] = dict(stft_cfg)
                 torch.save(saved, os.path.join(checkpoint_directory, f"{n_iter}.pkl"))
                 print(f"model at iteration {n_iter} is saved")
                 if generate_cfg and generate_cfg.get("n_samples", 0):

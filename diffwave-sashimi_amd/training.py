@@ -2,6 +2,8 @@
 any differentiable module of the reference surface; with the engine modules the call goes through
 ``models.engine._EngineTrainFn`` (``dws_model_forward_train`` / ``dws_model_backward``), which keeps the
 activations of exactly one forward per module -- pair every forward with its backward."""
+import math
+
 import torch
 
 
@@ -69,8 +71,32 @@ def _check_prior_std(prior_std, audio):
     return prior_std.detach().to(device=audio.device, dtype=torch.float32)
 
 
+def stft_loss_options(stft_weight=None, stft_max_step=None, stft_resolutions=None, T=None, where="training_loss"):
+    """The spectral-loss arguments, checked: ``stft_weight`` a finite number > 0, ``stft_max_step`` an integer >= 0 (at
+    most ``T`` where that is given; default: every step), ``stft_resolutions`` (n_fft, hop, win) triples the kernel
+    builds (default: Parallel WaveGAN's three).  Returns None without ``stft_weight`` (the other two then need it), else
+    a dict of the three values."""
+    from .metrics import MR_STFT_RESOLUTIONS, check_resolutions
+    if stft_weight is None:
+        if stft_max_step is not None or stft_resolutions is not None:
+            raise ValueError(f"{where}: stft_max_step / stft_resolutions need stft_weight")
+        return None
+    if isinstance(stft_weight, (bool, str)) or not isinstance(stft_weight, (int, float)) or \
+            not math.isfinite(float(stft_weight)) or not float(stft_weight) > 0.0:
+        raise ValueError(f"{where}: stft_weight = {stft_weight!r} (needs a finite number > 0)")
+    if stft_max_step is not None:
+        if isinstance(stft_max_step, bool) or not isinstance(stft_max_step, int) or stft_max_step < 0 or \
+                (T is not None and stft_max_step > T):
+            raise ValueError(f"{where}: stft_max_step = {stft_max_step!r} (needs an integer in 0 .. T"
+                             + (f" = {T})" if T is not None else ")"))
+    resolutions = MR_STFT_RESOLUTIONS if stft_resolutions is None else stft_resolutions
+    resolutions = check_resolutions(resolutions, (), where)      # (the clips' lengths: mr_stft_loss, or the caller)
+    return dict(weight=float(stft_weight), max_step=stft_max_step, resolutions=[list(r) for r in resolutions])
+
+
 def training_loss(net, loss_fn, audio, diffusion_hyperparams, mel_spec=None, generator=None, labels=None,
-                  label_dropout=0.0, prior_std=None):
+                  label_dropout=0.0, prior_std=None, stft_weight=None, stft_max_step=None, stft_resolutions=None,
+                  parts=None):
     """``train.py:198-222``: ``t ~ U{0..T-1}``, ``z ~ N(0, I)``, ``loss_fn(net((x_t, t), mel), z)``.
     Steps and noise are drawn on the CPU generator exactly like the reference (then moved, through pinned staging
     buffers so the host does not stall), so a seeded call consumes the RNG stream in the same order.
@@ -86,9 +112,33 @@ def training_loss(net, loss_fn, audio, diffusion_hyperparams, mel_spec=None, gen
     shows as an inf / NaN loss).  ``z`` is drawn exactly as without it;
     the forward process noises with ``eps = prior_std * z`` and the loss is the paper's Sigma^-1-weighted norm with mean
     reduction, ``mean(((eps_theta - eps) / prior_std)^2)``.  ``loss_fn`` is ignored then.  Without ``prior_std`` not one
-    operation changes."""
+    operation changes.
+
+    ``stft_weight`` = lambda > 0 (spectral loss on the denoised estimate, as InferGrad, WaveFit and FastDiff train with;
+    not in the reference; one channel only) adds Parallel WaveGAN's multi-resolution STFT loss of the estimate
+
+        x0_hat = (x_t - sqrt(1 - abar_t) eps_theta) / sqrt(abar_t)           (eps = prior_std * z under a prior)
+        aux    = (1 / B) sum_b [t_b < stft_max_step] mr_stft_loss(x0_hat, audio)_b
+        loss   = base + lambda * aux
+
+    against the clean audio (``metrics.mr_stft_loss``: ``dws_spectral_distance`` forwards, ``dws_spectral_loss_backward``
+    backwards; no gradient goes to ``audio`` through the reference side).  ``stft_max_step`` (default T: every step) keeps
+    the term to the low-noise steps, where the estimate resembles audio; the mask is a product on the device and the
+    divisor is B, not the number of clips that pass, so nothing waits for the GPU and the scale does not jump from batch
+    to batch.  ``stft_resolutions``: (n_fft, hop, win) triples, default ``metrics.MR_STFT_RESOLUTIONS``; a clip too short
+    for one is ``check_resolution``'s ValueError, raised before anything is drawn.  ``parts`` (a dict) receives the two
+    detached device scalars ``eps`` (the base loss) and ``stft`` (aux).  Without ``stft_weight`` not one operation or
+    RNG draw changes."""
     T, Alpha_bar = diffusion_hyperparams["T"], diffusion_hyperparams["Alpha_bar"]
     B, C, L = audio.shape
+    stft = stft_loss_options(stft_weight, stft_max_step, stft_resolutions, T)
+    if stft is not None:
+        from .metrics import check_resolutions
+        if C != 1:
+            raise ValueError(f"training_loss: stft_weight needs one audio channel (audio has {C})")
+        check_resolutions(stft["resolutions"], [L] * B, "training_loss")
+        if parts is not None and not isinstance(parts, dict):
+            raise ValueError("training_loss: parts must be a dict")
     if prior_std is not None:
         prior_std = _check_prior_std(prior_std, audio)
     diffusion_steps = _stage(torch.randint(T, size=(B, 1, 1), generator=generator), audio.device, "steps")
@@ -105,5 +155,18 @@ def training_loss(net, loss_fn, audio, diffusion_hyperparams, mel_spec=None, gen
     else:
         epsilon_theta = net((x_t, diffusion_steps.view(B, 1)), mel_spec=mel_spec)
     if prior_std is not None:
-        return (((epsilon_theta - z) / prior_std) ** 2).mean()
-    return loss_fn(epsilon_theta, z)
+        loss = (((epsilon_theta - z) / prior_std) ** 2).mean()
+    else:
+        loss = loss_fn(epsilon_theta, z)
+    if stft is None:
+        return loss
+    from .metrics import mr_stft_loss
+    ab = _alpha_bar(Alpha_bar, audio.device)[diffusion_steps]
+    x0_hat = (x_t - torch.sqrt(1 - ab) * epsilon_theta) / torch.sqrt(ab)
+    per_clip = mr_stft_loss(x0_hat, audio.detach(), resolutions=stft["resolutions"])
+    if stft["max_step"] is not None:
+        per_clip = per_clip * (diffusion_steps.view(B) < stft["max_step"]).to(per_clip.dtype)
+    aux = per_clip.sum() / B
+    if parts is not None:
+        parts["eps"], parts["stft"] = loss.detach(), aux.detach()
+    return loss + stft["weight"] * aux

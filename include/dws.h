@@ -677,6 +677,37 @@ int dws_spectral_distance(const float* x, const float* y, int64_t B, int64_t T, 
 /* Bytes of dws_spectral_distance's workspace; 0 for a shape it refuses. */
 int64_t dws_spectral_distance_workspace(int64_t B, int64_t T, int32_t hop);
 
+/* The adjoint of dws_spectral_distance's first three sums with respect to the generated signal x (not in the reference):
+ * what a multi-resolution STFT training loss (Parallel WaveGAN's spectral convergence + log-magnitude L1) needs at ONE
+ * resolution.  dws_spectral_distance is the forward.  With its notation (frame_f, rho_b, Re / Im with +sin, p = Re^2 +
+ * Im^2, |S| = sqrt(max(p, 1e-7)), l = ln|Y| - ln|X|), and for clip b the two numbers coef[b][0], coef[b][1] (DEVICE,
+ * DOUBLE [B][2]: the cotangents of out[b][0] and out[b][2] up to the factors the caller's loss puts on them -- for
+ * sc = sqrt(out0 / out1) and mag = out2 / (frames K): g_sc / sqrt(out0 out1) and g_mag / (frames K)):
+ *     dmag_k   = -(coef[b][0] (|Y|_k - |X|_k) + coef[b][1] sgn(l_k) / |X|_k)      where p_x >= 1e-7, else 0  (sgn(0) = 0)
+ *     dRe_k    = dmag_k Re_k / |X|_k,    dIm_k = dmag_k Im_k / |X|_k               (X's Re / Im)
+ *     dframe_f[i] = w[i] sum_k (dRe_k cos(2 pi i k / N) + dIm_k sin(2 pi i k / N)) (k = 0 .. N/2 ascending, each bin once)
+ *     dx[b][j] = sum over all (f, i) with rho_b(f hop + i - N/2) = j  of  dframe_f[i]          (j < len_b)
+ * Floor: a bin of X below the floor passes no gradient, the tie p_x == 1e-7 passes it (clamp_min's rule); Re, Im and the
+ * floor decisions are recomputed with the forward's own arithmetic.  A silent x (p_x = 0 everywhere) so has an exactly
+ * zero gradient, and so has x == y with coef[b][0] = 0 (the caller's convention where out[b][0] == 0; torch autograd
+ * through the square root gives NaN there).
+ * dx: DEVICE [B][T].  accumulate == 0: positions j < len_b are overwritten, positions j >= len_b are written as exactly 0;
+ * accumulate != 0: positions j < len_b are added to, the others are left untouched.
+ * Order of summation: a sample of a frame over k ascending (fp32 fmaf, cos term then sin term); the overlap-add is a
+ * gather in a fixed order (per sample: its direct position, its left reflection, its right reflection about len_b, each
+ * in ascending frame order) with no atomics.  The result is bitwise reproducible, and row b depends on clip b's own len_b
+ * samples and coef[b] alone: not on B, T, b or on anything stored behind len_b (never read; may be NaN).
+ * workspace: DEVICE, dws_spectral_loss_backward_workspace(B, T, n_fft, hop) bytes ([B][T/hop + 1][n_fft] floats) owned by
+ * the caller (overwritten; the library allocates nothing per call).  LDS per workgroup: 16 n_fft + 8 (n_fft/2 + 1) bytes.
+ * DWS_ERR_INVALID: as dws_spectral_distance (a null x, y, window, coef, dx or workspace; n_fft not a power of two in
+ * 64 .. 2048; hop < 1; B outside 1 .. 65535; a len_b outside n_fft/2 + 1 .. T; lengths without lengths_host). */
+int dws_spectral_loss_backward(const float* x, const float* y, int64_t B, int64_t T, const int32_t* lengths,
+                               const int32_t* lengths_host, const float* window, int32_t n_fft, int32_t hop,
+                               const double* coef, float* dx, int32_t accumulate, float* workspace, void* stream);
+
+/* Bytes of dws_spectral_loss_backward's workspace; 0 for a shape it refuses. */
+int64_t dws_spectral_loss_backward_workspace(int64_t B, int64_t T, int32_t n_fft, int32_t hop);
+
 /* The arithmetic of precision="bf16x6" alone (accuracy tests; not a tuned GEMM): C[M][N] = A[M][K] . B[K][N], row-major
  * fp32 device tensors, every operand split into three bf16 terms in registers, six bf16 MFMA products per term pair
  * accumulated in fp32 -- exactly what the bf16x6 layer kernels execute per k-block.  M, N multiples of 32, K of 16. */
