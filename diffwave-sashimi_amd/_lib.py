@@ -138,6 +138,13 @@ _SIGS = {
                                                   ctypes.c_void_p, c_f32p, ctypes.c_int32, c_f32p, ctypes.c_void_p]),
     "dws_spectral_loss_backward_workspace": (ctypes.c_int64, [ctypes.c_int64, ctypes.c_int64, ctypes.c_int32,
                                                               ctypes.c_int32]),
+    "dws_pitch_track": (ctypes.c_int, [c_f32p, ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p,
+                                       ctypes.POINTER(ctypes.c_int32)] + [ctypes.c_int32] * 4 +
+                        [ctypes.c_float, ctypes.c_double, c_f32p, ctypes.c_void_p]),
+    "dws_pitch_distance": (ctypes.c_int, [c_f32p, c_f32p, ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p,
+                                          ctypes.POINTER(ctypes.c_int32)] + [ctypes.c_int32] * 4 +
+                           [ctypes.c_float, ctypes.c_double, c_f32p, ctypes.c_void_p, ctypes.c_void_p]),
+    "dws_pitch_distance_workspace": (ctypes.c_int64, [ctypes.c_int64, ctypes.c_int64, ctypes.c_int32]),
     "dws_gemm_bf16x6": (ctypes.c_int, [c_f32p] * 3 + [ctypes.c_int64] * 3 + [ctypes.c_void_p]),
     "dws_gemm_f16x3": (ctypes.c_int, [c_f32p] * 3 + [ctypes.c_int64] * 3 + [ctypes.c_float] * 2 + [ctypes.c_void_p]),
     "dws_profile_enable": (ctypes.c_int, [ctypes.c_char_p]),

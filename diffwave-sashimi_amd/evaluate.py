@@ -12,6 +12,12 @@ deviation, 95 % interval of the mean, n -- and ``--json`` receives the per-file 
 The STFT keys (``--sampling-rate``, ``--filter-length``, ``--hop-length``, ``--win-length``, ``--mel-fmin``,
 ``--mel-fmax``) set the transform of ``ls_mae`` / ``lsd`` / ``mcd``; with ``--config-dir`` they are read from the
 composed config's ``dataset`` (``key=value`` overrides as for ``generate``), and a key spelled out wins.
+
+``--pitch`` adds the pitch family of ``metrics.pitch_metrics`` (YIN tracks of both files at ``--sampling-rate`` and
+``--hop-length``; ``--pitch-win``, ``--pitch-fmin``, ``--pitch-fmax``, ``--pitch-threshold``): six more rows, printed after
+the others.  ``f0_rmse`` / ``f0_cents`` / ``gpe`` of a pair with no frame voiced in both files, and ``vuv_f1`` of a pair
+without a voiced frame, are NaN: such a pair is left out of that metric's mean, and the ``n`` column counts the rest.  ``--json`` holds ``null``
+for such a value (strict JSON has no NaN) and the parameters under ``"pitch"``.
 """
 import argparse
 import json
@@ -88,10 +94,12 @@ def load_pairs(generated_dir, reference_dir, pairs, sampling_rate, hop_length):
     return out
 
 
-def evaluate_pairs(clips, stft, batch_size=16, device=None, resolutions=_metrics.MR_STFT_RESOLUTIONS, n_cep=13):
+def evaluate_pairs(clips, stft, batch_size=16, device=None, resolutions=_metrics.MR_STFT_RESOLUTIONS, n_cep=13, pitch=None):
     """``spectral_metrics`` of a list of ``(x, y)`` clips of different lengths: sorted longest first and cut into
     batches of ``batch_size`` (``generate.ragged_plan``), each batch at its longest length with ``lengths=``.  Returns a
-    list of dicts of floats in the order of ``clips``.  Without a GPU the metric call raises (there is no CPU path)."""
+    list of dicts of floats in the order of ``clips``.  Without a GPU the metric call raises (there is no CPU path).
+    ``pitch``: None, or the keyword arguments of ``metrics.pitch_metrics`` (a dict, possibly empty), whose
+    ``PITCH_METRICS`` are then added to every row (NaN where a clip has none)."""
     from .generate import ragged_plan
     if device is None:
         device = "cuda" if torch.cuda.is_available() else "cpu"
@@ -102,8 +110,11 @@ def evaluate_pairs(clips, stft, batch_size=16, device=None, resolutions=_metrics
         x, y = torch.zeros(len(batch), T), torch.zeros(len(batch), T)
         for b, k in enumerate(batch):
             x[b, :lens[k]], y[b, :lens[k]] = clips[k]
-        m = _metrics.spectral_metrics(x.to(device), y.to(device), [lens[k] for k in batch], stft=stft,
-                                      resolutions=resolutions, n_cep=n_cep)
+        x, y = x.to(device), y.to(device)
+        m = _metrics.spectral_metrics(x, y, [lens[k] for k in batch], stft=stft, resolutions=resolutions, n_cep=n_cep)
+        if pitch is not None:
+            pm = _metrics.pitch_metrics(x, y, [lens[k] for k in batch], **pitch)
+            m = dict(m, **{key: pm[key] for key in _metrics.PITCH_METRICS})
         for b, k in enumerate(batch):
             rows[k] = {key: float(v[b]) for key, v in m.items()}
     return rows
@@ -120,7 +131,33 @@ def summarise(rows):
     return out
 
 
-def main(argv=None):
+def summarise_finite(rows, keys):
+    """``summarise`` of ``keys`` over the rows whose value is finite (a NaN marks a clip on which the metric is
+    undefined): n counts those rows; the mean is NaN and the rest 0 where there is none."""
+    out = {}
+    for key in keys:
+        v = np.array([r[key] for r in rows], dtype=np.float64)
+        v = v[np.isfinite(v)]
+        sd = float(v.std(ddof=1)) if len(v) > 1 else 0.0
+        out[key] = (float(v.mean()), sd, 1.96 * sd / math.sqrt(len(v)), len(v)) if len(v) else (float("nan"), 0.0, 0.0, 0)
+    return out
+
+
+def pitch_arguments(args, keys):
+    """The ``metrics.pitch_metrics`` keywords of the parsed ``--pitch*`` flags at the STFT ``keys``' rate and hop, or
+    None without ``--pitch`` (a ``--pitch-*`` value without it is a ValueError)."""
+    given = {k: getattr(args, "pitch_" + k) for k in ("win", "fmin", "fmax", "threshold")}
+    if not args.pitch:
+        extra = [k for k, v in given.items() if v is not None]
+        if extra:
+            raise ValueError(f"evaluate: --pitch-{extra[0]} needs --pitch")
+        return None
+    pitch = dict(_metrics.PITCH_DEFAULTS, sampling_rate=keys["sampling_rate"], hop=keys["hop_length"])
+    pitch.update({k: v for k, v in given.items() if v is not None})
+    return pitch
+
+
+def build_parser():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--generated", required=True, help="directory of generated wavs")
     ap.add_argument("--reference", required=True, help="directory of the recordings")
@@ -130,8 +167,17 @@ def main(argv=None):
     ap.add_argument("--batch-size", type=int, default=16)
     ap.add_argument("--json", help="write the per-file values here")
     ap.add_argument("--strict", action="store_true", help="an unpaired file is an error")
+    ap.add_argument("--pitch", action="store_true", help="add the pitch metrics (metrics.pitch_metrics)")
+    ap.add_argument("--pitch-win", type=int, help="integration window of the pitch tracker in samples (default 1024)")
+    ap.add_argument("--pitch-fmin", type=float, help="lowest F0 searched, Hz (default 50)")
+    ap.add_argument("--pitch-fmax", type=float, help="highest F0 searched, Hz (default 550)")
+    ap.add_argument("--pitch-threshold", type=float, help="YIN threshold (default 0.15)")
     ap.add_argument("overrides", nargs="*", help="key=value overrides of --config-dir, e.g. experiment=ljspeech")
-    args = ap.parse_args(argv)
+    return ap
+
+
+def main(argv=None):
+    args = build_parser().parse_args(argv)
     if args.overrides and not args.config_dir:
         raise ValueError("evaluate: key=value overrides need --config-dir")
     keys = dict(STFT_DEFAULTS)
@@ -142,6 +188,9 @@ def main(argv=None):
     keys.update({k: getattr(args, k) for k in STFT_KEYS if getattr(args, k) is not None})
     if args.batch_size < 1:
         raise ValueError(f"evaluate: --batch-size {args.batch_size}: expected an integer >= 1")
+    pitch = pitch_arguments(args, keys)
+    if pitch is not None:       # the parameters are checked before a file is read (the clips: once they are loaded)
+        _metrics.check_pitch([], what="evaluate --pitch", **pitch)
 
     pairs, lone_gen, lone_ref = pair_files(args.generated, args.reference)
     for name, lone in (("generated", lone_gen), ("reference", lone_ref)):
@@ -155,8 +204,13 @@ def main(argv=None):
     from .mel import TacotronSTFT
     stft = TacotronSTFT(filter_length=keys["filter_length"], hop_length=keys["hop_length"], win_length=keys["win_length"],
                         sampling_rate=keys["sampling_rate"], mel_fmin=keys["mel_fmin"], mel_fmax=keys["mel_fmax"])
-    rows = evaluate_pairs(clips, stft, args.batch_size)
-    summary = summarise(rows)
+    if pitch is None:
+        rows = evaluate_pairs(clips, stft, args.batch_size)
+        summary = summarise(rows)
+    else:
+        rows = evaluate_pairs(clips, stft, args.batch_size, pitch=pitch)
+        summary = summarise([{k: v for k, v in row.items() if k not in _metrics.PITCH_METRICS} for row in rows])
+        summary.update(summarise_finite(rows, _metrics.PITCH_METRICS))
     print(f"{'metric':<20}{'mean':>12}{'std':>12}{'95% +-':>12}{'n':>6}")
     for key, (mean, sd, ci, n) in summary.items():
         print(f"{key:<20}{mean:>12.6f}{sd:>12.6f}{ci:>12.6f}{n:>6d}")
@@ -166,6 +220,13 @@ def main(argv=None):
                             for (g, r), c, row in zip(pairs, clips, rows)],
                   "summary": {k: dict(mean=m, std=s, ci95=c, n=n) for k, (m, s, c, n) in summary.items()},
                   "unpaired_generated": lone_gen, "unpaired_reference": lone_ref}
+        if pitch is not None:           # an undefined pitch value (NaN) is written as null: strict JSON has no NaN
+            record["pitch"] = pitch
+            for entry in record["files"]:
+                entry.update({k: None for k in _metrics.PITCH_METRICS if math.isnan(entry[k])})
+            for k in _metrics.PITCH_METRICS:
+                if math.isnan(record["summary"][k]["mean"]):
+                    record["summary"][k]["mean"] = None
         with open(args.json, "w") as f:
             json.dump(record, f, indent=1)
     return rows

@@ -383,21 +383,60 @@ def _load_clip(dataset_cfg, stem, audio_length, conditional):
     return t.unsqueeze(0)
 
 
-def _report_metrics(i, audio, stems, numbers, lens, dataset_cfg, rows):
-    """``generate.report_metrics``: the clips of batch ``i`` (``audio`` [B, 1, L] on the GPU, clip b its first
-    ``lens[b]`` samples, made from the mel of ``stems[b]``) against their source wavs, each pair trimmed to its shorter
-    member.  Prints the batch means and appends one dict per clip to ``rows`` where that is a list."""
-    from .mel import MAX_WAV_VALUE, TacotronSTFT, load_wav_to_torch
-    from .metrics import METRICS, spectral_metrics
-    keys = ("filter_length", "hop_length", "win_length", "sampling_rate", "mel_fmin", "mel_fmax")
-    stft = TacotronSTFT(**{k: dataset_cfg[k] for k in keys if k in dataset_cfg})
-    sources = {s: load_wav_to_torch(os.path.join(str(dataset_cfg["data_path"]), f"{s}.wav"))[0] / MAX_WAV_VALUE
-               for s in set(stems)}
+def _source_pairs(audio, stems, lens, dataset_cfg, sources):
+    """``(x, y, n)``: the clips ``audio`` [B, 1, L] (clip b its first ``lens[b]`` samples) and the source wavs of
+    ``stems`` as two [B, max(n)] batches, pair b trimmed to its shorter member ``n[b]``; y on the CPU.  ``sources``: the
+    run's dict of the wavs read so far (stem -> [len] in [-1, 1]): each is read once, whichever report asks first."""
+    from .mel import MAX_WAV_VALUE, load_wav_to_torch
+    for s in set(stems) - set(sources):
+        sources[s] = load_wav_to_torch(os.path.join(str(dataset_cfg["data_path"]), f"{s}.wav"))[0] / MAX_WAV_VALUE
     n = [min(int(lens[b]), int(sources[s].shape[0])) for b, s in enumerate(stems)]
     x = audio[:, 0, :max(n)].to(torch.float32)
     y = torch.zeros(len(stems), max(n), dtype=torch.float32)
     for b, s in enumerate(stems):
         y[b, :n[b]] = sources[s][:n[b]]
+    return x, y, n
+
+
+def _check_pitch_source(stem, samples, dataset_cfg):
+    """``generate.report_pitch``, before anything is sampled: ValueError where the pair of ``stem`` -- ``samples`` long,
+    the shorter of the clip to be generated and its source wav -- is one ``metrics.pitch_metrics`` refuses at
+    ``dataset``'s sampling rate and hop (734 samples at 22050 Hz; nothing is clamped)."""
+    from .metrics import check_pitch
+    check_pitch([int(samples)], sampling_rate=dataset_cfg.get("sampling_rate", 22050), hop=dataset_cfg.get("hop_length", 256),
+                what=f"generate.report_pitch ({stem}.wav)")
+
+
+def _report_pitch(i, audio, stems, numbers, lens, dataset_cfg, rows, shared, sources):
+    """``generate.report_pitch``: as ``_report_metrics`` with ``metrics.pitch_metrics`` at ``dataset``'s sampling rate and
+    hop.  Prints the nan-means over the batch's clips; the keys go into the dicts ``_report_metrics`` just appended to
+    ``rows`` where ``shared``, into new ones otherwise."""
+    from .metrics import PITCH_METRICS, nanmean, pitch_metrics
+    x, y, n = _source_pairs(audio, stems, lens, dataset_cfg, sources)
+    m = pitch_metrics(x, y.to(x.device), n, sampling_rate=dataset_cfg.get("sampling_rate", 22050),
+                      hop=dataset_cfg.get("hop_length", 256))
+    mean = {k: nanmean(m[k].tolist()) for k in PITCH_METRICS}
+    print(f"batch {i} pitch: f0_rmse = {mean['f0_rmse']:.4f} Hz  " +
+          "  ".join(f"{k} = {mean[k]:.4f}" for k in PITCH_METRICS[1:]) +
+          f"  (nan-means of {len(stems)} clips against their source wavs)")
+    if rows is not None:
+        for b, s in enumerate(stems):
+            values = {k: float(m[k][b]) for k in PITCH_METRICS}
+            if shared:
+                rows[len(rows) - len(stems) + b].update(values)
+            else:
+                rows.append(dict(values, name=s, clip=numbers[b]))
+
+
+def _report_metrics(i, audio, stems, numbers, lens, dataset_cfg, rows, sources):
+    """``generate.report_metrics``: the clips of batch ``i`` (``audio`` [B, 1, L] on the GPU, clip b its first
+    ``lens[b]`` samples, made from the mel of ``stems[b]``) against their source wavs, each pair trimmed to its shorter
+    member.  Prints the batch means and appends one dict per clip to ``rows`` where that is a list."""
+    from .mel import TacotronSTFT
+    from .metrics import METRICS, spectral_metrics
+    keys = ("filter_length", "hop_length", "win_length", "sampling_rate", "mel_fmin", "mel_fmax")
+    stft = TacotronSTFT(**{k: dataset_cfg[k] for k in keys if k in dataset_cfg})
+    x, y, n = _source_pairs(audio, stems, lens, dataset_cfg, sources)
     m = spectral_metrics(x, y.to(x.device), n, stft=stft)
     print(f"batch {i} metrics: " + "  ".join(f"{k} = {float(m[k].mean()):.4f}" for k in METRICS) +
           f"  (mcd in dB; means of {len(stems)} clips against their source wavs)")
@@ -414,7 +453,7 @@ def generate(rank, diffusion_cfg, model_cfg, dataset_cfg, ckpt_iter="max", n_sam
              guide_name=None, guide_op=None, guide_clip=None, guide_factor=None, guide_scale=None, label=None,
              cfg_scale=None, ema=None, clip_seeds=None, clips=None, num_ranks=None, report_mel=None, mel_errors=None,
              mel_names=None, prior=None, prior_energy_max=None, prior_energy_min=None, prior_std_min=None,
-             report_metrics=None, metric_rows=None):
+             report_metrics=None, metric_rows=None, report_pitch=None):
     """``generate.py:58-200``.  ``ckpt_iter`` may additionally be ``"init"``: seeded random weights
     (no checkpoint), for smoke runs without trained weights.  ``precision`` (not in the reference; CLI:
     ``+engine.precision=bf16x6|f16x3``): the engine's opt-in matrix arithmetic, see ``include/dws.h``.
@@ -455,7 +494,12 @@ def generate(rank, diffusion_cfg, model_cfg, dataset_cfg, ckpt_iter="max", n_sam
     wav through ``metrics.spectral_metrics`` (the pair trimmed to the recording's length; the log-mel terms at
     ``dataset``'s transform), prints per batch the means of ``mr_stft / ls_mae / lsd / mcd`` and appends one dict per clip
     (``name``, ``clip`` and every metric) to ``metric_rows`` where that is a list.  With ``mel_path`` tensors (there is no
-    source wav) and on unconditional runs it is a ValueError.
+    source wav) and on unconditional runs it is a ValueError.  ``report_pitch=true`` (the same runs, the same
+    ValueErrors; alone or with ``report_metrics``) does the same through ``metrics.pitch_metrics`` at ``dataset``'s
+    sampling rate and hop: it prints per batch the nan-means of ``f0_rmse / f0_cents / gpe / vuv_error / vuv_f1 /
+    periodicity_rmse`` over the clips (a clip with no frame voiced in both signals has no F0 numbers) and adds the six
+    keys to the clip's dict in ``metric_rows`` -- the dict of ``report_metrics`` where both are on.  A clip or source wav
+    shorter than the tracker admits (734 samples at 22050 Hz and hop 256) is a ValueError before anything is sampled.
 
     Class-conditional models (``model.n_classes = K``; not in the reference): ``label`` is a class index in 0..K (K = the
     null class), a list of them cycled over the samples, or ``all`` (= 0..K-1 in turn); the wav names get ``_c{label}``.
@@ -567,6 +611,17 @@ def generate(rank, diffusion_cfg, model_cfg, dataset_cfg, ckpt_iter="max", n_sam
             raise ValueError("generate.report_metrics does not combine with generate.mel_path (pre-computed mel tensors "
                              "have no source wav to compare with)")
 
+    if report_pitch is not None:        # (the preconditions of report_metrics)
+        if not isinstance(report_pitch, bool):
+            raise ValueError(f"generate.report_pitch={report_pitch!r}: expected true or false")
+        if report_pitch and (model_cfg.get("unconditional") or (mel_name is None and mel_names is None)):
+            raise ValueError("generate.report_pitch needs a mel-conditional run (generate.mel_name or generate.mel_names: "
+                             "the clips are compared with the wavs their mels were computed from)")
+        if report_pitch and mel_path is not None:
+            raise ValueError("generate.report_pitch does not combine with generate.mel_path (pre-computed mel tensors "
+                             "have no source wav to compare with)")
+
+    source_wavs = {}        # report_metrics / report_pitch: the source wavs read so far
     n_classes = check_n_classes(model_cfg.get("n_classes"))
     labels_of = None        # the class of every sample, cycled
     if label is not None:
@@ -716,6 +771,8 @@ def generate(rank, diffusion_cfg, model_cfg, dataset_cfg, ckpt_iter="max", n_sam
                 _mel = Mel2Samp(**{k: dataset_cfg[k] for k in keys if k in dataset_cfg})
                 audio, sr = load_wav_to_torch(os.path.join(str(dataset_cfg["data_path"]), f"{stem}.wav"))
                 mels.append(_mel.get_mel(audio).to(torch.float32).cuda())
+                if report_pitch:        # refused here, before the first batch is sampled
+                    _check_pitch_source(stem, min(int(audio.shape[0]), int(mels[-1].shape[-1]) * hop), dataset_cfg)
         frames = [int(m.shape[-1]) for m in mels]
         batches = ragged_plan(frames, len(mel_names) if batch_size is None else batch_size)
         clips_out = [None] * len(mel_names)
@@ -742,7 +799,10 @@ def generate(rank, diffusion_cfg, model_cfg, dataset_cfg, ckpt_iter="max", n_sam
             for b, k in enumerate(batch):
                 clips_out[k] = x[b, :, :lens[b]].clone()
             if report_metrics:
-                _report_metrics(i, x, [mel_names[k] for k in batch], batch, lens, dataset_cfg, metric_rows)
+                _report_metrics(i, x, [mel_names[k] for k in batch], batch, lens, dataset_cfg, metric_rows, source_wavs)
+            if report_pitch:
+                _report_pitch(i, x, [mel_names[k] for k in batch], batch, lens, dataset_cfg, metric_rows,
+                              bool(report_metrics), source_wavs)
         torch.cuda.synchronize()
         made = [k for k, c in enumerate(clips_out) if c is not None]
         print(f"generated {len(made)} utterances of {len(mel_names)} at iteration {ckpt_iter} in "
@@ -769,6 +829,9 @@ def generate(rank, diffusion_cfg, model_cfg, dataset_cfg, ckpt_iter="max", n_sam
             _mel = Mel2Samp(**{k: dataset_cfg[k] for k in keys if k in dataset_cfg})
             audio, sr = load_wav_to_torch(os.path.join(str(dataset_cfg["data_path"]), f"{mel_name}.wav"))
             mel = _mel.get_mel(audio).unsqueeze(0)
+            if report_pitch:          # refused here, before anything is sampled
+                _check_pitch_source(mel_name, min(int(audio.shape[0]), int(mel.shape[-1]) * dataset_cfg["hop_length"]),
+                                    dataset_cfg)
         audio_length = mel.shape[-1] * dataset_cfg["hop_length"]
     else:
         audio_length, mel = dataset_cfg["segment_length"], None
@@ -848,7 +911,10 @@ def generate(rank, diffusion_cfg, model_cfg, dataset_cfg, ckpt_iter="max", n_sam
                 mel_errors.append(err)
         if report_metrics:
             _report_metrics(i, out[-1], [mel_name] * len(batch), batch, [audio_length] * len(batch), dataset_cfg,
-                            metric_rows)
+                            metric_rows, source_wavs)
+        if report_pitch:
+            _report_pitch(i, out[-1], [mel_name] * len(batch), batch, [audio_length] * len(batch), dataset_cfg,
+                          metric_rows, bool(report_metrics), source_wavs)
     generated_audio = torch.cat(out, dim=0) if out else torch.empty(0, 1, audio_length, device="cuda")
     torch.cuda.synchronize()
     print(f"generated {len(numbers)} samples shape {tuple(generated_audio.shape)} at iteration {ckpt_iter} in "

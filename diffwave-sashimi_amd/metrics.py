@@ -74,25 +74,25 @@ def check_resolution(n_fft, hop, win, lengths):
                              f"n_fft/2 + 1 = {n_fft // 2 + 1}")
 
 
-def _pair(x, y, lengths):
+def _pair(x, y, lengths, what="spectral_metrics"):
     """Shape checks of a pair of batches (ValueError): the two as [B, T] views and the host lengths."""
     for name, t in (("x", x), ("y", y)):
         if not isinstance(t, torch.Tensor) or not t.dtype.is_floating_point or t.dim() not in (2, 3) or \
                 (t.dim() == 3 and t.shape[1] != 1):
-            raise ValueError(f"spectral_metrics: {name} has shape {tuple(getattr(t, 'shape', ()))!r}, expected a float "
+            raise ValueError(f"{what}: {name} has shape {tuple(getattr(t, 'shape', ()))!r}, expected a float "
                              "tensor [B, T] or [B, 1, T]")
     x = x[:, 0] if x.dim() == 3 else x
     y = y[:, 0] if y.dim() == 3 else y
     if x.shape != y.shape or x.shape[0] < 1 or x.shape[1] < 1:
-        raise ValueError(f"spectral_metrics: x {tuple(x.shape)} and y {tuple(y.shape)} must be two equal non-empty batches")
+        raise ValueError(f"{what}: x {tuple(x.shape)} and y {tuple(y.shape)} must be two equal non-empty batches")
     B, T = (int(v) for v in x.shape)
     if lengths is None:
         return x, y, None, [T] * B
     host = lengths.detach().cpu().tolist() if isinstance(lengths, torch.Tensor) else list(lengths)
     if len(host) != B or (isinstance(lengths, torch.Tensor) and lengths.dim() != 1):
-        raise ValueError(f"spectral_metrics: lengths has {len(host)} entries for a batch of {B} clips")
+        raise ValueError(f"{what}: lengths has {len(host)} entries for a batch of {B} clips")
     if any(not _is_int(n) or not 1 <= n <= T for n in host):
-        raise ValueError(f"spectral_metrics: lengths = {host!r}: expected integers in 1 .. T = {T}")
+        raise ValueError(f"{what}: lengths = {host!r}: expected integers in 1 .. T = {T}")
     return x, y, [int(n) for n in host], [int(n) for n in host]
 
 
@@ -216,6 +216,146 @@ def spectral_metrics(x, y, lengths=None, *, stft=None, resolutions=MR_STFT_RESOL
 
 
 METRICS = ("mr_stft", "ls_mae", "lsd", "mcd")       # the four headline numbers, in the order they are printed
+
+
+# ---- pitch: dws_pitch_track / dws_pitch_distance (csrc/pitch_kernels.hip; DESIGN.md section 4, "Pitch metrics")
+PITCH_METRICS = ("f0_rmse", "f0_cents", "gpe", "vuv_error", "vuv_f1", "periodicity_rmse")      # in print order
+PITCH_SUMS = ("voiced_both", "f0_sq", "cents_sq", "voiced_y", "voiced_x", "vuv_differ", "periodicity_sq", "gross")
+PITCH_DEFAULTS = dict(sampling_rate=22050, hop=256, win=1024, fmin=50.0, fmax=550.0, threshold=0.15)
+PITCH_WIN_MIN, PITCH_WIN_MAX, PITCH_LAG_MAX = 64, 2048, 2048
+
+
+def _is_real(v):
+    return isinstance(v, (int, float, np.integer, np.floating)) and not isinstance(v, bool) and math.isfinite(float(v))
+
+
+def pitch_lags(sampling_rate, fmin, fmax):
+    """``(tau_lo, tau_hi) = (floor(sr / fmax), ceil(sr / fmin))``: the lags the tracker searches."""
+    return int(math.floor(sampling_rate / fmax)), int(math.ceil(sampling_rate / fmin))
+
+
+def check_pitch(lengths, sampling_rate=22050, hop=256, win=1024, fmin=50.0, fmax=550.0, threshold=0.15,
+                what="pitch_metrics"):
+    """``(tau_lo, tau_hi)`` of parameters the kernel runs on clips of these ``lengths`` (host integers), or ValueError
+    naming the parameter (and the clip): ``win`` in 64 .. 2048, ``M = tau_hi + 1 <= 2048``, ``2 <= tau_lo < tau_hi``,
+    ``hop >= 1``, ``threshold`` inside (0, 1), every clip at least ``(win + M + 1) // 2 + 1`` samples long (reflect
+    padding; nothing is clamped)."""
+    if not _is_real(sampling_rate) or sampling_rate <= 0:
+        raise ValueError(f"{what}: sampling_rate = {sampling_rate!r}: expected a number > 0")
+    if not _is_int(win) or not PITCH_WIN_MIN <= win <= PITCH_WIN_MAX:
+        raise ValueError(f"{what}: win = {win!r}: expected an integer in {PITCH_WIN_MIN} .. {PITCH_WIN_MAX}")
+    if not _is_int(hop) or hop < 1:
+        raise ValueError(f"{what}: hop = {hop!r}: expected an integer >= 1")
+    if not _is_real(threshold) or not 0.0 < float(np.float32(threshold)) < 1.0:
+        raise ValueError(f"{what}: threshold = {threshold!r}: expected a number inside (0, 1)")
+    if not _is_real(fmin) or not _is_real(fmax) or fmin <= 0 or fmax <= 0:
+        raise ValueError(f"{what}: fmin = {fmin!r}, fmax = {fmax!r}: expected two numbers > 0")
+    tau_lo, tau_hi = pitch_lags(sampling_rate, fmin, fmax)
+    if tau_hi + 1 > PITCH_LAG_MAX:
+        raise ValueError(f"{what}: fmin = {fmin!r} at sampling_rate = {sampling_rate!r} needs lags up to M = {tau_hi + 1}: "
+                         f"the kernel computes at most {PITCH_LAG_MAX}")
+    if tau_lo < 2:
+        raise ValueError(f"{what}: fmax = {fmax!r} at sampling_rate = {sampling_rate!r} gives tau_lo = {tau_lo}: the "
+                         "smallest lag must be at least 2")
+    if tau_lo >= tau_hi:
+        raise ValueError(f"{what}: fmin = {fmin!r}, fmax = {fmax!r} give lags {tau_lo} .. {tau_hi}: tau_lo must lie below tau_hi")
+    need = (win + tau_hi + 2) // 2 + 1
+    for b, n in enumerate(lengths):
+        if n < need:
+            raise ValueError(f"{what}: clip {b} has {n} samples, reflect padding at win = {win} and lags up to "
+                             f"{tau_hi + 1} needs at least (win + M + 1) // 2 + 1 = {need}")
+    return tau_lo, tau_hi
+
+
+def _pitch_args(host, dev, B, dev_len=None):
+    if host is None:
+        return None, None
+    return (torch.tensor(host, dtype=torch.int32).to(dev) if dev_len is None else dev_len), (ctypes.c_int32 * B)(*host)
+
+
+def pitch_track(x, lengths=None, *, sampling_rate=22050, hop=256, win=1024, fmin=50.0, fmax=550.0, threshold=0.15):
+    """YIN pitch track (de Cheveigne & Kawahara, 2002; fixed threshold) of ``x`` ([B, T] or [B, 1, T], cuda):
+    ``(f0, periodicity)``, both float32 [B, T // hop + 1] on the device.  Frame ``f`` is centred on sample ``f hop`` (the
+    frames of ``spectral_metrics`` at that hop, ``f = 0 .. len // hop``); ``f0`` is in Hz and 0 on an unvoiced frame,
+    ``periodicity`` is ``1 - d'`` at the chosen lag (at the smallest ``d'`` of the search range on an unvoiced frame),
+    clamped to [0, 1].  ``lengths`` as in ``spectral_metrics``; frames behind a clip's last are exactly (0, 0).  The
+    definitions are those of ``dws_pitch_track`` (include/dws.h).  Arguments are checked first (ValueError naming the
+    parameter and the clip), then the device (RuntimeError)."""
+    x, _, host, lens = _pair(x, x, lengths, "pitch_track")
+    tau_lo, tau_hi = check_pitch(lens, sampling_rate, hop, win, fmin, fmax, threshold, "pitch_track")
+    _need_gpu(x, x)
+    x = x.detach().to(torch.float32).contiguous()
+    lib = _lib.load()
+    B, T = x.shape
+    track = torch.empty(B, T // hop + 1, 2, device=x.device, dtype=torch.float32)
+    dev_len, host_len = _pitch_args(host, x.device, B)
+    with torch.cuda.device(x.device):
+        _lib.check(lib.dws_pitch_track(x.data_ptr(), B, T, _lib.ptr(dev_len), host_len, hop, win, tau_lo, tau_hi,
+                                       float(threshold), float(sampling_rate), track.data_ptr(), _lib.current_stream()))
+    return track[:, :, 0].contiguous(), track[:, :, 1].contiguous()
+
+
+def _pitch_sums(what, x, y, lengths, sampling_rate, hop, win, fmin, fmax, threshold):
+    """``pitch_sums`` and the host lengths of the clips."""
+    x, y, host, lens = _pair(x, y, lengths, what)
+    tau_lo, tau_hi = check_pitch(lens, sampling_rate, hop, win, fmin, fmax, threshold, what)
+    _need_gpu(x, y)
+    x = x.detach().to(torch.float32).contiguous()
+    y = y.detach().to(torch.float32).contiguous()
+    return _pitch_run(x, y, host, sampling_rate, hop, win, tau_lo, tau_hi, threshold).cpu(), lens
+
+
+def _pitch_run(x, y, host, sampling_rate, hop, win, tau_lo, tau_hi, threshold):
+    """One ``dws_pitch_distance`` call on checked arguments: float64 [B, 8] on the device."""
+    lib = _lib.load()
+    B, T = x.shape
+    dev = x.device
+    out = torch.empty(B, len(PITCH_SUMS), device=dev, dtype=torch.float64)
+    ws = torch.empty(lib.dws_pitch_distance_workspace(B, T, hop) // 4, device=dev, dtype=torch.float32)
+    dev_len, host_len = _pitch_args(host, dev, B)
+    with torch.cuda.device(dev):
+        _lib.check(lib.dws_pitch_distance(x.data_ptr(), y.data_ptr(), B, T, _lib.ptr(dev_len), host_len, hop, win, tau_lo,
+                                          tau_hi, float(threshold), float(sampling_rate), ws.data_ptr(), out.data_ptr(),
+                                          _lib.current_stream()))
+    return out
+
+
+def pitch_sums(x, y, lengths=None, *, sampling_rate=22050, hop=256, win=1024, fmin=50.0, fmax=550.0, threshold=0.15):
+    """The eight sums of ``dws_pitch_distance`` (include/dws.h), columns ``PITCH_SUMS``: float64 [B, 8] on the CPU.  A
+    clip's row depends on its own samples and length alone, bit for bit.  Arguments are checked first (ValueError), then
+    the device (RuntimeError)."""
+    return _pitch_sums("pitch_sums", x, y, lengths, sampling_rate, hop, win, fmin, fmax, threshold)[0]
+
+
+def pitch_metrics(x, y, lengths=None, *, sampling_rate=22050, hop=256, win=1024, fmin=50.0, fmax=550.0, threshold=0.15):
+    """Pitch distances of generated ``x`` from reference ``y`` ([B, T] or [B, 1, T], cuda), clip by clip, from the YIN
+    tracks of the two (``pitch_track``).  Returns a dict of float64 [B] CPU tensors; with ``vv`` the frames voiced in both:
+
+    ``f0_rmse``: ``sqrt(mean_vv (f0x - f0y)^2)`` in Hz (PriorGrad's F0 RMSE); ``f0_cents``: the same of
+    ``1200 log2(f0x / f0y)``; ``gpe``: the share of ``vv`` frames with ``|f0x / f0y - 1| > 0.2`` (gross pitch errors);
+    ``vuv_error``: the share of ALL frames on which the voicing decisions differ; ``vuv_f1``:
+    ``2 #vv / (#voiced_x + #voiced_y)``; ``periodicity_rmse``: ``sqrt(mean (p_x - p_y)^2)`` over all frames; ``frames``
+    (``len // hop + 1``) and ``voiced_both`` (``#vv``).
+
+    NaN: ``f0_rmse``, ``f0_cents`` and ``gpe`` of a clip with no frame voiced in both signals, ``vuv_f1`` where neither
+    signal has a voiced frame.  ``vuv_error`` and ``periodicity_rmse`` are always finite.
+
+    This is plain YIN with a fixed threshold: no pYIN / Viterbi smoothing, not CREPE or WORLD, so the absolute values are
+    not those of the papers that report these metrics; it orders systems evaluated with this function.  Arguments are
+    checked before anything runs (ValueError naming the parameter and the clip); CPU tensors raise RuntimeError."""
+    s, lens = _pitch_sums("pitch_metrics", x, y, lengths, sampling_rate, hop, win, fmin, fmax, threshold)
+    frames = torch.tensor([n // hop + 1 for n in lens], dtype=torch.float64)
+    return {"f0_rmse": torch.sqrt(s[:, 1] / s[:, 0]), "f0_cents": torch.sqrt(s[:, 2] / s[:, 0]), "gpe": s[:, 7] / s[:, 0],
+            "vuv_error": s[:, 5] / frames, "vuv_f1": 2.0 * s[:, 0] / (s[:, 3] + s[:, 4]),
+            "periodicity_rmse": torch.sqrt(s[:, 6] / frames), "frames": frames, "voiced_both": s[:, 0].clone()}
+
+
+def nanmean(values):
+    """The mean of the finite entries of ``values`` (NaN where there is none): a clip whose metric is undefined is left
+    out of that metric's mean."""
+    v = np.asarray(list(values), dtype=np.float64)
+    v = v[np.isfinite(v)]
+    return float(v.mean()) if len(v) else float("nan")
 
 
 def check_resolutions(resolutions, lengths, what="spectral_metrics"):

@@ -7,7 +7,10 @@ Adam at ``train.learning_rate``, one process per GPU with ``apply_gradient_allre
 checkpoints followed by an in-loop ``generate`` call.  wandb is replaced by a JSON-lines log
 (``exp/<run>/train_log.jsonl``, same keys: ``train/loss``, ``train/log_loss``, ``train/loss_epoch``).  With
 ``+generate.report_metrics=true`` the in-loop ``generate`` compares its clips with their source wavs and the log gets
-``val/mr_stft``, ``val/ls_mae``, ``val/lsd`` and ``val/mcd`` at that iteration (``metrics.py``).
+``val/mr_stft``, ``val/ls_mae``, ``val/lsd`` and ``val/mcd`` at that iteration (``metrics.py``); with
+``+generate.report_pitch=true`` it gets ``val/f0_rmse``, ``val/f0_cents``, ``val/gpe``, ``val/vuv_error``, ``val/vuv_f1``
+and ``val/periodicity_rmse`` (``metrics.pitch_metrics``; means over the clips on which a key is defined, a key that is
+defined on none is left out).
 
     python -m diffwave_sashimi_amd.train --config-dir /path/to/configs experiment=sc09 model=sashimi \
         dataset.data_path=/data/sc09 train.batch_size_per_gpu=32
@@ -398,16 +401,21 @@ def train(rank, num_gpus, diffusion_cfg, model_cfg, dataset_cfg, generate_cfg, c
                         gen.setdefault("label", "all")      # the classes in turn over the batch
                     net.eval()
                     wavs = []
-                    rows = [] if gen.get("report_metrics") else None      # generate.report_metrics: metrics.py
+                    # generate.report_metrics / generate.report_pitch: metrics.py
+                    rows = [] if gen.get("report_metrics") or gen.get("report_pitch") else None
                     if rows is not None:
                         gen["metric_rows"] = rows
                     generate(rank, diffusion_cfg, model_cfg, dataset_cfg, name=name, exp_root=exp_root,
                              written=wavs, **gen)
                     net.train()
                     log({"val/audio": wavs}, n_iter)     # the reference logs the clips to wandb (`train.py:180-183`)
-                    if rows:        # the means over the clips just written, against their source wavs
+                    if rows and gen.get("report_metrics"):     # the means over the clips just written, against their source wavs
                         log({"val/" + k: float(np.mean([r[k] for r in rows]))
                              for k in ("mr_stft", "ls_mae", "lsd", "mcd")}, n_iter)
+                    if rows and gen.get("report_pitch"):       # nan-means: a clip without a voiced frame has no F0 numbers
+                        from .metrics import PITCH_METRICS, nanmean
+                        means = {k: nanmean(r[k] for r in rows) for k in PITCH_METRICS if k in rows[0]}
+                        log({"val/" + k: v for k, v in means.items() if np.isfinite(v)}, n_iter)
             n_iter += 1
             if n_iter >= n_iters + 1:
                 break

@@ -708,6 +708,56 @@ int dws_spectral_loss_backward(const float* x, const float* y, int64_t B, int64_
 /* Bytes of dws_spectral_loss_backward's workspace; 0 for a shape it refuses. */
 int64_t dws_spectral_loss_backward_workspace(int64_t B, int64_t T, int32_t n_fft, int32_t hop);
 
+/* Pitch track of a batch of waveforms (not in the reference): s DEVICE float32 [B][T], YIN (de Cheveigne & Kawahara,
+ * 2002) with a fixed threshold, one workgroup per frame.  With len_b = lengths[b] (T where lengths is null), W = win,
+ * M = tau_hi + 1 (the largest lag computed: the chosen lag always has a right neighbour), S = W + M, rho_b the reflect map
+ * about the clip's OWN ends as in dws_spectral_distance, and frames f = 0 .. len_b / hop (its frame count at that hop):
+ *     u_f[i] = s[rho_b(f hop - S/2 + i)]                          i = 0 .. S-1
+ *     d(tau) = sum_{j=0}^{W-1} (u_f[j] - u_f[j + tau])^2          tau = 1 .. M,   d(0) = 0
+ *     d'(tau) = d(tau) tau / sum_{t=1}^{tau} d(t)                 (1 where the sum is 0; d'(0) = 1)
+ * Decision: the smallest tau in [tau_lo, tau_hi] with d'(tau) < threshold, then tau <- tau + 1 while tau + 1 <= tau_hi and
+ * d'(tau + 1) < d'(tau); the result is tau*.  If there is one the frame is voiced: with a, b, c = d'(tau* - 1), d'(tau*),
+ * d'(tau* + 1), delta = (a - c) / (2 (a - 2b + c)) where a - 2b + c > 0 and |delta| <= 1, else 0:
+ *     f0 = sampling_rate / (tau* + delta),    periodicity = clamp(1 - b, 0, 1);
+ * otherwise it is unvoiced: f0 = 0, periodicity = clamp(1 - min_{tau_lo..tau_hi} d', 0, 1).  Digital silence is unvoiced
+ * with periodicity 0.  track [B][T/hop + 1][2] (DEVICE, float32) receives (f0, periodicity); frames behind a clip's last
+ * are written as exactly (0, 0).
+ * Arithmetic and order of summation: d(tau) is the direct sum of squares of exact differences in fp32 (never energy -
+ * 2 autocorrelation, which cancels at the minimum that decides).  A work item owns lags 4g .. 4g + 3 and one of
+ * P = max(1, 256 / G) contiguous parts of the 4-sample blocks of j (G = (M + 4) / 4; the last part also takes the
+ * W mod 4 samples that are left); it adds its j in ascending order (fmaf), and the parts are added in ascending order.
+ * Everything after that is double -- the prefix sum (thread t of 256 owns ceil(M / 256) consecutive lags serially, an
+ * inclusive scan over the lanes of a wave, the four waves in wave order), d', every comparison (threshold is widened
+ * from the float32 it travels as) and the interpolation -- and the two outputs are rounded to float32.  The decision is
+ * three min reductions; there are no atomics.  The result is bitwise reproducible, and clip b's rows depend on its own
+ * len_b samples alone: not on B, T, b or on anything stored behind len_b (never read; may be NaN).  Scaling s by a power
+ * of two changes no bit of the track.
+ * lengths / lengths_host: as dws_spectral_distance (DEVICE and HOST copies of the same numbers, both or neither; the
+ * host copy is checked, nothing waits for the GPU; a device value the host did not admit makes its clip an empty one).
+ * LDS per workgroup: 4 (S + 16 .. 19 + 4 G P) + 8 (4G + 10) bytes (at most 41 KiB).
+ * DWS_ERR_INVALID: a null s or track; win outside 64 .. 2048; tau_lo < 2, tau_lo >= tau_hi or tau_hi + 1 > 2048;
+ * hop < 1; threshold outside (0, 1); sampling_rate <= 0; B outside 1 .. 65535; a len_b outside (S + 1) / 2 + 1 .. T
+ * (reflect padding; no length is clamped); lengths without lengths_host. */
+int dws_pitch_track(const float* s, int64_t B, int64_t T, const int32_t* lengths, const int32_t* lengths_host, int32_t hop,
+                    int32_t win, int32_t tau_lo, int32_t tau_hi, float threshold, double sampling_rate, float* track,
+                    void* stream);
+
+/* Pitch distances between two batches of waveforms (not in the reference): the tracks of x (generated) and y (reference)
+ * as dws_pitch_track computes them, in one launch, and the sums of a clip over its frames in ascending order in double.
+ * With v_x, v_y the voicing flags (f0 > 0), vv = both voiced and p the periodicity, out [B][8] (DEVICE, double):
+ *     out[b][0] = #vv                   out[b][1] = sum_vv (f0x - f0y)^2 [Hz^2]   out[b][2] = sum_vv (1200 log2(f0x / f0y))^2
+ *     out[b][3] = #v_y                  out[b][4] = #v_x                          out[b][5] = #(v_x != v_y)
+ *     out[b][6] = sum (p_x - p_y)^2     out[b][7] = #vv with |f0x / f0y - 1| > 0.2   (gross pitch errors)
+ * workspace: DEVICE, dws_pitch_distance_workspace(B, T, hop) bytes (the two tracks, x's then y's, [2][B][T/hop + 1][2]
+ * floats) owned by the caller (overwritten; the library allocates nothing per call).  Reproducibility, independence of a
+ * clip from its batch and the error codes are dws_pitch_track's (and a null workspace or out: DWS_ERR_INVALID). */
+int dws_pitch_distance(const float* x, const float* y, int64_t B, int64_t T, const int32_t* lengths,
+                       const int32_t* lengths_host, int32_t hop, int32_t win, int32_t tau_lo, int32_t tau_hi,
+                       float threshold, double sampling_rate, float* workspace, double* out, void* stream);
+
+/* Bytes of dws_pitch_distance's workspace; 0 for a shape it refuses. */
+int64_t dws_pitch_distance_workspace(int64_t B, int64_t T, int32_t hop);
+
 /* The arithmetic of precision="bf16x6" alone (accuracy tests; not a tuned GEMM): C[M][N] = A[M][K] . B[K][N], row-major
  * fp32 device tensors, every operand split into three bf16 terms in registers, six bf16 MFMA products per term pair
  * accumulated in fp32 -- exactly what the bf16x6 layer kernels execute per k-block.  M, N multiples of 32, K of 16. */

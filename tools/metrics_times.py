@@ -6,7 +6,9 @@ the same inputs on the same GPU.
 
 One JSON line per pass (Parallel WaveGAN's three resolutions and the mel pass of ``TacotronSTFT()``): the median over
 --repeats of one ``dws_spectral_distance`` call between two events (tables cached, workspace allocation included, no
-copy to the host), the same for the restatement, and the largest relative difference of the two results.
+copy to the host), the same for the restatement, and the largest relative difference of the two results.  A last line
+times the pitch pass (``dws_pitch_distance`` at the defaults of ``metrics.pitch_metrics``, DESIGN.md section 4, "Pitch
+metrics") at the same shape; it has no torch restatement beside it.
 
     python tools/metrics_times.py --loss [--batch 32] [--samples 16000] [--repeats 20]
 
@@ -120,6 +122,22 @@ def main():
                               max_rel_diff=rel)), flush=True)
     print(json.dumps(dict(all_passes=True, kernel_ms=round(total_k, 3), torch_stft_f32_ms=round(total_t, 3),
                           audio_seconds_at_22050=round(args.batch * args.samples / 22050.0, 2))), flush=True)
+    # the pitch pass ("Pitch metrics"): one dws_pitch_distance call at the defaults -- the YIN
+    # tracks of x and y and the eight sums.  The same noise is unvoiced throughout; a tracker's time does not depend on
+    # the decision (every lag of every frame is computed either way), so a second input with voiced frames is timed
+    # only to show that.
+    pd = metrics.PITCH_DEFAULTS
+    lo, hi = metrics.pitch_lags(pd["sampling_rate"], pd["fmin"], pd["fmax"])
+    run = lambda a, b: metrics._pitch_run(a, b, None, pd["sampling_rate"], pd["hop"], pd["win"], lo, hi, pd["threshold"])
+    p_ms, p_min, p_out = timed(lambda: run(x, y))
+    t = torch.arange(args.samples, device=dev, dtype=torch.float32) / pd["sampling_rate"]
+    tone = 0.3 * torch.sin(2.0 * torch.pi * 140.0 * t).expand(args.batch, -1).contiguous()
+    v_ms, v_min, v_out = timed(lambda: run(tone + 0.1 * x, tone))
+    print(json.dumps(dict(pitch=True, B=args.batch, T=args.samples, **pd, lags=[lo, hi],
+                          kernel_ms_median=round(p_ms, 3), kernel_ms_min=round(p_min, 3),
+                          voiced_input_ms_median=round(v_ms, 3), voiced_input_ms_min=round(v_min, 3),
+                          voiced_both_noise=float(p_out[:, 0].sum()), voiced_both_tone=float(v_out[:, 0].sum()))),
+          flush=True)
 
 
 if __name__ == "__main__":
