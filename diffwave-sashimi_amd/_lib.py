@@ -145,6 +145,11 @@ _SIGS = {
                                           ctypes.POINTER(ctypes.c_int32)] + [ctypes.c_int32] * 4 +
                            [ctypes.c_float, ctypes.c_double, c_f32p, ctypes.c_void_p, ctypes.c_void_p]),
     "dws_pitch_distance_workspace": (ctypes.c_int64, [ctypes.c_int64, ctypes.c_int64, ctypes.c_int32]),
+    "dws_pqmf_analysis": (ctypes.c_int, [c_f32p, ctypes.c_int64, ctypes.c_int64, c_f32p, ctypes.c_int32, ctypes.c_int32,
+                                         ctypes.c_float, c_f32p, ctypes.c_void_p]),
+    "dws_pqmf_synthesis": (ctypes.c_int, [c_f32p, ctypes.c_int64, ctypes.c_int64, c_f32p, ctypes.c_int32, ctypes.c_int32,
+                                          ctypes.c_float, c_f32p, ctypes.c_void_p]),
+    "dws_pqmf_tile": (ctypes.c_int, []),
     "dws_gemm_bf16x6": (ctypes.c_int, [c_f32p] * 3 + [ctypes.c_int64] * 3 + [ctypes.c_void_p]),
     "dws_gemm_f16x3": (ctypes.c_int, [c_f32p] * 3 + [ctypes.c_int64] * 3 + [ctypes.c_float] * 2 + [ctypes.c_void_p]),
     "dws_profile_enable": (ctypes.c_int, [ctypes.c_char_p]),

@@ -159,10 +159,11 @@ def local_directory(name, model_cfg, diffusion_cfg, dataset_cfg, output_director
     return local_path, output_directory
 
 
-def smooth_ckpt(path, min_ckpt, max_ckpt, priors=None):
+def smooth_ckpt(path, min_ckpt, max_ckpt, priors=None, banks=None):
     """``utils.py:47-74,154-166`` (experimental in the reference): running arithmetic mean of the
     ``model_state_dict`` of every checkpoint with ``min_ckpt < iteration <= max_ckpt``.  ``priors``: a list that receives
-    ``(iteration, prior entry or None)`` of every checkpoint that went into the mean."""
+    ``(iteration, prior entry or None)`` of every checkpoint that went into the mean; ``banks``: the same of the ``pqmf``
+    entries."""
     ckpts = []
     for f in os.listdir(path):
         if len(f) > 4 and f.endswith(".pkl"):
@@ -182,6 +183,8 @@ def smooth_ckpt(path, min_ckpt, max_ckpt, priors=None):
             raise Exception(f"No valid model found at iteration {it}, path {model_path}")
         if priors is not None:
             priors.append((it, checkpoint.get("prior")))
+        if banks is not None:
+            banks.append((it, checkpoint.get("pqmf")))
         state_dict = sd if state_dict is None else {k: (state_dict[k] * n + sd[k]) / (n + 1) for k in sd}
     return state_dict
 
@@ -539,7 +542,19 @@ def generate(rank, diffusion_cfg, model_cfg, dataset_cfg, ckpt_iter="max", n_sam
     Without these keys a checkpoint's ``prior`` entry (written by ``train.prior=energy``) is used and printed;
     ``prior=none`` forces N(0, I); value keys that contradict the entry and ``cfg_scale`` with a prior raise ValueError.
     A model must have been trained with the prior it is sampled with.  What the samples sound like has not been
-    measured."""
+    measured.
+
+    Multi-band runs (not in the reference; ``pqmf.py``): with ``model.subbands = K`` (``model_cfg``; optional
+    ``pqmf_taps`` / ``pqmf_cutoff`` / ``pqmf_beta``), or from a checkpoint with a ``pqmf`` entry (written by such a
+    training run; used and printed, and the network is then built with its K), the network has K channels, every
+    sampler runs on ``[B, K, length / K]`` and ``PQMF.synthesis`` turns the result into the waveform that is written,
+    returned and compared by ``report_mel`` / ``report_metrics`` / ``report_pitch``.  With ``mel_names`` the engine's
+    per-clip lengths are ``frames x hop_length / K``; the padding of the sub-bands is exactly zero, so an utterance's
+    waveform is the synthesis of its own sub-bands (with ``clip_seeds`` an utterance shorter than its batch is another
+    draw than alone: the noise of a K-channel state is numbered over the padded length).  Labels, ``cfg_scale``, every ``sampler`` and ``clip_seeds`` work as
+    before; the editing, start, resampling and guide keys and ``prior`` are ValueErrors (they act on the full-band
+    signal), as are keys that contradict the checkpoint's entry, ``model.subbands`` on a checkpoint without one, and a
+    ``ckpt_smooth`` over differing entries.  What the samples sound like has not been measured."""
     from .models import construct_model
     from .models.utils import check_n_classes
     from .sampling import (calc_diffusion_hyperparams, ddim_steps, declip_operator, logsnr_steps, lowpass_operator,
@@ -550,6 +565,21 @@ def generate(rank, diffusion_cfg, model_cfg, dataset_cfg, ckpt_iter="max", n_sam
 
     if ckpt_smooth is not None or ckpt_iter == "init":     # checked here, before a model is built
         weights_key(None, ema, ckpt_smooth)
+    from .pqmf import PQMF, model_options
+
+    def check_subbands(cfg):      # a multi-band run (model.subbands, or the checkpoint's pqmf entry), before a model is built
+        from .pqmf import check_run
+        check_run(cfg, dataset_cfg, where="generate")
+        given = [k for k, v in (("known_name", known_name), ("keep", keep), ("start_name", start_name),
+                                ("start_step", start_step), ("resample_jump", resample_jump), ("resample_n", resample_n),
+                                ("guide_name", guide_name), ("guide_op", guide_op), ("guide_clip", guide_clip),
+                                ("guide_factor", guide_factor), ("guide_scale", guide_scale),
+                                ("prior", None if prior == "none" else prior)) if v is not None]
+        if given:
+            raise ValueError(f"generate.{given[0]} does not combine with model.subbands (editing, guidance and the "
+                             "adaptive prior act on the full-band signal; their sub-band forms are not built)")
+    if model_options(model_cfg) is not None:
+        check_subbands(model_cfg)
     prior_cfg = prior_settings(prior, prior_energy_max, prior_energy_min, prior_std_min, model_cfg.get("unconditional"))
     prior_given = [k for k, v in zip(PRIOR_KEYS, (prior_energy_max, prior_energy_min, prior_std_min)) if v is not None]
     if isinstance(prior_cfg, dict) and cfg_scale is not None:
@@ -704,6 +734,26 @@ def generate(rank, diffusion_cfg, model_cfg, dataset_cfg, ckpt_iter="max", n_sam
 
     ckpt_path = os.path.join(exp_root, local_path, "checkpoint")
     prior_entry = None      # what the checkpoint was trained with
+    pqmf_cfg = model_options(model_cfg)     # the filter bank of a multi-band run (below: against the checkpoint's entry)
+
+    def bank_of(entries):
+        """``pqmf.resolve`` of the run's keys against the checkpoints' ``pqmf`` entries (None: none); a checkpoint
+        trained on sub-bands and sampled without ``model.subbands`` has its network rebuilt with the entry's K."""
+        from .pqmf import resolve, same_options
+        odd = [it for it, e in entries if not same_options(e, entries[0][1])]
+        if odd:
+            raise ValueError(f"generate.ckpt_smooth: the checkpoints were trained with different filter banks (iteration "
+                             f"{entries[0][0]}: {entries[0][1]!r}, iteration {odd[0]}: {dict(entries)[odd[0]]!r})")
+        cfg = resolve(model_cfg, entries[0][1])
+        if cfg is None or pqmf_cfg is not None:
+            return cfg, net
+        full = dict(model_kwargs, subbands=cfg["subbands"], pqmf_taps=cfg["taps"], pqmf_cutoff=cfg["cutoff"],
+                    pqmf_beta=cfg["beta"])
+        check_subbands(full)
+        rebuilt = construct_model(full).cuda().eval()
+        if precision not in (None, "f32"):
+            rebuilt.set_option("precision", precision)
+        return cfg, rebuilt
     if ckpt_iter == "init":
         ckpt_iter = 0
     else:
@@ -717,6 +767,7 @@ def generate(rank, diffusion_cfg, model_cfg, dataset_cfg, ckpt_iter="max", n_sam
             except Exception as e:  # the reference raises a bare 'No valid model found' (`generate.py:110-112`)
                 raise Exception(f"No valid model found ({model_file}: {e})")
             key = weights_key(checkpoint, ema)
+            pqmf_cfg, net = bank_of([(ckpt_iter, checkpoint.get("pqmf"))])
             try:
                 net.load_state_dict(checkpoint[key])
             except Exception as e:
@@ -725,8 +776,8 @@ def generate(rank, diffusion_cfg, model_cfg, dataset_cfg, ckpt_iter="max", n_sam
                 print(f"sampling from the EMA weights of iteration {ckpt_iter} (generate.ema=false: the raw weights)")
             prior_entry = checkpoint.get("prior")
         else:                       # `generate.py:113-115`: average of the checkpoints in (ckpt_smooth, ckpt_iter]
-            entries = []
-            state_dict = smooth_ckpt(ckpt_path, int(ckpt_smooth), ckpt_iter, priors=entries)
+            entries, banks = [], []
+            state_dict = smooth_ckpt(ckpt_path, int(ckpt_smooth), ckpt_iter, priors=entries, banks=banks)
             if state_dict is None:
                 raise Exception(f"No checkpoints in ({ckpt_smooth}, {ckpt_iter}] under {ckpt_path}")
             odd = [it for it, e in entries if not same_prior(e, entries[0][1])]
@@ -735,7 +786,16 @@ def generate(rank, diffusion_cfg, model_cfg, dataset_cfg, ckpt_iter="max", n_sam
                                  f"different priors (iteration {entries[0][0]}: {entries[0][1]!r}, iteration {odd[0]}: "
                                  f"{dict(entries)[odd[0]]!r})")
             prior_entry = entries[0][1]
+            pqmf_cfg, net = bank_of(banks)
             net.load_state_dict(state_dict)
+    bank, K = None, 1       # multi-band runs: the samplers return K sub-bands at a K-th of the length
+    if pqmf_cfg is not None:
+        bank, K = PQMF(**pqmf_cfg), pqmf_cfg["subbands"]
+        print("multi-band run{}: subbands={subbands} taps={taps} cutoff={cutoff:g} beta={beta:g}".format(
+            " (the checkpoint's pqmf entry)" if model_cfg.get("subbands") is None else "", **pqmf_cfg))
+        if prior_entry is not None:
+            raise ValueError("the checkpoint holds a prior entry and a pqmf entry: the adaptive prior in sub-bands is not "
+                             "built")
     prior_cfg = resolve_prior(prior_cfg, prior_entry, prior_given)
     if prior_cfg is not None:
         if cfg_scale is not None:
@@ -783,19 +843,23 @@ def generate(rank, diffusion_cfg, model_cfg, dataset_cfg, ckpt_iter="max", n_sam
             mel = torch.zeros(len(batch), mels[0].shape[0], Tmax, device="cuda", dtype=torch.float32)
             for b, k in enumerate(batch):
                 mel[b, :, :frames[k]] = mels[k]
-            size = (len(batch), 1, Lmax)
+            size = (len(batch), K, Lmax // K)
             s = [seeds_of_clips(seed, k, 1)[0] for k in batch] if clip_seeds else (None if seed is None else seed + i)
             print(f"batch {i}: L_max = {Lmax}, lengths = {lens}, padded share = "
                   f"{1.0 - sum(lens) / float(len(batch) * Lmax):.3f}")
             pr = sigma_of(mel, Lmax)     # (each frame on its own: a clip's sigma is what it is alone; its padding is unused)
+            run_lens = lens if bank is None else [n // K for n in lens]      # what the engine runs: sub-band positions
             if sampler == "aligned":
-                x = sampling_aligned(net, size, diffusion_cfg, condition=mel, seed=s, lengths=lens, **pr)
+                x = sampling_aligned(net, size, diffusion_cfg, condition=mel, seed=s, lengths=run_lens, **pr)
             elif sampler == "ddim":
-                x = sampling_ddim(net, size, dh_train, steps, eta=float(eta or 0.0), condition=mel, seed=s, lengths=lens, **pr)
+                x = sampling_ddim(net, size, dh_train, steps, eta=float(eta or 0.0), condition=mel, seed=s, lengths=run_lens,
+                                  **pr)
             elif sampler == "dpmpp2m":
-                x = sampling_dpmpp(net, size, dh_train, steps, condition=mel, spacing=spacing, seed=s, lengths=lens, **pr)
+                x = sampling_dpmpp(net, size, dh_train, steps, condition=mel, spacing=spacing, seed=s, lengths=run_lens, **pr)
             else:
-                x = sampling(net, size, dh, condition=mel, seed=s, lengths=lens, **pr)
+                x = sampling(net, size, dh, condition=mel, seed=s, lengths=run_lens, **pr)
+            if bank is not None:        # the sub-band padding is exactly zero: a clip's synthesis is what it is alone
+                x = bank.synthesis(x)
             for b, k in enumerate(batch):
                 clips_out[k] = x[b, :, :lens[b]].clone()
             if report_metrics:
@@ -877,7 +941,7 @@ def generate(rank, diffusion_cfg, model_cfg, dataset_cfg, ckpt_iter="max", n_sam
                                              for i in range(n_samples // batch_size)]
     numbers = [k for batch in batches for k in batch]
     for i, batch in enumerate(batches):
-        size = (len(batch), 1, audio_length)
+        size = (len(batch), K, audio_length // K)
         if plan is not None:    # a seed and a class per clip, both functions of the global clip number alone
             s = [seeds_of_clips(seed, k, 1)[0] for k in batch]
             class_of = [k % len(labels_of) for k in batch] if labels_of is not None else None
@@ -904,6 +968,8 @@ def generate(rank, diffusion_cfg, model_cfg, dataset_cfg, ckpt_iter="max", n_sam
             out.append(sampling_dpmpp(net, size, dh_train, steps, condition=mel, spacing=spacing, seed=s, **edit))
         else:
             out.append(sampling(net, size, dh, condition=mel, seed=s, **edit))
+        if bank is not None:        # the samplers return the K sub-bands: one synthesis bank at the end of the run
+            out[-1] = bank.synthesis(out[-1])
         if report_mel:
             err = float((mel_of(out[-1]) - mel).abs().mean())
             print(f"batch {i} mel error: mean |log-mel(generated) - condition| = {err:.4f}")

@@ -214,6 +214,10 @@ class PriorMismatch(ValueError):
     """A resume whose ``train.prior`` keys differ from the checkpoint's ``prior`` entry."""
 
 
+class PqmfMismatch(ValueError):
+    """A resume whose ``model.subbands`` / ``model.pqmf_*`` keys differ from the checkpoint's ``pqmf`` entry."""
+
+
 def train(rank, num_gpus, diffusion_cfg, model_cfg, dataset_cfg, generate_cfg, ckpt_iter, n_iters, iters_per_ckpt,
           iters_per_logging, learning_rate, batch_size_per_gpu, name=None, exp_root="exp", num_workers=4, precision=None,
           honour_optim_hints=False, label_dropout=None, optimizer=None, ema_decay=None, clip_grad_norm=None, prior=None,
@@ -242,12 +246,26 @@ def train(rank, num_gpus, diffusion_cfg, model_cfg, dataset_cfg, generate_cfg, c
     estimate x0_hat against the clean audio, on the clips whose step is below K (``training_loss(stft_weight=)``).
     ``train/eps_loss`` and ``train/stft_loss`` join ``train/loss`` in the log; the checkpoints get a ``stft_loss`` entry
     with the three values, which a resume prints (it is information, not a condition: a run may change or drop the
-    term).  The term is local to a rank.  What it does for audio quality has not been measured."""
+    term).  The term is local to a rank.  What it does for audio quality has not been measured.
+
+    Multi-band runs (``+model.subbands=K [+model.pqmf_taps=62 +model.pqmf_cutoff=C +model.pqmf_beta=9.0]``, K = 2 or 4;
+    not in the reference; ``pqmf.py``): the network is built with K channels and trained on the PQMF sub-bands of every
+    batch (``training_loss(pqmf=)``), a K-th of the positions per evaluation.  On a mel-conditional model
+    ``prod(model.mel_upsample) x K`` must be ``dataset.hop_length``; ``dataset.segment_length`` must be a multiple of K
+    (and, on SaShiMi, of K times the pooling product; ``model.L`` stays the full-band length).  The checkpoints get a
+    ``pqmf`` entry with the four values, which ``generate`` picks up; a resume with other values raises ``PqmfMismatch``
+    (a ValueError).  ``train.prior`` is refused; ``train.stft_weight`` compares the synthesised estimate with the
+    waveform.  What such a model sounds like has not been measured."""
     opt_kind, ema_decay, clip_grad_norm = optimizer_options(optimizer, ema_decay, clip_grad_norm)
     from .training import stft_loss_options
     stft_cfg = stft_loss_options(stft_weight, stft_max_step, stft_resolutions, diffusion_cfg.get("T"), where="train")
-    if stft_cfg is not None and model_cfg.get("in_channels", 1) != 1:
+    from .pqmf import PQMF, check_run, same_options
+    pqmf_cfg = check_run(model_cfg, dataset_cfg, where="train")      # model.subbands: a multi-band run (pqmf.py)
+    if stft_cfg is not None and pqmf_cfg is None and model_cfg.get("in_channels", 1) != 1:
         raise ValueError(f"train.stft_weight needs model.in_channels = 1 (got {model_cfg.get('in_channels')!r})")
+    if pqmf_cfg is not None and prior not in (None, "none"):
+        raise ValueError("train.prior does not combine with model.subbands (the adaptive prior is a full-band quantity; "
+                         "its sub-band form is not built)")
     prior_cfg = prior_settings(prior, prior_energy_max, prior_energy_min, prior_std_min, model_cfg.get("unconditional"),
                                where="train")
     prior_cfg = prior_cfg if isinstance(prior_cfg, dict) else None
@@ -275,6 +293,9 @@ def train(rank, num_gpus, diffusion_cfg, model_cfg, dataset_cfg, generate_cfg, c
     net = construct_model(dict(model_cfg)).cuda().train()
     if precision not in (None, "f32"):      # `+engine.precision=bf16x6`: the split GEMMs of either backbone's step on the bf16 matrix cores
         net.set_option("precision", precision)
+    band = {} if pqmf_cfg is None else {"pqmf": PQMF(**pqmf_cfg)}    # (training_loss splits every batch into the sub-bands)
+    if pqmf_cfg is not None:
+        print("multi-band run: subbands={subbands} taps={taps} cutoff={cutoff:g} beta={beta:g}".format(**pqmf_cfg))
     print(f"{type(net).__name__} parameters: {sum(p.numel() for p in net.parameters()) / 1e6:.6f}M")   # `utils.py:76-88`
     if num_gpus > 1:
         net = apply_gradient_allreduce(net)
@@ -297,6 +318,9 @@ def train(rank, num_gpus, diffusion_cfg, model_cfg, dataset_cfg, generate_cfg, c
                 raise PriorMismatch(f"checkpoint {ckpt_iter} was trained with the prior {checkpoint.get('prior')!r}, this run "
                                     f"asks for {prior_cfg!r}: resume with the same train.prior keys (weights trained "
                                     "towards one prior are not a start for another)")
+            if not same_options(checkpoint.get("pqmf"), pqmf_cfg):
+                raise PqmfMismatch(f"checkpoint {ckpt_iter} was trained with the filter bank {checkpoint.get('pqmf')!r}, this "
+                                   f"run asks for {pqmf_cfg!r}: resume with the same model.subbands / model.pqmf_* keys")
             net.load_state_dict(checkpoint["model_state_dict"])
             if "stft_loss" in checkpoint or stft_cfg is not None:
                 print(f"checkpoint {ckpt_iter} was trained with stft_loss = {checkpoint.get('stft_loss')!r}, this run "
@@ -313,7 +337,7 @@ def train(rank, num_gpus, diffusion_cfg, model_cfg, dataset_cfg, generate_cfg, c
                     optimizer.reset_ema()
                     print(f"checkpoint {ckpt_iter} holds no ema_state_dict: the EMA starts from the loaded weights")
             print(f"Successfully loaded model at iteration {ckpt_iter}")
-        except PriorMismatch:    # (not a checkpoint that failed to load: a run that would silently change its loss)
+        except (PriorMismatch, PqmfMismatch):    # (not a checkpoint that failed to load: a run that would silently change its loss)
             raise
         except Exception as e:   # the reference swallows the error the same way (`train.py:115-117`)
             print(f"Model checkpoint found at iteration {ckpt_iter}, but was not successfully loaded ({e}) - "
@@ -359,7 +383,7 @@ def train(rank, num_gpus, diffusion_cfg, model_cfg, dataset_cfg, generate_cfg, c
                                                            **{k: prior_cfg[k] for k in PRIOR_KEYS})
                 loss = training_loss(net, loss_fn, audio, dh, mel_spec=mel, stft_weight=stft_cfg["weight"],
                                      stft_max_step=stft_cfg["max_step"], stft_resolutions=stft_cfg["resolutions"],
-                                     parts=parts, **more)
+                                     parts=parts, **more, **band)
             elif prior_cfg is not None:
                 from .mel import prior_std_from_mel
                 sigma = prior_std_from_mel(mel, prior_h, audio.shape[-1],
@@ -367,9 +391,10 @@ def train(rank, num_gpus, diffusion_cfg, model_cfg, dataset_cfg, generate_cfg, c
                 more = dict(labels=data[2], label_dropout=label_dropout) if n_classes else {}
                 loss = training_loss(net, loss_fn, audio, dh, mel_spec=mel, prior_std=sigma, **more)
             elif n_classes:    # (the labels stay on the host: the engine takes them from there, nothing waits for the GPU)
-                loss = training_loss(net, loss_fn, audio, dh, mel_spec=mel, labels=data[2], label_dropout=label_dropout)
+                loss = training_loss(net, loss_fn, audio, dh, mel_spec=mel, labels=data[2], label_dropout=label_dropout,
+                                     **band)
             else:
-                loss = training_loss(net, loss_fn, audio, dh, mel_spec=mel)
+                loss = training_loss(net, loss_fn, audio, dh, mel_spec=mel, **band)
             reduced_loss = reduce_tensor(loss.data, num_gpus).item() if num_gpus > 1 else loss.item()
             loss.backward()
             optimizer.step()
@@ -391,6 +416,8 @@ def train(rank, num_gpus, diffusion_cfg, model_cfg, dataset_cfg, generate_cfg, c
                     saved["prior"] = dict(prior_cfg)
                 if stft_cfg is not None:        # (informational: what the loss of these weights held)
                     saved["stft_loss"] = dict(stft_cfg)
+                if pqmf_cfg is not None:        # (generate synthesises with the bank the weights were trained on)
+                    saved["pqmf"] = dict(pqmf_cfg)
                 torch.save(saved, os.path.join(checkpoint_directory, f"{n_iter}.pkl"))
                 print(f"model at iteration {n_iter} is saved")
                 if generate_cfg and generate_cfg.get("n_samples", 0):

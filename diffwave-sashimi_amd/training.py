@@ -96,7 +96,7 @@ def stft_loss_options(stft_weight=None, stft_max_step=None, stft_resolutions=Non
 
 def training_loss(net, loss_fn, audio, diffusion_hyperparams, mel_spec=None, generator=None, labels=None,
                   label_dropout=0.0, prior_std=None, stft_weight=None, stft_max_step=None, stft_resolutions=None,
-                  parts=None):
+                  parts=None, pqmf=None):
     """``train.py:198-222``: ``t ~ U{0..T-1}``, ``z ~ N(0, I)``, ``loss_fn(net((x_t, t), mel), z)``.
     Steps and noise are drawn on the CPU generator exactly like the reference (then moved, through pinned staging
     buffers so the host does not stall), so a seeded call consumes the RNG stream in the same order.
@@ -128,8 +128,26 @@ def training_loss(net, loss_fn, audio, diffusion_hyperparams, mel_spec=None, gen
     to batch.  ``stft_resolutions``: (n_fft, hop, win) triples, default ``metrics.MR_STFT_RESOLUTIONS``; a clip too short
     for one is ``check_resolution``'s ValueError, raised before anything is drawn.  ``parts`` (a dict) receives the two
     detached device scalars ``eps`` (the base loss) and ``stft`` (aux).  Without ``stft_weight`` not one operation or
-    RNG draw changes."""
+    RNG draw changes.
+
+    ``pqmf`` (multi-band runs; a ``pqmf.PQMF`` of K sub-bands; not in the reference): ``audio`` stays the waveform
+    [B, 1, L]; its sub-bands ``pqmf.analysis(audio)`` [B, K, L / K] are what is noised and predicted by a ``net`` of K
+    channels, everything else being the call above on the sub-bands -- a seeded call equals the one that is handed
+    ``pqmf.analysis(audio)`` as its audio, bit for bit.  With ``stft_weight`` the spectral term stays a full-band one,
+    ``mr_stft_loss(pqmf.synthesis(x0_hat), audio)``: its gradient reaches eps_theta through the synthesis bank's adjoint.
+    ``prior_std`` with ``pqmf`` is a ValueError (sigma is a full-band quantity; its sub-band form is not built).  Without
+    ``pqmf`` not one operation changes."""
     T, Alpha_bar = diffusion_hyperparams["T"], diffusion_hyperparams["Alpha_bar"]
+    full = None
+    if pqmf is not None:
+        if prior_std is not None:
+            raise ValueError("training_loss: pqmf does not combine with prior_std (the adaptive prior is a full-band "
+                             "quantity; its sub-band form is not built)")
+        if not isinstance(audio, torch.Tensor) or audio.dim() != 3:
+            raise ValueError(f"training_loss: with pqmf the audio is the waveform [B, 1, L] (got "
+                             f"{tuple(getattr(audio, 'shape', ()))!r})")
+        pqmf.check_analysis_input(audio, "training_loss (pqmf)")
+        full = audio
     B, C, L = audio.shape
     stft = stft_loss_options(stft_weight, stft_max_step, stft_resolutions, T)
     if stft is not None:
@@ -141,6 +159,8 @@ def training_loss(net, loss_fn, audio, diffusion_hyperparams, mel_spec=None, gen
             raise ValueError("training_loss: parts must be a dict")
     if prior_std is not None:
         prior_std = _check_prior_std(prior_std, audio)
+    if pqmf is not None:
+        audio = pqmf.analysis(full.detach())        # [B, K, L / K]: what the network sees
     diffusion_steps = _stage(torch.randint(T, size=(B, 1, 1), generator=generator), audio.device, "steps")
     z = _stage(torch.normal(0, 1, size=audio.shape, generator=generator), audio.device, "z")
     if prior_std is not None:
@@ -163,7 +183,10 @@ def training_loss(net, loss_fn, audio, diffusion_hyperparams, mel_spec=None, gen
     from .metrics import mr_stft_loss
     ab = _alpha_bar(Alpha_bar, audio.device)[diffusion_steps]
     x0_hat = (x_t - torch.sqrt(1 - ab) * epsilon_theta) / torch.sqrt(ab)
-    per_clip = mr_stft_loss(x0_hat, audio.detach(), resolutions=stft["resolutions"])
+    if pqmf is not None:
+        per_clip = mr_stft_loss(pqmf.synthesis(x0_hat), full.detach(), resolutions=stft["resolutions"])
+    else:
+        per_clip = mr_stft_loss(x0_hat, audio.detach(), resolutions=stft["resolutions"])
     if stft["max_step"] is not None:
         per_clip = per_clip * (diffusion_steps.view(B) < stft["max_step"]).to(per_clip.dtype)
     aux = per_clip.sum() / B

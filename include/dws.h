@@ -758,6 +758,30 @@ int dws_pitch_distance(const float* x, const float* y, int64_t B, int64_t T, con
 /* Bytes of dws_pitch_distance's workspace; 0 for a shape it refuses. */
 int64_t dws_pitch_distance_workspace(int64_t B, int64_t T, int32_t hop);
 
+/* Pseudo-QMF filter bank of multi-band runs (Multi-band MelGAN, Yang et al. 2020; not in the reference).  Both entries
+ * take the filter table filt [K][taps + 1] (DEVICE, float32; designed by the caller) and a gain, so that each also serves
+ * as the other's adjoint.  K is 2 or 4, taps is even and in 2 .. 254, h = taps / 2.
+ *
+ * Analysis: x [B][T] -> out [B][K][T/K] (all DEVICE float32), T a positive multiple of K,
+ *     out[b][k][t] = gain sum_{n=0}^{taps} filt[k][n] x[b][K t + n - h]              (x read as 0 outside [0, T))
+ * Synthesis: s [B][K][Ts] -> out [B][K Ts], Ts >= 1,
+ *     out[b][u] = gain sum_k sum_n filt[k][n] s[b][k][q]      over the n in 0 .. taps with u + n - h = K q, 0 <= q < Ts
+ * (the polyphase form: about taps + 1 products per output sample; nothing is zero-stuffed).
+ * Adjoints (rev(f)[k][n] = f[k][taps - n]): the adjoint of analysis (f, gain g) is synthesis (rev(f), g); the adjoint of
+ * synthesis (f, g) is analysis (rev(f), g).
+ * Order of summation: fp32 fmaf from 0, n ascending (analysis); n ascending and k ascending within an n (synthesis); the
+ * gain multiplies the finished sum.  One workgroup per clip and tile of dws_pqmf_tile() full-band positions, no atomics:
+ * the result is bitwise reproducible and clip b's rows depend on clip b alone, not on B or b.  A position outside the clip enters
+ * its sum as an explicit product with 0, so zeros appended to every band of s change no output sample u < K Ts.
+ * DWS_ERR_INVALID: a null x / s, filt or out; K outside {2, 4}; taps odd or outside 2 .. 254; T not a positive multiple
+ * of K; Ts < 1; B outside 1 .. 65535. */
+int dws_pqmf_analysis(const float* x, int64_t B, int64_t T, const float* filt, int32_t K, int32_t taps, float gain,
+                      float* out, void* stream);
+int dws_pqmf_synthesis(const float* s, int64_t B, int64_t Ts, const float* filt, int32_t K, int32_t taps, float gain,
+                       float* out, void* stream);
+/* Full-band positions per workgroup of the two kernels (tests put shapes on both sides of it). */
+int dws_pqmf_tile(void);
+
 /* The arithmetic of precision="bf16x6" alone (accuracy tests; not a tuned GEMM): C[M][N] = A[M][K] . B[K][N], row-major
  * fp32 device tensors, every operand split into three bf16 terms in registers, six bf16 MFMA products per term pair
  * accumulated in fp32 -- exactly what the bf16x6 layer kernels execute per k-block.  M, N multiples of 32, K of 16. */
