@@ -88,9 +88,14 @@ inline int wn_split_terms(int split) { return split == WN_SPLIT_F16X3 ? 2 : 3; }
 //   WN_BX6_MFMA_32: v_mfma_f32_32x32x16_bf16 throughout;  WN_BX6_MFMA_G2_16: GEMM2 on v_mfma_f32_16x16x32_bf16;  WN_BX6_MFMA_16: both GEMMs
 enum { WN_BX6_MFMA_32 = 0, WN_BX6_MFMA_G2_16 = 1, WN_BX6_MFMA_16 = 2 };
 constexpr int WN_BX6_MFMA_DEFAULT = WN_BX6_MFMA_16;   // what the A/B decided (profiles/r08_ab_bx6_mfma_shape.txt)
+// Ring of GEMM1's A fragments in the both-GEMM 16x16x32 kernel (ignored wherever another kernel runs: mfma != WN_BX6_MFMA_16 or
+// !wn_layer_bx6_mfma16_supported):  WN_BX6_A_RING_HALF: six fragments one half-step (24 MFMAs) ahead;  WN_BX6_A_RING_QUARTER: three
+// fragments three quarter-steps (36 MFMAs) ahead in the same registers.  Equal bits.
+enum { WN_BX6_A_RING_HALF = 0, WN_BX6_A_RING_QUARTER = 1 };
+constexpr int WN_BX6_A_RING_DEFAULT = WN_BX6_A_RING_QUARTER;   // what the A/Bs decided (profiles/r10_ab_bx6_a_ring.txt)
 bool wn_layer_bx6_supported(int C, int S);
 bool wn_layer_bx6_mfma16_supported(int C, int S, int split);
-int launch_wn_layer_bx6(int C, int S, const WnLayerArgs& a, int split, int mfma, hipStream_t s);
+int launch_wn_layer_bx6(int C, int S, const WnLayerArgs& a, int split, int mfma, int a_ring, hipStream_t s);
 int launch_weight_scale(const float* w, size_t n, const float* bias, int nb, const float* bias_b, int nb_b, float* out, hipStream_t s);   // power of two bringing max(|w|, |bias|/1024) into [1, 2)
 int launch_pack_a1_bx6(const float* w, void* out, int C, int split, const float* scale, hipStream_t s);        // folded [2C][C][3] -> G0..G3 fragments
 int launch_pack_a_bx6(const float* w, void* out, int M, int K, int split, const float* scale, hipStream_t s);  // row-major [M][K] -> fragments

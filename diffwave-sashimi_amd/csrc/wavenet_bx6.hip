@@ -45,6 +45,14 @@
 // the chip is power-capped under this kernel and holds 1970 instead of 1838 MHz on it (profiles/r08_ab_bx6_mfma_shape.txt).
 // "gemm2-16x16x32": GEMM2 and the epilogue only (measured: a third of the gain).  "32x32x16": the code as it was, instruction for instruction.
 //
+// A ring of the 16x16x32 GEMM1 (template parameter AR; set_option("bx6_a_ring") / DWS_BX6_A_RING; no other instance has the parameter's
+// second value).  "quarter-step", the default: a half-step runs as its two row halves (disjoint fragments, disjoint accumulators), 12 MFMAs
+// on two alternating accumulators each, and the 48 fragment registers are a ring of four sets of three, each requested three quarter-steps =
+// 36 MFMAs ahead of its use where "half-step" (the code as it was, instruction for instruction) requests six fragments one half-step = 24
+// MFMAs ahead.  Same fragments, L2 bytes, MFMAs and registers; every accumulator keeps its order of summation, so the bits are equal
+// (tests/test_bx6_a_ring_gpu.py).  A wave that runs a stretch of a chunk alone goes at the pace of its A-fragment round trips: chunk period
+// 8.8 k -> 8.3 k cycles, tile span - 3.0 %, - 1.2 % of the step (profiles/r10_ab_bx6_a_ring.txt, r10_bx6_a_ring_trace.txt).
+//
 // Work per launch at C = S = 256, B = 16, L = 16000: 204.5 GFLOP of fp32-equivalent GEMM (the f32 Winograd kernel's
 // executed flops) = 1.227 PFLOP of bf16 MFMA = 0.49 ms at 2.5 PFLOP/s, against 1.30 ms at the fp32 matrix rate.
 #include <cstdlib>
@@ -231,6 +239,13 @@ enum { BX6_MF_32 = 0, BX6_MF_G2_16 = 1, BX6_MF_16 = 2 };
 #ifndef BX6_T16_SLOTS
 #define BX6_T16_SLOTS 1, 5, 7, 9, 13, 15, 19   // 16x16x32 GEMM1: the MFMA (of 24) of a chunk's first half-step behind which each transform unit stands
 #endif
+// AR: the ring of GEMM1's A fragments on the 16x16x32 shape (set_option("bx6_a_ring") / DWS_BX6_A_RING; nothing in any other instance).
+//   BX6_AR_HALF: two sets of six fragments (row halves h = 0, 1 x three terms), requested one half-step = 24 MFMAs ahead;
+//   BX6_AR_QUARTER: the same 48 registers as four sets of three (one row half), requested BX6_A_LEAD quarter-steps of 12 MFMAs ahead.
+enum { BX6_AR_HALF = 0, BX6_AR_QUARTER = 1 };
+#ifndef BX6_A_LEAD
+#define BX6_A_LEAD 3   // quarter-step ring: lead of an A-fragment request over its first use, in quarter-steps (1..3: the set of quarter q + 4 is still in use)
+#endif
 struct Bx6Nothing {};
 // state of the 16x16x32 GEMM2 (nothing at all in a 32x32x16 instance, so that those compile to the code they had)
 template <int MS>
@@ -249,6 +264,12 @@ __device__ __forceinline__ void bx6_load_a1h(V8 (&dst)[2][NT], __amdgpu_buffer_r
 #pragma unroll
         for (int t = 0; t < NT; ++t) dst[h][t] = __builtin_bit_cast(V8, __builtin_amdgcn_raw_buffer_load_b128(r, voff + h * 256, soff + t * 1024, 0));
 }
+// the three A fragments of a GEMM1 quarter-step (row tile, product, row half h): [term], voff = bx6_voff_a1h + h * 256
+template <typename V8, int NT>
+__device__ __forceinline__ void bx6_load_a1q(V8 (&dst)[NT], __amdgpu_buffer_rsrc_t r, int voff, int soff) {
+#pragma unroll
+    for (int t = 0; t < NT; ++t) dst[t] = __builtin_bit_cast(V8, __builtin_amdgcn_raw_buffer_load_b128(r, voff, soff + t * 1024, 0));
+}
 // state of the 16x16x32 GEMM1
 template <typename V8, int NT>
 struct Bx6G1State {
@@ -256,12 +277,16 @@ struct Bx6G1State {
     // [m][h].  Dead once the start values are formed (ahead of the first chunk barrier).
     bx_f32x4 av[2][2][4], ab[2][2];
     bx_f32x4 acc[2][4][2][2];           // [row tile m][product j][row half h][column half c]
-    V8 ar[2][2][NT];                    // A fragments, ring over the half-steps: [half-step & 1][h][term]
+    // A fragments.  BX6_AR_HALF: ring over the half-steps, [half-step & 1][h][term].  BX6_AR_QUARTER: the same registers as a ring
+    // of four sets over the quarter-steps, set s = quarter & 3 is [s >> 1][s & 1][term].
+    V8 ar[2][2][NT];
 };
-template <typename P, int C, int S, bool EXTRA, int MF = BX6_MF_32>
+template <typename P, int C, int S, bool EXTRA, int MF = BX6_MF_32, int AR = BX6_AR_HALF>
 __global__ __launch_bounds__(C * 2, (C >= 128 ? 2 : 1)) void wn_layer_bx6_kernel(WnLayerArgs a, int log2d) {
     using T = Bx6Tile<C, S, P::NT>;
     static_assert(MF == BX6_MF_32 || (P::NT == 3 && !P::SCALED && C == 256 && S == 256), "the 16x16x32 shape: bf16 split, C = S = 256");
+    static_assert(AR == BX6_AR_HALF || MF >= BX6_MF_16, "the quarter-step A ring belongs to the 16x16x32 GEMM1");
+    static_assert(BX6_A_LEAD >= 1 && BX6_A_LEAD <= 3, "quarter-step ring of four sets: a lead of four would request into the set in use");
     using v8 = typename P::v8;
     using v4 = typename P::v4;
     constexpr int NT = P::NT, NPR = P::NP, NA = 2 * P::NT;   // terms, products per term pair, A fragments per GEMM1 step
@@ -520,6 +545,13 @@ __global__ __launch_bounds__(C * 2, (C >= 128 ? 2 : 1)) void wn_layer_bx6_kernel
                 dst[m][t] = __builtin_bit_cast(v8, __builtin_amdgcn_raw_buffer_load_b128(rA1, lane16, (((mt1[m] * NKB + kb) * 4 + j) * NT + t) * 1024, 0));
 #endif
     };
+    // quarter-step ring (AR == BX6_AR_QUARTER): request the three fragments of quarter-step qq = 4 j + 2 m + h of the chunk with
+    // loop index cbi into set qq & 3 -- bx6_load_a1h's addressing for the one row half h
+    [[maybe_unused]] auto req_a1q = [&](int cbi, int qq) __attribute__((always_inline)) {
+        if constexpr (MF >= BX6_MF_16)
+            bx6_load_a1q<v8, NT>(gs1.ar[(qq >> 1) & 1][qq & 1], rA1, bx6_voff_a1h<NT>(lane) + (qq & 1) * 256,
+                                 ((mt1[(qq >> 1) & 1] * NKB + 2 * chunk_of(cbi)) * 4 + (qq >> 2)) * NT * 1024);
+    };
 
     if constexpr (MF >= BX6_MF_16) {
         // 16x16x32: the first half-step's six A fragments (product 0 of row tile 0 -- bx6_load_a1h) are requested AHEAD of the
@@ -528,7 +560,14 @@ __global__ __launch_bounds__(C * 2, (C >= 128 ? 2 : 1)) void wn_layer_bx6_kernel
         // form: the wait in front of the start values (below) leaves those outstanding and does not wait for the staged x.
         static_assert(T::HALVES && NCB > 1 && BX6_PF(NT) == 1 && KC == 32,
                       "a wave stages chunk 0 or chunk 1; one half-step of six fragments ahead: NAF and the chunk loop's vmcnt counts as in the 32x32x16 form");
+        if constexpr (AR == BX6_AR_QUARTER) {
+            // quarter-step ring: the sets of the first BX6_A_LEAD quarter-steps of chunk 0 (three fragments each), all of them
+            // ahead of the pieces -- the same order of ages: correction rows, L2-served fragments (nine instead of six), pieces
+#pragma unroll
+            for (int qq = 0; qq < BX6_A_LEAD; ++qq) req_a1q(0, qq);
+        } else {
         bx6_load_a1h<v8, NT>(gs1.ar[0], rA1, bx6_voff_a1h<NT>(lane), ((mt1[0] * NKB + 2 * chunk_of(0)) * 4 + 0) * NT * 1024);
+        }
         stage_dma(shalf);
     } else {
     if (stages(0)) stage_dma(0);
@@ -558,7 +597,7 @@ __global__ __launch_bounds__(C * 2, (C >= 128 ? 2 : 1)) void wn_layer_bx6_kernel
         // transform of the in-range indicator of the four shifts (exact small integers, per column half), plus the conv bias in
         // product 1 (m1 enters both outputs of a pair with +1) -- is a rank-1 fp32 expression per register, one rounding each.
         // The rows were the kernel's first requests (vmcnt retires in order: the compiler's waits in front of these FMAs count
-        // the six A fragments behind them and leave the younger LDS-DMA pieces alone), so this runs under the first staging
+        // the six A fragments -- quarter-step ring: nine -- behind them and leave the younger LDS-DMA pieces alone), so this runs under the first staging
         // wait and not behind the chunk barrier.
         float bi[2][4];
 #pragma unroll
@@ -721,6 +760,96 @@ __global__ __launch_bounds__(C * 2, (C >= 128 ? 2 : 1)) void wn_layer_bx6_kernel
         const int voffa = bx6_voff_a1h<NT>(lane);
         constexpr int T16_SLOTS[T_UNITS] = {BX6_T16_SLOTS};
         v8 bq[2][NT], bq0[2][2];   // [column half][term] (terms 1, 2); term 0: [product & 1][column half]
+        if constexpr (AR == BX6_AR_QUARTER) {
+        // Quarter-step ring.  The two row halves h of a half-step use disjoint fragments and disjoint accumulators, so the half-step
+        // runs as two quarter-steps (h outer, then t, then c: 12 MFMAs on two alternating accumulators), a quarter-step needs three
+        // fragments, and the 48 registers hold four sets.  Quarter-step q = 4 j + 2 m + h (sixteen per chunk) requests the set of quarter-step
+        // q + BX6_A_LEAD (the last BX6_A_LEAD of a chunk: of the next chunk's first ones) into set (q + BX6_A_LEAD) & 3, last read
+        // 4 - BX6_A_LEAD quarter-steps ago: a request leads its first use by 12 BX6_A_LEAD MFMAs (36 = 576 matrix-pipe cycles of
+        // the wave's own work against 24 = 384 of the half-step ring) at the same registers, L2 bytes and MFMA count.  Every
+        // accumulator receives its start value, the chunks and the products in the order of the half-step ring: equal bits.
+        // B side: the six fragments of a product serve its four quarter-steps; the refills behind a term's last use and the
+        // alternate term-0 set stand in the product's last quarter-step (m = 1, h = 1), where the registers come free.
+        // The transform units ride in quarter-steps 0 and 1 (T16_SLOTS counts MFMAs across both), the residual copy stands ahead
+        // of quarter-step 4.
+        constexpr int LEAD = BX6_A_LEAD, QPC = 16;   // quarter-steps per chunk: four products x two row tiles x two row halves
+        auto do_quarter = [&](int cb, auto QS, auto WITH_T, TState& ts) __attribute__((always_inline)) {
+            constexpr int qs = decltype(QS)::value, j = qs >> 2, m = (qs >> 1) & 1, h = qs & 1;
+            constexpr bool ride = decltype(WITH_T)::value;
+            constexpr bool lastq = m == 1 && h == 1;
+            const char* tb = Bop + (cb & 1) * T::BOP_BYTES + oct * (4 * NT * 512) + r16 * 16;
+            if (qs == 4 && cb + 1 < NCB) keep_residual(cb + 1);
+            // (fenced on both sides: with LEAD = 3 the request overwrites the set the previous quarter-step's MFMAs read, and a request
+            // moved up between those would need three more registers per fragment)
+            __builtin_amdgcn_sched_barrier(0);
+            if (qs + LEAD < QPC) req_a1q(cb, qs + LEAD);
+            else if (cb + 1 < NCB) req_a1q(cb + 1, qs + LEAD - QPC);   // (no load left in flight behind the last chunk)
+            __builtin_amdgcn_sched_barrier(0);   // keep the prefetch LEAD whole quarter-steps ahead of its use
+            if (qs == 0) {   // (a chunk's first fragments cannot be asked for before the chunk barrier)
+#pragma unroll
+                for (int t = 0; t < NT; ++t)
+#pragma unroll
+                    for (int c = 0; c < 2; ++c) (t ? bq[c][t] : bq0[0][c]) = *reinterpret_cast<const v8*>(tb + (j * NT + t) * 512 + c * 256);
+            }
+            if (lastq && j < 3) {   // term 0 of the next product: needed by its first MFMA, so it has a register set of its own
+#pragma unroll
+                for (int c = 0; c < 2; ++c) bq0[(j + 1) & 1][c] = *reinterpret_cast<const v8*>(tb + ((j + 1) * NT) * 512 + c * 256);
+            }
+#pragma unroll
+            for (int t = 0; t < NPR; ++t) {
+#pragma unroll
+                for (int c = 0; c < 2; ++c) {
+                    gs1.acc[m][j][h][c] = P::mfma16(gs1.ar[m][h][P::ia(t)], P::ib(t) ? bq[c][P::ib(t)] : bq0[j & 1][c], gs1.acc[m][j][h][c]);
+                    if (ride) {
+                        const int i = 12 * qs + 2 * t + c;
+#pragma unroll
+                        for (int u = 0; u < T_UNITS; ++u)
+                            if (T16_SLOTS[u] == i) transform_unit(cb + 1, u, ts);
+                        __builtin_amdgcn_sched_barrier(0);
+                    }
+                }
+                if (lastq && j < 3 && (t == 2 || t == 4)) {   // the next product's fragments of the term that has just had its last use
+                    const int term = (t == 2) ? 2 : 1;
+#pragma unroll
+                    for (int c = 0; c < 2; ++c) bq[c][term] = *reinterpret_cast<const v8*>(tb + ((j + 1) * NT + term) * 512 + c * 256);
+                }
+            }
+        };
+        for (int cb = 0; cb < NCB; ++cb) {
+            if (cb + 2 < NCB && stages(cb + 2)) stage_dma(cb + 2);
+            TState ts;
+            if (cb + 1 < NCB) {
+                do_quarter(cb, std::integral_constant<int, 0>{}, std::true_type{}, ts);
+                do_quarter(cb, std::integral_constant<int, 1>{}, std::true_type{}, ts);
+            } else {
+                do_quarter(cb, std::integral_constant<int, 0>{}, std::false_type{}, ts);
+                do_quarter(cb, std::integral_constant<int, 1>{}, std::false_type{}, ts);
+            }
+            do_quarter(cb, std::integral_constant<int, 2>{}, std::false_type{}, ts);
+            do_quarter(cb, std::integral_constant<int, 3>{}, std::false_type{}, ts);
+            do_quarter(cb, std::integral_constant<int, 4>{}, std::false_type{}, ts);
+            do_quarter(cb, std::integral_constant<int, 5>{}, std::false_type{}, ts);
+            do_quarter(cb, std::integral_constant<int, 6>{}, std::false_type{}, ts);
+            do_quarter(cb, std::integral_constant<int, 7>{}, std::false_type{}, ts);
+            do_quarter(cb, std::integral_constant<int, 8>{}, std::false_type{}, ts);
+            do_quarter(cb, std::integral_constant<int, 9>{}, std::false_type{}, ts);
+            do_quarter(cb, std::integral_constant<int, 10>{}, std::false_type{}, ts);
+            do_quarter(cb, std::integral_constant<int, 11>{}, std::false_type{}, ts);
+            do_quarter(cb, std::integral_constant<int, 12>{}, std::false_type{}, ts);
+            do_quarter(cb, std::integral_constant<int, 13>{}, std::false_type{}, ts);
+            do_quarter(cb, std::integral_constant<int, 14>{}, std::false_type{}, ts);
+            do_quarter(cb, std::integral_constant<int, 15>{}, std::false_type{}, ts);
+            stamp(8 + 2 * cb);
+            // The LDS-DMA of chunk cb + 2 (requested at the top of this iteration) has landed: younger than the pieces are only
+            // the 3 BX6_A_LEAD fragments of the next chunk's first quarter-steps -- every older fragment of this chunk has been
+            // waited for by the MFMAs that read it.  (Last chunk: nothing is in flight.)  The count must stay below 16: this form
+            // of the immediate carries only the counter's low four bits.
+            static_assert(3 * LEAD < 16, "vmcnt immediate: low four bits only");
+            __builtin_amdgcn_s_waitcnt(0x0F70 | (NT * LEAD));
+            __syncthreads();
+            stamp(9 + 2 * cb);
+        }
+        } else {
         auto do_half = [&](int cb, auto HS, auto WITH_T) {
             constexpr int hs = decltype(HS)::value, j = hs >> 1, m = hs & 1;
             constexpr bool ride = decltype(WITH_T)::value;
@@ -777,6 +906,7 @@ __global__ __launch_bounds__(C * 2, (C >= 128 ? 2 : 1)) void wn_layer_bx6_kernel
             __builtin_amdgcn_s_waitcnt(0x0F70 | NAF);   // (as below: the LDS-DMA of chunk cb + 2 has landed, only the next half-step's A fragments are younger)
             __syncthreads();
             stamp(9 + 2 * cb);
+        }
         }
     } else {
     for (int cb = 0; cb < NCB; ++cb) {
@@ -1209,7 +1339,7 @@ __global__ __launch_bounds__(C * 2, (C >= 128 ? 2 : 1)) void wn_layer_bx6_kernel
     }
 }
 
-template <typename P, int C, int S, int MF = BX6_MF_32>
+template <typename P, int C, int S, int MF = BX6_MF_32, int AR = BX6_AR_HALF>
 static int launch_bx6_t(const WnLayerArgs& a, int log2d, hipStream_t s) {
     ProfileScope ps(P::NT == 3 ? "wn_layer_bx6" : "wn_layer_f16x3", s);
     using T = Bx6Tile<C, S, P::NT>;
@@ -1220,12 +1350,12 @@ static int launch_bx6_t(const WnLayerArgs& a, int log2d, hipStream_t s) {
     static const bool trace = std::getenv("DWS_BX6_TRACE") != nullptr;
     if (trace && !a.melc && !a.hsave) {
         wino_trace_launch(ntiles, T::WAVES, a, s, [&](const WnLayerArgs& at) {
-            hipLaunchKernelGGL((wn_layer_bx6_kernel<P, C, S, false, MF>), dim3(ntiles), dim3(T::NTH), 0, s, at, log2d);
+            hipLaunchKernelGGL((wn_layer_bx6_kernel<P, C, S, false, MF, AR>), dim3(ntiles), dim3(T::NTH), 0, s, at, log2d);
         }, P::NT == 3 ? "bx6" : "f16x3");
         return DWS_OK;
     }
-    if (a.melc || a.hsave) hipLaunchKernelGGL((wn_layer_bx6_kernel<P, C, S, true, MF>), dim3(ntiles), dim3(T::NTH), 0, s, a, log2d);
-    else hipLaunchKernelGGL((wn_layer_bx6_kernel<P, C, S, false, MF>), dim3(ntiles), dim3(T::NTH), 0, s, a, log2d);
+    if (a.melc || a.hsave) hipLaunchKernelGGL((wn_layer_bx6_kernel<P, C, S, true, MF, AR>), dim3(ntiles), dim3(T::NTH), 0, s, a, log2d);
+    else hipLaunchKernelGGL((wn_layer_bx6_kernel<P, C, S, false, MF, AR>), dim3(ntiles), dim3(T::NTH), 0, s, a, log2d);
     return DWS_OK;
 }
 
@@ -1244,7 +1374,7 @@ static int launch_bx6_p(int C, int S, const WnLayerArgs& a, int log2d, hipStream
     return set_error(DWS_ERR_UNSUPPORTED, "wn_layer_bx6: (C=%d,S=%d) not instantiated", C, S);
 }
 
-int launch_wn_layer_bx6(int C, int S, const WnLayerArgs& a, int split, int mfma, hipStream_t s) {
+int launch_wn_layer_bx6(int C, int S, const WnLayerArgs& a, int split, int mfma, int a_ring, hipStream_t s) {
     int log2d = 0;
     while ((1 << log2d) < a.dilation) ++log2d;
     DWS_CHECK((1 << log2d) == a.dilation, DWS_ERR_UNSUPPORTED, "wn_layer_bx6: dilation %d is not a power of two", a.dilation);
@@ -1265,7 +1395,12 @@ int launch_wn_layer_bx6(int C, int S, const WnLayerArgs& a, int split, int mfma,
     }
     // the 16x16x32 shape exists for the instances it was measured on; every other instance has one shape and keeps it
     if (mfma == WN_BX6_MFMA_G2_16 && wn_layer_bx6_mfma16_supported(C, S, split)) return launch_bx6_t<SplitBf16x3, 256, 256, BX6_MF_G2_16>(a, log2d, s);
-    if (mfma == WN_BX6_MFMA_16 && wn_layer_bx6_mfma16_supported(C, S, split)) return launch_bx6_t<SplitBf16x3, 256, 256, BX6_MF_16>(a, log2d, s);
+    // the A ring is a property of the 16x16x32 GEMM1: every other kernel has no such ring and runs whatever a_ring says
+    DWS_CHECK(a_ring == WN_BX6_A_RING_HALF || a_ring == WN_BX6_A_RING_QUARTER, DWS_ERR_INVALID, "wn_layer_bx6: unknown A ring %d", a_ring);
+    if (mfma == WN_BX6_MFMA_16 && wn_layer_bx6_mfma16_supported(C, S, split)) {
+        if (a_ring == WN_BX6_A_RING_QUARTER) return launch_bx6_t<SplitBf16x3, 256, 256, BX6_MF_16, BX6_AR_QUARTER>(a, log2d, s);
+        return launch_bx6_t<SplitBf16x3, 256, 256, BX6_MF_16>(a, log2d, s);
+    }
     DWS_CHECK(mfma == WN_BX6_MFMA_32 || mfma == WN_BX6_MFMA_G2_16 || mfma == WN_BX6_MFMA_16, DWS_ERR_INVALID, "wn_layer_bx6: unknown MFMA shape %d", mfma);
     return launch_bx6_p<SplitBf16x3>(C, S, a, log2d, s);
 }

@@ -27,6 +27,14 @@ struct WaveNetModel : dws_model {
         if (v == "16x16x32") { out = WN_BX6_MFMA_16; return true; }
         return false;
     }
+    // bx6_a_ring option (initial value: DWS_BX6_A_RING): ring of GEMM1's A fragments in the 16x16x32 kernel; no effect on any other
+    int bx6_a_ring = WN_BX6_A_RING_DEFAULT;
+    bool bx6_a_ring_env_bad = false;   // DWS_BX6_A_RING held no known value: commit reports it
+    static bool parse_bx6_a_ring(const std::string& v, int& out) {
+        if (v == "half-step") { out = WN_BX6_A_RING_HALF; return true; }
+        if (v == "quarter-step") { out = WN_BX6_A_RING_QUARTER; return true; }
+        return false;
+    }
     // the Winograd launcher addresses a clip's [C][L] tensor through one 32-bit buffer descriptor: over-long clips
     // (L >= ~2.1 M samples at C = 256) stay on the direct kernel, which has no such bound.  prepare() marks the model
     // dirty when the answer flips (the A1 / Abt layouts follow the choice).
@@ -85,6 +93,7 @@ struct WaveNetModel : dws_model {
         mfma_final = wn_final_mfma_supported(S);
         if (std::getenv("DWS_WN_DIRECT")) wino_opt = false;
         if (const char* e = std::getenv("DWS_BX6_MFMA")) bx6_mfma_env_bad = !parse_bx6_mfma(e, bx6_mfma);
+        if (const char* e = std::getenv("DWS_BX6_A_RING")) bx6_a_ring_env_bad = !parse_bx6_a_ring(e, bx6_a_ring);
         auto wn = [&](const std::string& p, std::vector<int64_t> vshape) {
             std::vector<int64_t> g(vshape.size(), 1);
             g[0] = vshape[0];
@@ -157,6 +166,12 @@ struct WaveNetModel : dws_model {
             bx6_mfma = v; bx6_mfma_env_bad = false; dirty = true; trained_fwd = false;
             return DWS_OK;
         }
+        if (key == "bx6_a_ring") {
+            int v = 0;
+            DWS_CHECK(parse_bx6_a_ring(value, v), DWS_ERR_INVALID, "bx6_a_ring: half-step | quarter-step, not '%s'", value.c_str());
+            bx6_a_ring = v; bx6_a_ring_env_bad = false; dirty = true; trained_fwd = false;
+            return DWS_OK;
+        }
         return dws_model::set_option(key, value);
     }
 
@@ -168,6 +183,7 @@ struct WaveNetModel : dws_model {
 
     int commit(hipStream_t s) override {
         DWS_CHECK(!bx6_mfma_env_bad, DWS_ERR_INVALID, "DWS_BX6_MFMA: 32x32x16 | gemm2-16x16x32 | 16x16x32, not '%s'", std::getenv("DWS_BX6_MFMA") ? std::getenv("DWS_BX6_MFMA") : "");
+        DWS_CHECK(!bx6_a_ring_env_bad, DWS_ERR_INVALID, "DWS_BX6_A_RING: half-step | quarter-step, not '%s'", std::getenv("DWS_BX6_A_RING") ? std::getenv("DWS_BX6_A_RING") : "");
         DWS_TRY(Wi.ensure((size_t)C * Cin * 4));
         DWS_TRY(fold("init_conv.0.conv", Wi.f(), C, Cin, s));
         DWS_TRY(Wt_all.ensure((size_t)NL * C * Eout * 4));
@@ -599,8 +615,8 @@ struct WaveNetModel : dws_model {
             a.dilation = 1 << (n % cycle);
             a.first_layer = (n == 0); a.last_layer = (n == NL - 1);
             if (mfma_layer && bf16x3) DWS_TRY(launch_wn_layer_bf16x3(C, S, a, s));
-            else if (bf16x6) DWS_TRY(launch_wn_layer_bx6(C, S, a, WN_SPLIT_BF16X6, bx6_mfma, s));
-            else if (f16x3) { a.wscale = wscale.f() + 2 * n; DWS_TRY(launch_wn_layer_bx6(C, S, a, WN_SPLIT_F16X3, WN_BX6_MFMA_32, s)); }
+            else if (bf16x6) DWS_TRY(launch_wn_layer_bx6(C, S, a, WN_SPLIT_BF16X6, bx6_mfma, bx6_a_ring, s));
+            else if (f16x3) { a.wscale = wscale.f() + 2 * n; DWS_TRY(launch_wn_layer_bx6(C, S, a, WN_SPLIT_F16X3, WN_BX6_MFMA_32, WN_BX6_A_RING_HALF, s)); }
             else if (wino()) DWS_TRY(launch_wn_layer_wino(C, S, a, s));
             else if (mfma_layer) DWS_TRY(launch_wn_layer_mfma(C, S, a, s));
             else DWS_TRY(launch_wn_layer_generic(C, S, a, s));

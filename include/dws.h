@@ -165,7 +165,11 @@ int dws_model_update_params(dws_model* m, int32_t count, const char* const* name
  *                          res_channels = skip_channels = 256: both GEMMs of the layer kernel on v_mfma_f32_16x16x32_bf16 (the
  *                          chip holds a higher clock on it); same error class, last bits differ from "32x32x16"
  *              = "gemm2-16x16x32" only the [res; skip] GEMM and the epilogue on that shape
- *              = "32x32x16" the v_mfma_f32_32x32x16_bf16 kernel (every other width runs it whatever this says). */
+ *              = "32x32x16" the v_mfma_f32_32x32x16_bf16 kernel (every other width runs it whatever this says).
+ *   "bx6_a_ring" = "quarter-step" (default; initial value from the environment variable DWS_BX6_A_RING) the "16x16x32" kernel above:
+ *                          GEMM1's weight fragments are requested three at a time, three quarter-steps (36 MFMAs) ahead of their use
+ *                = "half-step" six at a time, one half-step (24 MFMAs) ahead: the kernel as it was.  The two give equal bits; the
+ *                          option has no effect where another kernel runs (bx6_mfma other than "16x16x32", other widths). */
 int dws_model_set_option(dws_model* m, const char* key, const char* value);
 
 /* Class conditioning (class-conditional generation; not in the reference).  Call after dws_model_create and before the
