@@ -150,6 +150,15 @@ _SIGS = {
     "dws_pqmf_synthesis": (ctypes.c_int, [c_f32p, ctypes.c_int64, ctypes.c_int64, c_f32p, ctypes.c_int32, ctypes.c_int32,
                                           ctypes.c_float, c_f32p, ctypes.c_void_p]),
     "dws_pqmf_tile": (ctypes.c_int, []),
+    "dws_resample": (ctypes.c_int, [c_f32p, ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p, ctypes.POINTER(ctypes.c_int32),
+                                    c_f32p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, c_f32p, ctypes.c_int64,
+                                    ctypes.c_void_p]),
+    "dws_resample_tile": (ctypes.c_int, []),
+    "dws_stoi": (ctypes.c_int, [c_f32p, c_f32p, ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p,
+                                ctypes.POINTER(ctypes.c_int32), c_f32p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, c_f32p,
+                                ctypes.c_int32, ctypes.c_int32, ctypes.c_double, ctypes.c_double, ctypes.c_void_p,
+                                ctypes.c_void_p, ctypes.c_void_p]),
+    "dws_stoi_workspace": (ctypes.c_int64, [ctypes.c_int64, ctypes.c_int64] + [ctypes.c_int32] * 3),
     "dws_gemm_bf16x6": (ctypes.c_int, [c_f32p] * 3 + [ctypes.c_int64] * 3 + [ctypes.c_void_p]),
     "dws_gemm_f16x3": (ctypes.c_int, [c_f32p] * 3 + [ctypes.c_int64] * 3 + [ctypes.c_float] * 2 + [ctypes.c_void_p]),
     "dws_profile_enable": (ctypes.c_int, [ctypes.c_char_p]),

@@ -18,6 +18,14 @@ composed config's ``dataset`` (``key=value`` overrides as for ``generate``), and
 the others.  ``f0_rmse`` / ``f0_cents`` / ``gpe`` of a pair with no frame voiced in both files, and ``vuv_f1`` of a pair
 without a voiced frame, are NaN: such a pair is left out of that metric's mean, and the ``n`` column counts the rest.  ``--json`` holds ``null``
 for such a value (strict JSON has no NaN) and the parameters under ``"pitch"``.
+
+``--stoi`` adds ``stoi`` and ``estoi`` (``metrics.stoi``: both files converted to 10 kHz on the GPU, Taal's constants):
+two more rows, printed last.  A pair that keeps fewer than 30 frames has neither; it is treated like an undefined pitch
+value (left out of the mean, ``null`` in ``--json``, the parameters under ``"stoi"``).
+
+``--resample``: a wav whose rate is not ``--sampling-rate`` is converted on the GPU after loading (``audio.resample``)
+instead of being refused; the one-hop pairing check and the trim see the converted clips, and the number of converted
+files is printed.
 """
 import argparse
 import json
@@ -61,6 +69,14 @@ def pair_files(generated_dir, reference_dir):
     return pairs, lone, sorted(ref - set(taken))
 
 
+def read_wav(path):
+    """``(x, sampling rate)``: a wav as float32 [T] -- int16 scaled by 1/32768, float as it is, the first channel -- at
+    whatever rate it has; ValueError on another sample type."""
+    from scipy.io import wavfile
+    sr, x = wavfile.read(path)
+    return _samples(path, x), int(sr)
+
+
 def load_wav(path, sampling_rate):
     """A wav as float32 [T]: int16 scaled by 1/32768, float as it is, the first channel; ValueError on another rate or
     sample type."""
@@ -68,6 +84,10 @@ def load_wav(path, sampling_rate):
     sr, x = wavfile.read(path)
     if sr != sampling_rate:
         raise ValueError(f"evaluate: {path} has sampling rate {sr}, expected {sampling_rate}")
+    return _samples(path, x)
+
+
+def _samples(path, x):
     if x.dtype == np.int16:
         x = x.astype(np.float32) / 32768.0
     elif x.dtype.kind == "f":
@@ -79,13 +99,31 @@ def load_wav(path, sampling_rate):
     return torch.from_numpy(np.ascontiguousarray(x))
 
 
-def load_pairs(generated_dir, reference_dir, pairs, sampling_rate, hop_length):
+def _load_converted(path, sampling_rate, converted):
+    """``--resample``: the wav at ``path``, converted to ``sampling_rate`` on the GPU (``audio.resample``) where it has
+    another rate; such a path is appended to ``converted``."""
+    from . import audio
+    x, sr = read_wav(path)
+    if sr == sampling_rate:
+        return x
+    audio.check_ratio(sr, sampling_rate, what=f"evaluate --resample ({path})")
+    converted.append(path)
+    return audio.resample(x[None].to("cuda" if torch.cuda.is_available() else "cpu"), sr, sampling_rate)[0][0].cpu()
+
+
+def load_pairs(generated_dir, reference_dir, pairs, sampling_rate, hop_length, converted=None):
     """The wavs of ``pairs`` as a list of ``(x, y)`` float32 [len] tensors, each trimmed to its shorter member; a pair
-    whose lengths differ by more than ``hop_length`` is not the same utterance (ValueError)."""
+    whose lengths differ by more than ``hop_length`` is not the same utterance (ValueError).  ``converted``: None -- a wav
+    at another rate than ``sampling_rate`` is a ValueError -- or a list: such a wav is converted on the GPU first (the
+    length check and the trim see the converted clips) and its path appended."""
     out = []
     for g, r in pairs:
-        x = load_wav(os.path.join(generated_dir, g + ".wav"), sampling_rate)
-        y = load_wav(os.path.join(reference_dir, r + ".wav"), sampling_rate)
+        if converted is None:
+            x = load_wav(os.path.join(generated_dir, g + ".wav"), sampling_rate)
+            y = load_wav(os.path.join(reference_dir, r + ".wav"), sampling_rate)
+        else:
+            x = _load_converted(os.path.join(generated_dir, g + ".wav"), sampling_rate, converted)
+            y = _load_converted(os.path.join(reference_dir, r + ".wav"), sampling_rate, converted)
         if abs(x.shape[0] - y.shape[0]) > hop_length:
             raise ValueError(f"evaluate: {g}.wav has {x.shape[0]} samples and {r}.wav {y.shape[0]}: more than one hop "
                              f"({hop_length}) apart")
@@ -94,12 +132,14 @@ def load_pairs(generated_dir, reference_dir, pairs, sampling_rate, hop_length):
     return out
 
 
-def evaluate_pairs(clips, stft, batch_size=16, device=None, resolutions=_metrics.MR_STFT_RESOLUTIONS, n_cep=13, pitch=None):
+def evaluate_pairs(clips, stft, batch_size=16, device=None, resolutions=_metrics.MR_STFT_RESOLUTIONS, n_cep=13, pitch=None,
+                   stoi=None):
     """``spectral_metrics`` of a list of ``(x, y)`` clips of different lengths: sorted longest first and cut into
     batches of ``batch_size`` (``generate.ragged_plan``), each batch at its longest length with ``lengths=``.  Returns a
     list of dicts of floats in the order of ``clips``.  Without a GPU the metric call raises (there is no CPU path).
     ``pitch``: None, or the keyword arguments of ``metrics.pitch_metrics`` (a dict, possibly empty), whose
-    ``PITCH_METRICS`` are then added to every row (NaN where a clip has none)."""
+    ``PITCH_METRICS`` are then added to every row (NaN where a clip has none).  ``stoi``: None, or the clips' sampling
+    rate: ``metrics.stoi``'s ``STOI_METRICS`` are added (NaN for a clip that keeps fewer than 30 frames)."""
     from .generate import ragged_plan
     if device is None:
         device = "cuda" if torch.cuda.is_available() else "cpu"
@@ -115,6 +155,9 @@ def evaluate_pairs(clips, stft, batch_size=16, device=None, resolutions=_metrics
         if pitch is not None:
             pm = _metrics.pitch_metrics(x, y, [lens[k] for k in batch], **pitch)
             m = dict(m, **{key: pm[key] for key in _metrics.PITCH_METRICS})
+        if stoi is not None:
+            sm = _metrics.stoi(x, y, [lens[k] for k in batch], sampling_rate=stoi)
+            m = dict(m, **{key: sm[key] for key in _metrics.STOI_METRICS})
         for b, k in enumerate(batch):
             rows[k] = {key: float(v[b]) for key, v in m.items()}
     return rows
@@ -172,6 +215,9 @@ def build_parser():
     ap.add_argument("--pitch-fmin", type=float, help="lowest F0 searched, Hz (default 50)")
     ap.add_argument("--pitch-fmax", type=float, help="highest F0 searched, Hz (default 550)")
     ap.add_argument("--pitch-threshold", type=float, help="YIN threshold (default 0.15)")
+    ap.add_argument("--stoi", action="store_true", help="add STOI and ESTOI (metrics.stoi; both files go to 10 kHz)")
+    ap.add_argument("--resample", action="store_true",
+                    help="convert a wav at another rate to --sampling-rate on the GPU instead of refusing it")
     ap.add_argument("overrides", nargs="*", help="key=value overrides of --config-dir, e.g. experiment=ljspeech")
     return ap
 
@@ -200,17 +246,23 @@ def main(argv=None):
         raise ValueError(f"evaluate: --strict: {len(lone_gen)} generated and {len(lone_ref)} reference files have no partner")
     if not pairs:
         raise ValueError(f"evaluate: no generated wav under {args.generated} pairs with a wav under {args.reference}")
-    clips = load_pairs(args.generated, args.reference, pairs, keys["sampling_rate"], keys["hop_length"])
+    if args.stoi:               # the rate is checked before a file is read
+        _metrics.stoi_lengths([], keys["sampling_rate"], "evaluate --stoi")
+    converted = [] if args.resample else None
+    clips = load_pairs(args.generated, args.reference, pairs, keys["sampling_rate"], keys["hop_length"], converted)
+    if converted is not None:
+        print(f"converted to {keys['sampling_rate']} Hz: {len(converted)} files")
     from .mel import TacotronSTFT
     stft = TacotronSTFT(filter_length=keys["filter_length"], hop_length=keys["hop_length"], win_length=keys["win_length"],
                         sampling_rate=keys["sampling_rate"], mel_fmin=keys["mel_fmin"], mel_fmax=keys["mel_fmax"])
-    if pitch is None:
+    nan_keys = (_metrics.PITCH_METRICS if pitch is not None else ()) + (_metrics.STOI_METRICS if args.stoi else ())
+    if not nan_keys:
         rows = evaluate_pairs(clips, stft, args.batch_size)
         summary = summarise(rows)
     else:
-        rows = evaluate_pairs(clips, stft, args.batch_size, pitch=pitch)
-        summary = summarise([{k: v for k, v in row.items() if k not in _metrics.PITCH_METRICS} for row in rows])
-        summary.update(summarise_finite(rows, _metrics.PITCH_METRICS))
+        rows = evaluate_pairs(clips, stft, args.batch_size, pitch=pitch, stoi=keys["sampling_rate"] if args.stoi else None)
+        summary = summarise([{k: v for k, v in row.items() if k not in nan_keys} for row in rows])
+        summary.update(summarise_finite(rows, nan_keys))
     print(f"{'metric':<20}{'mean':>12}{'std':>12}{'95% +-':>12}{'n':>6}")
     for key, (mean, sd, ci, n) in summary.items():
         print(f"{key:<20}{mean:>12.6f}{sd:>12.6f}{ci:>12.6f}{n:>6d}")
@@ -220,11 +272,16 @@ def main(argv=None):
                             for (g, r), c, row in zip(pairs, clips, rows)],
                   "summary": {k: dict(mean=m, std=s, ci95=c, n=n) for k, (m, s, c, n) in summary.items()},
                   "unpaired_generated": lone_gen, "unpaired_reference": lone_ref}
-        if pitch is not None:           # an undefined pitch value (NaN) is written as null: strict JSON has no NaN
+        if pitch is not None:
             record["pitch"] = pitch
+        if args.stoi:
+            record["stoi"] = dict(_metrics.STOI_DEFAULTS, sampling_rate=keys["sampling_rate"])
+        if converted is not None:
+            record["converted"] = [os.path.basename(p) for p in converted]
+        if nan_keys:                    # an undefined value (NaN) is written as null: strict JSON has no NaN
             for entry in record["files"]:
-                entry.update({k: None for k in _metrics.PITCH_METRICS if math.isnan(entry[k])})
-            for k in _metrics.PITCH_METRICS:
+                entry.update({k: None for k in nan_keys if math.isnan(entry[k])})
+            for k in nan_keys:
                 if math.isnan(record["summary"][k]["mean"]):
                     record["summary"][k]["mean"] = None
         with open(args.json, "w") as f:

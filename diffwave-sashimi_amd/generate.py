@@ -431,6 +431,31 @@ def _report_pitch(i, audio, stems, numbers, lens, dataset_cfg, rows, shared, sou
                 rows.append(dict(values, name=s, clip=numbers[b]))
 
 
+def _check_stoi_source(stem, samples, dataset_cfg):
+    """``generate.report_stoi``, before anything is sampled: ValueError where ``dataset``'s sampling rate is one
+    ``audio.resample`` does not bring to 10 kHz, or the pair of ``stem`` (``samples`` long) is shorter than one frame
+    there."""
+    from .metrics import stoi_lengths
+    stoi_lengths([int(samples)], dataset_cfg.get("sampling_rate", 22050), f"generate.report_stoi ({stem}.wav)")
+
+
+def _report_stoi(i, audio, stems, numbers, lens, dataset_cfg, rows, shared, sources):
+    """``generate.report_stoi``: as ``_report_pitch`` with ``metrics.stoi`` at ``dataset``'s sampling rate."""
+    from .metrics import STOI_METRICS, nanmean, stoi
+    x, y, n = _source_pairs(audio, stems, lens, dataset_cfg, sources)
+    m = stoi(x, y.to(x.device), n, sampling_rate=dataset_cfg.get("sampling_rate", 22050))
+    mean = {k: nanmean(m[k].tolist()) for k in STOI_METRICS}
+    print(f"batch {i} intelligibility: " + "  ".join(f"{k} = {mean[k]:.4f}" for k in STOI_METRICS) +
+          f"  (nan-means of {len(stems)} clips against their source wavs, at 10 kHz)")
+    if rows is not None:
+        for b, s in enumerate(stems):
+            values = {k: float(m[k][b]) for k in STOI_METRICS}
+            if shared:
+                rows[len(rows) - len(stems) + b].update(values)
+            else:
+                rows.append(dict(values, name=s, clip=numbers[b]))
+
+
 def _report_metrics(i, audio, stems, numbers, lens, dataset_cfg, rows, sources):
     """``generate.report_metrics``: the clips of batch ``i`` (``audio`` [B, 1, L] on the GPU, clip b its first
     ``lens[b]`` samples, made from the mel of ``stems[b]``) against their source wavs, each pair trimmed to its shorter
@@ -456,7 +481,7 @@ def generate(rank, diffusion_cfg, model_cfg, dataset_cfg, ckpt_iter="max", n_sam
              guide_name=None, guide_op=None, guide_clip=None, guide_factor=None, guide_scale=None, label=None,
              cfg_scale=None, ema=None, clip_seeds=None, clips=None, num_ranks=None, report_mel=None, mel_errors=None,
              mel_names=None, prior=None, prior_energy_max=None, prior_energy_min=None, prior_std_min=None,
-             report_metrics=None, metric_rows=None, report_pitch=None):
+             report_metrics=None, metric_rows=None, report_pitch=None, report_stoi=None):
     """``generate.py:58-200``.  ``ckpt_iter`` may additionally be ``"init"``: seeded random weights
     (no checkpoint), for smoke runs without trained weights.  ``precision`` (not in the reference; CLI:
     ``+engine.precision=bf16x6|f16x3``): the engine's opt-in matrix arithmetic, see ``include/dws.h``.
@@ -503,6 +528,10 @@ def generate(rank, diffusion_cfg, model_cfg, dataset_cfg, ckpt_iter="max", n_sam
     periodicity_rmse`` over the clips (a clip with no frame voiced in both signals has no F0 numbers) and adds the six
     keys to the clip's dict in ``metric_rows`` -- the dict of ``report_metrics`` where both are on.  A clip or source wav
     shorter than the tracker admits (734 samples at 22050 Hz and hop 256) is a ValueError before anything is sampled.
+    ``report_stoi=true`` (the same runs, the same ValueErrors; alone or with either) does the same through
+    ``metrics.stoi`` at ``dataset``'s sampling rate: the nan-means of ``stoi / estoi`` per batch (a clip that keeps fewer
+    than 30 frames at 10 kHz has neither) and the two keys in ``metric_rows``; a sampling rate the resampler does not
+    bring to 10 kHz, or a clip shorter than one 256-sample frame there, is a ValueError before anything is sampled.
 
     Class-conditional models (``model.n_classes = K``; not in the reference): ``label`` is a class index in 0..K (K = the
     null class), a list of them cycled over the samples, or ``all`` (= 0..K-1 in turn); the wav names get ``_c{label}``.
@@ -651,7 +680,17 @@ def generate(rank, diffusion_cfg, model_cfg, dataset_cfg, ckpt_iter="max", n_sam
             raise ValueError("generate.report_pitch does not combine with generate.mel_path (pre-computed mel tensors "
                              "have no source wav to compare with)")
 
-    source_wavs = {}        # report_metrics / report_pitch: the source wavs read so far
+    if report_stoi is not None:         # (the preconditions of report_metrics)
+        if not isinstance(report_stoi, bool):
+            raise ValueError(f"generate.report_stoi={report_stoi!r}: expected true or false")
+        if report_stoi and (model_cfg.get("unconditional") or (mel_name is None and mel_names is None)):
+            raise ValueError("generate.report_stoi needs a mel-conditional run (generate.mel_name or generate.mel_names: "
+                             "the clips are compared with the wavs their mels were computed from)")
+        if report_stoi and mel_path is not None:
+            raise ValueError("generate.report_stoi does not combine with generate.mel_path (pre-computed mel tensors "
+                             "have no source wav to compare with)")
+
+    source_wavs = {}        # report_metrics / report_pitch / report_stoi: the source wavs read so far
     n_classes = check_n_classes(model_cfg.get("n_classes"))
     labels_of = None        # the class of every sample, cycled
     if label is not None:
@@ -833,6 +872,8 @@ def generate(rank, diffusion_cfg, model_cfg, dataset_cfg, ckpt_iter="max", n_sam
                 mels.append(_mel.get_mel(audio).to(torch.float32).cuda())
                 if report_pitch:        # refused here, before the first batch is sampled
                     _check_pitch_source(stem, min(int(audio.shape[0]), int(mels[-1].shape[-1]) * hop), dataset_cfg)
+                if report_stoi:
+                    _check_stoi_source(stem, min(int(audio.shape[0]), int(mels[-1].shape[-1]) * hop), dataset_cfg)
         frames = [int(m.shape[-1]) for m in mels]
         batches = ragged_plan(frames, len(mel_names) if batch_size is None else batch_size)
         clips_out = [None] * len(mel_names)
@@ -867,6 +908,9 @@ def generate(rank, diffusion_cfg, model_cfg, dataset_cfg, ckpt_iter="max", n_sam
             if report_pitch:
                 _report_pitch(i, x, [mel_names[k] for k in batch], batch, lens, dataset_cfg, metric_rows,
                               bool(report_metrics), source_wavs)
+            if report_stoi:
+                _report_stoi(i, x, [mel_names[k] for k in batch], batch, lens, dataset_cfg, metric_rows,
+                             bool(report_metrics or report_pitch), source_wavs)
         torch.cuda.synchronize()
         made = [k for k, c in enumerate(clips_out) if c is not None]
         print(f"generated {len(made)} utterances of {len(mel_names)} at iteration {ckpt_iter} in "
@@ -896,6 +940,9 @@ def generate(rank, diffusion_cfg, model_cfg, dataset_cfg, ckpt_iter="max", n_sam
             if report_pitch:          # refused here, before anything is sampled
                 _check_pitch_source(mel_name, min(int(audio.shape[0]), int(mel.shape[-1]) * dataset_cfg["hop_length"]),
                                     dataset_cfg)
+            if report_stoi:
+                _check_stoi_source(mel_name, min(int(audio.shape[0]), int(mel.shape[-1]) * dataset_cfg["hop_length"]),
+                                   dataset_cfg)
         audio_length = mel.shape[-1] * dataset_cfg["hop_length"]
     else:
         audio_length, mel = dataset_cfg["segment_length"], None
@@ -981,6 +1028,9 @@ def generate(rank, diffusion_cfg, model_cfg, dataset_cfg, ckpt_iter="max", n_sam
         if report_pitch:
             _report_pitch(i, out[-1], [mel_name] * len(batch), batch, [audio_length] * len(batch), dataset_cfg,
                           metric_rows, bool(report_metrics), source_wavs)
+        if report_stoi:
+            _report_stoi(i, out[-1], [mel_name] * len(batch), batch, [audio_length] * len(batch), dataset_cfg,
+                         metric_rows, bool(report_metrics or report_pitch), source_wavs)
     generated_audio = torch.cat(out, dim=0) if out else torch.empty(0, 1, audio_length, device="cuda")
     torch.cuda.synchronize()
     print(f"generated {len(numbers)} samples shape {tuple(generated_audio.shape)} at iteration {ckpt_iter} in "

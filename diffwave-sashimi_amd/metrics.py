@@ -14,6 +14,10 @@ resolution; this module builds the constant tables, checks the arguments and div
 
 ``mr_stft_loss(x, y)`` is ``mr_stft`` as a training loss: float32 [B] on the device, differentiable in ``x`` through
 ``dws_spectral_loss_backward`` (the hand-written adjoint of the two terms; DESIGN.md section 4, "Spectral loss").
+
+``pitch_metrics(x, y)`` is the pitch family (YIN tracks of both signals, ``dws_pitch_distance``) and ``stoi(x, y)`` the
+intelligibility family: STOI and ESTOI at 10 kHz (``dws_stoi`` on top of ``audio.resample``; DESIGN.md section 4,
+"Pitch metrics" and "Intelligibility metrics").
 """
 import ctypes
 import math
@@ -348,6 +352,116 @@ def pitch_metrics(x, y, lengths=None, *, sampling_rate=22050, hop=256, win=1024,
     return {"f0_rmse": torch.sqrt(s[:, 1] / s[:, 0]), "f0_cents": torch.sqrt(s[:, 2] / s[:, 0]), "gpe": s[:, 7] / s[:, 0],
             "vuv_error": s[:, 5] / frames, "vuv_f1": 2.0 * s[:, 0] / (s[:, 3] + s[:, 4]),
             "periodicity_rmse": torch.sqrt(s[:, 6] / frames), "frames": frames, "voiced_both": s[:, 0].clone()}
+
+
+# ---- intelligibility: dws_stoi on top of dws_resample (csrc/stoi_kernels.hip; DESIGN.md section 4, "Intelligibility metrics")
+STOI_METRICS = ("stoi", "estoi")
+STOI_SUMS = ("stoi_sum", "estoi_sum", "segments", "frames_kept")
+# Taal's constants (Taal et al. 2011): 10 kHz, 256-sample frames at hop 128, a 512-point DFT, 15 third-octave bands from
+# 150 Hz, segments of 30 frames (384 ms), clipping at beta = -15 dB, 40 dB of dynamic range for the silent-frame removal
+STOI_DEFAULTS = dict(fs=10000, frame=256, hop=128, n_fft=512, n_bands=15, f_min=150.0, segment=30, beta=-15.0, dyn_range=40.0)
+
+_stoi_tables = {}   # device -> (window [frame], obm [n_bands, n_fft/2 + 1]) float32
+
+
+def third_octave_bands(fs=10000, n_fft=512, n_bands=15, f_min=150.0):
+    """``(obm, centres)``: the 0 / 1 band matrix float64 ``[n_bands, n_fft/2 + 1]`` and the centre frequencies
+    ``f_min 2^(k/3)``.  Band k has the edges ``centre 2^(-1/6)`` and ``centre 2^(+1/6)``, each moved to the nearest DFT bin
+    (bin q is ``q fs / n_fft`` Hz), and holds the bins ``[lo, hi)``."""
+    f = np.linspace(0.0, fs, n_fft + 1)[:n_fft // 2 + 1]
+    centres = f_min * 2.0 ** (np.arange(n_bands, dtype=np.float64) / 3.0)
+    obm = np.zeros((n_bands, len(f)), dtype=np.float64)
+    for k, c in enumerate(centres):
+        lo = int(np.argmin((f - c * 2.0 ** (-1.0 / 6.0)) ** 2))
+        hi = int(np.argmin((f - c * 2.0 ** (1.0 / 6.0)) ** 2))
+        obm[k, lo:hi] = 1.0
+    return obm, centres
+
+
+def stoi_window(frame=256):
+    """``hanning(frame + 2)[1:-1]``: the Hann window without its two zeros, float64 [frame]."""
+    return np.hanning(frame + 2)[1:-1]
+
+
+def _stoi_constants(device):
+    if device not in _stoi_tables:
+        d = STOI_DEFAULTS
+        obm, _ = third_octave_bands(d["fs"], d["n_fft"], d["n_bands"], d["f_min"])
+        _stoi_tables[device] = (torch.from_numpy(stoi_window(d["frame"]).astype(np.float32)).to(device),
+                                torch.from_numpy(obm.astype(np.float32)).to(device).contiguous())
+    return _stoi_tables[device]
+
+
+def stoi_lengths(lengths, sampling_rate, what="stoi"):
+    """The lengths of clips of ``lengths`` samples at ``sampling_rate`` once they are at 10 kHz, or ValueError: a rate
+    ``audio.resample`` refuses, or a clip shorter than one frame (256 samples at 10 kHz) after the conversion."""
+    from . import audio
+    fs, frame = STOI_DEFAULTS["fs"], STOI_DEFAULTS["frame"]
+    U, D = audio.check_ratio(sampling_rate, fs, what=what)
+    out = [audio.output_length(n, U, D) for n in lengths]
+    for b, (n, m) in enumerate(zip(lengths, out)):
+        if m < frame:
+            raise ValueError(f"{what}: clip {b} has {n} samples at {sampling_rate} Hz, {m} at {fs} Hz: one frame is {frame}")
+    return out
+
+
+def stoi_sums(x, y, lengths=None):
+    """The four numbers of ``dws_stoi`` (include/dws.h) for two batches ALREADY at 10 kHz, columns ``STOI_SUMS``: float64
+    [B, 4] on the CPU, with Taal's constants (``STOI_DEFAULTS``).  A clip's row depends on its own samples and length
+    alone, bit for bit.  Arguments are checked first (ValueError), then the device (RuntimeError)."""
+    x, y, host, lens = _pair(x, y, lengths, "stoi_sums")
+    stoi_lengths(lens, STOI_DEFAULTS["fs"], "stoi_sums")
+    _need_gpu(x, y)
+    return _stoi_run(x.detach().to(torch.float32).contiguous(), y.detach().to(torch.float32).contiguous(), host).cpu()
+
+
+def _stoi_run(x, y, host):
+    """One ``dws_stoi`` call on checked arguments at 10 kHz: float64 [B, 4] on the device."""
+    lib = _lib.load()
+    d = STOI_DEFAULTS
+    B, T = x.shape
+    dev = x.device
+    window, obm = _stoi_constants(dev)
+    out = torch.empty(B, len(STOI_SUMS), device=dev, dtype=torch.float64)
+    ws = torch.empty(lib.dws_stoi_workspace(B, T, d["frame"], d["hop"], d["n_bands"]) // 8, device=dev, dtype=torch.float64)
+    dev_len, host_len = _pitch_args(host, dev, B)
+    with torch.cuda.device(dev):
+        _lib.check(lib.dws_stoi(x.data_ptr(), y.data_ptr(), B, T, _lib.ptr(dev_len), host_len, window.data_ptr(), d["frame"],
+                                d["hop"], d["n_fft"], obm.data_ptr(), d["n_bands"], d["segment"], d["beta"], d["dyn_range"],
+                                ws.data_ptr(), out.data_ptr(), _lib.current_stream()))
+    return out
+
+
+def stoi(x, y, lengths=None, *, sampling_rate=22050):
+    """Short-time objective intelligibility of generated ``x`` against the clean reference ``y`` ([B, T] or [B, 1, T],
+    cuda, time-aligned, at ``sampling_rate``), clip by clip.  Returns a dict of float64 [B] CPU tensors: ``stoi`` (Taal et
+    al. 2011), ``estoi`` (Jensen & Taal 2016), ``frames_kept`` (the frames left after the silent frames of ``y`` are
+    removed) and ``segments`` (``frames_kept - 29`` or 0).
+
+    Both signals are converted to 10 kHz with ``audio.resample`` (not at all where ``sampling_rate`` is 10000), then
+    ``dws_stoi`` (include/dws.h) with Taal's constants (``STOI_DEFAULTS``) and the bands of ``third_octave_bands``.  A clip
+    that keeps fewer than 30 frames has no segment: its ``stoi`` and ``estoi`` are NaN.  ``lengths`` as in
+    ``spectral_metrics``.
+
+    The filter of the rate conversion and the frame count are this project's, not pystoi's or the Matlab original's, and
+    the values have not been compared with either.  Arguments are checked before anything runs (ValueError naming the
+    ratio or the clip: a rate ``audio.resample`` refuses, a clip shorter than one frame at 10 kHz); CPU tensors raise
+    RuntimeError."""
+    from . import audio
+    x, y, host, lens = _pair(x, y, lengths, "stoi")
+    lens10 = stoi_lengths(lens, sampling_rate)
+    _need_gpu(x, y)
+    x = x.detach().to(torch.float32).contiguous()
+    y = y.detach().to(torch.float32).contiguous()
+    fs = STOI_DEFAULTS["fs"]
+    if sampling_rate != fs:
+        x, _ = audio.resample(x, sampling_rate, fs, host)
+        y, _ = audio.resample(y, sampling_rate, fs, host)
+    s = _stoi_run(x, y, None if host is None else lens10).cpu()
+    m = s[:, 2]
+    nan = torch.full_like(m, float("nan"))
+    return {"stoi": torch.where(m > 0, s[:, 0] / (m * STOI_DEFAULTS["n_bands"]), nan),
+            "estoi": torch.where(m > 0, s[:, 1] / m, nan), "frames_kept": s[:, 3].clone(), "segments": m.clone()}
 
 
 def nanmean(values):

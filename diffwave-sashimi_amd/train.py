@@ -10,7 +10,8 @@ checkpoints followed by an in-loop ``generate`` call.  wandb is replaced by a JS
 ``val/mr_stft``, ``val/ls_mae``, ``val/lsd`` and ``val/mcd`` at that iteration (``metrics.py``); with
 ``+generate.report_pitch=true`` it gets ``val/f0_rmse``, ``val/f0_cents``, ``val/gpe``, ``val/vuv_error``, ``val/vuv_f1``
 and ``val/periodicity_rmse`` (``metrics.pitch_metrics``; means over the clips on which a key is defined, a key that is
-defined on none is left out).
+defined on none is left out); with ``+generate.report_stoi=true`` ``val/stoi`` and ``val/estoi`` (``metrics.stoi``, the
+same rule).
 
     python -m diffwave_sashimi_amd.train --config-dir /path/to/configs experiment=sc09 model=sashimi \
         dataset.data_path=/data/sc09 train.batch_size_per_gpu=32
@@ -429,7 +430,7 @@ def train(rank, num_gpus, diffusion_cfg, model_cfg, dataset_cfg, generate_cfg, c
                     net.eval()
                     wavs = []
                     # generate.report_metrics / generate.report_pitch: metrics.py
-                    rows = [] if gen.get("report_metrics") or gen.get("report_pitch") else None
+                    rows = [] if gen.get("report_metrics") or gen.get("report_pitch") or gen.get("report_stoi") else None
                     if rows is not None:
                         gen["metric_rows"] = rows
                     generate(rank, diffusion_cfg, model_cfg, dataset_cfg, name=name, exp_root=exp_root,
@@ -442,6 +443,10 @@ def train(rank, num_gpus, diffusion_cfg, model_cfg, dataset_cfg, generate_cfg, c
                     if rows and gen.get("report_pitch"):       # nan-means: a clip without a voiced frame has no F0 numbers
                         from .metrics import PITCH_METRICS, nanmean
                         means = {k: nanmean(r[k] for r in rows) for k in PITCH_METRICS if k in rows[0]}
+                        log({"val/" + k: v for k, v in means.items() if np.isfinite(v)}, n_iter)
+                    if rows and gen.get("report_stoi"):        # nan-means: a clip that keeps under 30 frames has neither
+                        from .metrics import STOI_METRICS, nanmean
+                        means = {k: nanmean(r[k] for r in rows) for k in STOI_METRICS if k in rows[0]}
                         log({"val/" + k: v for k, v in means.items() if np.isfinite(v)}, n_iter)
             n_iter += 1
             if n_iter >= n_iters + 1:

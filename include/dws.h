@@ -762,6 +762,67 @@ int dws_pitch_distance(const float* x, const float* y, int64_t B, int64_t T, con
 /* Bytes of dws_pitch_distance's workspace; 0 for a shape it refuses. */
 int64_t dws_pitch_distance_workspace(int64_t B, int64_t T, int32_t hop);
 
+/* Sample-rate conversion by the rational factor U / D (not in the reference; U = sr_out / g, D = sr_in / g, g their gcd):
+ * a polyphase FIR resampler.  x [B][T] (DEVICE float32), h [taps] = h[0 .. 2 half] (DEVICE float32; an odd count, gain U,
+ * designed by the caller).  With len_b = lengths[b] (T where lengths is null) clip b has out_len_b = ceil(len_b U / D)
+ * output samples
+ *     y[b][m] = sum_i x[b][i] h[m D - i U + half]         over the i in 0 .. len_b - 1 whose tap index lies in 0 .. 2 half
+ * (about taps / U products per output; nothing is zero-stuffed).  This is scipy.signal.resample_poly(x, U, D,
+ * window=h / U).  y is [B][T_out] with T_out >= the largest out_len_b; positions m >= out_len_b are written as exactly 0.
+ * Order of summation: fp32 fmaf from 0 with i ascending.  One workgroup per clip and tile of dws_resample_tile() output
+ * positions, the table and the tile's input span in LDS, no atomics: the result is bitwise reproducible, and row b
+ * depends on clip b's own len_b samples alone: not on B, T, b or on anything stored behind len_b (never read; may be NaN).
+ * U == D == 1 copies the len_b samples bit for bit (h is not read).
+ * lengths / lengths_host: as dws_spectral_distance (DEVICE and HOST copies of the same numbers, both or neither; the
+ * host copy is checked, nothing waits for the GPU; a device value the host did not admit makes its clip an empty one).
+ * DWS_ERR_INVALID: a null x, h or y; an even tap count; U or D < 1; B outside 1 .. 65535; T < 1; a len_b outside
+ * 1 .. T; T_out below the largest out_len_b; lengths without lengths_host.  DWS_ERR_UNSUPPORTED, with a message naming the
+ * ratio: more than 16384 taps, or a D / U so large that the (1023 D + taps - 1) / U + 2 input samples of a tile exceed
+ * the 16384 that fit in LDS. */
+int dws_resample(const float* x, int64_t B, int64_t T, const int32_t* lengths, const int32_t* lengths_host, const float* h,
+                 int32_t taps, int32_t U, int32_t D, float* y, int64_t T_out, void* stream);
+/* Output positions per workgroup of dws_resample (tests put shapes on both sides of it). */
+int dws_resample_tile(void);
+
+/* Short-time objective intelligibility of x (generated) against y (the clean reference), STOI (Taal et al. 2011) and
+ * ESTOI (Jensen & Taal 2016); not in the reference.  x, y [B][T] DEVICE float32 at the rate the band matrix is built for
+ * (10 kHz in the papers).  Taal's constants are arguments: frame 256, hop 128, n_fft 512, 15 third-octave bands, segment
+ * N = 30 frames, beta = -15 dB, dyn_range = 40 dB.  window [frame] (DEVICE float32; hanning(frame + 2)[1:-1]), obm
+ * [n_bands][n_fft/2 + 1] (DEVICE float32, entries >= 0; 0 / 1 for third-octave bands).  eps = DBL_EPSILON.  Per clip, with
+ * len_b = lengths[b] (T where lengths is null) and w = window:
+ *  1. Silent frames, decided by y alone: frames j = 0 .. (len_b - frame) / hop, e_j = 20 log10(||w y_j|| + eps); frame j
+ *     is kept where e_j > max_j e_j - dyn_range.  The kept windowed frames of both signals, K of them, are overlap-added
+ *     at `hop` in their order; the compacted signals are never stored -- frame k of one (k = 0 .. K - 1) is
+ *         c_k[n] = sum_{k'} w[i] s[idx[k'] hop + i],   i = n + (k - k') hop in 0 .. frame - 1,   |k - k'| <= (frame - 1) / hop
+ *     over the list idx of kept frames (a fixed-order prefix sum over the keep flags).
+ *  2. Band magnitudes: S_k = the n_fft-point DFT of w c_k (its `frame` samples; only bins some band uses),
+ *         X[k][j] = sqrt(sum_q obm[j][q] |S_k[q]|^2)        of x, Y[k][j] of y.
+ *  3. For every segment m = 0 .. K - N of N consecutive frames, per band j, with x, y the N values of that band:
+ *         alpha = ||y|| / (||x|| + eps),   x' = min(alpha x, (1 + 10^(-beta / 20)) y),
+ *         d_mj = sum ((x' - mean x') / (||x' - mean x'|| + eps)) ((y - mean y) / (||y - mean y|| + eps));
+ *     ESTOI, no clipping: the rows (bands) of both [n_bands][N] blocks made zero-mean and divided by (norm + eps) over
+ *     time, then the columns (frames) over bands, d_m = (1 / N) sum of the N column inner products.
+ * out [B][4] (DEVICE, double): sum_{m, j} d_mj, sum_m d_m, the number of segments M = max(K - N + 1, 0) and K.  The caller
+ * divides (STOI = out0 / (M n_bands), ESTOI = out1 / M); K < N gives M = 0 and zero sums.
+ * Arithmetic and order of summation: the frame energies, the overlap-add, the band sums and everything behind them are
+ * double; the DFT is a direct fp32 sum (one thread per bin, fmaf over the samples ascending).  An energy and a band sum
+ * are a lane's terms ascending (stride 64) and an xor tree over the wave; the maximum is exact; within a segment a band
+ * sums its frames ascending and a frame its bands ascending, the bands and then the frames are added in ascending order,
+ * and a clip's segments in ascending order.  No atomics: the result is bitwise reproducible, and clip b's four numbers
+ * depend on its own len_b samples alone: not on B, T, b or on anything stored behind len_b (never read; may be NaN).
+ * lengths / lengths_host: as dws_spectral_distance.  workspace: DEVICE, dws_stoi_workspace(B, T, frame, hop, n_bands) bytes
+ * owned by the caller (overwritten; the library allocates nothing per call): with F = (T - frame) / hop + 1, doubles e
+ * [B][F], bands [B][2][F][n_bands] (x then y), segments [B][F][2], then int32 idx [B][F] and kept [B].
+ * DWS_ERR_INVALID: a null x, y, window, obm, workspace or out; n_fft not a power of two in 64 .. 2048; frame outside
+ * 1 .. n_fft; hop < 1; segment outside 2 .. 128; n_bands outside 1 .. 64; B outside 1 .. 65535; a len_b outside
+ * frame .. T; a dyn_range <= 0; lengths without lengths_host. */
+int dws_stoi(const float* x, const float* y, int64_t B, int64_t T, const int32_t* lengths, const int32_t* lengths_host,
+             const float* window, int32_t frame, int32_t hop, int32_t n_fft, const float* obm, int32_t n_bands,
+             int32_t segment, double beta, double dyn_range, void* workspace, double* out, void* stream);
+
+/* Bytes of dws_stoi's workspace; 0 for a shape it refuses. */
+int64_t dws_stoi_workspace(int64_t B, int64_t T, int32_t frame, int32_t hop, int32_t n_bands);
+
 /* Pseudo-QMF filter bank of multi-band runs (Multi-band MelGAN, Yang et al. 2020; not in the reference).  Both entries
  * take the filter table filt [K][taps + 1] (DEVICE, float32; designed by the caller) and a gain, so that each also serves
  * as the other's adjoint.  K is 2 or 4, taps is even and in 2 .. 254, h = taps / 2.
