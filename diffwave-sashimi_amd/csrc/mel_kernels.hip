@@ -1,162 +1,90 @@
 // Mel-spectrogram front-end of the vocoding path (`dataloaders/stft.py:100-244`,
 // `dataloaders/mel2samp.py:76-82`): reflect-pad by n_fft/2, windowed DFT magnitude at hop
 // `hop`, mel filterbank, log(clamp(., clip)).  One workgroup per frame: the windowed frame,
-// a cos/sin table and the magnitudes live in LDS; a thread owns DFT bins k = tid, tid+256, ...
+// the (cos, sin) table and the magnitudes live in LDS; a thread owns DFT bins k = tid, tid+256, ...
 // (direct O(n_fft^2 / 2) transform: 63 frames of 1024 samples per second of audio is 33 MFLOP,
 // not worth an FFT), then 80 mel rows are reduced by one wave each.
-#include "dws_common.h"
+#include "stft_core.h"
 
 namespace dws {
+
+// What both mel kernels start with (framing, table and transform: stft_core.h): frame f = blockIdx.x of clip
+// b = blockIdx.y windowed into LDS, its magnitudes, and the mel rows s_m = sum_k W[m,k] mag_k, one wave per row (a lane
+// adds its bins in ascending k, then wave_sum).  emit(m, s_m) runs on lane 0 of the row's wave; `ri`, where not null,
+// keeps (Re_k, Im_k).  The adjoint calls this very function, so its clamp and zero-magnitude decisions are the forward's.
+template <typename Emit>
+__device__ __forceinline__ void mel_frame_rows(const float* __restrict__ audio, const float* __restrict__ window,
+                                               const float* __restrict__ basis, float2* __restrict__ tab,
+                                               float* __restrict__ frame, float* __restrict__ mag, float2* __restrict__ ri,
+                                               int T, int n_fft, int hop, int n_mels, Emit emit) {
+    const int f = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
+    const int half = n_fft / 2, nb = half + 1;
+    load_centred_frame<1>(frame, tab, audio + (size_t)b * T, nullptr, window, f * hop - half, T, n_fft, tid);
+    __syncthreads();
+    for (int k = tid; k < nb; k += 256) {
+        float re[1], im[1];
+        dft_bin<1>(frame, tab, k, n_fft, n_fft - 1, re, im);
+        if (ri) ri[k] = make_float2(re[0], im[0]);
+        mag[k] = sqrtf(re[0] * re[0] + im[0] * im[0]);
+    }
+    __syncthreads();
+    const int wave = tid >> 6, lane = tid & 63;
+    for (int m = wave; m < n_mels; m += 4) {
+        const float* w = basis + (size_t)m * nb;
+        float s = 0.f;
+        for (int k = lane; k < nb; k += 64) s = fmaf(w[k], mag[k], s);
+        s = wave_sum(s);
+        if (lane == 0) emit(m, s);
+    }
+}
 
 __global__ __launch_bounds__(256) void mel_frame_kernel(const float* __restrict__ audio, const float* __restrict__ window,
                                                         const float* __restrict__ basis, float* __restrict__ out, int T,
                                                         int n_fft, int hop, int n_mels, int n_frames, float clip) {
-    extern __shared__ float lds[];
-    float* frame = lds;                 // [n_fft]
-    float* ct = frame + n_fft;          // [n_fft] cos(2 pi j / n_fft)
-    float* st = ct + n_fft;             // [n_fft] sin(2 pi j / n_fft)
-    float* mag = st + n_fft;            // [n_fft/2 + 1]
-    const int f = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
-    const int half = n_fft / 2, nb = half + 1;
-    const float* a = audio + (size_t)b * T;
-    for (int i = tid; i < n_fft; i += 256) {
-        int j = f * hop + i - half;      // index into the un-padded signal; reflect (no edge repeat) outside
-        if (j < 0) j = -j;
-        if (j >= T) j = 2 * (T - 1) - j;
-        frame[i] = a[j] * window[i];
-        float s, c;
-        sincospif(2.f * (float)i / (float)n_fft, &s, &c);
-        ct[i] = c;
-        st[i] = s;
-    }
-    __syncthreads();
-    const int mask = n_fft - 1;          // n_fft is a power of two
-    for (int k = tid; k < nb; k += 256) {
-        float re = 0.f, im = 0.f;
-        int ph = 0;
-        for (int i = 0; i < n_fft; ++i) {
-            const float v = frame[i];
-            re = fmaf(v, ct[ph], re);
-            im = fmaf(v, st[ph], im);
-            ph = (ph + k) & mask;
-        }
-        mag[k] = sqrtf(re * re + im * im);
-    }
-    __syncthreads();
-    const int wave = tid >> 6, lane = tid & 63;
-    for (int m = wave; m < n_mels; m += 4) {
-        const float* w = basis + (size_t)m * nb;
-        float s = 0.f;
-        for (int k = lane; k < nb; k += 64) s = fmaf(w[k], mag[k], s);
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off);
-        if (lane == 0) out[((size_t)b * n_mels + m) * n_frames + f] = logf(fmaxf(s, clip));
-    }
+    extern __shared__ float2 mel_lds[];
+    float2* tab = mel_lds;                                   // [n_fft] (cos, sin)(2 pi j / n_fft)
+    float* frame = reinterpret_cast<float*>(tab + n_fft);    // [n_fft]
+    float* mag = frame + n_fft;                              // [n_fft/2 + 1]
+    const int f = blockIdx.x, b = blockIdx.y;
+    mel_frame_rows(audio, window, basis, tab, frame, mag, nullptr, T, n_fft, hop, n_mels, [&](int m, float s) {
+        out[((size_t)b * n_mels + m) * n_frames + f] = logf(fmaxf(s, clip));
+    });
 }
 
-// Adjoint, stage 1 of 2: one workgroup per (frame, clip).  Re/Im of the frame are recomputed exactly as
-// mel_frame_kernel computes them (same tables, same fmaf order, same wave reduction of the mel rows), then
+// Adjoint, stage 1 of 2: one workgroup per (frame, clip).  Re/Im of the frame and the mel rows s_m are mel_frame_rows',
+// then
 //   ds_m = g[m,f] / s_m  (0 where s_m <= clip),   dmag_k = sum_m W[m,k] ds_m  (ascending m),
 //   dRe_k = dmag_k Re_k / mag_k,  dIm_k = dmag_k Im_k / mag_k  (both 0 where mag_k == 0),
-//   ws[b,f,i] = w[i] sum_k (dRe_k cos(2 pi i k / N) + dIm_k sin(2 pi i k / N))  (ascending k).
-// Nothing is accumulated across workgroups here: the overlap-add is mel_gather_kernel's.
+//   ws[b,f,i] = w[i] sum_k (dRe_k cos(2 pi i k / N) + dIm_k sin(2 pi i k / N))  (ascending k: idft_sample).
+// Nothing is accumulated across workgroups here: the overlap-add is ola_gather_kernel's.
 __global__ __launch_bounds__(256) void mel_frame_backward_kernel(const float* __restrict__ audio, const float* __restrict__ window,
                                                                  const float* __restrict__ basis, const float* __restrict__ dout,
                                                                  float* __restrict__ ws, int T, int n_fft, int hop, int n_mels,
                                                                  int n_frames, float clip) {
-    extern __shared__ float lds[];
-    float* frame = lds;                 // [n_fft]
-    float* ct = frame + n_fft;          // [n_fft]
-    float* st = ct + n_fft;             // [n_fft]
-    float* mag = st + n_fft;            // [n_fft/2 + 1]
+    extern __shared__ float2 mel_lds[];
     const int f = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
-    const int half = n_fft / 2, nb = half + 1;
-    float* re = mag + nb;               // [nb] Re_k, then dRe_k
-    float* im = re + nb;                // [nb] Im_k, then dIm_k
-    float* ds = im + nb;                // [n_mels]
-    const float* a = audio + (size_t)b * T;
-    for (int i = tid; i < n_fft; i += 256) {
-        int j = f * hop + i - half;
-        if (j < 0) j = -j;
-        if (j >= T) j = 2 * (T - 1) - j;
-        frame[i] = a[j] * window[i];
-        float s, c;
-        sincospif(2.f * (float)i / (float)n_fft, &s, &c);
-        ct[i] = c;
-        st[i] = s;
-    }
-    __syncthreads();
-    const int mask = n_fft - 1;
-    for (int k = tid; k < nb; k += 256) {
-        float r = 0.f, q = 0.f;
-        int ph = 0;
-        for (int i = 0; i < n_fft; ++i) {
-            const float v = frame[i];
-            r = fmaf(v, ct[ph], r);
-            q = fmaf(v, st[ph], q);
-            ph = (ph + k) & mask;
-        }
-        re[k] = r;
-        im[k] = q;
-        mag[k] = sqrtf(r * r + q * q);
-    }
-    __syncthreads();
-    const int wave = tid >> 6, lane = tid & 63;
-    for (int m = wave; m < n_mels; m += 4) {
-        const float* w = basis + (size_t)m * nb;
-        float s = 0.f;
-        for (int k = lane; k < nb; k += 64) s = fmaf(w[k], mag[k], s);
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off);
+    const int nb = n_fft / 2 + 1;
+    float2* tab = mel_lds;                                   // [n_fft]
+    float2* dri = tab + n_fft;                               // [nb] (Re_k, Im_k), then (dRe_k, dIm_k)
+    float* frame = reinterpret_cast<float*>(dri + nb);       // [n_fft]
+    float* mag = frame + n_fft;                              // [nb]
+    float* ds = mag + nb;                                    // [n_mels]
+    mel_frame_rows(audio, window, basis, tab, frame, mag, dri, T, n_fft, hop, n_mels, [&](int m, float s) {
         // the clamp passes no gradient at or below `clip` (the tie s == clip counts as clamped)
-        if (lane == 0) ds[m] = s > clip ? dout[((size_t)b * n_mels + m) * n_frames + f] / s : 0.f;
-    }
+        ds[m] = s > clip ? dout[((size_t)b * n_mels + m) * n_frames + f] / s : 0.f;
+    });
     __syncthreads();
     for (int k = tid; k < nb; k += 256) {
         float dmag = 0.f;
         for (int m = 0; m < n_mels; ++m) dmag = fmaf(basis[(size_t)m * nb + k], ds[m], dmag);
         const float mk = mag[k];
         const float t = mk > 0.f ? dmag / mk : 0.f;      // |z| has no gradient at 0: a silent bin contributes exactly 0
-        re[k] = t * re[k];
-        im[k] = t * im[k];
+        const float2 r = dri[k];
+        dri[k] = make_float2(t * r.x, t * r.y);
     }
     __syncthreads();
     float* o = ws + ((size_t)b * n_frames + f) * n_fft;
-    for (int i = tid; i < n_fft; i += 256) {
-        float acc = 0.f;
-        int ph = 0;
-        for (int k = 0; k < nb; ++k) {
-            acc = fmaf(re[k], ct[ph], acc);
-            acc = fmaf(im[k], st[ph], acc);
-            ph = (ph + i) & mask;
-        }
-        o[i] = window[i] * acc;
-    }
-}
-
-// Adjoint, stage 2 of 2: one thread per sample.  Sample j sits at padded position j + N/2 and, through the reflect
-// padding, at N/2 - j (j = 1 .. N/2) and at N/2 + 2(T-1) - j (j = T-1-N/2 .. T-2); every frame covering one of these
-// positions contributed ws[b,f,position - f hop].  Summed in a fixed order: the direct position, then the left
-// reflection, then the right one, each in ascending frame order.
-__device__ __forceinline__ float mel_gather_position(const float* __restrict__ wsb, int p, int n_fft, int hop, int n_frames, float acc) {
-    int lo = p - n_fft + 1;
-    lo = lo <= 0 ? 0 : (lo + hop - 1) / hop;
-    int hi = p / hop;
-    if (hi > n_frames - 1) hi = n_frames - 1;
-    for (int f = lo; f <= hi; ++f) acc += wsb[(size_t)f * n_fft + (p - f * hop)];
-    return acc;
-}
-
-__global__ __launch_bounds__(256) void mel_gather_kernel(const float* __restrict__ ws, float* __restrict__ daudio, int T,
-                                                         int n_fft, int hop, int n_frames) {
-    const int j = blockIdx.x * 256 + threadIdx.x, b = blockIdx.y;
-    if (j >= T) return;
-    const int half = n_fft / 2;
-    const float* wsb = ws + (size_t)b * n_frames * n_fft;
-    float acc = mel_gather_position(wsb, j + half, n_fft, hop, n_frames, 0.f);
-    if (j >= 1 && j <= half) acc = mel_gather_position(wsb, half - j, n_fft, hop, n_frames, acc);
-    if (j <= T - 2 && j >= T - 1 - half) acc = mel_gather_position(wsb, half + 2 * (T - 1) - j, n_fft, hop, n_frames, acc);
-    daudio[(size_t)b * T + j] = acc;
+    for (int i = tid; i < n_fft; i += 256) o[i] = window[i] * idft_sample(dri, tab, i, nb, n_fft - 1);
 }
 
 // Adaptive prior (PriorGrad, Lee et al., ICLR 2022): the per-sample standard deviation read off the frame energy of a
@@ -251,7 +179,7 @@ extern "C" int dws_mel_spectrogram_backward(const float* audio, int64_t B, int64
     DWS_CHECK(audio && window && mel_basis && dout && daudio, DWS_ERR_INVALID, "dws_mel_spectrogram_backward: null argument");
     DWS_CHECK(workspace, DWS_ERR_INVALID, "dws_mel_spectrogram_backward: null workspace ([B][T/hop+1][n_fft] floats)");
     DWS_CHECK(B > 0 && hop > 0 && n_mels > 0, DWS_ERR_INVALID, "dws_mel_spectrogram_backward: bad shape");
-    DWS_CHECK(n_fft >= 64 && n_fft <= 4096 && (n_fft & (n_fft - 1)) == 0, DWS_ERR_UNSUPPORTED,
+    DWS_CHECK(n_fft_ok(n_fft, 4096), DWS_ERR_UNSUPPORTED,
               "dws_mel_spectrogram_backward: filter_length %d (powers of two 64..4096 are built)", n_fft);
     DWS_CHECK(T > n_fft / 2, DWS_ERR_INVALID,
               "dws_mel_spectrogram_backward: reflect padding needs T > filter_length/2 (`stft.py:127-131`)");
@@ -263,10 +191,7 @@ extern "C" int dws_mel_spectrogram_backward(const float* audio, int64_t B, int64
     hipLaunchKernelGGL(mel_frame_backward_kernel, dim3(n_frames, (unsigned)B), dim3(256), lds, (hipStream_t)stream, audio,
                        window, mel_basis, dout, workspace, (int)T, n_fft, hop, n_mels, n_frames, clip);
     DWS_HIP(hipGetLastError());
-    hipLaunchKernelGGL(mel_gather_kernel, dim3((unsigned)((T + 255) / 256), (unsigned)B), dim3(256), 0, (hipStream_t)stream,
-                       workspace, daudio, (int)T, n_fft, hop, n_frames);
-    DWS_HIP(hipGetLastError());
-    return DWS_OK;
+    return ola_gather(workspace, nullptr, daudio, B, T, n_fft, hop, n_frames, 0, (hipStream_t)stream);
 }
 
 extern "C" int dws_mel_spectrogram(const float* audio, int64_t B, int64_t T, const float* window, const float* mel_basis,
@@ -274,7 +199,7 @@ extern "C" int dws_mel_spectrogram(const float* audio, int64_t B, int64_t T, con
     using namespace dws;
     DWS_CHECK(audio && window && mel_basis && out, DWS_ERR_INVALID, "dws_mel_spectrogram: null argument");
     DWS_CHECK(B > 0 && hop > 0 && n_mels > 0, DWS_ERR_INVALID, "dws_mel_spectrogram: bad shape");
-    DWS_CHECK(n_fft >= 64 && n_fft <= 4096 && (n_fft & (n_fft - 1)) == 0, DWS_ERR_UNSUPPORTED,
+    DWS_CHECK(n_fft_ok(n_fft, 4096), DWS_ERR_UNSUPPORTED,
               "dws_mel_spectrogram: filter_length %d (powers of two 64..4096 are built)", n_fft);
     DWS_CHECK(T > n_fft / 2, DWS_ERR_INVALID, "dws_mel_spectrogram: reflect padding needs T > filter_length/2 (`stft.py:127-131`)");
     const int n_frames = (int)(T / hop) + 1;

@@ -2,7 +2,7 @@
 // with a fixed threshold, one workgroup per (frame, clip, signal), and the eight per-clip sums of the pitch metrics
 // (F0 RMSE in Hz and cents, gross pitch errors, voicing decision error and F1, periodicity RMSE).
 //
-// Framing is spectral_frame_kernel's: frames f = 0 .. len_b / hop, centred, reflected about the clip's OWN ends (a
+// Framing is stft_core.h's: frames f = 0 .. len_b / hop, centred, reflected about the clip's OWN ends (a
 // ragged batch: nothing behind len_b is read).  A frame is S = W + M samples (W the integration window, M = tau_hi + 1
 // the largest lag computed) in LDS, and
 //   d(tau) = sum_{j < W} (u[j] - u[j + tau])^2        tau = 0 .. M
@@ -20,7 +20,7 @@
 // owns C = ceil(M / 256) consecutive lags serially; an inclusive shuffle scan over the lanes of a wave; the waves in
 // wave order), d'(tau) = d(tau) tau / prefix(tau), and the decision as three min reductions (first tau below the
 // threshold, first tau at which the descent stops, smallest d' of the search range).  No atomics; bitwise reproducible.
-#include "dws_common.h"
+#include "stft_core.h"
 
 namespace dws {
 
@@ -30,12 +30,8 @@ typedef float pitch_v4 __attribute__((ext_vector_type(4)));     // a native vect
 // <= u[S + 3] and the tail up to u[W - 1 + 4 (G - 1) + 3] <= u[S + 2]; what they feed are lags above M, which nobody reads
 constexpr int PITCH_PAD = 16;
 
-// frames of clip b: 0 where the length is not one the host admitted (the guard keeps every index inside the row
-// whatever the device array holds)
-__device__ __forceinline__ int pitch_clip_frames(const int* __restrict__ lengths, int b, int T, int S, int hop, int& len) {
-    len = lengths ? lengths[b] : T;
-    return (len >= (S + 1) / 2 + 1 && len <= T) ? len / hop + 1 : 0;
-}
+// the shortest clip a frame of S samples can be reflected about (one reflection per side)
+__host__ __device__ __forceinline__ int pitch_min_len(int S) { return (S + 1) / 2 + 1; }
 
 __device__ __forceinline__ int pitch_block_min(int v, int* slot, int wave, int lane) {
 #pragma unroll
@@ -63,7 +59,7 @@ __global__ __launch_bounds__(256) void pitch_frame_kernel(const float* __restric
     const int M = tau_hi + 1, S = W + M;
     float* o = track + (((size_t)z * gridDim.y + b) * f_max + f) * 2;
     int len;
-    if (f >= pitch_clip_frames(lengths, b, T, S, hop, len)) {      // the whole workgroup, before any barrier
+    if (f >= centred_clip_frames(lengths, b, T, pitch_min_len(S), hop, len)) {      // the whole workgroup, before any barrier
         if (tid < 2) o[tid] = 0.f;
         return;
     }
@@ -79,14 +75,7 @@ __global__ __launch_bounds__(256) void pitch_frame_kernel(const float* __restric
     const float* sa = (z ? s1 : s0) + (size_t)b * T;
     const int start = f * hop - S / 2;
     for (int i = tid; i < S_pad; i += 256) {
-        float v = 0.f;
-        if (i < S) {
-            int j = start + i;           // reflect (no edge repeat) about the clip's own ends; len >= (S+1)/2 + 1 keeps j in [0, len)
-            if (j < 0) j = -j;
-            if (j >= len) j = 2 * (len - 1) - j;
-            v = sa[j];
-        }
-        u[i] = v;
+        u[i] = i < S ? sa[reflect_index(start + i, len)] : 0.f;      // len >= pitch_min_len(S) keeps the index in [0, len)
     }
     __syncthreads();
 
@@ -222,7 +211,7 @@ __global__ __launch_bounds__(64) void pitch_clip_sum_kernel(const float* __restr
     const int b = blockIdx.x, q = threadIdx.x;
     if (q >= PITCH_Q) return;
     int len;
-    const int nf = pitch_clip_frames(lengths, b, T, S, hop, len);
+    const int nf = centred_clip_frames(lengths, b, T, pitch_min_len(S), hop, len);
     const float2* px = reinterpret_cast<const float2*>(tx) + (size_t)b * f_max;
     const float2* py = reinterpret_cast<const float2*>(ty) + (size_t)b * f_max;
     double s = 0.0;
@@ -255,19 +244,7 @@ static int pitch_check(const char* who, int64_t B, int64_t T, const int32_t* len
     DWS_CHECK(sampling_rate > 0.0 && sampling_rate < 1e12, DWS_ERR_INVALID, "%s: sampling_rate = %g", who, sampling_rate);
     DWS_CHECK(B > 0 && B <= 65535 && hop > 0 && T > 0 && T <= INT32_MAX - 8192, DWS_ERR_INVALID,
               "%s: bad shape (B = %lld, T = %lld, hop = %d)", who, (long long)B, (long long)T, hop);
-    DWS_CHECK((lengths == nullptr) == (lengths_host == nullptr), DWS_ERR_INVALID,
-              "%s: lengths (device) and lengths_host (the same numbers on the host) come together", who);
-    const int need = (win + tau_hi + 1 + 1) / 2 + 1;
-    if (lengths_host) {
-        for (int64_t b = 0; b < B; ++b)
-            DWS_CHECK(lengths_host[b] >= need && lengths_host[b] <= T, DWS_ERR_INVALID,
-                      "%s: clip %lld has %d samples (win = %d and tau_hi = %d need %d .. T = %lld)", who, (long long)b,
-                      lengths_host[b], win, tau_hi, need, (long long)T);
-    } else {
-        DWS_CHECK(T >= need, DWS_ERR_INVALID, "%s: T = %lld (win = %d and tau_hi = %d need at least %d samples)", who,
-                  (long long)T, win, tau_hi, need);
-    }
-    return DWS_OK;
+    return check_clip_lengths(who, B, T, lengths, lengths_host, pitch_min_len(win + tau_hi + 1)) < 0 ? DWS_ERR_INVALID : DWS_OK;
 }
 
 static int pitch_launch(const float* s0, const float* s1, int signals, int64_t B, int64_t T, const int32_t* lengths,

@@ -15,7 +15,7 @@
 // group are spread.  A phase-major table [U][taps per phase] would put a lane's own taps side by side, which serves a
 // lane's consecutive reads and does nothing for the lanes of a group at one t (rows r_m apart times the row length);
 // it also needs a padded row per ratio.  It was not built, so there is no A/B.
-#include "dws_common.h"
+#include "stft_core.h"      // check_clip_lengths
 
 namespace dws {
 
@@ -103,17 +103,8 @@ extern "C" int dws_resample(const float* x, int64_t B, int64_t T, const int32_t*
               taps, U, D);
     DWS_CHECK(B > 0 && B <= 65535, DWS_ERR_INVALID, "dws_resample: B = %lld (1 .. 65535)", (long long)B);
     DWS_CHECK(T > 0 && T <= INT32_MAX - 8192, DWS_ERR_INVALID, "dws_resample: T = %lld (1 .. 2^31 - 8193)", (long long)T);
-    DWS_CHECK((lengths == nullptr) == (lengths_host == nullptr), DWS_ERR_INVALID,
-              "dws_resample: lengths (device) and lengths_host (the same numbers on the host) come together");
-    int64_t longest = T;
-    if (lengths_host) {
-        longest = 0;
-        for (int64_t b = 0; b < B; ++b) {
-            DWS_CHECK(lengths_host[b] >= 1 && lengths_host[b] <= T, DWS_ERR_INVALID,
-                      "dws_resample: clip %lld has %d samples (1 .. T = %lld)", (long long)b, lengths_host[b], (long long)T);
-            if (lengths_host[b] > longest) longest = lengths_host[b];
-        }
-    }
+    const int64_t longest = check_clip_lengths("dws_resample", B, T, lengths, lengths_host, 1);
+    if (longest < 0) return DWS_ERR_INVALID;
     const int64_t need = (longest * U + D - 1) / D;
     DWS_CHECK(T_out >= need && T_out <= INT32_MAX - 8192, DWS_ERR_INVALID,
               "dws_resample: T_out = %lld at ratio %d / %d (the longest clip, %lld samples, gives %lld; below 2^31 - 8192)",

@@ -3,28 +3,41 @@
 // log-spectral distance, and -- where a mel filterbank is passed -- the log-mel L1 and a mel-cepstral distortion.  No
 // spectrogram goes to memory: a workgroup owns frame f of clip b of BOTH signals and writes six partial sums.
 //
-// Framing and transform are mel_frame_kernel's (reflect-pad by n_fft/2, windowed direct DFT, a thread owns bins
-// k = tid, tid + 256, ...), with two changes: the reflection is about the clip's OWN end len_b (a ragged batch: nothing
-// behind len_b is read, so the padding may hold anything), and the frames of x and y sit interleaved in LDS next to an
-// interleaved (cos, sin) table, so one 8-byte table read and one 8-byte frame read feed four FMAs.
+// Framing and transform are stft_core.h's, on two signals: reflect-pad by n_fft/2 about the clip's OWN end len_b (a
+// ragged batch: nothing behind len_b is read, so the padding may hold anything), windowed direct DFT, a thread owns bins
+// k = tid, tid + 256, ..., the frames of x and y interleaved in LDS.
 //
-// Reduction, in a fixed order: a thread adds its bins in ascending k (fp32), a wave adds its lanes by an xor tree
+// Reduction, in a fixed order: a thread adds its bins in ascending k (fp32), a wave adds its lanes by wave_sum
 // (fp32), thread 0 adds the four waves in wave order (double).  The mel terms take ln() and the cepstral products in
 // double: with x = y / 2 the band differences are then ln 2 to the last bit and the distortion cancels to 1e-16, where
 // fp32 logs would leave 1e-5 dB of rounding noise.  spectral_clip_sum_kernel adds a clip's frames in ascending order in
 // double.  A clip's six numbers depend on its own samples and length alone.
-#include "dws_common.h"
+#include "stft_core.h"
 
 namespace dws {
 
 constexpr int SPEC_Q = 6;                 // sc_num, sc_den, mag_abs, lsd, mel_abs, mcd
 constexpr float SPEC_FLOOR = 1e-7f;       // Parallel WaveGAN: |X| = sqrt(max(re^2 + im^2, 1e-7))
 
-// frames of clip b: 0 where the length is not one the host admitted (never the case after dws_spectral_distance's
-// checks; the guard keeps every index inside the row whatever the device array holds)
-__device__ __forceinline__ int spectral_clip_frames(const int* __restrict__ lengths, int b, int T, int half, int hop, int& len) {
-    len = lengths ? lengths[b] : T;
-    return (len > half && len <= T) ? len / hop + 1 : 0;
+// What both frame kernels start with: frame f of clip b (len samples) of x and y windowed into fr, the table into tab.
+__device__ __forceinline__ void spectral_load(const float* __restrict__ x, const float* __restrict__ y,
+                                              const float* __restrict__ window, float2* __restrict__ fr,
+                                              float2* __restrict__ tab, int f, int b, int T, int len, int n_fft, int hop) {
+    load_centred_frame<2>(fr, tab, x + (size_t)b * T, y + (size_t)b * T, window, f * hop - n_fft / 2, len, n_fft,
+                          threadIdx.x);
+    __syncthreads();
+}
+
+// ... and go on with per bin: Re/Im of X (index 0) and Y (1), and the unfloored powers px = |X|^2, py = |Y|^2 every
+// floor decision of the forward and of the adjoint is taken on.  Re/Im are the same bits in both kernels (fmaf only).
+// The powers are left to the compiler's contraction, per kernel: today an fma on the rounded re^2 in the forward, two
+// rounded products and an add in the adjoint, so at a tie within one rounding of the floor the two can decide
+// differently.  Writing the form out would change the results of one of them.
+__device__ __forceinline__ void spectral_bin(const float2* __restrict__ fr, const float2* __restrict__ tab, int k, int n_fft,
+                                             float (&re)[2], float (&im)[2], float& px, float& py) {
+    dft_bin<2>(fr, tab, k, n_fft, n_fft - 1, re, im);
+    px = re[0] * re[0] + im[0] * im[0];
+    py = re[1] * re[1] + im[1] * im[1];
 }
 
 __global__ __launch_bounds__(256) void spectral_frame_kernel(const float* __restrict__ x, const float* __restrict__ y,
@@ -36,7 +49,7 @@ __global__ __launch_bounds__(256) void spectral_frame_kernel(const float* __rest
     const int f = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
     const int half = n_fft / 2, nb = half + 1;
     int len;
-    if (f >= spectral_clip_frames(lengths, b, T, half, hop, len)) return;      // the whole workgroup, before any barrier
+    if (f >= centred_clip_frames(lengths, b, T, half + 1, hop, len)) return;   // the whole workgroup, before any barrier
     double* red = lds64;                                   // [4 waves][4]
     double* dl = red + 16;                                 // [n_mels] logmel(Y) - logmel(X)
     double* c2 = dl + n_mels;                              // [n_cep]  squared cepstral differences
@@ -44,34 +57,11 @@ __global__ __launch_bounds__(256) void spectral_frame_kernel(const float* __rest
     float2* tab = fr + n_fft;                              // [n_fft]  (cos, sin)(2 pi j / n_fft)
     float* magx = reinterpret_cast<float*>(tab + n_fft);   // [nb] unfloored |X|, with a filterbank only
     float* magy = magx + nb;                               // [nb]
-    const float* xa = x + (size_t)b * T;
-    const float* ya = y + (size_t)b * T;
-    for (int i = tid; i < n_fft; i += 256) {
-        int j = f * hop + i - half;      // reflect (no edge repeat) about the clip's own ends; len > half keeps j in [0, len)
-        if (j < 0) j = -j;
-        if (j >= len) j = 2 * (len - 1) - j;
-        const float w = window[i];
-        fr[i] = make_float2(xa[j] * w, ya[j] * w);
-        float s, c;
-        sincospif(2.f * (float)i / (float)n_fft, &s, &c);
-        tab[i] = make_float2(c, s);
-    }
-    __syncthreads();
-    const int mask = n_fft - 1;          // n_fft is a power of two
+    spectral_load(x, y, window, fr, tab, f, b, T, len, n_fft, hop);       // len > half keeps every index in [0, len)
     float a_num = 0.f, a_den = 0.f, a_abs = 0.f, a_lsd = 0.f;
     for (int k = tid; k < nb; k += 256) {
-        float xr = 0.f, xi = 0.f, yr = 0.f, yi = 0.f;
-        int ph = 0;
-        for (int i = 0; i < n_fft; ++i) {
-            const float2 v = fr[i];
-            const float2 t = tab[ph];
-            xr = fmaf(v.x, t.x, xr);
-            xi = fmaf(v.x, t.y, xi);
-            yr = fmaf(v.y, t.x, yr);
-            yi = fmaf(v.y, t.y, yi);
-            ph = (ph + k) & mask;
-        }
-        const float px = xr * xr + xi * xi, py = yr * yr + yi * yi;
+        float re[2], im[2], px, py;
+        spectral_bin(fr, tab, k, n_fft, re, im, px, py);
         if (basis) {
             magx[k] = sqrtf(px);
             magy[k] = sqrtf(py);
@@ -87,6 +77,7 @@ __global__ __launch_bounds__(256) void spectral_frame_kernel(const float* __rest
         a_lsd = fmaf(l, l, a_lsd);
     }
     const int wave = tid >> 6, lane = tid & 63;
+    // wave_sum's tree for the four sums at once: written as one loop the 24 shuffles overlap, as four calls they queue up
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) {
         a_num += __shfl_xor(a_num, off);
@@ -125,11 +116,8 @@ __global__ __launch_bounds__(256) void spectral_frame_kernel(const float* __rest
             sx = fmaf(wk, magx[k], sx);
             sy = fmaf(wk, magy[k], sy);
         }
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) {
-            sx += __shfl_xor(sx, off);
-            sy += __shfl_xor(sy, off);
-        }
+        sx = wave_sum(sx);
+        sy = wave_sum(sy);
         if (lane == 0) dl[m] = log((double)(sy < clip ? clip : sy)) - log((double)(sx < clip ? clip : sx));
     }
     __syncthreads();
@@ -156,7 +144,7 @@ __global__ __launch_bounds__(64) void spectral_clip_sum_kernel(const double* __r
     const int b = blockIdx.x, q = threadIdx.x;
     if (q >= SPEC_Q) return;
     int len;
-    const int nf = spectral_clip_frames(lengths, b, T, n_fft / 2, hop, len);
+    const int nf = centred_clip_frames(lengths, b, T, n_fft / 2 + 1, hop, len);
     const double* p = ws + (size_t)b * f_max * SPEC_Q + q;
     double s = 0.0;
     for (int f = 0; f < nf; ++f) s += p[(size_t)f * SPEC_Q];
@@ -164,15 +152,14 @@ __global__ __launch_bounds__(64) void spectral_clip_sum_kernel(const double* __r
 }
 
 // Adjoint of the two Parallel WaveGAN terms (sums 0 .. 2) with respect to x, stage 1 of 2: one workgroup per (frame,
-// clip).  Re/Im of x and y are recomputed exactly as spectral_frame_kernel computes them (same interleaved frames, same
-// table, same fmaf order), so every floor decision is the forward's.  With c0, c1 = coef[b][0], coef[b][1]
+// clip).  Re/Im of x and y and the two powers are recomputed by the forward's own spectral_load and spectral_bin, so
+// the floor decisions are the forward's (up to the contraction noted there).  With c0, c1 = coef[b][0], coef[b][1]
 //   dmag_k = -(c0 (|Y|_k - |X|_k) + c1 sgn(ln|Y|_k - ln|X|_k) / |X|_k)     where p_x >= 1e-7, else 0   (sgn(0) = 0)
 //   dRe_k = dmag_k Re_k / |X|_k,   dIm_k = dmag_k Im_k / |X|_k
 //   ws[b,f,i] = w[i] sum_k (dRe_k cos(2 pi i k / N) + dIm_k sin(2 pi i k / N))      (k = 0 .. N/2 ascending)
-// Nothing is accumulated across workgroups: the overlap-add is spectral_gather_kernel's.
+// Nothing is accumulated across workgroups: the overlap-add is ola_gather_kernel's.
 //
-// LDS: the forward's 16 N bytes and 8 K bytes of (dRe, dIm).  The inverse stage mirrors the transform's access pattern
-// with the roles swapped: the (dRe, dIm) row is one address for the whole wave (a broadcast), the table is read at
+// LDS: the forward's 16 N bytes and 8 K bytes of (dRe, dIm).  The inverse stage (idft_sample) reads the table at
 // (i k) & (N - 1) with a lane stride of k float2 -- conflict-free for odd k, 2^m-way where k = 2^m (odd) until the lanes
 // start to share addresses; the same cost profile as the forward's table reads at lane stride i, so the inverse runs at
 // the forward's LDS rate with half its FMAs per read pair.
@@ -185,38 +172,15 @@ __global__ __launch_bounds__(256) void spectral_frame_backward_kernel(const floa
     const int f = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
     const int half = n_fft / 2, nb = half + 1;
     int len;
-    if (f >= spectral_clip_frames(lengths, b, T, half, hop, len)) return;      // the whole workgroup, before any barrier
+    if (f >= centred_clip_frames(lengths, b, T, half + 1, hop, len)) return;   // the whole workgroup, before any barrier
     float2* fr = reinterpret_cast<float2*>(lds64);         // [n_fft]  (x, y) windowed
     float2* tab = fr + n_fft;                              // [n_fft]  (cos, sin)(2 pi j / n_fft)
     float2* dri = tab + n_fft;                             // [nb]     (dRe, dIm)
-    const float* xa = x + (size_t)b * T;
-    const float* ya = y + (size_t)b * T;
-    for (int i = tid; i < n_fft; i += 256) {
-        int j = f * hop + i - half;
-        if (j < 0) j = -j;
-        if (j >= len) j = 2 * (len - 1) - j;
-        const float w = window[i];
-        fr[i] = make_float2(xa[j] * w, ya[j] * w);
-        float s, c;
-        sincospif(2.f * (float)i / (float)n_fft, &s, &c);
-        tab[i] = make_float2(c, s);
-    }
-    __syncthreads();
-    const int mask = n_fft - 1;
+    spectral_load(x, y, window, fr, tab, f, b, T, len, n_fft, hop);
     const float c0 = (float)coef[(size_t)b * 2], c1 = (float)coef[(size_t)b * 2 + 1];
     for (int k = tid; k < nb; k += 256) {
-        float xr = 0.f, xi = 0.f, yr = 0.f, yi = 0.f;
-        int ph = 0;
-        for (int i = 0; i < n_fft; ++i) {
-            const float2 v = fr[i];
-            const float2 t = tab[ph];
-            xr = fmaf(v.x, t.x, xr);
-            xi = fmaf(v.x, t.y, xi);
-            yr = fmaf(v.y, t.x, yr);
-            yi = fmaf(v.y, t.y, yi);
-            ph = (ph + k) & mask;
-        }
-        const float px = xr * xr + xi * xi, py = yr * yr + yi * yi;
+        float re[2], im[2], px, py;
+        spectral_bin(fr, tab, k, n_fft, re, im, px, py);
         float2 d = make_float2(0.f, 0.f);
         if (px >= SPEC_FLOOR) {          // the floor passes no gradient below it (the tie counts as passed: clamp_min's rule)
             const float qy = py < SPEC_FLOOR ? SPEC_FLOOR : py;
@@ -224,66 +188,52 @@ __global__ __launch_bounds__(256) void spectral_frame_backward_kernel(const floa
             const float l = 0.5f * (logf(qy) - logf(px));
             const float sg = l > 0.f ? 1.f : (l < 0.f ? -1.f : 0.f);
             const float t = -(c0 * (my - mx) + c1 * sg / mx) / mx;
-            d = make_float2(t * xr, t * xi);
+            d = make_float2(t * re[0], t * im[0]);
         }
         dri[k] = d;
     }
     __syncthreads();
     float* o = ws + ((size_t)b * f_max + f) * n_fft;
-    for (int i = tid; i < n_fft; i += 256) {
-        float acc = 0.f;
-        int ph = 0;
-        for (int k = 0; k < nb; ++k) {
-            const float2 d = dri[k];
-            const float2 t = tab[ph];
-            acc = fmaf(d.x, t.x, acc);
-            acc = fmaf(d.y, t.y, acc);
-            ph = (ph + i) & mask;
-        }
-        o[i] = window[i] * acc;
-    }
+    for (int i = tid; i < n_fft; i += 256) o[i] = window[i] * idft_sample(dri, tab, i, nb, n_fft - 1);
 }
 
-// Every frame of the clip that covers padded position p, in ascending order, added to acc.
-__device__ __forceinline__ float spectral_gather_position(const float* __restrict__ wsb, int p, int n_fft, int hop, int nf, float acc) {
-    int lo = p - n_fft + 1;
-    lo = lo <= 0 ? 0 : (lo + hop - 1) / hop;
-    int hi = p / hop;
-    if (hi > nf - 1) hi = nf - 1;
-    for (int f = lo; f <= hi; ++f) acc += wsb[(size_t)f * n_fft + (p - f * hop)];
-    return acc;
-}
-
-// Adjoint, stage 2 of 2: one thread per sample.  Sample j < len_b sits at padded position j + N/2 and, through the
+// Adjoint, stage 2 of 2, of this file's loss and of the mel front-end's (ola_gather): one thread per sample.  Sample j < len_b sits at padded position j + N/2 and, through the
 // reflection about the clip's OWN ends, at N/2 - j (j = 1 .. N/2) and at N/2 + 2 (len_b - 1) - j
 // (j = len_b - 1 - N/2 .. len_b - 2) -- at len_b <= N/2 + 1 at both at once.  Summed in a fixed order: the direct
 // position, the left reflection, the right reflection, each in ascending frame order; a sample no frame covers
 // (hop > N) gets exactly 0.  Behind len_b: exactly 0 without `accumulate`, untouched with it.
-__global__ __launch_bounds__(256) void spectral_gather_kernel(const float* __restrict__ ws, const int* __restrict__ lengths,
-                                                              float* __restrict__ dx, int T, int n_fft, int hop, int f_max,
-                                                              int accumulate) {
+__global__ __launch_bounds__(256) void ola_gather_kernel(const float* __restrict__ ws, const int* __restrict__ lengths,
+                                                         float* __restrict__ dx, int T, int n_fft, int hop, int f_max,
+                                                         int accumulate) {
     const int j = blockIdx.x * 256 + threadIdx.x, b = blockIdx.y;
     if (j >= T) return;
     const int half = n_fft / 2;
     int len;
-    const int nf = spectral_clip_frames(lengths, b, T, half, hop, len);
+    const int nf = centred_clip_frames(lengths, b, T, half + 1, hop, len);
     float* o = dx + (size_t)b * T + j;
     if (nf == 0 || j >= len) {
         if (!accumulate) *o = 0.f;
         return;
     }
     const float* wsb = ws + (size_t)b * f_max * n_fft;
-    float acc = spectral_gather_position(wsb, j + half, n_fft, hop, nf, 0.f);
-    if (j >= 1 && j <= half) acc = spectral_gather_position(wsb, half - j, n_fft, hop, nf, acc);
-    if (j <= len - 2 && j >= len - 1 - half) acc = spectral_gather_position(wsb, half + 2 * (len - 1) - j, n_fft, hop, nf, acc);
+    float acc = ola_gather_position(wsb, j + half, n_fft, hop, nf, 0.f);
+    if (j >= 1 && j <= half) acc = ola_gather_position(wsb, half - j, n_fft, hop, nf, acc);
+    if (j <= len - 2 && j >= len - 1 - half) acc = ola_gather_position(wsb, half + 2 * (len - 1) - j, n_fft, hop, nf, acc);
     *o = accumulate ? *o + acc : acc;
+}
+
+int ola_gather(const float* ws, const int32_t* lengths, float* dx, int64_t B, int64_t T, int32_t n_fft, int32_t hop,
+               int f_max, int32_t accumulate, hipStream_t stream) {
+    hipLaunchKernelGGL(ola_gather_kernel, dim3((unsigned)((T + 255) / 256), (unsigned)B), dim3(256), 0, stream, ws, lengths,
+                       dx, (int)T, n_fft, hop, f_max, accumulate);
+    DWS_HIP(hipGetLastError());
+    return DWS_OK;
 }
 
 }  // namespace dws
 
 extern "C" int64_t dws_spectral_loss_backward_workspace(int64_t B, int64_t T, int32_t n_fft, int32_t hop) {
-    if (B < 1 || T < 1 || hop < 1 || T > INT32_MAX || B > 65535 || n_fft < 64 || n_fft > 2048 || (n_fft & (n_fft - 1)))
-        return 0;
+    if (B < 1 || T < 1 || hop < 1 || T > INT32_MAX || B > 65535 || !dws::n_fft_ok(n_fft, 2048)) return 0;
     return B * (T / hop + 1) * (int64_t)n_fft * (int64_t)sizeof(float);
 }
 
@@ -294,22 +244,12 @@ extern "C" int dws_spectral_loss_backward(const float* x, const float* y, int64_
     DWS_CHECK(x && y && window && coef && dx, DWS_ERR_INVALID, "dws_spectral_loss_backward: null argument");
     DWS_CHECK(workspace, DWS_ERR_INVALID,
               "dws_spectral_loss_backward: null workspace (dws_spectral_loss_backward_workspace bytes)");
-    DWS_CHECK(n_fft >= 64 && n_fft <= 2048 && (n_fft & (n_fft - 1)) == 0, DWS_ERR_INVALID,
-              "dws_spectral_loss_backward: n_fft = %d (powers of two 64..2048)", n_fft);
+    DWS_CHECK(n_fft_ok(n_fft, 2048), DWS_ERR_INVALID, "dws_spectral_loss_backward: n_fft = %d (powers of two 64..2048)",
+              n_fft);
     DWS_CHECK(B > 0 && B <= 65535 && hop > 0 && T > 0 && T <= INT32_MAX - n_fft, DWS_ERR_INVALID,
               "dws_spectral_loss_backward: bad shape (B = %lld, T = %lld, hop = %d)", (long long)B, (long long)T, hop);
-    DWS_CHECK((lengths == nullptr) == (lengths_host == nullptr), DWS_ERR_INVALID,
-              "dws_spectral_loss_backward: lengths (device) and lengths_host (the same numbers on the host) come together");
-    if (lengths_host) {
-        for (int64_t b = 0; b < B; ++b)
-            DWS_CHECK(lengths_host[b] > n_fft / 2 && lengths_host[b] <= T, DWS_ERR_INVALID,
-                      "dws_spectral_loss_backward: clip %lld has %d samples (n_fft = %d needs %d .. T = %lld)", (long long)b,
-                      lengths_host[b], n_fft, n_fft / 2 + 1, (long long)T);
-    } else {
-        DWS_CHECK(T > n_fft / 2, DWS_ERR_INVALID,
-                  "dws_spectral_loss_backward: T = %lld (n_fft = %d needs at least %d samples)", (long long)T, n_fft,
-                  n_fft / 2 + 1);
-    }
+    // reflect padding: a clip holds at least n_fft / 2 + 1 samples
+    if (check_clip_lengths("dws_spectral_loss_backward", B, T, lengths, lengths_host, n_fft / 2 + 1) < 0) return DWS_ERR_INVALID;
     const int f_max = (int)(T / hop) + 1;
     const size_t lds = (size_t)n_fft * 16 + (size_t)(n_fft / 2 + 1) * 8;
     DWS_HIP(hipFuncSetAttribute((const void*)spectral_frame_backward_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -317,10 +257,7 @@ extern "C" int dws_spectral_loss_backward(const float* x, const float* y, int64_
     hipLaunchKernelGGL(spectral_frame_backward_kernel, dim3((unsigned)f_max, (unsigned)B), dim3(256), lds, (hipStream_t)stream,
                        x, y, lengths, window, coef, workspace, (int)T, n_fft, hop, f_max);
     DWS_HIP(hipGetLastError());
-    hipLaunchKernelGGL(spectral_gather_kernel, dim3((unsigned)((T + 255) / 256), (unsigned)B), dim3(256), 0,
-                       (hipStream_t)stream, workspace, lengths, dx, (int)T, n_fft, hop, f_max, accumulate);
-    DWS_HIP(hipGetLastError());
-    return DWS_OK;
+    return ola_gather(workspace, lengths, dx, B, T, n_fft, hop, f_max, accumulate, (hipStream_t)stream);
 }
 
 extern "C" int64_t dws_spectral_distance_workspace(int64_t B, int64_t T, int32_t hop) {
@@ -335,21 +272,11 @@ extern "C" int dws_spectral_distance(const float* x, const float* y, int64_t B, 
     using namespace dws;
     DWS_CHECK(x && y && window && out, DWS_ERR_INVALID, "dws_spectral_distance: null argument");
     DWS_CHECK(workspace, DWS_ERR_INVALID, "dws_spectral_distance: null workspace (dws_spectral_distance_workspace bytes)");
-    DWS_CHECK(n_fft >= 64 && n_fft <= 2048 && (n_fft & (n_fft - 1)) == 0, DWS_ERR_INVALID,
-              "dws_spectral_distance: n_fft = %d (powers of two 64..2048)", n_fft);
+    DWS_CHECK(n_fft_ok(n_fft, 2048), DWS_ERR_INVALID, "dws_spectral_distance: n_fft = %d (powers of two 64..2048)", n_fft);
     DWS_CHECK(B > 0 && B <= 65535 && hop > 0 && T > 0 && T <= INT32_MAX - n_fft, DWS_ERR_INVALID,
               "dws_spectral_distance: bad shape (B = %lld, T = %lld, hop = %d)", (long long)B, (long long)T, hop);
-    DWS_CHECK((lengths == nullptr) == (lengths_host == nullptr), DWS_ERR_INVALID,
-              "dws_spectral_distance: lengths (device) and lengths_host (the same numbers on the host) come together");
-    if (lengths_host) {
-        for (int64_t b = 0; b < B; ++b)
-            DWS_CHECK(lengths_host[b] > n_fft / 2 && lengths_host[b] <= T, DWS_ERR_INVALID,
-                      "dws_spectral_distance: clip %lld has %d samples (n_fft = %d needs %d .. T = %lld)", (long long)b,
-                      lengths_host[b], n_fft, n_fft / 2 + 1, (long long)T);
-    } else {
-        DWS_CHECK(T > n_fft / 2, DWS_ERR_INVALID, "dws_spectral_distance: T = %lld (n_fft = %d needs at least %d samples)",
-                  (long long)T, n_fft, n_fft / 2 + 1);
-    }
+    // reflect padding: a clip holds at least n_fft / 2 + 1 samples
+    if (check_clip_lengths("dws_spectral_distance", B, T, lengths, lengths_host, n_fft / 2 + 1) < 0) return DWS_ERR_INVALID;
     DWS_CHECK(mel_basis ? (n_mels > 0 && n_mels <= 4096) : (n_mels == 0 && cep == nullptr), DWS_ERR_INVALID,
               "dws_spectral_distance: n_mels = %d %s a filterbank (a cepstral table needs one)", n_mels,
               mel_basis ? "with" : "without");

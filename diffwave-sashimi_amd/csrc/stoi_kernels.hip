@@ -18,7 +18,7 @@
 // len_b samples alone.
 #include <cfloat>
 
-#include "dws_common.h"
+#include "stft_core.h"
 
 namespace dws {
 
@@ -52,12 +52,6 @@ __device__ __forceinline__ int stoi_clip_frames(const int* __restrict__ lengths,
     return (len >= frame && len <= T) ? (len - frame) / hop + 1 : 0;
 }
 
-__device__ __forceinline__ double stoi_wave_sum(double v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-    return v;
-}
-
 // grid (ceil(F / 4), B), 256 threads: wave w of workgroup g takes frame 4 g + w
 __global__ __launch_bounds__(256) void stoi_energy_kernel(const float* __restrict__ y, const int* __restrict__ lengths,
                                                           const float* __restrict__ window, double* __restrict__ e, int T,
@@ -71,7 +65,7 @@ __global__ __launch_bounds__(256) void stoi_energy_kernel(const float* __restric
         const double v = (double)window[n] * (double)s[n];
         acc = fma(v, v, acc);
     }
-    acc = stoi_wave_sum(acc);
+    acc = wave_sum(acc);
     if (lane == 0) e[(size_t)b * F + j] = 20.0 * log10(sqrt(acc) + DBL_EPSILON);
 }
 
@@ -152,31 +146,18 @@ __global__ __launch_bounds__(256) void stoi_band_kernel(const float* __restrict_
         const double w = (double)window[n];
         fr[n] = make_float2((float)(w * sx), (float)(w * sy));
     }
-    for (int i = tid; i < n_fft; i += 256) {
-        float s, c;
-        sincospif(2.f * (float)i / (float)n_fft, &s, &c);
-        tab[i] = make_float2(c, s);
-    }
+    for (int i = tid; i < n_fft; i += 256) tab[i] = twiddle(i, n_fft);
     __syncthreads();
-    const int mask = n_fft - 1;
     for (int q = tid; q < nb; q += 256) {
         bool used = false;
         for (int j = 0; j < J; ++j) used = used || obm[(size_t)j * nb + q] != 0.f;
         float px = 0.f, py = 0.f;
         if (used) {
-            float xr = 0.f, xi = 0.f, yr = 0.f, yi = 0.f;
-            int ph = 0;
-            for (int i = 0; i < frame; ++i) {
-                const float2 v = fr[i];
-                const float2 t = tab[ph];
-                xr = fmaf(v.x, t.x, xr);
-                xi = fmaf(v.x, t.y, xi);
-                yr = fmaf(v.y, t.x, yr);
-                yi = fmaf(v.y, t.y, yi);
-                ph = (ph + q) & mask;
-            }
-            px = xr * xr + xi * xi;
-            py = yr * yr + yi * yi;
+            float re[2], im[2];
+            dft_bin<2>(fr, tab, q, frame, n_fft - 1, re, im);      // `frame` samples against the n_fft-point table
+            // written out: `re re + im im` leaves the contraction (which product is rounded on its own) to the compiler
+            px = fmaf(re[0], re[0], im[0] * im[0]);
+            py = fmaf(re[1], re[1], im[1] * im[1]);
         }
         pw[q] = make_float2(px, py);
     }
@@ -190,8 +171,8 @@ __global__ __launch_bounds__(256) void stoi_band_kernel(const float* __restrict_
             sx = fma(w, (double)pw[q].x, sx);
             sy = fma(w, (double)pw[q].y, sy);
         }
-        sx = stoi_wave_sum(sx);
-        sy = stoi_wave_sum(sy);
+        sx = wave_sum(sx);
+        sy = wave_sum(sy);
         if (lane == 0) {
             bands[(((size_t)b * 2 + 0) * F + k) * J + j] = sqrt(sx);
             bands[(((size_t)b * 2 + 1) * F + k) * J + j] = sqrt(sy);
@@ -329,8 +310,7 @@ extern "C" int dws_stoi(const float* x, const float* y, int64_t B, int64_t T, co
     using namespace dws;
     DWS_CHECK(x && y && window && obm && out, DWS_ERR_INVALID, "dws_stoi: null argument");
     DWS_CHECK(workspace, DWS_ERR_INVALID, "dws_stoi: null workspace (dws_stoi_workspace bytes)");
-    DWS_CHECK(n_fft >= 64 && n_fft <= 2048 && (n_fft & (n_fft - 1)) == 0, DWS_ERR_INVALID,
-              "dws_stoi: n_fft = %d (powers of two 64..2048)", n_fft);
+    DWS_CHECK(n_fft_ok(n_fft, 2048), DWS_ERR_INVALID, "dws_stoi: n_fft = %d (powers of two 64..2048)", n_fft);
     DWS_CHECK(frame >= 1 && frame <= n_fft, DWS_ERR_INVALID, "dws_stoi: frame = %d (1 .. n_fft = %d)", frame, n_fft);
     DWS_CHECK(hop >= 1, DWS_ERR_INVALID, "dws_stoi: hop = %d (at least 1)", hop);
     DWS_CHECK(segment >= 2 && segment <= STOI_MAX_SEGMENT, DWS_ERR_INVALID, "dws_stoi: segment = %d frames (2 .. %d)", segment,
@@ -341,20 +321,8 @@ extern "C" int dws_stoi(const float* x, const float* y, int64_t B, int64_t T, co
               "dws_stoi: bad shape (B = %lld, T = %lld)", (long long)B, (long long)T);
     DWS_CHECK(dyn_range > 0.0 && dyn_range < 1e6 && beta > -1e3 && beta < 1e3, DWS_ERR_INVALID,
               "dws_stoi: beta = %g dB, dynamic range = %g dB", beta, dyn_range);
-    DWS_CHECK((lengths == nullptr) == (lengths_host == nullptr), DWS_ERR_INVALID,
-              "dws_stoi: lengths (device) and lengths_host (the same numbers on the host) come together");
-    int64_t longest = T;
-    if (lengths_host) {
-        longest = 0;
-        for (int64_t b = 0; b < B; ++b) {
-            DWS_CHECK(lengths_host[b] >= frame && lengths_host[b] <= T, DWS_ERR_INVALID,
-                      "dws_stoi: clip %lld has %d samples (frame = %d .. T = %lld)", (long long)b, lengths_host[b], frame,
-                      (long long)T);
-            if (lengths_host[b] > longest) longest = lengths_host[b];
-        }
-    } else {
-        DWS_CHECK(T >= frame, DWS_ERR_INVALID, "dws_stoi: T = %lld (one frame is %d samples)", (long long)T, frame);
-    }
+    const int64_t longest = check_clip_lengths("dws_stoi", B, T, lengths, lengths_host, frame);      // one frame at least
+    if (longest < 0) return DWS_ERR_INVALID;
     hipStream_t s = (hipStream_t)stream;
     const int64_t F = stoi_frames(T, frame, hop);          // the workspace's rows
     const int64_t Fb = stoi_frames(longest, frame, hop);   // the most frames a clip of this batch can keep

@@ -105,6 +105,19 @@ def _need_gpu(x, y):
         raise RuntimeError("libdws runs on the GPU only: move both waveforms to one cuda device (there is no CPU fallback)")
 
 
+def _f32(*waves):
+    """The waveforms detached, float32 and contiguous, as a tuple: what the kernels read."""
+    return tuple(w.detach().to(torch.float32).contiguous() for w in waves)
+
+
+def _length_args(host, dev, B, dev_len=None):
+    """The ``(lengths, lengths_host)`` pair of a C entry point from the host integers (``(None, None)`` without them):
+    an int32 tensor on ``dev`` -- ``dev_len`` where the caller already holds one -- and a ctypes array."""
+    if host is None:
+        return None, None
+    return (torch.tensor(host, dtype=torch.int32).to(dev) if dev_len is None else dev_len), (ctypes.c_int32 * B)(*host)
+
+
 def _window(device, n_fft, win):
     key = (device, n_fft, win)
     if key not in _windows:
@@ -127,11 +140,7 @@ def _run(x, y, host, n_fft, hop, win, basis, cep, dev_len=None):
     dev = x.device
     out = torch.empty(B, len(SUMS), device=dev, dtype=torch.float64)
     ws = torch.empty(lib.dws_spectral_distance_workspace(B, T, hop) // 8, device=dev, dtype=torch.float64)
-    if host is None:
-        dev_len = host_len = None
-    else:
-        host_len = (ctypes.c_int32 * B)(*host)
-        dev_len = torch.tensor(host, dtype=torch.int32).to(dev) if dev_len is None else dev_len
+    dev_len, host_len = _length_args(host, dev, B, dev_len)
     n_mels = 0 if basis is None else int(basis.shape[0])
     n_cep = 0 if cep is None else int(cep.shape[0])
     with torch.cuda.device(dev):
@@ -154,8 +163,7 @@ def spectral_sums(x, y, lengths=None, *, n_fft, hop, win, mel_basis=None, n_cep=
     if not _is_int(n_cep) or n_cep < 0 or n_cep > 256 or (n_cep and mel_basis is None):
         raise ValueError(f"spectral_sums: n_cep = {n_cep!r} (0 .. 256, and a mel_basis with it)")
     _need_gpu(x, y)
-    x = x.detach().to(torch.float32).contiguous()
-    y = y.detach().to(torch.float32).contiguous()
+    x, y = _f32(x, y)
     basis = None if mel_basis is None else mel_basis.to(device=x.device, dtype=torch.float32).contiguous()
     cep = _cep(x.device, n_cep, int(basis.shape[0])) if n_cep else None
     return _run(x, y, host, n_fft, hop, win, basis, cep).cpu()
@@ -188,17 +196,13 @@ def spectral_metrics(x, y, lengths=None, *, stft=None, resolutions=MR_STFT_RESOL
     ``n_fft / 2 + 1`` raises ValueError naming the resolution and the clip; CPU tensors raise RuntimeError."""
     stft = default_stft() if stft is None else stft
     x, y, host, lens = _pair(x, y, lengths)
-    resolutions = [tuple(r) for r in resolutions]
-    if not resolutions or any(len(r) != 3 for r in resolutions):
-        raise ValueError(f"spectral_metrics: resolutions = {resolutions!r}: expected (n_fft, hop, win) triples")
+    resolutions = check_resolutions(resolutions, lens)
     own = (stft.filter_length, stft.hop_length, stft.win_length)
-    for r in resolutions + [own]:
-        check_resolution(*r, lens)
+    check_resolution(*own, lens)
     if not _is_int(n_cep) or not 1 <= n_cep <= min(256, stft.n_mel_channels - 1):
         raise ValueError(f"spectral_metrics: n_cep = {n_cep!r} (1 .. min(256, n_mel_channels - 1))")
     _need_gpu(x, y)
-    x = x.detach().to(torch.float32).contiguous()
-    y = y.detach().to(torch.float32).contiguous()
+    x, y = _f32(x, y)
     out = {}
     total = 0.0
     for r in resolutions:
@@ -271,12 +275,6 @@ def check_pitch(lengths, sampling_rate=22050, hop=256, win=1024, fmin=50.0, fmax
     return tau_lo, tau_hi
 
 
-def _pitch_args(host, dev, B, dev_len=None):
-    if host is None:
-        return None, None
-    return (torch.tensor(host, dtype=torch.int32).to(dev) if dev_len is None else dev_len), (ctypes.c_int32 * B)(*host)
-
-
 def pitch_track(x, lengths=None, *, sampling_rate=22050, hop=256, win=1024, fmin=50.0, fmax=550.0, threshold=0.15):
     """YIN pitch track (de Cheveigne & Kawahara, 2002; fixed threshold) of ``x`` ([B, T] or [B, 1, T], cuda):
     ``(f0, periodicity)``, both float32 [B, T // hop + 1] on the device.  Frame ``f`` is centred on sample ``f hop`` (the
@@ -288,11 +286,11 @@ def pitch_track(x, lengths=None, *, sampling_rate=22050, hop=256, win=1024, fmin
     x, _, host, lens = _pair(x, x, lengths, "pitch_track")
     tau_lo, tau_hi = check_pitch(lens, sampling_rate, hop, win, fmin, fmax, threshold, "pitch_track")
     _need_gpu(x, x)
-    x = x.detach().to(torch.float32).contiguous()
+    (x,) = _f32(x)
     lib = _lib.load()
     B, T = x.shape
     track = torch.empty(B, T // hop + 1, 2, device=x.device, dtype=torch.float32)
-    dev_len, host_len = _pitch_args(host, x.device, B)
+    dev_len, host_len = _length_args(host, x.device, B)
     with torch.cuda.device(x.device):
         _lib.check(lib.dws_pitch_track(x.data_ptr(), B, T, _lib.ptr(dev_len), host_len, hop, win, tau_lo, tau_hi,
                                        float(threshold), float(sampling_rate), track.data_ptr(), _lib.current_stream()))
@@ -304,8 +302,7 @@ def _pitch_sums(what, x, y, lengths, sampling_rate, hop, win, fmin, fmax, thresh
     x, y, host, lens = _pair(x, y, lengths, what)
     tau_lo, tau_hi = check_pitch(lens, sampling_rate, hop, win, fmin, fmax, threshold, what)
     _need_gpu(x, y)
-    x = x.detach().to(torch.float32).contiguous()
-    y = y.detach().to(torch.float32).contiguous()
+    x, y = _f32(x, y)
     return _pitch_run(x, y, host, sampling_rate, hop, win, tau_lo, tau_hi, threshold).cpu(), lens
 
 
@@ -316,7 +313,7 @@ def _pitch_run(x, y, host, sampling_rate, hop, win, tau_lo, tau_hi, threshold):
     dev = x.device
     out = torch.empty(B, len(PITCH_SUMS), device=dev, dtype=torch.float64)
     ws = torch.empty(lib.dws_pitch_distance_workspace(B, T, hop) // 4, device=dev, dtype=torch.float32)
-    dev_len, host_len = _pitch_args(host, dev, B)
+    dev_len, host_len = _length_args(host, dev, B)
     with torch.cuda.device(dev):
         _lib.check(lib.dws_pitch_distance(x.data_ptr(), y.data_ptr(), B, T, _lib.ptr(dev_len), host_len, hop, win, tau_lo,
                                           tau_hi, float(threshold), float(sampling_rate), ws.data_ptr(), out.data_ptr(),
@@ -412,7 +409,7 @@ def stoi_sums(x, y, lengths=None):
     x, y, host, lens = _pair(x, y, lengths, "stoi_sums")
     stoi_lengths(lens, STOI_DEFAULTS["fs"], "stoi_sums")
     _need_gpu(x, y)
-    return _stoi_run(x.detach().to(torch.float32).contiguous(), y.detach().to(torch.float32).contiguous(), host).cpu()
+    return _stoi_run(*_f32(x, y), host).cpu()
 
 
 def _stoi_run(x, y, host):
@@ -424,7 +421,7 @@ def _stoi_run(x, y, host):
     window, obm = _stoi_constants(dev)
     out = torch.empty(B, len(STOI_SUMS), device=dev, dtype=torch.float64)
     ws = torch.empty(lib.dws_stoi_workspace(B, T, d["frame"], d["hop"], d["n_bands"]) // 8, device=dev, dtype=torch.float64)
-    dev_len, host_len = _pitch_args(host, dev, B)
+    dev_len, host_len = _length_args(host, dev, B)
     with torch.cuda.device(dev):
         _lib.check(lib.dws_stoi(x.data_ptr(), y.data_ptr(), B, T, _lib.ptr(dev_len), host_len, window.data_ptr(), d["frame"],
                                 d["hop"], d["n_fft"], obm.data_ptr(), d["n_bands"], d["segment"], d["beta"], d["dyn_range"],
@@ -451,8 +448,7 @@ def stoi(x, y, lengths=None, *, sampling_rate=22050):
     x, y, host, lens = _pair(x, y, lengths, "stoi")
     lens10 = stoi_lengths(lens, sampling_rate)
     _need_gpu(x, y)
-    x = x.detach().to(torch.float32).contiguous()
-    y = y.detach().to(torch.float32).contiguous()
+    x, y = _f32(x, y)
     fs = STOI_DEFAULTS["fs"]
     if sampling_rate != fs:
         x, _ = audio.resample(x, sampling_rate, fs, host)
@@ -522,7 +518,7 @@ class _MrStftBackward(torch.autograd.Function):
         lib = _lib.load()
         B, T = x.shape
         dev = x.device
-        host_len = None if host is None else (ctypes.c_int32 * B)(*host)
+        dev_len, host_len = _length_args(host, dev, B, dev_len)
         g = g.to(torch.float64) / len(resolutions)
         dx = torch.empty_like(x)
         sums = sums.unbind(0)
@@ -586,16 +582,14 @@ def mr_stft_loss(x, y, lengths=None, *, resolutions=MR_STFT_RESOLUTIONS, sc_weig
         raise ValueError("mr_stft_loss: y requires grad, and the gradient with respect to the reference is not built "
                          "(pass y.detach())")
     _need_gpu(x, y)
-    y = y.detach().to(torch.float32).contiguous()
+    (y,) = _f32(y)
     dev = x.device
+    dev_len, _ = _length_args(host, dev, len(lens))
     if host is None:
-        dev_len = None
         frames = [float(lens[0] // r[1] + 1) for r in resolutions]
     else:
-        dev_len = torch.tensor(host, dtype=torch.int32).to(dev)
         frames = [torch.tensor([n // r[1] + 1 for n in lens], dtype=torch.float64).to(dev) for r in resolutions]
     cfg = (host, frames, resolutions, sc_weight, mag_weight)
     if x.requires_grad and torch.is_grad_enabled():
         return _MrStftLoss.apply(x.to(torch.float32).contiguous(), y, dev_len, cfg)
-    return _loss_value(x.detach().to(torch.float32).contiguous(), y, host, dev_len, frames, resolutions, sc_weight,
-                       mag_weight)[0]
+    return _loss_value(*_f32(x), y, host, dev_len, frames, resolutions, sc_weight, mag_weight)[0]
