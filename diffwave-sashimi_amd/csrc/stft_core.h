@@ -1,5 +1,6 @@
-// The short-time DFT core of the analysis kernels (mel_kernels, spectral_kernels, stoi_kernels, pitch_kernels): every
-// piece the four files share exists here once, so the adjoints recompute the forward's numbers -- and take its clamp and
+// The short-time DFT core of the analysis kernels (mel_kernels, spectral_kernels, stoi_kernels, pitch_kernels) and of the
+// inversion kernels (griffinlim_kernels, whose projection is a forward and an inverse stage in one workgroup): every
+// piece the files share exists here once, so the adjoints recompute the forward's numbers -- and take its clamp and
 // floor decisions -- by calling the forward's own code.
 //
 // Layout: a workgroup of 256 threads owns one frame.  The twiddle table is float2 (cos, sin)(2 pi i / n_fft), i = 0 ..

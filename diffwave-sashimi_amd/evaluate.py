@@ -23,6 +23,13 @@ for such a value (strict JSON has no NaN) and the parameters under ``"pitch"``.
 two more rows, printed last.  A pair that keeps fewer than 30 frames has neither; it is treated like an undefined pitch
 value (left out of the mean, ``null`` in ``--json``, the parameters under ``"stoi"``).
 
+``--griffin-lim N`` (``--griffin-lim-momentum``, default 0) adds the baseline that needs no weights: the engine's log-mel of
+every recording at the run's STFT keys is inverted with N Griffin-Lim iterations (``TacotronSTFT.mel_to_audio``, in the same
+ragged batches) and scored against the recording -- cut to its whole hops, ``samples // hop_length`` of them -- with the
+same metric calls as the generated file, ``--pitch`` and ``--stoi`` included.  A second block of rows headed ``griffin-lim
+baseline (N iterations)`` is printed; ``--json`` receives ``baseline_<metric>`` per file and the parameters and the
+block's summary under ``"griffin_lim"``.
+
 ``--resample``: a wav whose rate is not ``--sampling-rate`` is converted on the GPU after loading (``audio.resample``)
 instead of being refused; the one-hop pairing check and the trim see the converted clips, and the number of converted
 files is printed.
@@ -163,6 +170,28 @@ def evaluate_pairs(clips, stft, batch_size=16, device=None, resolutions=_metrics
     return rows
 
 
+def griffin_lim_clips(clips, stft, n_iters, momentum=0.0, batch_size=16, device=None):
+    """The Griffin-Lim baseline of a list of ``(x, y)`` clips: ``(g, y')`` per clip, ``y'`` the recording cut to its whole
+    hops and ``g = stft.mel_to_audio(stft.mel_spectrogram(y'))`` with ``n_iters`` iterations, of the same length.  The mels
+    are taken clip by clip (a clip's own reflection), the inversions run in the ragged batches of ``evaluate_pairs``; a
+    clip's estimate does not depend on its batch."""
+    from .generate import ragged_plan
+    if device is None:
+        device = "cuda" if torch.cuda.is_available() else "cpu"
+    hop = stft.hop_length
+    lens = [int(y.shape[0]) // hop * hop for _, y in clips]
+    out = [None] * len(clips)
+    for batch in ragged_plan(lens, batch_size) if clips else []:
+        mels = [stft.mel_spectrogram(clips[k][1][None, :lens[k]].to(device)) for k in batch]
+        mel = torch.zeros(len(batch), mels[0].shape[1], mels[0].shape[2], device=device)
+        for b, m in enumerate(mels):
+            mel[b, :, :m.shape[2]] = m[0]
+        g = stft.mel_to_audio(mel, n_iters=n_iters, momentum=momentum, lengths=[lens[k] for k in batch]).cpu()
+        for b, k in enumerate(batch):
+            out[k] = (g[b, :lens[k]].clone(), clips[k][1][:lens[k]])
+    return out
+
+
 def summarise(rows):
     """Per metric ``(mean, standard deviation, half width of the 95 % interval of the mean, n)``: the sample standard
     deviation (n - 1) and the normal interval 1.96 s / sqrt(n); both 0 for a single file."""
@@ -216,6 +245,9 @@ def build_parser():
     ap.add_argument("--pitch-fmax", type=float, help="highest F0 searched, Hz (default 550)")
     ap.add_argument("--pitch-threshold", type=float, help="YIN threshold (default 0.15)")
     ap.add_argument("--stoi", action="store_true", help="add STOI and ESTOI (metrics.stoi; both files go to 10 kHz)")
+    ap.add_argument("--griffin-lim", type=int, metavar="N",
+                    help="add the baseline rows: every recording's mel inverted with N Griffin-Lim iterations")
+    ap.add_argument("--griffin-lim-momentum", type=float, help="Fast Griffin-Lim's momentum in [0, 1) (default 0)")
     ap.add_argument("--resample", action="store_true",
                     help="convert a wav at another rate to --sampling-rate on the GPU instead of refusing it")
     ap.add_argument("overrides", nargs="*", help="key=value overrides of --config-dir, e.g. experiment=ljspeech")
@@ -238,6 +270,13 @@ def main(argv=None):
     if pitch is not None:       # the parameters are checked before a file is read (the clips: once they are loaded)
         _metrics.check_pitch([], what="evaluate --pitch", **pitch)
 
+    baseline = None             # --griffin-lim: (N, momentum), checked before a file is read
+    if args.griffin_lim is None and args.griffin_lim_momentum is not None:
+        raise ValueError("evaluate: --griffin-lim-momentum needs --griffin-lim")
+    if args.griffin_lim is not None:
+        from .mel import check_griffin_lim
+        baseline = check_griffin_lim(args.griffin_lim, args.griffin_lim_momentum or 0.0, "evaluate --griffin-lim")
+
     pairs, lone_gen, lone_ref = pair_files(args.generated, args.reference)
     for name, lone in (("generated", lone_gen), ("reference", lone_ref)):
         if lone:
@@ -256,16 +295,24 @@ def main(argv=None):
     stft = TacotronSTFT(filter_length=keys["filter_length"], hop_length=keys["hop_length"], win_length=keys["win_length"],
                         sampling_rate=keys["sampling_rate"], mel_fmin=keys["mel_fmin"], mel_fmax=keys["mel_fmax"])
     nan_keys = (_metrics.PITCH_METRICS if pitch is not None else ()) + (_metrics.STOI_METRICS if args.stoi else ())
-    if not nan_keys:
-        rows = evaluate_pairs(clips, stft, args.batch_size)
-        summary = summarise(rows)
-    else:
-        rows = evaluate_pairs(clips, stft, args.batch_size, pitch=pitch, stoi=keys["sampling_rate"] if args.stoi else None)
-        summary = summarise([{k: v for k, v in row.items() if k not in nan_keys} for row in rows])
-        summary.update(summarise_finite(rows, nan_keys))
-    print(f"{'metric':<20}{'mean':>12}{'std':>12}{'95% +-':>12}{'n':>6}")
-    for key, (mean, sd, ci, n) in summary.items():
-        print(f"{key:<20}{mean:>12.6f}{sd:>12.6f}{ci:>12.6f}{n:>6d}")
+
+    def score(clips):
+        if not nan_keys:
+            rows = evaluate_pairs(clips, stft, args.batch_size)
+            summary = summarise(rows)
+        else:
+            rows = evaluate_pairs(clips, stft, args.batch_size, pitch=pitch, stoi=keys["sampling_rate"] if args.stoi else None)
+            summary = summarise([{k: v for k, v in row.items() if k not in nan_keys} for row in rows])
+            summary.update(summarise_finite(rows, nan_keys))
+        print(f"{'metric':<20}{'mean':>12}{'std':>12}{'95% +-':>12}{'n':>6}")
+        for key, (mean, sd, ci, n) in summary.items():
+            print(f"{key:<20}{mean:>12.6f}{sd:>12.6f}{ci:>12.6f}{n:>6d}")
+        return rows, summary
+
+    rows, summary = score(clips)
+    if baseline is not None:
+        print(f"griffin-lim baseline ({baseline[0]} iterations)")
+        base_rows, base_summary = score(griffin_lim_clips(clips, stft, *baseline, batch_size=args.batch_size))
     if args.json:
         record = {"stft": keys,
                   "files": [dict(generated=g + ".wav", reference=r + ".wav", samples=int(c[0].shape[0]), **row)
@@ -278,12 +325,21 @@ def main(argv=None):
             record["stoi"] = dict(_metrics.STOI_DEFAULTS, sampling_rate=keys["sampling_rate"])
         if converted is not None:
             record["converted"] = [os.path.basename(p) for p in converted]
+        base_keys = ()
+        if baseline is not None:
+            for entry, row in zip(record["files"], base_rows):
+                entry.update({"baseline_" + k: v for k, v in row.items()})
+            base_keys = tuple("baseline_" + k for k in nan_keys)
+            record["griffin_lim"] = dict(n_iters=baseline[0], momentum=baseline[1], seed=0,
+                                         summary={k: dict(mean=m, std=s, ci95=c, n=n) for k, (m, s, c, n) in base_summary.items()})
         if nan_keys:                    # an undefined value (NaN) is written as null: strict JSON has no NaN
             for entry in record["files"]:
-                entry.update({k: None for k in nan_keys if math.isnan(entry[k])})
+                entry.update({k: None for k in nan_keys + base_keys if math.isnan(entry[k])})
             for k in nan_keys:
                 if math.isnan(record["summary"][k]["mean"]):
                     record["summary"][k]["mean"] = None
+                if baseline is not None and math.isnan(record["griffin_lim"]["summary"][k]["mean"]):
+                    record["griffin_lim"]["summary"][k]["mean"] = None
         with open(args.json, "w") as f:
             json.dump(record, f, indent=1)
     return rows

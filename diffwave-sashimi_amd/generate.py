@@ -481,7 +481,8 @@ def generate(rank, diffusion_cfg, model_cfg, dataset_cfg, ckpt_iter="max", n_sam
              guide_name=None, guide_op=None, guide_clip=None, guide_factor=None, guide_scale=None, label=None,
              cfg_scale=None, ema=None, clip_seeds=None, clips=None, num_ranks=None, report_mel=None, mel_errors=None,
              mel_names=None, prior=None, prior_energy_max=None, prior_energy_min=None, prior_std_min=None,
-             report_metrics=None, metric_rows=None, report_pitch=None, report_stoi=None):
+             report_metrics=None, metric_rows=None, report_pitch=None, report_stoi=None, start_griffinlim=None,
+             griffinlim_momentum=None):
     """``generate.py:58-200``.  ``ckpt_iter`` may additionally be ``"init"``: seeded random weights
     (no checkpoint), for smoke runs without trained weights.  ``precision`` (not in the reference; CLI:
     ``+engine.precision=bf16x6|f16x3``): the engine's opt-in matrix arithmetic, see ``include/dws.h``.
@@ -501,6 +502,14 @@ def generate(rank, diffusion_cfg, model_cfg, dataset_cfg, ckpt_iter="max", n_sam
     ``resample_jump`` with ``resample_n`` (both or neither; they need ``known_name``) run the inpainting with RePaint's
     resampling: at every ``resample_jump``-th position the chain goes back up that many steps and down again,
     ``resample_n`` times in all (``sampling.repaint_program``).
+
+    Warm start (not in the reference; mel-conditional runs, ``mel_name`` and ``mel_names``): ``start_griffinlim`` = N
+    (0 .. 4096) with ``start_step`` starts the loop from the Griffin-Lim estimate of the conditioning mel itself
+    (``TacotronSTFT.mel_to_audio`` at the dataset's STFT keys, N iterations, ``griffinlim_momentum`` in [0, 1), default
+    0) instead of a wav; the mel's last frame is repeated once so that the estimate has frames x hop samples, and with
+    ``mel_names`` every clip is inverted at its own length.  Everything behind it is the partial start above
+    (``start_noise`` included).  Refused on unconditional runs, together with ``start_name``, without ``start_step``, with
+    ``mel_path`` (the STFT keys of stored mels are unknown) and with ``model.subbands``.
 
     Restoration (not in the reference; ``sampler`` ddpm or ddim, no editing): ``guide_name`` (a wav stem under
     ``dataset.data_path``, the degraded recording, at ``dataset.sampling_rate``) with ``guide_op`` = ``declip`` (the
@@ -600,7 +609,7 @@ def generate(rank, diffusion_cfg, model_cfg, dataset_cfg, ckpt_iter="max", n_sam
         from .pqmf import check_run
         check_run(cfg, dataset_cfg, where="generate")
         given = [k for k, v in (("known_name", known_name), ("keep", keep), ("start_name", start_name),
-                                ("start_step", start_step), ("resample_jump", resample_jump), ("resample_n", resample_n),
+                                ("start_griffinlim", start_griffinlim), ("start_step", start_step), ("resample_jump", resample_jump), ("resample_n", resample_n),
                                 ("guide_name", guide_name), ("guide_op", guide_op), ("guide_clip", guide_clip),
                                 ("guide_factor", guide_factor), ("guide_scale", guide_scale),
                                 ("prior", None if prior == "none" else prior)) if v is not None]
@@ -650,9 +659,9 @@ def generate(rank, diffusion_cfg, model_cfg, dataset_cfg, ckpt_iter="max", n_sam
             raise ValueError("generate.guide_clip belongs to generate.guide_op=declip")
         if (sampler or "ddpm") not in ("ddpm", "ddim"):
             raise ValueError(f"{guide_key} with generate.sampler={sampler}: guided runs are built for ddpm and ddim")
-        if known_name is not None or start_name is not None or resample_jump is not None:
+        if known_name is not None or start_name is not None or resample_jump is not None or start_griffinlim is not None:
             raise ValueError(f"{guide_key} does not combine with the editing keys (known_name, start_name, "
-                             "resample_jump)")
+                             "start_griffinlim, resample_jump)")
     if report_mel is not None:
         if not isinstance(report_mel, bool):
             raise ValueError(f"generate.report_mel={report_mel!r}: expected true or false")
@@ -714,17 +723,33 @@ def generate(rank, diffusion_cfg, model_cfg, dataset_cfg, ckpt_iter="max", n_sam
         if guided:
             raise ValueError(f"generate.cfg_scale does not combine with {guide_key} (guided runs take "
                              "generate.label alone)")
-        if known_name is not None or start_name is not None or resample_jump is not None:
+        if known_name is not None or start_name is not None or resample_jump is not None or start_griffinlim is not None:
             raise ValueError("generate.cfg_scale does not combine with the editing keys (known_name, start_name, "
-                             "resample_jump)")
+                             "start_griffinlim, resample_jump)")
     if known_name is not None and not keep:
         raise ValueError("generate.known_name needs generate.keep: at least one [start, end) span of kept samples")
     if keep and known_name is None:
         raise ValueError("generate.keep needs generate.known_name (the wav whose samples are kept)")
     if start_name is not None and start_step is None:
         raise ValueError("generate.start_name needs generate.start_step (the step the loop starts at)")
-    if start_step is not None and start_name is None:
+    if start_step is not None and start_name is None and start_griffinlim is None:
         raise ValueError("generate.start_step needs generate.start_name (the wav the loop starts from)")
+    if start_griffinlim is None and griffinlim_momentum is not None:
+        raise ValueError("generate.griffinlim_momentum belongs to generate.start_griffinlim")
+    if start_griffinlim is not None:        # the warm start from the conditioning mel itself, before a model is built
+        from .mel import check_griffin_lim
+        if model_cfg.get("unconditional") or (mel_name is None and mel_names is None):
+            raise ValueError("generate.start_griffinlim needs a mel-conditional run (generate.mel_name or "
+                             "generate.mel_names: the start is the Griffin-Lim estimate of the conditioning mel)")
+        if start_name is not None:
+            raise ValueError("generate.start_griffinlim and generate.start_name exclude each other (two starts)")
+        if start_step is None:
+            raise ValueError("generate.start_griffinlim needs generate.start_step (the step the loop starts at)")
+        if mel_path is not None:
+            raise ValueError("generate.start_griffinlim does not combine with generate.mel_path (the STFT keys of "
+                             "pre-computed mel tensors are unknown)")
+        start_griffinlim, griffinlim_momentum = check_griffin_lim(
+            start_griffinlim, 0.0 if griffinlim_momentum is None else griffinlim_momentum, "generate.start_griffinlim")
     if (resample_jump is None) != (resample_n is None):
         raise ValueError("generate.resample_jump and generate.resample_n come together (got "
                          f"{'resample_jump' if resample_n is None else 'resample_n'} only)")
@@ -851,6 +876,22 @@ def generate(rank, diffusion_cfg, model_cfg, dataset_cfg, ckpt_iter="max", n_sam
         return {"prior_std": prior_std_from_mel(mel.to(device="cuda", dtype=torch.float32), hop_of_prior, L,
                                                 **{k: prior_cfg[k] for k in PRIOR_KEYS})}
 
+    def griffinlim_start(mel, frame_counts, lens=None):
+        """The partial-start arguments of generate.start_griffinlim: ``x_start`` [B, 1, frames x hop] is ``mel_to_audio``
+        of the conditioning mel [B, bands, F] at the run's STFT keys.  A run of frames x hop samples has one frame more
+        than its mel: every clip's last frame (of its own ``frame_counts[b]``) is repeated once."""
+        from .mel import Mel2Samp
+        keys = ("filter_length", "hop_length", "win_length", "sampling_rate", "mel_fmin", "mel_fmax")
+        stft = Mel2Samp(**{k: dataset_cfg[k] for k in keys if k in dataset_cfg}).stft
+        mel = mel.detach().to(device="cuda", dtype=torch.float32)
+        ext = torch.cat([mel, mel[..., -1:]], dim=-1)
+        for b, f in enumerate(frame_counts):
+            ext[b, :, f] = mel[b, :, f - 1]
+        x0 = stft.mel_to_audio(ext, n_iters=start_griffinlim, momentum=griffinlim_momentum, lengths=lens)
+        print(f"start: Griffin-Lim estimate of the conditioning mel ({start_griffinlim} iterations, momentum "
+              f"{griffinlim_momentum:g}), the loop starts at step {start_step}")
+        return dict(x_start=x0[:, None, :], start_step=start_step, start_noise=None if start_noise else False)
+
     output_directory = os.path.join(output_directory, str(ckpt_iter))
     os.makedirs(output_directory, mode=0o775, exist_ok=True)
 
@@ -890,6 +931,8 @@ def generate(rank, diffusion_cfg, model_cfg, dataset_cfg, ckpt_iter="max", n_sam
                   f"{1.0 - sum(lens) / float(len(batch) * Lmax):.3f}")
             pr = sigma_of(mel, Lmax)     # (each frame on its own: a clip's sigma is what it is alone; its padding is unused)
             run_lens = lens if bank is None else [n // K for n in lens]      # what the engine runs: sub-band positions
+            if start_griffinlim is not None:
+                pr = dict(pr, **griffinlim_start(mel, [frames[k] for k in batch], lens))
             if sampler == "aligned":
                 x = sampling_aligned(net, size, diffusion_cfg, condition=mel, seed=s, lengths=run_lens, **pr)
             elif sampler == "ddim":
@@ -954,6 +997,8 @@ def generate(rank, diffusion_cfg, model_cfg, dataset_cfg, ckpt_iter="max", n_sam
         edit["x_start"] = _load_clip(dataset_cfg, start_name, audio_length, mel is not None)
         edit["start_step"] = start_step
         edit["start_noise"] = None if start_noise else False
+    if start_griffinlim is not None:
+        edit.update(griffinlim_start(mel, [int(mel.shape[-1])]))
     if resample_jump is not None:
         edit["resample"] = (resample_jump, resample_n)
     mel_of = None       # log-mel of a [B, 1, L] batch on the engine, cut to the frames of the conditioning mel

@@ -10,6 +10,8 @@ The filterbank restates the published algorithm of ``librosa.filters.mel`` (``ht
 ``norm='slaney'``) -- librosa itself is not a dependency here; its numbers are pinned against an independent
 implementation through ``tests/golden/mel.npz`` (``tests/test_mel.py``).
 """
+import ctypes
+
 import numpy as np
 import torch
 
@@ -129,6 +131,140 @@ def prior_std_from_mel(mel, hop, L=None, *, energy_max, energy_min=0.0, std_min=
     return out
 
 
+# ---- inversion: dws_istft / dws_griffin_lim (csrc/griffinlim_kernels.hip; DESIGN.md section 4, "Mel inversion")
+GL_MAX_ITERS = 4096
+
+
+def _is_int(v):
+    return isinstance(v, (int, np.integer)) and not isinstance(v, bool)
+
+
+def check_griffin_lim(n_iters, momentum, what="griffin_lim"):
+    """``(n_iters, momentum)`` as an int in 0 .. 4096 and a float in [0, 1), or ValueError."""
+    if not _is_int(n_iters) or not 0 <= n_iters <= GL_MAX_ITERS:
+        raise ValueError(f"{what}: n_iters = {n_iters!r} (needs an integer in 0 .. {GL_MAX_ITERS})")
+    if isinstance(momentum, bool) or not isinstance(momentum, (int, float, np.integer, np.floating)) or \
+            not 0.0 <= float(momentum) < 1.0:
+        raise ValueError(f"{what}: momentum = {momentum!r} (needs a number in [0, 1))")
+    return int(n_iters), float(momentum)
+
+
+def _check_spectrum(what, name, t, shape=None):
+    if not isinstance(t, torch.Tensor) or t.dim() != 3 or t.dtype != torch.float32:
+        raise ValueError(f"{what}: {name} has shape {tuple(getattr(t, 'shape', ()))!r} and dtype "
+                         f"{getattr(t, 'dtype', type(t).__name__)}, expected a float32 tensor [B, K, F]")
+    if t.device.type != "cuda":
+        raise ValueError(f"{what}: {name} is on {t.device}: libdws runs on the GPU only (there is no CPU path)")
+    if t.requires_grad:
+        raise ValueError(f"{what}: {name} requires grad: no adjoint of the inversion is built (detach it)")
+    if shape is not None and tuple(t.shape) != tuple(shape):
+        raise ValueError(f"{what}: {name} has shape {tuple(t.shape)}, expected magnitude's {tuple(shape)}")
+
+
+def _check_inversion(what, magnitude, phase, window, hop_length, lengths):
+    """Argument checks of ``istft`` / ``griffin_lim`` (ValueError before anything runs).  Returns ``(n_fft, hop, host)``:
+    ``host`` the lengths as a list of ints, or None."""
+    _check_spectrum(what, "magnitude", magnitude)
+    B, K, F = (int(v) for v in magnitude.shape)
+    if isinstance(phase, torch.Tensor):
+        _check_spectrum(what, "phase", phase, magnitude.shape)
+        if phase.device != magnitude.device:
+            raise ValueError(f"{what}: phase is on {phase.device}, magnitude on {magnitude.device}")
+    if not isinstance(window, torch.Tensor) or window.dim() != 1 or window.dtype != torch.float32 or \
+            window.device != magnitude.device or window.requires_grad:
+        raise ValueError(f"{what}: window must be a float32 tensor [n_fft] on magnitude's device that does not require grad "
+                         f"(got shape {tuple(getattr(window, 'shape', ()))!r})")
+    n_fft = int(window.shape[0])
+    if n_fft < 64 or n_fft > 4096 or n_fft & (n_fft - 1):
+        raise ValueError(f"{what}: window has {n_fft} points: n_fft must be a power of two in 64 .. 4096")
+    if B < 1 or K != n_fft // 2 + 1:
+        raise ValueError(f"{what}: magnitude has shape {(B, K, F)}, expected K = n_fft/2 + 1 = {n_fft // 2 + 1} bins "
+                         "and at least one clip")
+    if not _is_int(hop_length) or hop_length < 1:
+        raise ValueError(f"{what}: hop_length = {hop_length!r} (needs an integer >= 1)")
+    hop = int(hop_length)
+    T = (F - 1) * hop
+    if T < n_fft // 2 + 1:
+        raise ValueError(f"{what}: F = {F} frames at hop_length {hop} make {T} samples, reflect padding needs at least "
+                         f"n_fft/2 + 1 = {n_fft // 2 + 1}")
+    if lengths is None:
+        return n_fft, hop, None
+    host = lengths.detach().cpu().tolist() if isinstance(lengths, torch.Tensor) else list(lengths)
+    if len(host) != B or (isinstance(lengths, torch.Tensor) and lengths.dim() != 1):
+        raise ValueError(f"{what}: lengths has {len(host)} entries for a batch of {B} clips")
+    for b, n in enumerate(host):
+        if not _is_int(n) or not n_fft // 2 + 1 <= n <= T:
+            raise ValueError(f"{what}: lengths: clip {b} has {n!r} samples (needs an integer in n_fft/2 + 1 = "
+                             f"{n_fft // 2 + 1} .. (F - 1) hop = {T})")
+        if n % hop:
+            raise ValueError(f"{what}: lengths: clip {b} has {n} samples, not a multiple of hop_length = {hop}")
+    return n_fft, hop, [int(n) for n in host]
+
+
+def _invert(magnitude, phase, window, n_fft, hop, host, n_iters, momentum):
+    lib = _lib.load()
+    dev = magnitude.device
+    B, _, F = (int(v) for v in magnitude.shape)
+    magnitude = magnitude.contiguous()
+    phase = None if phase is None else phase.contiguous()
+    window = window.contiguous()
+    out = torch.empty(B, (F - 1) * hop, device=dev, dtype=torch.float32)
+    ws = torch.empty(lib.dws_griffin_lim_workspace(B, F, n_fft, hop, int(momentum != 0.0)) // 4, device=dev,
+                     dtype=torch.float32)
+    dev_len = None if host is None else torch.tensor(host, dtype=torch.int32).to(dev)
+    host_len = None if host is None else (ctypes.c_int32 * B)(*host)
+    with torch.cuda.device(dev):
+        if n_iters is None:
+            _lib.check(lib.dws_istft(magnitude.data_ptr(), _lib.ptr(phase), B, F, _lib.ptr(dev_len), host_len,
+                                     window.data_ptr(), n_fft, hop, out.data_ptr(), ws.data_ptr(), _lib.current_stream()))
+        else:
+            _lib.check(lib.dws_griffin_lim(magnitude.data_ptr(), _lib.ptr(phase), B, F, _lib.ptr(dev_len), host_len,
+                                           window.data_ptr(), n_fft, hop, n_iters, momentum, out.data_ptr(), ws.data_ptr(),
+                                           _lib.current_stream()))
+    return out
+
+
+def istft(magnitude, phase, *, window, hop_length, lengths=None):
+    """``STFT.inverse(magnitude, phase)`` of `dataloaders/stft.py:165-194` (= ``torch.istft(center=True)`` of
+    ``magnitude * exp(1j * phase)``) in ``dws_istft``: magnitude and phase [B, K, F] (cuda, float32, ``K = n_fft/2 + 1``),
+    ``window`` [n_fft] on the same device -> [B, (F - 1) * hop_length].  ``lengths`` (B integers, multiples of the hop)
+    marks a ragged batch: clip b has ``lengths[b] // hop + 1`` frames, nothing behind them is read, and its row is exactly
+    0 from ``lengths[b]`` on.  Bad arguments raise ValueError before anything runs; there is no CPU path and no adjoint."""
+    if not isinstance(phase, torch.Tensor):
+        raise ValueError(f"istft: phase is {type(phase).__name__}, expected a float32 tensor [B, K, F]")
+    n_fft, hop, host = _check_inversion("istft", magnitude, phase, window, hop_length, lengths)
+    return _invert(magnitude, phase, window, n_fft, hop, host, None, 0.0)
+
+
+def griffin_lim(magnitude, *, window, hop_length, n_iters=32, momentum=0.0, phase=None, seed=0, lengths=None):
+    """``griffin_lim(magnitudes, stft_fn, n_iters)`` of `dataloaders/stft.py:66-82` in ``dws_griffin_lim``: the waveform
+    [B, (F - 1) * hop_length] whose STFT magnitudes approach ``magnitude`` [B, K, F] (cuda, float32).  ``phase`` is the
+    start: None draws uniform phases in [-pi, pi) from a ``torch.Generator`` on the device seeded with ``seed`` (a call is
+    reproducible; every clip draws its own [K, frames] from the seed, so its result does not depend on the batch around
+    it), ``"zero"`` is phase 0, a tensor [B, K, F] is taken as given.  ``momentum`` in [0, 1) is Fast
+    Griffin-Lim's (Perraudin et al. 2013; 0.99 is the usual choice), 0 the reference's loop.  ``n_iters = 0`` is
+    ``istft(magnitude, phase)``, bit for bit.  ``lengths`` as in ``istft``.  Bad arguments raise ValueError before
+    anything runs."""
+    what = "griffin_lim"
+    if not (phase is None or isinstance(phase, torch.Tensor) or (isinstance(phase, str) and phase == "zero")):
+        raise ValueError(f"{what}: phase = {phase!r} (None for seeded random phases, \"zero\", or a tensor [B, K, F])")
+    n_iters, momentum = check_griffin_lim(n_iters, momentum, what)
+    if not _is_int(seed) or seed < 0:
+        raise ValueError(f"{what}: seed = {seed!r} (needs a non-negative integer)")
+    n_fft, hop, host = _check_inversion(what, magnitude, phase, window, hop_length, lengths)
+    if phase is None:
+        B, K, F = (int(v) for v in magnitude.shape)
+        g = torch.Generator(device=magnitude.device)
+        phase = torch.zeros_like(magnitude)
+        for b in range(B):      # every clip from the seed itself: its [K, frames] phases do not depend on the batch around it
+            g.manual_seed(int(seed))
+            f = F if host is None else host[b] // hop + 1
+            phase[b, :, :f] = (torch.rand(K, f, device=magnitude.device, dtype=torch.float32, generator=g) * 2.0 - 1.0) * np.pi
+    elif isinstance(phase, str):
+        phase = None
+    return _invert(magnitude, phase, window, n_fft, hop, host, n_iters, momentum)
+
+
 class _MelBackward(torch.autograd.Function):
     """``dws_mel_spectrogram_backward`` as a node of its own, so that differentiating it (a second-order request) is
     an error with a name instead of a silent zero."""
@@ -179,6 +315,7 @@ class TacotronSTFT:
         self.mel_basis = torch.from_numpy(mel_filterbank(sampling_rate, filter_length, n_mel_channels, mel_fmin, mel_fmax))
         self.window = torch.from_numpy(padded_hann(win_length, filter_length))
         self._dev = {}
+        self._pinv, self._pinv_dev = None, {}
 
     def _tables(self, device):
         if device not in self._dev:
@@ -207,6 +344,50 @@ class TacotronSTFT:
             raise RuntimeError("libdws runs on the GPU only: move the waveform to cuda (there is no CPU fallback)")
         assert float(y.min()) >= -1 and float(y.max()) <= 1            # `stft.py:233-234`
         return self.differentiable_mel(y)
+
+    # ---- the other direction (`stft.py:66-82,165-194`): istft / griffin_lim of this module at the object's STFT keys
+    def inverse(self, magnitude, phase):
+        """``STFT.inverse(magnitude, phase)``: [B, K, F] (cuda, float32) twice -> [B, (F - 1) * hop_length]."""
+        _check_spectrum("inverse", "magnitude", magnitude)
+        return istft(magnitude, phase, window=self._tables(magnitude.device)[0], hop_length=self.hop_length)
+
+    def griffin_lim(self, magnitude, n_iters=32, momentum=0.0, phase=None, seed=0, lengths=None):
+        """``griffin_lim`` of this module on linear magnitudes [B, K, F] at the object's own STFT keys."""
+        _check_spectrum("griffin_lim", "magnitude", magnitude)
+        return griffin_lim(magnitude, window=self._tables(magnitude.device)[0], hop_length=self.hop_length, n_iters=n_iters,
+                           momentum=momentum, phase=phase, seed=seed, lengths=lengths)
+
+    def mel_pinv(self):
+        """``numpy.linalg.pinv`` of the filterbank in float64: [K, n_mel_channels]."""
+        if self._pinv is None:
+            self._pinv = np.linalg.pinv(self.mel_basis.numpy().astype(np.float64))
+        return self._pinv
+
+    def mel_to_magnitude(self, mel):
+        """Log-mel [B, n_mel_channels, F] (cuda, float32; ``mel_spectrogram``'s output) -> linear magnitudes [B, K, F]:
+        ``clamp(P @ exp(mel), min=0)`` with ``P = mel_pinv()``, the least-squares inverse of the filterbank (cached per
+        device in float64).  One torch matmul per call, taken in float64 and rounded to float32 once; NNLS inversion is
+        not built."""
+        if not isinstance(mel, torch.Tensor) or mel.dim() != 3 or mel.dtype != torch.float32 or \
+                mel.shape[1] != self.n_mel_channels:
+            raise ValueError(f"mel_to_magnitude: the mel has shape {tuple(getattr(mel, 'shape', ()))!r} and dtype "
+                             f"{getattr(mel, 'dtype', type(mel).__name__)}, expected a float32 tensor "
+                             f"[B, {self.n_mel_channels}, frames]")
+        if mel.device.type != "cuda":
+            raise ValueError(f"mel_to_magnitude: the mel is on {mel.device}: libdws runs on the GPU only (there is no CPU path)")
+        if mel.requires_grad:
+            raise ValueError("mel_to_magnitude: the mel requires grad: no adjoint of the inversion is built (detach it)")
+        if mel.device not in self._pinv_dev:
+            self._pinv_dev[mel.device] = torch.from_numpy(self.mel_pinv()).to(mel.device)
+        # the product in float64, rounded once: a float32 GEMM adds the bands in an order that depends on the batch's
+        # shape, and a clip's magnitudes (so its inversion) must not depend on the batch around it
+        return torch.matmul(self._pinv_dev[mel.device], torch.exp(mel).double()).clamp_(min=0.0).float()
+
+    def mel_to_audio(self, mel, n_iters=32, momentum=0.0, seed=0, lengths=None):
+        """``griffin_lim(mel_to_magnitude(mel))`` from seeded random phases: log-mel [B, n_mel_channels, F] ->
+        [B, (F - 1) * hop_length].  ``lengths`` (samples, multiples of the hop) as in ``griffin_lim``."""
+        check_griffin_lim(n_iters, momentum, "mel_to_audio")
+        return self.griffin_lim(self.mel_to_magnitude(mel), n_iters=n_iters, momentum=momentum, seed=seed, lengths=lengths)
 
 
 def load_wav_to_torch(full_path):

@@ -823,6 +823,52 @@ int dws_stoi(const float* x, const float* y, int64_t B, int64_t T, const int32_t
 /* Bytes of dws_stoi's workspace; 0 for a shape it refuses. */
 int64_t dws_stoi_workspace(int64_t B, int64_t T, int32_t frame, int32_t hop, int32_t n_bands);
 
+/* Inverse short-time Fourier transform, STFT.inverse(magnitude, phase) of `dataloaders/stft.py:165-194` (=
+ * torch.istft(center=True) of magnitude e^{i phase}), with a length per clip.  magnitude and phase are DEVICE float32
+ * [B][K][f_max], K = n_fft/2 + 1 (the reference's layout); a null phase is phase 0.  The spectrum is the public one,
+ * e^{-i theta}: X_k = sum_i frame[i] e^{-2 pi i k / N}, so Re_k = M_k cos(phase_k), Im_k = M_k sin(phase_k).  With
+ * N = n_fft, w = window [N] (DEVICE; a periodic Hann window of win <= N points centred in N), len_b = lengths[b]
+ * ((f_max - 1) hop where lengths is null; each a multiple of hop) and frames f = 0 .. len_b / hop of clip b:
+ *     h_k = 1/N for k = 0 and k = N/2 (whose imaginary part does not enter, as irfft ignores it), 2/N otherwise
+ *     row_f[i] = w[i] sum_k h_k (Re_k cos(2 pi i k / N) - Im_k sin(2 pi i k / N))         (k = 0 .. N/2 ascending)
+ *     wss(p)   = sum_f w[p - f hop]^2,   s(p) = sum_f row_f[p - f hop]                    (the frames that cover p, ascending)
+ *     out[b][j] = s(p) / wss(p) where wss(p) > FLT_MIN, else s(p),   p = j + N/2,  j < len_b
+ * (the reference's `tiny` rule; its n_fft / hop factors cancel and do not appear).  out is [B][(f_max - 1) hop];
+ * positions j >= len_b are written as exactly 0.  Frames behind a clip's own (f > len_b / hop) are never read and may
+ * hold NaN.  No atomics, fixed order: the result is bitwise reproducible, and row b depends on clip b's own frames alone.
+ * lengths / lengths_host: as dws_spectral_distance (DEVICE and HOST copies of the same numbers, both or neither; the
+ * host copy is checked, nothing waits for the GPU).  workspace: DEVICE, dws_griffin_lim_workspace(B, f_max, n_fft, hop, 0)
+ * bytes ([B][f_max][n_fft] floats) owned by the caller (overwritten; the library allocates nothing per call).
+ * LDS per workgroup: 8 n_fft + 8 K bytes.
+ * DWS_ERR_UNSUPPORTED: n_fft not a power of two in 64 .. 4096 (dws_mel_spectrogram's limits), or more LDS than a
+ * workgroup has.  DWS_ERR_INVALID, the message naming the parameter and the clip: a null magnitude, window, out or
+ * workspace; B outside 1 .. 65535; hop < 1; f_max < 2; a len_b outside n_fft/2 + 1 .. (f_max - 1) hop or not a multiple of
+ * hop; lengths without lengths_host. */
+int dws_istft(const float* magnitude, const float* phase, int64_t B, int64_t f_max, const int32_t* lengths,
+              const int32_t* lengths_host, const float* window, int32_t n_fft, int32_t hop, float* out, float* workspace,
+              void* stream);
+
+/* Griffin-Lim phase reconstruction (`dataloaders/stft.py:66-82`; Griffin & Lim 1984) from the magnitudes M [B][K][f_max]
+ * and initial phases phase0 (null: phase 0), shapes, framing, lengths and sign convention as dws_istft:
+ *     x_0 = dws_istft(M, phase0),   y_0 = x_0
+ *     iteration n = 1 .. n_iters:
+ *       projection: X = STFT(y_{n-1}) (dws_mel_spectrogram's framing, reflected about the clip's OWN ends),
+ *                   (Re_k, Im_k) <- (Re_k, Im_k) M_k / |X_k|,  (M_k, 0) where |X_k| == 0 exactly (phase atan2(0, 0) = 0),
+ *       gather:     x_n = the normalised overlap-add of dws_istft on these rows,   y_n = x_n + momentum (x_n - x_{n-1})
+ *     out = x_{n_iters}.
+ * momentum = 0 is the reference's loop.  momentum > 0 is Fast Griffin-Lim (Perraudin, Balazs & Sondergaard 2013) stated
+ * in the signal domain, which is exact because STFT . iSTFT is linear.  n_iters = 0 is dws_istft(M, phase0), bit for bit.
+ * Two launches per iteration; no spectrogram of an iterate goes to memory.  Reproducibility and independence of a clip from
+ * its batch are dws_istft's.  workspace: DEVICE, dws_griffin_lim_workspace(B, f_max, n_fft, hop, momentum != 0) bytes (the
+ * rows, then y [B][(f_max - 1) hop] with momentum).  LDS per workgroup: 12 n_fft + 8 K bytes.
+ * Error codes: dws_istft's, and DWS_ERR_INVALID for n_iters outside 0 .. 4096 or momentum outside [0, 1). */
+int dws_griffin_lim(const float* magnitude, const float* phase0, int64_t B, int64_t f_max, const int32_t* lengths,
+                    const int32_t* lengths_host, const float* window, int32_t n_fft, int32_t hop, int32_t n_iters,
+                    float momentum, float* out, float* workspace, void* stream);
+
+/* Bytes of the workspace of dws_griffin_lim (and, with momentum = 0, of dws_istft); 0 for a shape they refuse. */
+int64_t dws_griffin_lim_workspace(int64_t B, int64_t f_max, int32_t n_fft, int32_t hop, int32_t momentum);
+
 /* Pseudo-QMF filter bank of multi-band runs (Multi-band MelGAN, Yang et al. 2020; not in the reference).  Both entries
  * take the filter table filt [K][taps + 1] (DEVICE, float32; designed by the caller) and a gain, so that each also serves
  * as the other's adjoint.  K is 2 or 4, taps is even and in 2 .. 254, h = taps / 2.
