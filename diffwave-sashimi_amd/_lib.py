@@ -152,6 +152,9 @@ _SIGS = {
                                        ctypes.POINTER(ctypes.c_int32), c_f32p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
                                        ctypes.c_float, c_f32p, c_f32p, ctypes.c_void_p]),
     "dws_griffin_lim_workspace": (ctypes.c_int64, [ctypes.c_int64, ctypes.c_int64] + [ctypes.c_int32] * 3),
+    "dws_tv_filter": (ctypes.c_int, [c_f32p, ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p,
+                                     ctypes.POINTER(ctypes.c_int32), c_f32p, c_f32p, c_f32p, ctypes.c_int32, ctypes.c_int32,
+                                     ctypes.c_int32, c_f32p, c_f32p, ctypes.c_void_p]),
     "dws_pqmf_analysis": (ctypes.c_int, [c_f32p, ctypes.c_int64, ctypes.c_int64, c_f32p, ctypes.c_int32, ctypes.c_int32,
                                          ctypes.c_float, c_f32p, ctypes.c_void_p]),
     "dws_pqmf_synthesis": (ctypes.c_int, [c_f32p, ctypes.c_int64, ctypes.c_int64, c_f32p, ctypes.c_int32, ctypes.c_int32,

@@ -21,18 +21,6 @@
 
 namespace dws {
 
-__device__ __forceinline__ float2 hermitian_row(int k, int half, float inv_n, float re, float im) {
-    const bool edge = k == 0 || k == half;
-    const float h = edge ? inv_n : 2.f * inv_n;
-    return make_float2(h * re, edge ? 0.f : h * im);
-}
-
-// ws[b][f][i] = w[i] sum_k (d_k.x cos + d_k.y sin)(2 pi i k / N): the windowed frame the overlap-add gathers
-__device__ __forceinline__ void inverse_rows(const float2* __restrict__ d, const float2* __restrict__ tab,
-                                             const float* __restrict__ window, float* __restrict__ o, int n_fft, int tid) {
-    for (int i = tid; i < n_fft; i += 256) o[i] = idft_sample(d, tab, i, n_fft / 2 + 1, n_fft - 1) * window[i];
-}
-
 // Frame f of clip b from (magnitude, phase) [B][K][f_max]; a null phase is phase 0.
 __global__ __launch_bounds__(256) void istft_rows_kernel(const float* __restrict__ mag, const float* __restrict__ phase,
                                                          const int* __restrict__ lengths, const float* __restrict__ window,
@@ -124,33 +112,8 @@ __global__ __launch_bounds__(256) void istft_gather_kernel(const float* __restri
     x[at] = v;
 }
 
-constexpr size_t gl_lds_bytes(int n_fft, bool frame) { return (size_t)n_fft * 8 + (size_t)(n_fft / 2 + 1) * 8 + (frame ? (size_t)n_fft * 4 : 0); }
-
-// Everything dws_istft and dws_griffin_lim check alike; f_max frames make T = (f_max - 1) hop samples.
-static int gl_check(const char* who, const float* magnitude, int64_t B, int64_t f_max, const int32_t* lengths,
-                    const int32_t* lengths_host, const float* window, int32_t n_fft, int32_t hop, const float* out,
-                    const float* workspace) {
-    DWS_CHECK(magnitude, DWS_ERR_INVALID, "%s: null magnitude", who);
-    DWS_CHECK(window, DWS_ERR_INVALID, "%s: null window", who);
-    DWS_CHECK(out, DWS_ERR_INVALID, "%s: null out", who);
-    DWS_CHECK(workspace, DWS_ERR_INVALID, "%s: null workspace (dws_griffin_lim_workspace bytes)", who);
-    DWS_CHECK(n_fft_ok(n_fft, 4096), DWS_ERR_UNSUPPORTED, "%s: n_fft = %d (powers of two 64..4096 are built)", who, n_fft);
-    DWS_CHECK(gl_lds_bytes(n_fft, true) <= 160 * 1024, DWS_ERR_UNSUPPORTED,
-              "%s: n_fft = %d needs %zu bytes of LDS (160 KiB per workgroup)", who, n_fft, gl_lds_bytes(n_fft, true));
-    DWS_CHECK(B > 0 && B <= 65535, DWS_ERR_INVALID, "%s: B = %lld (needs 1 .. 65535)", who, (long long)B);
-    DWS_CHECK(hop > 0, DWS_ERR_INVALID, "%s: hop = %d (needs at least 1)", who, hop);
-    DWS_CHECK(f_max >= 2 && (f_max - 1) <= (INT32_MAX - (int64_t)n_fft) / hop, DWS_ERR_INVALID,
-              "%s: f_max = %lld (needs 2 frames at least, and (f_max - 1) hop + n_fft below 2^31)", who, (long long)f_max);
-    const int64_t T = (f_max - 1) * hop;
-    if (check_clip_lengths(who, B, T, lengths, lengths_host, n_fft / 2 + 1) < 0) return DWS_ERR_INVALID;
-    for (int64_t b = 0; lengths_host && b < B; ++b)
-        DWS_CHECK(lengths_host[b] % hop == 0, DWS_ERR_INVALID, "%s: lengths: clip %lld has %d samples, not a multiple of hop = %d",
-                  who, (long long)b, lengths_host[b], hop);
-    return DWS_OK;
-}
-
-static int gl_gather(const float* ws, const int32_t* lengths, const float* window, float* x, float* y, int64_t B, int64_t T,
-                     int32_t n_fft, int32_t hop, int f_max, float alpha, hipStream_t stream) {
+int gl_gather(const float* ws, const int32_t* lengths, const float* window, float* x, float* y, int64_t B, int64_t T,
+              int32_t n_fft, int32_t hop, int f_max, float alpha, hipStream_t stream) {
     hipLaunchKernelGGL(istft_gather_kernel, dim3((unsigned)((T + 255) / 256), (unsigned)B), dim3(256), 0, stream, ws, lengths,
                        window, x, y, (int)T, n_fft, hop, f_max, alpha);
     DWS_HIP(hipGetLastError());
@@ -171,7 +134,7 @@ extern "C" int dws_griffin_lim(const float* magnitude, const float* phase0, int6
                                float momentum, float* out, float* workspace, void* stream) {
     using namespace dws;
     const char* who = "dws_griffin_lim";
-    const int rc = gl_check(who, magnitude, B, f_max, lengths, lengths_host, window, n_fft, hop, out, workspace);
+    const int rc = gl_check(who, "magnitude", magnitude, B, f_max, lengths, lengths_host, window, n_fft, hop, out, workspace);
     if (rc != DWS_OK) return rc;
     DWS_CHECK(n_iters >= 0 && n_iters <= 4096, DWS_ERR_INVALID, "%s: n_iters = %d (needs 0 .. 4096)", who, n_iters);
     DWS_CHECK(momentum >= 0.f && momentum < 1.f, DWS_ERR_INVALID, "%s: momentum = %g (needs 0 <= momentum < 1)", who,
@@ -204,7 +167,7 @@ extern "C" int dws_istft(const float* magnitude, const float* phase, int64_t B, 
                          const int32_t* lengths_host, const float* window, int32_t n_fft, int32_t hop, float* out,
                          float* workspace, void* stream) {
     using namespace dws;
-    const int rc = gl_check("dws_istft", magnitude, B, f_max, lengths, lengths_host, window, n_fft, hop, out, workspace);
+    const int rc = gl_check("dws_istft", "magnitude", magnitude, B, f_max, lengths, lengths_host, window, n_fft, hop, out, workspace);
     if (rc != DWS_OK) return rc;
     return dws_griffin_lim(magnitude, phase, B, f_max, lengths, lengths_host, window, n_fft, hop, 0, 0.f, out, workspace,
                            stream);

@@ -1,7 +1,7 @@
 // The short-time DFT core of the analysis kernels (mel_kernels, spectral_kernels, stoi_kernels, pitch_kernels) and of the
-// inversion kernels (griffinlim_kernels, whose projection is a forward and an inverse stage in one workgroup): every
-// piece the files share exists here once, so the adjoints recompute the forward's numbers -- and take its clamp and
-// floor decisions -- by calling the forward's own code.
+// inversion kernels (griffinlim_kernels and tvfilter_kernels, whose frame kernels are a forward and an inverse stage in one
+// workgroup): every piece the files share exists here once, so the adjoints recompute the forward's numbers -- and take
+// its clamp and floor decisions -- by calling the forward's own code.
 //
 // Layout: a workgroup of 256 threads owns one frame.  The twiddle table is float2 (cos, sin)(2 pi i / n_fft), i = 0 ..
 // n_fft - 1, in LDS on an 8-byte border; the frame sits next to it as float (one signal) or float2 (x, y) (two signals),
@@ -100,6 +100,20 @@ __device__ __forceinline__ float idft_sample(const float2* __restrict__ d, const
     return acc;
 }
 
+// Row k of the inverse stage's input: h_k (re, im) with h = 1/N at k = 0 and k = N/2, whose imaginary part does not
+// enter (irfft ignores it), and 2/N elsewhere.
+__device__ __forceinline__ float2 hermitian_row(int k, int half, float inv_n, float re, float im) {
+    const bool edge = k == 0 || k == half;
+    const float h = edge ? inv_n : 2.f * inv_n;
+    return make_float2(h * re, edge ? 0.f : h * im);
+}
+
+// ws[b][f][i] = w[i] sum_k (d_k.x cos + d_k.y sin)(2 pi i k / N): the windowed frame the overlap-add gathers
+__device__ __forceinline__ void inverse_rows(const float2* __restrict__ d, const float2* __restrict__ tab,
+                                             const float* __restrict__ window, float* __restrict__ o, int n_fft, int tid) {
+    for (int i = tid; i < n_fft; i += 256) o[i] = idft_sample(d, tab, i, n_fft / 2 + 1, n_fft - 1) * window[i];
+}
+
 template <typename T>
 __device__ __forceinline__ T wave_sum(T v) {
 #pragma unroll
@@ -151,6 +165,39 @@ static inline int64_t check_clip_lengths(const char* who, int64_t B, int64_t T, 
         if (lengths_host[b] > longest) longest = lengths_host[b];
     }
     return longest;
+}
+
+// ---- the inversion family (griffinlim_kernels, tvfilter_kernels): a frame kernel writes rows, a gather adds them up.
+// LDS of a frame kernel: the table, the nb rows of the inverse stage and, where it transforms first, the frame.
+constexpr size_t gl_lds_bytes(int n_fft, bool frame) { return (size_t)n_fft * 8 + (size_t)(n_fft / 2 + 1) * 8 + (frame ? (size_t)n_fft * 4 : 0); }
+
+// The normalised overlap-add of the rows ws [B][f_max][n_fft] into x [B][T] (istft_gather_kernel, griffinlim_kernels.hip);
+// y and alpha are Griffin-Lim's momentum pair (null and 0 elsewhere).
+int gl_gather(const float* ws, const int32_t* lengths, const float* window, float* x, float* y, int64_t B, int64_t T,
+              int32_t n_fft, int32_t hop, int f_max, float alpha, hipStream_t stream);
+
+// Everything dws_istft, dws_griffin_lim and dws_tv_filter check alike; f_max frames make T = (f_max - 1) hop samples.
+// `input` is the entry's first array under the name its message gives it.
+static inline int gl_check(const char* who, const char* input_name, const float* input, int64_t B, int64_t f_max,
+                           const int32_t* lengths, const int32_t* lengths_host, const float* window, int32_t n_fft,
+                           int32_t hop, const float* out, const float* workspace) {
+    DWS_CHECK(input, DWS_ERR_INVALID, "%s: null %s", who, input_name);
+    DWS_CHECK(window, DWS_ERR_INVALID, "%s: null window", who);
+    DWS_CHECK(out, DWS_ERR_INVALID, "%s: null out", who);
+    DWS_CHECK(workspace, DWS_ERR_INVALID, "%s: null workspace (dws_griffin_lim_workspace bytes)", who);
+    DWS_CHECK(n_fft_ok(n_fft, 4096), DWS_ERR_UNSUPPORTED, "%s: n_fft = %d (powers of two 64..4096 are built)", who, n_fft);
+    DWS_CHECK(gl_lds_bytes(n_fft, true) <= 160 * 1024, DWS_ERR_UNSUPPORTED,
+              "%s: n_fft = %d needs %zu bytes of LDS (160 KiB per workgroup)", who, n_fft, gl_lds_bytes(n_fft, true));
+    DWS_CHECK(B > 0 && B <= 65535, DWS_ERR_INVALID, "%s: B = %lld (needs 1 .. 65535)", who, (long long)B);
+    DWS_CHECK(hop > 0, DWS_ERR_INVALID, "%s: hop = %d (needs at least 1)", who, hop);
+    DWS_CHECK(f_max >= 2 && (f_max - 1) <= (INT32_MAX - (int64_t)n_fft) / hop, DWS_ERR_INVALID,
+              "%s: f_max = %lld (needs 2 frames at least, and (f_max - 1) hop + n_fft below 2^31)", who, (long long)f_max);
+    const int64_t T = (f_max - 1) * hop;
+    if (check_clip_lengths(who, B, T, lengths, lengths_host, n_fft / 2 + 1) < 0) return DWS_ERR_INVALID;
+    for (int64_t b = 0; lengths_host && b < B; ++b)
+        DWS_CHECK(lengths_host[b] % hop == 0, DWS_ERR_INVALID, "%s: lengths: clip %lld has %d samples, not a multiple of hop = %d",
+                  who, (long long)b, lengths_host[b], hop);
+    return DWS_OK;
 }
 
 }  // namespace dws

@@ -275,26 +275,51 @@ def _check_mel_names(mel_names, mel_name, clip_seeds, seed, **others):
     return names
 
 
-PRIOR_KEYS = ("energy_max", "energy_min", "std_min")
+PRIOR_KEYS = ("energy_max", "energy_min", "std_min")       # the value keys of a {"kind": "energy"} entry
+SPECTRAL_PRIOR_KEYS = ("ref", "floor", "lifter")            # and of a {"kind": "spectral"} one
+PRIOR_KEYS_OF = {"energy": PRIOR_KEYS, "spectral": SPECTRAL_PRIOR_KEYS}
 
 
-def prior_settings(prior, energy_max=None, energy_min=None, std_min=None, unconditional=False, where="generate"):
-    """The adaptive-prior keys of a CLI run (``+{where}.prior=energy +{where}.prior_energy_max=E
-    [+{where}.prior_energy_min=0 +{where}.prior_std_min=0.1]``), checked before a model is built (ValueError).  Returns
-    None (no key given), ``"none"`` (``prior=none``: N(0, I) whatever the checkpoint says) or the dict
-    ``{"kind": "energy", "energy_max", "energy_min", "std_min"}`` of ``mel.prior_std_from_mel``'s settings."""
-    from .mel import _check_prior_range
+def prior_settings(prior, energy_max=None, energy_min=None, std_min=None, unconditional=False, where="generate", *,
+                   ref=None, floor=None, lifter=None, n_fft=None):
+    """The adaptive-prior keys of a CLI run, checked before a model is built (ValueError):
+    ``+{where}.prior=energy +{where}.prior_energy_max=E [+{where}.prior_energy_min=0 +{where}.prior_std_min=0.1]``
+    (PriorGrad) or ``+{where}.prior=spectral +{where}.prior_ref=R [+{where}.prior_floor=0.01 +{where}.prior_lifter=24]``
+    (SpecGrad; ``n_fft``: ``dataset.filter_length``, which bounds the lifter).  Returns None (no key given), ``"none"``
+    (``prior=none``: N(0, I) whatever the checkpoint says) or the dict
+    ``{"kind": "energy", "energy_max", "energy_min", "std_min"}`` of ``mel.prior_std_from_mel``'s settings, or
+    ``{"kind": "spectral", "ref", "floor", "lifter"}`` of ``TacotronSTFT.spectral_filter``'s."""
+    from .mel import _check_filter_design, _check_prior_range
     given = [k for k, v in (("prior_energy_max", energy_max), ("prior_energy_min", energy_min), ("prior_std_min", std_min))
              if v is not None]
+    given_s = [k for k, v in (("prior_ref", ref), ("prior_floor", floor), ("prior_lifter", lifter)) if v is not None]
     if prior is None or prior == "none":
         if given:
             raise ValueError(f"{where}.{given[0]} needs {where}.prior=energy")
+        if given_s:
+            raise ValueError(f"{where}.{given_s[0]} needs {where}.prior=spectral")
         return prior
-    if prior != "energy":
-        raise ValueError(f"{where}.prior={prior!r}: expected energy or none")
+    if prior not in PRIOR_KEYS_OF:
+        raise ValueError(f"{where}.prior={prior!r}: expected energy or none (or spectral, the time-varying spectral prior)")
     if unconditional:
-        raise ValueError(f"{where}.prior=energy needs a mel-conditional model (model.unconditional=false): the prior is "
+        raise ValueError(f"{where}.prior={prior} needs a mel-conditional model (model.unconditional=false): the prior is "
                          "read off the conditioning mel")
+    if prior == "spectral":
+        if given:
+            raise ValueError(f"{where}.{given[0]} needs {where}.prior=energy (this run names {where}.prior=spectral)")
+        if ref is None:
+            raise ValueError(f"{where}.prior=spectral needs {where}.prior_ref (the magnitude that maps to gain 1: the largest "
+                             "of the dataset, mel.spectral_prior_ref; no default is chosen: it depends on the dataset)")
+        if any(isinstance(v, (bool, str)) for v in (ref, floor, lifter)):
+            raise ValueError(f"{where}.prior_ref / prior_floor / prior_lifter: expected numbers")
+        try:
+            r, fl, lf = _check_filter_design(ref, 0.01 if floor is None else floor, 24 if lifter is None else lifter,
+                                             1 << 30 if n_fft is None else int(n_fft))
+        except ValueError as e:
+            raise ValueError(f"{where}.prior=spectral: {e}")
+        return {"kind": "spectral", "ref": r, "floor": fl, "lifter": lf}
+    if given_s:
+        raise ValueError(f"{where}.{given_s[0]} needs {where}.prior=spectral (this run names {where}.prior=energy)")
     if energy_max is None:
         raise ValueError(f"{where}.prior=energy needs {where}.prior_energy_max (the largest frame energy of the dataset, "
                          "mel.mel_energy; no default is chosen: it depends on the dataset)")
@@ -317,26 +342,31 @@ def prior_hop(model_cfg, dataset_cfg):
 
 
 def same_prior(a, b):
-    """Two ``prior`` entries (None: N(0, I)) name the same prior."""
+    """Two ``prior`` entries (None: N(0, I)) name the same prior: the same kind with the same values (an energy entry and
+    a spectral entry never do)."""
     if a is None or b is None:
         return a is None and b is None
-    return a.get("kind") == b.get("kind") and all(k in a and k in b and float(a[k]) == float(b[k]) for k in PRIOR_KEYS)
+    keys = PRIOR_KEYS_OF.get(a.get("kind"), PRIOR_KEYS)
+    return a.get("kind") == b.get("kind") and all(k in a and k in b and float(a[k]) == float(b[k]) for k in keys)
 
 
 def resolve_prior(settings, entry, given=()):
     """The prior a ``generate`` run uses: ``settings`` (``prior_settings``) against the checkpoint's ``prior`` entry (None:
-    it has none).  ``"none"`` -> None; no keys -> the entry; keys that contradict the entry -> ValueError (``given``: the
-    value keys the run spelled out; the others follow the entry)."""
+    it has none).  ``"none"`` -> None; no keys -> the entry; another kind than the entry's, or keys that contradict it ->
+    ValueError (``given``: the value keys the run spelled out; the others follow the entry)."""
     if settings == "none":
         return None
-    if entry is not None and (not isinstance(entry, dict) or entry.get("kind") != "energy"
-                              or any(k not in entry for k in PRIOR_KEYS)):
+    if entry is not None and (not isinstance(entry, dict) or entry.get("kind") not in PRIOR_KEYS_OF
+                              or any(k not in entry for k in PRIOR_KEYS_OF[entry["kind"]])):
         raise ValueError(f"the checkpoint's prior entry {entry!r} is not one this version writes")
     if settings is None:
         return None if entry is None else dict(entry)
     if entry is None:
         return settings
-    for k in PRIOR_KEYS:
+    if settings["kind"] != entry["kind"]:
+        raise ValueError(f"generate.prior={settings['kind']} contradicts the checkpoint, which was trained with the "
+                         f"{entry['kind']} prior {entry!r} (drop the key, or generate.prior=none for N(0, I))")
+    for k in PRIOR_KEYS_OF[entry["kind"]]:
         if k in given and float(entry[k]) != float(settings[k]):
             raise ValueError(f"generate.prior_{k}={settings[k]!r} contradicts the checkpoint, which was trained with "
                              f"{k}={entry[k]!r} (drop the key, or generate.prior=none for N(0, I))")
@@ -482,7 +512,7 @@ def generate(rank, diffusion_cfg, model_cfg, dataset_cfg, ckpt_iter="max", n_sam
              cfg_scale=None, ema=None, clip_seeds=None, clips=None, num_ranks=None, report_mel=None, mel_errors=None,
              mel_names=None, prior=None, prior_energy_max=None, prior_energy_min=None, prior_std_min=None,
              report_metrics=None, metric_rows=None, report_pitch=None, report_stoi=None, start_griffinlim=None,
-             griffinlim_momentum=None):
+             griffinlim_momentum=None, prior_ref=None, prior_floor=None, prior_lifter=None):
     """``generate.py:58-200``.  ``ckpt_iter`` may additionally be ``"init"``: seeded random weights
     (no checkpoint), for smoke runs without trained weights.  ``precision`` (not in the reference; CLI:
     ``+engine.precision=bf16x6|f16x3``): the engine's opt-in matrix arithmetic, see ``include/dws.h``.
@@ -582,6 +612,14 @@ def generate(rank, diffusion_cfg, model_cfg, dataset_cfg, ckpt_iter="max", n_sam
     A model must have been trained with the prior it is sampled with.  What the samples sound like has not been
     measured.
 
+    Spectral prior (not in the reference; SpecGrad, Koizumi et al., Interspeech 2022; mel-conditional models, the
+    unguided samplers, ``mel_name`` and ``mel_names``, with the clip-seed keys): ``prior=spectral`` with ``prior_ref``
+    (required) and ``prior_floor`` (0.01) / ``prior_lifter`` (24) runs from N(0, Sigma) with Sigma shaped per frame and
+    bin by ``TacotronSTFT.spectral_filter`` of the conditioning mel at the dataset's STFT keys (the ``prior_filter`` of
+    the samplers).  The checkpoint's entry (written by ``train.prior=spectral``), ``prior=none`` and contradicting keys
+    behave as above; the editing, partial-start, resampling and guide keys raise ValueError (their noise is not shaped).
+    What the samples sound like has not been measured.
+
     Multi-band runs (not in the reference; ``pqmf.py``): with ``model.subbands = K`` (``model_cfg``; optional
     ``pqmf_taps`` / ``pqmf_cutoff`` / ``pqmf_beta``), or from a checkpoint with a ``pqmf`` entry (written by such a
     training run; used and printed, and the network is then built with its K), the network has K channels, every
@@ -618,15 +656,18 @@ def generate(rank, diffusion_cfg, model_cfg, dataset_cfg, ckpt_iter="max", n_sam
                              "adaptive prior act on the full-band signal; their sub-band forms are not built)")
     if model_options(model_cfg) is not None:
         check_subbands(model_cfg)
-    prior_cfg = prior_settings(prior, prior_energy_max, prior_energy_min, prior_std_min, model_cfg.get("unconditional"))
-    prior_given = [k for k, v in zip(PRIOR_KEYS, (prior_energy_max, prior_energy_min, prior_std_min)) if v is not None]
+    prior_cfg = prior_settings(prior, prior_energy_max, prior_energy_min, prior_std_min, model_cfg.get("unconditional"),
+                               ref=prior_ref, floor=prior_floor, lifter=prior_lifter,
+                               n_fft=dataset_cfg.get("filter_length", 1024))
+    prior_given = [k for k, v in zip(PRIOR_KEYS + SPECTRAL_PRIOR_KEYS, (prior_energy_max, prior_energy_min, prior_std_min,
+                                                                      prior_ref, prior_floor, prior_lifter)) if v is not None]
     if isinstance(prior_cfg, dict) and cfg_scale is not None:
-        raise ValueError("generate.cfg_scale does not combine with generate.prior=energy (classifier-free guidance with an "
+        raise ValueError(f"generate.cfg_scale does not combine with generate.prior={prior} (classifier-free guidance with an "
                          "adaptive prior is not built)")
     if isinstance(prior_cfg, dict):
         prior_hop(model_cfg, dataset_cfg)
     if isinstance(prior_cfg, dict) and mel_name is None and mel_names is None:
-        raise ValueError("generate.prior=energy needs generate.mel_name or generate.mel_names (the conditioning mel)")
+        raise ValueError(f"generate.prior={prior} needs generate.mel_name or generate.mel_names (the conditioning mel)")
     if mel_names is not None:
         mel_names = _check_mel_names(mel_names, mel_name, clip_seeds, seed, known_name=known_name, start_name=start_name,
                                      resample_jump=resample_jump, guide_name=guide_name, guide_op=guide_op, label=label,
@@ -866,12 +907,36 @@ def generate(rank, diffusion_cfg, model_cfg, dataset_cfg, ckpt_iter="max", n_sam
             raise ValueError("generate.cfg_scale does not combine with the adaptive prior of the checkpoint "
                              "(generate.prior=none samples from N(0, I))")
         hop_of_prior = prior_hop(model_cfg, dataset_cfg)
-        print("adaptive prior{}: energy_max={energy_max:g} energy_min={energy_min:g} std_min={std_min:g}".format(
-            " (the checkpoint's prior entry)" if prior is None else "", **prior_cfg))
+        if prior_cfg["kind"] == "spectral":
+            given = [k for k, v in (("known_name", known_name), ("start_name", start_name),
+                                    ("start_griffinlim", start_griffinlim), ("resample_jump", resample_jump)) if v is not None]
+            if guided:
+                given.append(guide_key[len("generate."):])
+            if given:
+                raise ValueError(f"generate.{given[0]} does not combine with the spectral prior (editing, partial starts, "
+                                 "resampling and guidance draw noise the prior does not shape; generate.prior=none "
+                                 "samples from N(0, I))")
+            from .mel import TacotronSTFT
+            keys = ("filter_length", "hop_length", "win_length", "sampling_rate", "mel_fmin", "mel_fmax")
+            prior_stft = TacotronSTFT(**{k: dataset_cfg[k] for k in keys if k in dataset_cfg})
+            print("spectral prior{}: ref={ref:g} floor={floor:g} lifter={lifter}".format(
+                " (the checkpoint's prior entry)" if prior is None else "", **prior_cfg))
+        else:
+            print("adaptive prior{}: energy_max={energy_max:g} energy_min={energy_min:g} std_min={std_min:g}".format(
+                " (the checkpoint's prior entry)" if prior is None else "", **prior_cfg))
 
-    def sigma_of(mel, L):       # the prior's standard deviation [B, 1, L] of a conditioning mel, or nothing
+    def sigma_of(mel, L, frame_counts=None):
+        """The prior's sampler arguments of a conditioning mel [B, bands, frames], or nothing: the standard deviation
+        [B, 1, L] (energy), or the filter [B, K, L // hop + 1] and its STFT (spectral; clip b's last own frame, of its
+        ``frame_counts[b]``, is repeated once: a run of frames x hop samples has one frame more than its mel)."""
         if prior_cfg is None or mel is None:
             return {}
+        if prior_cfg["kind"] == "spectral":
+            filt = prior_stft.spectral_filter(mel.to(device="cuda", dtype=torch.float32), L,
+                                              **{k: prior_cfg[k] for k in SPECTRAL_PRIOR_KEYS})
+            for b, f in enumerate(frame_counts or ()):
+                filt[b, :, f] = filt[b, :, f - 1]
+            return {"prior_filter": filt, "prior_stft": prior_stft}
         from .mel import prior_std_from_mel
         return {"prior_std": prior_std_from_mel(mel.to(device="cuda", dtype=torch.float32), hop_of_prior, L,
                                                 **{k: prior_cfg[k] for k in PRIOR_KEYS})}
@@ -929,7 +994,7 @@ def generate(rank, diffusion_cfg, model_cfg, dataset_cfg, ckpt_iter="max", n_sam
             s = [seeds_of_clips(seed, k, 1)[0] for k in batch] if clip_seeds else (None if seed is None else seed + i)
             print(f"batch {i}: L_max = {Lmax}, lengths = {lens}, padded share = "
                   f"{1.0 - sum(lens) / float(len(batch) * Lmax):.3f}")
-            pr = sigma_of(mel, Lmax)     # (each frame on its own: a clip's sigma is what it is alone; its padding is unused)
+            pr = sigma_of(mel, Lmax, [frames[k] for k in batch])     # (each frame on its own: a clip's sigma is what it is alone; its padding is unused)
             run_lens = lens if bank is None else [n // K for n in lens]      # what the engine runs: sub-band positions
             if start_griffinlim is not None:
                 pr = dict(pr, **griffinlim_start(mel, [frames[k] for k in batch], lens))
@@ -1044,8 +1109,10 @@ def generate(rank, diffusion_cfg, model_cfg, dataset_cfg, ckpt_iter="max", n_sam
             edit["labels"] = [labels_of[c] for c in class_of]
             if cfg_scale is not None:
                 edit["cfg_scale"] = float(cfg_scale)
-        if prior_one:
+        if "prior_std" in prior_one:
             edit["prior_std"] = prior_one["prior_std"].expand(len(batch), 1, audio_length)
+        elif prior_one:
+            edit.update(prior_one, prior_filter=prior_one["prior_filter"].expand(len(batch), -1, -1))
         if guide is not None:
             ddim = sampler == "ddim"
             guide_b = dict(guide, measurement=guide["measurement"][:len(batch)])

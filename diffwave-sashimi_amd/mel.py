@@ -161,10 +161,11 @@ def _check_spectrum(what, name, t, shape=None):
         raise ValueError(f"{what}: {name} has shape {tuple(t.shape)}, expected magnitude's {tuple(shape)}")
 
 
-def _check_inversion(what, magnitude, phase, window, hop_length, lengths):
-    """Argument checks of ``istft`` / ``griffin_lim`` (ValueError before anything runs).  Returns ``(n_fft, hop, host)``:
-    ``host`` the lengths as a list of ints, or None."""
-    _check_spectrum(what, "magnitude", magnitude)
+def _check_inversion(what, magnitude, phase, window, hop_length, lengths, name="magnitude"):
+    """Argument checks of ``istft`` / ``griffin_lim`` / ``tv_filter`` (ValueError before anything runs); ``name`` is what
+    the messages call the [B, K, F] array.  Returns ``(n_fft, hop, host)``: ``host`` the lengths as a list of ints, or
+    None."""
+    _check_spectrum(what, name, magnitude)
     B, K, F = (int(v) for v in magnitude.shape)
     if isinstance(phase, torch.Tensor):
         _check_spectrum(what, "phase", phase, magnitude.shape)
@@ -172,13 +173,13 @@ def _check_inversion(what, magnitude, phase, window, hop_length, lengths):
             raise ValueError(f"{what}: phase is on {phase.device}, magnitude on {magnitude.device}")
     if not isinstance(window, torch.Tensor) or window.dim() != 1 or window.dtype != torch.float32 or \
             window.device != magnitude.device or window.requires_grad:
-        raise ValueError(f"{what}: window must be a float32 tensor [n_fft] on magnitude's device that does not require grad "
+        raise ValueError(f"{what}: window must be a float32 tensor [n_fft] on {name}'s device that does not require grad "
                          f"(got shape {tuple(getattr(window, 'shape', ()))!r})")
     n_fft = int(window.shape[0])
     if n_fft < 64 or n_fft > 4096 or n_fft & (n_fft - 1):
         raise ValueError(f"{what}: window has {n_fft} points: n_fft must be a power of two in 64 .. 4096")
     if B < 1 or K != n_fft // 2 + 1:
-        raise ValueError(f"{what}: magnitude has shape {(B, K, F)}, expected K = n_fft/2 + 1 = {n_fft // 2 + 1} bins "
+        raise ValueError(f"{what}: {name} has shape {(B, K, F)}, expected K = n_fft/2 + 1 = {n_fft // 2 + 1} bins "
                          "and at least one clip")
     if not _is_int(hop_length) or hop_length < 1:
         raise ValueError(f"{what}: hop_length = {hop_length!r} (needs an integer >= 1)")
@@ -263,6 +264,130 @@ def griffin_lim(magnitude, *, window, hop_length, n_iters=32, momentum=0.0, phas
     elif isinstance(phase, str):
         phase = None
     return _invert(magnitude, phase, window, n_fft, hop, host, n_iters, momentum)
+
+
+# ---- time-varying spectral filter: dws_tv_filter (csrc/tvfilter_kernels.hip; DESIGN.md section 4, "Spectral prior")
+def _tv_filter_call(x, fr, fi, window, n_fft, hop, host, adjoint):
+    lib = _lib.load()
+    B, T = (int(v) for v in x.shape)
+    F = T // hop + 1
+    out = torch.empty_like(x)
+    ws = torch.empty(lib.dws_griffin_lim_workspace(B, F, n_fft, hop, 0) // 4, device=x.device, dtype=torch.float32)
+    dev_len = None if host is None else torch.tensor(host, dtype=torch.int32).to(x.device)
+    host_len = None if host is None else (ctypes.c_int32 * B)(*host)
+    with torch.cuda.device(x.device):
+        _lib.check(lib.dws_tv_filter(x.data_ptr(), B, F, _lib.ptr(dev_len), host_len, fr.data_ptr(), _lib.ptr(fi),
+                                     window.data_ptr(), n_fft, hop, int(adjoint), out.data_ptr(), ws.data_ptr(),
+                                     _lib.current_stream()))
+    return out
+
+
+class _TvFilter(torch.autograd.Function):
+    """``dws_tv_filter`` on ``x`` [B, T] (cuda, float32, contiguous); the backward is the same call with ``adjoint``
+    flipped, as a node that cannot be differentiated again."""
+
+    @staticmethod
+    def forward(ctx, x, fr, fi, window, n_fft, hop, host, adjoint, again):
+        ctx.save_for_backward(fr, fi, window)
+        ctx.args = (n_fft, hop, host, adjoint, again)
+        return _tv_filter_call(x, fr, fi, window, n_fft, hop, host, adjoint)
+
+    @staticmethod
+    def backward(ctx, g):
+        n_fft, hop, host, adjoint, again = ctx.args
+        if not again:
+            raise RuntimeError("tv_filter: the second derivative is not built (the backward of dws_tv_filter is a "
+                               "first-order adjoint; there is no double backward)")
+        fr, fi, window = ctx.saved_tensors
+        dx = _TvFilter.apply(g.to(torch.float32).contiguous(), fr, fi, window, n_fft, hop, host, not adjoint, False)
+        return dx, None, None, None, None, None, None, None, None
+
+
+def tv_filter(x, filt, *, window, hop_length, lengths=None, adjoint=False):
+    """The time-varying spectral filter ``G+ (filt . G x)`` in ``dws_tv_filter``: ``x`` [B, T] (cuda, float32, T a multiple
+    of ``hop_length``) is framed as ``mel_spectrogram`` frames it (centred, reflected about each clip's own ends), every
+    frame's spectrum is multiplied by ``filt`` [B, K, T // hop_length + 1] (complex64, or float32 for a real filter;
+    ``K = n_fft/2 + 1``, torch.stft's sign convention) and the frames go back through ``istft``'s normalised overlap-add
+    -> [B, T].  ``adjoint=True`` is the exact transpose of that linear map (with the same ``filt``), not its inverse.
+    ``window`` [n_fft] on the same device; ``lengths`` as in ``istft`` (filter frames behind a clip's own are not read).
+    Differentiable in ``x``: the backward is this call with ``adjoint`` flipped; first order only (a second derivative
+    is a RuntimeError).  No filter gradient is built: ``filt.requires_grad`` is a ValueError.  Bad arguments raise
+    ValueError before anything runs; there is no CPU path."""
+    what = "tv_filter"
+    if not isinstance(filt, torch.Tensor) or filt.dim() != 3 or filt.dtype not in (torch.complex64, torch.float32):
+        raise ValueError(f"{what}: filt has shape {tuple(getattr(filt, 'shape', ()))!r} and dtype "
+                         f"{getattr(filt, 'dtype', type(filt).__name__)}, expected a complex64 or float32 tensor [B, K, F]")
+    if filt.requires_grad:
+        raise ValueError(f"{what}: filt requires grad: no gradient with respect to the filter is built (detach it)")
+    if not isinstance(x, torch.Tensor) or x.dim() != 2 or x.dtype != torch.float32:
+        raise ValueError(f"{what}: x has shape {tuple(getattr(x, 'shape', ()))!r} and dtype "
+                         f"{getattr(x, 'dtype', type(x).__name__)}, expected a float32 tensor [B, T]")
+    if x.device.type != "cuda" or filt.device != x.device:
+        raise ValueError(f"{what}: x is on {x.device}, filt on {filt.device}: libdws runs on the GPU only, on one device "
+                         "(there is no CPU path)")
+    if not isinstance(adjoint, (bool, np.bool_)):
+        raise ValueError(f"{what}: adjoint = {adjoint!r} (needs True or False)")
+    if _is_int(hop_length) and hop_length >= 1 and (x.shape[1] % hop_length or
+                                                    tuple(filt.shape[::2]) != (x.shape[0], x.shape[1] // hop_length + 1)):
+        raise ValueError(f"{what}: x {tuple(x.shape)} at hop_length {hop_length} needs T a multiple of the hop and filt "
+                         f"[B, K, T // hop_length + 1], got {tuple(filt.shape)}")
+    fr = torch.view_as_real(filt.contiguous()) if filt.is_complex() else None
+    fi = None if fr is None else fr[..., 1].contiguous()
+    fr = filt.contiguous() if fr is None else fr[..., 0].contiguous()
+    n_fft, hop, host = _check_inversion(what, fr, None, window, hop_length, lengths, name="filt")
+    window = window.contiguous()
+    if x.requires_grad and torch.is_grad_enabled():
+        return _TvFilter.apply(x.contiguous(), fr, fi, window, n_fft, hop, host, bool(adjoint), True)
+    return _tv_filter_call(x.detach().contiguous(), fr, fi, window, n_fft, hop, host, bool(adjoint))
+
+
+def _check_filter_design(ref, floor, lifter, n_fft):
+    try:
+        r, fl = float(ref), float(floor)
+    except (TypeError, ValueError):
+        raise ValueError(f"spectral_filter: ref = {ref!r}, floor = {floor!r} (need numbers)")
+    if not (np.isfinite(r) and r > 0.0):
+        raise ValueError(f"spectral_filter: ref = {ref!r} (needs a finite magnitude > 0: the one that maps to gain 1)")
+    if not 0.0 < fl <= 1.0:
+        raise ValueError(f"spectral_filter: floor = {floor!r} (needs 0 < floor <= 1)")
+    if not _is_int(lifter) or not 1 <= lifter <= n_fft // 2 - 1:
+        raise ValueError(f"spectral_filter: lifter = {lifter!r} (needs an integer in 1 .. n_fft/2 - 1 = {n_fft // 2 - 1})")
+    return r, fl, int(lifter)
+
+
+def minimum_phase_filter(magnitude, n_frames=None, *, ref, floor=0.01, lifter=24):
+    """The filter design of ``TacotronSTFT.spectral_filter`` on linear magnitudes [B, K, frames] (any device; taken in
+    float64): ``P = max(M, floor ref)^2 / ref^2``, ``c = irfft(log P, n_fft)``, ``c_mp[0] = c[0]``, ``c_mp[n] = 2 c[n]``
+    for 1 <= n <= lifter, 0 elsewhere, ``F = exp(rfft(c_mp) / 2)`` -> complex64 [B, K, n_frames].  Frame f of the result
+    comes from frame ``min(f, frames - 1)`` of the magnitudes (default ``n_frames = frames``)."""
+    if not isinstance(magnitude, torch.Tensor) or magnitude.dim() != 3 or not magnitude.dtype.is_floating_point:
+        raise ValueError(f"spectral_filter: magnitudes of shape {tuple(getattr(magnitude, 'shape', ()))!r}, expected a "
+                         "float tensor [B, K, frames]")
+    B, K, frames = (int(v) for v in magnitude.shape)
+    n_fft = 2 * (K - 1)
+    if B < 1 or frames < 1 or K < 3:
+        raise ValueError(f"spectral_filter: empty magnitudes {tuple(magnitude.shape)}")
+    r, fl, lifter = _check_filter_design(ref, floor, lifter, n_fft)
+    n_frames = frames if n_frames is None else n_frames
+    if not _is_int(n_frames) or n_frames < 1:
+        raise ValueError(f"spectral_filter: {n_frames!r} frames (needs an integer >= 1)")
+    m = magnitude.detach().to(torch.float64).transpose(1, 2)                # [B, frames, K]
+    logp = 2.0 * torch.log(m.clamp(min=fl * r) / r)
+    c = torch.fft.irfft(logp, n=n_fft, dim=-1)
+    c_mp = torch.zeros_like(c)
+    c_mp[..., 0] = c[..., 0]
+    c_mp[..., 1:lifter + 1] = 2.0 * c[..., 1:lifter + 1]
+    F = torch.exp(0.5 * torch.fft.rfft(c_mp, dim=-1))
+    F.imag[..., 0] = 0.0                # exactly real at DC and Nyquist (rfft leaves rounding there at most)
+    F.imag[..., -1] = 0.0
+    idx = torch.arange(int(n_frames), device=F.device).clamp(max=frames - 1)
+    return F[:, idx].transpose(1, 2).to(torch.complex64).contiguous()
+
+
+def spectral_prior_ref(mel, stft):
+    """The largest linear magnitude ``stft.mel_to_magnitude(mel)`` holds (``stft`` a ``TacotronSTFT``), as a float:
+    scanned over a dataset it is the ``ref`` of ``TacotronSTFT.spectral_filter`` (the magnitude that maps to gain 1)."""
+    return float(stft.mel_to_magnitude(mel).max())
 
 
 class _MelBackward(torch.autograd.Function):
@@ -382,6 +507,39 @@ class TacotronSTFT:
         # the product in float64, rounded once: a float32 GEMM adds the bands in an order that depends on the batch's
         # shape, and a clip's magnitudes (so its inversion) must not depend on the batch around it
         return torch.matmul(self._pinv_dev[mel.device], torch.exp(mel).double()).clamp_(min=0.0).float()
+
+    def spectral_filter(self, mel, L=None, *, ref, floor=0.01, lifter=24):
+        """The noise-shaping filter of the spectral prior (SpecGrad: Koizumi et al., Interspeech 2022) from a clip's own
+        log-mel [B, n_mel_channels, frames] (cuda, float32): complex64 [B, K, L // hop_length + 1] on the mel's device
+        (default ``L = frames * hop_length``, a multiple of the hop), the ``filt`` of ``tv_filter``.  Per frame, with
+        ``M = mel_to_magnitude(mel)``::
+
+            P    = max(M, floor * ref)^2 / ref^2                 the envelope, 1 at the magnitude ``ref``
+            c    = irfft(log P, n_fft)                           its cepstrum
+            c_mp = c[0], 2 c[1 .. lifter], 0 elsewhere           liftered and folded: the minimum-phase cepstrum
+            F    = exp(rfft(c_mp) / 2)
+
+        so ``|F|^2`` is the cepstrally smoothed envelope, F is minimum phase and its imaginary part is 0 at DC and
+        Nyquist.  Frame f of the filter comes from mel frame ``min(f, frames - 1)``: a training segment's mel has L / hop
+        frames, the framing L / hop + 1.  Everything runs in float64 torch and is rounded to complex64 once (a
+        ``torch.fft`` over [B, frames, n_fft]: not the hot path).  ``ref`` is required: the magnitude that maps to gain
+        1, a property of the dataset (``spectral_prior_ref`` scans for it); ``floor`` in (0, 1] keeps ``1 / F`` finite,
+        ``lifter`` in 1 .. n_fft/2 - 1 is the number of cepstral coefficients kept.  The inverse filter of the training
+        loss is ``1 / F``: ``tv_filter(., 1 / F)`` stands for the inverse of ``tv_filter(., F)`` as in the paper -- an
+        approximation (frames overlap and the window is not flat), not an exact inverse.  Bad arguments raise
+        ValueError."""
+        r, fl, lifter = _check_filter_design(ref, floor, lifter, self.filter_length)
+        mag = self.mel_to_magnitude(mel)
+        frames = int(mag.shape[-1])
+        L = frames * self.hop_length if L is None else L
+        if not _is_int(L) or L < self.hop_length or L % self.hop_length or L > frames * self.hop_length:
+            raise ValueError(f"spectral_filter: L = {L!r} (needs a multiple of hop_length = {self.hop_length} in "
+                             f"{self.hop_length} .. frames * hop_length = {frames * self.hop_length})")
+        return minimum_phase_filter(mag, int(L) // self.hop_length + 1, ref=r, floor=fl, lifter=lifter)
+
+    def spectral_prior_ref(self, mel):
+        """``spectral_prior_ref(mel, self)``."""
+        return spectral_prior_ref(mel, self)
 
     def mel_to_audio(self, mel, n_iters=32, momentum=0.0, seed=0, lengths=None):
         """``griffin_lim(mel_to_magnitude(mel))`` from seeded random phases: log-mel [B, n_mel_channels, F] ->

@@ -114,6 +114,78 @@ def _set_prior(net, sigma):
                                              _lib.current_stream()))
 
 
+SPECTRAL_NOISE_LIMIT = 4 << 30      # bytes of injected noise a spectral-prior run may hold: the cap of the CFG step table
+
+
+def philox_normal(size, seed, stream_id, device="cuda"):
+    """The standard-normal numbers a seeded run draws, as a float32 tensor of shape ``size = (B, C, L)`` on ``device``:
+    Philox stream ``stream_id`` of the scalar ``seed`` over the whole batch (``dws_philox_normal``), or, with a list of B
+    seeds, of every clip's own seed over its C L elements (``dws_philox_normal_clips``).  Stream ids as include/dws.h
+    numbers them: s for the update noise of step s, S for x_T."""
+    B, C, L = (int(v) for v in size)
+    z = torch.empty(B, C, L, device=device, dtype=torch.float32)
+    with torch.cuda.device(z.device):
+        if isinstance(seed, (list, tuple)):
+            _lib.check(_lib.load().dws_philox_normal_clips(z.data_ptr(), B, C * L, (ctypes.c_uint64 * B)(*seed), stream_id,
+                                                           _lib.current_stream()))
+        else:
+            _lib.check(_lib.load().dws_philox_normal(z.data_ptr(), z.numel(), seed, stream_id, _lib.current_stream()))
+    return z
+
+
+def _spectral_prior_run(who, size, S, noisy, prior_filter, prior_stft, x_T, noise, seed, lengths, refused):
+    """The spectral prior (``prior_filter=`` / ``prior_stft=``) of a sampler: checks (ValueError), then the run's
+    standard-normal numbers -- drawn here from the documented Philox streams, or injected -- through
+    ``mel.tv_filter(., prior_filter)``.  Returns ``(x_T, noise, seed)`` to hand to the plain run: ``x_T`` [B, 1, L] (an
+    injected one is a state and is returned as given), ``noise`` [S, B, 1, L] (None where ``noisy`` is false: the run
+    consumes no update noise; row 0 is never read and holds 0) and the seed that was drawn where none was given."""
+    from .mel import tv_filter
+    if prior_stft is None or prior_filter is None:
+        raise ValueError(f"{who}: prior_filter (the filter) and prior_stft (the TacotronSTFT that frames it) come together")
+    for name, v in refused.items():
+        if v is not None:
+            raise ValueError(f"{who}: prior_filter= (spectral prior) is not built together with {name}= (its noise sites "
+                             "are not shaped)")
+    B, C, L = (int(v) for v in size)
+    if C != 1:
+        raise ValueError(f"{who}: prior_filter= needs one audio channel (size = {tuple(size)})")
+    if noisy and S * B * L * 4 > SPECTRAL_NOISE_LIMIT:
+        raise ValueError(f"{who}: prior_filter= holds the shaped update noise of the whole run, [{S}, {B}, 1, {L}] float32 = "
+                         f"{S * B * L * 4 / 1e9:.2f} GB (limit {SPECTRAL_NOISE_LIMIT / 1e9:.2f} GB): sample fewer steps or "
+                         "clips at a time")
+    if not isinstance(prior_filter, torch.Tensor) or prior_filter.device.type != "cuda":
+        raise ValueError(f"{who}: prior_filter must be a cuda tensor [B, K, L // hop + 1] (TacotronSTFT.spectral_filter)")
+    dev = prior_filter.device
+    tv = dict(window=prior_stft._tables(dev)[0], hop_length=prior_stft.hop_length,
+              lengths=None if lengths is None else list(lengths))
+    seeds = seed_list(seed, B)
+    if seeds is None and seed is None:
+        seed = int(torch.randint(0, 2 ** 63 - 1, (1,), dtype=torch.int64).item())
+    draw = seeds if seeds is not None else int(seed)
+    with torch.no_grad():
+        if x_T is None:
+            x_T = tv_filter(philox_normal(size, draw, S, dev).view(B, L), prior_filter, **tv).view(B, 1, L)
+        if not noisy:
+            return x_T, None, seed
+        if noise is not None and tuple(noise.shape) != (S, B, C, L):
+            raise ValueError(f"{who}: noise has shape {tuple(noise.shape)}, expected {(S, B, C, L)}")
+        shaped = torch.zeros(S, B, 1, L, device=dev, dtype=torch.float32)
+        for s in range(1, S):       # a chunk of B clips per call; noise[0] is not read by any sampler
+            z = philox_normal(size, draw, s, dev) if noise is None else noise[s].detach().to(device=dev, dtype=torch.float32)
+            shaped[s] = tv_filter(z.reshape(B, L).contiguous(), prior_filter, **tv).view(B, 1, L)
+    return x_T, shaped, seed
+
+
+def spectral_prior_noise(size, steps, prior_filter, prior_stft, *, seed=None, lengths=None, x_T=None, noise=None,
+                         update_noise=True):
+    """What a sampler with ``prior_filter=`` hands to the plain run, as a call of its own: ``(x_T, noise, seed)`` with
+    ``x_T = T_F(z_S)`` [B, 1, L], ``noise[s] = T_F(z_s)`` [steps, B, 1, L] (None with ``update_noise=False``: DDIM at
+    eta = 0, DPM-Solver++) and the seed that was drawn where none was given -- the shaped noise of a run of ``steps``
+    steps at ``size = (B, 1, L)``, for holding it across runs or timing it."""
+    return _spectral_prior_run("spectral_prior_noise", size, int(steps), bool(update_noise), prior_filter, prior_stft, x_T,
+                               noise, seed, lengths, {})
+
+
 def _splitmix64(z):
     """The splitmix64 finaliser (Steele, Lea & Flood, 2014) of a 64-bit integer, in host integer arithmetic."""
     z = (z + _GOLDEN64) & _MASK64
@@ -402,8 +474,26 @@ def _check_edit(size, S, x_T, known=None, mask=None, known_noise=None, x_start=N
 
 def sampling(net, size, diffusion_hyperparams, condition=None, *, x_T=None, noise=None, seed=None,
              use_graph=True, net_steps=None, known=None, mask=None, known_noise=None, x_start=None, start_step=None,
-             start_noise=None, resample=None, labels=None, cfg_scale=None, lengths=None, prior_std=None):
+             start_noise=None, resample=None, labels=None, cfg_scale=None, lengths=None, prior_std=None,
+             prior_filter=None, prior_stft=None):
     """``x_0 = sampling(net, (B, C, L), dh, condition)`` as in ``generate.py:23-55``.
+
+    Spectral prior (SpecGrad: Koizumi et al., Interspeech 2022; ``dws_tv_filter``), on ``sampling``, ``sampling_aligned``,
+    ``sampling_ddim`` and ``sampling_dpmpp``:
+      prior_filter, prior_stft  the complex64 filter F [B, K, L // hop + 1] of ``prior_stft.spectral_filter`` on the
+             conditioning mel, and that ``mel.TacotronSTFT`` (its window and hop frame the filter; L a multiple of the
+             hop, one channel).  The run ends in N(0, Sigma), Sigma = T_F T_F^T with T_F = ``mel.tv_filter(., F)``.
+             Nothing in the engine's sampler changes: this wrapper draws the run's standard-normal numbers itself
+             (``philox_normal``: stream S for x_T, stream s for the update noise of step s, of the scalar seed or of
+             every clip's own), filters them B clips at a time ahead of the loop and hands them over as the injected
+             ``x_T`` and ``noise``.  The contract: the run is bit-equal to the plain run (no ``prior_filter``) that is
+             handed ``x_T = T_F(z_S)`` and ``noise[s] = T_F(z_s)``.  An injected ``x_T`` is a state and is taken as
+             given; an injected ``noise`` stays standard normal and is filtered.  DDIM at eta = 0 and DPM-Solver++
+             consume no update noise: only ``x_T`` is shaped.  The shaped noise of the whole run, [S, B, 1, L], is held
+             at once: above 4 GB it is a ValueError naming the size.  The network must have been trained for it
+             (``training_loss(prior_filter=)``).  Combines with ``seed=[...]``, ``labels`` and ``lengths`` (multiples
+             of the hop); refused (ValueError) with ``prior_std``, ``cfg_scale``, the editing / start / resample
+             arguments and on ``sampling_guided``, whose noise sites are not shaped.
 
     Adaptive prior (PriorGrad: Lee et al., ICLR 2022; ``dws_sampler_set_prior``), on every sampler of this module:
       prior_std  float tensor [B, 1, L] or [B, C, L], finite and > 0 (``mel.prior_std_from_mel``): the run ends in
@@ -466,6 +556,10 @@ def sampling(net, size, diffusion_hyperparams, condition=None, *, x_T=None, nois
     assert len(Alpha) == T and len(Alpha_bar) == T and len(Sigma) == T and len(size) == 3
     edit = dict(known=known, mask=mask, known_noise=known_noise, x_start=x_start, start_step=start_step,
                 start_noise=start_noise)
+    if prior_filter is not None or prior_stft is not None:
+        S = T if net_steps is None else len(np.asarray(net_steps).reshape(-1))
+        x_T, noise, seed = _spectral_prior_run("sampling", size, S, True, prior_filter, prior_stft, x_T, noise, seed, lengths,
+                                               dict(edit, resample=resample, cfg_scale=cfg_scale, prior_std=prior_std))
     lengths = _check_lengths(net, size, lengths, cfg_scale)
     if prior_std is not None and cfg_scale is not None:      # (the table itself is checked by _run_schedule, where it goes)
         _check_prior(size, prior_std, cfg_scale)
@@ -638,15 +732,21 @@ def ddim_coefficients(alpha_bar, tau, eta):
 
 def sampling_ddim(net, size, dh_train, steps, eta=0.0, condition=None, *, x_T=None, noise=None, seed=None,
                   use_graph=True, known=None, mask=None, known_noise=None, x_start=None, start_step=None,
-                  start_noise=None, resample=None, labels=None, cfg_scale=None, lengths=None, prior_std=None):
+                  start_noise=None, resample=None, labels=None, cfg_scale=None, lengths=None, prior_std=None,
+                  prior_filter=None, prior_stft=None):
     """DDIM over ``ddim_steps(T, steps)`` of the training schedule ``dh_train`` (``steps``: S or an explicit list),
     deterministic for ``eta = 0``.  ``noise``: injected z, [S, B, C, L] (``noise[s]`` is used after step s > 0).
     The editing arguments, ``resample``, ``labels``, ``cfg_scale`` and ``prior_std`` are those of ``sampling`` (levels:
-    ``Alpha_bar[tau]``).  Not the reference's loop."""
+    ``Alpha_bar[tau]``); ``prior_filter`` / ``prior_stft`` (spectral prior) as there too: at ``eta = 0`` only ``x_T``
+    is shaped.  Not the reference's loop."""
     tau = ddim_steps(dh_train["T"], steps)
     coef = ddim_coefficients(dh_train["Alpha_bar"], tau, eta)
     edit = dict(known=known, mask=mask, known_noise=known_noise, x_start=x_start, start_step=start_step,
                 start_noise=start_noise)
+    if prior_filter is not None or prior_stft is not None:
+        x_T, noise, seed = _spectral_prior_run("sampling_ddim", size, len(tau), float(eta) != 0.0, prior_filter, prior_stft,
+                                               x_T, noise, seed, lengths,
+                                               dict(edit, resample=resample, cfg_scale=cfg_scale, prior_std=prior_std))
     if resample is None and all(v is None for v in edit.values()):
         edit = None
     return _run_schedule(net, size, _lib.DWS_SAMPLER_DDIM, np.asarray(tau, dtype=np.float32), coef, condition, x_T,
@@ -706,7 +806,7 @@ def dpmpp_coefficients(alpha_bar, tau):
 def sampling_dpmpp(net, size, dh_train, steps, condition=None, *, spacing="logsnr", x_T=None, seed=None,
                    use_graph=True, known=None, mask=None, known_noise=None, x_start=None, start_step=None,
                    start_noise=None, resample=None, noise=None, labels=None, cfg_scale=None, lengths=None,
-                   prior_std=None):
+                   prior_std=None, prior_filter=None, prior_stft=None):
     """DPM-Solver++(2M) over ``logsnr_steps(Alpha_bar, steps)`` of the training schedule ``dh_train``
     (``spacing="uniform"``: over ``ddim_steps(T, steps)``; ``steps``: S or an explicit list).  Second order at the cost
     of DDIM: one network evaluation per step, the previous step's data prediction kept on the device.  Deterministic:
@@ -714,8 +814,9 @@ def sampling_dpmpp(net, size, dh_train, steps, condition=None, *, spacing="logsn
     accepted only together with ``resample`` ([V, B, C, L], of which the rows of jump visits are read).  The editing
     arguments and ``resample`` are those of ``sampling`` (levels: ``Alpha_bar[tau]``); the step after a jump and the
     first step of a partial start are first order.  ``labels`` / ``cfg_scale`` as in ``sampling``; ``prior_std`` as
-    there too: with no update noise it scales a drawn ``x_T`` and the known-region, start and jump noise.  Not the
-    reference's loop."""
+    there too: with no update noise it scales a drawn ``x_T`` and the known-region, start and jump noise;
+    ``prior_filter`` / ``prior_stft`` (spectral prior) as in ``sampling``: only ``x_T`` is shaped.  Not the reference's
+    loop."""
     if spacing not in ("logsnr", "uniform"):
         raise ValueError(f"sampling_dpmpp: spacing = {spacing!r} (expected 'logsnr' or 'uniform')")
     if noise is not None and resample is None:
@@ -726,6 +827,10 @@ def sampling_dpmpp(net, size, dh_train, steps, condition=None, *, spacing="logsn
     coef = dpmpp_coefficients(ab, tau)
     edit = dict(known=known, mask=mask, known_noise=known_noise, x_start=x_start, start_step=start_step,
                 start_noise=start_noise)
+    if prior_filter is not None or prior_stft is not None:
+        x_T, _, seed = _spectral_prior_run("sampling_dpmpp", size, len(tau), False, prior_filter, prior_stft, x_T, None,
+                                           seed, lengths, dict(edit, resample=resample, cfg_scale=cfg_scale,
+                                                               prior_std=prior_std, noise=noise))
     if resample is None and all(v is None for v in edit.values()):
         edit = None
     return _run_schedule(net, size, _lib.DWS_SAMPLER_DPMPP2M, np.asarray(tau, dtype=np.float32), coef, condition, x_T,
@@ -886,6 +991,11 @@ def sampling_guided(net, size, diffusion_hyperparams, *, measurement, operator, 
     class-conditional model) are passed to every network call.  ``prior_std`` ([B, 1, L] or [B, C, L], finite, > 0): the
     adaptive prior of ``sampling`` -- every z, drawn or injected, is multiplied by it (one product of its own) before
     ``c z`` is formed, and so is a drawn initial state; it works with any ``net``.  Not the reference's loop."""
+    if unsupported.get("prior_filter") is not None or unsupported.get("prior_stft") is not None:
+        raise ValueError("sampling_guided: prior_filter= (spectral prior) is not built for guided runs (their noise sites "
+                         "are not shaped)")
+    unsupported.pop("prior_filter", None)
+    unsupported.pop("prior_stft", None)
     if unsupported.get("cfg_scale") is not None and prior_std is not None:
         raise ValueError("sampling_guided: prior_std= (adaptive prior) is not built for classifier-free guidance (cfg_scale=)")
     if unsupported.get("lengths") is not None:

@@ -32,7 +32,7 @@ import numpy as np
 import torch
 import torch.nn as nn
 
-from .generate import (PRIOR_KEYS, find_max_epoch, generate, load_config, local_directory, prior_hop, prior_settings,
+from .generate import (PRIOR_KEYS, SPECTRAL_PRIOR_KEYS, find_max_epoch, generate, load_config, local_directory, prior_hop, prior_settings,
                        same_prior)
 
 HASH_DIVIDER, EXCEPT_FOLDER = "_nohash_", "_background_noise_"   # `dataloaders/sc.py:15-16`
@@ -223,7 +223,7 @@ def train(rank, num_gpus, diffusion_cfg, model_cfg, dataset_cfg, generate_cfg, c
           iters_per_logging, learning_rate, batch_size_per_gpu, name=None, exp_root="exp", num_workers=4, precision=None,
           honour_optim_hints=False, label_dropout=None, optimizer=None, ema_decay=None, clip_grad_norm=None, prior=None,
           prior_energy_max=None, prior_energy_min=None, prior_std_min=None, stft_weight=None, stft_max_step=None,
-          stft_resolutions=None):
+          stft_resolutions=None, prior_ref=None, prior_floor=None, prior_lifter=None):
     """``train.py:49-196``.  With ``model.n_classes`` (class-conditional; not in the reference) every batch's class
     indices go to the network and ``label_dropout`` (``train.label_dropout``, default 0.1) of them are replaced by the
     null class, which is what classifier-free guidance needs at sampling time; the in-loop ``generate`` cycles the
@@ -241,6 +241,14 @@ def train(rank, num_gpus, diffusion_cfg, model_cfg, dataset_cfg, generate_cfg, c
     which ``generate`` -- the in-loop one too -- picks up.  A resume must name the prior the checkpoint was trained with
     (none for a checkpoint without an entry): anything else raises ``PriorMismatch`` (a ValueError).  What such a model
     sounds like has not been measured.
+
+    ``prior=spectral`` (``+train.prior=spectral +train.prior_ref=R [+train.prior_floor=0.01 +train.prior_lifter=24]``; not
+    in the reference; mel-conditional models, one audio channel): the time-varying spectral prior of SpecGrad (Koizumi et
+    al., Interspeech 2022).  Every batch is noised with ``eps = T_F(z)``, F = ``TacotronSTFT.spectral_filter`` of its own
+    mel segment at the dataset's STFT keys, and trained on ``mean(T_{1/F}(eps_theta - eps)^2)``
+    (``training_loss(prior_filter=)``; ``dws_tv_filter``).  The checkpoints' ``prior`` entry is then
+    ``{"kind": "spectral", "ref", "floor", "lifter"}``; ``generate`` and a resume treat it as above (an energy entry and
+    a spectral entry never match).  What such a model sounds like has not been measured.
 
     ``stft_weight`` (``+train.stft_weight=W [+train.stft_max_step=K] [+train.stft_resolutions=[[n_fft,hop,win],...]]``;
     not in the reference; one audio channel): adds W times Parallel WaveGAN's multi-resolution STFT loss of the denoised
@@ -268,9 +276,20 @@ def train(rank, num_gpus, diffusion_cfg, model_cfg, dataset_cfg, generate_cfg, c
         raise ValueError("train.prior does not combine with model.subbands (the adaptive prior is a full-band quantity; "
                          "its sub-band form is not built)")
     prior_cfg = prior_settings(prior, prior_energy_max, prior_energy_min, prior_std_min, model_cfg.get("unconditional"),
-                               where="train")
+                               where="train", ref=prior_ref, floor=prior_floor, lifter=prior_lifter,
+                               n_fft=dataset_cfg.get("filter_length", 1024))
     prior_cfg = prior_cfg if isinstance(prior_cfg, dict) else None
     prior_h = prior_hop(model_cfg, dataset_cfg) if prior_cfg is not None else None
+    spectral = prior_cfg is not None and prior_cfg["kind"] == "spectral"
+    if spectral and model_cfg.get("in_channels", 1) != 1:
+        raise ValueError(f"train.prior=spectral needs model.in_channels = 1 (got {model_cfg.get('in_channels')!r})")
+
+    def prior_of(mel, L):       # the prior's arguments of training_loss from a batch's own mel
+        if spectral:
+            return dict(prior_filter=stft.spectral_filter(mel, L, **{k: prior_cfg[k] for k in SPECTRAL_PRIOR_KEYS}),
+                        prior_stft=stft)
+        from .mel import prior_std_from_mel
+        return dict(prior_std=prior_std_from_mel(mel, prior_h, L, **{k: prior_cfg[k] for k in PRIOR_KEYS}))
     from .distributed_util import apply_gradient_allreduce, reduce_tensor
     from .models import construct_model
     from .sampling import calc_diffusion_hyperparams
@@ -379,18 +398,13 @@ def train(rank, num_gpus, diffusion_cfg, model_cfg, dataset_cfg, generate_cfg, c
                 parts = {}
                 more = dict(labels=data[2], label_dropout=label_dropout) if n_classes else {}
                 if prior_cfg is not None:
-                    from .mel import prior_std_from_mel
-                    more["prior_std"] = prior_std_from_mel(mel, prior_h, audio.shape[-1],
-                                                           **{k: prior_cfg[k] for k in PRIOR_KEYS})
+                    more.update(prior_of(mel, audio.shape[-1]))
                 loss = training_loss(net, loss_fn, audio, dh, mel_spec=mel, stft_weight=stft_cfg["weight"],
                                      stft_max_step=stft_cfg["max_step"], stft_resolutions=stft_cfg["resolutions"],
                                      parts=parts, **more, **band)
             elif prior_cfg is not None:
-                from .mel import prior_std_from_mel
-                sigma = prior_std_from_mel(mel, prior_h, audio.shape[-1],
-                                           **{k: prior_cfg[k] for k in PRIOR_KEYS})
                 more = dict(labels=data[2], label_dropout=label_dropout) if n_classes else {}
-                loss = training_loss(net, loss_fn, audio, dh, mel_spec=mel, prior_std=sigma, **more)
+                loss = training_loss(net, loss_fn, audio, dh, mel_spec=mel, **prior_of(mel, audio.shape[-1]), **more)
             elif n_classes:    # (the labels stay on the host: the engine takes them from there, nothing waits for the GPU)
                 loss = training_loss(net, loss_fn, audio, dh, mel_spec=mel, labels=data[2], label_dropout=label_dropout,
                                      **band)

@@ -96,7 +96,7 @@ def stft_loss_options(stft_weight=None, stft_max_step=None, stft_resolutions=Non
 
 def training_loss(net, loss_fn, audio, diffusion_hyperparams, mel_spec=None, generator=None, labels=None,
                   label_dropout=0.0, prior_std=None, stft_weight=None, stft_max_step=None, stft_resolutions=None,
-                  parts=None, pqmf=None):
+                  parts=None, pqmf=None, prior_filter=None, prior_stft=None):
     """``train.py:198-222``: ``t ~ U{0..T-1}``, ``z ~ N(0, I)``, ``loss_fn(net((x_t, t), mel), z)``.
     Steps and noise are drawn on the CPU generator exactly like the reference (then moved, through pinned staging
     buffers so the host does not stall), so a seeded call consumes the RNG stream in the same order.
@@ -136,9 +136,31 @@ def training_loss(net, loss_fn, audio, diffusion_hyperparams, mel_spec=None, gen
     ``pqmf.analysis(audio)`` as its audio, bit for bit.  With ``stft_weight`` the spectral term stays a full-band one,
     ``mr_stft_loss(pqmf.synthesis(x0_hat), audio)``: its gradient reaches eps_theta through the synthesis bank's adjoint.
     ``prior_std`` with ``pqmf`` is a ValueError (sigma is a full-band quantity; its sub-band form is not built).  Without
-    ``pqmf`` not one operation changes."""
+    ``pqmf`` not one operation changes.
+
+    ``prior_filter`` (spectral prior, SpecGrad: Koizumi et al., Interspeech 2022; not in the reference): the complex64
+    filter F [B, K, L // hop + 1] of ``prior_stft.spectral_filter`` on the batch's own mel, with ``prior_stft`` the
+    ``mel.TacotronSTFT`` whose window and hop frame it (L a multiple of the hop; one audio channel).  ``z`` is drawn
+    exactly as without it; with T_F = ``mel.tv_filter(., F)`` (``dws_tv_filter``) the forward process noises with
+    ``eps = T_F(z)`` -- N(0, Sigma), Sigma = T_F T_F^T -- and the loss is ``mean(T_{1/F}(eps_theta - eps)^2)``, the
+    paper's Sigma^-1 norm with its approximation of the inverse of T_F by the filter 1 / F.  Its gradient reaches
+    eps_theta through the kernel's adjoint.  ``loss_fn`` is ignored then.  It works with ``labels`` and ``stft_weight``
+    (eps = T_F(z) there too); with ``prior_std``, with ``pqmf`` or on more than one channel it is a ValueError.  Without
+    ``prior_filter`` not one operation or RNG draw changes."""
     T, Alpha_bar = diffusion_hyperparams["T"], diffusion_hyperparams["Alpha_bar"]
     full = None
+    if (prior_filter is None) != (prior_stft is None):
+        raise ValueError("training_loss: prior_filter (the filter) and prior_stft (the TacotronSTFT that frames it) come "
+                         "together")
+    if prior_filter is not None:
+        if prior_std is not None:
+            raise ValueError("training_loss: prior_filter (spectral prior) and prior_std (energy prior) exclude each other")
+        if pqmf is not None:
+            raise ValueError("training_loss: pqmf does not combine with prior_filter (the spectral prior is a full-band "
+                             "quantity; its sub-band form is not built)")
+        if not isinstance(audio, torch.Tensor) or audio.dim() != 3 or audio.shape[1] != 1:
+            raise ValueError(f"training_loss: prior_filter needs one audio channel, [B, 1, L] (got "
+                             f"{tuple(getattr(audio, 'shape', ()))!r})")
     if pqmf is not None:
         if prior_std is not None:
             raise ValueError("training_loss: pqmf does not combine with prior_std (the adaptive prior is a full-band "
@@ -165,6 +187,11 @@ def training_loss(net, loss_fn, audio, diffusion_hyperparams, mel_spec=None, gen
     z = _stage(torch.normal(0, 1, size=audio.shape, generator=generator), audio.device, "z")
     if prior_std is not None:
         z = prior_std * z           # eps: the target, and what the forward process adds
+    if prior_filter is not None:
+        from .mel import tv_filter
+        tv = dict(window=prior_stft._tables(audio.device)[0], hop_length=prior_stft.hop_length)
+        prior_filter = prior_filter.to(audio.device)
+        z = tv_filter(z.view(B, L), prior_filter, **tv).view(B, 1, L)      # eps = T_F(z)
     x_t = q_sample(audio, diffusion_steps, Alpha_bar, z)
     if labels is not None:
         labels = torch.as_tensor(labels).detach().cpu().reshape(-1)     # (host side: the engine takes them from the host)
@@ -176,6 +203,8 @@ def training_loss(net, loss_fn, audio, diffusion_hyperparams, mel_spec=None, gen
         epsilon_theta = net((x_t, diffusion_steps.view(B, 1)), mel_spec=mel_spec)
     if prior_std is not None:
         loss = (((epsilon_theta - z) / prior_std) ** 2).mean()
+    elif prior_filter is not None:
+        loss = (tv_filter((epsilon_theta - z).reshape(B, L).float(), 1.0 / prior_filter, **tv) ** 2).mean()
     else:
         loss = loss_fn(epsilon_theta, z)
     if stft is None:

@@ -869,6 +869,47 @@ int dws_griffin_lim(const float* magnitude, const float* phase0, int64_t B, int6
 /* Bytes of the workspace of dws_griffin_lim (and, with momentum = 0, of dws_istft); 0 for a shape they refuse. */
 int64_t dws_griffin_lim_workspace(int64_t B, int64_t f_max, int32_t n_fft, int32_t hop, int32_t momentum);
 
+/* Time-varying spectral filter (the noise shaping of SpecGrad: Koizumi et al., Interspeech 2022; not in the reference):
+ * out = G+ (F . G x), and with adjoint = 1 the exact transpose of that map.  G is the short-time DFT of
+ * dws_mel_spectrogram's framing and G+ the normalised overlap-add of dws_istft; framing, lengths / lengths_host, sign
+ * convention, window and workspace are dws_istft's.  x and out are DEVICE float32 [B][T], T = (f_max - 1) hop; filt_re and
+ * filt_im DEVICE float32 [B][K][f_max], K = n_fft/2 + 1 (the layout of dws_istft's magnitude), one complex gain
+ * F = filt_re + i filt_im per clip, bin and frame in the public convention X_k = sum_i frame[i] e^{-2 pi i k / N}; a null
+ * filt_im is a real filter.  With N = n_fft, w = window, len_b and frames f = 0 .. len_b / hop as in dws_istft:
+ *
+ * adjoint = 0, two launches:
+ *     frame_f[i] = w[i] x[b][reflect(f hop + i - N/2)]                          (reflected about the clip's OWN ends)
+ *     X_k = sum_i frame_f[i] e^{-2 pi i k / N}                                  (k = 0 .. N/2, direct, ascending i)
+ *     Re Y_k = fl(fl(Fr Re X_k) - fl(Fi Im X_k)),  Im Y_k = fl(fl(Fr Im X_k) + fl(Fi Re X_k))
+ *     row_f, wss, s and out[b][j] = s(p) / wss(p) (the `tiny` rule) exactly as dws_istft on the spectrum Y
+ * The complex product is four fp32 products, each rounded on its own, then one subtraction and one addition; nothing of
+ * it is contracted into an fma, so the bits do not depend on the compiler.  (The kernel works on the conjugate spectrum,
+ * Im_core = -Im; negation is exact, so the statement above holds bit for bit.)
+ *
+ * adjoint = 1 (x is the cotangent g), two launches:
+ *     q(p) = g[b][j] / wss(p) where wss(p) > FLT_MIN, else g[b][j],  p = j + N/2, j < len_b;  q = 0 elsewhere
+ *     row_f[i] = w[i] q(f hop + i)
+ *     dRe_k = h_k sum_i row_f[i] cos(2 pi i k / N),  dIm_k = -h_k sum_i row_f[i] sin(2 pi i k / N)    (h_k as dws_istft;
+ *                                                                                 dIm is exactly 0 at k = 0 and k = N/2)
+ *     dX_k = conj(F_k) dY_k       (Re = fl(fl(Fr dRe) + fl(Fi dIm)), Im = fl(fl(Fr dIm) - fl(Fi dRe)), uncontracted)
+ *     u_f[i] = w[i] sum_k (Re dX_k cos - Im dX_k sin)(2 pi i k / N)             (k = 0 .. N/2 ascending, no h weights)
+ *     out[b][j] = the rows u_f folded back through the reflect map (the overlap-add of dws_spectral_loss_backward:
+ *                 direct position, left reflection, right reflection, each in ascending frame order)
+ * <dws_tv_filter(x, 0), g> = <x, dws_tv_filter(g, 1)> up to fp32 rounding, for every F.
+ *
+ * Positions j >= len_b of out are written as exactly 0 in both directions; x behind len_b and filter frames behind a clip's
+ * own (f > len_b / hop) are never read and may hold NaN.  No atomics and a fixed summation order: the result is bitwise
+ * reproducible, and row b depends on clip b alone, not on B or b.  No spectrogram goes to memory.  One workgroup of 256
+ * threads per frame; LDS per workgroup: 12 n_fft + 8 K bytes.  The adjoint's frame kernel recomputes wss(p) for each of its
+ * n_fft samples from the window in global memory, ceil(n_fft / hop) reads per sample at most: 4 at hop = n_fft/4, but n_fft
+ * of them at hop = 1 (correct, and as slow as that reads).  workspace: DEVICE,
+ * dws_griffin_lim_workspace(B, f_max, n_fft, hop, 0) bytes, owned by the caller (overwritten; nothing is allocated per call).
+ * Error codes: dws_istft's (with x in the place of magnitude), and DWS_ERR_INVALID for a null filt_re or an adjoint
+ * outside {0, 1}. */
+int dws_tv_filter(const float* x, int64_t B, int64_t f_max, const int32_t* lengths, const int32_t* lengths_host,
+                  const float* filt_re, const float* filt_im, const float* window, int32_t n_fft, int32_t hop,
+                  int32_t adjoint, float* out, float* workspace, void* stream);
+
 /* Pseudo-QMF filter bank of multi-band runs (Multi-band MelGAN, Yang et al. 2020; not in the reference).  Both entries
  * take the filter table filt [K][taps + 1] (DEVICE, float32; designed by the caller) and a gain, so that each also serves
  * as the other's adjoint.  K is 2 or 4, taps is even and in 2 .. 254, h = taps / 2.
